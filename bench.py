@@ -27,6 +27,8 @@ measured; their full records -- BASELINE configs[2], [4], zero fill, the 1 GiB c
   config4       (N > 1, or --config4) BASELINE configs[3], cut to 1 GiB: Silesia-like mix, BrotliEncoderCompressMulti with
                 8 shards dealt to the N GPUs -- strong scaling, same stream for every N, verified against the frozen hash.
                 (At the full 4 GiB -- 512 MiB per shard -- the REFERENCE fails on every seed that was tried)
+--dump-outputs DIR writes the compressed stream of the last timed step (rank 0) as .npy files (dump_outputs); the input is seeded, so
+two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes
@@ -37,9 +39,6 @@ import sys
 import time
 
 
-# 16 hardware queues -- eight shard workers side by side -- instead of the runtime's four: the HIP runtime reads the variable when
-# it starts (torch starts it here), and the library never touches the environment itself
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 # every CPU figure of this file comes from the optimised build of the oracle (oracle/liborc_fast.so: -O3 -march=native), run on THIS
 # host, pinned to one core (tests/orc.py reads the variable when it loads the library)
 os.environ.setdefault("ORC_FAST", "1")
@@ -205,6 +204,28 @@ def stream_roofline(kernel, input_bytes, output_bytes, sec, note):
     achieved = (input_bytes + output_bytes) / sec / 1e9 if sec > 0 else 0.0
     return {"bound": "hbm", "kernel": kernel, "achieved": round(achieved, 4), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 8),
             "traffic": None, "accounting": "compulsory bytes (input + compressed stream) / wall time of the call", "what_bounds_it": note}
+
+
+DUMP_MAX_SAMPLES = 5_000_000  # 4 B value + 8 B position each: 60 MB, inside the 64 MB an output dump may take
+DUMP_SEED = 0x5EED000000000003
+
+
+def dump_outputs(dirname, comp):
+    """--dump-outputs DIR: what the headline's caller received from the last timed step, so that two builds can be compared output
+    for output.  compressed.npy holds the bytes of the compressed stream as float32 at the positions in compressed_index.npy
+    (float64): every position, or a fixed seeded sample of DUMP_MAX_SAMPLES positions when the stream is longer;
+    compressed_size.npy holds the stream's length in bytes."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    stream = np.frombuffer(comp, dtype=np.uint8)
+    n = len(stream)
+    if n <= DUMP_MAX_SAMPLES:
+        index = np.arange(n)
+    else:
+        index = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_SAMPLES, replace=False))
+    np.save(os.path.join(dirname, "compressed.npy"), stream[index].astype(np.float32))
+    np.save(os.path.join(dirname, "compressed_index.npy"), index.astype(np.float64))
+    np.save(os.path.join(dirname, "compressed_size.npy"), np.array([n], dtype=np.float64))
 
 
 def timed_steps(fn, steps, warmup, torch):
@@ -700,7 +721,10 @@ def main():
     ap.add_argument("--config4", action="store_true", help="run the 4 GiB config 4 at N = 1 as well (it always runs for N > 1)")
     ap.add_argument("--extras-budget", type=float, default=60.0, help="wall-clock seconds the side workloads may take (they run in a child process)")
     ap.add_argument("--extras-only", action="store_true", help="run the side workloads only and write bench_extras.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the compressed stream of the last timed step to DIR/*.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.extras_only:
         return extras_only(args)
 
@@ -823,6 +847,8 @@ def main():
         return
 
     comp = bytes(comp) if shard_job else bytes(out_dev[:last_size[0]].cpu().numpy())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, comp)
     ms_per_step = elapsed / args.steps * 1e3
     value = total * args.steps / elapsed / 1e6
     # ---- roofline of the dominant kernel, from what its launches did (all chains: dry runs, round 0, re-parses)

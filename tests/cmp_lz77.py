@@ -26,11 +26,12 @@ def check(name, data, q=5, w=22, size_hint=None, catable=False, prefix=b"", seg=
     print('%-28s q%d w%d n=%d seg=%d %s rounds=%d parsed=%d emu=%.2fs'%(name,q,w,len(data),seg,'OK' if ok else 'FAIL',st['rounds'],st['segments_parsed'],te))
     return ok
 
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
+
 if __name__=='__main__':
     allok=True
-    for f in sorted(glob.glob('/root/reference/testdata/*')):
+    for f in sorted(glob.glob(os.path.join(GOLDEN, 'small', '*'))) + [os.path.join(GOLDEN, n) for n in ('alice29.txt', 'random_then_unicode')]:
         b=os.path.basename(f)
-        if 'compressed' in b and b not in ('compressed_file','compressed_repeated'): continue
         d=open(f,'rb').read()
         if len(d)==0: continue
         for q in (5,6,7,8):

@@ -20,10 +20,7 @@ _ALICE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ali
 
 
 def alice():
-    for p in (_ALICE, "/root/reference/testdata/alice29.txt"):
-        if os.path.exists(p):
-            return open(p, "rb").read()
-    raise FileNotFoundError("alice29.txt fixture")
+    return open(_ALICE, "rb").read()
 
 
 _clib = None

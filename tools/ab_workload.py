@@ -5,7 +5,6 @@ import ctypes, hashlib, json, os, sys, time
 for kv in sys.argv[2:]:
     k, v = kv.split("=", 1)
     os.environ[k] = v
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "rust-brotli_amd"))

@@ -2,7 +2,6 @@
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "rust-brotli_amd"))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import synth
 import brotli_mi355x as bm
 lib = bm.default_library()
