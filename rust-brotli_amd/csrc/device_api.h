@@ -10,6 +10,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "lz77_types.h"
 
 // Every thread of the host program works on its own HIP stream (hipStreamPerThread): independent encoder calls from
@@ -28,7 +30,15 @@ ihipStream_t* dev_stream_flushed();  // the calling thread's stream, behind the 
 // ---- memory ----
 void* dev_alloc(size_t bytes);  // zero-initialised device allocation; throws std::runtime_error
 void* dev_alloc_uninit(size_t bytes);  // contents undefined: only for arrays that are written before they are read
+// nullptr: nothing happens.  Blocks are freed in destructors, so the device library's dev_free does not throw (a failing flush of
+// noted zero fills drops the ranges).  The CPU emulation of this seam (BROTLI_HOST_EMU) hands the block to free(), which cannot
+// throw either; its definition carries no exception specification, and a declaration must agree with the definition.
+#ifdef BROTLI_HOST_EMU
 void dev_free(void* p);
+#else
+void dev_free(void* p) noexcept;
+static_assert(noexcept(dev_free(nullptr)), "blocks are freed in destructors");
+#endif
 void dev_memset(void* p, int value, size_t bytes);
 void dev_h2d(void* dst, const void* src, size_t bytes);
 void dev_d2h(void* dst, const void* src, size_t bytes);        // copy + wait
@@ -60,6 +70,62 @@ int dev_current_device();        // the calling thread's device (helper threads 
 void dev_use_device(int device);
 int dev_device_count();          // visible HIP devices
 const char* dev_name();  // "hip:gfx950 ..." or "host-emulation"
+
+// Owner of a set of device blocks: whatever it handed out is freed when it goes out of scope, on the normal path and on a throw
+// alike.  The structs that go to kernels by value (Lz77Buffers, ZopfliJob ...) keep raw pointers; their owner stands beside them.
+class DevBlocks {
+ public:
+  DevBlocks() = default;
+  DevBlocks(DevBlocks&& o) noexcept : blocks_(std::move(o.blocks_)) { o.blocks_.clear(); }
+  DevBlocks& operator=(DevBlocks&& o) noexcept {
+    if (this != &o) {
+      clear();
+      blocks_.swap(o.blocks_);
+    }
+    return *this;
+  }
+  ~DevBlocks() { clear(); }
+  template <typename T = void>
+  T* zeroed(size_t bytes) { return (T*)get(bytes, true); }
+  template <typename T = void>
+  T* uninit(size_t bytes) { return (T*)get(bytes, false); }  // only for arrays that are written before they are read
+  // frees one block of this owner (no-op for nullptr) and nulls the caller's pointer
+  template <typename T>
+  void drop(T*& p) {
+    if (p) dev_free(forget(p));
+    p = nullptr;
+  }
+  // hands one block over to another owner (a carry that outlives the stage); returns it and nulls the caller's pointer
+  template <typename T>
+  T* give(DevBlocks& to, T*& p) {
+    T* q = p;
+    to.blocks_.reserve(to.blocks_.size() + 1);
+    to.blocks_.push_back(forget(p));
+    p = nullptr;
+    return q;
+  }
+  void clear() noexcept {
+    for (void* p : blocks_) dev_free(p);
+    blocks_.clear();
+  }
+
+ private:
+  void* get(size_t bytes, bool zero) {
+    blocks_.reserve(blocks_.size() + 1);  // (so that nothing can throw between the allocation and its entry)
+    blocks_.push_back(zero ? dev_alloc(bytes) : dev_alloc_uninit(bytes));
+    return blocks_.back();
+  }
+  void* forget(const void* p) {
+    for (size_t i = blocks_.size(); i-- > 0;)
+      if (blocks_[i] == p) {
+        void* q = blocks_[i];
+        blocks_.erase(blocks_.begin() + (ptrdiff_t)i);
+        return q;
+      }
+    return nullptr;  // not one of this owner's: left alone
+  }
+  std::vector<void*> blocks_;
+};
 
 // Static read-only tables resident on the device (dictionary, dictionary hash, log tables ...).
 struct DeviceTables {

@@ -333,9 +333,15 @@ static void* AllocBlock(size_t bytes) {
   }
   return p;
 }
-void dev_free(void* p) {
+void dev_free(void* p) noexcept {
   if (!p) return;
-  flush_zero();  // (a noted fill of this block must not outlive it: the pool may hand the block back to the driver)
+  // a noted fill of this block must not outlive it: the pool may hand the block back to the driver.  Blocks are freed in destructors,
+  // so a flush that fails drops the noted ranges instead of throwing: this block is going away, and a caller that still wants one of
+  // the others filled is about to see the same error from its own next launch
+  try {
+    flush_zero();
+  } catch (...) {
+  }
   Pool& P = pool();
   std::lock_guard<std::mutex> lock(P.mu);
   auto it = P.capacity.find(p);

@@ -22,30 +22,22 @@ namespace brotli_mi355x {
 namespace {
 
 struct DevMem {
-  std::vector<void*> ptrs;
+  DevBlocks blocks;
   // small buffers are carved out of zero-filled arenas (one fill per arena instead of one tiny fill kernel each)
   static constexpr size_t kArenaBytes = (size_t)4 << 20, kSmall = (size_t)256 << 10;
   uint8_t* arena = nullptr;
   size_t arena_used = kArenaBytes;
-  ~DevMem() {
-    for (void* p : ptrs) dev_free(p);
-  }
   template <typename T>
   T* alloc(size_t count) {
     const size_t bytes = (count * sizeof(T) + 64 + 255) & ~(size_t)255;
-    if (bytes <= kSmall) {
-      if (arena_used + bytes > kArenaBytes) {
-        arena = (uint8_t*)dev_alloc(kArenaBytes);
-        ptrs.push_back(arena);
-        arena_used = 0;
-      }
-      T* p = (T*)(arena + arena_used);
-      arena_used += bytes;
-      return p;
+    if (bytes > kSmall) return blocks.zeroed<T>(bytes);
+    if (arena_used + bytes > kArenaBytes) {
+      arena = blocks.zeroed<uint8_t>(kArenaBytes);
+      arena_used = 0;
     }
-    void* p = dev_alloc(bytes);
-    ptrs.push_back(p);
-    return (T*)p;
+    T* p = (T*)(arena + arena_used);
+    arena_used += bytes;
+    return p;
   }
 };
 

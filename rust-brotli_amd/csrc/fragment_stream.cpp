@@ -69,14 +69,6 @@ void Start(const EncoderParams& p, FragmentStream* fs) {
   InitCommandPrefixCodes(&fs->state);
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  explicit DevBuf(size_t bytes, bool zero = false) : p(zero ? dev_alloc(bytes) : dev_alloc_uninit(bytes)) {}
-  ~DevBuf() { dev_free(p); }
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-};
-
 // HashTableSize / GetHashTable, encode.rs:1643-1700
 uint32_t TableBits(int quality, size_t input_size) {
   const size_t max_table_size = quality == 0 ? ((size_t)1 << 15) : ((size_t)1 << 17);
@@ -126,16 +118,19 @@ void RunFragments(const EncoderParams& p, FragmentStream* fs, const uint8_t* inp
   B.table_stride = (size_t)1 << TableBits(p.quality, largest);
   B.cmd_stride = std::min<size_t>(largest, (size_t)1 << 17) + 16;
   B.lit_stride = std::min<size_t>(largest, (size_t)1 << 17) + 64;
-  DevBuf in(in_cap + 64, true), slots(slots_cap + 64), table(max_jobs * B.table_stride * 4 + 64),
-      commands(q0 ? 64 : max_jobs * B.cmd_stride * 4 + 64), literals(q0 ? 64 : max_jobs * B.lit_stride + 64),
-      states_a((max_jobs + 1) * sizeof(FragmentState) + 64), states_b(max_jobs * sizeof(FragmentState) + 64),
-      jobs_dev(max_jobs * sizeof(FragmentJob) + 64), results_dev(max_jobs * sizeof(FragmentResult) + 64),
-      pieces_dev(2 * max_jobs * sizeof(FragmentPiece) + 64);
-  B.table = (uint32_t*)table.p;
-  B.commands = q0 ? nullptr : (uint32_t*)commands.p;
-  B.literals = q0 ? nullptr : (uint8_t*)literals.p;
-  FragmentState* const sa = (FragmentState*)states_a.p;  // [0] the code the batch comes in with, [j + 1] what fragment j leaves behind (pass A)
-  FragmentState* const sb = (FragmentState*)states_b.p;  // what fragment j leaves behind (pass B)
+  DevBlocks mem;
+  uint8_t* const in = mem.zeroed<uint8_t>(in_cap + 64);
+  uint8_t* const slots = mem.uninit<uint8_t>(slots_cap + 64);
+  B.table = mem.uninit<uint32_t>(max_jobs * B.table_stride * 4 + 64);
+  uint32_t* const commands = mem.uninit<uint32_t>(q0 ? 64 : max_jobs * B.cmd_stride * 4 + 64);
+  uint8_t* const literals = mem.uninit<uint8_t>(q0 ? 64 : max_jobs * B.lit_stride + 64);
+  B.commands = q0 ? nullptr : commands;
+  B.literals = q0 ? nullptr : literals;
+  FragmentState* const sa = mem.uninit<FragmentState>((max_jobs + 1) * sizeof(FragmentState) + 64);  // [0] the code the batch comes in with, [j + 1] what fragment j leaves behind (pass A)
+  FragmentState* const sb = mem.uninit<FragmentState>(max_jobs * sizeof(FragmentState) + 64);  // what fragment j leaves behind (pass B)
+  FragmentJob* const jobs_dev = mem.uninit<FragmentJob>(max_jobs * sizeof(FragmentJob) + 64);
+  FragmentResult* const results_dev = mem.uninit<FragmentResult>(max_jobs * sizeof(FragmentResult) + 64);
+  FragmentPiece* const pieces_dev = mem.uninit<FragmentPiece>(2 * max_jobs * sizeof(FragmentPiece) + 64);
   size_t done = 0;
   bool more = true;
   std::vector<FragmentJob> jobs;
@@ -144,7 +139,7 @@ void RunFragments(const EncoderParams& p, FragmentStream* fs, const uint8_t* inp
   std::vector<uint8_t> bytes;
   while (more) {
     const size_t here = std::min(size - done, batch_bytes);
-    if (here) dev_h2d_bulk(in.p, input + done, here);
+    if (here) dev_h2d_bulk(in, input + done, here);
     // ---- the fragments of this batch
     jobs.clear();
     size_t at = 0, slot_at = 0;
@@ -177,15 +172,15 @@ void RunFragments(const EncoderParams& p, FragmentStream* fs, const uint8_t* inp
       // what each leaves behind, pass B runs them all with the right incoming codes
       dev_h2d(sa, &fs->state, sizeof(FragmentState));
       if (n > 1) {
-        dev_h2d(jobs_dev.p, jobs.data(), (size_t)(n - 1) * sizeof(FragmentJob));
-        frag_compress_batch(0, (const uint8_t*)in.p, (const FragmentJob*)jobs_dev.p, n - 1, B, sa, sa + 1, (FragmentResult*)results_dev.p, (uint8_t*)slots.p);
+        dev_h2d(jobs_dev, jobs.data(), (size_t)(n - 1) * sizeof(FragmentJob));
+        frag_compress_batch(0, in, jobs_dev, n - 1, B, sa, sa + 1, results_dev, slots);
       }
       for (uint32_t j = 0; j < n; ++j) jobs[j].state_in = j;
     }
-    dev_h2d(jobs_dev.p, jobs.data(), (size_t)n * sizeof(FragmentJob));
-    frag_compress_batch(p.quality, (const uint8_t*)in.p, (const FragmentJob*)jobs_dev.p, n, B, sa, q0 ? sb : nullptr, (FragmentResult*)results_dev.p, (uint8_t*)slots.p);
+    dev_h2d(jobs_dev, jobs.data(), (size_t)n * sizeof(FragmentJob));
+    frag_compress_batch(p.quality, in, jobs_dev, n, B, sa, q0 ? sb : nullptr, results_dev, slots);
     results.resize(n);
-    dev_d2h(results.data(), results_dev.p, (size_t)n * sizeof(FragmentResult));
+    dev_d2h(results.data(), results_dev, (size_t)n * sizeof(FragmentResult));
     if (q0 && selftest && n > 1) {
       std::vector<FragmentState> a(n + 1), b(n);
       dev_d2h(a.data(), sa, (size_t)(n + 1) * sizeof(FragmentState));
@@ -219,14 +214,14 @@ void RunFragments(const EncoderParams& p, FragmentStream* fs, const uint8_t* inp
         FragmentJob one = jobs[j];
         one.start_bits = phase;
         one.state_in = 0;
-        dev_h2d((FragmentJob*)jobs_dev.p + j, &one, sizeof(FragmentJob));
+        dev_h2d(jobs_dev + j, &one, sizeof(FragmentJob));
         FragmentBuffers Bj = B;
         Bj.table += (size_t)j * B.table_stride;
         if (Bj.commands) Bj.commands += (size_t)j * B.cmd_stride;
         if (Bj.literals) Bj.literals += (size_t)j * B.lit_stride;
-        frag_compress_batch(p.quality, (const uint8_t*)in.p, (const FragmentJob*)jobs_dev.p + j, 1, Bj, sa + j, q0 ? sb + j : nullptr, (FragmentResult*)results_dev.p + j,
-                            (uint8_t*)slots.p);
-        dev_d2h(&r, (FragmentResult*)results_dev.p + j, sizeof(FragmentResult));
+        frag_compress_batch(p.quality, in, jobs_dev + j, 1, Bj, sa + j, q0 ? sb + j : nullptr, results_dev + j,
+                            slots);
+        dev_d2h(&r, results_dev + j, sizeof(FragmentResult));
         if (r.bad) throw std::runtime_error("brotli_mi355x: fragment compressor failed");
         pieces.push_back({slot_bit + phase, cur, r.end_bits - phase});
         cur += r.end_bits - phase;
@@ -247,15 +242,16 @@ void RunFragments(const EncoderParams& p, FragmentStream* fs, const uint8_t* inp
     // ---- the join
     const uint64_t ix = cur;
     const size_t joined_bytes = (size_t)(ix >> 3) + 2;
-    DevBuf joined(((joined_bytes + 7) & ~(size_t)7) + 64, true);
+    DevBlocks join_mem;
+    uint8_t* const joined = join_mem.zeroed<uint8_t>(((joined_bytes + 7) & ~(size_t)7) + 64);
     uint8_t head[2] = {(uint8_t)fs->last_bytes, (uint8_t)(fs->last_bytes >> 8)};
-    dev_h2d(joined.p, head, 2);
+    dev_h2d(joined, head, 2);
     if (!pieces.empty()) {
-      dev_h2d(pieces_dev.p, pieces.data(), pieces.size() * sizeof(FragmentPiece));
-      frag_join((const uint8_t*)slots.p, (const FragmentPiece*)pieces_dev.p, (uint32_t)pieces.size(), (uint8_t*)joined.p);
+      dev_h2d(pieces_dev, pieces.data(), pieces.size() * sizeof(FragmentPiece));
+      frag_join(slots, pieces_dev, (uint32_t)pieces.size(), joined);
     }
     bytes.resize(joined_bytes);
-    dev_d2h_bulk(bytes.data(), joined.p, bytes.size());
+    dev_d2h_bulk(bytes.data(), joined, bytes.size());
     out->insert(out->end(), bytes.begin(), bytes.begin() + (ptrdiff_t)(ix >> 3));
     fs->last_bytes = (uint16_t)(bytes[(size_t)(ix >> 3)] | (bytes[(size_t)(ix >> 3) + 1] << 8));
     fs->last_bytes_bits = (uint8_t)(ix & 7);

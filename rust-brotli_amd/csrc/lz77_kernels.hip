@@ -27,7 +27,9 @@
 namespace brotli_mi355x {
 
 void hip_check(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string("HIP error in ") + what + ": " + hipGetErrorString(e));
+  if (e == hipSuccess) return;
+  (void)hipGetLastError();  // (or the launch check of a later, healthy call reports this error once more)
+  throw std::runtime_error(std::string("HIP error in ") + what + ": " + hipGetErrorString(e));
 }
 
 // ------------------------------------------------------------------------------------------ keys

@@ -19,115 +19,36 @@
 
 namespace brotli_mi355x {
 
-Lz77Stage::~Lz77Stage() { Release(); }
-
 void Lz77Stage::Release() {
-  if (owns_buffers_) {
-    dev_free(B_.keys);
-    dev_free(B_.by_key);
-    dev_free(B_.sorted_keys);
-    dev_free(B_.fbits);
-    dev_free(B_.key_first);
-    dev_free(B_.key_last);
-    dev_free(B_.changed_keys);
-    dev_free(B_.changed_count);
-    dev_free(B_.info[0]);
-    dev_free(B_.info[1]);
-    dev_free(B_.sorted[0]);
-    dev_free(B_.sorted[1]);
-    dev_free(B_.sorted_tag[0]);
-    dev_free(B_.sorted_tag[1]);
-    B_.sorted_tag[0] = B_.sorted_tag[1] = nullptr;
-    dev_free(B_.search_log);
-    dev_free(B_.recheck_list);
-    dev_free(B_.recheck_count);
-    B_.search_log = B_.recheck_list = B_.recheck_count = nullptr;
-    dev_free(B_.key_base);
-    dev_free(B_.stag);
-    dev_free(B_.rows);
-    dev_free(B_.dict_items);
-    dev_free(B_.checkpoints);
-    dev_free(B_.rows_changed_lo);
-    dev_free(B_.rows_changed_hi);
-    dev_free(B_.changed_slot);
-    dev_free(B_.row_ctl);
-    dev_free(B_.big_tile);
-    dev_free(B_.run_end);
-    dev_free(L_.num);
-    dev_free(L_.buckets);
-    dev_free(L_.slot_of);
-    dev_free(L_.rank[0]);
-    dev_free(L_.rank[1]);
-    dev_free(L_.entry[0]);
-    dev_free(L_.entry[1]);
-    dev_free(L_.changed_key);
-    dev_free(L_.state);
-    L_ = LiveBuffers{};
-    dev_free(count_base_dev_);
-    count_base_dev_ = nullptr;
-    dev_free(B_.reset_counts);
-    dev_free(B_.smask);
-    dev_free(B_.gprev);
-    dev_free(B_.pot);
-    dev_free(B_.pot_state);
-    dev_free(B_.pot_list);
-    dev_free(B_.flip_cells);
-    dev_free(Z_.buckets);
-    dev_free(Z_.forest);
-    dev_free(Z_.nodes);
-    dev_free(Z_.literal_costs);
-    dev_free(Z_.cost_dist);
-    dev_free(Z_.cost_cmd);
-    dev_free(Z_.matches);
-    dev_free(Z_.num_matches);
-    dev_free(Z_.tmp_cmds);
-    dev_free(Z_.histo);
-    dev_free(Z_.forest_new);
-    dev_free(Z_.forest_bak);
-    dev_free(Z_.buckets_bak);
-    dev_free(Z_.rerooted);
-    dev_free(Z_.ctl);
-    Z_ = ZopfliJob{};
-    dev_free(Q_.table);
-    dev_free(S_.ev_slot);
-    dev_free(S_.ev_id);
-    dev_free(S_.ev_of);
-    dev_free(S_.slot_first);
-    dev_free(S_.qrank);
-    dev_free(S_.act);
-    dev_free(S_.val);
-    dev_free(S_.cand);
-    dev_free(S_.flags);
-    dev_free(S_.actraw);
-    dev_free(S_.flags_prev);
-    dev_free(S_.chg_list);
-    dev_free(S_.chg_range);
-    dev_free(S_.chg_count);
-    dev_free(S_.sort_tmp);
-    dev_free(S_.sort_keys_tmp);
-    dev_free(S_.sort_ids_tmp);
-    dev_free(S_.scan_tmp);
-    S_ = QuickSpec{};
-    Q_ = QuickJob{};
-    dev_free(qsnap_table_);
-    qsnap_table_ = nullptr;
-    dev_free(zsnap_buckets_);
-    dev_free(zsnap_forest_);
-    zsnap_buckets_ = zsnap_forest_ = nullptr;
-    dev_free(B_.flags[0]);
-    dev_free(B_.flags[1]);
-    dev_free(B_.cmds);
-    dev_free(B_.segments);
-    dev_free(B_.entries);
-    dev_free(B_.exits);
-    dev_free(B_.sort_tmp);
-    dev_free(gathered_cmds_);
-    dev_free(histo_dev_);
-    dev_free(gather_offsets_dev_);
-    dev_free(gather_counts_dev_);
-  }
-  owns_buffers_ = false;
+  mem_.clear();
+  // (a stage that is set up again must not see stale pointers)
+  L_ = LiveBuffers{};
+  Z_ = ZopfliJob{};
+  S_ = QuickSpec{};
+  Q_ = QuickJob{};
+  count_base_dev_ = qsnap_table_ = zsnap_buckets_ = zsnap_forest_ = nullptr;
+  histo_dev_ = gather_offsets_dev_ = gather_counts_dev_ = nullptr;
   gathered_cmds_ = nullptr;
+  gathered_capacity_ = 0;
+}
+
+// What every path of Setup() ends with: the command slabs, the per-segment arrays and the arrays of Gather()
+void Lz77Stage::SetupCommon(bool with_sort_tmp) {
+  cmds_bytes_ = (size_t)total_cmd_slots_ * sizeof(Command) + 64;
+  B_.cmds = mem_.uninit<Command>(cmds_bytes_);
+  B_.segments = mem_.zeroed<Segment>(segments_.size() * sizeof(Segment) + 64);
+  B_.entries = mem_.zeroed<SegEntry>(segments_.size() * sizeof(SegEntry) + 64);
+  B_.exits = mem_.zeroed<SegExit>(segments_.size() * sizeof(SegExit) + 64);
+  if (with_sort_tmp) {
+    B_.sort_tmp_bytes = lz77_sort_tmp_bytes(P_.total_bytes);
+    B_.sort_tmp = mem_.uninit(B_.sort_tmp_bytes);  // (every user writes what it reads: histograms, tile sums, ping-pong arrays)
+  }
+  histo_dev_ = mem_.zeroed<uint32_t>(256 * 4);
+  gather_offsets_dev_ = mem_.zeroed<uint32_t>(segments_.size() * 4 + 64);
+  gather_counts_dev_ = mem_.zeroed<uint32_t>(segments_.size() * 4 + 64);
+  segments_upload_.resize_discard(segments_.size());
+  memcpy(segments_upload_.data(), segments_.data(), segments_.size() * sizeof(Segment));
+  dev_h2d(B_.segments, segments_upload_.data(), segments_.size() * sizeof(Segment));
 }
 
 void Lz77Stage::Setup(const EncoderParams& params, uint8_t* text_dev, uint32_t prefix_bytes, uint32_t input_bytes,
@@ -201,46 +122,35 @@ void Lz77Stage::Setup(const EncoderParams& params, uint8_t* text_dev, uint32_t p
     Q_.use_dictionary = (params.use_dictionary && (Q_.kind == 2 || Q_.kind == 4)) ? 1 : 0;
     // serial path: the throttle books travel with the table, not with the resolver; speculative path: the resolver keeps them
     P_.use_dictionary = use_qspec_ ? Q_.use_dictionary : 0;
-    Q_.table = (uint32_t*)dev_alloc_uninit((size_t)quick_table_words(Q_) * 4 + 64);
+    Q_.table = mem_.uninit<uint32_t>((size_t)quick_table_words(Q_) * 4 + 64);
     if (use_qspec_) {
       S_ = QuickSpec{};
       S_.n = P_.total_bytes;
       S_.events = Q_.sweep == 1 ? S_.n : 2u * S_.n;
       S_.slots = quick_slots(Q_);
       const size_t E = S_.events, N = S_.n;
-      S_.ev_slot = (uint32_t*)dev_alloc_uninit(E * 4 + 64);
-      S_.ev_id = (uint32_t*)dev_alloc_uninit(E * 4 + 64);
-      S_.ev_of = (uint32_t*)dev_alloc_uninit(E * 4 + 64);
-      S_.slot_first = (uint32_t*)dev_alloc_uninit(((size_t)S_.slots + 2) * 4 + 64);
-      S_.qrank = (uint32_t*)dev_alloc_uninit(N * Q_.sweep * 4 + 64);
-      S_.actraw = (uint32_t*)dev_alloc_uninit(E * 4 + 64);
-      S_.act = (uint32_t*)dev_alloc_uninit(E * 4 + 64);
-      S_.val = (uint32_t*)dev_alloc_uninit(E * 4 + 64);
-      S_.cand = (uint32_t*)dev_alloc_uninit(N * Q_.sweep * 4 + 64);
-      S_.flags = (uint8_t*)dev_alloc_uninit(N + 64);
-      S_.flags_prev = (uint8_t*)dev_alloc_uninit(N + 64);
+      S_.ev_slot = mem_.uninit<uint32_t>(E * 4 + 64);
+      S_.ev_id = mem_.uninit<uint32_t>(E * 4 + 64);
+      S_.ev_of = mem_.uninit<uint32_t>(E * 4 + 64);
+      S_.slot_first = mem_.uninit<uint32_t>(((size_t)S_.slots + 2) * 4 + 64);
+      S_.qrank = mem_.uninit<uint32_t>(N * Q_.sweep * 4 + 64);
+      S_.actraw = mem_.uninit<uint32_t>(E * 4 + 64);
+      S_.act = mem_.uninit<uint32_t>(E * 4 + 64);
+      S_.val = mem_.uninit<uint32_t>(E * 4 + 64);
+      S_.cand = mem_.uninit<uint32_t>(N * Q_.sweep * 4 + 64);
+      S_.flags = mem_.uninit<uint8_t>(N + 64);
+      S_.flags_prev = mem_.uninit<uint8_t>(N + 64);
       S_.chg_cap = (uint32_t)std::max<size_t>(4096, E / (getenv("BROTLI_MI355X_QUICK_CAP_DIV") ? (size_t)atoi(getenv("BROTLI_MI355X_QUICK_CAP_DIV")) : 16));
-      S_.chg_list = (uint32_t*)dev_alloc_uninit((size_t)S_.chg_cap * 4 + 64);
-      S_.chg_range = (uint32_t*)dev_alloc_uninit((size_t)S_.chg_cap * 12 + 64);
-      S_.chg_count = (uint32_t*)dev_alloc(64);
+      S_.chg_list = mem_.uninit<uint32_t>((size_t)S_.chg_cap * 4 + 64);
+      S_.chg_range = mem_.uninit<uint32_t>((size_t)S_.chg_cap * 12 + 64);
+      S_.chg_count = mem_.zeroed<uint32_t>(64);
       S_.sort_tmp_bytes = lz77_qspec_sort_tmp_bytes(S_.events);
-      S_.sort_tmp = dev_alloc_uninit(S_.sort_tmp_bytes);
-      S_.sort_keys_tmp = (uint32_t*)dev_alloc_uninit(E * 4 + 64);
-      S_.sort_ids_tmp = (uint32_t*)dev_alloc_uninit(E * 4 + 64);
-      S_.scan_tmp = (uint32_t*)dev_alloc_uninit((E / 1024 + E / (1024 * 1024) + 8192) * 4);
+      S_.sort_tmp = mem_.uninit(S_.sort_tmp_bytes);
+      S_.sort_keys_tmp = mem_.uninit<uint32_t>(E * 4 + 64);
+      S_.sort_ids_tmp = mem_.uninit<uint32_t>(E * 4 + 64);
+      S_.scan_tmp = mem_.uninit<uint32_t>((E / 1024 + E / (1024 * 1024) + 8192) * 4);
     }
-    cmds_bytes_ = (size_t)total_cmd_slots_ * sizeof(Command) + 64;
-    B_.cmds = (Command*)dev_alloc_uninit(cmds_bytes_);
-    B_.segments = (Segment*)dev_alloc(segments_.size() * sizeof(Segment) + 64);
-    B_.entries = (SegEntry*)dev_alloc(segments_.size() * sizeof(SegEntry) + 64);
-    B_.exits = (SegExit*)dev_alloc(segments_.size() * sizeof(SegExit) + 64);
-    histo_dev_ = (uint32_t*)dev_alloc(256 * 4);
-    gather_offsets_dev_ = (uint32_t*)dev_alloc(segments_.size() * 4 + 64);
-    gather_counts_dev_ = (uint32_t*)dev_alloc(segments_.size() * 4 + 64);
-    owns_buffers_ = true;
-    segments_upload_.resize_discard(segments_.size());
-    memcpy(segments_upload_.data(), segments_.data(), segments_.size() * sizeof(Segment));
-    dev_h2d(B_.segments, segments_upload_.data(), segments_.size() * sizeof(Segment));
+    SetupCommon(false);
     exits_.assign((uint32_t)segments_.size(), SegExit{});
     return;
   }
@@ -260,57 +170,46 @@ void Lz77Stage::Setup(const EncoderParams& params, uint8_t* text_dev, uint32_t p
     P_.hasher_kind = 5;
     P_.bucket_bits = 16;
     P_.htl = 4;
-    B_.keys = (uint16_t*)dev_alloc_uninit(M * 2 + 64);
-    B_.by_key = (uint32_t*)dev_alloc_uninit(M * 4 + 64);
-    B_.sorted_keys = (uint16_t*)dev_alloc_uninit(M * 2 + 64);
-    B_.key_first = (uint32_t*)dev_alloc((65536 + 1) * 4);
-    B_.key_last = (uint32_t*)dev_alloc((65536 + 1) * 4);
-    B_.changed_count = (uint32_t*)dev_alloc(64);
+    B_.keys = mem_.uninit<uint16_t>(M * 2 + 64);
+    B_.by_key = mem_.uninit<uint32_t>(M * 4 + 64);
+    B_.sorted_keys = mem_.uninit<uint16_t>(M * 2 + 64);
+    B_.key_first = mem_.zeroed<uint32_t>((65536 + 1) * 4);
+    B_.key_last = mem_.zeroed<uint32_t>((65536 + 1) * 4);
+    B_.changed_count = mem_.zeroed<uint32_t>(64);
     B_.sort_tmp_bytes = lz77_sort_tmp_bytes(P_.total_bytes);
-    B_.sort_tmp = dev_alloc_uninit(B_.sort_tmp_bytes);
+    B_.sort_tmp = mem_.uninit(B_.sort_tmp_bytes);
     Z_ = ZopfliJob{};
     Z_.quality = (uint32_t)params.quality;
     Z_.lgwin = (uint32_t)params.lgwin;
     Z_.use_dictionary = params.use_dictionary ? 1 : 0;
     Z_.dist_alphabet_size = params.dist.alphabet_size;
     Z_.block_bytes = block_bytes_;
-    Z_.buckets = (uint32_t*)dev_alloc_uninit(((size_t)1 << 17) * 4 + 64);
-    Z_.forest = (uint32_t*)dev_alloc_uninit(((size_t)2 << params.lgwin) * 4 + 64);
-    Z_.nodes = dev_alloc_uninit(((size_t)block_bytes_ + 2) * 20 + 64);
-    Z_.literal_costs = (float*)dev_alloc_uninit(((size_t)block_bytes_ + 4) * 4 + 64);
-    Z_.cost_dist = (float*)dev_alloc((size_t)(params.dist.alphabet_size + 64) * 4 + 64);
-    Z_.cost_cmd = (float*)dev_alloc(704 * 4 + 64);
-    Z_.histo = (uint32_t*)dev_alloc(2048 * 4 + 64);
-    Z_.matches = (unsigned long long*)dev_alloc_uninit((size_t)128 * block_bytes_ * 8 + 64);
-    Z_.num_matches = (uint32_t*)dev_alloc((size_t)block_bytes_ * 4 + 64);
-    Z_.tmp_cmds = (Command*)dev_alloc_uninit(((size_t)block_bytes_ / 2 + 8) * sizeof(Command) + 64);
-    Z_.forest_new = (uint32_t*)dev_alloc_uninit(((size_t)2 << params.lgwin) * 4 + 64);
-    Z_.forest_bak = (uint32_t*)dev_alloc_uninit(((size_t)2 << params.lgwin) * 4 + 64);
-    Z_.buckets_bak = (uint32_t*)dev_alloc_uninit(((size_t)1 << 17) * 4 + 64);
-    Z_.rerooted = (uint8_t*)dev_alloc((size_t)block_bytes_ + 64);
-    Z_.ctl = (uint32_t*)dev_alloc(64);
-    cmds_bytes_ = (size_t)total_cmd_slots_ * sizeof(Command) + 64;
-    B_.cmds = (Command*)dev_alloc_uninit(cmds_bytes_);
-    B_.segments = (Segment*)dev_alloc(segments_.size() * sizeof(Segment) + 64);
-    B_.entries = (SegEntry*)dev_alloc(segments_.size() * sizeof(SegEntry) + 64);
-    B_.exits = (SegExit*)dev_alloc(segments_.size() * sizeof(SegExit) + 64);
-    histo_dev_ = (uint32_t*)dev_alloc(256 * 4);
-    gather_offsets_dev_ = (uint32_t*)dev_alloc(segments_.size() * 4 + 64);
-    gather_counts_dev_ = (uint32_t*)dev_alloc(segments_.size() * 4 + 64);
-    owns_buffers_ = true;
-    segments_upload_.resize_discard(segments_.size());
-    memcpy(segments_upload_.data(), segments_.data(), segments_.size() * sizeof(Segment));
-    dev_h2d(B_.segments, segments_upload_.data(), segments_.size() * sizeof(Segment));
+    Z_.buckets = mem_.uninit<uint32_t>(((size_t)1 << 17) * 4 + 64);
+    Z_.forest = mem_.uninit<uint32_t>(((size_t)2 << params.lgwin) * 4 + 64);
+    Z_.nodes = mem_.uninit(((size_t)block_bytes_ + 2) * 20 + 64);
+    Z_.literal_costs = mem_.uninit<float>(((size_t)block_bytes_ + 4) * 4 + 64);
+    Z_.cost_dist = mem_.zeroed<float>((size_t)(params.dist.alphabet_size + 64) * 4 + 64);
+    Z_.cost_cmd = mem_.zeroed<float>(704 * 4 + 64);
+    Z_.histo = mem_.zeroed<uint32_t>(2048 * 4 + 64);
+    Z_.matches = mem_.uninit<unsigned long long>((size_t)128 * block_bytes_ * 8 + 64);
+    Z_.num_matches = mem_.zeroed<uint32_t>((size_t)block_bytes_ * 4 + 64);
+    Z_.tmp_cmds = mem_.uninit<Command>(((size_t)block_bytes_ / 2 + 8) * sizeof(Command) + 64);
+    Z_.forest_new = mem_.uninit<uint32_t>(((size_t)2 << params.lgwin) * 4 + 64);
+    Z_.forest_bak = mem_.uninit<uint32_t>(((size_t)2 << params.lgwin) * 4 + 64);
+    Z_.buckets_bak = mem_.uninit<uint32_t>(((size_t)1 << 17) * 4 + 64);
+    Z_.rerooted = mem_.zeroed<uint8_t>((size_t)block_bytes_ + 64);
+    Z_.ctl = mem_.zeroed<uint32_t>(64);
+    SetupCommon(false);
     exits_.assign((uint32_t)segments_.size(), SegExit{});
     return;
   }
-  B_.keys = (uint16_t*)dev_alloc_uninit(M * 2 + 64);
-  B_.by_key = (uint32_t*)dev_alloc_uninit(M * 4 + 64);
-  B_.sorted_keys = (uint16_t*)dev_alloc_uninit(M * 2 + 64);
-  B_.fbits = (uint8_t*)dev_alloc_uninit(M + 64);
-  B_.key_first = (uint32_t*)dev_alloc((65536 + 1) * 4);
-  B_.key_last = (uint32_t*)dev_alloc((65536 + 1) * 4);
-  B_.changed_count = (uint32_t*)dev_alloc(64);
+  B_.keys = mem_.uninit<uint16_t>(M * 2 + 64);
+  B_.by_key = mem_.uninit<uint32_t>(M * 4 + 64);
+  B_.sorted_keys = mem_.uninit<uint16_t>(M * 2 + 64);
+  B_.fbits = mem_.uninit<uint8_t>(M + 64);
+  B_.key_first = mem_.zeroed<uint32_t>((65536 + 1) * 4);
+  B_.key_last = mem_.zeroed<uint32_t>((65536 + 1) * 4);
+  B_.changed_count = mem_.zeroed<uint32_t>(64);
   // Ring depth 16 (quality 5): position-indexed candidate rows (lz77_chain.h); deeper rings keep the rank structures.
   substitute_inherited_pushes_ = getenv("BROTLI_MI355X_PUSH_SUBSTITUTION") != nullptr;
   use_rows_ = P_.hasher_kind != 9 && (1u << P_.block_bits) <= kRowEntries && getenv("BROTLI_MI355X_NO_ROWS") == nullptr;
@@ -342,95 +241,82 @@ void Lz77Stage::Setup(const EncoderParams& params, uint8_t* text_dev, uint32_t p
     const size_t K = (size_t)1 << P_.bucket_bits;
     L_.span_blocks = (uint32_t)std::max<size_t>(1, segments_.size());
     L_.tables = 1;
-    L_.num = (uint16_t*)dev_alloc_uninit(K * 2 + 64);
-    L_.buckets = (uint32_t*)dev_alloc_uninit((K << P_.block_bits) * 4 + 64);
-    L_.state = (LiveBlockState*)dev_alloc(segments_.size() * sizeof(LiveBlockState) + 64);
+    L_.num = mem_.uninit<uint16_t>(K * 2 + 64);
+    L_.buckets = mem_.uninit<uint32_t>((K << P_.block_bits) * 4 + 64);
+    L_.state = mem_.zeroed<LiveBlockState>(segments_.size() * sizeof(LiveBlockState) + 64);
     live_verify_ = getenv("BROTLI_MI355X_LIVE_VERIFY") != nullptr || getenv("BROTLI_MI355X_SELFTEST") != nullptr;
-    L_.slot_of = (uint32_t*)dev_alloc_uninit(M * 4 + 64);
+    L_.slot_of = mem_.uninit<uint32_t>(M * 4 + 64);
     for (int i = 0; i < 2; ++i) {
-      L_.rank[i] = (uint32_t*)dev_alloc_uninit((M + 1) * 4 + 64);
-      L_.entry[i] = (uint32_t*)dev_alloc_uninit(M * 4 + 64);
+      L_.rank[i] = mem_.uninit<uint32_t>((M + 1) * 4 + 64);
+      L_.entry[i] = mem_.uninit<uint32_t>(M * 4 + 64);
     }
     if (live_verify_) {
       // every search is logged; the verification repeats them one by one against the final flags (lz77_live_verify)
-      B_.search_log = (uint32_t*)dev_alloc(M * kSearchLogWords * 4 + 64);
+      B_.search_log = mem_.zeroed<uint32_t>(M * kSearchLogWords * 4 + 64);
       B_.recheck_cap = (uint32_t)(M + 4096);  // (every position can be a searched one)
-      B_.recheck_list = (uint32_t*)dev_alloc_uninit((size_t)B_.recheck_cap * 4 + 64);
-      B_.recheck_count = (uint32_t*)dev_alloc(64);
+      B_.recheck_list = mem_.uninit<uint32_t>((size_t)B_.recheck_cap * 4 + 64);
+      B_.recheck_count = mem_.zeroed<uint32_t>(64);
     }
-    L_.changed_key = (uint8_t*)dev_alloc(65536 + 64);
+    L_.changed_key = mem_.zeroed<uint8_t>(65536 + 64);
     B_.changed_cap = kChangedCap;
-    B_.changed_keys = (uint32_t*)dev_alloc((size_t)kChangedCap * 4);
+    B_.changed_keys = mem_.zeroed<uint32_t>((size_t)kChangedCap * 4);
   } else
   if (use_rows_) {
     B_.changed_cap = (uint32_t)std::max<size_t>(kChangedCap, M / 32);
-    B_.changed_keys = (uint32_t*)dev_alloc_uninit((size_t)B_.changed_cap * 4 + 64);
-    B_.changed_slot = (uint32_t*)dev_alloc_uninit((size_t)B_.changed_cap * 4 + 64);
-    B_.row_ctl = (uint32_t*)dev_alloc(64);
-    B_.big_tile = (uint8_t*)dev_alloc(M / 1024 + 128);
-    B_.smask = (unsigned long long*)dev_alloc_uninit((M / 64 + 2) * 8 + 64);
-    B_.gprev = (uint32_t*)dev_alloc_uninit((M / 64 + 2) * 4 + 64);
+    B_.changed_keys = mem_.uninit<uint32_t>((size_t)B_.changed_cap * 4 + 64);
+    B_.changed_slot = mem_.uninit<uint32_t>((size_t)B_.changed_cap * 4 + 64);
+    B_.row_ctl = mem_.zeroed<uint32_t>(64);
+    B_.big_tile = mem_.zeroed<uint8_t>(M / 1024 + 128);
+    B_.smask = mem_.uninit<unsigned long long>((M / 64 + 2) * 8 + 64);
+    B_.gprev = mem_.uninit<uint32_t>((M / 64 + 2) * 4 + 64);
     if (getenv("BROTLI_MI355X_NO_POTENTIAL_MASK") == nullptr) {
-      B_.pot = (unsigned long long*)dev_alloc_uninit((M / 64 + 2) * 8 + 64);
-      B_.pot_state = (uint32_t*)dev_alloc(64);
+      B_.pot = mem_.uninit<unsigned long long>((M / 64 + 2) * 8 + 64);
+      B_.pot_state = mem_.zeroed<uint32_t>(64);
       B_.pot_list_cap = (uint32_t)(M / 16 + 1024);  // (denser than that: the pass over all rows is the cheaper one)
-      B_.pot_list = (uint32_t*)dev_alloc_uninit((size_t)B_.pot_list_cap * 4 + 64);
+      B_.pot_list = mem_.uninit<uint32_t>((size_t)B_.pot_list_cap * 4 + 64);
       if (getenv("BROTLI_MI355X_NO_FLIP_CELLS") == nullptr) {
         uint32_t shift = 8;
         while (shift < 31 && (1u << shift) < P_.max_backward_limit + 1u) ++shift;
         while (shift < 31 && (M >> shift) + 2 > 1024) ++shift;
         B_.cell_shift = shift;
         B_.cells_per_key = (uint32_t)(M >> shift) + 2;
-        B_.flip_cells = (uint32_t*)dev_alloc((size_t)65536 * B_.cells_per_key / 8 + 64);
+        B_.flip_cells = mem_.zeroed<uint32_t>((size_t)65536 * B_.cells_per_key / 8 + 64);
       }
     }
-    B_.stag = (uint16_t*)dev_alloc_uninit(M * 2 + 64);
-    B_.rows = (uint32_t*)dev_alloc_uninit(M * kRowEntries * 4 + 64);
-    if (P_.use_dictionary) B_.dict_items = (uint32_t*)dev_alloc_uninit(M * 4 + 256);
+    B_.stag = mem_.uninit<uint16_t>(M * 2 + 64);
+    B_.rows = mem_.uninit<uint32_t>(M * kRowEntries * 4 + 64);
+    if (P_.use_dictionary) B_.dict_items = mem_.uninit<uint32_t>(M * 4 + 256);
     if (getenv("BROTLI_MI355X_NO_CHECKPOINTS") == nullptr) {
-      B_.checkpoints = dev_alloc((M / kCheckpointStride + 2) * sizeof(Checkpoint));  // (zero: no record is valid)
-      B_.rows_changed_lo = (uint32_t*)dev_alloc_uninit(segments_.size() * 4 + 64);
-      B_.rows_changed_hi = (uint32_t*)dev_alloc_uninit(segments_.size() * 4 + 64);
+      B_.checkpoints = mem_.zeroed((M / kCheckpointStride + 2) * sizeof(Checkpoint));  // (zero: no record is valid)
+      B_.rows_changed_lo = mem_.uninit<uint32_t>(segments_.size() * 4 + 64);
+      B_.rows_changed_hi = mem_.uninit<uint32_t>(segments_.size() * 4 + 64);
     }
   } else {
     B_.changed_cap = kChangedCap;
-    B_.changed_keys = (uint32_t*)dev_alloc((size_t)kChangedCap * 4);
-    B_.info[0] = (uint32_t*)dev_alloc_uninit(M * 8 + 64);
-    B_.info[1] = (uint32_t*)dev_alloc_uninit(M * 8 + 64);
-    B_.sorted[0] = (uint32_t*)dev_alloc(M * 4 + 64);
-    B_.sorted[1] = (uint32_t*)dev_alloc(M * 4 + 64);
+    B_.changed_keys = mem_.zeroed<uint32_t>((size_t)kChangedCap * 4);
+    B_.info[0] = mem_.uninit<uint32_t>(M * 8 + 64);
+    B_.info[1] = mem_.uninit<uint32_t>(M * 8 + 64);
+    B_.sorted[0] = mem_.zeroed<uint32_t>(M * 4 + 64);
+    B_.sorted[1] = mem_.zeroed<uint32_t>(M * 4 + 64);
     // tags of the ring entries (ChainTables::sorted_tag): candidates that start with other bytes are not fetched
     if (getenv("BROTLI_MI355X_NO_TAGS") == nullptr) {
-      B_.stag = (uint16_t*)dev_alloc_uninit(M * 2 + 64);
-      B_.sorted_tag[0] = (uint16_t*)dev_alloc(M * 2 + 64);
-      B_.sorted_tag[1] = (uint16_t*)dev_alloc(M * 2 + 64);
+      B_.stag = mem_.uninit<uint16_t>(M * 2 + 64);
+      B_.sorted_tag[0] = mem_.zeroed<uint16_t>(M * 2 + 64);
+      B_.sorted_tag[1] = mem_.zeroed<uint16_t>(M * 2 + 64);
     }
     // every search is logged so that a flag change can be answered by repeating single searches (lz77_recheck_searches)
     if (getenv("BROTLI_MI355X_NO_RECHECK") == nullptr) {
-      B_.search_log = (uint32_t*)dev_alloc(M * kSearchLogWords * 4 + 64);
+      B_.search_log = mem_.zeroed<uint32_t>(M * kSearchLogWords * 4 + 64);
       B_.recheck_cap = (uint32_t)std::max<size_t>(4096, M / 8);
-      B_.recheck_list = (uint32_t*)dev_alloc_uninit((size_t)B_.recheck_cap * 4 + 64);
-      B_.recheck_count = (uint32_t*)dev_alloc(64);
+      B_.recheck_list = mem_.uninit<uint32_t>((size_t)B_.recheck_cap * 4 + 64);
+      B_.recheck_count = mem_.zeroed<uint32_t>(64);
     }
   }
-  B_.key_base = (uint32_t*)dev_alloc((65536 + 1) * 4);
-  B_.reset_counts = (uint32_t*)dev_alloc((65536 + 1) * 4);
-  B_.flags[0] = (uint8_t*)dev_alloc(M + 64);
-  B_.flags[1] = (uint8_t*)dev_alloc(M + 64);
-  cmds_bytes_ = (size_t)total_cmd_slots_ * sizeof(Command) + 64;
-  B_.cmds = (Command*)dev_alloc_uninit(cmds_bytes_);
-  B_.segments = (Segment*)dev_alloc(segments_.size() * sizeof(Segment) + 64);
-  B_.entries = (SegEntry*)dev_alloc(segments_.size() * sizeof(SegEntry) + 64);
-  B_.exits = (SegExit*)dev_alloc(segments_.size() * sizeof(SegExit) + 64);
-  B_.sort_tmp_bytes = lz77_sort_tmp_bytes(P_.total_bytes);
-  B_.sort_tmp = dev_alloc_uninit(B_.sort_tmp_bytes);  // (every user writes what it reads: histograms, tile sums, ping-pong arrays)
-  histo_dev_ = (uint32_t*)dev_alloc(256 * 4);
-  gather_offsets_dev_ = (uint32_t*)dev_alloc(segments_.size() * 4 + 64);
-  gather_counts_dev_ = (uint32_t*)dev_alloc(segments_.size() * 4 + 64);
-  owns_buffers_ = true;
-  segments_upload_.resize_discard(segments_.size());
-  memcpy(segments_upload_.data(), segments_.data(), segments_.size() * sizeof(Segment));
-  dev_h2d(B_.segments, segments_upload_.data(), segments_.size() * sizeof(Segment));
+  B_.key_base = mem_.zeroed<uint32_t>((65536 + 1) * 4);
+  B_.reset_counts = mem_.zeroed<uint32_t>((65536 + 1) * 4);
+  B_.flags[0] = mem_.zeroed<uint8_t>(M + 64);
+  B_.flags[1] = mem_.zeroed<uint8_t>(M + 64);
+  SetupCommon(true);
 }
 
 void Lz77Stage::BuildSegments() {
@@ -1271,18 +1157,15 @@ void Lz77Stage::WarmupBegin(WarmupJob* job, uint32_t first_seg, uint32_t end_seg
     wentries[i] = e;
   }
   timeline().stamp("wu-prepared");
-  Segment* wsegs_dev = (Segment*)dev_alloc(count * sizeof(Segment));
-  SegEntry* wentries_dev = (SegEntry*)dev_alloc(count * sizeof(SegEntry));
-  SegExit* wexits_dev = (SegExit*)dev_alloc(count * sizeof(SegExit));
+  Segment* wsegs_dev = job->mem.zeroed<Segment>(count * sizeof(Segment));
+  SegEntry* wentries_dev = job->mem.zeroed<SegEntry>(count * sizeof(SegEntry));
+  SegExit* wexits_dev = job->mem.zeroed<SegExit>(count * sizeof(SegExit));
   dev_h2d(wsegs_dev, wsegs.data(), count * sizeof(Segment));
   dev_h2d(wentries_dev, wentries.data(), count * sizeof(SegEntry));
   lz77_parse_custom(P_, B_, which, rbuf, wsegs_dev, wentries_dev, wexits_dev, count);
   timeline().stamp("wu-queued");
   dev_d2h_async(wexits.data(), wexits_dev, count * sizeof(SegExit));
   dev_mark_n(mark);
-  job->wsegs_dev = wsegs_dev;
-  job->wentries_dev = wentries_dev;
-  job->wexits_dev = wexits_dev;
 }
 
 void Lz77Stage::WarmupEnd(WarmupJob* job) {
@@ -1297,9 +1180,7 @@ void Lz77Stage::WarmupEnd(WarmupJob* job) {
   const bool only_after_dirty = !job->whole_input;
   dev_wait_mark_n(job->mark);
   timeline().stamp("wu-exits");
-  dev_free(job->wsegs_dev);
-  dev_free(job->wentries_dev);
-  dev_free(job->wexits_dev);
+  job->mem.clear();
   if (!dict_dead && !only_after_dirty) {
     // lookups / matches the dry runs saw, scaled to the whole segment: a forecast of where the throttle trips
     if (warm_lookups_.size() != nseg || ks[0] == 0) {
@@ -1395,14 +1276,14 @@ uint32_t Lz77Stage::RecheckCacheOnly(int which, std::vector<uint32_t>* accepted)
   }
   if (items.empty()) return 0;
   const uint32_t count = (uint32_t)items.size();
-  CacheCheck* items_dev = (CacheCheck*)dev_alloc(count * sizeof(CacheCheck) + 64);
-  uint8_t* ok_dev = (uint8_t*)dev_alloc(count + 64);
+  DevBlocks tmp;
+  CacheCheck* items_dev = tmp.zeroed<CacheCheck>(count * sizeof(CacheCheck) + 64);
+  uint8_t* ok_dev = tmp.zeroed<uint8_t>(count + 64);
   dev_h2d(items_dev, items.data(), count * sizeof(CacheCheck));
   lz77_check_cache(P_, B_, which, items_dev, count, ok_dev);
   std::vector<uint8_t> ok(count);
   dev_d2h(ok.data(), ok_dev, count);
-  dev_free(items_dev);
-  dev_free(ok_dev);
+  tmp.clear();
   uint32_t cleared = 0;
   for (uint32_t i = 0; i < count; ++i) {
     if (!ok[i]) continue;
@@ -1475,7 +1356,7 @@ void Lz77Stage::Run() {
   // block; the run table lets the chains jump over a run instead of comparing it 32 bytes at a time (lz77_chain.h).
   // One sample in 64 positions: 64 samples ~ 4 KiB of runs.
   if (run_samples >= 64 && getenv("BROTLI_MI355X_NO_RUN_TABLE") == nullptr) {
-    if (!B_.run_end) B_.run_end = (uint32_t*)dev_alloc_uninit((size_t)P_.total_bytes * 4 + 64);
+    if (!B_.run_end) B_.run_end = mem_.uninit<uint32_t>((size_t)P_.total_bytes * 4 + 64);
     lz77_run_table(P_, B_);
     if (getenv("BROTLI_MI355X_SELFTEST")) {
       const uint32_t n = P_.total_bytes;
@@ -1489,15 +1370,14 @@ void Lz77Stage::Run() {
         if (got[p] != end) throw std::runtime_error("selftest: run table wrong at position " + std::to_string(p));
       }
     }
-  } else if (B_.run_end) {
-    dev_free(B_.run_end);
-    B_.run_end = nullptr;
+  } else {
+    mem_.drop(B_.run_end);
   }
   has_big_keys_ = false;
   for (uint32_t key = 0; key < 65536 && !has_big_keys_; ++key) has_big_keys_ = key_last_[key] - key_first_[key] >= 65536u;
   // a later piece of a stream: the ring counters of the reference have been running since the start of the stream
   if (carry_ && carry_->valid && carry_->key_counts.size() == 65536) {
-    if (!count_base_dev_) count_base_dev_ = (uint32_t*)dev_alloc(65536 * 4);
+    if (!count_base_dev_) count_base_dev_ = mem_.zeroed<uint32_t>(65536 * 4);
     dev_h2d(count_base_dev_, carry_->key_counts.data(), 65536 * 4);
     B_.count_base = count_base_dev_;
     has_big_keys_ = true;
@@ -1530,8 +1410,8 @@ void Lz77Stage::Resegment(uint32_t segment_bytes) {
   P_.num_segments = (uint32_t)segments_.size();
   const size_t need = (size_t)total_cmd_slots_ * sizeof(Command) + 64;
   if (need > cmds_bytes_) {
-    dev_free(B_.cmds);
-    B_.cmds = (Command*)dev_alloc_uninit(need);
+    mem_.drop(B_.cmds);
+    B_.cmds = mem_.uninit<Command>(need);
     cmds_bytes_ = need;
   }
   segments_upload_.resize_discard(segments_.size());
@@ -1583,8 +1463,9 @@ void Lz77Stage::RunLive() {
     }
   }
   tm.stop(&stats_.ms_init);
-  uint32_t* first_dev = (uint32_t*)dev_alloc(64);
-  uint32_t* start_dev = (uint32_t*)dev_alloc(64);
+  DevBlocks tmp;
+  uint32_t* first_dev = tmp.zeroed<uint32_t>(64);
+  uint32_t* start_dev = tmp.zeroed<uint32_t>(64);
   PinnedArray<uint32_t> first_start;
   PinnedArray<LiveBlockState> books;
   first_start.resize_discard(2);
@@ -1631,8 +1512,7 @@ void Lz77Stage::RunLive() {
     from = wrong;
     done = wrong == nseg;
   }
-  dev_free(first_dev);
-  dev_free(start_dev);
+  tmp.clear();
   if (!done) throw std::runtime_error("brotli_mi355x: backward-reference search (live chain) did not reach a fixed point");
   final_flags_ = which;
   if (live_verify_) {
@@ -1643,22 +1523,17 @@ void Lz77Stage::RunLive() {
     geo.num_blocks = nseg;
     geo.num_segments = nseg;
     geo.block_size = 1u << P_.block_bits;
-    uint8_t* dirty_dev = (uint8_t*)dev_alloc(nseg + 64);
+    uint8_t* dirty_dev = tmp.zeroed<uint8_t>(nseg + 64);
     std::vector<uint8_t> failed(nseg);
     lz77_live_slots(P_, B_, L_);
     lz77_live_index(P_, B_, L_, which);
     lz77_live_verify(P_, B_, L_, -1, which, geo, nullptr, dirty_dev);
     dev_d2h(failed.data(), dirty_dev, nseg);
-    dev_free(dirty_dev);
+    tmp.clear();
     for (uint32_t k = 0; k < nseg; ++k)
       if (failed[k]) throw std::runtime_error("brotli_mi355x: live chain verification failed in block " + std::to_string(k));
   }
   for (uint32_t k = 0; k < nseg; ++k) stats_.searches += exits_[k].n_searches;
-}
-
-ZopfliCarry::~ZopfliCarry() {
-  dev_free(buckets);
-  dev_free(forest);
 }
 
 void Lz77Stage::ExportZopfli(StreamCarry* co, bool partial) {
@@ -1667,18 +1542,14 @@ void Lz77Stage::ExportZopfli(StreamCarry* co, bool partial) {
   zc->text_base = (carry_ && carry_->valid) ? carry_->stream_base : 0;
   if (partial) {
     if (!zsnap_buckets_) throw std::runtime_error("brotli_mi355x: quality 10 / 11: no snapshot of the trees at the resume point");
-    zc->buckets = zsnap_buckets_;
-    zc->forest = zsnap_forest_;
-    zsnap_buckets_ = zsnap_forest_ = nullptr;
+    zc->buckets = mem_.give(zc->mem, zsnap_buckets_);
+    zc->forest = mem_.give(zc->mem, zsnap_forest_);
   } else {
-    zc->buckets = Z_.buckets;
-    zc->forest = Z_.forest;
-    Z_.buckets = Z_.forest = nullptr;
+    zc->buckets = mem_.give(zc->mem, Z_.buckets);
+    zc->forest = mem_.give(zc->mem, Z_.forest);
   }
   co->zopfli = std::move(zc);
 }
-
-QuickCarry::~QuickCarry() { dev_free(table); }
 
 void Lz77Stage::ExportQuick(StreamCarry* co, bool partial) {
   auto qc = std::make_shared<QuickCarry>();
@@ -1688,7 +1559,7 @@ void Lz77Stage::ExportQuick(StreamCarry* co, bool partial) {
     // of the block at the resume point, before that block's StitchToPreviousBlock files the three positions in front of it (the next
     // piece does that itself) -- from the final flags.  The books of the throttle behind the slots: the resolver's, as the encoder
     // has put them into the carry (once the throttle has tripped only "matches < lookups >> 7" matters: nothing is looked up any more).
-    uint32_t* table = (uint32_t*)dev_alloc_uninit((size_t)quick_table_words(Q_) * 4 + 64);
+    uint32_t* table = qc->mem.uninit<uint32_t>((size_t)quick_table_words(Q_) * 4 + 64);
     const uint32_t first = segments_.empty() ? P_.total_bytes : segments_[0].blk_start;
     uint32_t upto = 0xffffffffu;
     if (partial) upto = resume_pos_ >= 3 ? resume_pos_ - 3 : 0;
@@ -1711,11 +1582,9 @@ void Lz77Stage::ExportQuick(StreamCarry* co, bool partial) {
   }
   if (partial) {
     if (!qsnap_table_) throw std::runtime_error("brotli_mi355x: qualities 2 .. 4: no snapshot of the hash table at the resume point");
-    qc->table = qsnap_table_;
-    qsnap_table_ = nullptr;
+    qc->table = mem_.give(qc->mem, qsnap_table_);
   } else {
-    qc->table = Q_.table;
-    Q_.table = nullptr;
+    qc->table = mem_.give(qc->mem, Q_.table);
   }
   co->quick = std::move(qc);
 }
@@ -1738,7 +1607,7 @@ void Lz77Stage::RunQuick() {
     if (P_.prefix_bytes > 1) lz77_quick_prepend(P_, B_, Q_, P_.prefix_bytes);  // custom dictionary, encode.rs:1163-1194
   }
   auto snapshot = [&]() {
-    if (!qsnap_table_) qsnap_table_ = (uint32_t*)dev_alloc_uninit(table_bytes + 64);
+    if (!qsnap_table_) qsnap_table_ = mem_.uninit<uint32_t>(table_bytes + 64);
     dev_d2d(qsnap_table_, Q_.table, table_bytes);
   };
   bool starts_metablock = true;
@@ -1823,17 +1692,18 @@ void Lz77Stage::RunQuickSpec() {
   geo.first_block_start = segments_[0].blk_start;
   geo.block_bytes = block_bytes_;
   geo.num_blocks = (uint32_t)block_segment_bytes_.size();
-  uint32_t* geo_tables = (uint32_t*)dev_alloc((block_first_segment_.size() + block_segment_bytes_.size()) * 4 + 64);
+  DevBlocks tmp;  // the scratch of this pass
+  uint32_t* geo_tables = tmp.zeroed<uint32_t>((block_first_segment_.size() + block_segment_bytes_.size()) * 4 + 64);
   dev_h2d(geo_tables, block_first_segment_.data(), block_first_segment_.size() * 4);
   dev_h2d(geo_tables + block_first_segment_.size(), block_segment_bytes_.data(), block_segment_bytes_.size() * 4);
   geo.block_first_segment = geo_tables;
   geo.block_segment_bytes = geo_tables + block_first_segment_.size();
   geo.num_segments = nseg;
   geo.block_size = 1;
-  uint8_t* dirty_dev = (uint8_t*)dev_alloc(nseg + 64);
-  uint32_t* list_dev = (uint32_t*)dev_alloc((size_t)nseg * 4 + 64);
-  SegEntry* up_entries_dev = (SegEntry*)dev_alloc_uninit((size_t)nseg * sizeof(SegEntry) + 64);
-  SegExit* got_exits_dev = (SegExit*)dev_alloc_uninit((size_t)nseg * sizeof(SegExit) + 64);
+  uint8_t* dirty_dev = tmp.zeroed<uint8_t>(nseg + 64);
+  uint32_t* list_dev = tmp.zeroed<uint32_t>((size_t)nseg * 4 + 64);
+  SegEntry* up_entries_dev = tmp.uninit<SegEntry>((size_t)nseg * sizeof(SegEntry) + 64);
+  SegExit* got_exits_dev = tmp.uninit<SegExit>((size_t)nseg * sizeof(SegExit) + 64);
   PinnedArray<uint8_t> dirty;
   dirty.resize_discard(nseg);
   // One chain per block (the restart below): every chain on a table of its own, read and filed into as the reference does
@@ -1848,9 +1718,9 @@ void Lz77Stage::RunQuickSpec() {
   const bool can_own = qspec_coarse_ && getenv("BROTLI_MI355X_QUICK_NO_OWN_TABLES") == nullptr;
   bool own = can_own && getenv("BROTLI_MI355X_QUICK_OWN_TABLES_FIRST") != nullptr;  // (tests: the tables from round 0 on)
   const uint32_t own_slots = own ? nseg : std::min(nseg, own_window);
-  uint32_t* own_tables = can_own ? (uint32_t*)dev_alloc_uninit((size_t)own_slots * own_stride * 4 + 64) : nullptr;
+  uint32_t* own_tables = can_own ? tmp.uninit<uint32_t>((size_t)own_slots * own_stride * 4 + 64) : nullptr;
   uint32_t own_from = 0, own_upto = nseg;  // (with the tables from round 0 on, that round parses every block)
-  uint32_t* first_change_dev = (uint32_t*)dev_alloc(64);
+  uint32_t* first_change_dev = tmp.zeroed<uint32_t>(64);
   PinnedArray<uint32_t> first_change;
   first_change.resize_discard(16);
   first_change[0] = 0xffffffffu;
@@ -1897,12 +1767,12 @@ void Lz77Stage::RunQuickSpec() {
       e.head_kind = kHeadNone;
       wentries[k] = e;
     }
-    Segment* wsegs_dev = (Segment*)dev_alloc_uninit((size_t)nseg * sizeof(Segment) + 64);
+    Segment* wsegs_dev = tmp.uninit<Segment>((size_t)nseg * sizeof(Segment) + 64);
     dev_h2d(wsegs_dev, wsegs.data(), (size_t)nseg * sizeof(Segment));
     dev_h2d(up_entries_dev, wentries.data(), (size_t)nseg * sizeof(SegEntry));
     lz77_qspec_parse_custom(P_, B_, Q_, S_, wsegs_dev, up_entries_dev, got_exits_dev, nseg);
     dev_d2h(wexits.data(), got_exits_dev, (size_t)nseg * sizeof(SegExit));
-    dev_free(wsegs_dev);
+    tmp.drop(wsegs_dev);
     for (uint32_t k = 0; k + 1 < nseg; ++k) {
       const SegExit& x = wexits[k];
       SegEntry& n = entries_[k + 1];
@@ -2083,13 +1953,7 @@ void Lz77Stage::RunQuickSpec() {
         throw std::runtime_error("selftest: candidate " + std::to_string(i % Q_.sweep) + " of position " + std::to_string(i / Q_.sweep) + " is " + std::to_string(kept[i]) +
                                  " after the repairs of " + std::to_string(incremental_rounds) + " rounds, " + std::to_string(fresh[i]) + " from the final flags");
   }
-  dev_free(geo_tables);
-  dev_free(dirty_dev);
-  dev_free(own_tables);
-  dev_free(first_change_dev);
-  dev_free(list_dev);
-  dev_free(up_entries_dev);
-  dev_free(got_exits_dev);
+  tmp.clear();  // (before a restart: it allocates the same again)
   if (restart_coarse) {
     saved_block_guess_.clear();
     for (uint32_t k = 0; k < nseg; ++k)
@@ -2108,14 +1972,14 @@ void Lz77Stage::RunQuickSpec() {
     use_qspec_ = false;
     P_.use_dictionary = 0;
     Resegment(block_bytes_);
-    dev_free(B_.entries);
-    dev_free(B_.exits);
-    dev_free(gather_offsets_dev_);
-    dev_free(gather_counts_dev_);
-    B_.entries = (SegEntry*)dev_alloc(segments_.size() * sizeof(SegEntry) + 64);
-    B_.exits = (SegExit*)dev_alloc(segments_.size() * sizeof(SegExit) + 64);
-    gather_offsets_dev_ = (uint32_t*)dev_alloc(segments_.size() * 4 + 64);
-    gather_counts_dev_ = (uint32_t*)dev_alloc(segments_.size() * 4 + 64);
+    mem_.drop(B_.entries);
+    mem_.drop(B_.exits);
+    mem_.drop(gather_offsets_dev_);
+    mem_.drop(gather_counts_dev_);
+    B_.entries = mem_.zeroed<SegEntry>(segments_.size() * sizeof(SegEntry) + 64);
+    B_.exits = mem_.zeroed<SegExit>(segments_.size() * sizeof(SegExit) + 64);
+    gather_offsets_dev_ = mem_.zeroed<uint32_t>(segments_.size() * 4 + 64);
+    gather_counts_dev_ = mem_.zeroed<uint32_t>(segments_.size() * 4 + 64);
     stats_.coarse_restarts++;
     RunQuick();
     return;
@@ -2156,8 +2020,8 @@ void Lz77Stage::RunZopfli() {
       // the next piece starts again at the first block of the meta-block that is still open when this one ends: the trees as
       // they are in front of every block that opens a meta-block (the last such copy is the one that travels)
       if (!zsnap_buckets_) {
-        zsnap_buckets_ = (uint32_t*)dev_alloc_uninit(bucket_bytes + 64);
-        zsnap_forest_ = (uint32_t*)dev_alloc_uninit(forest_bytes + 64);
+        zsnap_buckets_ = mem_.uninit<uint32_t>(bucket_bytes + 64);
+        zsnap_forest_ = mem_.uninit<uint32_t>(forest_bytes + 64);
       }
       dev_d2d(zsnap_buckets_, Z_.buckets, bucket_bytes);
       dev_d2d(zsnap_forest_, Z_.forest, forest_bytes);
@@ -2185,8 +2049,8 @@ void Lz77Stage::RunZopfli() {
   if (!done) throw std::runtime_error("brotli_mi355x: quality 10 / 11 parse did not finish");
   if (partial_ && starts_metablock) {  // (the flush rule closed a meta-block with the last block: the next piece starts behind it)
     if (!zsnap_buckets_) {
-      zsnap_buckets_ = (uint32_t*)dev_alloc_uninit(bucket_bytes + 64);
-      zsnap_forest_ = (uint32_t*)dev_alloc_uninit(forest_bytes + 64);
+      zsnap_buckets_ = mem_.uninit<uint32_t>(bucket_bytes + 64);
+      zsnap_forest_ = mem_.uninit<uint32_t>(forest_bytes + 64);
     }
     dev_d2d(zsnap_buckets_, Z_.buckets, bucket_bytes);
     dev_d2d(zsnap_forest_, Z_.forest, forest_bytes);
@@ -2290,26 +2154,27 @@ void Lz77Stage::RunRounds(bool allow_restart) {
   geo.first_block_start = segments_[0].blk_start;
   geo.block_bytes = block_bytes_;
   geo.num_blocks = (uint32_t)block_segment_bytes_.size();
-  uint32_t* geo_tables = (uint32_t*)dev_alloc((block_first_segment_.size() + block_segment_bytes_.size()) * 4 + 64);
+  DevBlocks tmp;  // the scratch of this pass
+  uint32_t* geo_tables = tmp.zeroed<uint32_t>((block_first_segment_.size() + block_segment_bytes_.size()) * 4 + 64);
   dev_h2d(geo_tables, block_first_segment_.data(), block_first_segment_.size() * 4);
   dev_h2d(geo_tables + block_first_segment_.size(), block_segment_bytes_.data(), block_segment_bytes_.size() * 4);
   geo.block_first_segment = geo_tables;
   geo.block_segment_bytes = geo_tables + block_first_segment_.size();
   geo.num_segments = nseg;
   geo.block_size = 1u << P_.block_bits;
-  uint8_t* dirty_dev = (uint8_t*)dev_alloc(nseg + 64);
-  uint32_t* list_dev = (uint32_t*)dev_alloc((size_t)nseg * 8 + 64);  // (listed segments + entries accepted by RecheckCacheOnly)
+  uint8_t* dirty_dev = tmp.zeroed<uint8_t>(nseg + 64);
+  uint32_t* list_dev = tmp.zeroed<uint32_t>((size_t)nseg * 8 + 64);  // (listed segments + entries accepted by RecheckCacheOnly)
   std::vector<uint8_t> dirty(nseg, 0);
   std::vector<uint32_t> list(nseg);
   // list rounds: compact transfers (lz77_scatter_entries / lz77_gather_results)
   static constexpr uint32_t kContFirst = 64;
   const uint32_t cont_cap = std::max(nseg, kContFirst);
-  SegEntry* up_entries_dev = (SegEntry*)dev_alloc_uninit((size_t)nseg * 2 * sizeof(SegEntry) + 64);
-  SegExit* got_exits_dev = (SegExit*)dev_alloc_uninit((size_t)nseg * sizeof(SegExit) + 64);
-  uint32_t* cont_count_dev = (uint32_t*)dev_alloc(64);
-  uint32_t* cont_index_dev = (uint32_t*)dev_alloc((size_t)cont_cap * 4 + 64);
-  SegExit* cont_exits_dev = (SegExit*)dev_alloc_uninit((size_t)cont_cap * sizeof(SegExit) + 64);
-  SegEntry* cont_entries_dev = (SegEntry*)dev_alloc_uninit((size_t)cont_cap * sizeof(SegEntry) + 64);
+  SegEntry* up_entries_dev = tmp.uninit<SegEntry>((size_t)nseg * 2 * sizeof(SegEntry) + 64);
+  SegExit* got_exits_dev = tmp.uninit<SegExit>((size_t)nseg * sizeof(SegExit) + 64);
+  uint32_t* cont_count_dev = tmp.zeroed<uint32_t>(64);
+  uint32_t* cont_index_dev = tmp.zeroed<uint32_t>((size_t)cont_cap * 4 + 64);
+  SegExit* cont_exits_dev = tmp.uninit<SegExit>((size_t)cont_cap * sizeof(SegExit) + 64);
+  SegEntry* cont_entries_dev = tmp.uninit<SegEntry>((size_t)cont_cap * sizeof(SegEntry) + 64);
   std::vector<uint32_t> also_upload;
   // bursts (device_api.h): up to burst_max list launches per pass of the host resolver, scheduled on the device in between
   static const uint32_t burst_env = getenv("BROTLI_MI355X_BURST") ? (uint32_t)atoi(getenv("BROTLI_MI355X_BURST")) : 8u;
@@ -2322,14 +2187,14 @@ void Lz77Stage::RunRounds(bool allow_restart) {
   BurstBuffers U;
   bool stale_marks_valid = false;  // U.stale says where the two flag arrays differ (from the first launch of the first burst on)
   if (burst_max != 0) {
-    U.sched = (uint8_t*)dev_alloc(nseg + 64);
+    U.sched = tmp.zeroed<uint8_t>(nseg + 64);
     U.cand_dirty = dirty_dev;
-    U.entry_dirty = (uint8_t*)dev_alloc(nseg + 64);
-    U.touched = (uint8_t*)dev_alloc(nseg + 64);
-    U.stale = (uint8_t*)dev_alloc(nseg + 64);
-    U.new_entries = (SegEntry*)dev_alloc_uninit((size_t)nseg * sizeof(SegEntry) + 64);
-    U.list = (uint32_t*)dev_alloc_uninit((size_t)nseg * 4 + 64);
-    U.counters = (uint32_t*)dev_alloc(64);
+    U.entry_dirty = tmp.zeroed<uint8_t>(nseg + 64);
+    U.touched = tmp.zeroed<uint8_t>(nseg + 64);
+    U.stale = tmp.zeroed<uint8_t>(nseg + 64);
+    U.new_entries = tmp.uninit<SegEntry>((size_t)nseg * sizeof(SegEntry) + 64);
+    U.list = tmp.uninit<uint32_t>((size_t)nseg * 4 + 64);
+    U.counters = tmp.zeroed<uint32_t>(64);
   }
   RoundBuffers& rb = round_buffers_;  // page-locked, kept from call to call
   rb.up_index.resize_discard((size_t)nseg * 2);
@@ -2565,12 +2430,12 @@ void Lz77Stage::RunRounds(bool allow_restart) {
           for (uint32_t b = lo; b < hi; b += kRerankChunk)
             chunks.push_back({lo, b, std::min(hi, b + kRerankChunk), first_sum, (uint32_t)chunks.size()});
         }
-        RerankChunk* chunks_dev = (RerankChunk*)dev_alloc(chunks.size() * sizeof(RerankChunk) + 64);
-        uint32_t* sums_dev = (uint32_t*)dev_alloc(chunks.size() * 4 + 64);
+        RerankChunk* chunks_dev = tmp.zeroed<RerankChunk>(chunks.size() * sizeof(RerankChunk) + 64);
+        uint32_t* sums_dev = tmp.zeroed<uint32_t>(chunks.size() * 4 + 64);
         dev_h2d(chunks_dev, chunks.data(), chunks.size() * sizeof(RerankChunk));
         lz77_rerank_keys(P_, B_, which, rbuf, chunks_dev, (uint32_t)chunks.size(), sums_dev, geo, dirty_dev);
-        dev_free(chunks_dev);
-        dev_free(sums_dev);
+        tmp.drop(chunks_dev);
+        tmp.drop(sums_dev);
         stats_.incremental_ranks++;
       } else {
         lz77_rank_flags(P_, B_, which, rbuf ^ 1);
@@ -2750,22 +2615,7 @@ void Lz77Stage::RunRounds(bool allow_restart) {
     full_round = false;
   }
   resolve_incremental_ = false;
-  dev_free(dirty_dev);
-  dev_free(list_dev);
-  dev_free(geo_tables);
-  dev_free(up_entries_dev);
-  dev_free(got_exits_dev);
-  dev_free(cont_count_dev);
-  dev_free(cont_index_dev);
-  dev_free(cont_exits_dev);
-  dev_free(cont_entries_dev);
-  dev_free(U.stale);
-  dev_free(U.sched);
-  dev_free(U.entry_dirty);
-  dev_free(U.touched);
-  dev_free(U.new_entries);
-  dev_free(U.list);
-  dev_free(U.counters);
+  tmp.clear();  // (before a restart: it allocates the same again)
   if (restart) {
     // what the pass so far says about the state at every block start
     saved_block_guess_.clear();
@@ -2920,22 +2770,23 @@ void Lz77Stage::SelfTestRows(int which) {
 }
 
 void Lz77Stage::KeyCountsBetween(uint32_t from, uint32_t upto, std::vector<uint32_t>* out) {
-  uint32_t* dev = (uint32_t*)dev_alloc(2 * 65536 * 4);
+  DevBlocks tmp;
+  uint32_t* dev = tmp.zeroed<uint32_t>(2 * 65536 * 4);
   lz77_key_counts(P_, B_, final_flags_, upto, dev, false);
   lz77_key_counts(P_, B_, final_flags_, from, dev + 65536, false);
   std::vector<uint32_t> both(2 * 65536);
   dev_d2h(both.data(), dev, both.size() * 4);
-  dev_free(dev);
+  tmp.clear();
   out->resize(65536);
   for (uint32_t k = 0; k < 65536; ++k) (*out)[k] = both[k] - both[65536 + k];
 }
 
 void Lz77Stage::KeyCountsBefore(uint32_t upto, std::vector<uint32_t>* out) {
-  uint32_t* dev = (uint32_t*)dev_alloc(65536 * 4);
+  DevBlocks tmp;
+  uint32_t* dev = tmp.zeroed<uint32_t>(65536 * 4);
   lz77_key_counts(P_, B_, final_flags_, upto, dev);
   out->resize(65536);
   dev_d2h(out->data(), dev, 65536 * 4);
-  dev_free(dev);
 }
 
 void Lz77Stage::Gather() {
@@ -2988,20 +2839,20 @@ void Lz77Stage::Gather() {
     mb.cmd_offset = first_seg < nseg ? offsets[first_seg] : (uint32_t)total;
   }
   if (gathered_capacity_ < total + 16) {
-    dev_free(gathered_cmds_);
+    mem_.drop(gathered_cmds_);
     gathered_capacity_ = total + total / 8 + 1024;
-    gathered_cmds_ = (Command*)dev_alloc(gathered_capacity_ * sizeof(Command));
+    gathered_cmds_ = mem_.zeroed<Command>(gathered_capacity_ * sizeof(Command));
   }
   dev_h2d(gather_offsets_dev_, offsets.data(), nseg * 4);
   dev_h2d(gather_counts_dev_, counts.data(), nseg * 4);
   lz77_gather_commands(P_, B_, nseg, gather_offsets_dev_, gather_counts_dev_, gathered_cmds_);
   for (const std::vector<CmdPatch>* batch : {&fix, &fix_ext}) {
     if (batch->empty()) continue;
-    CmdPatch* fix_dev = (CmdPatch*)dev_alloc(batch->size() * sizeof(CmdPatch));
+    DevBlocks tmp;
+    CmdPatch* fix_dev = tmp.zeroed<CmdPatch>(batch->size() * sizeof(CmdPatch));
     dev_h2d(fix_dev, batch->data(), batch->size() * sizeof(CmdPatch));
     lz77_patch_commands(gathered_cmds_, fix_dev, (uint32_t)batch->size());
     dev_sync();
-    dev_free(fix_dev);
   }
   dev_sync();
 }

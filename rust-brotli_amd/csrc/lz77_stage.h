@@ -49,24 +49,18 @@ struct Lz77Stats {
 
 // Qualities 10 / 11: the H10 trees as a piece of a stream leaves them for the next one (device memory, owned here)
 struct ZopfliCarry {
+  DevBlocks mem;
   uint32_t* buckets = nullptr;  // [1 << 17]
   uint32_t* forest = nullptr;   // [2 << lgwin]
   uint32_t lgwin = 0;
   uint64_t text_base = 0;       // stream position of text position 0 of the piece that left them
-  ZopfliCarry() = default;
-  ZopfliCarry(const ZopfliCarry&) = delete;
-  ZopfliCarry& operator=(const ZopfliCarry&) = delete;
-  ~ZopfliCarry();
 };
 
 // Qualities 2 .. 4: the BasicHasher table (slots + dictionary-throttle counters, quick_api.h) as a piece of a stream leaves it
 struct QuickCarry {
+  DevBlocks mem;
   uint32_t* table = nullptr;  // [quick_table_words()]
   uint64_t text_base = 0;     // stream position of text position 0 of the piece that left it
-  QuickCarry() = default;
-  QuickCarry(const QuickCarry&) = delete;
-  QuickCarry& operator=(const QuickCarry&) = delete;
-  ~QuickCarry();
 };
 
 // What an encoder keeps between two encode_data calls of one stream (BROTLI_OPERATION_FLUSH): the reference's hasher
@@ -103,7 +97,6 @@ struct StreamCarry {
 class Lz77Stage {
  public:
   Lz77Stage() = default;
-  ~Lz77Stage();
   Lz77Stage(const Lz77Stage&) = delete;
   Lz77Stage& operator=(const Lz77Stage&) = delete;
 
@@ -186,9 +179,7 @@ class Lz77Stage {
     PinnedArray<Segment> wsegs;
     PinnedArray<SegEntry> wentries;
     PinnedArray<SegExit> wexits;
-    Segment* wsegs_dev = nullptr;
-    SegEntry* wentries_dev = nullptr;
-    SegExit* wexits_dev = nullptr;
+    DevBlocks mem;  // the device side of the three, from WarmupBegin to WarmupEnd
     uint32_t count = 0;
     bool dict_dead = false, whole_input = true;
     int mark = 0;
@@ -202,10 +193,12 @@ class Lz77Stage {
   void SelfTestRows(int which);
   bool FetchShouldCompress();
   bool ResolvePass(bool final_pass, bool incremental);
+  void SetupCommon(bool with_sort_tmp);
   void Release();
 
   EncoderParams params_;
   Lz77Params P_{};
+  DevBlocks mem_;  // every device block behind the pointers below that lives longer than one function
   Lz77Buffers B_{};
   LiveBuffers L_{};    // live chains (lz77_live.h)
   bool use_live_ = false;
@@ -330,7 +323,6 @@ class Lz77Stage {
   std::vector<uint8_t> dirty_entry_;
   uint32_t dict_death_seg_ = 0xffffffffu;
   uint32_t dict_flips_ = 0;
-  bool owns_buffers_ = false;
   uint32_t* count_base_dev_ = nullptr;  // carried-in ring counters per key (StreamCarry::key_counts)
   bool use_rows_ = false;      // quality 5: candidate rows instead of rank structures (device_api.h)
   bool has_big_keys_ = false;  // some hash key owns >= 65 536 positions (the u16 ring counter of the reference wraps)

@@ -45,7 +45,8 @@ long brotli_mi355x_lz77_trace(int quality, int lgwin, uint32_t size_hint, int ca
     const char* why = nullptr;
     if (!IsAccelerated(p, &why)) throw std::runtime_error(why);
     const uint32_t M = prefix_bytes + input_bytes;
-    uint8_t* text = (uint8_t*)dev_alloc((size_t)M + 64);
+    DevBlocks tmp;
+    uint8_t* text = tmp.zeroed<uint8_t>((size_t)M + 64);
     if (prefix_bytes) dev_h2d(text, prefix, prefix_bytes);
     dev_h2d(text + prefix_bytes, input, input_bytes);
     Lz77Stage stage;
@@ -81,7 +82,7 @@ long brotli_mi355x_lz77_trace(int quality, int lgwin, uint32_t size_hint, int ca
       const double ms[8] = {st.ms_keys, st.ms_sort, st.ms_init, st.ms_rank, st.ms_parse, st.ms_resolve, st.ms_gather, st.ms_total};
       for (int i = 0; i < 8; ++i) stats_out[4 + i] = (uint32_t)(ms[i] * 1000.0);  // microseconds
     }
-    dev_free(text);
+    tmp.clear();
     return (long)n;
   } catch (const std::exception& e) {
     if (err && err_len) {
@@ -103,11 +104,12 @@ int brotli_mi355x_debug_check_cache(const uint8_t* text, const uint8_t* flags, u
     P.ndist = ndist;
     P.max_backward_limit = max_backward_limit;
     Lz77Buffers B{};
-    B.text = (uint8_t*)dev_alloc((size_t)n + 64);
-    B.flags[0] = (uint8_t*)dev_alloc((size_t)n + 64);
-    B.segments = (Segment*)dev_alloc(sizeof(Segment));
-    CacheCheck* item_dev = (CacheCheck*)dev_alloc(sizeof(CacheCheck));
-    uint8_t* ok_dev = (uint8_t*)dev_alloc(64);
+    DevBlocks tmp;
+    B.text = tmp.zeroed<uint8_t>((size_t)n + 64);
+    B.flags[0] = tmp.zeroed<uint8_t>((size_t)n + 64);
+    B.segments = tmp.zeroed<Segment>(sizeof(Segment));
+    CacheCheck* item_dev = tmp.zeroed<CacheCheck>(sizeof(CacheCheck));
+    uint8_t* ok_dev = tmp.zeroed<uint8_t>(64);
     Segment seg{};
     seg.start = seg_start;
     seg.end = seg_end;
@@ -123,11 +125,6 @@ int brotli_mi355x_debug_check_cache(const uint8_t* text, const uint8_t* flags, u
     lz77_check_cache(P, B, 0, item_dev, 1, ok_dev);
     uint8_t ok = 0;
     dev_d2h(&ok, ok_dev, 1);
-    dev_free(B.text);
-    dev_free(B.flags[0]);
-    dev_free(B.segments);
-    dev_free(item_dev);
-    dev_free(ok_dev);
     return ok ? 1 : 0;
   } catch (const std::exception&) {
     return -1;

@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <numeric>
 #include <stdexcept>
 #include <vector>
@@ -25,19 +26,26 @@
 
 namespace brotli_mi355x {
 
-void* dev_alloc(size_t bytes) {
-  void* p = calloc(bytes ? bytes : 16, 1);
+// Block accounting and failure injection (tests/test_device_memory.py): how many blocks are live, how many were ever asked for, and
+// "the k-th allocation from now throws".  Exported from this library only (the brotli_emu_* functions at the end of the file).
+static std::atomic<long> g_live_blocks{0}, g_alloc_count{0}, g_fail_in{0};
+static void* emu_block(size_t bytes, bool zero) {
+  if (bytes == 0) bytes = 16;
+  g_alloc_count++;
+  if (g_fail_in > 0 && --g_fail_in == 0) throw std::runtime_error("emu: injected allocation failure");
+  void* p = zero ? calloc(bytes, 1) : malloc(bytes);
   if (!p) throw std::runtime_error("emu alloc failed");
-  return p;
-}
-void* dev_alloc_uninit(size_t bytes) {
   // poisoned, so that the CPU tests notice a read of something the device build leaves undefined
-  void* p = malloc(bytes ? bytes : 16);
-  if (!p) throw std::runtime_error("emu alloc failed");
-  memset(p, 0xA5, bytes ? bytes : 16);
+  if (!zero) memset(p, 0xA5, bytes);
+  g_live_blocks++;
   return p;
 }
-void dev_free(void* p) { free(p); }
+void* dev_alloc(size_t bytes) { return emu_block(bytes, true); }
+void* dev_alloc_uninit(size_t bytes) { return emu_block(bytes, false); }
+void dev_free(void* p) {
+  if (p) g_live_blocks--;
+  free(p);
+}
 void dev_memset(void* p, int value, size_t bytes) { memset(p, value, bytes); }
 void dev_h2d(void* dst, const void* src, size_t bytes) {
   if (bytes) memcpy(dst, src, bytes);  // (an empty vector hands over a null pointer)
@@ -1018,3 +1026,9 @@ void frag_join(const uint8_t* src, const FragmentPiece* pieces, uint32_t n, uint
 }
 
 }  // namespace brotli_mi355x
+
+extern "C" {
+long brotli_emu_live_blocks() { return brotli_mi355x::g_live_blocks; }
+long brotli_emu_alloc_count() { return brotli_mi355x::g_alloc_count; }
+void brotli_emu_fail_alloc(long k) { brotli_mi355x::g_fail_in = k; }  // the k-th allocation from now throws std::runtime_error; 0 = off
+}
