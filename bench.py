@@ -8,7 +8,12 @@ device-resident time; `output_to_pinned_host` and `e2e` give the PCIe-inclusive 
 N > 1 (one process per GPU under torch.distributed.run): ONE stream of N x 64 MiB compressed with the reference's
 compress_multi split (src/enc/threading/mod.rs:333-411): rank r encodes shard r (its 64 MiB plus the preceding <= 4 MiB
 as LZ77 prefix), the shards are gathered to rank 0 over RCCL and stitched there (BroCatli).  Weak scaling: per-GPU work
-is fixed.  The stitched stream is checked against the CPU oracle's compress_multi (frozen hash for N > 1).
+is fixed.  Under --full the stitched stream is checked against the CPU oracle's compress_multi (frozen hash for N > 1).
+
+A PLAIN run (`bench.py --gpus N --steps K --warmup W`) does only what the headline needs: it sets up, warms up, times the K steps, writes
+--dump-outputs if asked and prints the line with the headline and the roofline block below (which costs no run of its own: the kernel
+counts its work inside the timed steps).  Everything else -- cpu_baseline and the byte comparison with the CPU oracle, the PCIe-inclusive
+steps, the side workloads, config4, the frozen-hash check of N > 1, bench_extras.json -- runs after the headline under --full only.
 
 The ONE stdout line is compact (< 4 KB, tests/test_bench_line.py: round 5's 24.6 KB line never reached the driver's record) and carries
   roofline      k_parse_segments (dominant kernel) against the 8 TB/s HBM peak, from what its launches really did:
@@ -17,14 +22,15 @@ The ONE stdout line is compact (< 4 KB, tests/test_bench_line.py: round 5's 24.6
                 16 B per command; time = HIP events around every launch.  useful_only_frac: one pass over the input / total
                 kernel time; whole_step_frac: SURVEY 8d's full formula / ms_per_step.  traffic: FETCH_SIZE + WRITE_SIZE per launch
                 from the newest profiles/r*_pmc_parse.json taken on the same kernel sources (null otherwise)
+and, under --full,
   cpu_baseline  the CPU oracle (port of the reference path) pinned to one core, same workload; plus Google's
                 libbrotlienc 1.0.9 at the same settings as an independent column
   output_to_pinned_host_ms / e2e_pinned_ms / e2e_c_abi_pageable_ms   the same step with the PCIe copies inside the timed region
   other         digest of the side workloads, {name: [MB/s, x one CPU core of this host, identical to the oracle]}
-The side workloads (N = 1) run in a CHILD process under a wall-clock budget (--extras-budget, default 60 s) after the headline is
+The side workloads (--full, N = 1) run in a CHILD process under a wall-clock budget (--extras-budget, default 60 s) after the headline is
 measured; their full records -- BASELINE configs[2], [4], zero fill, the 1 GiB cut of configs[3], qualities 0-4 / 9.5 / 10 / 11, alice29
 (SURVEY 8d C1), the CompressorWriter pattern without a size hint -- go to bench_extras.json and stderr, never into the stdout line.
-  config4       (N > 1, or --config4) BASELINE configs[3], cut to 1 GiB: Silesia-like mix, BrotliEncoderCompressMulti with
+  config4       (--full; N > 1, or --config4) BASELINE configs[3], cut to 1 GiB: Silesia-like mix, BrotliEncoderCompressMulti with
                 8 shards dealt to the N GPUs -- strong scaling, same stream for every N, verified against the frozen hash.
                 (At the full 4 GiB -- 512 MiB per shard -- the REFERENCE fails on every seed that was tried)
 --dump-outputs DIR writes the compressed stream of the last timed step (rank 0) as .npy files (dump_outputs); the input is seeded, so
@@ -716,17 +722,24 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--mib", type=int, default=WORKLOAD_BYTES >> 20, help="per-GPU batch size in MiB")
     ap.add_argument("--segment-bytes", type=int, default=0, help="bytes per parse chain (0 = the library's choice for the input size)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip other_workloads / config4 / e2e")
-    ap.add_argument("--config4", action="store_true", help="run the 4 GiB config 4 at N = 1 as well (it always runs for N > 1)")
+    ap.add_argument("--full", action="store_true", help="after the headline, measure and check everything else as well: the CPU baseline and the comparison "
+                    "with the CPU oracle, the PCIe-inclusive steps, the side workloads, config 4, bench_extras.json (a plain run does none of it)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip other_workloads / config4 / e2e")
+    ap.add_argument("--config4", action="store_true", help="with --full: run config 4 (cut to 1 GiB) at N = 1 as well (under --full it always runs for N > 1)")
     ap.add_argument("--extras-budget", type=float, default=60.0, help="wall-clock seconds the side workloads may take (they run in a child process)")
     ap.add_argument("--extras-only", action="store_true", help="run the side workloads only and write bench_extras.json")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write the compressed stream of the last timed step to DIR/*.npy")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.config4 and not args.full:
+        ap.error("--config4 is part of the full run: give --full as well")
     if args.extras_only:
         return extras_only(args)
+    # a plain run sets up, warms up, times the steps and prints the line; everything else waits for --full
+    extras = args.full and not args.no_extras
+    cpu_leg = args.full and not args.no_cpu_baseline
 
     import torch
     rank = int(os.environ.get("RANK", "0"))
@@ -836,7 +849,7 @@ def main():
         elapsed = float(tmax.item())
 
     c4 = None
-    if not args.no_extras and (world > 1 or args.config4):
+    if extras and (world > 1 or args.config4):
         try:
             c4 = config4(torch, dist, bm, lib, enc, rank, world, frozen, 1)
         except Exception as e:  # the headline must not die with an extra (every rank takes the same path: no collective is left hanging)
@@ -900,11 +913,11 @@ def main():
                           "by the kernel); time = HIP events around the launches; useful_only = one pass over the input (2N + 64S + 16K) / all "
                           "kernel time; whole_step = SURVEY 8d formula 9N + 64S + 48K + 2L + C per step / ms_per_step",
             "positions_walked_per_step": agg["walked"] / args.steps}
-    if shard_job and world > 1:
+    if args.full and shard_job and world > 1:
         key = "text_%dx64MiB_multi%d_hinted" % (world, world)
         if key in frozen and args.mib == 64:
             line["config"]["identical_to_cpu_oracle"] = hashlib.sha256(comp).hexdigest() == frozen[key]["stream_sha256"]
-    if not args.no_extras and not shard_job:
+    if extras and not shard_job:
         # the step with the stream delivered into page-locked host memory (the headline of rounds 1 and 2)
         sec, _ = timed_steps(lambda: enc.encode(params, b"", dev.data_ptr(), len(chunk), True, copy=False), min(args.steps, 5), 1, torch)
         line["output_to_pinned_host_ms"] = round(sec * 1e3, 3)
@@ -935,14 +948,14 @@ def main():
             del src, dst
         except Exception as e:
             full["e2e_c_abi_error"] = repr(e)
-    if not args.no_cpu_baseline and not shard_job:  # (the CPU leg is reported at N = 1 only)
+    if cpu_leg and not shard_job:  # (the CPU leg is reported at N = 1 only)
         base, ref_bytes = cpu_baseline(stream)
         line["cpu_baseline"] = base
         line["config"]["identical_to_cpu_oracle"] = (ref_bytes == comp)
     if c4 is not None:
         full["config4"] = c4
         line["config4"] = {k: c4.get(k) for k in ("value", "unit", "ms_per_step", "identical_to_cpu_oracle", "scaling", "error") if k in c4}
-    if not args.no_extras and not shard_job:
+    if extras and not shard_job:
         # the side workloads run in a CHILD process under a wall-clock budget: whatever happens there (a crash, a hang cut by the
         # timeout), the line below is printed; their full records go to bench_extras.json and stderr, a digest
         # {name: [MB/s, x one CPU core (oracle on this host), identical to the oracle]} into the line
@@ -970,10 +983,11 @@ def main():
                 line["other_skipped_for_budget"] = len(ex["skipped"])
         except Exception as e:
             full["extras_error"] = full.get("extras_error", "") + " / " + repr(e)
-    try:
-        json.dump(full, open(os.path.join(ROOT, "bench_extras.json"), "w"), indent=1)
-    except Exception:
-        pass
+    if args.full:
+        try:
+            json.dump(full, open(os.path.join(ROOT, "bench_extras.json"), "w"), indent=1)
+        except Exception:
+            pass
     text = final_text(line)
     sys.stderr.flush()
     print(text)

@@ -58,12 +58,57 @@ def test_budget_skips_what_does_not_fit():
     assert b.skipped == ["long"]
 
 
+HEADLINE = ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config", "roofline")
+FULL_ONLY = ("cpu_baseline", "other", "output_to_pinned_host_ms", "e2e_pinned_ms", "e2e_c_abi_pageable_ms", "config4")
+PLAIN_OVERHEAD_S = 30.0  # what a plain run may spend outside its warm-up and timed steps
+
+
+def _bench(*argv):
+    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + list(argv), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+
+
+def test_full_is_an_option_and_config4_belongs_to_it():
+    """(no GPU: the arguments are parsed before anything is imported) --full is there, off by default; --config4 without it is refused"""
+    p = _bench("--help")
+    assert p.returncode == 0 and b"--full" in p.stdout
+    p = _bench("--gpus", "1", "--steps", "1", "--warmup", "0", "--config4")
+    assert p.returncode == 2 and b"--full" in p.stderr
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean():
+    """the driver's command without --full: one line with the headline and nothing that takes a run of its own, no bench_extras.json, and
+    at most PLAIN_OVERHEAD_S of wall time outside the (steps + warmup) steps -- the whole process, start to exit"""
+    import time
+    extras = os.path.join(ROOT, "bench_extras.json")
+    if os.path.exists(extras):
+        os.remove(extras)
+    steps, warmup = 2, 1
+    t0 = time.time()
+    p = _bench("--gpus", "1", "--steps", str(steps), "--warmup", str(warmup))
+    wall = time.time() - t0
+    assert p.returncode == 0, p.stderr.decode()[-4000:]
+    lines = [l for l in p.stdout.decode().splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    j = json.loads(lines[0])
+    for k in HEADLINE:
+        assert k in j, k
+    for k in FULL_ONLY:
+        assert k not in j, k
+    assert "identical_to_cpu_oracle" not in j["config"]
+    assert j["unit"] == "MB/s" and j["higher_is_better"] is True and j["dtype"] == "u8" and j["value"] > 0 and j["roofline"]["frac"] > 0
+    assert not os.path.exists(extras)
+    outside = wall - (steps + warmup) * j["ms_per_step"] * 1e-3
+    print("plain run: %.1f s in all, %.1f s outside its steps" % (wall, outside))
+    assert outside <= PLAIN_OVERHEAD_S, outside
+
+
 @pytest.mark.gpu
 def test_bench_prints_one_compact_parseable_line():
-    """the driver's own command shape, short: the LAST stdout line parses, is below 4 KB and carries roofline + cpu_baseline + the digest;
-    the full records are in bench_extras.json"""
+    """the driver's own command shape with --full, short: the LAST stdout line parses, is below 4 KB and carries roofline + cpu_baseline +
+    the digest; the full records are in bench_extras.json"""
     env = dict(os.environ)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--extras-budget", "12"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--extras-budget", "12"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-4000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.strip()]

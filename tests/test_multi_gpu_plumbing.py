@@ -53,7 +53,7 @@ def test_device_shard_job_world1():
 
 def test_bench_shard_job_path_prints_its_line():
     """bench.py as the driver launches it for N > 1 -- process group on the nccl backend, device-resident shard, gather,
-    stitch, then BASELINE config 4 (cut to 1 GiB, 8 shards dealt to the ranks) -- with a single rank: the code path of the
+    stitch, then (--full) BASELINE config 4 (cut to 1 GiB, 8 shards dealt to the ranks) -- with a single rank: the code path of the
     multi-GPU run is executed on every GPU round, and must print its one JSON line with config 4 verified."""
     import json
     import subprocess
@@ -64,7 +64,7 @@ def test_bench_shard_job_path_prints_its_line():
     env = dict(os.environ, BROTLI_MI355X_BENCH_SHARD_JOB="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--config4", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--config4", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -5,7 +5,7 @@
 #   wtrace    ordered kernel trace of one large workload's last call (tools/step_trace.py)
 #   q01       qualities 0 / 1: -m gpu tests of test_quality_0_1.py and tools/q01_probe.py
 #   suite     the whole -m gpu suite
-#   bench     python bench.py with the driver's defaults
+#   bench     python bench.py --full with the driver's default steps: the headline and everything measured beside it
 #   profile   tools/profile_round.sh (kernel stats + PMC passes of the headline workload)
 # (one script instead of one file per call; the committed summaries live under profiles/)
 WHAT=${1:-probe}; TAG=${2:-r05}
@@ -37,7 +37,7 @@ case $WHAT in
   suite)
     timeout 2400 python -m pytest tests/ -x -q -m gpu > $OUT/${TAG}_gpu_suite.log 2>&1; tail -5 $OUT/${TAG}_gpu_suite.log;;
   bench)
-    timeout 1500 python bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; head -c 700 $OUT/${TAG}_bench.json; echo; tail -3 $OUT/${TAG}_bench.err;;
+    timeout 1500 python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; head -c 700 $OUT/${TAG}_bench.json; echo; tail -3 $OUT/${TAG}_bench.err;;
   profile)
     bash tools/profile_round.sh $TAG $(git -C $ROOT rev-parse --short HEAD 2>/dev/null || echo unknown); tail -5 $OUT/${TAG}_summary.err;;
   *) echo "unknown: $WHAT"; exit 2;;
