@@ -192,6 +192,18 @@ int32_t BrotliMi355xConcatChunkEnds(size_t num_chunks, const uint8_t* heads, con
 BROTLI_BOOL BrotliMi355xCompressDevice(int quality, int lgwin, BrotliEncoderMode mode, size_t input_size,
                                        const uint8_t* input_device, size_t* encoded_size, uint8_t* encoded_host,
                                        double* stats);
+/* Many inputs in one call, each a complete stream of its own: item i gets exactly what
+   BrotliEncoderCompress(quality, lgwin, mode, input_sizes[i], inputs[i], &output_sizes[i], outputs[i]) gives -- bytes, size,
+   success or failure.  output_sizes[i] holds the capacity of outputs[i] on entry and the size of the stream on return.
+   An item that fails (capacity 0, or a buffer too small) fails alone: its size becomes 0 and item_results[i] (may be NULL)
+   becomes 0, the other items are still produced.  Returns 1 if every item succeeded (count == 0 included), 0 otherwise.  A
+   device error fails the whole call: every size becomes 0 and BrotliMi355xLastError says why.  Inputs are host memory.
+   Qualities 0 and 1 run the fragments of all items side by side on the device, with one upload and one download per group of
+   up to 4096 fragments; this is the call for many small payloads.  Every other quality is accepted and runs item by item
+   through the one-shot path on the calling thread: the same bytes, no gain in speed. */
+int32_t BrotliMi355xCompressBatch(int quality, int lgwin, BrotliEncoderMode mode, size_t count, const uint8_t* const* inputs,
+                                  const size_t* input_sizes, uint8_t* const* outputs,
+                                  size_t* output_sizes /* in: capacity, out: size */, int32_t* item_results /* may be NULL */);
 /* Human-readable description of the device backing the library ("hip:gfx950 (...)"). */
 const char* BrotliMi355xDeviceName(void);
 /* Message of the last failure on the calling thread ("" if none). */

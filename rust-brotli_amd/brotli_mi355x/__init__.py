@@ -85,6 +85,9 @@ def _bind(lib):
     lib.BrotliMi355xCompressDevice.restype = c_int
     lib.BrotliMi355xCompressDevice.argtypes = [c_int, c_int, c_int, c_size_t, c_void_p, POINTER(c_size_t), c_char_p,
                                                POINTER(c_double)]
+    lib.BrotliMi355xCompressBatch.restype = c_int32
+    lib.BrotliMi355xCompressBatch.argtypes = [c_int, c_int, c_int, c_size_t, POINTER(c_char_p), POINTER(c_size_t), POINTER(c_void_p),
+                                              POINTER(c_size_t), POINTER(c_int32)]
     lib.BrotliMi355xDeviceName.restype = c_char_p
     lib.BrotliMi355xLastError.restype = c_char_p
     return lib
@@ -163,6 +166,34 @@ class Library(object):
         if not self.lib.BrotliEncoderCompress(quality, lgwin, mode, len(data), data, byref(n), out):
             raise BrotliCompressorException("BrotliEncoderCompress failed: " + self.last_error())
         return ctypes.string_at(out, n.value)
+
+    def compress_batch(self, items, quality=0, lgwin=22, mode=0):
+        """BrotliMi355xCompressBatch: every item becomes a stream of its own, the same bytes as compress(item, quality, lgwin,
+        mode), in one call.  At qualities 0 and 1 all items run side by side on the device (the call for many small payloads);
+        other qualities run item by item.  Returns a list of bytes."""
+        items = [bytes(x) for x in items]
+        count = len(items)
+        if count == 0:
+            return []
+        sizes = [len(x) for x in items]
+        caps = [self.lib.BrotliEncoderMaxCompressedSize(n) + 16 for n in sizes]
+        starts = [0] * count
+        at = 0
+        for i, cap in enumerate(caps):
+            starts[i] = at
+            at += (cap + 15) & ~15
+        out = ctypes.create_string_buffer(at)
+        base = ctypes.addressof(out)
+        inputs = (c_char_p * count)(*items)
+        in_sizes = (c_size_t * count)(*sizes)
+        outputs = (c_void_p * count)(*[base + s for s in starts])
+        out_sizes = (c_size_t * count)(*caps)
+        results = (c_int32 * count)()
+        if not self.lib.BrotliMi355xCompressBatch(quality, lgwin, mode, count, inputs, in_sizes, outputs, out_sizes, results):
+            failed = [i for i in range(count) if not results[i]]
+            raise BrotliCompressorException("BrotliMi355xCompressBatch failed (items %s): %s" % (failed[:8], self.last_error()))
+        view = memoryview(out)
+        return [bytes(view[starts[i]:starts[i] + out_sizes[i]]) for i in range(count)]
 
     def compress_device(self, device_ptr, nbytes, quality=5, lgwin=22, mode=0, out_buffer=None):
         """One-shot compression of `nbytes` at device address `device_ptr` (e.g. tensor.data_ptr()).

@@ -424,7 +424,9 @@ class ShardWorkers {
 // by the device and are not gated.
 class SmallCallGate {
  public:
-  explicit SmallCallGate(size_t input_size) : held_(input_size <= ((size_t)1 << 20) && Seats() != 0) {
+  // caller_is_seated: the call runs inside one that holds a seat already (the items of BrotliMi355xCompressBatch) and takes none
+  explicit SmallCallGate(size_t input_size, bool caller_is_seated = false)
+      : held_(!caller_is_seated && input_size <= ((size_t)1 << 20) && Seats() != 0) {
     if (!held_) return;
     std::unique_lock<std::mutex> lock(Mu());
     Cv().wait(lock, [] { return InFlight() < Seats(); });
@@ -868,17 +870,47 @@ static int CompressOneShotStreamed(int quality, int lgwin, BrotliEncoderMode mod
   return result;
 }
 
-static BROTLI_BOOL CompressOneShot(int quality, int lgwin, BrotliEncoderMode mode, size_t input_size, const uint8_t* input,
-                                   bool input_on_device, size_t* encoded_size, uint8_t* encoded, double* stats_out) {
-  // encoder_compress, encode.rs:1436-1538
-  const size_t out_size = *encoded_size;
-  const size_t max_out_size = MaxCompressedSize(input_size);
-  if (out_size == 0) return BROTLI_FALSE;
+// The cases of encoder_compress that no encoder sees (encode.rs:1436-1466): an output buffer of no bytes fails, an empty input is
+// the one byte of an empty last meta-block.  -1 = neither, otherwise the result of the call.
+static int OneShotWithoutEncoder(size_t input_size, size_t* encoded_size, uint8_t* encoded) {
+  if (*encoded_size == 0) return BROTLI_FALSE;
   if (input_size == 0) {
     *encoded_size = 1;
     encoded[0] = 6;
     return BROTLI_TRUE;
   }
+  return -1;
+}
+
+// What encoder_compress does with the stream its encoder made (encode.rs:1521-1538): it goes out if it fits the buffer and is no
+// larger than BrotliEncoderMaxCompressedSize; otherwise the input goes out as an uncompressed stream if the buffer holds that.
+static BROTLI_BOOL OneShotDeliver(const uint8_t* stream, size_t stream_size, const uint8_t* input, size_t input_size, bool input_on_device,
+                                  size_t out_size, size_t* encoded_size, uint8_t* encoded) {
+  const size_t max_out_size = MaxCompressedSize(input_size);
+  if (stream_size <= out_size && !(max_out_size != 0 && stream_size > max_out_size)) {
+    memcpy(encoded, stream, stream_size);
+    *encoded_size = stream_size;
+    return BROTLI_TRUE;
+  }
+  *encoded_size = 0;
+  if (max_out_size == 0) return BROTLI_FALSE;
+  if (out_size >= max_out_size && !input_on_device) {
+    *encoded_size = MakeUncompressedStream(input, input_size, encoded);
+    return BROTLI_TRUE;
+  }
+  return BROTLI_FALSE;
+}
+
+// batch_item_error != nullptr: the call is an item of BrotliMi355xCompressBatch -- its caller sits in the small-call gate already, and
+// an encoder that throws fails that whole call: the message goes to *batch_item_error and not to the last error
+static BROTLI_BOOL CompressOneShot(int quality, int lgwin, BrotliEncoderMode mode, size_t input_size, const uint8_t* input,
+                                   bool input_on_device, size_t* encoded_size, uint8_t* encoded, double* stats_out,
+                                   std::string* batch_item_error = nullptr) {
+  // encoder_compress, encode.rs:1436-1538
+  const size_t out_size = *encoded_size;
+  const size_t max_out_size = MaxCompressedSize(input_size);
+  const int early = OneShotWithoutEncoder(input_size, encoded_size, encoded);
+  if (early >= 0) return early;
   // encode.rs:1468-1481: the one-shot entry runs quality 10 ("9.5") at quality 9, with an H9 hasher made ahead of time from
   // {q9_5, quality 10} -- the hasher quality 9 selects anyway.  (Quality 10 / 11 through the stream API are Zopfli.)
   if (quality == 10) quality = 9;
@@ -908,7 +940,6 @@ static BROTLI_BOOL CompressOneShot(int quality, int lgwin, BrotliEncoderMode mod
     }
     return BROTLI_FALSE;
   }
-  bool ok = false;
   std::vector<uint8_t> out;
   try {
     EncodeRequest req;
@@ -921,7 +952,7 @@ static BROTLI_BOOL CompressOneShot(int quality, int lgwin, BrotliEncoderMode mod
     req.input_size = input_size;
     req.input_on_device = input_on_device;
     EncodeStats st;
-    SmallCallGate gate(input_size);
+    SmallCallGate gate(input_size, batch_item_error != nullptr);
     if (IsFragmentStream(req.params)) {
       // qualities 0 and 1: compress_stream(FINISH) takes the fragment path (encode.rs:2929-2937)
       if (input_on_device) throw std::runtime_error("qualities 0 and 1 take their input from host memory");
@@ -948,24 +979,12 @@ static BROTLI_BOOL CompressOneShot(int quality, int lgwin, BrotliEncoderMode mod
       stats_out[29] = st.num_segments;
       stats_out[30] = st.segment_bytes;
     }
-    ok = out.size() <= out_size;
   } catch (const std::exception& e) {
-    SetError("BrotliEncoderCompress", e.what());
+    if (batch_item_error) *batch_item_error = e.what(); else SetError("BrotliEncoderCompress", e.what());
     *encoded_size = 0;
     return BROTLI_FALSE;  // no silent fallback for unsupported parameters / missing device
   }
-  if (ok && !(max_out_size != 0 && out.size() > max_out_size)) {
-    memcpy(encoded, out.data(), out.size());
-    *encoded_size = out.size();
-    return BROTLI_TRUE;
-  }
-  *encoded_size = 0;
-  if (max_out_size == 0) return BROTLI_FALSE;
-  if (out_size >= max_out_size && !input_on_device) {
-    *encoded_size = MakeUncompressedStream(input, input_size, encoded);
-    return BROTLI_TRUE;
-  }
-  return BROTLI_FALSE;
+  return OneShotDeliver(out.data(), out.size(), input, input_size, input_on_device, out_size, encoded_size, encoded);
 }
 
 BROTLI_BOOL BrotliEncoderCompress(int quality, int lgwin, BrotliEncoderMode mode, size_t input_size, const uint8_t* input_buffer,
@@ -976,6 +995,65 @@ BROTLI_BOOL BrotliEncoderCompress(int quality, int lgwin, BrotliEncoderMode mode
 BROTLI_BOOL BrotliMi355xCompressDevice(int quality, int lgwin, BrotliEncoderMode mode, size_t input_size,
                                        const uint8_t* input_device, size_t* encoded_size, uint8_t* encoded_host, double* stats) {
   return CompressOneShot(quality, lgwin, mode, input_size, input_device, true, encoded_size, encoded_host, stats);
+}
+
+int32_t BrotliMi355xCompressBatch(int quality, int lgwin, BrotliEncoderMode mode, size_t count, const uint8_t* const* inputs,
+                                  const size_t* input_sizes, uint8_t* const* outputs, size_t* output_sizes, int32_t* item_results) {
+  if (count == 0) return 1;
+  size_t total = 0;
+  for (size_t i = 0; i < count; ++i) total += input_sizes[i];
+  std::vector<int32_t> results(count, 0);
+  try {
+    EncoderParams params;
+    SetParameter(&params, kParamQuality, (uint32_t)quality);
+    SetParameter(&params, kParamLgwin, (uint32_t)lgwin);
+    SetParameter(&params, kParamMode, (uint32_t)mode);
+    if (lgwin > 24) SetParameter(&params, kParamLargeWindow, 1);
+    SmallCallGate gate(total);
+    if (!IsFragmentStream(params)) {
+      // every other quality: item by item through the one-shot path, on this thread (the same bytes, no gain in speed)
+      for (size_t i = 0; i < count; ++i) {
+        std::string error;
+        results[i] = CompressOneShot(quality, lgwin, mode, input_sizes[i], inputs[i], false, &output_sizes[i], outputs[i], nullptr, &error);
+        if (!error.empty()) throw std::runtime_error(error);  // (a device error, not a buffer that is too small: the call fails as a whole)
+        if (!results[i]) output_sizes[i] = 0;
+      }
+    } else {
+      // the items an encoder sees, side by side on the device (fragment_stream.h)
+      std::vector<size_t> item;
+      std::vector<const uint8_t*> in;
+      std::vector<size_t> in_size;
+      for (size_t i = 0; i < count; ++i) {
+        const int early = OneShotWithoutEncoder(input_sizes[i], &output_sizes[i], outputs[i]);
+        if (early >= 0) {
+          results[i] = early;
+          if (!early) output_sizes[i] = 0;
+          continue;
+        }
+        item.push_back(i);
+        in.push_back(inputs[i]);
+        in_size.push_back(input_sizes[i]);
+      }
+      std::vector<std::vector<uint8_t>> streams;
+      if (!item.empty()) FragmentBatchCompress(params, item.size(), in.data(), in_size.data(), &streams);
+      for (size_t k = 0; k < item.size(); ++k) {
+        const size_t i = item[k];
+        results[i] = OneShotDeliver(streams[k].data(), streams[k].size(), inputs[i], input_sizes[i], false, output_sizes[i], &output_sizes[i], outputs[i]);
+      }
+    }
+  } catch (const std::exception& e) {
+    // a device error fails the call as a whole
+    SetError("BrotliMi355xCompressBatch", e.what());
+    for (size_t i = 0; i < count; ++i) output_sizes[i] = 0;
+    if (item_results) memset(item_results, 0, count * sizeof(int32_t));
+    return 0;
+  }
+  int32_t all = 1;
+  for (size_t i = 0; i < count; ++i) {
+    if (item_results) item_results[i] = results[i];
+    if (!results[i]) all = 0;
+  }
+  return all;
 }
 
 int32_t BrotliEncoderCompressMulti(size_t num_params, const BrotliEncoderParameter* param_keys, const uint32_t* param_values,

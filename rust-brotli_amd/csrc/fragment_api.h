@@ -35,6 +35,11 @@ struct FragmentJob {
   uint64_t out_offset;  // byte offset of the fragment's output slot (a multiple of 8; >= 2 * in_size + 520 bytes, first byte zero)
   uint32_t start_bits;  // 0..7: the bit phase the fragment starts with inside its slot
   uint32_t state_in;    // index into states_in of the command code it comes in with (quality 0)
+  // where the fragment's scratch starts in FragmentBuffers: every job has slabs of its own size, so one large fragment among
+  // thousands of small ones costs what it needs and no more
+  uint64_t table_offset;  // words; at least 1 << table_bits of them (unused where the table lives in workgroup memory)
+  uint64_t cmd_offset;    // words (quality 1); at least min(in_size, 1 << 17) + 16 of them
+  uint64_t lit_offset;    // bytes (quality 1); at least min(in_size, 1 << 17) + 64 of them
 };
 
 // What a fragment reports.  Bit positions count from the start of the slot (start_bits included).
@@ -49,26 +54,40 @@ struct FragmentResult {
   uint32_t bad;             // never expected
 };
 
-// Scratch of a batch in device memory: per fragment a hash table (zeroed by frag_compress_batch), and for quality 1 the command
-// and literal buffers of one 128 KiB block (compress_fragment_two_pass.rs:646-703).  Fragment j uses [j * stride, (j + 1) * stride) of each.
+// Scratch of a batch in device memory: per fragment a hash table (zeroed by frag_compress_jobs), and for quality 1 the command
+// and literal buffers of one 128 KiB block (compress_fragment_two_pass.rs:646-703).  Fragment j's share of each starts at
+// its job's offset + j * stride.  The host plan gives every job offsets of its own and leaves the strides 0, and the kernels refuse
+// anything else.  The strides are what is left of the seam this one replaced (equal slabs for all jobs of one stream): the host
+// emulation's own sources still compile a walker of that form, which nothing calls any more.
 struct FragmentBuffers {
-  uint32_t* table = nullptr;     // n x table_stride words, table_stride >= 1 << (largest table_bits of the batch)
-  uint32_t* commands = nullptr;  // n x cmd_stride words (quality 1), cmd_stride >= min(largest fragment, 1 << 17)
-  uint8_t* literals = nullptr;   // n x lit_stride bytes (quality 1), lit_stride >= min(largest fragment, 1 << 17) + 64
+  uint32_t* table = nullptr;
+  uint32_t* commands = nullptr;  // (quality 1)
+  uint8_t* literals = nullptr;   // (quality 1)
   size_t table_stride = 0, cmd_stride = 0, lit_stride = 0;
 };
 
+// The largest table a fragment keeps in workgroup memory: 1 << 11 words, 8 KiB beside 24 KiB of other scratch, which still lets
+// the CU hold the 4 wavefronts its registers allow.  Larger tables cost occupancy, and on the MI355X they did not pay for it
+// (2^12 no gain, 2^13 slower than the device table), so they are not offered.
+enum { kFragmentWorkgroupTableBitsMax = 11 };
+
 // n fragments side by side, one wavefront each: input[job.in_offset, + in_size) (device memory, >= 64 readable bytes behind the
 // last one) is compressed as the reference compresses one fragment and its bits go to out + job.out_offset from bit
-// job.start_bits on.  states_in / states_out: quality 0 only (states_out[j] = the code fragment j leaves behind; may alias nothing).
-void frag_compress_batch(int quality, const uint8_t* input, const FragmentJob* jobs_dev, uint32_t n, const FragmentBuffers& B,
-                         const FragmentState* states_in_dev, FragmentState* states_out_dev, FragmentResult* results_dev, uint8_t* out);
+// job.start_bits on (frag_compress_jobs).  The fragments are jobs[j] for j = order[0 .. n), or j = 0 .. n - 1 where order is null; jobs[j] reports to
+// results[j] and states_out[j].  states_in / states_out: quality 0 only (states_out[j] = the code that fragment leaves behind).
+// workgroup_table_bits != 0: every fragment of the call has table_bits <= workgroup_table_bits <= kFragmentWorkgroupTableBitsMax
+// and keeps its hash table in workgroup memory, zeroed there: B.table is not touched.
+void frag_compress_jobs(int quality, const uint8_t* input, const FragmentJob* jobs_dev, const uint32_t* order_dev, uint32_t n,
+                        uint32_t workgroup_table_bits, const FragmentBuffers& B, const FragmentState* states_in_dev,
+                        FragmentState* states_out_dev, FragmentResult* results_dev, uint8_t* out);
 
 // dst (zeroed) |= bits [src_bit, src_bit + nbits) of src, placed at dst_bit, for every piece.  Pieces do not overlap in dst.
 struct FragmentPiece {
   uint64_t src_bit, dst_bit, nbits;
 };
 void frag_join(const uint8_t* src, const FragmentPiece* pieces_dev, uint32_t n, uint8_t* dst);
+// the same where an upper bound of the pieces' nbits is known (it sizes the grid: thousands of pieces of a few KiB)
+void frag_join_bounded(const uint8_t* src, const FragmentPiece* pieces_dev, uint32_t n, uint8_t* dst, uint64_t longest_bits);
 
 }  // namespace brotli_mi355x
 #endif

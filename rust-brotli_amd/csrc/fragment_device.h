@@ -260,16 +260,36 @@ BR_DEV uint32_t fr2_hash(const uint8_t* p, uint32_t shift, uint32_t length) { re
 BR_DEV bool fr2_is_match(const uint8_t* p1, const uint8_t* p2, uint32_t length) {  // IsMatch :151-155
   return br_load32(p1) == br_load32(p2) && (length == 4 || (p1[4] == p2[4] && p1[5] == p2[5]));
 }
-BR_DEV uint32_t fr_table_get(uint32_t* table, uint32_t h) { return BR_UNIFORM(BR_LIVE_LD32(table + h)); }
-BR_DEV void fr_table_put(uint32_t* table, uint32_t h, uint32_t v) {
-  if (BR_LANE == 0) BR_LIVE_ST32(table + h, v);
+// Where the hash table of a fragment lives: in device memory (its slab of FragmentBuffers; device-scope accesses, served by the
+// L2), or -- a small fragment of a batch -- in the workgroup memory of the wavefront that walks it, whose accesses execute in program
+// order.  The two accessors below are the only places that touch the table.
+struct FrTableDevice {
+  uint32_t* p;
+};
+struct FrTableWorkgroup {
+  uint32_t* p;
+};
+BR_DEV uint32_t fr_table_get(FrTableDevice t, uint32_t h) { return BR_UNIFORM(BR_LIVE_LD32(t.p + h)); }
+BR_DEV void fr_table_put(FrTableDevice t, uint32_t h, uint32_t v) {
+  if (BR_LANE == 0) BR_LIVE_ST32(t.p + h, v);
+}
+BR_DEV uint32_t fr_table_get(FrTableWorkgroup t, uint32_t h) { return BR_UNIFORM(*(volatile uint32_t*)(t.p + h)); }
+BR_DEV void fr_table_put(FrTableWorkgroup t, uint32_t h, uint32_t v) {
+  if (BR_LANE == 0) *(volatile uint32_t*)(t.p + h) = v;
+}
+// a workgroup table is zeroed in place by the wavefront that owns it (a device table by frag_compress_jobs, ahead of the fragments)
+BR_DEV void fr_table_clear(FrTableDevice, uint32_t) {}
+BR_DEV void fr_table_clear(FrTableWorkgroup t, uint32_t table_bits) {
+  for (uint32_t i = BR_LANE; i < (1u << table_bits); i += BR_NLANES) t.p[i] = 0;
+  BR_WAVE_SYNC();
 }
 BR_DEV void fr_copy_literals(uint8_t* dst, const uint8_t* src, uint32_t n) {
   for (uint32_t i = BR_LANE; i < n; i += BR_NLANES) dst[i] = src[i];
 }
 
 // the table updates behind a copy (:262-330): the positions just in front of ip, then the look-up at ip itself
-BR_DEV uint32_t fr2_after_copy(const uint8_t* base_ip, uint32_t ip_index, uint32_t* table, uint32_t shift, uint32_t min_match, bool first) {
+template <typename Table>
+BR_DEV uint32_t fr2_after_copy(const uint8_t* base_ip, uint32_t ip_index, Table table, uint32_t shift, uint32_t min_match, bool first) {
   uint32_t cur_hash;
   if (min_match == 4) {
     const uint64_t input_bytes = br_load64(base_ip + ip_index - 3);
@@ -295,7 +315,8 @@ BR_DEV uint32_t fr2_after_copy(const uint8_t* base_ip, uint32_t ip_index, uint32
 }
 
 // CreateCommands, :157-385.  Returns the number of literals.
-BR_DEV uint32_t fr2_create_commands(uint32_t input_index, uint32_t block_size, uint32_t input_size, const uint8_t* base_ip, uint32_t* table,
+template <typename Table>
+BR_DEV uint32_t fr2_create_commands(uint32_t input_index, uint32_t block_size, uint32_t input_size, const uint8_t* base_ip, Table table,
                                     uint32_t table_bits, uint32_t min_match, uint8_t* literals, FragmentCmds& cmds) {
   uint32_t ip_index = input_index;
   const uint32_t shift = 64 - table_bits;
@@ -512,7 +533,8 @@ struct FragmentDecision {
 };
 
 // compress_fragment_two_pass, :646-703 + 752-905
-BR_DEV void fr2_compress(const EntropyTables& et, const uint8_t* input, uint32_t input_size, bool is_last, uint32_t table_bits, const FragmentBuffers& B,
+template <typename Table>
+BR_DEV void fr2_compress(const EntropyTables& et, const uint8_t* input, uint32_t input_size, bool is_last, Table table, uint32_t table_bits, const FragmentBuffers& B,
                          FragmentScratch& S, FragmentOut& o, FragmentDecision& dec) {
   const uint64_t initial = o.pos;
   if (table_bits >= 8 && table_bits <= 17) {
@@ -523,7 +545,7 @@ BR_DEV void fr2_compress(const EntropyTables& et, const uint8_t* input, uint32_t
       FragmentCmds cmds;
       cmds.at = B.commands;
       cmds.n = 0;
-      const uint32_t num_literals = fr2_create_commands(input_index, block_size, remaining, input, B.table, table_bits, min_match, B.literals, cmds);
+      const uint32_t num_literals = fr2_create_commands(input_index, block_size, remaining, input, table, table_bits, min_match, B.literals, cmds);
       FR_FENCE();  // (what lane 0 wrote is read back by all lanes below)
       if (fr2_should_compress(et, input + input_index, block_size, num_literals, S)) {
         fr_store_meta_block_header(block_size, false, o);
@@ -723,7 +745,8 @@ struct FragmentTreeToCode {  // the serialised command code kept for the next fr
 };
 
 // the table updates behind a copy, :868-878 and :905-915
-BR_DEV uint32_t fr0_after_copy(const uint8_t* input, uint32_t ip_index, uint32_t* table, uint32_t shift) {
+template <typename Table>
+BR_DEV uint32_t fr0_after_copy(const uint8_t* input, uint32_t ip_index, Table table, uint32_t shift) {
   const uint64_t input_bytes = br_load64(input + ip_index - 3);
   const uint32_t cur_hash = BR_UNIFORM(fr0_hash_at(input_bytes, 3, shift));
   fr_table_put(table, fr0_hash_at(input_bytes, 0, shift), ip_index - 3);
@@ -735,7 +758,8 @@ BR_DEV uint32_t fr0_after_copy(const uint8_t* input, uint32_t ip_index, uint32_t
 }
 
 // compress_fragment_fast_impl, :650-1045.  cmd_code (words) / cmd_code_numbits: the command code in serialised form, in and out.
-BR_DEV void fr0_compress_impl(const EntropyTables& et, const uint8_t* input_ptr, uint32_t input_size, bool is_last, uint32_t* table, uint32_t table_bits,
+template <typename Table>
+BR_DEV void fr0_compress_impl(const EntropyTables& et, const uint8_t* input_ptr, uint32_t input_size, bool is_last, Table table, uint32_t table_bits,
                               FragmentScratch& S, uint64_t* cmd_code, uint32_t* cmd_code_numbits, FragmentOut& o) {
   const uint32_t kCmdHistoSeed[128] = {
       0, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1,
@@ -917,7 +941,8 @@ BR_DEV void fr0_compress_impl(const EntropyTables& et, const uint8_t* input_ptr,
 }
 
 // compress_fragment_fast, :1089-1179
-BR_DEV void fr0_compress(const EntropyTables& et, const uint8_t* input, uint32_t input_size, bool is_last, uint32_t table_bits, const FragmentBuffers& B,
+template <typename Table>
+BR_DEV void fr0_compress(const EntropyTables& et, const uint8_t* input, uint32_t input_size, bool is_last, Table table, uint32_t table_bits,
                          FragmentScratch& S, uint64_t* cmd_code, uint32_t* cmd_code_numbits, FragmentOut& o, FragmentDecision& dec) {
   const uint64_t initial = o.pos;
   dec.bits = 0;
@@ -930,7 +955,7 @@ BR_DEV void fr0_compress(const EntropyTables& et, const uint8_t* input, uint32_t
     return;
   }
   if (table_bits == 9 || table_bits == 11 || table_bits == 13 || table_bits == 15)
-    fr0_compress_impl(et, input, input_size, is_last, B.table, table_bits, S, cmd_code, cmd_code_numbits, o);
+    fr0_compress_impl(et, input, input_size, is_last, table, table_bits, S, cmd_code, cmd_code_numbits, o);
   dec.bits = o.pos - initial;
   dec.align = o.first_align;
   if (o.pos - initial > 31 + ((uint64_t)input_size << 3)) {
@@ -944,15 +969,17 @@ BR_DEV void fr0_compress(const EntropyTables& et, const uint8_t* input, uint32_t
   }
 }
 
-// One fragment of a batch (the seam's frag_compress_batch): job j on slab j of B, bits into its own slot of `out`.
-// cmd_code_words: kTreeBitsWords words of workgroup memory.
+// One fragment of a batch (the seam's frag_compress_jobs): job j on its own slabs of B and on `table` (its table slab, or workgroup
+// memory), bits into its own slot of `out`.  cmd_code_words: kTreeBitsWords words of workgroup memory.
+template <typename Table>
 BR_DEV void br_fragment_job(int quality, const EntropyTables& et, const uint8_t* input_base, const FragmentJob& job, uint32_t j, const FragmentBuffers& slabs,
-                            const FragmentState* states_in, FragmentState* states_out, FragmentResult* results, uint8_t* out_base, FragmentScratch& S,
-                            uint64_t* cmd_code_words) {
+                            Table table, const FragmentState* states_in, FragmentState* states_out, FragmentResult* results, uint8_t* out_base,
+                            FragmentScratch& S, uint64_t* cmd_code_words) {
   FragmentBuffers B;
-  B.table = slabs.table + (size_t)j * slabs.table_stride;
-  B.commands = slabs.commands ? slabs.commands + (size_t)j * slabs.cmd_stride : nullptr;
-  B.literals = slabs.literals ? slabs.literals + (size_t)j * slabs.lit_stride : nullptr;
+  B.table = nullptr;
+  B.commands = slabs.commands ? slabs.commands + job.cmd_offset + (size_t)j * slabs.cmd_stride : nullptr;
+  B.literals = slabs.literals ? slabs.literals + job.lit_offset + (size_t)j * slabs.lit_stride : nullptr;
+  fr_table_clear(table, job.table_bits);
   const uint8_t* input = input_base + job.in_offset;
   uint8_t* out = out_base + job.out_offset;
   FragmentOut o;
@@ -978,9 +1005,9 @@ BR_DEV void br_fragment_job(int quality, const EntropyTables& et, const uint8_t*
       for (uint32_t b = 0; b < 8; ++b) w |= (uint64_t)st->cmd_code[8 * i + b] << (8 * b);
       cmd_code_words[i] = w;
     }
-    fr0_compress(et, input, job.in_size, job.is_last != 0, job.table_bits, B, S, cmd_code_words, &numbits, o, dec);
+    fr0_compress(et, input, job.in_size, job.is_last != 0, table, job.table_bits, S, cmd_code_words, &numbits, o, dec);
   } else {
-    fr2_compress(et, input, job.in_size, job.is_last != 0, job.table_bits, B, S, o, dec);
+    fr2_compress(et, input, job.in_size, job.is_last != 0, table, job.table_bits, B, S, o, dec);
   }
   o.park();
   FR_FENCE();
@@ -1004,6 +1031,17 @@ BR_DEV void br_fragment_job(int quality, const EntropyTables& et, const uint8_t*
       for (uint32_t i = 0; i < 512; ++i) st->cmd_code[i] = (uint8_t)(cmd_code_words[i >> 3] >> (8 * (i & 7)));
     }
   }
+}
+
+// the table slab of job j in device memory (FragmentBuffers: offset + j * stride)
+BR_DEV FrTableDevice fr_table_slab(const FragmentBuffers& slabs, const FragmentJob& job, uint32_t j) {
+  return FrTableDevice{slabs.table + job.table_offset + (size_t)j * slabs.table_stride};
+}
+// the same on the job's table slab (zeroed by the caller)
+BR_DEV void br_fragment_job(int quality, const EntropyTables& et, const uint8_t* input_base, const FragmentJob& job, uint32_t j, const FragmentBuffers& slabs,
+                            const FragmentState* states_in, FragmentState* states_out, FragmentResult* results, uint8_t* out_base, FragmentScratch& S,
+                            uint64_t* cmd_code_words) {
+  br_fragment_job(quality, et, input_base, job, j, slabs, fr_table_slab(slabs, job, j), states_in, states_out, results, out_base, S, cmd_code_words);
 }
 
 }  // namespace brotli_mi355x

@@ -9,6 +9,9 @@
 #include <stdexcept>
 
 #include "device_api.h"
+#if defined(BROTLI_HOST_EMU)
+#include "fragment_seam_emu.inc"  // the host emulation of frag_compress_jobs / frag_join_bounded
+#endif
 
 namespace brotli_mi355x {
 
@@ -90,173 +93,323 @@ bool IsFragmentStream(const EncoderParams& user_params) {
 
 namespace {
 
-// The fragments of `size` bytes (cut at 1 << lgwin, as compress_stream_fast cuts one call's input; one block of the ring-buffer path
-// is a single fragment), all fragments of a batch side by side on the device (fragment_api.h); `finish`: the last one carries
-// is_last.  They go in batches of whole fragments (about 256 MiB of input, at least one fragment): device memory stays bounded
-// however much one call hands over.  Whole bytes are appended to *out, the open byte stays in *fs.
-void RunFragments(const EncoderParams& p, FragmentStream* fs, const uint8_t* input, size_t size, bool finish, std::vector<uint8_t>* out) {
+// The largest table_bits a fragment keeps in workgroup memory when it runs in a batch; 0 = never.  One setting per process, read
+// once; by default, and at most, the largest the kernel takes (fragment_api.h).
+uint32_t WorkgroupTableBits() {
+  static const uint32_t v = [] {
+    const char* s = getenv("BROTLI_MI355X_BATCH_LDS_BITS");
+    if (!s) return (uint32_t)kFragmentWorkgroupTableBitsMax;
+    return (uint32_t)std::min<unsigned long>(strtoul(s, nullptr, 10), kFragmentWorkgroupTableBitsMax);
+  }();
+  return v;
+}
+
+// One stream's share of a plan: `size` bytes of input behind what the stream has seen so far; `finish`: its last fragment carries
+// is_last.  Whole bytes of output are appended to *out, the open byte stays in *fs.
+struct FragmentWork {
+  FragmentStream* fs;
+  const uint8_t* input;
+  size_t size;
+  bool finish;
+  std::vector<uint8_t>* out;
+};
+
+// A run of fragments of one stream inside a group, and the group: what goes to the device side by side.
+struct FragmentRun {
+  size_t work;      // index into the plan's work list
+  size_t at, size;  // the input bytes [at, at + size) of that work
+  bool last;        // the run ends the work's input (its last fragment carries is_last if the work finishes the stream)
+  uint32_t first_job = 0, jobs = 0;
+};
+struct FragmentGroup {
+  std::vector<FragmentRun> runs;
+  size_t in_bytes = 0, slot_bytes = 0, table_words = 0, cmd_words = 0, lit_bytes = 0, jobs = 0;
+};
+
+size_t SlotBytes(size_t in_size) { return (2 * in_size + 520 + 63) & ~(size_t)63; }
+
+// The fragments of every work of the list (cut at 1 << lgwin, as compress_stream_fast cuts one call's input; one block of the
+// ring-buffer path is a single fragment), side by side on the device (fragment_api.h), whatever stream they belong to: streams are
+// independent, and the fragments of one stream hang together through the bit position and (quality 0) the command code only.
+// They go in groups of whole fragments: at most 4096 of them, about 256 MiB of input and 512 MiB of per-fragment scratch (hash
+// table + command + literal buffers: about 1.1 MiB per fragment of >= 128 KiB) -- at least one fragment: device memory stays
+// bounded however much one call hands over, slabs and grid dimensions stay bounded when the fragments are tiny.  A stream whose
+// fragments do not fit one group goes on in the next.  Every fragment has scratch of its own size (no stride of the largest), and
+// a fragment whose table is small enough for workgroup memory has no table slab at all.
+void RunFragments(const EncoderParams& p, const std::vector<FragmentWork>& works) {
   const size_t block_size_limit = (size_t)1 << p.lgwin;
   static const size_t batch_target = getenv("BROTLI_MI355X_FRAGMENT_BATCH") ? (size_t)strtoull(getenv("BROTLI_MI355X_FRAGMENT_BATCH"), nullptr, 10) : ((size_t)256 << 20);
   static const bool selftest = getenv("BROTLI_MI355X_SELFTEST") != nullptr;
   static const bool test_again = getenv("BROTLI_MI355X_TEST_FRAGMENT_AGAIN") != nullptr;  // every fragment off phase 0 takes the one-by-one path
-  // (at most 4096 fragments side by side: slabs and grid dimensions stay bounded when the fragments are tiny -- and at most as many as
-  // 512 MiB of per-fragment scratch hold (hash table + command + literal buffers: about 1.1 MiB per fragment of >= 128 KiB): a 256 MiB
-  // call at lgwin 16 otherwise asked for 4096 of them = 2.5 GiB, times the concurrent callers of the library)
-  const size_t table_bytes = ((size_t)1 << TableBits(p.quality, std::min(size, block_size_limit))) * 4;
-  const size_t scratch_per_fragment = table_bytes + (p.quality == 0 ? 0 : 5 * (std::min<size_t>(std::min(size, block_size_limit), (size_t)1 << 17) + 64));
   static const size_t scratch_budget = getenv("BROTLI_MI355X_FRAGMENT_SCRATCH") ? (size_t)strtoull(getenv("BROTLI_MI355X_FRAGMENT_SCRATCH"), nullptr, 10) : ((size_t)512 << 20);
-  const size_t by_scratch = std::max<size_t>(1, scratch_budget / std::max<size_t>(1, scratch_per_fragment));
-  const size_t per_batch = std::min<size_t>(std::min<size_t>(4096, by_scratch), std::max<size_t>(1, batch_target / block_size_limit));
-  const size_t batch_bytes = per_batch * block_size_limit;
-  const size_t in_cap = std::min(size, batch_bytes);
-  const size_t max_jobs = in_cap == 0 ? 1 : (in_cap + block_size_limit - 1) / block_size_limit;
-  auto slot_bytes = [](size_t in_size) { return (2 * in_size + 520 + 63) & ~(size_t)63; };
-  const size_t slots_cap = 2 * in_cap + (520 + 64) * max_jobs + 64;
+  const size_t group_bytes = std::max<size_t>(1, batch_target / block_size_limit) * block_size_limit;
   const bool q0 = p.quality == 0;
-  const size_t largest = std::min(in_cap, block_size_limit);  // (the largest fragment of the call)
+  // (a single stream keeps the kernel it always had: the workgroup table is for the small items of a batch)
+  const uint32_t wg_bits = works.size() > 1 ? WorkgroupTableBits() : 0;
+  auto table_words_of = [&](size_t block_size) {
+    const uint32_t bits = TableBits(p.quality, block_size);
+    return bits <= wg_bits ? (size_t)0 : (size_t)1 << bits;
+  };
+  auto cmd_words_of = [&](size_t block_size) { return q0 ? (size_t)0 : (std::min<size_t>(block_size, (size_t)1 << 17) + 16 + 3) & ~(size_t)3; };
+  auto lit_bytes_of = [&](size_t block_size) { return q0 ? (size_t)0 : (std::min<size_t>(block_size, (size_t)1 << 17) + 64 + 15) & ~(size_t)15; };
+  // ---- the plan: groups of runs
+  std::vector<FragmentGroup> groups;
+  for (size_t w = 0; w < works.size(); ++w) {
+    const FragmentWork& work = works[w];
+    size_t at = 0;
+    for (;;) {
+      const size_t block_size = std::min(block_size_limit, work.size - at);
+      const bool ends = at + block_size == work.size;
+      if (block_size == 0 && !(ends && work.finish)) break;
+      const size_t scratch = 4 * table_words_of(block_size) + 4 * cmd_words_of(block_size) + lit_bytes_of(block_size);
+      if (groups.empty() || groups.back().jobs == 4096 ||
+          (groups.back().jobs != 0 && (groups.back().in_bytes + block_size > group_bytes ||
+                                       4 * groups.back().table_words + 4 * groups.back().cmd_words + groups.back().lit_bytes + scratch > scratch_budget)))
+        groups.emplace_back();
+      FragmentGroup& g = groups.back();
+      if (g.runs.empty() || g.runs.back().work != w) g.runs.push_back({w, at, 0, false, (uint32_t)g.jobs, 0});
+      FragmentRun& run = g.runs.back();
+      run.size += block_size;
+      run.jobs++;
+      run.last = ends;
+      g.jobs++;
+      g.in_bytes += block_size;
+      g.slot_bytes += SlotBytes(block_size);
+      g.table_words += table_words_of(block_size);
+      g.cmd_words += cmd_words_of(block_size);
+      g.lit_bytes += lit_bytes_of(block_size);
+      at += block_size;
+      if (ends) break;
+    }
+  }
+  if (groups.empty()) return;
+  // ---- device memory of the largest group, once
+  FragmentGroup cap;
+  size_t max_runs = 0;
+  for (const FragmentGroup& g : groups) {
+    cap.in_bytes = std::max(cap.in_bytes, g.in_bytes);
+    cap.slot_bytes = std::max(cap.slot_bytes, g.slot_bytes);
+    cap.table_words = std::max(cap.table_words, g.table_words);
+    cap.cmd_words = std::max(cap.cmd_words, g.cmd_words);
+    cap.lit_bytes = std::max(cap.lit_bytes, g.lit_bytes);
+    cap.jobs = std::max(cap.jobs, g.jobs);
+    max_runs = std::max(max_runs, g.runs.size());
+  }
+  const size_t max_jobs = cap.jobs;
   FragmentBuffers B;
-  B.table_stride = (size_t)1 << TableBits(p.quality, largest);
-  B.cmd_stride = std::min<size_t>(largest, (size_t)1 << 17) + 16;
-  B.lit_stride = std::min<size_t>(largest, (size_t)1 << 17) + 64;
   DevBlocks mem;
-  uint8_t* const in = mem.zeroed<uint8_t>(in_cap + 64);
-  uint8_t* const slots = mem.uninit<uint8_t>(slots_cap + 64);
-  B.table = mem.uninit<uint32_t>(max_jobs * B.table_stride * 4 + 64);
-  uint32_t* const commands = mem.uninit<uint32_t>(q0 ? 64 : max_jobs * B.cmd_stride * 4 + 64);
-  uint8_t* const literals = mem.uninit<uint8_t>(q0 ? 64 : max_jobs * B.lit_stride + 64);
+  uint8_t* const in = mem.zeroed<uint8_t>(cap.in_bytes + 64);
+  // (behind the slots: the open bytes the runs come in with, 8 bytes each -- they are joined like any other piece)
+  uint8_t* const slots = mem.uninit<uint8_t>(cap.slot_bytes + 8 * max_runs + 64);
+  B.table = mem.uninit<uint32_t>(cap.table_words * 4 + 64);
+  uint32_t* const commands = mem.uninit<uint32_t>(cap.cmd_words * 4 + 64);
+  uint8_t* const literals = mem.uninit<uint8_t>(cap.lit_bytes + 64);
   B.commands = q0 ? nullptr : commands;
   B.literals = q0 ? nullptr : literals;
-  FragmentState* const sa = mem.uninit<FragmentState>((max_jobs + 1) * sizeof(FragmentState) + 64);  // [0] the code the batch comes in with, [j + 1] what fragment j leaves behind (pass A)
+  // quality 0: [0, K) the distinct codes the runs come in with, [K + a] what fragment a of pass A leaves behind
+  FragmentState* const sa = mem.uninit<FragmentState>((max_jobs + max_runs) * sizeof(FragmentState) + 64);
   FragmentState* const sb = mem.uninit<FragmentState>(max_jobs * sizeof(FragmentState) + 64);  // what fragment j leaves behind (pass B)
   FragmentJob* const jobs_dev = mem.uninit<FragmentJob>(max_jobs * sizeof(FragmentJob) + 64);
+  uint32_t* const order_dev = mem.uninit<uint32_t>(max_jobs * sizeof(uint32_t) + 64);
   FragmentResult* const results_dev = mem.uninit<FragmentResult>(max_jobs * sizeof(FragmentResult) + 64);
-  FragmentPiece* const pieces_dev = mem.uninit<FragmentPiece>(2 * max_jobs * sizeof(FragmentPiece) + 64);
-  size_t done = 0;
-  bool more = true;
-  std::vector<FragmentJob> jobs;
+  FragmentPiece* const pieces_dev = mem.uninit<FragmentPiece>((2 * max_jobs + max_runs) * sizeof(FragmentPiece) + 64);
+  std::vector<FragmentJob> jobs, pass_a;
+  std::vector<uint32_t> a_of_job, order;
+  std::vector<FragmentState> incoming;
+  std::vector<uint32_t> incoming_of_run;
   std::vector<FragmentResult> results;
   std::vector<FragmentPiece> pieces;
-  std::vector<uint8_t> bytes;
-  while (more) {
-    const size_t here = std::min(size - done, batch_bytes);
-    if (here) dev_h2d_bulk(in, input + done, here);
-    // ---- the fragments of this batch
-    jobs.clear();
-    size_t at = 0, slot_at = 0;
-    for (;;) {
-      const size_t block_size = std::min(block_size_limit, here - at);
-      const bool is_last = (size - done - at == block_size) && finish;
-      if (block_size == 0 && !is_last) break;
-      FragmentJob job;
-      job.in_offset = (uint32_t)at;
-      job.in_size = (uint32_t)block_size;
-      job.is_last = is_last ? 1u : 0u;
-      job.table_bits = TableBits(p.quality, block_size);
-      job.out_offset = slot_at;
-      job.start_bits = 0;
-      job.state_in = 0;
-      jobs.push_back(job);
-      slot_at += slot_bytes(block_size);
-      at += block_size;
-      if (is_last || at == here) break;
+  std::vector<uint8_t> staged, heads, bytes;
+  std::vector<uint64_t> run_base, run_end;
+  // the fragments of `list` (uploaded to jobs_dev), class by class: the small ones on workgroup tables, the rest on their slabs
+  auto launch = [&](int quality, const std::vector<FragmentJob>& list, const FragmentState* states_in, FragmentState* states_out) {
+    const uint32_t n = (uint32_t)list.size();
+    dev_h2d(jobs_dev, list.data(), (size_t)n * sizeof(FragmentJob));
+    uint32_t classes[kFragmentWorkgroupTableBitsMax + 2] = {0};  // [0] device tables, [b] workgroup tables of b bits
+    auto class_of = [&](const FragmentJob& job) { return job.table_bits <= wg_bits ? job.table_bits : 0u; };
+    for (const FragmentJob& job : list) classes[class_of(job)]++;
+    if (classes[0] == n) {
+      frag_compress_jobs(quality, in, jobs_dev, nullptr, n, 0, B, states_in, states_out, results_dev, slots);
+      return;
     }
-    done += here;
-    more = done < size;
-    const uint32_t n = (uint32_t)jobs.size();
-    if (n == 0) break;
-    if (slot_at > slots_cap) throw std::runtime_error("brotli_mi355x: fragment output ran over its bound");
-    // ---- side by side, each into its own slot from bit 0 on
-    if (q0) {
-      // the command code a fragment leaves behind is built from the commands of its own last block, whatever code it came in
-      // with (compress_fragment.rs:1033-1044): pass A runs every fragment but the last with the batch's incoming code to learn
-      // what each leaves behind, pass B runs them all with the right incoming codes
-      dev_h2d(sa, &fs->state, sizeof(FragmentState));
-      if (n > 1) {
-        dev_h2d(jobs_dev, jobs.data(), (size_t)(n - 1) * sizeof(FragmentJob));
-        frag_compress_batch(0, in, jobs_dev, n - 1, B, sa, sa + 1, results_dev, slots);
+    uint32_t first[kFragmentWorkgroupTableBitsMax + 2], fill[kFragmentWorkgroupTableBitsMax + 2];
+    for (uint32_t c = 0, at = 0; c < kFragmentWorkgroupTableBitsMax + 2; at += classes[c], ++c) first[c] = fill[c] = at;
+    order.resize(n);
+    for (uint32_t j = 0; j < n; ++j) order[fill[class_of(list[j])]++] = j;
+    dev_h2d(order_dev, order.data(), (size_t)n * sizeof(uint32_t));
+    for (uint32_t c = 0; c < kFragmentWorkgroupTableBitsMax + 2; ++c)
+      if (classes[c]) frag_compress_jobs(quality, in, jobs_dev, order_dev + first[c], classes[c], c, B, states_in, states_out, results_dev, slots);
+  };
+  for (const FragmentGroup& g : groups) {
+    const uint32_t n = (uint32_t)g.jobs, n_runs = (uint32_t)g.runs.size();
+    // ---- staging: one upload, every run at its own offset
+    if (g.in_bytes) {
+      if (n_runs == 1) {
+        dev_h2d_bulk(in, works[g.runs[0].work].input + g.runs[0].at, g.in_bytes);
+      } else {
+        staged.resize(g.in_bytes);
+        size_t at = 0;
+        for (const FragmentRun& run : g.runs) {
+          if (run.size) memcpy(staged.data() + at, works[run.work].input + run.at, run.size);
+          at += run.size;
+        }
+        dev_h2d_bulk(in, staged.data(), g.in_bytes);
       }
-      for (uint32_t j = 0; j < n; ++j) jobs[j].state_in = j;
     }
-    dev_h2d(jobs_dev, jobs.data(), (size_t)n * sizeof(FragmentJob));
-    frag_compress_batch(p.quality, in, jobs_dev, n, B, sa, q0 ? sb : nullptr, results_dev, slots);
+    // ---- the fragments of this group
+    jobs.clear();
+    pass_a.clear();
+    a_of_job.assign(n, ~0u);
+    incoming.clear();
+    incoming_of_run.clear();
+    size_t at = 0, slot_at = 0, table_at = 0, cmd_at = 0, lit_at = 0;
+    for (const FragmentRun& run : g.runs) {
+      const FragmentWork& work = works[run.work];
+      if (q0) {
+        if (incoming.empty() || memcmp(&incoming.back(), &work.fs->state, sizeof(FragmentState)) != 0) incoming.push_back(work.fs->state);
+        incoming_of_run.push_back((uint32_t)incoming.size() - 1);
+      }
+      size_t left = run.size;
+      for (uint32_t k = 0; k < run.jobs; ++k) {
+        const size_t block_size = std::min(block_size_limit, left);
+        FragmentJob job;
+        job.in_offset = (uint32_t)at;
+        job.in_size = (uint32_t)block_size;
+        job.is_last = (run.last && work.finish && k + 1 == run.jobs) ? 1u : 0u;
+        job.table_bits = TableBits(p.quality, block_size);
+        job.out_offset = slot_at;
+        job.start_bits = 0;
+        job.state_in = q0 ? incoming_of_run.back() : 0;
+        job.table_offset = table_at;
+        job.cmd_offset = cmd_at;
+        job.lit_offset = lit_at;
+        // the command code a fragment leaves behind is built from the commands of its own last block, whatever code it came in
+        // with (compress_fragment.rs:1033-1044): pass A runs every fragment that has a successor in its run with the run's
+        // incoming code to learn what each leaves behind, pass B runs them all with the right incoming codes.  (A stream of a
+        // single fragment needs no pass A.)
+        if (q0 && k + 1 < run.jobs) {
+          a_of_job[jobs.size()] = (uint32_t)pass_a.size();
+          pass_a.push_back(job);
+        }
+        jobs.push_back(job);
+        slot_at += SlotBytes(block_size);
+        table_at += table_words_of(block_size);
+        cmd_at += cmd_words_of(block_size);
+        lit_at += lit_bytes_of(block_size);
+        at += block_size;
+        left -= block_size;
+      }
+    }
+    if (jobs.size() != n || slot_at > cap.slot_bytes || table_at > cap.table_words || cmd_at > cap.cmd_words || lit_at > cap.lit_bytes || at > cap.in_bytes)
+      throw std::runtime_error("brotli_mi355x: fragment plan ran over its bound");
+    // ---- side by side, each into its own slot from bit 0 on
+    const uint32_t K = (uint32_t)incoming.size();
+    if (q0) {
+      dev_h2d(sa, incoming.data(), (size_t)K * sizeof(FragmentState));
+      if (!pass_a.empty()) launch(0, pass_a, sa, sa + K);
+      for (uint32_t j = 0; j < n; ++j)
+        if (j > 0 && a_of_job[j - 1] != ~0u) jobs[j].state_in = K + a_of_job[j - 1];
+    }
+    launch(p.quality, jobs, sa, q0 ? sb : nullptr);
     results.resize(n);
     dev_d2h(results.data(), results_dev, (size_t)n * sizeof(FragmentResult));
-    if (q0 && selftest && n > 1) {
-      std::vector<FragmentState> a(n + 1), b(n);
-      dev_d2h(a.data(), sa, (size_t)(n + 1) * sizeof(FragmentState));
+    if (q0 && selftest && !pass_a.empty()) {
+      std::vector<FragmentState> a(pass_a.size()), b(n);
+      dev_d2h(a.data(), sa + K, a.size() * sizeof(FragmentState));
       dev_d2h(b.data(), sb, (size_t)n * sizeof(FragmentState));
-      for (uint32_t j = 0; j + 1 < n; ++j)
-        if (memcmp(&a[j + 1], &b[j], sizeof(FragmentState)) != 0) throw std::runtime_error("brotli_mi355x selftest: the command code a quality 0 fragment leaves behind depends on the code it came in with");
+      for (uint32_t j = 0; j < n; ++j)
+        if (a_of_job[j] != ~0u && memcmp(&a[a_of_job[j]], &b[j], sizeof(FragmentState)) != 0) throw std::runtime_error("brotli_mi355x selftest: the command code a quality 0 fragment leaves behind depends on the code it came in with");
     }
-    // ---- where the slots go in the stream.  A fragment's bits move with the phase up to its first jump to a byte boundary; what
+    // ---- where the slots go in the streams.  A fragment's bits move with the phase up to its first jump to a byte boundary; what
     // comes behind lands on whole bytes.  The padding of that jump is the one thing of a fragment that depends on the phase, and it
     // reaches one decision -- "larger than stored raw?", which counts output bits: where the true phase turns that decision around,
-    // the fragment is compressed again by itself at its true phase.
+    // the fragment is compressed again by itself at its true phase.  Every run has its own stretch of the joined buffer, which
+    // starts with the open byte its stream comes in with.
     pieces.clear();
-    uint64_t cur = fs->last_bytes_bits;
-    for (uint32_t j = 0; j < n; ++j) {
-      FragmentResult r = results[j];
-      if (r.bad) throw std::runtime_error("brotli_mi355x: fragment compressor failed");
-      const uint32_t phase = (uint32_t)(cur & 7u);
-      const uint64_t slot_bit = jobs[j].out_offset * 8;
-      bool again = false;
-      if (phase != 0 && r.decision_align != ~0ull) {
-        const uint64_t a = r.decision_align;
-        const uint64_t pad0 = (8 - (a & 7)) & 7, padt = (8 - ((phase + a) & 7)) & 7;
-        const uint64_t total = r.decision_bits - pad0 + padt;
-        const bool fall_back = total > 31 + ((uint64_t)jobs[j].in_size << 3);
-        again = fall_back != (r.fell_back != 0);
+    heads.assign((size_t)8 * n_runs, 0);
+    run_base.assign(n_runs, 0);
+    run_end.assign(n_runs, 0);
+    const size_t heads_at = (cap.slot_bytes + 7) & ~(size_t)7;
+    uint64_t joined_bytes = 0, longest = 0;
+    for (uint32_t r = 0; r < n_runs; ++r) {
+      const FragmentRun& run = g.runs[r];
+      FragmentStream* const fs = works[run.work].fs;
+      const uint64_t base = joined_bytes * 8;
+      run_base[r] = base;
+      heads[(size_t)8 * r] = (uint8_t)fs->last_bytes;
+      heads[(size_t)8 * r + 1] = (uint8_t)(fs->last_bytes >> 8);
+      if (fs->last_bytes_bits) pieces.push_back({(uint64_t)(heads_at + 8 * r) * 8, base, fs->last_bytes_bits});
+      uint64_t cur = base + fs->last_bytes_bits;
+      for (uint32_t j = run.first_job; j < run.first_job + run.jobs; ++j) {
+        FragmentResult res = results[j];
+        if (res.bad) throw std::runtime_error("brotli_mi355x: fragment compressor failed");
+        const uint32_t phase = (uint32_t)(cur & 7u);
+        const uint64_t slot_bit = jobs[j].out_offset * 8;
+        bool again = false;
+        if (phase != 0 && res.decision_align != ~0ull) {
+          const uint64_t a = res.decision_align;
+          const uint64_t pad0 = (8 - (a & 7)) & 7, padt = (8 - ((phase + a) & 7)) & 7;
+          const uint64_t total = res.decision_bits - pad0 + padt;
+          const bool fall_back = total > 31 + ((uint64_t)jobs[j].in_size << 3);
+          again = fall_back != (res.fell_back != 0);
+        }
+        if (test_again && phase != 0) again = true;
+        if (again) {
+          if (getenv("BROTLI_MI355X_DEBUG")) fprintf(stderr, "fragment %u of %u: compressed again at phase %u (the raw fall-back hangs on the padding)\n", j, n, phase);
+          // (by itself, where it sat: its slabs, its incoming code, its result slot)
+          FragmentJob one = jobs[j];
+          one.start_bits = phase;
+          dev_h2d(jobs_dev + j, &one, sizeof(FragmentJob));
+          frag_compress_jobs(p.quality, in, jobs_dev + j, nullptr, 1, one.table_bits <= wg_bits ? one.table_bits : 0, B, sa, q0 ? sb + j : nullptr,
+                             results_dev + j, slots);
+          dev_d2h(&res, results_dev + j, sizeof(FragmentResult));
+          if (res.bad) throw std::runtime_error("brotli_mi355x: fragment compressor failed");
+          pieces.push_back({slot_bit + phase, cur, res.end_bits - phase});
+          cur += res.end_bits - phase;
+          longest = std::max(longest, res.end_bits);
+          continue;
+        }
+        longest = std::max(longest, res.end_bits);
+        if (res.first_align == ~0ull) {
+          pieces.push_back({slot_bit, cur, res.end_bits});
+          cur += res.end_bits;
+        } else {
+          const uint64_t a = res.first_align, a8 = (a + 7) & ~(uint64_t)7;
+          if (a) pieces.push_back({slot_bit, cur, a});
+          const uint64_t aligned = (cur + a + 7) & ~(uint64_t)7;
+          if (res.end_bits > a8) pieces.push_back({slot_bit + a8, aligned, res.end_bits - a8});
+          cur = aligned + (res.end_bits - a8);
+        }
       }
-      if (test_again && phase != 0) again = true;
-      if (again) {
-        if (getenv("BROTLI_MI355X_DEBUG")) fprintf(stderr, "fragment %u of %u: compressed again at phase %u (the raw fall-back hangs on the padding)\n", j, n, phase);
-        // (as fragment 0 of a batch of one that sits where fragment j sat: its table slab, its incoming code, its result slot)
-        FragmentJob one = jobs[j];
-        one.start_bits = phase;
-        one.state_in = 0;
-        dev_h2d(jobs_dev + j, &one, sizeof(FragmentJob));
-        FragmentBuffers Bj = B;
-        Bj.table += (size_t)j * B.table_stride;
-        if (Bj.commands) Bj.commands += (size_t)j * B.cmd_stride;
-        if (Bj.literals) Bj.literals += (size_t)j * B.lit_stride;
-        frag_compress_batch(p.quality, in, jobs_dev + j, 1, Bj, sa + j, q0 ? sb + j : nullptr, results_dev + j,
-                            slots);
-        dev_d2h(&r, results_dev + j, sizeof(FragmentResult));
-        if (r.bad) throw std::runtime_error("brotli_mi355x: fragment compressor failed");
-        pieces.push_back({slot_bit + phase, cur, r.end_bits - phase});
-        cur += r.end_bits - phase;
-        continue;
-      }
-      if (r.first_align == ~0ull) {
-        pieces.push_back({slot_bit, cur, r.end_bits});
-        cur += r.end_bits;
-      } else {
-        const uint64_t a = r.first_align, a8 = (a + 7) & ~(uint64_t)7;
-        if (a) pieces.push_back({slot_bit, cur, a});
-        const uint64_t aligned = (cur + a + 7) & ~(uint64_t)7;
-        if (r.end_bits > a8) pieces.push_back({slot_bit + a8, aligned, r.end_bits - a8});
-        cur = aligned + (r.end_bits - a8);
-      }
+      run_end[r] = cur;
+      joined_bytes = (((cur >> 3) + 2) + 7) & ~(uint64_t)7;
+      // (the code the stream goes on with: only a stream that has not finished needs it)
+      if (q0 && run.jobs != 0 && !(run.last && works[run.work].finish)) dev_d2h(&fs->state, sb + (run.first_job + run.jobs - 1), sizeof(FragmentState));
     }
-    if (q0) dev_d2h(&fs->state, sb + (n - 1), sizeof(FragmentState));
-    // ---- the join
-    const uint64_t ix = cur;
-    const size_t joined_bytes = (size_t)(ix >> 3) + 2;
+    // ---- the join, and every stream of the group back in one download
     DevBlocks join_mem;
-    uint8_t* const joined = join_mem.zeroed<uint8_t>(((joined_bytes + 7) & ~(size_t)7) + 64);
-    uint8_t head[2] = {(uint8_t)fs->last_bytes, (uint8_t)(fs->last_bytes >> 8)};
-    dev_h2d(joined, head, 2);
+    uint8_t* const joined = join_mem.zeroed<uint8_t>((size_t)joined_bytes + 64);
     if (!pieces.empty()) {
+      dev_h2d(slots + heads_at, heads.data(), heads.size());
       dev_h2d(pieces_dev, pieces.data(), pieces.size() * sizeof(FragmentPiece));
-      frag_join(slots, pieces_dev, (uint32_t)pieces.size(), joined);
+      frag_join_bounded(slots, pieces_dev, (uint32_t)pieces.size(), joined, longest);
     }
-    bytes.resize(joined_bytes);
+    bytes.resize((size_t)joined_bytes);
     dev_d2h_bulk(bytes.data(), joined, bytes.size());
-    out->insert(out->end(), bytes.begin(), bytes.begin() + (ptrdiff_t)(ix >> 3));
-    fs->last_bytes = (uint16_t)(bytes[(size_t)(ix >> 3)] | (bytes[(size_t)(ix >> 3) + 1] << 8));
-    fs->last_bytes_bits = (uint8_t)(ix & 7);
-    if (fs->last_bytes_bits != 0) fs->last_bytes &= (uint16_t)((1u << fs->last_bytes_bits) - 1u); else fs->last_bytes = 0;
+    for (uint32_t r = 0; r < n_runs; ++r) {
+      const FragmentWork& work = works[g.runs[r].work];
+      FragmentStream* const fs = work.fs;
+      const size_t from = (size_t)(run_base[r] >> 3), to = (size_t)(run_end[r] >> 3);
+      work.out->insert(work.out->end(), bytes.begin() + (ptrdiff_t)from, bytes.begin() + (ptrdiff_t)to);
+      fs->last_bytes = (uint16_t)(bytes[to] | (bytes[to + 1] << 8));
+      fs->last_bytes_bits = (uint8_t)(run_end[r] & 7);
+      if (fs->last_bytes_bits != 0) fs->last_bytes &= (uint16_t)((1u << fs->last_bytes_bits) - 1u); else fs->last_bytes = 0;
+    }
   }
+}
+
+void RunFragments(const EncoderParams& p, FragmentStream* fs, const uint8_t* input, size_t size, bool finish, std::vector<uint8_t>* out) {
+  RunFragments(p, std::vector<FragmentWork>{{fs, input, size, finish, out}});
 }
 
 // inject_byte_padding_block, encode.rs:1541-1566: an empty metadata block seals the open byte
@@ -316,6 +469,20 @@ void FragmentStreamCompress(const EncoderParams& user_params, FragmentStream* fs
   Start(p, fs);
   if (size != 0 || finish) RunFragments(p, fs, input, size, finish, out);
   if (flush) InjectPadding(fs, out);
+}
+
+void FragmentBatchCompress(const EncoderParams& user_params, size_t count, const uint8_t* const* inputs, const size_t* sizes,
+                           std::vector<std::vector<uint8_t>>* outs) {
+  EncoderParams p = user_params;
+  FinalizeParams(&p);
+  std::vector<FragmentStream> streams(count);
+  std::vector<FragmentWork> works(count);
+  outs->assign(count, std::vector<uint8_t>());
+  for (size_t i = 0; i < count; ++i) {
+    Start(p, &streams[i]);
+    works[i] = {&streams[i], inputs[i], sizes[i], true, &(*outs)[i]};
+  }
+  RunFragments(p, works);
 }
 
 bool IsFragmentRing(const EncoderParams& user_params) {

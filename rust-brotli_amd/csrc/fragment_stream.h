@@ -42,6 +42,12 @@ void FragmentRingCompress(const EncoderParams& user_params, FragmentStream* fs, 
 // (the byte-alignment block behind the data, encode.rs:1541-1566), neither = PROCESS.  Whole bytes of output are appended to *out.
 void FragmentStreamCompress(const EncoderParams& user_params, FragmentStream* fs, const uint8_t* input, size_t size, bool finish, bool flush,
                             std::vector<uint8_t>* out);
+// `count` inputs, each a complete stream of its own -- (*outs)[i] is what FragmentStreamCompress(..., inputs[i], sizes[i], finish) gives
+// on a fresh stream -- with the fragments of all of them side by side on the device: one plan, one upload, one join and one download
+// per group of fragments.  Small fragments keep their hash table in workgroup memory (BROTLI_MI355X_BATCH_LDS_BITS: the largest
+// table_bits that do, 0 = none; read once).
+void FragmentBatchCompress(const EncoderParams& user_params, size_t count, const uint8_t* const* inputs, const size_t* sizes,
+                           std::vector<std::vector<uint8_t>>* outs);
 // BROTLI_OPERATION_EMIT_METADATA on a catable stream of these qualities: process_metadata (encode.rs:2579-2685) has encode_data flush
 // "pending" input until input_pos_ == last_flush_pos_ -- which the quality 0 / 1 branch moves by the raw first bytes only.  True if
 // the reference returns from that loop: everything received so far is (or, after the forced flush, will be) raw first bytes.

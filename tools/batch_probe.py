@@ -1,0 +1,257 @@
+#!/usr/bin/env python3
+"""tools/batch_probe.py -- what BrotliMi355xCompressBatch buys for many small payloads (qualities 0 and 1, lgwin 22).
+
+For every class of items (seeded markov text and synth.mixed):
+  batch     the batch call on all items (host clock around the synchronous call, warm-up, median and spread of the repeats)
+  loop      the same items as a loop of BrotliEncoderCompress from 1 and from 4 threads, on the library given with --parent-lib (a
+            build of the parent commit) -- on the first --loop-items items of the class, scaled to the class by item count
+  cpu       the oracle (oracle/liborc_fast.so) on one core of the same host, on the same first items, scaled likewise
+            (the items of a class are independent draws, so the first ones are a fair sample of it)
+and the A/B of the two homes of a small fragment's hash table: the classes whose tables fit workgroup memory -- 512 B items (2^9
+words) and 2 KiB items (2^11 words) -- and the log-uniform mix, with BROTLI_MI355X_BATCH_LDS_BITS=0 and =11, alternating.
+
+Every measurement runs in a child process of its own (the table's home is one setting per process, read once; the parent's library
+is another shared object), one after the other, each under its own time limit; the first failure ends the probe.
+
+  python tools/batch_probe.py --parent-lib <libbrotli_mi355x.so of the parent commit> --out profiles/r07_batch_q01.json
+"""
+import argparse
+import ctypes
+import json
+import os
+import random
+import statistics
+import subprocess
+import sys
+import threading
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+LGWIN = 22
+
+CLASSES = {
+    "4096x4KiB": ("uniform", 4096, 4 << 10),
+    "4096x16KiB": ("uniform", 4096, 16 << 10),
+    "1024x64KiB": ("uniform", 1024, 64 << 10),
+    "64xalice29": ("alice", 64, 0),
+    "4096xlog200B-256KiB": ("log", 4096, 0),
+    # one table size each (the A/B of the table's home)
+    "4096x512B": ("uniform", 4096, 512),
+    "4096x2KiB": ("uniform", 4096, 2 << 10),
+}
+HEADLINE = ["4096x4KiB", "4096x16KiB", "1024x64KiB", "64xalice29", "4096xlog200B-256KiB"]
+AB = ["4096x512B", "4096x2KiB", "4096xlog200B-256KiB"]
+
+
+def items_of(name, data):
+    import synth
+    kind, count, size = CLASSES[name]
+    if kind == "alice":
+        return [synth.alice()] * count
+    rng = random.Random(17)
+    pool = synth.markov_text(8 << 20, 5) if data == "text" else synth.mixed(8 << 20, 5)
+    out = []
+    for _ in range(count):
+        n = size if kind == "uniform" else int(200 * ((256 << 10) / 200) ** rng.random())
+        off = rng.randrange(0, len(pool) - n)
+        out.append(pool[off:off + n])
+    return out
+
+
+def stats(times):
+    times = sorted(times)
+    return {"median_ms": round(1e3 * statistics.median(times), 3), "min_ms": round(1e3 * times[0], 3), "max_ms": round(1e3 * times[-1], 3),
+            "spread_pct": round(100.0 * (times[-1] - times[0]) / statistics.median(times), 2), "runs": len(times)}
+
+
+def bind(path):
+    L = ctypes.CDLL(path)
+    L.BrotliEncoderMaxCompressedSize.restype = ctypes.c_size_t
+    L.BrotliEncoderMaxCompressedSize.argtypes = [ctypes.c_size_t]
+    L.BrotliEncoderCompress.restype = ctypes.c_int
+    L.BrotliEncoderCompress.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.c_char_p, ctypes.POINTER(ctypes.c_size_t),
+                                        ctypes.c_char_p]
+    return L
+
+
+def measure_batch(lib_path, items, quality, runs, warmup):
+    L = bind(lib_path)
+    L.BrotliMi355xCompressBatch.restype = ctypes.c_int32
+    n = len(items)
+    caps = [L.BrotliEncoderMaxCompressedSize(len(x)) + 16 for x in items]
+    bufs = [ctypes.create_string_buffer(c) for c in caps]
+    inputs = (ctypes.c_char_p * n)(*items)
+    in_sizes = (ctypes.c_size_t * n)(*[len(x) for x in items])
+    outputs = (ctypes.c_void_p * n)(*[ctypes.addressof(b) for b in bufs])
+    out_sizes = (ctypes.c_size_t * n)()
+    times = []
+    for it in range(warmup + runs):
+        for i in range(n):
+            out_sizes[i] = caps[i]
+        t = time.perf_counter()
+        ok = L.BrotliMi355xCompressBatch(quality, LGWIN, 0, ctypes.c_size_t(n), inputs, in_sizes, outputs, out_sizes, None)
+        dt = time.perf_counter() - t
+        assert ok == 1
+        if it >= warmup:
+            times.append(dt)
+    return times, sum(out_sizes)
+
+
+def measure_loop(lib_path, items, quality, threads, runs, warmup):
+    L = bind(lib_path)
+    caps = [L.BrotliEncoderMaxCompressedSize(len(x)) + 16 for x in items]
+    bufs = [ctypes.create_string_buffer(c) for c in caps]
+
+    def work(lo, hi):
+        size = ctypes.c_size_t()
+        for i in range(lo, hi):
+            size.value = caps[i]
+            assert L.BrotliEncoderCompress(quality, LGWIN, 0, len(items[i]), items[i], ctypes.byref(size), bufs[i])
+
+    times = []
+    n = len(items)
+    for it in range(warmup + runs):
+        pool = [threading.Thread(target=work, args=(n * k // threads, n * (k + 1) // threads)) for k in range(threads)]
+        t = time.perf_counter()
+        for th in pool:
+            th.start()
+        for th in pool:
+            th.join()
+        dt = time.perf_counter() - t
+        if it >= warmup:
+            times.append(dt)
+    return times
+
+
+def measure_cpu(items, quality, runs):
+    os.environ["ORC_FAST"] = "1"
+    import orc
+    times = []
+    for it in range(1 + runs):
+        t = time.perf_counter()
+        for x in items:
+            orc.compress(x, quality, LGWIN)
+        dt = time.perf_counter() - t
+        if it >= 1:
+            times.append(dt)
+    return times
+
+
+def child(args):
+    out = []
+    for name in args.classes.split(","):
+        for data in (["text"] if CLASSES[name][0] == "alice" else ["text", "mixed"]):
+            items = items_of(name, data)
+            first = items[:args.loop_items]
+            for quality in (0, 1):
+                row = {"class": name, "data": data, "quality": quality, "items": len(items), "bytes": sum(map(len, items))}
+                if args.child == "batch":
+                    times, csize = measure_batch(args.lib, items, quality, args.runs, args.warmup)
+                    row.update(stats(times), compressed_bytes=csize)
+                elif args.child == "loop":
+                    row.update(stats(measure_loop(args.lib, first, quality, args.threads, args.runs, 1)), threads=args.threads, measured_items=len(first))
+                else:
+                    row.update(stats(measure_cpu(first, quality, args.runs)), measured_items=len(first))
+                out.append(row)
+                print(json.dumps(row), flush=True)
+    with open(args.child_out, "w") as f:
+        json.dump(out, f)
+
+
+def run_child(args, what, classes, lib=None, lds=None, threads=1, limit=600):
+    env = dict(os.environ)
+    env.pop("BROTLI_MI355X_BATCH_LDS_BITS", None)
+    if lds is not None:
+        env["BROTLI_MI355X_BATCH_LDS_BITS"] = str(lds)
+    tmp = os.path.join(os.path.dirname(os.path.abspath(args.out)), ".batch_probe_child.json")
+    cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--child", what, "--classes", ",".join(classes), "--lib", lib or args.lib,
+           "--threads", str(threads), "--runs", str(args.runs), "--warmup", str(args.warmup), "--loop-items", str(args.loop_items), "--child-out", tmp]
+    r = subprocess.run(cmd, env=env)
+    if r.returncode != 0:
+        raise SystemExit("batch_probe: %s (lds=%s, threads=%d) ended with status %d: nothing more is started" % (what, lds, threads, r.returncode))
+    rows = json.load(open(tmp))
+    os.remove(tmp)
+    return rows
+
+
+def key(row):
+    return "%s/%s/q%d" % (row["class"], row["data"], row["quality"])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--lib", default=os.path.join(ROOT, "rust-brotli_amd", "libbrotli_mi355x.so"))
+    ap.add_argument("--parent-lib", default=None, help="a build of the parent commit (the loop baseline); without it the loop is not measured")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_probe.json"))
+    ap.add_argument("--runs", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--loop-items", type=int, default=256)
+    ap.add_argument("--ab-rounds", type=int, default=3, help="how often the A/B alternates between the two settings")
+    ap.add_argument("--skip", default="", help="comma list of: headline, ab")
+    ap.add_argument("--child", default=None)
+    ap.add_argument("--classes", default="")
+    ap.add_argument("--threads", type=int, default=1)
+    ap.add_argument("--child-out", default=None)
+    args = ap.parse_args()
+    if args.child:
+        return child(args)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    skip = set(args.skip.split(","))
+    doc = {"what": "BrotliMi355xCompressBatch vs a loop of BrotliEncoderCompress (parent commit) vs the oracle on one CPU core; lgwin 22",
+           "method": "host clock around the synchronous call, %d warm-up runs, median of %d runs; spread = (max - min) / median of the repeats; "
+                     "loop and cpu on the first %d items of a class, scaled by item count" % (args.warmup, args.runs, args.loop_items)}
+
+    def save():
+        with open(args.out, "w") as f:
+            json.dump(doc, f, indent=1)
+
+    if "ab" not in skip:
+        # the table's home: device memory (0) against workgroup memory (11, the largest the library keeps there), the same jobs,
+        # alternating: device, workgroup, device, workgroup ... one child each
+        ab = {}
+        for rnd in range(args.ab_rounds):
+            for lds in (0, 11):
+                for row in run_child(args, "batch", AB, lds=lds):
+                    ab.setdefault(key(row), {}).setdefault("lds%d_ms" % lds, []).append(row["median_ms"])
+                    ab[key(row)].setdefault("spread_pct", []).append(row["spread_pct"])
+        for k, v in ab.items():
+            a, b = statistics.median(v["lds0_ms"]), statistics.median(v["lds11_ms"])
+            v["workgroup_over_device"] = round(b / a, 4)
+            # the spread a difference has to beat: the largest of the repeats inside a child and of the children of either arm
+            v["repeat_spread_pct"] = round(max(max(v.pop("spread_pct")), 100.0 * (max(v["lds0_ms"]) - min(v["lds0_ms"])) / a,
+                                               100.0 * (max(v["lds11_ms"]) - min(v["lds11_ms"])) / b), 2)
+            v["workgroup_wins"] = bool(100.0 * (1.0 - b / a) > v["repeat_spread_pct"])
+        doc["table_home_ab"] = ab
+        save()
+    if "headline" not in skip:
+        rows = {}
+        for row in run_child(args, "batch", HEADLINE):
+            rows[key(row)] = {"items": row["items"], "bytes": row["bytes"], "compressed_bytes": row["compressed_bytes"], "batch": {k: row[k] for k in ("median_ms", "min_ms", "max_ms", "spread_pct", "runs")}}
+        doc["classes"] = rows
+        save()
+        for row in run_child(args, "cpu", HEADLINE):
+            scale = row["items"] / row["measured_items"]
+            rows[key(row)]["cpu_one_core"] = {"median_ms_scaled": round(row["median_ms"] * scale, 3), "measured_items": row["measured_items"], "spread_pct": row["spread_pct"]}
+        save()
+        for threads in (1, 4):
+            if not args.parent_lib:
+                for v in rows.values():
+                    v["loop_%dt" % threads] = "not measured"
+                continue
+            for row in run_child(args, "loop", HEADLINE, lib=os.path.abspath(args.parent_lib), threads=threads, limit=900):
+                scale = row["items"] / row["measured_items"]
+                rows[key(row)]["loop_%dt" % threads] = {"median_ms_scaled": round(row["median_ms"] * scale, 3), "measured_items": row["measured_items"], "spread_pct": row["spread_pct"]}
+            save()
+        for k, v in rows.items():
+            b = v["batch"]["median_ms"]
+            loops = [v[n]["median_ms_scaled"] for n in ("loop_1t", "loop_4t") if isinstance(v.get(n), dict)]
+            v["batch_MBps"] = round(v["bytes"] / 1e3 / b, 1)
+            v["cpu_over_batch"] = round(v["cpu_one_core"]["median_ms_scaled"] / b, 3)
+            v["better_loop_over_batch"] = round(min(loops) / b, 2) if loops else "not measured"
+        save()
+    print(json.dumps(doc, indent=1))
+
+
+if __name__ == "__main__":
+    main()
