@@ -41,6 +41,49 @@ struct DevMem {
   }
 };
 
+// Bring-up checks of the meta-block kernels (BROTLI_MI355X_SELFTEST=1), in the manner of Lz77Stage::SelfTestSort.
+// The rows of k_context_stats against a recomputation from the text (encode.rs:1802-1927).
+void SelfTestContextStats(const uint8_t* text_dev, const std::vector<MbDesc>& descs, const std::vector<uint32_t>& rows) {
+  uint8_t utf8[512];
+  dev_d2h(utf8, dev_tables().utf8_context_lookup, sizeof(utf8));
+  std::vector<uint8_t> bytes;
+  for (size_t m = 0; m < descs.size(); ++m) {
+    uint32_t s[kContextStatsWords] = {0};
+    const uint32_t length = descs[m].end - descs[m].start;
+    const uint32_t n_strides = length >= 64 ? (length - 64) / 4096 + 1 : 0;
+    bytes.resize(length);
+    if (n_strides) dev_d2h(bytes.data(), text_dev + descs[m].start, length);
+    for (uint32_t t = 0; t < n_strides; ++t) {
+      const uint8_t* p = bytes.data() + (size_t)t * 4096;
+      const uint32_t lut[4] = {0, 0, 1, 2};
+      for (uint32_t k = 1; k < 64; ++k) s[lut[p[k - 1] >> 6] * 3 + lut[p[k] >> 6]]++;
+      for (uint32_t k = 2; k < 64; ++k) {
+        const uint32_t context = kStaticContextMapComplexUTF8[utf8[p[k - 1]] | utf8[256 + p[k - 2]]];
+        s[480]++;
+        s[16 + (p[k] >> 3)]++;
+        s[48 + context * 32 + (p[k] >> 3)]++;
+      }
+    }
+    for (uint32_t j = 0; j < kContextStatsWords; ++j)
+      if (rows[m * kContextStatsWords + j] != s[j])
+        throw std::runtime_error("selftest: context statistics of meta-block " + std::to_string(m) + " differ at word " + std::to_string(j));
+  }
+}
+
+// The stream behind mb_emit against the same pieces ORed in one by one.
+void SelfTestEmit(const MbBuffers& B, size_t out_words) {
+#if !defined(BROTLI_HOST_EMU)  // (the emulation's mb_emit is the piecewise form itself)
+  DevBlocks blocks;
+  uint64_t* again = blocks.zeroed<uint64_t>(out_words * 8);
+  mb_emit_piecewise(B, again);
+  std::vector<uint64_t> a(out_words), b(out_words);
+  dev_d2h(a.data(), B.out_words, out_words * 8);
+  dev_d2h(b.data(), again, out_words * 8);
+  for (size_t i = 0; i < out_words; ++i)
+    if (a[i] != b[i]) throw std::runtime_error("selftest: mb_emit differs from the piecewise emission at word " + std::to_string(i));
+#endif
+}
+
 // host-composed pieces of the stream (window bits, metadata block, uncompressed headers, tail blocks)
 struct BitPiece {
   uint64_t pos;
@@ -797,6 +840,7 @@ void EncodeStream(const EncodeRequest& req, std::vector<uint8_t>* out, EncodeSta
         mb_context_stats(B, stats_dev);
         std::vector<uint32_t> cs((size_t)n_mb * kContextStatsWords);
         dev_d2h(cs.data(), stats_dev, cs.size() * 4);
+        if (getenv("BROTLI_MI355X_SELFTEST")) SelfTestContextStats(text, descs, cs);
         for (uint32_t m = 0; m < n_mb; ++m) {
           if (descs[m].uncompressed) continue;
           DecideContexts(cs.data() + (size_t)m * kContextStatsWords, p.quality, p.size_hint, descs[m].end - descs[m].start,
@@ -941,6 +985,7 @@ void EncodeStream(const EncodeRequest& req, std::vector<uint8_t>* out, EncodeSta
     if (!all_raw) {
       dev_h2d(B.mb_out_bit, mb_out_bit.data(), (n_mb + 1) * 8);
       mb_emit(B);
+      if (getenv("BROTLI_MI355X_SELFTEST")) SelfTestEmit(B, out_words);
     }
     {
       // the headers of the compressed meta-blocks, the bytes of the stored ones and what the host composed (stream header, the

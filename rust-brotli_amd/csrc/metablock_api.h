@@ -40,6 +40,9 @@ void mb_build_codes(const MbBuffers& B, const CodeJob* jobs_dev, uint32_t n_jobs
 void mb_write_headers(const MbBuffers& B);
 void mb_symbol_bits(const MbBuffers& B, void* scan_scratch);
 void mb_emit(const MbBuffers& B);
+// the same bits piece by piece (one atomic OR per piece, the form the emulation runs) into zeroed words of the caller: what
+// BROTLI_MI355X_SELFTEST compares mb_emit with
+void mb_emit_piecewise(const MbBuffers& B, uint64_t* out_words);
 void mb_copy_bits(uint64_t* out, uint64_t dst_bit, const uint64_t* src, uint64_t nbits);
 // The tail of the emission in three launches, however many meta-blocks there are (an incompressible gigabyte is 700 stored
 // meta-blocks, each with a handful of host-composed header pieces and one copy of its bytes):

@@ -32,7 +32,8 @@ struct BitSink {
 // BR_CODES_PROFILE (experiment builds only): cycles per phase of the Huffman jobs, summed in g_codes_prof[phase] and
 // the slowest job's in g_codes_prof[16 + phase]; printed by mb_build_codes
 #if defined(BR_CODES_PROFILE) && !defined(BROTLI_HOST_EMU)
-extern __device__ unsigned long long g_codes_prof[32];
+// (a copy per translation unit: the kernels that are measured and the host code that prints are both in metablock_kernels.hip)
+static __device__ unsigned long long g_codes_prof[32];
 struct CodesPhaseClock {
   unsigned long long last;
   BR_DEV CodesPhaseClock() : last(__builtin_readcyclecounter()) {}
@@ -47,9 +48,26 @@ struct CodesPhaseClock {
 };
 #define BR_PHASE_CLOCK() CodesPhaseClock br_phase_clock
 #define BR_PHASE(k) br_phase_clock.mark(k)
+// the same for the one lane that composes a meta-block's header (mb_item_write_header): g_header_prof[phase] / [8 + phase],
+// printed by mb_write_headers
+static __device__ unsigned long long g_header_prof[16];
+struct HeaderPhaseClock {
+  unsigned long long last;
+  BR_DEV HeaderPhaseClock() : last(__builtin_readcyclecounter()) {}
+  BR_DEV void mark(int phase) {
+    const unsigned long long now = __builtin_readcyclecounter();
+    atomicAdd(&g_header_prof[phase], now - last);
+    atomicMax(&g_header_prof[8 + phase], now - last);
+    last = __builtin_readcyclecounter();
+  }
+};
+#define BR_HEADER_PHASE_CLOCK() HeaderPhaseClock br_header_clock
+#define BR_HEADER_PHASE(k) br_header_clock.mark(k)
 #else
 #define BR_PHASE_CLOCK()
 #define BR_PHASE(k)
+#define BR_HEADER_PHASE_CLOCK()
+#define BR_HEADER_PHASE(k)
 #endif
 
 // ---------------------------------------------------------------------------------------------- Huffman
@@ -1068,9 +1086,11 @@ BR_DEV uint32_t br_context(const uint8_t* utf8_lut, const uint8_t* signed_lut, u
 }
 
 // static context maps, encode.rs:1723-1732, 1782-1798
+static constexpr uint8_t kStaticContextMapComplexUTF8[64] = {11, 11, 12, 12, 0, 0, 0, 0, 1, 1, 9,  9, 2, 2, 2,  2, 1, 1, 1, 1, 8, 3,
+                                                             3,  3,  1,  1,  1, 1, 2, 2, 2, 2, 8,  4, 4, 4, 8,  7, 4, 4, 8, 0, 0, 0,
+                                                             3,  3,  3,  3,  5, 5, 10, 5, 5, 5, 10, 5, 6, 6, 6, 6, 6, 6, 6, 6};
 BR_DEV uint32_t br_static_context_map(uint32_t map_id, uint32_t context) {
-  const uint8_t kComplex[64] = {11, 11, 12, 12, 0, 0, 0, 0, 1, 1, 9, 9, 2, 2, 2, 2, 1, 1, 1, 1, 8, 3, 3, 3, 1, 1, 1, 1, 2, 2, 2, 2,
-                                8,  4,  4,  4,  8, 7, 4, 4, 8, 0, 0, 0, 3, 3, 3, 3, 5, 5, 10, 5, 5, 5, 10, 5, 6, 6, 6, 6, 6, 6, 6, 6};
+  const uint8_t* kComplex = kStaticContextMapComplexUTF8;
   switch (map_id) {
     case 1: return (context == 2 || context == 3) ? 1u : 0u;                       // kStaticContextMapSimpleUTF8
     case 2: return context < 2 ? 1u : (context < 4 ? 2u : 0u);                    // kStaticContextMapContinuation

@@ -535,6 +535,7 @@ BR_DEV void mb_item_write_header(const MbBuffers& B, uint32_t m, HuffmanScratch*
   BitSink out;
   out.words = words;
   out.pos = 0;
+  BR_HEADER_PHASE_CLOCK();
   br_store_compressed_meta_block_header(d.is_last != 0, d.end - d.start, out);
   BlockSplitCode own_code;
   for (uint32_t kind = 0; kind < 3; ++kind) {
@@ -552,6 +553,7 @@ BR_DEV void mb_item_write_header(const MbBuffers& B, uint32_t m, HuffmanScratch*
                                         B.switch_bits[kind] + d.block_base[kind], B.switch_nbits[kind] + d.block_base[kind], out,
                                         prepared ? prepared->histograms[kind] : nullptr);
   }
+  BR_HEADER_PHASE(0);  // block-split codes
   out.put(2, d.dist_postfix_bits);
   out.put(4, d.num_direct_distance_codes >> d.dist_postfix_bits);
   for (uint32_t i = 0; i < r.num_types[kSplitLiteral]; ++i) out.put(2, d.context_mode);
@@ -573,12 +575,14 @@ BR_DEV void mb_item_write_header(const MbBuffers& B, uint32_t m, HuffmanScratch*
     }
     br_store_trivial_context_map(r.num_histos[kSplitDistance], 2, sc, out);
   }
+  BR_HEADER_PHASE(1);  // context maps
   for (uint32_t kind = 0; kind < 3; ++kind) {
     for (uint32_t i = 0; i < r.num_histos[kind]; ++i) {
       const uint32_t row_index = d.histo_base[kind] + i;
       mb_append_bits(out, B.tree_bits[kind] + (size_t)row_index * kTreeBitsWords, B.tree_nbits[kind][row_index]);
     }
   }
+  BR_HEADER_PHASE(2);  // the serialised trees
   r.header_bits = (uint32_t)out.pos;
 }
 
@@ -763,12 +767,28 @@ BR_DEV void mb_put_bits_atomic(uint64_t* words, uint64_t pos, uint32_t nbits, ui
 }
 
 // ---- K9: emission
-BR_DEV void mb_item_emit_command(const MbBuffers& B, uint32_t c) {
+// Where a piece of the body goes is the sink's business: put(pos, nbits, bits) takes `nbits` < 64 bits for bit `pos` of the stream.
+// The default ORs every piece into the stream's words by itself; the emit kernels collect the pieces of a wavefront in workgroup
+// memory first (MbWindowSink, metablock_kernels.hip).
+struct MbAtomicSink {
+  uint64_t* words;
+  BR_DEV void put(uint64_t pos, uint32_t nbits, uint64_t bits) const { mb_put_bits_atomic(words, pos, nbits, bits); }
+};
+
+// meta-block of command c and the stream bit where the command starts; false: a stored meta-block, nothing to emit
+BR_DEV bool mb_command_base(const MbBuffers& B, uint32_t c, uint32_t* m_out, uint64_t* base) {
   const uint32_t m = mb_find_by_cmd(B, c);
   const MbDesc& d = B.descs[m];
-  if (d.uncompressed) return;
+  if (d.uncompressed) return false;
+  *m_out = m;
+  *base = B.mb_out_bit[m] + B.results[m].header_bits + (B.cmd_nbits[c] - B.cmd_nbits[d.cmd_offset]);
+  return true;
+}
+
+template <typename Sink>
+BR_DEV void mb_emit_command_pieces(const MbBuffers& B, uint32_t c, uint32_t m, uint64_t base, const Sink& sink) {
+  const MbDesc& d = B.descs[m];
   const Command cmd = B.cmds[c];
-  const uint64_t base = B.mb_out_bit[m] + B.results[m].header_bits + (B.cmd_nbits[c] - B.cmd_nbits[d.cmd_offset]);
   // own symbols, written in two pieces (switch + code, then extras) to stay below 64 bits per piece
   {
     SymbolCode sc;
@@ -783,35 +803,52 @@ BR_DEV void mb_item_emit_command(const MbBuffers& B, uint32_t c) {
       sc.nbits = B.switch_nbits[kSplitCommand][d.block_base[kSplitCommand] + blk];
     }
     uint64_t pos = base;
-    mb_put_bits_atomic(B.out_words, pos, sc.nbits, sc.bits);
+    sink.put(pos, sc.nbits, sc.bits);
     pos += sc.nbits;
     const size_t ix = ((size_t)d.histo_base[kSplitCommand] + type) * kNumCommandSymbols + cmd.cmd_prefix_;
-    mb_put_bits_atomic(B.out_words, pos, B.depth[kSplitCommand][ix], B.bits[kSplitCommand][ix]);
+    sink.put(pos, B.depth[kSplitCommand][ix], B.bits[kSplitCommand][ix]);
     pos += B.depth[kSplitCommand][ix];
     uint32_t en;
     const uint64_t eb = br_command_extra_bits(cmd, &en);
-    mb_put_bits_atomic(B.out_words, pos, en, eb);
+    sink.put(pos, en, eb);
   }
   if (br_command_has_distance(cmd)) {
     const uint32_t lit_bits = B.lit_nbits[B.cmd_lit_start[c + 1]] - B.lit_nbits[B.cmd_lit_start[c]];
     uint64_t pos = base + B.cmd_own_bits[c] + lit_bits;
     const SymbolCode dc = mb_distance_code(B, c, d, m);
-    mb_put_bits_atomic(B.out_words, pos, dc.nbits, dc.bits);
+    sink.put(pos, dc.nbits, dc.bits);
     pos += dc.nbits;
-    mb_put_bits_atomic(B.out_words, pos, (uint32_t)(cmd.dist_prefix_ >> 10), cmd.dist_extra_);
+    sink.put(pos, (uint32_t)(cmd.dist_prefix_ >> 10), cmd.dist_extra_);
   }
 }
 
-BR_DEV void mb_item_emit_literal(const MbBuffers& B, uint32_t i) {
+template <typename Sink>
+BR_DEV void mb_item_emit_command(const MbBuffers& B, uint32_t c, const Sink& sink) {
+  uint32_t m;
+  uint64_t base;
+  if (mb_command_base(B, c, &m, &base)) mb_emit_command_pieces(B, c, m, base, sink);
+}
+BR_DEV void mb_item_emit_command(const MbBuffers& B, uint32_t c) { mb_item_emit_command(B, c, MbAtomicSink{B.out_words}); }
+
+// stream bit where literal i starts; false: a stored meta-block
+BR_DEV bool mb_literal_base(const MbBuffers& B, uint32_t i, uint64_t* pos) {
   const uint32_t m = mb_find_by_lit(B, i);
   const MbDesc& d = B.descs[m];
-  if (d.uncompressed) return;
+  if (d.uncompressed) return false;
   const uint32_t c = B.lit_cmd[i];
-  const uint64_t pos = B.mb_out_bit[m] + B.results[m].header_bits + (B.cmd_nbits[c] - B.cmd_nbits[d.cmd_offset]) + B.cmd_own_bits[c] +
-                       (B.lit_nbits[i] - B.lit_nbits[B.cmd_lit_start[c]]);
-  const SymbolCode sc = mb_literal_code(B, i);
-  mb_put_bits_atomic(B.out_words, pos, sc.nbits, sc.bits);
+  *pos = B.mb_out_bit[m] + B.results[m].header_bits + (B.cmd_nbits[c] - B.cmd_nbits[d.cmd_offset]) + B.cmd_own_bits[c] +
+         (B.lit_nbits[i] - B.lit_nbits[B.cmd_lit_start[c]]);
+  return true;
 }
+
+template <typename Sink>
+BR_DEV void mb_item_emit_literal(const MbBuffers& B, uint32_t i, const Sink& sink) {
+  uint64_t pos;
+  if (!mb_literal_base(B, i, &pos)) return;
+  const SymbolCode sc = mb_literal_code(B, i);
+  sink.put(pos, sc.nbits, sc.bits);
+}
+BR_DEV void mb_item_emit_literal(const MbBuffers& B, uint32_t i) { mb_item_emit_literal(B, i, MbAtomicSink{B.out_words}); }
 
 // ---- K10: copy `nbits` bits from a word-aligned source to an arbitrary bit offset of the output
 BR_DEV void mb_item_copy_bits_word(uint64_t* out, uint64_t dst_bit, const uint64_t* src, uint64_t nbits, uint64_t w) {

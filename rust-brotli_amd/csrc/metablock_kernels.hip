@@ -1,7 +1,8 @@
 // metablock_kernels.hip -- gfx950 kernels of the meta-block stage: per-granule histograms, greedy block
 // splitting (one workgroup per splitter, strictly ordered f32 entropy sums), Huffman code construction
 // (one thread per histogram), header serialisation (one thread per meta-block) and the parallel symbol
-// emission (bit length per symbol -> prefix sums -> 64-bit atomic OR scatter).  Integer/byte work, no MFMA.
+// emission (bit length per symbol -> prefix sums -> pieces ORed together per wavefront in LDS -> 64-bit atomic OR per stream
+// word).  Integer/byte work, no MFMA.
 #include <hip/hip_runtime.h>
 
 #include "device_api.h"
@@ -59,49 +60,71 @@ void mb_literal_map(const MbBuffers& B) {
   HIP_CHECK(hipGetLastError());
 }
 
-// sampled context statistics, one workgroup per meta-block (encode.rs:1802-1927)
+// sampled context statistics (encode.rs:1802-1927): a 64-byte sample every 4096 bytes of the meta-block.  One wavefront per sample,
+// lane k holds byte k (one coalesced load) and takes its two predecessors from the lanes below; the workgroups of a meta-block
+// share its samples and add their counters to its row of `stats` (zeroed by the caller; integer sums, so the order is free).
+static constexpr uint32_t kStatsChunks = 64;  // workgroups per meta-block: 2048 samples of an 8 MiB meta-block are 8 per wavefront
 __global__ __launch_bounds__(256) void k_context_stats(MbBuffers B, uint32_t* stats) {
   __shared__ uint32_t s[kContextStatsWords];
-  const uint32_t m = blockIdx.x;
+  const uint32_t m = blockIdx.y;
   const MbDesc d = B.descs[m];
-  for (uint32_t j = threadIdx.x; j < kContextStatsWords; j += blockDim.x) s[j] = 0;
-  __syncthreads();
   const uint32_t length = d.end - d.start;
   const uint32_t n_strides = length >= 64 ? (length - 64) / 4096 + 1 : 0;
-  for (uint32_t t = threadIdx.x; t < n_strides; t += blockDim.x) {
-    const uint32_t start_pos = d.start + t * 4096;
-    const uint8_t* p = B.text + start_pos;
-    // simple bigram-prefix histogram (encode.rs:1885-1918)
-    {
-      const int lut[4] = {0, 0, 1, 2};
-      int prev = lut[p[0] >> 6] * 3;
-      for (uint32_t k = 1; k < 64; ++k) {
-        const uint8_t literal = p[k];
-        atomicAdd(&s[prev + lut[literal >> 6]], 1u);
-        prev = lut[literal >> 6] * 3;
-      }
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63, n_waves = kStatsChunks * 4;
+  if (blockIdx.x * 4 >= n_strides) return;  // (the whole workgroup)
+  for (uint32_t j = threadIdx.x; j < kContextStatsWords; j += blockDim.x) s[j] = 0;
+  __syncthreads();
+  const uint8_t* text = B.text + d.start + lane;
+  constexpr uint32_t kBatch = 4;  // loads in flight per wavefront
+  for (uint32_t t0 = blockIdx.x * 4 + wave; t0 < n_strides; t0 += n_waves * kBatch) {
+    uint32_t bytes[kBatch];
+    for (uint32_t u = 0; u < kBatch; ++u) {
+      const uint32_t t = t0 + u * n_waves;
+      bytes[u] = t < n_strides ? text[(size_t)t * 4096] : 0u;
     }
-    // complex context statistics (encode.rs:1820-1842)
-    {
-      uint8_t prev2 = p[0], prev1 = p[1];
-      for (uint32_t k = 2; k < 64; ++k) {
-        const uint8_t literal = p[k];
-        const uint32_t context = br_static_context_map(3, br_context(B.utf8_lut, B.signed_lut, prev1, prev2, 2));
-        atomicAdd(&s[480], 1u);
-        atomicAdd(&s[16 + (literal >> 3)], 1u);
-        atomicAdd(&s[48 + context * 32 + (literal >> 3)], 1u);
-        prev2 = prev1;
-        prev1 = literal;
+    for (uint32_t u = 0; u < kBatch; ++u) {
+      if (t0 + u * n_waves >= n_strides) break;  // (wave-uniform)
+      const uint32_t literal = bytes[u];
+      const uint32_t prev1 = (uint32_t)__shfl_up((int)literal, 1, 64), prev2 = (uint32_t)__shfl_up((int)literal, 2, 64);
+      // simple bigram-prefix histogram (encode.rs:1885-1918): nine counters, counted across the lanes
+      {
+        const uint32_t lut = 0x90u;  // {0, 0, 1, 2}, two bits each
+        const uint32_t bin = ((lut >> ((prev1 >> 6) * 2)) & 3u) * 3u + ((lut >> ((literal >> 6) * 2)) & 3u);
+        uint32_t mine = 0;
+        for (uint32_t b = 0; b < 9; ++b) {
+          const uint32_t count = (uint32_t)__popcll(__ballot(lane >= 1 && bin == b));
+          if (lane == b) mine = count;
+        }
+        if (mine) atomicAdd(&s[lane], mine);
       }
+      // complex context statistics (encode.rs:1820-1842); the combined histogram [16..48) is the sum of the per-context ones
+      // and the total [480] is 62 per sample: both are filled in when the counters leave the workgroup
+      if (lane >= 2) {
+        const uint32_t context = br_static_context_map(3, br_context(B.utf8_lut, B.signed_lut, (uint8_t)prev1, (uint8_t)prev2, 2));
+        atomicAdd(&s[48 + context * 32 + (literal >> 3)], 1u);
+      }
+      if (lane == 0) atomicAdd(&s[480], 62u);
     }
   }
   __syncthreads();
-  for (uint32_t j = threadIdx.x; j < kContextStatsWords; j += blockDim.x) stats[(size_t)m * kContextStatsWords + j] = s[j];
+  uint32_t* row = stats + (size_t)m * kContextStatsWords;
+  for (uint32_t j = threadIdx.x; j < kContextStatsWords; j += blockDim.x) {
+    uint32_t v = s[j];
+    if (j >= 16 && j < 48)
+      for (uint32_t c = 0; c < 13; ++c) v += s[48 + c * 32 + (j - 16)];
+    if (v) atomicAdd(&row[j], v);
+  }
 }
 
 void mb_context_stats(const MbBuffers& B, uint32_t* stats_dev) {
   if (B.n_mb == 0) return;
-  hipLaunchKernelGGL(k_context_stats, dim3(B.n_mb), dim3(256), 0, BR_STREAM, B, stats_dev);
+  // (a grid dimension holds 65 535 meta-blocks)
+  for (uint32_t first = 0; first < B.n_mb; first += 32768) {
+    MbBuffers b = B;
+    b.descs += first;
+    const uint32_t n = B.n_mb - first < 32768 ? B.n_mb - first : 32768;
+    hipLaunchKernelGGL(k_context_stats, dim3(kStatsChunks, n), dim3(256), 0, BR_STREAM, b, stats_dev + (size_t)first * kContextStatsWords);
+  }
   HIP_CHECK(hipGetLastError());
 }
 
@@ -134,9 +157,6 @@ void mb_split_chains(const MbBuffers& B, bool wide) {
   HIP_CHECK(hipGetLastError());
 }
 
-#if defined(BR_CODES_PROFILE)
-__device__ unsigned long long g_codes_prof[32];
-#endif
 // The Huffman construction is sequential, data-dependent control flow: 64 different histograms in the lanes of one
 // wavefront would serialise on every divergent branch.  One histogram per wavefront (lane 0 works) puts the jobs
 // on different SIMDs instead, where they really run concurrently.
@@ -262,6 +282,17 @@ void mb_write_headers(const MbBuffers& B) {
   if (B.n_mb == 0) return;
   hipLaunchKernelGGL(k_write_headers, dim3(B.n_mb), dim3(64), 0, BR_STREAM, B);
   HIP_CHECK(hipGetLastError());
+#if defined(BR_CODES_PROFILE)
+  {
+    unsigned long long h[16];
+    HIP_CHECK(hipStreamSynchronize(BR_STREAM));
+    HIP_CHECK(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_header_prof), sizeof(h)));
+    fprintf(stderr, "header profile (%u meta-blocks), cycles sum / slowest meta-block: block-split codes %llu / %llu, context maps %llu / %llu, trees %llu / %llu\n",
+            B.n_mb, h[0], h[8], h[1], h[9], h[2], h[10]);
+    unsigned long long z[16] = {0};
+    HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_header_prof), z, sizeof(z)));
+  }
+#endif
 }
 
 void mb_symbol_bits(const MbBuffers& B, void* scan_scratch) {
@@ -275,8 +306,86 @@ void mb_symbol_bits(const MbBuffers& B, void* scan_scratch) {
   HIP_CHECK(hipGetLastError());
 }
 
+// ---- emission.  An item's pieces are a few bits each, and neighbouring items write neighbouring bits: a wavefront takes 64
+// consecutive items and collects their pieces in a window of kWords 64-bit words of workgroup memory that starts at the stream word
+// of its first item, then ORs every non-zero word of the window into the stream once.  A piece that does not lie wholly inside the
+// window -- behind a long literal run, behind the header of the next meta-block, across the window's end -- goes to the stream by
+// itself, as every piece does with MbAtomicSink.  Everything is an OR into zero-filled words, so no order is assumed anywhere.
+template <uint32_t kWords>
+struct MbWindowSink {
+  uint64_t* words;            // the stream
+  unsigned long long* window; // kWords words of workgroup memory, this wavefront's own
+  uint64_t first_word;        // stream word of window[0]
+  __device__ __forceinline__ void put(uint64_t pos, uint32_t nbits, uint64_t bits) const {
+    if (nbits == 0) return;
+    const uint32_t sh = (uint32_t)(pos & 63u);
+    const uint64_t at = (pos >> 6) - first_word;  // (a word in front of the window: a huge number)
+    const bool two = sh + nbits > 64;
+    if (at < kWords && (!two || at + 1 < kWords)) {
+      atomicOr(window + at, (unsigned long long)(bits << sh));
+      if (two) atomicOr(window + at + 1, (unsigned long long)(bits >> (64 - sh)));
+    } else {
+      mb_put_bits_atomic(words, pos, nbits, bits);
+    }
+  }
+};
+
+// 64 commands of text are about 25 words, 64 literals and the commands between them about 15.  Measured on the 64 MiB text
+// workload, k_emit_commands takes the same 0.100 ms with windows of 64, 128 and 256 words.
+static constexpr uint32_t kEmitCommandWindow = 128;
+static constexpr uint32_t kEmitLiteralWindow = 64;
+
+// first(i, &bit): where item i starts in the stream, false if it has nothing to emit; emit(i, bit, sink): its pieces
+template <uint32_t kWords, typename First, typename Emit>
+__device__ __forceinline__ void mb_emit_wave(const MbBuffers& B, uint32_t n, unsigned long long* windows, First first, Emit emit) {
+  const uint32_t lane = threadIdx.x & 63u;
+  unsigned long long* window = windows + (threadIdx.x >> 6) * kWords;
+  for (uint32_t j = lane; j < kWords; j += 64) window[j] = 0;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  uint64_t bit = 0;
+  const bool mine = i < n && first(i, &bit);
+  // the window starts at the first item of the wavefront that emits anything
+  const unsigned long long emitting = __ballot(mine);
+  uint64_t first_word = 0;
+  if (emitting) first_word = (uint64_t)__shfl((unsigned long long)(bit >> 6), __ffsll(emitting) - 1, 64);
+  __syncthreads();
+  if (mine) emit(i, bit, MbWindowSink<kWords>{B.out_words, window, first_word});
+  __syncthreads();
+  // (a non-zero word holds a piece of the stream, so it lies inside out_words)
+  for (uint32_t j = lane; j < kWords; j += 64) {
+    const unsigned long long v = window[j];
+    if (v) atomicOr((unsigned long long*)B.out_words + first_word + j, v);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_emit_commands(MbBuffers B) {
+  __shared__ unsigned long long windows[4 * kEmitCommandWindow];
+  uint32_t m = 0;  // (each lane's own: set by first, read by emit)
+  mb_emit_wave<kEmitCommandWindow>(
+      B, B.n_cmds, windows, [&](uint32_t c, uint64_t* bit) { return mb_command_base(B, c, &m, bit); },
+      [&](uint32_t c, uint64_t bit, const MbWindowSink<kEmitCommandWindow>& sink) { mb_emit_command_pieces(B, c, m, bit, sink); });
+}
+
+__global__ __launch_bounds__(256) void k_emit_literals(MbBuffers B) {
+  __shared__ unsigned long long windows[4 * kEmitLiteralWindow];
+  mb_emit_wave<kEmitLiteralWindow>(
+      B, B.n_lits, windows, [&](uint32_t i, uint64_t* bit) { return mb_literal_base(B, i, bit); },
+      [&](uint32_t i, uint64_t bit, const MbWindowSink<kEmitLiteralWindow>& sink) {
+        const SymbolCode sc = mb_literal_code(B, i);
+        sink.put(bit, sc.nbits, sc.bits);
+      });
+}
+
 void mb_emit(const MbBuffers& B) {
-  const MbBuffers b = B;
+  if (B.n_cmds) hipLaunchKernelGGL(k_emit_commands, dim3((B.n_cmds + 255) / 256), dim3(256), 0, BR_STREAM, B);
+  if (B.n_lits) hipLaunchKernelGGL(k_emit_literals, dim3((B.n_lits + 255) / 256), dim3(256), 0, BR_STREAM, B);
+  HIP_CHECK(hipGetLastError());
+}
+
+// every piece by itself (MbAtomicSink), into `out_words` instead of B.out_words: what mb_emit is checked against
+void mb_emit_piecewise(const MbBuffers& B, uint64_t* out_words) {
+  MbBuffers b = B;
+  b.out_words = out_words;
   for_each(b.n_cmds, [b] __device__(uint32_t c) { mb_item_emit_command(b, c); });
   for_each(b.n_lits, [b] __device__(uint32_t i) { mb_item_emit_literal(b, i); });
   HIP_CHECK(hipGetLastError());
