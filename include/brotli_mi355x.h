@@ -198,12 +198,23 @@ BROTLI_BOOL BrotliMi355xCompressDevice(int quality, int lgwin, BrotliEncoderMode
    An item that fails (capacity 0, or a buffer too small) fails alone: its size becomes 0 and item_results[i] (may be NULL)
    becomes 0, the other items are still produced.  Returns 1 if every item succeeded (count == 0 included), 0 otherwise.  A
    device error fails the whole call: every size becomes 0 and BrotliMi355xLastError says why.  Inputs are host memory.
-   Qualities 0 and 1 run the fragments of all items side by side on the device, with one upload and one download per group of
-   up to 4096 fragments; this is the call for many small payloads.  Every other quality is accepted and runs item by item
-   through the one-shot path on the calling thread: the same bytes, no gain in speed. */
+   This is the call for many small payloads.  Which items run side by side on the device:
+     qualities 0 and 1: every item; the fragments of all items share one upload and one download per group of up to 4096;
+     qualities 5 .. 8:  the items of at most one input block (65 536 bytes) at lgwin 17 .. 24 -- one parse chain and one
+                        meta-block each, thousands of them in flight, one upload and one download per group of up to 4096 items.
+   Every other item -- qualities 2 .. 4 and 9 .. 11, lgwin <= 16 or > 24, items longer than one input block -- is accepted and
+   runs by itself through the one-shot path on the calling thread, in the same call and in the caller's order: the same bytes,
+   no gain in speed.  Both kinds may be mixed in one call; BrotliMi355xLastBatchInfo tells how a call was taken.
+   Environment (read once per process): BROTLI_MI355X_BATCH_GROUP_ITEMS / BROTLI_MI355X_BATCH_GROUP_BYTES bound a group of
+   qualities 5 .. 8 (4096 items, 64 MiB), BROTLI_MI355X_BATCH_TABLES the number of hash tables, i.e. of chains in flight
+   (default: as many as stay resident, within 8 GiB; a table is 1 MiB at quality 5 and 16 MiB at quality 8). */
 int32_t BrotliMi355xCompressBatch(int quality, int lgwin, BrotliEncoderMode mode, size_t count, const uint8_t* const* inputs,
                                   const size_t* input_sizes, uint8_t* const* outputs,
                                   size_t* output_sizes /* in: capacity, out: size */, int32_t* item_results /* may be NULL */);
+/* The last BrotliMi355xCompressBatch call of the calling thread: info[0] items, [1] items encoded side by side on the device,
+   [2] items run one by one through the one-shot path, [3] items answered without an encoder (empty input, capacity 0),
+   [4] device groups, [5..7] zero.  After a call that failed as a whole only info[0] is set. */
+void BrotliMi355xLastBatchInfo(uint64_t info[8]);
 /* Human-readable description of the device backing the library ("hip:gfx950 (...)"). */
 const char* BrotliMi355xDeviceName(void);
 /* Message of the last failure on the calling thread ("" if none). */

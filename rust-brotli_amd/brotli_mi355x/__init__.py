@@ -11,7 +11,7 @@ not been built, and every call fails loudly (BrotliCompressorException) if no gf
 """
 import ctypes
 import os
-from ctypes import POINTER, byref, c_char_p, c_double, c_int, c_int32, c_size_t, c_uint32, c_void_p
+from ctypes import POINTER, byref, c_char_p, c_double, c_int, c_int32, c_size_t, c_uint32, c_uint64, c_void_p
 
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -169,8 +169,9 @@ class Library(object):
 
     def compress_batch(self, items, quality=0, lgwin=22, mode=0):
         """BrotliMi355xCompressBatch: every item becomes a stream of its own, the same bytes as compress(item, quality, lgwin,
-        mode), in one call.  At qualities 0 and 1 all items run side by side on the device (the call for many small payloads);
-        other qualities run item by item.  Returns a list of bytes."""
+        mode), in one call.  Side by side on the device (the call for many small payloads): every item at qualities 0 and 1, and
+        at qualities 5 to 8 the items of at most 65 536 bytes at lgwin 17 to 24.  Everything else runs item by item in the same
+        call; last_batch_info() tells how the items of the last call were taken.  Returns a list of bytes."""
         items = [bytes(x) for x in items]
         count = len(items)
         if count == 0:
@@ -194,6 +195,15 @@ class Library(object):
             raise BrotliCompressorException("BrotliMi355xCompressBatch failed (items %s): %s" % (failed[:8], self.last_error()))
         view = memoryview(out)
         return [bytes(view[starts[i]:starts[i] + out_sizes[i]]) for i in range(count)]
+
+    def last_batch_info(self):
+        """BrotliMi355xLastBatchInfo: the last compress_batch call of this thread as a list of 8 integers -- [0] items, [1] items
+        encoded side by side on the device, [2] items run one by one, [3] items answered without an encoder, [4] device groups."""
+        info = (c_uint64 * 8)()
+        self.lib.BrotliMi355xLastBatchInfo.restype = None
+        self.lib.BrotliMi355xLastBatchInfo.argtypes = [POINTER(c_uint64)]
+        self.lib.BrotliMi355xLastBatchInfo(info)
+        return list(info)
 
     def compress_device(self, device_ptr, nbytes, quality=5, lgwin=22, mode=0, out_buffer=None):
         """One-shot compression of `nbytes` at device address `device_ptr` (e.g. tensor.data_ptr()).

@@ -1,0 +1,77 @@
+// batch_greedy.h -- the small items of a batch at qualities 5 .. 8, side by side on the device (BrotliMi355xCompressBatch).
+//
+// An item of at most one input block (1 << lgblock bytes) under an H5 hasher is ONE live chain (lz77_live.h) and ONE meta-block:
+// it starts on empty bucket rings, so the chain is exact on its own stores and nothing is speculated, verified or repeated.
+// A group of such items shares one text buffer (every item at a 64-byte boundary, at least 64 zero bytes behind it), one key
+// pass, one parse launch (k_parse_batch: one wavefront per item, each on a private table that it zeroes itself), one command
+// gather and one pass of the meta-block stage with one meta-block per item.  The streams come out of the same kernels as those
+// of the one-shot call, item by item the bytes BrotliEncoderCompress gives.
+#ifndef BROTLI_MI355X_BATCH_GREEDY_H_
+#define BROTLI_MI355X_BATCH_GREEDY_H_
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include <vector>
+
+#include "encoder_params.h"
+#include "lz77_types.h"
+
+namespace brotli_mi355x {
+
+// ---- device seam (lz77_kernels.hip; the emulation build: batch_greedy_emu.inc)
+struct BatchItem {
+  uint32_t text_off;  // where the item starts in the group's padded text (a multiple of 64)
+  uint32_t bytes;     // 1 .. 1 << lgblock
+  uint32_t cmd_base;  // its command slab
+  uint32_t cmd_cap;
+};
+// What the chain leaves per item: Lz77Stage::Resolve for a stream of one block.
+struct BatchRecord {
+  uint32_t n_cmds;        // commands of the meta-block, the trailing insert-only one included
+  uint32_t n_lits;        // literals, the trailing ones included
+  uint32_t trailing;      // literals of the trailing insert-only command (0: there is none)
+  uint32_t uncompressed;  // should_compress (encode.rs:1325-1354) said no
+  uint32_t overflow;      // the slab was too small (cannot happen: a copy is at least two bytes long)
+  uint32_t pad[3];
+};
+struct BatchParseJob {
+  Lz77Params P;  // of a stream that starts at 0; total_bytes is the item's and set per item
+  const uint8_t* text;
+  const uint16_t* keys;
+  uint8_t* flags;
+  Command* slabs;
+  const BatchItem* items;
+  const uint32_t* order;  // largest item first
+  uint32_t n_items;
+  uint32_t tables;
+  uint16_t* num;      // [tables][1 << bucket_bits]
+  uint32_t* buckets;  // [tables][(1 << bucket_bits) << block_bits]
+  uint32_t* counter;  // [1], zero: the next place of `order` to hand out
+  BatchRecord* records;
+};
+// one wavefront per table; a wavefront takes items from `counter` until none is left
+void lz77_batch_parse(const BatchParseJob& J);
+// out[offsets[i] ..) = the finished commands of item i (Command::init) and its trailing insert-only command
+void lz77_batch_gather(const BatchParseJob& J, const uint32_t* offsets_dev, Command* out);
+
+// ---- host
+// Does this item go side by side?  `params`: the caller's parameters as set (quality, lgwin, mode), not finalized.
+bool BatchGreedyEligible(const EncoderParams& params, size_t input_size);
+// The streams of `count` eligible items.  Throws std::runtime_error on a device error.  *groups: device groups run.
+void BatchGreedyCompress(const EncoderParams& params, size_t count, const uint8_t* const* inputs, const size_t* sizes,
+                         std::vector<std::vector<uint8_t>>* streams, uint32_t* groups);
+
+// One group through the meta-block stage (encoder.cpp): meta-block i = item i, a complete stream of its own.
+struct BatchStreamItem {
+  uint32_t start, bytes;         // in the group's packed text (items back to back)
+  uint32_t cmd_offset, n_cmds;   // in the gathered command array
+  uint32_t n_lits;
+  uint32_t uncompressed;
+  uint64_t out_byte, out_bytes;  // result: where its stream lies in `out`
+};
+void EncodeBatchMetaBlocks(const EncoderParams& finalized, const uint8_t* packed_text_dev, const Command* cmds_dev, uint32_t n_cmds,
+                           std::vector<BatchStreamItem>* items, std::vector<uint8_t>* out);
+
+}  // namespace brotli_mi355x
+#endif

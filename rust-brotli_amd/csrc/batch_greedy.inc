@@ -1,0 +1,189 @@
+// batch_greedy.inc -- see batch_greedy.h: the plan of a group, its upload, the parse launch, the command gather and the
+// hand-over to the meta-block stage.  The product library compiles it as batch_greedy.cpp; the emulation library, whose list of
+// sources is fixed, gets it through cabi.cpp (the caller), together with the host emulation of the seam.
+#include "batch_greedy.h"
+
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <stdexcept>
+
+#include "device_api.h"
+#if defined(BROTLI_HOST_EMU)
+#include "batch_greedy_emu.inc"  // the host emulation of lz77_batch_parse / lz77_batch_gather
+#endif
+
+namespace brotli_mi355x {
+
+namespace {
+
+size_t EnvSize(const char* name, size_t otherwise) {
+  const char* s = getenv(name);
+  return s ? (size_t)strtoull(s, nullptr, 10) : otherwise;
+}
+
+// the parameters every eligible item of a call shares: FinalizeParams + ChooseHasher as EncodeStream runs them for a one-shot
+// call whose size hint is the item's size (<= 1 << lgblock, so the hint reaches nothing the items differ in)
+EncoderParams ItemParams(const EncoderParams& user, size_t input_size) {
+  EncoderParams p = user;
+  FinalizeParams(&p);
+  p.size_hint = input_size;
+  ChooseHasher(&p);
+  return p;
+}
+
+uint32_t Padded(uint32_t bytes) { return ((bytes + 63u) & ~63u) + 64u; }  // at least 64 zero bytes behind every item
+
+}  // namespace
+
+bool BatchGreedyEligible(const EncoderParams& user, size_t input_size) {
+  if (input_size == 0) return false;  // (answered without an encoder)
+  if (user.quality < 5 || user.quality > 8 || user.lgwin < 17 || user.lgwin > 24 || user.large_window) return false;
+  if (user.catable || user.appendable || user.bare_stream || user.byte_align || user.magic_number) return false;
+  if (input_size > ((size_t)1 << 24)) return false;
+  const EncoderParams p = ItemParams(user, input_size);
+  return p.hasher.type == 5 && input_size <= ((size_t)1 << p.lgblock);
+}
+
+void BatchGreedyCompress(const EncoderParams& user, size_t count, const uint8_t* const* inputs, const size_t* sizes,
+                         std::vector<std::vector<uint8_t>>* streams, uint32_t* groups) {
+  // read once per process, like BROTLI_MI355X_FRAGMENT_BATCH
+  static const size_t group_items = std::max<size_t>(1, EnvSize("BROTLI_MI355X_BATCH_GROUP_ITEMS", 4096));
+  static const size_t group_bytes = std::max<size_t>(1, EnvSize("BROTLI_MI355X_BATCH_GROUP_BYTES", (size_t)64 << 20));
+  // a table is 1 MiB at quality 5 and 16 MiB at quality 8: as many as the parse kernel keeps resident (256 CUs x 4 SIMDs x 4
+  // wavefronts) within 8 GiB
+  static const size_t table_override = EnvSize("BROTLI_MI355X_BATCH_TABLES", 0);
+  streams->assign(count, std::vector<uint8_t>());
+  *groups = 0;
+  if (count == 0) return;
+  const EncoderParams p = ItemParams(user, sizes[0]);
+  const size_t keys_per_table = (size_t)1 << p.hasher.bucket_bits;
+  const size_t table_bytes = keys_per_table * 2 + (keys_per_table << p.hasher.block_bits) * 4;
+  const size_t tables_max = table_override ? table_override : std::max<size_t>(1, std::min<size_t>(4096, ((size_t)8 << 30) / table_bytes));
+
+  Lz77Params P;
+  memset(&P, 0, sizeof(P));
+  P.ring_mask = (1u << ComputeRbBits(p)) - 1u;
+  P.max_backward_limit = (1u << p.lgwin) - 16u;
+  P.hasher_kind = 5;
+  P.bucket_bits = (uint32_t)p.hasher.bucket_bits;
+  P.block_bits = (uint32_t)p.hasher.block_bits;
+  P.hash_len = (uint32_t)p.hasher.hash_len;
+  P.ndist = (uint32_t)p.hasher.num_last_distances_to_check;
+  P.htl = 4;
+  P.literal_byte_score = (uint32_t)(p.hasher.literal_byte_score ? p.hasher.literal_byte_score : 540);
+  P.score_per_byte = P.literal_byte_score >> 2;
+  P.use_dictionary = p.use_dictionary ? 1 : 0;
+  P.spree_window = 64;
+  P.dist_max_distance = (uint32_t)p.dist.max_distance;
+  P.quality = (uint32_t)p.quality;
+  P.num_segments = 1;
+  P.dist_postfix_bits = p.dist.distance_postfix_bits;
+  P.num_direct_distance_codes = p.dist.num_direct_distance_codes;
+  P.masked_from = kNeverMasked;  // (an item ends inside the first ring-buffer revolution of its stream)
+  P.block_bytes = 1u << p.lgblock;
+  P.max_metablock_bytes = (uint32_t)MaxMetablockSize(p);
+
+  PinnedArray<uint8_t> staging;
+  PinnedArray<BatchItem> items;
+  PinnedArray<uint32_t> order, offsets;
+  PinnedArray<BatchRecord> records;
+  size_t first = 0;
+  while (first < count) {
+    // ---- the group: items [first, last)
+    size_t last = first, padded = 0, packed = 0;
+    while (last < count && last - first < group_items && (last == first || packed + sizes[last] <= group_bytes)) {
+      padded += Padded((uint32_t)sizes[last]);
+      packed += sizes[last];
+      ++last;
+    }
+    const uint32_t n = (uint32_t)(last - first);
+    ++*groups;
+    // one page-locked buffer, one upload: [padded text | 64 | packed text | 64]
+    const size_t packed_at = padded + 64;
+    const size_t text_bytes = packed_at + packed + 64;
+    staging.resize_discard(text_bytes);
+    memset(staging.data(), 0, text_bytes);
+    items.resize_discard(n);
+    order.resize_discard(n);
+    std::vector<BatchStreamItem> mbs(n);
+    {
+      uint32_t off = 0, start = 0, cmd_base = 0;
+      for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t bytes = (uint32_t)sizes[first + i];
+        memcpy(staging.data() + off, inputs[first + i], bytes);
+        memcpy(staging.data() + packed_at + start, inputs[first + i], bytes);
+        items[i] = BatchItem{off, bytes, cmd_base, bytes / 2 + 8};
+        mbs[i].start = start;
+        mbs[i].bytes = bytes;
+        off += Padded(bytes);
+        start += bytes;
+        cmd_base += bytes / 2 + 8;
+        order[i] = i;
+      }
+      // largest first: the large items of a group run as long as a lone wavefront takes, the small ones fill in behind them
+      std::stable_sort(order.data(), order.data() + n, [&](uint32_t a, uint32_t b) { return items[a].bytes > items[b].bytes; });
+    }
+    const size_t cmd_slots = (size_t)items[n - 1].cmd_base + items[n - 1].cmd_cap;
+    const uint32_t tables = (uint32_t)std::min<size_t>(tables_max, n);
+
+    DevBlocks mem;
+    uint8_t* text = mem.uninit<uint8_t>(text_bytes);
+    dev_h2d_bulk(text, staging.data(), text_bytes);
+    Lz77Buffers B{};
+    B.text = text;
+    B.keys = mem.uninit<uint16_t>(padded * 2 + 256);
+    B.changed_count = mem.zeroed<uint32_t>(64);
+    B.dict_items = nullptr;
+    B.run_end = nullptr;
+    Lz77Params PK = P;
+    PK.total_bytes = (uint32_t)padded;  // (the last item's padding gives every position four bytes to hash)
+    lz77_compute_keys(PK, B);
+
+    BatchParseJob J{};
+    J.P = P;
+    J.text = text;
+    J.keys = B.keys;
+    J.flags = mem.uninit<uint8_t>(padded + 64);
+    J.slabs = mem.uninit<Command>(cmd_slots * sizeof(Command) + 64);
+    BatchItem* items_dev = mem.uninit<BatchItem>((size_t)n * sizeof(BatchItem));
+    uint32_t* order_dev = mem.uninit<uint32_t>((size_t)n * 4);
+    dev_h2d(items_dev, items.data(), (size_t)n * sizeof(BatchItem));
+    dev_h2d(order_dev, order.data(), (size_t)n * 4);
+    J.items = items_dev;
+    J.order = order_dev;
+    J.n_items = n;
+    J.tables = tables;
+    J.num = mem.uninit<uint16_t>((size_t)tables * keys_per_table * 2 + 64);
+    J.buckets = mem.uninit<uint32_t>(((size_t)tables * keys_per_table << p.hasher.block_bits) * 4 + 64);
+    J.counter = mem.zeroed<uint32_t>(64);
+    J.records = mem.uninit<BatchRecord>((size_t)n * sizeof(BatchRecord));
+    lz77_batch_parse(J);
+    records.resize_discard(n);
+    dev_d2h(records.data(), J.records, (size_t)n * sizeof(BatchRecord));
+    // ---- command gather: the offsets from the per-item records (one small round trip)
+    offsets.resize_discard(n);
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+      if (records[i].overflow) throw std::runtime_error("brotli_mi355x: a batch chain ran out of its command slab");
+      offsets[i] = (uint32_t)total;
+      mbs[i].cmd_offset = (uint32_t)total;
+      mbs[i].n_cmds = records[i].n_cmds;
+      mbs[i].n_lits = records[i].n_lits;
+      mbs[i].uncompressed = records[i].uncompressed;
+      total += records[i].n_cmds;
+    }
+    uint32_t* offsets_dev = mem.uninit<uint32_t>((size_t)n * 4);
+    dev_h2d(offsets_dev, offsets.data(), (size_t)n * 4);
+    Command* cmds = mem.uninit<Command>((size_t)(total + 16) * sizeof(Command));
+    lz77_batch_gather(J, offsets_dev, cmds);
+    // ---- one meta-block per item
+    std::vector<uint8_t> out;
+    EncodeBatchMetaBlocks(p, text + packed_at, cmds, (uint32_t)total, &mbs, &out);
+    for (uint32_t i = 0; i < n; ++i) (*streams)[first + i].assign(out.begin() + (ptrdiff_t)mbs[i].out_byte, out.begin() + (ptrdiff_t)(mbs[i].out_byte + mbs[i].out_bytes));
+    first = last;
+  }
+}
+
+}  // namespace brotli_mi355x

@@ -18,11 +18,15 @@
 #include <string>
 #include <vector>
 
+#include "batch_greedy.h"
 #include "concat.h"
 #include "device_api.h"
 #include "encoder.h"
 #include "encoder_params.h"
 #include "fragment_stream.h"
+#if defined(BROTLI_HOST_EMU)
+#include "batch_greedy.inc"  // (the emulation build has no batch_greedy.cpp: its host plan and the emulation of its seam come in here)
+#endif
 
 using namespace brotli_mi355x;
 
@@ -997,8 +1001,13 @@ BROTLI_BOOL BrotliMi355xCompressDevice(int quality, int lgwin, BrotliEncoderMode
   return CompressOneShot(quality, lgwin, mode, input_size, input_device, true, encoded_size, encoded_host, stats);
 }
 
+// what BrotliMi355xLastBatchInfo reports: the last BrotliMi355xCompressBatch call of this thread
+static thread_local uint64_t g_batch_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+
 int32_t BrotliMi355xCompressBatch(int quality, int lgwin, BrotliEncoderMode mode, size_t count, const uint8_t* const* inputs,
                                   const size_t* input_sizes, uint8_t* const* outputs, size_t* output_sizes, int32_t* item_results) {
+  uint64_t info[8] = {count, 0, 0, 0, 0, 0, 0, 0};
+  memcpy(g_batch_info, info, sizeof(info));
   if (count == 0) return 1;
   size_t total = 0;
   for (size_t i = 0; i < count; ++i) total += input_sizes[i];
@@ -1010,36 +1019,48 @@ int32_t BrotliMi355xCompressBatch(int quality, int lgwin, BrotliEncoderMode mode
     SetParameter(&params, kParamMode, (uint32_t)mode);
     if (lgwin > 24) SetParameter(&params, kParamLargeWindow, 1);
     SmallCallGate gate(total);
-    if (!IsFragmentStream(params)) {
-      // every other quality: item by item through the one-shot path, on this thread (the same bytes, no gain in speed)
-      for (size_t i = 0; i < count; ++i) {
-        std::string error;
-        results[i] = CompressOneShot(quality, lgwin, mode, input_sizes[i], inputs[i], false, &output_sizes[i], outputs[i], nullptr, &error);
-        if (!error.empty()) throw std::runtime_error(error);  // (a device error, not a buffer that is too small: the call fails as a whole)
-        if (!results[i]) output_sizes[i] = 0;
+    const bool fragments = IsFragmentStream(params);
+    // The items an encoder sees and that go side by side on the device: every item of qualities 0 and 1 (fragment_stream.h), the
+    // items of one input block under an H5 hasher at qualities 5 .. 8 (batch_greedy.h).  Every other item goes through the one-shot
+    // path by itself, on this thread, in the caller's order (the same bytes, no gain in speed).
+    std::vector<size_t> item;
+    std::vector<const uint8_t*> in;
+    std::vector<size_t> in_size;
+    for (size_t i = 0; i < count; ++i) {
+      const int early = OneShotWithoutEncoder(input_sizes[i], &output_sizes[i], outputs[i]);
+      if (early >= 0) {
+        results[i] = early;
+        if (!early) output_sizes[i] = 0;
+        ++info[3];
+        continue;
       }
-    } else {
-      // the items an encoder sees, side by side on the device (fragment_stream.h)
-      std::vector<size_t> item;
-      std::vector<const uint8_t*> in;
-      std::vector<size_t> in_size;
-      for (size_t i = 0; i < count; ++i) {
-        const int early = OneShotWithoutEncoder(input_sizes[i], &output_sizes[i], outputs[i]);
-        if (early >= 0) {
-          results[i] = early;
-          if (!early) output_sizes[i] = 0;
-          continue;
-        }
+      if (fragments || BatchGreedyEligible(params, input_sizes[i])) {
         item.push_back(i);
         in.push_back(inputs[i]);
         in_size.push_back(input_sizes[i]);
+        continue;
       }
-      std::vector<std::vector<uint8_t>> streams;
-      if (!item.empty()) FragmentBatchCompress(params, item.size(), in.data(), in_size.data(), &streams);
-      for (size_t k = 0; k < item.size(); ++k) {
-        const size_t i = item[k];
-        results[i] = OneShotDeliver(streams[k].data(), streams[k].size(), inputs[i], input_sizes[i], false, output_sizes[i], &output_sizes[i], outputs[i]);
+      std::string error;
+      results[i] = CompressOneShot(quality, lgwin, mode, input_sizes[i], inputs[i], false, &output_sizes[i], outputs[i], nullptr, &error);
+      if (!error.empty()) throw std::runtime_error(error);  // (a device error, not a buffer that is too small: the call fails as a whole)
+      if (!results[i]) output_sizes[i] = 0;
+      ++info[2];
+    }
+    std::vector<std::vector<uint8_t>> streams;
+    if (!item.empty()) {
+      if (fragments) {
+        FragmentBatchCompress(params, item.size(), in.data(), in_size.data(), &streams);
+        info[4] = 1;
+      } else {
+        uint32_t groups = 0;
+        BatchGreedyCompress(params, item.size(), in.data(), in_size.data(), &streams, &groups);
+        info[4] = groups;
       }
+      info[1] = item.size();
+    }
+    for (size_t k = 0; k < item.size(); ++k) {
+      const size_t i = item[k];
+      results[i] = OneShotDeliver(streams[k].data(), streams[k].size(), inputs[i], input_sizes[i], false, output_sizes[i], &output_sizes[i], outputs[i]);
     }
   } catch (const std::exception& e) {
     // a device error fails the call as a whole
@@ -1048,6 +1069,7 @@ int32_t BrotliMi355xCompressBatch(int quality, int lgwin, BrotliEncoderMode mode
     if (item_results) memset(item_results, 0, count * sizeof(int32_t));
     return 0;
   }
+  memcpy(g_batch_info, info, sizeof(info));
   int32_t all = 1;
   for (size_t i = 0; i < count; ++i) {
     if (item_results) item_results[i] = results[i];
@@ -1055,6 +1077,8 @@ int32_t BrotliMi355xCompressBatch(int quality, int lgwin, BrotliEncoderMode mode
   }
   return all;
 }
+
+void BrotliMi355xLastBatchInfo(uint64_t info[8]) { memcpy(info, g_batch_info, sizeof(g_batch_info)); }
 
 int32_t BrotliEncoderCompressMulti(size_t num_params, const BrotliEncoderParameter* param_keys, const uint32_t* param_values,
                                    size_t input_size, const uint8_t* input_buffer, size_t* encoded_size, uint8_t* encoded,

@@ -9,6 +9,7 @@
 #include <chrono>
 #include <stdexcept>
 
+#include "batch_greedy.h"
 #include "device_api.h"
 #include "host_entropy.h"
 #include "lz77_stage.h"
@@ -211,6 +212,83 @@ void DecideContexts(const uint32_t* s, int quality, size_t size_hint, size_t len
     *num_contexts = 3;
     *map_id = 2;
   }
+}
+
+// The pools of the greedy splitters (metablock.rs:885-928) for these meta-blocks: per split kind the granules, their histogram rows,
+// the blocks and histograms a meta-block can come to, and the arrays that hold them; header scratch and output positions.
+void PlanGreedyPools(DevMem* mm, std::vector<MbDesc>* descs, MbBuffers* B) {
+  const uint32_t n_mb = (uint32_t)descs->size();
+  uint32_t gran_total[3] = {0, 0, 0}, row_total[3] = {0, 0, 0}, block_total[3] = {0, 0, 0}, histo_total[3] = {0, 0, 0};
+  for (uint32_t m = 0; m < n_mb; ++m) {
+    MbDesc& d = (*descs)[m];
+    d.n_symbols[0] = d.n_lits;
+    d.n_symbols[1] = d.n_cmds;
+    d.n_symbols[2] = d.n_dists;
+    for (uint32_t k = 0; k < 3; ++k) {
+      const uint32_t gl = kGranuleLen[k];
+      const uint32_t nc = k == 0 ? d.num_contexts : 1;
+      d.granule_base[k] = gran_total[k];
+      d.n_granules[k] = d.uncompressed ? 0 : (d.n_symbols[k] + gl - 1) / gl;
+      d.gran_row_base[k] = row_total[k];
+      d.block_base[k] = block_total[k];
+      d.max_blocks[k] = d.n_symbols[k] / gl + 1;
+      const uint32_t max_types = (k == 0 && nc > 1) ? 256 / nc : 256;
+      d.histo_base[k] = histo_total[k];
+      d.max_histos[k] = std::min(d.max_blocks[k], max_types + 1) * nc;
+      gran_total[k] += d.n_granules[k];
+      row_total[k] += d.n_granules[k] * nc;
+      block_total[k] += d.max_blocks[k] + 1;
+      histo_total[k] += d.max_histos[k];
+    }
+  }
+  std::vector<uint32_t> gran_mb_host[3];
+  for (uint32_t k = 0; k < 3; ++k) {
+    gran_mb_host[k].resize(gran_total[k] + 1);
+    for (uint32_t m = 0; m < n_mb; ++m)
+      for (uint32_t g = 0; g < (*descs)[m].n_granules[k]; ++g) gran_mb_host[k][(*descs)[m].granule_base[k] + g] = m;
+    B->n_granules[k] = gran_total[k];
+    B->gran_mb[k] = mm->alloc<uint32_t>(gran_total[k] + 1);
+    dev_h2d(B->gran_mb[k], gran_mb_host[k].data(), (size_t)gran_total[k] * 4);
+    B->gran_hist[k] = mm->alloc<uint16_t>((size_t)row_total[k] * kRowLen[k] + 8);
+    B->gran_block[k] = mm->alloc<uint16_t>(gran_total[k] + 8);
+    B->histo[k] = mm->alloc<uint32_t>((size_t)histo_total[k] * kRowLen[k] + 8);
+    B->depth[k] = mm->alloc<uint8_t>((size_t)histo_total[k] * kRowLen[k] + 8);
+    B->bits[k] = mm->alloc<uint16_t>((size_t)histo_total[k] * kRowLen[k] + 8);
+    B->tree_bits[k] = mm->alloc<uint64_t>((size_t)histo_total[k] * kTreeBitsWords + 8);
+    B->tree_nbits[k] = mm->alloc<uint32_t>(histo_total[k] + 8);
+    B->block_types[k] = mm->alloc<uint8_t>(block_total[k] + 8);
+    B->block_lengths[k] = mm->alloc<uint32_t>(block_total[k] + 8);
+    B->switch_bits[k] = mm->alloc<uint64_t>(block_total[k] + 8);
+    B->switch_nbits[k] = mm->alloc<uint8_t>(block_total[k] + 8);
+  }
+  B->header_words = mm->alloc<uint64_t>((size_t)n_mb * kHeaderWords);
+  B->ctxmap_scratch = mm->alloc<uint32_t>((size_t)n_mb * 2 * 256 * 64);
+  B->mb_out_bit = mm->alloc<uint64_t>(n_mb + 1);
+}
+
+// The tail of the emission: the headers of the compressed meta-blocks, the bytes of the stored ones and what the host composed, in
+// one upload and three launches however many there are.
+void PlaceHostPieces(DevMem* mm, const MbBuffers& B, const uint8_t* text, const std::vector<MbBitCopy>& headers, const std::vector<MbRawCopy>& raws,
+                     const std::vector<MbBitPiece>& pieces) {
+  const size_t bytes = headers.size() * sizeof(MbBitCopy) + raws.size() * sizeof(MbRawCopy) + pieces.size() * sizeof(MbBitPiece);
+  if (bytes == 0) return;
+  std::vector<uint8_t> blob(bytes);
+  uint8_t* at = blob.data();
+  if (!headers.empty()) memcpy(at, headers.data(), headers.size() * sizeof(MbBitCopy));
+  at += headers.size() * sizeof(MbBitCopy);
+  if (!raws.empty()) memcpy(at, raws.data(), raws.size() * sizeof(MbRawCopy));
+  at += raws.size() * sizeof(MbRawCopy);
+  if (!pieces.empty()) memcpy(at, pieces.data(), pieces.size() * sizeof(MbBitPiece));
+  uint8_t* blob_dev = mm->alloc<uint8_t>(bytes + 64);
+  dev_h2d(blob_dev, blob.data(), bytes);
+  const MbBitCopy* headers_dev = (const MbBitCopy*)blob_dev;
+  const MbRawCopy* raws_dev = (const MbRawCopy*)(blob_dev + headers.size() * sizeof(MbBitCopy));
+  const MbBitPiece* pieces_dev = (const MbBitPiece*)(blob_dev + headers.size() * sizeof(MbBitCopy) + raws.size() * sizeof(MbRawCopy));
+  // (a grid dimension holds 65 535 items)
+  for (size_t i = 0; i < headers.size(); i += 32768) mb_copy_bits_batch(B.out_words, B.header_words, headers_dev + i, (uint32_t)std::min<size_t>(32768, headers.size() - i));
+  for (size_t i = 0; i < raws.size(); i += 32768) mb_raw_copies((uint8_t*)B.out_words, text, raws_dev + i, (uint32_t)std::min<size_t>(32768, raws.size() - i));
+  mb_place_pieces(B.out_words, pieces_dev, (uint32_t)pieces.size());
+  dev_sync();  // (blob is host memory that goes out of scope)
 }
 
 struct Clock {
@@ -847,53 +925,7 @@ void EncodeStream(const EncodeRequest& req, std::vector<uint8_t>* out, EncodeSta
                          &descs[m].num_contexts, &descs[m].context_map_id);
         }
       }
-      // pools
-      uint32_t gran_total[3] = {0, 0, 0}, row_total[3] = {0, 0, 0}, block_total[3] = {0, 0, 0}, histo_total[3] = {0, 0, 0};
-      for (uint32_t m = 0; m < n_mb; ++m) {
-        MbDesc& d = descs[m];
-        d.n_symbols[0] = d.n_lits;
-        d.n_symbols[1] = d.n_cmds;
-        d.n_symbols[2] = d.n_dists;
-        for (uint32_t k = 0; k < 3; ++k) {
-          const uint32_t gl = kGranuleLen[k];
-          const uint32_t nc = k == 0 ? d.num_contexts : 1;
-          d.granule_base[k] = gran_total[k];
-          d.n_granules[k] = d.uncompressed ? 0 : (d.n_symbols[k] + gl - 1) / gl;
-          d.gran_row_base[k] = row_total[k];
-          d.block_base[k] = block_total[k];
-          d.max_blocks[k] = d.n_symbols[k] / gl + 1;
-          const uint32_t max_types = (k == 0 && nc > 1) ? 256 / nc : 256;
-          d.histo_base[k] = histo_total[k];
-          d.max_histos[k] = std::min(d.max_blocks[k], max_types + 1) * nc;
-          gran_total[k] += d.n_granules[k];
-          row_total[k] += d.n_granules[k] * nc;
-          block_total[k] += d.max_blocks[k] + 1;
-          histo_total[k] += d.max_histos[k];
-        }
-      }
-      std::vector<uint32_t> gran_mb_host[3];
-      for (uint32_t k = 0; k < 3; ++k) {
-        gran_mb_host[k].resize(gran_total[k] + 1);
-        for (uint32_t m = 0; m < n_mb; ++m)
-          for (uint32_t g = 0; g < descs[m].n_granules[k]; ++g) gran_mb_host[k][descs[m].granule_base[k] + g] = m;
-        B.n_granules[k] = gran_total[k];
-        B.gran_mb[k] = mm.alloc<uint32_t>(gran_total[k] + 1);
-        dev_h2d(B.gran_mb[k], gran_mb_host[k].data(), (size_t)gran_total[k] * 4);
-        B.gran_hist[k] = mm.alloc<uint16_t>((size_t)row_total[k] * kRowLen[k] + 8);
-        B.gran_block[k] = mm.alloc<uint16_t>(gran_total[k] + 8);
-        B.histo[k] = mm.alloc<uint32_t>((size_t)histo_total[k] * kRowLen[k] + 8);
-        B.depth[k] = mm.alloc<uint8_t>((size_t)histo_total[k] * kRowLen[k] + 8);
-        B.bits[k] = mm.alloc<uint16_t>((size_t)histo_total[k] * kRowLen[k] + 8);
-        B.tree_bits[k] = mm.alloc<uint64_t>((size_t)histo_total[k] * kTreeBitsWords + 8);
-        B.tree_nbits[k] = mm.alloc<uint32_t>(histo_total[k] + 8);
-        B.block_types[k] = mm.alloc<uint8_t>(block_total[k] + 8);
-        B.block_lengths[k] = mm.alloc<uint32_t>(block_total[k] + 8);
-        B.switch_bits[k] = mm.alloc<uint64_t>(block_total[k] + 8);
-        B.switch_nbits[k] = mm.alloc<uint8_t>(block_total[k] + 8);
-      }
-      B.header_words = mm.alloc<uint64_t>((size_t)n_mb * kHeaderWords);
-      B.ctxmap_scratch = mm.alloc<uint32_t>((size_t)n_mb * 2 * 256 * 64);
-      B.mb_out_bit = mm.alloc<uint64_t>(n_mb + 1);
+      PlanGreedyPools(&mm, &descs, &B);
       dev_h2d(B.descs, descs.data(), n_mb * sizeof(MbDesc));
       stats.ms_phase[1] += clk.lap(prof, "mb1");
       mb_granule_histograms(B);
@@ -998,26 +1030,7 @@ void EncodeStream(const EncodeRequest& req, std::vector<uint8_t>* out, EncodeSta
       for (const RawCopy& rc : copies) raws.push_back({rc.dst_byte, rc.src_pos, rc.bytes});
       std::vector<MbBitPiece> pieces;
       for (const BitPiece& bp : bits.pieces) pieces.push_back({bp.pos, bp.nbits, 0, bp.bits});
-      const size_t bytes = headers.size() * sizeof(MbBitCopy) + raws.size() * sizeof(MbRawCopy) + pieces.size() * sizeof(MbBitPiece);
-      if (bytes != 0) {
-        std::vector<uint8_t> blob(bytes);
-        uint8_t* at = blob.data();
-        memcpy(at, headers.data(), headers.size() * sizeof(MbBitCopy));
-        at += headers.size() * sizeof(MbBitCopy);
-        memcpy(at, raws.data(), raws.size() * sizeof(MbRawCopy));
-        at += raws.size() * sizeof(MbRawCopy);
-        memcpy(at, pieces.data(), pieces.size() * sizeof(MbBitPiece));
-        uint8_t* blob_dev = mm.alloc<uint8_t>(bytes + 64);
-        dev_h2d(blob_dev, blob.data(), bytes);
-        const MbBitCopy* headers_dev = (const MbBitCopy*)blob_dev;
-        const MbRawCopy* raws_dev = (const MbRawCopy*)(blob_dev + headers.size() * sizeof(MbBitCopy));
-        const MbBitPiece* pieces_dev = (const MbBitPiece*)(blob_dev + headers.size() * sizeof(MbBitCopy) + raws.size() * sizeof(MbRawCopy));
-        // (a grid dimension holds 65 535 items)
-        for (size_t i = 0; i < headers.size(); i += 32768) mb_copy_bits_batch(B.out_words, B.header_words, headers_dev + i, (uint32_t)std::min<size_t>(32768, headers.size() - i));
-        for (size_t i = 0; i < raws.size(); i += 32768) mb_raw_copies((uint8_t*)B.out_words, text, raws_dev + i, (uint32_t)std::min<size_t>(32768, raws.size() - i));
-        mb_place_pieces(B.out_words, pieces_dev, (uint32_t)pieces.size());
-        dev_sync();  // (blob is host memory that goes out of scope)
-      }
+      PlaceHostPieces(&mm, B, text, headers, raws, pieces);
     }
     stats.ms_phase[7] += clk.lap(prof, "mb7");
     if (req.direct_out) {
@@ -1129,5 +1142,198 @@ void EncodeStream(const EncodeRequest& req, std::vector<uint8_t>* out, EncodeSta
   for (int i = 1; i < 9; ++i) stats.ms_metablock += stats.ms_phase[i];
   if (stats_out) *stats_out = stats;
 }
+
+// The meta-block stage for the items of a batch group (batch_greedy.h): what EncodeStream does between its MbBuffers set-up and
+// the emission, for n streams of one meta-block each instead of one stream of n meta-blocks.  The kernels are the same; they take
+// a meta-block's context bytes, ISLAST bit and output position from its descriptor, and that is all a stream of its own needs:
+// prev_byte = prev_byte2 = 0 (the first two literals of an item must not see the neighbour in front of it in the text),
+// is_last = 1, the window bits in front, and every stream on an 8-byte boundary of the group's output.  `text` holds the items
+// back to back, so that the running sum of the command lengths is the text position, as in one stream.  The size fallback
+// (encode.rs:2141-2163) is per item: nothing follows an item, so it is flipped to stored and laid out again without a second parse.
+void EncodeBatchMetaBlocks(const EncoderParams& p, const uint8_t* text, const Command* cmds_dev, uint32_t n_cmds,
+                           std::vector<BatchStreamItem>* items_io, std::vector<uint8_t>* out) {
+  std::vector<BatchStreamItem>& items = *items_io;
+  const uint32_t n_mb = (uint32_t)items.size();
+  out->clear();
+  if (n_mb == 0) return;
+  if (p.quality < 5 || p.quality > 9 || p.large_window || p.appendable || p.byte_align || p.magic_number)
+    throw std::runtime_error("brotli_mi355x: parameters the batch meta-block stage does not take");
+  uint64_t L64 = 0;
+  for (const BatchStreamItem& it : items) L64 += it.n_lits;
+  const uint32_t K = n_cmds, L = (uint32_t)L64;
+  bool all_raw = true;
+  for (const BatchStreamItem& it : items) all_raw = all_raw && it.uncompressed;
+
+  DevMem mm;
+  MbBuffers B{};
+  const DeviceTables& dt = dev_tables();
+  B.text = text;
+  B.cmds = cmds_dev;
+  B.n_cmds = K;
+  B.n_lits = L;
+  B.n_mb = n_mb;
+  B.text_base = 0;
+  B.utf8_lut = dt.utf8_context_lookup;
+  B.signed_lut = dt.signed_context_lookup;
+  B.et.logs_16 = dt.logs_16;
+  B.et.logs_8 = dt.logs_8;
+  B.header_stride = kHeaderWords;
+  B.descs = mm.alloc<MbDesc>(n_mb);
+  B.results = mm.alloc<MbResult>(n_mb);
+  std::vector<MbDesc> descs(n_mb);
+  {
+    uint32_t lit_base = 0;
+    for (uint32_t m = 0; m < n_mb; ++m) {
+      MbDesc& d = descs[m];
+      memset(&d, 0, sizeof(d));
+      d.start = items[m].start;
+      d.end = items[m].start + items[m].bytes;
+      d.cmd_offset = items[m].cmd_offset;
+      d.n_cmds = items[m].n_cmds;
+      d.n_lits = items[m].n_lits;
+      d.lit_base = lit_base;
+      lit_base += d.n_lits;
+      d.context_mode = 2;  // ChooseContextMode: UTF8 below quality 10 unless forced (encode.rs:1357-1377)
+      switch (p.mode) {
+        case 3: d.context_mode = 0; break;
+        case 4: d.context_mode = 1; break;
+        case 6: d.context_mode = 3; break;
+        default: break;
+      }
+      d.uncompressed = items[m].uncompressed ? 1 : 0;
+      d.is_last = 1;
+      d.prev_byte = d.prev_byte2 = 0;  // a stream starts here
+      d.num_distance_symbols = p.dist.alphabet_size;
+      d.dist_postfix_bits = p.dist.distance_postfix_bits;
+      d.num_direct_distance_codes = p.dist.num_direct_distance_codes;
+      d.num_contexts = 1;
+      d.simple = kMbGreedy;
+    }
+  }
+  std::vector<MbResult> results(n_mb);
+  std::vector<uint32_t> body_off(n_mb + 1, 0);
+  if (!all_raw) {
+    B.cmd_lit_start = mm.alloc<uint32_t>((size_t)K + 1);
+    B.cmd_pos = mm.alloc<uint32_t>((size_t)K + 1);
+    B.cmd_dist_index = mm.alloc<uint32_t>((size_t)K + 1);
+    B.lit_pos = mm.alloc<uint32_t>((size_t)L + 1);
+    B.lit_cmd = mm.alloc<uint32_t>((size_t)L + 1);
+    B.lit_nbits = mm.alloc<uint32_t>((size_t)L + 1);
+    B.cmd_nbits = mm.alloc<uint32_t>((size_t)K + 1);
+    B.cmd_own_bits = mm.alloc<uint32_t>((size_t)K + 1);
+    void* scan_scratch = mm.alloc<uint8_t>(mb_scan_scratch_bytes(std::max<size_t>(K, L) + 2));
+    dev_h2d(B.descs, descs.data(), n_mb * sizeof(MbDesc));
+    uint32_t* boundary_words = mm.alloc<uint32_t>(n_mb + 1);
+    mb_command_scans(B, scan_scratch);
+    mb_literal_map(B);
+    {
+      std::vector<uint32_t> di(n_mb + 1);
+      mb_gather_at_metablock_starts(B, B.cmd_dist_index, boundary_words);
+      dev_d2h(di.data(), boundary_words, (n_mb + 1) * 4);
+      for (uint32_t m = 0; m < n_mb; ++m) {
+        descs[m].dist_base = di[m];
+        descs[m].n_dists = di[m + 1] - di[m];
+      }
+      B.n_dists = di[n_mb];
+    }
+    // literal context modelling decision, with the size hint of the item's own stream
+    if (p.disable_literal_context_modeling == 0) {
+      uint32_t* stats_dev = mm.alloc<uint32_t>((size_t)n_mb * kContextStatsWords);
+      mb_context_stats(B, stats_dev);
+      std::vector<uint32_t> cs((size_t)n_mb * kContextStatsWords);
+      dev_d2h(cs.data(), stats_dev, cs.size() * 4);
+      if (getenv("BROTLI_MI355X_SELFTEST")) SelfTestContextStats(text, descs, cs);
+      for (uint32_t m = 0; m < n_mb; ++m) {
+        if (descs[m].uncompressed) continue;
+        DecideContexts(cs.data() + (size_t)m * kContextStatsWords, p.quality, items[m].bytes, items[m].bytes, &descs[m].num_contexts,
+                       &descs[m].context_map_id);
+      }
+    }
+    PlanGreedyPools(&mm, &descs, &B);
+    dev_h2d(B.descs, descs.data(), n_mb * sizeof(MbDesc));
+    mb_granule_histograms(B);
+    bool wide = false;
+    for (uint32_t m = 0; m < n_mb; ++m) wide = wide || (!descs[m].uncompressed && descs[m].num_contexts > 3);
+    mb_split_chains(B, wide);
+    dev_d2h(results.data(), B.results, n_mb * sizeof(MbResult));
+    // Huffman codes: one job per histogram
+    std::vector<CodeJob> jobs;
+    for (uint32_t m = 0; m < n_mb; ++m) {
+      if (descs[m].uncompressed) continue;
+      for (uint32_t k = 0; k < 3; ++k)
+        for (uint32_t i = 0; i < results[m].num_histos[k]; ++i) jobs.push_back({k, descs[m].histo_base[k] + i, descs[m].num_distance_symbols, kCodeOptimized});
+    }
+    B.huff_scratch = mm.alloc<HuffmanScratch>(std::max<size_t>(jobs.size(), n_mb) + 1);
+    CodeJob* jobs_dev = mm.alloc<CodeJob>(jobs.size() + 1);
+    dev_h2d(jobs_dev, jobs.data(), jobs.size() * sizeof(CodeJob));
+    mb_build_codes(B, jobs_dev, (uint32_t)jobs.size());
+    mb_write_headers(B);
+    mb_symbol_bits(B, scan_scratch);
+    mb_gather_at_metablock_starts(B, B.cmd_nbits, boundary_words);
+    dev_d2h_async(results.data(), B.results, n_mb * sizeof(MbResult));
+    dev_d2h_async(body_off.data(), boundary_words, (n_mb + 1) * 4);
+    dev_sync();
+  }
+
+  // ---- layout: every item a stream of its own (WriteMetaBlockInternal, encode.rs:1941-2167)
+  HostBits bits;
+  std::vector<uint64_t> mb_out_bit(n_mb + 1, 0);
+  std::vector<MbRawCopy> raws;
+  std::vector<MbBitCopy> headers;
+  bool flipped = false;
+  for (uint32_t m = 0; m < n_mb; ++m) {
+    MbDesc& d = descs[m];
+    bits.pos = (bits.pos + 63) & ~(uint64_t)63;
+    const uint64_t stream_bit = bits.pos;
+    // stream header: window bits (EncodeWindowBits, encode.rs:603-625), lgwin 17 .. 24
+    if (p.lgwin == 17) {
+      bits.put(7, 1);
+    } else {
+      bits.put(4, (uint64_t)(((p.lgwin - 17) << 1) | 1));
+    }
+    const uint32_t bytes = d.end - d.start;
+    if (!d.uncompressed) {
+      const uint64_t start_bit = bits.pos;
+      const uint64_t end_bit = (start_bit + results[m].header_bits + (body_off[m + 1] - body_off[m]) + 7) & ~(uint64_t)7;
+      if ((uint64_t)bytes + 4 + ((start_bit - stream_bit) >> 3) < ((end_bit - stream_bit) >> 3)) {  // encode.rs:2141-2163
+        d.uncompressed = 1;
+        flipped = true;
+      } else {
+        mb_out_bit[m] = start_bit;
+        headers.push_back({start_bit, (uint64_t)m * B.header_stride, results[m].header_bits});
+        bits.pos = end_bit;
+      }
+    }
+    if (d.uncompressed) {
+      WriteUncompressedHeader(bytes, &bits);
+      raws.push_back({bits.pos >> 3, d.start, bytes});
+      bits.pos += (uint64_t)bytes * 8;
+      bits.put(1, 1);
+      bits.put(1, 1);
+      bits.jump_to_byte_boundary();
+    }
+    items[m].uncompressed = d.uncompressed;
+    items[m].out_byte = stream_bit >> 3;
+    items[m].out_bytes = (bits.pos - stream_bit) >> 3;
+  }
+  // ---- emission
+  const size_t all_bytes = (size_t)((bits.pos + 7) >> 3);
+  const size_t out_words = all_bytes / 8 + 4;
+  B.out_words = mm.alloc<uint64_t>(out_words);
+  if (!all_raw) {
+    if (flipped) dev_h2d(B.descs, descs.data(), n_mb * sizeof(MbDesc));
+    dev_h2d(B.mb_out_bit, mb_out_bit.data(), (n_mb + 1) * 8);
+    mb_emit(B);
+    if (getenv("BROTLI_MI355X_SELFTEST")) SelfTestEmit(B, out_words);
+  }
+  {
+    std::vector<MbBitPiece> pieces;
+    for (const BitPiece& bp : bits.pieces) pieces.push_back({bp.pos, bp.nbits, 0, bp.bits});
+    PlaceHostPieces(&mm, B, text, headers, raws, pieces);
+  }
+  out->resize(all_bytes);
+  dev_d2h_bulk(out->data(), B.out_words, all_bytes);
+}
+
 
 }  // namespace brotli_mi355x

@@ -23,6 +23,7 @@
 #include "device_scan.h"
 #include "lz77_parse_args.h"
 #include "zopfli_device.h"
+#include "batch_greedy_device.h"
 
 namespace brotli_mi355x {
 
@@ -2493,6 +2494,82 @@ void lz77_live_parse(const Lz77Params& P, const Lz77Buffers& B, const LiveBuffer
   } else {
     hipLaunchKernelGGL((k_parse_live<false>), dim3(count), dim3(64), 0, BR_STREAM, a);
   }
+  HIP_CHECK(hipGetLastError());
+}
+
+// ---- batch_greedy.h: the small items of a batch, one live chain each
+static ChainTables batch_chain_tables(const BatchParseJob& J) {
+  const DeviceTables& dt = dev_tables();
+  ChainTables T;
+  T.text = J.text;
+  T.info = nullptr;
+  T.sorted = nullptr;
+  T.sorted_tag = nullptr;
+  T.rows = nullptr;
+  T.run_end = nullptr;
+  T.search_log = nullptr;
+  T.flags_next = J.flags;
+  T.cmds = J.slabs;
+  T.dict_hash = dt.dict_hash;
+  T.dict_data = dt.dict_data;
+  T.dict_offsets_by_length = dt.dict_offsets_by_length;
+  T.dict_size_bits_by_length = dt.dict_size_bits_by_length;
+  T.dist_postfix_bits = J.P.dist_postfix_bits;
+  T.num_direct_distance_codes = J.P.num_direct_distance_codes;
+  T.work = nullptr;
+  T.keys = J.keys;
+  T.logs.logs_16 = dt.logs_16;
+  T.logs.logs_8 = dt.logs_8;
+  return T;
+}
+
+// One wavefront per table, persistent over the group: it takes the next place of `order` (largest item first) from the device
+// counter until none is left.  Like k_parse_live a chain is bound by the latency of its own dependent loads; the throughput of
+// the launch is the number of chains in flight.
+template <bool kRows>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_parse_batch(BatchParseJob J, ChainTables T) {
+  __shared__ ChainScratchT<false, kRows> scratch;
+  __shared__ uint32_t histo[256];
+  const uint32_t table = blockIdx.x;
+  if (table >= J.tables) return;
+  for (;;) {
+    uint32_t mine = 0;
+    if (threadIdx.x == 0) mine = atomicAdd(J.counter, 1u);
+    const uint32_t place = BR_UNIFORM(mine);
+    if (place >= J.n_items) break;
+    const uint32_t index = BR_UNIFORM(J.order[place]);
+    if (index >= J.n_items) break;  // (never: the plan's order is a permutation)
+    br_batch_item<kRows>(J, T, scratch, histo, index, table);
+  }
+}
+
+void lz77_batch_parse(const BatchParseJob& J) {
+  if (J.n_items == 0) return;
+  if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
+  const ChainTables T = batch_chain_tables(J);
+  const uint32_t grid = J.tables < J.n_items ? J.tables : J.n_items;
+  if ((1u << J.P.block_bits) <= kRowEntries) {
+    hipLaunchKernelGGL((k_parse_batch<true>), dim3(grid), dim3(64), 0, BR_STREAM, J, T);
+  } else if (J.P.block_bits <= 7) {
+    hipLaunchKernelGGL((k_parse_batch<false>), dim3(grid), dim3(64), 0, BR_STREAM, J, T);
+  } else {
+    throw std::runtime_error("brotli_mi355x: the batch chains do not run the 512-deep rings");
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+__global__ __launch_bounds__(256) void k_batch_gather(BatchParseJob J, const uint32_t* __restrict__ offsets, Command* __restrict__ out) {
+  const uint32_t i = blockIdx.x;
+  const BatchItem it = J.items[i];
+  const BatchRecord r = J.records[i];
+  if (r.overflow || r.n_cmds > it.cmd_cap) return;
+  Command* dst = out + offsets[i];
+  for (uint32_t c = threadIdx.x; c < r.n_cmds; c += blockDim.x) dst[c] = br_batch_command(J, it, r, c);
+}
+
+void lz77_batch_gather(const BatchParseJob& J, const uint32_t* offsets_dev, Command* out) {
+  if (J.n_items == 0) return;
+  hipLaunchKernelGGL(k_batch_gather, dim3(J.n_items), dim3(256), 0, BR_STREAM, J, offsets_dev, out);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/batch_probe.py -- what BrotliMi355xCompressBatch buys for many small payloads (qualities 0 and 1, lgwin 22).
+"""tools/batch_probe.py -- what BrotliMi355xCompressBatch buys for many small payloads (--qualities, default 0 and 1; lgwin 22).
 
 For every class of items (seeded markov text and synth.mixed):
   batch     the batch call on all items (host clock around the synchronous call, warm-up, median and spread of the repeats)
@@ -9,6 +9,11 @@ For every class of items (seeded markov text and synth.mixed):
             (the items of a class are independent draws, so the first ones are a fair sample of it)
 and the A/B of the two homes of a small fragment's hash table: the classes whose tables fit workgroup memory -- 512 B items (2^9
 words) and 2 KiB items (2^11 words) -- and the log-uniform mix, with BROTLI_MI355X_BATCH_LDS_BITS=0 and =11, alternating.
+
+With --qualities 5,8 (the items of one input block side by side, batch_greedy.h) the baseline of the parent commit is the same
+BrotliMi355xCompressBatch call on its library -- there a loop over the one-shot path -- on the first --loop-items items, scaled by
+item count, and the loop from 4 threads; --rounds 3 alternates this build and the parent (one child each) and records whether every
+run of this build beats every run of the parent.  The table-home A/B belongs to qualities 0 and 1 and is skipped otherwise.
 
 Every measurement runs in a child process of its own (the table's home is one setting per process, read once; the parent's library
 is another shared object), one after the other, each under its own time limit; the first failure ends the probe.
@@ -78,6 +83,7 @@ def bind(path):
 def measure_batch(lib_path, items, quality, runs, warmup):
     L = bind(lib_path)
     L.BrotliMi355xCompressBatch.restype = ctypes.c_int32
+    info = (ctypes.c_uint64 * 8)()
     n = len(items)
     caps = [L.BrotliEncoderMaxCompressedSize(len(x)) + 16 for x in items]
     bufs = [ctypes.create_string_buffer(c) for c in caps]
@@ -95,7 +101,9 @@ def measure_batch(lib_path, items, quality, runs, warmup):
         assert ok == 1
         if it >= warmup:
             times.append(dt)
-    return times, sum(out_sizes)
+    if hasattr(L, "BrotliMi355xLastBatchInfo"):  # (the parent's library has none)
+        L.BrotliMi355xLastBatchInfo(info)
+    return times, sum(out_sizes), list(info)
 
 
 def measure_loop(lib_path, items, quality, threads, runs, warmup):
@@ -144,11 +152,11 @@ def child(args):
         for data in (["text"] if CLASSES[name][0] == "alice" else ["text", "mixed"]):
             items = items_of(name, data)
             first = items[:args.loop_items]
-            for quality in (0, 1):
+            for quality in [int(q) for q in args.qualities.split(",")]:
                 row = {"class": name, "data": data, "quality": quality, "items": len(items), "bytes": sum(map(len, items))}
                 if args.child == "batch":
-                    times, csize = measure_batch(args.lib, items, quality, args.runs, args.warmup)
-                    row.update(stats(times), compressed_bytes=csize)
+                    times, csize, info = measure_batch(args.lib, first if args.first_only else items, quality, args.runs, args.warmup)
+                    row.update(stats(times), compressed_bytes=csize, batch_info=info, measured_items=len(first) if args.first_only else len(items))
                 elif args.child == "loop":
                     row.update(stats(measure_loop(args.lib, first, quality, args.threads, args.runs, 1)), threads=args.threads, measured_items=len(first))
                 else:
@@ -159,14 +167,14 @@ def child(args):
         json.dump(out, f)
 
 
-def run_child(args, what, classes, lib=None, lds=None, threads=1, limit=600):
+def run_child(args, what, classes, lib=None, lds=None, threads=1, limit=600, first_only=False):
     env = dict(os.environ)
     env.pop("BROTLI_MI355X_BATCH_LDS_BITS", None)
     if lds is not None:
         env["BROTLI_MI355X_BATCH_LDS_BITS"] = str(lds)
     tmp = os.path.join(os.path.dirname(os.path.abspath(args.out)), ".batch_probe_child.json")
     cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--child", what, "--classes", ",".join(classes), "--lib", lib or args.lib,
-           "--threads", str(threads), "--runs", str(args.runs), "--warmup", str(args.warmup), "--loop-items", str(args.loop_items), "--child-out", tmp]
+           "--threads", str(threads), "--runs", str(args.runs), "--warmup", str(args.warmup), "--loop-items", str(args.loop_items), "--child-out", tmp, "--qualities", args.qualities] + (["--first-only"] if first_only else [])
     r = subprocess.run(cmd, env=env)
     if r.returncode != 0:
         raise SystemExit("batch_probe: %s (lds=%s, threads=%d) ended with status %d: nothing more is started" % (what, lds, threads, r.returncode))
@@ -189,6 +197,10 @@ def main():
     ap.add_argument("--loop-items", type=int, default=256)
     ap.add_argument("--ab-rounds", type=int, default=3, help="how often the A/B alternates between the two settings")
     ap.add_argument("--skip", default="", help="comma list of: headline, ab")
+    ap.add_argument("--qualities", default="0,1", help="comma list of qualities")
+    ap.add_argument("--rounds", type=int, default=1, help="how often this build and the parent's batch call alternate (qualities other than 0 and 1)")
+    ap.add_argument("--only", default="", help="comma list of headline classes (default: all)")
+    ap.add_argument("--first-only", action="store_true")
     ap.add_argument("--child", default=None)
     ap.add_argument("--classes", default="")
     ap.add_argument("--threads", type=int, default=1)
@@ -206,7 +218,9 @@ def main():
         with open(args.out, "w") as f:
             json.dump(doc, f, indent=1)
 
-    if "ab" not in skip:
+    headline = [c for c in HEADLINE if not args.only or c in args.only.split(",")]
+    fragment_qualities = set(args.qualities.split(",")) <= {"0", "1"}
+    if "ab" not in skip and fragment_qualities:
         # the table's home: device memory (0) against workgroup memory (11, the largest the library keeps there), the same jobs,
         # alternating: device, workgroup, device, workgroup ... one child each
         ab = {}
@@ -226,11 +240,22 @@ def main():
         save()
     if "headline" not in skip:
         rows = {}
-        for row in run_child(args, "batch", HEADLINE):
-            rows[key(row)] = {"items": row["items"], "bytes": row["bytes"], "compressed_bytes": row["compressed_bytes"], "batch": {k: row[k] for k in ("median_ms", "min_ms", "max_ms", "spread_pct", "runs")}}
-        doc["classes"] = rows
-        save()
-        for row in run_child(args, "cpu", HEADLINE):
+        for rnd in range(args.rounds):
+            for row in run_child(args, "batch", headline, limit=900):
+                this = {k: row[k] for k in ("median_ms", "min_ms", "max_ms", "spread_pct", "runs")}
+                if rnd == 0:
+                    rows[key(row)] = {"items": row["items"], "bytes": row["bytes"], "compressed_bytes": row["compressed_bytes"], "batch_info": row["batch_info"], "batch": this}
+                rows[key(row)].setdefault("batch_rounds", []).append(this)
+            doc["classes"] = rows
+            save()
+            if args.parent_lib and not fragment_qualities:
+                # the parent's own batch call: a loop over its one-shot path on the calling thread
+                for row in run_child(args, "batch", headline, lib=os.path.abspath(args.parent_lib), limit=900, first_only=True):
+                    scale = row["items"] / row["measured_items"]
+                    rows[key(row)].setdefault("parent_batch_rounds", []).append({"median_ms_scaled": round(row["median_ms"] * scale, 3), "min_ms_scaled": round(row["min_ms"] * scale, 3),
+                                                                               "max_ms_scaled": round(row["max_ms"] * scale, 3), "spread_pct": row["spread_pct"], "measured_items": row["measured_items"]})
+                save()
+        for row in run_child(args, "cpu", headline):
             scale = row["items"] / row["measured_items"]
             rows[key(row)]["cpu_one_core"] = {"median_ms_scaled": round(row["median_ms"] * scale, 3), "measured_items": row["measured_items"], "spread_pct": row["spread_pct"]}
         save()
@@ -239,7 +264,9 @@ def main():
                 for v in rows.values():
                     v["loop_%dt" % threads] = "not measured"
                 continue
-            for row in run_child(args, "loop", HEADLINE, lib=os.path.abspath(args.parent_lib), threads=threads, limit=900):
+            if threads == 1 and not fragment_qualities:
+                continue  # (the parent's batch call above is that loop)
+            for row in run_child(args, "loop", headline, lib=os.path.abspath(args.parent_lib), threads=threads, limit=900):
                 scale = row["items"] / row["measured_items"]
                 rows[key(row)]["loop_%dt" % threads] = {"median_ms_scaled": round(row["median_ms"] * scale, 3), "measured_items": row["measured_items"], "spread_pct": row["spread_pct"]}
             save()
@@ -249,6 +276,10 @@ def main():
             v["batch_MBps"] = round(v["bytes"] / 1e3 / b, 1)
             v["cpu_over_batch"] = round(v["cpu_one_core"]["median_ms_scaled"] / b, 3)
             v["better_loop_over_batch"] = round(min(loops) / b, 2) if loops else "not measured"
+            if v.get("parent_batch_rounds"):
+                parent = v["parent_batch_rounds"]
+                v["parent_batch_over_batch"] = round(statistics.median(r["median_ms_scaled"] for r in parent) / statistics.median(r["median_ms"] for r in v["batch_rounds"]), 2)
+                v["every_run_beats_every_parent_run"] = bool(max(r["max_ms"] for r in v["batch_rounds"]) < min(r["min_ms_scaled"] for r in parent))
         save()
     print(json.dumps(doc, indent=1))
 
