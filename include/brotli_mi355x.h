@@ -211,9 +211,33 @@ BROTLI_BOOL BrotliMi355xCompressDevice(int quality, int lgwin, BrotliEncoderMode
 int32_t BrotliMi355xCompressBatch(int quality, int lgwin, BrotliEncoderMode mode, size_t count, const uint8_t* const* inputs,
                                   const size_t* input_sizes, uint8_t* const* outputs,
                                   size_t* output_sizes /* in: capacity, out: size */, int32_t* item_results /* may be NULL */);
-/* The last BrotliMi355xCompressBatch call of the calling thread: info[0] items, [1] items encoded side by side on the device,
-   [2] items run one by one through the one-shot path, [3] items answered without an encoder (empty input, capacity 0),
-   [4] device groups, [5..7] zero.  After a call that failed as a whole only info[0] is set. */
+/* The batch call with one custom dictionary shared by every item -- the call for thousands of small payloads of one kind (messages,
+   records, API responses), whose redundancy lies in what they share with each other rather than in themselves.
+   Item i is exactly the stream of: BrotliEncoderCreateInstance; BrotliEncoderSetParameter(QUALITY, LGWIN, MODE);
+   BrotliEncoderSetCustomDictionary(dict_size, dict); one BrotliEncoderCompressStream(BROTLI_OPERATION_FINISH) with all of
+   inputs[i] and enough room -- in bytes, size, success or failure.  A decoder needs the same dictionary.  The rules are the stream
+   API's: no size hint is set and there is no fallback to a stored stream above BrotliEncoderMaxCompressedSize (give every item
+   BrotliEncoderMaxCompressedSize(size) + 1024 bytes of room); a dictionary longer than (1 << lgwin) - 16 bytes is cut to its last
+   (1 << lgwin) - 16; with dict_size <= 1 and at qualities 0 / 1 the reference takes no dictionary and only makes the stream
+   catable and appendable.  dict may be NULL when dict_size is 0.  count == 0 returns 1.
+   An item whose stream does not fit its capacity fails alone (size 0, item_results[i] = 0), the others are produced and the call
+   returns 0.  So does an item on which the reference itself fails -- a match cut to one byte at the end of the dictionary, a copy
+   the format cannot express: BrotliMi355xLastError then says "the reference encoder fails on this input".  A device error fails
+   the whole call.
+   Side by side on the device (one upload of the dictionary per call, the text dictionary | item laid out there, one chain per
+   item on a hash table already holding the dictionary): qualities 5 .. 8, lgwin 17 .. 24, 2 <= dict_size <= 65536 and
+   1 <= input_sizes[i] <= 65536.  Everything else -- other qualities and windows, longer items, longer or shorter dictionaries, the
+   empty item -- is accepted and runs by itself through the stream path on the calling thread, in the same call and in the
+   caller's order: the same bytes, no gain in speed.  The environment of BrotliMi355xCompressBatch applies; a group's byte limit
+   counts one copy of the dictionary per item. */
+int32_t BrotliMi355xCompressBatchWithDictionary(int quality, int lgwin, BrotliEncoderMode mode, size_t dict_size, const uint8_t* dict,
+                                                size_t count, const uint8_t* const* inputs, const size_t* input_sizes,
+                                                uint8_t* const* outputs, size_t* output_sizes /* in: capacity, out: size */,
+                                                int32_t* item_results /* may be NULL */);
+/* The last BrotliMi355xCompressBatch / BrotliMi355xCompressBatchWithDictionary call of the calling thread: info[0] items, [1] items
+   encoded side by side on the device, [2] items run one by one (the one-shot path; with a dictionary the stream path), [3] items
+   answered without an encoder (empty input, capacity 0; none with a dictionary), [4] device groups, [5] dictionary bytes in use
+   after the reference's truncation (0 for the plain call), [6..7] zero.  After a call that failed as a whole only info[0] is set. */
 void BrotliMi355xLastBatchInfo(uint64_t info[8]);
 /* Human-readable description of the device backing the library ("hip:gfx950 (...)"). */
 const char* BrotliMi355xDeviceName(void);

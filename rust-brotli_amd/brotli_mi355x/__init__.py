@@ -88,6 +88,10 @@ def _bind(lib):
     lib.BrotliMi355xCompressBatch.restype = c_int32
     lib.BrotliMi355xCompressBatch.argtypes = [c_int, c_int, c_int, c_size_t, POINTER(c_char_p), POINTER(c_size_t), POINTER(c_void_p),
                                               POINTER(c_size_t), POINTER(c_int32)]
+    if hasattr(lib, "BrotliMi355xCompressBatchWithDictionary"):  # (absent from libraries built before the call existed)
+        lib.BrotliMi355xCompressBatchWithDictionary.restype = c_int32
+        lib.BrotliMi355xCompressBatchWithDictionary.argtypes = [c_int, c_int, c_int, c_size_t, c_char_p, c_size_t, POINTER(c_char_p), POINTER(c_size_t),
+                                                                POINTER(c_void_p), POINTER(c_size_t), POINTER(c_int32)]
     lib.BrotliMi355xDeviceName.restype = c_char_p
     lib.BrotliMi355xLastError.restype = c_char_p
     return lib
@@ -167,17 +171,22 @@ class Library(object):
             raise BrotliCompressorException("BrotliEncoderCompress failed: " + self.last_error())
         return ctypes.string_at(out, n.value)
 
-    def compress_batch(self, items, quality=0, lgwin=22, mode=0):
+    def compress_batch(self, items, quality=0, lgwin=22, mode=0, dictionary=None):
         """BrotliMi355xCompressBatch: every item becomes a stream of its own, the same bytes as compress(item, quality, lgwin,
         mode), in one call.  Side by side on the device (the call for many small payloads): every item at qualities 0 and 1, and
         at qualities 5 to 8 the items of at most 65 536 bytes at lgwin 17 to 24.  Everything else runs item by item in the same
-        call; last_batch_info() tells how the items of the last call were taken.  Returns a list of bytes."""
+        call; last_batch_info() tells how the items of the last call were taken.  Returns a list of bytes.
+
+        dictionary (bytes): BrotliMi355xCompressBatchWithDictionary -- every item is the stream of an Encoder(params, dictionary)
+        that gets the item in one finish(); a decoder needs the same dictionary.  Side by side at qualities 5 to 8, lgwin 17 to 24,
+        a dictionary of 2 to 65 536 bytes and items of 1 to 65 536 bytes."""
         items = [bytes(x) for x in items]
         count = len(items)
         if count == 0:
             return []
         sizes = [len(x) for x in items]
-        caps = [self.lib.BrotliEncoderMaxCompressedSize(n) + 16 for n in sizes]
+        # (the stream API has no fallback to a stored stream at BrotliEncoderMaxCompressedSize: room beyond it)
+        caps = [self.lib.BrotliEncoderMaxCompressedSize(n) + (16 if dictionary is None else 1024) for n in sizes]
         starts = [0] * count
         at = 0
         for i, cap in enumerate(caps):
@@ -190,15 +199,23 @@ class Library(object):
         outputs = (c_void_p * count)(*[base + s for s in starts])
         out_sizes = (c_size_t * count)(*caps)
         results = (c_int32 * count)()
-        if not self.lib.BrotliMi355xCompressBatch(quality, lgwin, mode, count, inputs, in_sizes, outputs, out_sizes, results):
+        if dictionary is None:
+            name = "BrotliMi355xCompressBatch"
+            ok = self.lib.BrotliMi355xCompressBatch(quality, lgwin, mode, count, inputs, in_sizes, outputs, out_sizes, results)
+        else:
+            name = "BrotliMi355xCompressBatchWithDictionary"
+            dictionary = bytes(dictionary)
+            ok = self.lib.BrotliMi355xCompressBatchWithDictionary(quality, lgwin, mode, len(dictionary), dictionary, count, inputs, in_sizes,
+                                                                  outputs, out_sizes, results)
+        if not ok:
             failed = [i for i in range(count) if not results[i]]
-            raise BrotliCompressorException("BrotliMi355xCompressBatch failed (items %s): %s" % (failed[:8], self.last_error()))
+            raise BrotliCompressorException("%s failed (items %s): %s" % (name, failed[:8], self.last_error()))
         view = memoryview(out)
         return [bytes(view[starts[i]:starts[i] + out_sizes[i]]) for i in range(count)]
 
     def last_batch_info(self):
         """BrotliMi355xLastBatchInfo: the last compress_batch call of this thread as a list of 8 integers -- [0] items, [1] items
-        encoded side by side on the device, [2] items run one by one, [3] items answered without an encoder, [4] device groups."""
+        encoded side by side on the device, [2] items run one by one, [3] items answered without an encoder, [4] device groups, [5] dictionary bytes in use (0 without one)."""
         info = (c_uint64 * 8)()
         self.lib.BrotliMi355xLastBatchInfo.restype = None
         self.lib.BrotliMi355xLastBatchInfo.argtypes = [POINTER(c_uint64)]

@@ -6,6 +6,12 @@
 // pass, one parse launch (k_parse_batch: one wavefront per item, each on a private table that it zeroes itself), one command
 // gather and one pass of the meta-block stage with one meta-block per item.  The streams come out of the same kernels as those
 // of the one-shot call, item by item the bytes BrotliEncoderCompress gives.
+//
+// With a shared custom dictionary (BrotliMi355xCompressBatchWithDictionary) an item is the stream of an encoder whose hasher
+// HasherPrependCustomDictionary (encode.rs:1163-1194) has primed: its text is `dictionary | item`, laid out on the device with the
+// dictionary's end abutting the item's first byte, and its chain starts on a table that already holds the dictionary.  What the
+// prepend leaves in the rings hangs on the dictionary and the hasher parameters alone, so it is built once per call (BatchDictImage:
+// the ring counters, and the list of (slot, position) the counters still cover) and replayed by every chain with independent stores.
 #ifndef BROTLI_MI355X_BATCH_GREEDY_H_
 #define BROTLI_MI355X_BATCH_GREEDY_H_
 
@@ -33,7 +39,18 @@ struct BatchRecord {
   uint32_t trailing;      // literals of the trailing insert-only command (0: there is none)
   uint32_t uncompressed;  // should_compress (encode.rs:1325-1354) said no
   uint32_t overflow;      // the slab was too small (cannot happen: a copy is at least two bytes long)
-  uint32_t pad[3];
+  uint32_t bad_commands;  // SegExit::bad_commands (a match cut to one byte at the dictionary end): the reference fails on this item;
+                          // the record then describes the item as one insert-only command, stored, so that the gather and the
+                          // meta-block stage never see the copy (its stream is dropped by the host)
+  uint32_t pad[2];
+};
+// What HasherPrependCustomDictionary leaves in an H5 table, in a form a chain can replay without a dependent chain of stores.
+struct BatchDictImage {
+  uint32_t bytes;           // D: dictionary bytes in use (0: no dictionary); an item parses [D, D + its bytes) of its own text
+  const uint16_t* num;      // [1 << bucket_bits]: the ring counters behind the prepend
+  const uint32_t* entries;  // [2 * *n_entries]: (slot in `buckets`, position) of every entry the counters still cover;
+                            // nullptr: no image, every chain files the dictionary itself (measurement only)
+  const uint32_t* n_entries;  // [1], on the device: at most D
 };
 struct BatchParseJob {
   Lz77Params P;  // of a stream that starts at 0; total_bytes is the item's and set per item
@@ -49,9 +66,19 @@ struct BatchParseJob {
   uint32_t* buckets;  // [tables][(1 << bucket_bits) << block_bits]
   uint32_t* counter;  // [1], zero: the next place of `order` to hand out
   BatchRecord* records;
+  BatchDictImage dict;  // bytes == 0: the plain call
 };
 // one wavefront per table; a wavefront takes items from `counter` until none is left
 void lz77_batch_parse(const BatchParseJob& J);
+// The dictionary path.  lz77_batch_dict_text: text[items[i].text_off - dict_bytes ..) = dictionary | item i (packed + starts[i]) for
+// every item; `text` is zero where nothing is written, text_off is a multiple of 64 and at least dict_bytes rounded up to 16.
+// dict_shifted_dev: 16-byte aligned, (-dict_bytes & 15) zero bytes and then the dictionary, so that it ends on a 16-byte boundary.
+void lz77_batch_dict_text(const uint8_t* dict_shifted_dev, uint32_t dict_bytes, const uint8_t* packed_dev, const uint32_t* starts_dev,
+                          const BatchItem* items_dev, uint32_t n_items, uint8_t* text);
+// lz77_batch_dict_image: files the positions [0, dict_bytes - 3) of a text whose keys are `keys` on the scratch table (num, buckets)
+// -- `num` ends up as the image's counters -- and lists the covered entries: entries[2 * i], entries[2 * i + 1], *n_entries.
+void lz77_batch_dict_image(const Lz77Params& P, const uint16_t* keys, uint32_t dict_bytes, uint16_t* num, uint32_t* buckets,
+                           uint32_t* entries, uint32_t* n_entries);
 // out[offsets[i] ..) = the finished commands of item i (Command::init) and its trailing insert-only command
 void lz77_batch_gather(const BatchParseJob& J, const uint32_t* offsets_dev, Command* out);
 
@@ -61,6 +88,13 @@ bool BatchGreedyEligible(const EncoderParams& params, size_t input_size);
 // The streams of `count` eligible items.  Throws std::runtime_error on a device error.  *groups: device groups run.
 void BatchGreedyCompress(const EncoderParams& params, size_t count, const uint8_t* const* inputs, const size_t* sizes,
                          std::vector<std::vector<uint8_t>>* streams, uint32_t* groups);
+// The same with a custom dictionary of 2 .. 65536 bytes (after the reference's truncation): item i is the stream of
+// BrotliEncoderSetCustomDictionary + one BrotliEncoderCompressStream(FINISH).  (*reference_fails)[i] != 0: the reference itself
+// fails on item i (a copy of one byte at the dictionary end); its stream stays empty.
+bool BatchDictionaryEligible(const EncoderParams& params, size_t dict_size, size_t input_size);
+void BatchGreedyCompressWithDictionary(const EncoderParams& params, const uint8_t* dict, size_t dict_size, size_t count,
+                                       const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
+                                       std::vector<uint8_t>* reference_fails, uint32_t* groups);
 
 // One group through the meta-block stage (encoder.cpp): meta-block i = item i, a complete stream of its own.
 struct BatchStreamItem {

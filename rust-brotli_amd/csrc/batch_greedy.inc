@@ -33,6 +33,18 @@ EncoderParams ItemParams(const EncoderParams& user, size_t input_size) {
   return p;
 }
 
+// ... and behind BrotliEncoderSetCustomDictionary: no static dictionary, the hasher chosen inside that call with the size hint
+// of then (none), the hint itself filled in by the FINISH call with the item's size (encode.rs:1196-1270, 1604-1620)
+EncoderParams DictionaryItemParams(const EncoderParams& user, size_t input_size) {
+  EncoderParams p = user;
+  p.use_dictionary = false;
+  FinalizeParams(&p);
+  p.size_hint = 0;
+  ChooseHasher(&p);
+  p.size_hint = input_size;
+  return p;
+}
+
 uint32_t Padded(uint32_t bytes) { return ((bytes + 63u) & ~63u) + 64u; }  // at least 64 zero bytes behind every item
 
 }  // namespace
@@ -46,8 +58,20 @@ bool BatchGreedyEligible(const EncoderParams& user, size_t input_size) {
   return p.hasher.type == 5 && input_size <= ((size_t)1 << p.lgblock);
 }
 
-void BatchGreedyCompress(const EncoderParams& user, size_t count, const uint8_t* const* inputs, const size_t* sizes,
-                         std::vector<std::vector<uint8_t>>* streams, uint32_t* groups) {
+bool BatchDictionaryEligible(const EncoderParams& user, size_t dict_size, size_t input_size) {
+  if (input_size == 0 || input_size > 65536 || dict_size < 2 || dict_size > 65536) return false;
+  if (user.quality < 5 || user.quality > 8 || user.lgwin < 17 || user.lgwin > 24 || user.large_window) return false;
+  if (user.catable || user.appendable || user.bare_stream || user.byte_align || user.magic_number) return false;
+  // (dictionary + item stay below the ring-buffer size, 1 << (lgwin + 1): no masked entry differs from its position)
+  const EncoderParams p = DictionaryItemParams(user, input_size);
+  return p.hasher.type == 5 && p.hasher.block_bits <= 7 && input_size <= ((size_t)1 << p.lgblock) && dict_size <= ((size_t)1 << p.lgwin) - 16;
+}
+
+namespace {
+
+// p: the parameters the items share, finalized.  dict == nullptr: the plain call.
+void CompressGroups(const EncoderParams& p, const uint8_t* dict, uint32_t D, size_t count, const uint8_t* const* inputs, const size_t* sizes,
+                    std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* reference_fails, uint32_t* groups) {
   // read once per process, like BROTLI_MI355X_FRAGMENT_BATCH
   static const size_t group_items = std::max<size_t>(1, EnvSize("BROTLI_MI355X_BATCH_GROUP_ITEMS", 4096));
   static const size_t group_bytes = std::max<size_t>(1, EnvSize("BROTLI_MI355X_BATCH_GROUP_BYTES", (size_t)64 << 20));
@@ -55,9 +79,9 @@ void BatchGreedyCompress(const EncoderParams& user, size_t count, const uint8_t*
   // wavefronts) within 8 GiB
   static const size_t table_override = EnvSize("BROTLI_MI355X_BATCH_TABLES", 0);
   streams->assign(count, std::vector<uint8_t>());
+  if (reference_fails) reference_fails->assign(count, 0);
   *groups = 0;
   if (count == 0) return;
-  const EncoderParams p = ItemParams(user, sizes[0]);
   const size_t keys_per_table = (size_t)1 << p.hasher.bucket_bits;
   const size_t table_bytes = keys_per_table * 2 + (keys_per_table << p.hasher.block_bits) * 4;
   const size_t tables_max = table_override ? table_override : std::max<size_t>(1, std::min<size_t>(4096, ((size_t)8 << 30) / table_bytes));
@@ -85,36 +109,76 @@ void BatchGreedyCompress(const EncoderParams& user, size_t count, const uint8_t*
   P.block_bytes = 1u << p.lgblock;
   P.max_metablock_bytes = (uint32_t)MaxMetablockSize(p);
 
+  // ---- the dictionary, once per call: its bytes on the device, and what the prepend leaves in a table (BatchDictImage)
+  DevBlocks call_mem;
+  uint8_t *dict_shifted = nullptr, *dict_dev = nullptr;
+  BatchDictImage image{};
+  // measurement only (DESIGN.md section 10): no image, every chain files the dictionary itself with br_live_store
+  static const bool self_file = EnvSize("BROTLI_MI355X_BATCH_DICT_SELF_FILE", 0) != 0;
+  if (D != 0) {
+    // (shifted so that it ends on a 16-byte boundary, like its copies in the padded text: k_batch_dict_text moves whole words)
+    dict_shifted = call_mem.zeroed<uint8_t>((size_t)D + 16 + 64);
+    dict_dev = dict_shifted + ((0u - D) & 15u);
+    dev_h2d_bulk(dict_dev, dict, D);
+    image.bytes = D;
+  }
+  if (D != 0 && !self_file) {
+    Lz77Buffers B{};
+    B.text = dict_dev;
+    B.keys = call_mem.uninit<uint16_t>((size_t)D * 2 + 256);
+    B.changed_count = call_mem.zeroed<uint32_t>(64);
+    B.dict_items = nullptr;
+    B.run_end = nullptr;
+    Lz77Params PK = P;
+    PK.total_bytes = D;  // (every filed position hashes dictionary bytes only)
+    lz77_compute_keys(PK, B);
+    uint16_t* num = call_mem.uninit<uint16_t>(keys_per_table * 2 + 64);
+    uint32_t* scratch_buckets = call_mem.uninit<uint32_t>((keys_per_table << p.hasher.block_bits) * 4 + 64);
+    uint32_t* entries = call_mem.uninit<uint32_t>((size_t)D * 8 + 64);
+    uint32_t* n_entries = call_mem.zeroed<uint32_t>(64);
+    lz77_batch_dict_image(P, B.keys, D, num, scratch_buckets, entries, n_entries);
+    image.bytes = D;
+    image.num = num;
+    image.entries = entries;
+    image.n_entries = n_entries;
+  }
+  const uint32_t dict_room = (D + 63u) & ~63u;  // in front of every item in the padded text
+
   PinnedArray<uint8_t> staging;
   PinnedArray<BatchItem> items;
-  PinnedArray<uint32_t> order, offsets;
+  PinnedArray<uint32_t> order, offsets, starts;
   PinnedArray<BatchRecord> records;
   size_t first = 0;
   while (first < count) {
     // ---- the group: items [first, last)
+    // (the limit counts the dictionary copies of the padded text: scratch -- keys and flags -- grows with them)
     size_t last = first, padded = 0, packed = 0;
-    while (last < count && last - first < group_items && (last == first || packed + sizes[last] <= group_bytes)) {
-      padded += Padded((uint32_t)sizes[last]);
+    while (last < count && last - first < group_items && (last == first || packed + (last - first + 1) * (size_t)D + sizes[last] <= group_bytes)) {
+      padded += dict_room + Padded((uint32_t)sizes[last]);
       packed += sizes[last];
       ++last;
     }
     const uint32_t n = (uint32_t)(last - first);
     ++*groups;
-    // one page-locked buffer, one upload: [padded text | 64 | packed text | 64]
-    const size_t packed_at = padded + 64;
+    // one page-locked buffer, one upload: [padded text | 64 | packed text | 64]; with a dictionary the packed text alone -- the
+    // padded text, dictionary | item per item, is laid out on the device
+    const size_t packed_at = D != 0 ? 0 : padded + 64;
     const size_t text_bytes = packed_at + packed + 64;
     staging.resize_discard(text_bytes);
     memset(staging.data(), 0, text_bytes);
     items.resize_discard(n);
     order.resize_discard(n);
+    starts.resize_discard(n);
     std::vector<BatchStreamItem> mbs(n);
     {
       uint32_t off = 0, start = 0, cmd_base = 0;
       for (uint32_t i = 0; i < n; ++i) {
         const uint32_t bytes = (uint32_t)sizes[first + i];
-        memcpy(staging.data() + off, inputs[first + i], bytes);
+        off += dict_room;
+        if (D == 0) memcpy(staging.data() + off, inputs[first + i], bytes);
         memcpy(staging.data() + packed_at + start, inputs[first + i], bytes);
         items[i] = BatchItem{off, bytes, cmd_base, bytes / 2 + 8};
+        starts[i] = start;
         mbs[i].start = start;
         mbs[i].bytes = bytes;
         off += Padded(bytes);
@@ -129,8 +193,17 @@ void BatchGreedyCompress(const EncoderParams& user, size_t count, const uint8_t*
     const uint32_t tables = (uint32_t)std::min<size_t>(tables_max, n);
 
     DevBlocks mem;
-    uint8_t* text = mem.uninit<uint8_t>(text_bytes);
-    dev_h2d_bulk(text, staging.data(), text_bytes);
+    uint8_t* uploaded = mem.uninit<uint8_t>(text_bytes);
+    dev_h2d_bulk(uploaded, staging.data(), text_bytes);
+    BatchItem* items_dev = mem.uninit<BatchItem>((size_t)n * sizeof(BatchItem));
+    dev_h2d(items_dev, items.data(), (size_t)n * sizeof(BatchItem));
+    uint8_t* text = uploaded;
+    if (D != 0) {
+      text = mem.zeroed<uint8_t>(padded + 64);
+      uint32_t* starts_dev = mem.uninit<uint32_t>((size_t)n * 4);
+      dev_h2d(starts_dev, starts.data(), (size_t)n * 4);
+      lz77_batch_dict_text(dict_shifted, D, uploaded, starts_dev, items_dev, n, text);
+    }
     Lz77Buffers B{};
     B.text = text;
     B.keys = mem.uninit<uint16_t>(padded * 2 + 256);
@@ -147,9 +220,7 @@ void BatchGreedyCompress(const EncoderParams& user, size_t count, const uint8_t*
     J.keys = B.keys;
     J.flags = mem.uninit<uint8_t>(padded + 64);
     J.slabs = mem.uninit<Command>(cmd_slots * sizeof(Command) + 64);
-    BatchItem* items_dev = mem.uninit<BatchItem>((size_t)n * sizeof(BatchItem));
     uint32_t* order_dev = mem.uninit<uint32_t>((size_t)n * 4);
-    dev_h2d(items_dev, items.data(), (size_t)n * sizeof(BatchItem));
     dev_h2d(order_dev, order.data(), (size_t)n * 4);
     J.items = items_dev;
     J.order = order_dev;
@@ -159,6 +230,7 @@ void BatchGreedyCompress(const EncoderParams& user, size_t count, const uint8_t*
     J.buckets = mem.uninit<uint32_t>(((size_t)tables * keys_per_table << p.hasher.block_bits) * 4 + 64);
     J.counter = mem.zeroed<uint32_t>(64);
     J.records = mem.uninit<BatchRecord>((size_t)n * sizeof(BatchRecord));
+    J.dict = image;
     lz77_batch_parse(J);
     records.resize_discard(n);
     dev_d2h(records.data(), J.records, (size_t)n * sizeof(BatchRecord));
@@ -173,6 +245,7 @@ void BatchGreedyCompress(const EncoderParams& user, size_t count, const uint8_t*
       mbs[i].n_lits = records[i].n_lits;
       mbs[i].uncompressed = records[i].uncompressed;
       total += records[i].n_cmds;
+      if (records[i].bad_commands != 0 && reference_fails) (*reference_fails)[first + i] = 1;
     }
     uint32_t* offsets_dev = mem.uninit<uint32_t>((size_t)n * 4);
     dev_h2d(offsets_dev, offsets.data(), (size_t)n * 4);
@@ -180,10 +253,24 @@ void BatchGreedyCompress(const EncoderParams& user, size_t count, const uint8_t*
     lz77_batch_gather(J, offsets_dev, cmds);
     // ---- one meta-block per item
     std::vector<uint8_t> out;
-    EncodeBatchMetaBlocks(p, text + packed_at, cmds, (uint32_t)total, &mbs, &out);
-    for (uint32_t i = 0; i < n; ++i) (*streams)[first + i].assign(out.begin() + (ptrdiff_t)mbs[i].out_byte, out.begin() + (ptrdiff_t)(mbs[i].out_byte + mbs[i].out_bytes));
+    EncodeBatchMetaBlocks(p, uploaded + packed_at, cmds, (uint32_t)total, &mbs, &out);
+    for (uint32_t i = 0; i < n; ++i)
+      if (records[i].bad_commands == 0) (*streams)[first + i].assign(out.begin() + (ptrdiff_t)mbs[i].out_byte, out.begin() + (ptrdiff_t)(mbs[i].out_byte + mbs[i].out_bytes));
     first = last;
   }
+}
+
+}  // namespace
+
+void BatchGreedyCompress(const EncoderParams& user, size_t count, const uint8_t* const* inputs, const size_t* sizes,
+                         std::vector<std::vector<uint8_t>>* streams, uint32_t* groups) {
+  CompressGroups(ItemParams(user, count ? sizes[0] : 0), nullptr, 0, count, inputs, sizes, streams, nullptr, groups);
+}
+
+void BatchGreedyCompressWithDictionary(const EncoderParams& user, const uint8_t* dict, size_t dict_size, size_t count,
+                                       const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
+                                       std::vector<uint8_t>* reference_fails, uint32_t* groups) {
+  CompressGroups(DictionaryItemParams(user, count ? sizes[0] : 0), dict, (uint32_t)dict_size, count, inputs, sizes, streams, reference_fails, groups);
 }
 
 }  // namespace brotli_mi355x

@@ -8,8 +8,37 @@
 
 namespace brotli_mi355x {
 
+// Replays the dictionary image on the table of a chain (BatchDictImage): the ring counters of the image go over ALL the counters of
+// the table, then every entry they cover is written to its slot -- independent stores, through the device-scope macros the chain
+// reads back through.  A table is reused by the next item of its wavefront, and the buckets keep what the item in front filed;
+// none of it can be reached: a walk reads the min(counter, depth) slots in front of a key's counter and nothing else, every counter
+// is the image's after the first loop, and the image's list holds exactly those slots of every key.  (What the chain files
+// afterwards moves a counter one slot at a time and writes that slot first, br_live_insert / br_live_store.)
+BR_DEV void br_batch_replay_dictionary(const LiveRing& lr, const BatchDictImage& d, uint32_t bucket_bits) {
+  BR_SYNC();
+  const uint32_t words = 1u << (bucket_bits - 1);  // two counters per 32-bit word
+  const uint32_t* img = (const uint32_t*)d.num;
+  uint32_t* w = (uint32_t*)lr.num;
+  for (uint32_t i = BR_LANE; i < words; i += BR_NLANES) BR_LIVE_ST32(w + i, img[i]);
+  uint32_t n = BR_UNIFORM(*d.n_entries);
+  if (n > d.bytes) n = d.bytes;  // (at most one entry per filed position: the list's capacity)
+  // four entries per lane and step: the loads of a step are in flight together, and so are its stores
+  for (uint32_t i = 4u * (uint32_t)BR_LANE; i < n; i += 4u * BR_NLANES) {
+    uint32_t slot[4], pos[4];
+    for (uint32_t k = 0; k < 4; ++k) {
+      const uint32_t e = i + k < n ? i + k : i;
+      slot[k] = d.entries[2 * (size_t)e];
+      pos[k] = d.entries[2 * (size_t)e + 1];
+    }
+    for (uint32_t k = 0; k < 4; ++k)
+      if (i + k < n) BR_LIVE_ST32(lr.buckets + slot[k], pos[k]);
+  }
+  BR_SYNC();
+}
+
 // T: the job's tables with text / keys / flags / cmds still pointing at the group's arrays.
-template <bool kRows>
+// kDict: the item's text starts with J.dict.bytes bytes of custom dictionary (BrotliMi355xCompressBatchWithDictionary).
+template <bool kRows, bool kDict = false>
 BR_DEV void br_batch_item(const BatchParseJob& J, const ChainTables& T, ChainScratchT<false, kRows>& s, uint32_t* histo /* 256 words */,
                           uint32_t index, uint32_t table) {
   BatchItem it = J.items[index];
@@ -19,12 +48,15 @@ BR_DEV void br_batch_item(const BatchParseJob& J, const ChainTables& T, ChainScr
   it.cmd_cap = BR_UNIFORM(it.cmd_cap);
   // item-local coordinates: position 0 is the item's first byte, so no distance reaches a neighbour and max_backward is what
   // the reference computes for a stream that starts at 0
+  // (with a dictionary: position 0 is the dictionary's first byte and the item starts at D, as in the reference's ring buffer)
+  const uint32_t D = kDict ? BR_UNIFORM(J.dict.bytes) : 0u;
   Lz77Params P = J.P;
-  P.total_bytes = it.bytes;
+  P.total_bytes = D + it.bytes;
+  if constexpr (kDict) P.prefix_bytes = P.dict_break = D;
   ChainTables t = T;
-  t.text = J.text + it.text_off;
-  t.keys = J.keys + it.text_off;
-  t.flags_next = J.flags + it.text_off;
+  t.text = J.text + it.text_off - D;
+  t.keys = J.keys + it.text_off - D;
+  t.flags_next = J.flags + it.text_off - D;
   t.cmds = J.slabs;
   LiveRing lr;
   const size_t keys_per_table = (size_t)1 << P.bucket_bits;
@@ -33,16 +65,29 @@ BR_DEV void br_batch_item(const BatchParseJob& J, const ChainTables& T, ChainScr
   lr.keys = t.keys;
   lr.bits = P.block_bits;
   // an empty hasher: the ring counters at 0 (a walk never reads a slot its counter does not cover: `buckets` needs no fill)
-  br_live_reset(lr, P.bucket_bits);
+  if constexpr (kDict) {
+    // the hasher as HasherPrependCustomDictionary left it, then StitchToPreviousBlock of the first block (mod.rs:210-222): the
+    // last three dictionary positions, whose four bytes reach into the item
+    if (J.dict.entries != nullptr) {
+      br_batch_replay_dictionary(lr, J.dict, P.bucket_bits);
+    } else {
+      // (the A/B of DESIGN.md section 10, BROTLI_MI355X_BATCH_DICT_SELF_FILE: every chain files the dictionary itself)
+      br_live_reset(lr, P.bucket_bits);
+      if (D > P.htl - 1) br_live_store(lr, 0, 1, D - (P.htl - 1), 1, 0);
+    }
+    if (it.bytes >= P.htl - 1 && D >= 3) br_live_store(lr, D - 3u, 1, 3, 1, 0);
+  } else {
+    br_live_reset(lr, P.bucket_bits);
+  }
   Segment seg;
-  seg.start = seg.blk_start = 0;
-  seg.end = seg.blk_end = it.bytes;
+  seg.start = seg.blk_start = D;
+  seg.end = seg.blk_end = D + it.bytes;
   seg.flags = kSegFirstInBlock | kSegLastInBlock;
   seg.cmd_base = it.cmd_base;
   seg.block_index = 0;
   seg.cmd_cap = it.cmd_cap;
   SegEntry entry;
-  entry.pos = 0;
+  entry.pos = D;
   entry.apply = P.spree_window;
   entry.cache[0] = 4;
   entry.cache[1] = 11;
@@ -70,7 +115,7 @@ BR_DEV void br_batch_item(const BatchParseJob& J, const ChainTables& T, ChainScr
     BR_SYNC();
     for (uint32_t i = BR_LANE; i < 256; i += BR_NLANES) histo[i] = 0;
     BR_SYNC();
-    for (uint32_t q = 13u * (uint32_t)BR_LANE; q < bytes; q += 13u * BR_NLANES) BR_ATOMIC_INC(&histo[t.text[q]]);
+    for (uint32_t q = 13u * (uint32_t)BR_LANE; q < bytes; q += 13u * BR_NLANES) BR_ATOMIC_INC(&histo[t.text[D + q]]);
     BR_SYNC();
     const float threshold = (float)bytes * 7.92f / 13.0f;
     compress = !(br_bits_entropy(t.logs, histo, 256) > threshold);
@@ -82,7 +127,19 @@ BR_DEV void br_batch_item(const BatchParseJob& J, const ChainTables& T, ChainScr
     r.trailing = trailing;
     r.uncompressed = compress ? 0u : 1u;
     r.overflow = cmds_all > it.cmd_cap ? 1u : 0u;
-    r.pad[0] = r.pad[1] = r.pad[2] = 0;
+    r.bad_commands = 0;
+    if constexpr (kDict) {
+      // a copy of one byte: the reference cannot encode it (GetCopyLengthCode, command.rs:91-93) and neither do the tables behind
+      // br_finish_command -- the item is handed on as literals only and flagged
+      r.bad_commands = left.bad_commands;  // (lane 0 holds the exit)
+      if (r.bad_commands != 0) {
+        r.n_cmds = 1;
+        r.n_lits = r.trailing = bytes;
+        r.uncompressed = 1;
+        r.overflow = 0;
+      }
+    }
+    r.pad[0] = r.pad[1] = 0;
     J.records[index] = r;
   }
   BR_SYNC();

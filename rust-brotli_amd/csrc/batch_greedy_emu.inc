@@ -2,6 +2,8 @@
 // lz77_batch_gather), compiled into the emulation build only (BROTLI_HOST_EMU, tests/emu; batch_greedy.inc includes it there): the
 // same item code (batch_greedy_device.h) on plain memory, one item after the other in the order of the plan, the tables taken in
 // turn -- so that a table serves several items, as on the device.
+#include <string.h>
+
 #include <stdexcept>
 
 #include "batch_greedy_device.h"
@@ -35,8 +37,41 @@ void lz77_batch_parse(const BatchParseJob& J) {
   T.logs.logs_8 = dt.logs_8;
   static thread_local ChainScratchT<false, false> scratch;
   uint32_t histo[256];
-  for (uint32_t place = 0; place < J.n_items; ++place) br_batch_item<false>(J, T, scratch, histo, J.order[place], place % J.tables);
+  for (uint32_t place = 0; place < J.n_items; ++place) {
+    if (J.dict.bytes != 0) br_batch_item<false, true>(J, T, scratch, histo, J.order[place], place % J.tables);
+    else br_batch_item<false>(J, T, scratch, histo, J.order[place], place % J.tables);
+  }
   *J.counter = J.n_items;
+}
+
+void lz77_batch_dict_text(const uint8_t* dict, uint32_t dict_bytes, const uint8_t* packed, const uint32_t* starts, const BatchItem* items,
+                          uint32_t n_items, uint8_t* text) {
+  for (uint32_t i = 0; i < n_items; ++i) {
+    memcpy(text + items[i].text_off - dict_bytes, dict + ((0u - dict_bytes) & 15u), dict_bytes);
+    memcpy(text + items[i].text_off, packed + starts[i], items[i].bytes);
+  }
+}
+
+void lz77_batch_dict_image(const Lz77Params& P, const uint16_t* keys, uint32_t dict_bytes, uint16_t* num, uint32_t* buckets,
+                           uint32_t* entries, uint32_t* n_entries) {
+  LiveRing lr;
+  lr.num = num;
+  lr.buckets = buckets;
+  lr.keys = keys;
+  lr.bits = P.block_bits;
+  br_live_reset(lr, P.bucket_bits);
+  if (dict_bytes > P.htl - 1) br_live_store(lr, 0, 1, dict_bytes - (P.htl - 1), 1, 0);  // StoreLookaheadThenStore, mod.rs:224-229
+  const uint32_t depth = 1u << P.block_bits;
+  uint32_t n_out = 0;
+  for (uint32_t key = 0; key < (1u << P.bucket_bits); ++key) {
+    const uint32_t n = num[key], visible = n < depth ? n : depth;
+    for (uint32_t i = 0; i < visible; ++i, ++n_out) {
+      const uint32_t slot = (key << P.block_bits) | ((n - 1u - i) & (depth - 1u));
+      entries[2 * (size_t)n_out] = slot;
+      entries[2 * (size_t)n_out + 1] = buckets[slot];
+    }
+  }
+  *n_entries = n_out;
 }
 
 void lz77_batch_gather(const BatchParseJob& J, const uint32_t* offsets, Command* out) {

@@ -790,6 +790,7 @@ void BrotliEncoderSetCustomDictionary(BrotliEncoderState* s, size_t size, const 
   FinalizeParams(&fin);
   if (size == 0 || size <= 1 || fin.quality == 0 || fin.quality == 1) {  // (qualities 0 / 1 take no dictionary, encode.rs:1237-1241)
     // too short: the reference only turns on catable + appendable (encode.rs:1237-1241)
+    s->params.catable_behind_init = !s->params.catable;  // (ensure_initialized has run by now: the distance cache stays as it is)
     s->params.catable = true;
     s->params.appendable = true;
     s->params.use_dictionary = false;
@@ -1065,6 +1066,116 @@ int32_t BrotliMi355xCompressBatch(int quality, int lgwin, BrotliEncoderMode mode
   } catch (const std::exception& e) {
     // a device error fails the call as a whole
     SetError("BrotliMi355xCompressBatch", e.what());
+    for (size_t i = 0; i < count; ++i) output_sizes[i] = 0;
+    if (item_results) memset(item_results, 0, count * sizeof(int32_t));
+    return 0;
+  }
+  memcpy(g_batch_info, info, sizeof(info));
+  int32_t all = 1;
+  for (size_t i = 0; i < count; ++i) {
+    if (item_results) item_results[i] = results[i];
+    if (!results[i]) all = 0;
+  }
+  return all;
+}
+
+// One item of BrotliMi355xCompressBatchWithDictionary by itself, through the stream state machine: the definition of the call, run as
+// it reads.  1 = done; 0 = the item fails alone (its stream does not fit, or the reference fails on it: message set); throws on
+// anything else (a device error fails the whole call).
+static int CompressItemWithDictionary(int quality, int lgwin, BrotliEncoderMode mode, size_t dict_size, const uint8_t* dict, size_t input_size,
+                                      const uint8_t* input, size_t* encoded_size, uint8_t* encoded) {
+  const size_t capacity = *encoded_size;
+  *encoded_size = 0;
+  BrotliEncoderState* s = BrotliEncoderCreateInstance(nullptr, nullptr, nullptr);
+  if (!s) throw std::runtime_error("BrotliEncoderCreateInstance failed");
+  struct Destroy {
+    BrotliEncoderState* s;
+    ~Destroy() { BrotliEncoderDestroyInstance(s); }
+  } destroy{s};
+  BrotliEncoderSetParameter(s, BROTLI_PARAM_QUALITY, (uint32_t)quality);
+  BrotliEncoderSetParameter(s, BROTLI_PARAM_LGWIN, (uint32_t)lgwin);
+  BrotliEncoderSetParameter(s, BROTLI_PARAM_MODE, (uint32_t)mode);
+  BrotliEncoderSetCustomDictionary(s, dict_size, dict);
+  // (no room offered: the whole stream stays in the state's buffer, and goes out only if it fits)
+  size_t available_in = input_size, available_out = 0;
+  const uint8_t* next_in = input;
+  uint8_t* next_out = encoded;
+  if (!BrotliEncoderCompressStream(s, BROTLI_OPERATION_FINISH, &available_in, &next_in, &available_out, &next_out, nullptr)) {
+    if (g_last_error.find("reference encoder fails") != std::string::npos) return 0;
+    throw std::runtime_error(g_last_error.empty() ? std::string("BrotliEncoderCompressStream failed") : g_last_error);
+  }
+  const size_t n = AvailableOut(s);
+  if (n > capacity) return 0;
+  memcpy(encoded, s->output.data() + s->output_pos, n);
+  *encoded_size = n;
+  return 1;
+}
+
+int32_t BrotliMi355xCompressBatchWithDictionary(int quality, int lgwin, BrotliEncoderMode mode, size_t dict_size, const uint8_t* dict, size_t count,
+                                                const uint8_t* const* inputs, const size_t* input_sizes, uint8_t* const* outputs,
+                                                size_t* output_sizes, int32_t* item_results) {
+  uint64_t info[8] = {count, 0, 0, 0, 0, 0, 0, 0};
+  memcpy(g_batch_info, info, sizeof(info));
+  if (count == 0) return 1;
+  size_t total = 0;
+  for (size_t i = 0; i < count; ++i) total += input_sizes[i];
+  std::vector<int32_t> results(count, 0);
+  try {
+    EncoderParams params;
+    SetParameter(&params, kParamQuality, (uint32_t)quality);
+    SetParameter(&params, kParamLgwin, (uint32_t)lgwin);
+    SetParameter(&params, kParamMode, (uint32_t)mode);
+    // set_custom_dictionary (encode.rs:1196-1270): qualities 0 / 1 and dictionaries of less than two bytes take none; a longer one
+    // is cut to its last (1 << lgwin) - 16 bytes
+    size_t dict_use = 0;
+    {
+      EncoderParams fin = params;
+      FinalizeParams(&fin);
+      if (dict_size > 1 && fin.quality != 0 && fin.quality != 1) dict_use = std::min(dict_size, ((size_t)1 << fin.lgwin) - 16);
+    }
+    info[5] = dict_use;
+    SmallCallGate gate(total);
+    // Side by side: the items of 1 .. 65536 bytes at qualities 5 .. 8, lgwin 17 .. 24, behind a dictionary of 2 .. 65536 bytes
+    // (batch_greedy.h).  Every other item goes through the stream path by itself, on this thread, in the caller's order.
+    std::vector<size_t> item;
+    std::vector<const uint8_t*> in;
+    std::vector<size_t> in_size;
+    for (size_t i = 0; i < count; ++i) {
+      if (BatchDictionaryEligible(params, dict_size, input_sizes[i])) {
+        item.push_back(i);
+        in.push_back(inputs[i]);
+        in_size.push_back(input_sizes[i]);
+        continue;
+      }
+      results[i] = CompressItemWithDictionary(quality, lgwin, mode, dict_size, dict, input_sizes[i], inputs[i], &output_sizes[i], outputs[i]);
+      ++info[2];
+    }
+    if (!item.empty()) {
+      std::vector<std::vector<uint8_t>> streams;
+      std::vector<uint8_t> reference_fails;
+      uint32_t groups = 0;
+      BatchGreedyCompressWithDictionary(params, dict + (dict_size - dict_use), dict_use, item.size(), in.data(), in_size.data(), &streams, &reference_fails, &groups);
+      info[4] = groups;
+      info[1] = item.size();
+      for (size_t k = 0; k < item.size(); ++k) {
+        const size_t i = item[k];
+        const size_t capacity = output_sizes[i];
+        output_sizes[i] = 0;
+        if (reference_fails[k]) {
+          SetError("BrotliMi355xCompressBatchWithDictionary",
+                   ("item " + std::to_string(i) + ": the reference encoder fails on this input: a match cut to one byte at the end of the custom dictionary "
+                    "gives a copy it cannot encode (fix_unbroken_len, backward_references/mod.rs:42-54; GetCopyLengthCode, command.rs:91-93)").c_str());
+          continue;
+        }
+        if (streams[k].size() > capacity) continue;  // (no fallback to a stored stream: the stream API has none)
+        memcpy(outputs[i], streams[k].data(), streams[k].size());
+        output_sizes[i] = streams[k].size();
+        results[i] = 1;
+      }
+    }
+  } catch (const std::exception& e) {
+    // a device error fails the call as a whole
+    SetError("BrotliMi355xCompressBatchWithDictionary", e.what());
     for (size_t i = 0; i < count; ++i) output_sizes[i] = 0;
     if (item_results) memset(item_results, 0, count * sizeof(int32_t));
     return 0;

@@ -500,7 +500,8 @@ void EncodeStream(const EncodeRequest& req, std::vector<uint8_t>* out, EncodeSta
         co.hasher = p.hasher;
         co.size_hint = p.size_hint;
         const int32_t far_away = 0x7ffffff0;  // a catable stream starts without usable last distances (encode.rs:693-703)
-        const int32_t d0[4] = {p.catable ? far_away : 4, p.catable ? far_away : 11, p.catable ? far_away : 15, p.catable ? far_away : 16};
+        const bool far = p.catable && !p.catable_behind_init;
+        const int32_t d0[4] = {far ? far_away : 4, far ? far_away : 11, far ? far_away : 15, far ? far_away : 16};
         memcpy(co.dist_cache, d0, sizeof(d0));
         co.dict_break = prefix_bytes;
         if (prefix_bytes != 0) {

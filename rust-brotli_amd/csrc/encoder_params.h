@@ -75,6 +75,10 @@ struct EncoderParams {
   bool byte_align = false;
   bool bare_stream = false;
   bool catable = false;
+  // catable was turned on behind ensure_initialized (set_custom_dictionary with a too-short dictionary, encode.rs:1237-1241): the
+  // stream is written as a catable one, but what the initialisation does for one has not happened -- the last distances are the
+  // usual 4, 11, 15, 16 and not "far away" (encode.rs:693-703)
+  bool catable_behind_init = false;
   bool use_dictionary = true;
   bool appendable = false;
   bool magic_number = false;

@@ -2543,11 +2543,119 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 4))) void
   }
 }
 
+// The same launch for items behind a shared custom dictionary (J.dict): a sibling, so that the instances above stay what they were.
+template <bool kRows>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_parse_batch_dict(BatchParseJob J, ChainTables T) {
+  __shared__ ChainScratchT<false, kRows> scratch;
+  __shared__ uint32_t histo[256];
+  const uint32_t table = blockIdx.x;
+  if (table >= J.tables) return;
+  for (;;) {
+    uint32_t mine = 0;
+    if (threadIdx.x == 0) mine = atomicAdd(J.counter, 1u);
+    const uint32_t place = BR_UNIFORM(mine);
+    if (place >= J.n_items) break;
+    const uint32_t index = BR_UNIFORM(J.order[place]);
+    if (index >= J.n_items) break;  // (never: the plan's order is a permutation)
+    br_batch_item<kRows, true>(J, T, scratch, histo, index, table);
+  }
+}
+
+// dst[k] = src[k] for k < n, rounded up to whole 16-byte words (zeros behind); dst is 16-byte aligned, src is not: aligned dword
+// loads around the source and a funnel shift by its misalignment.  Reads stay inside the dwords that hold src[0 .. 16 * words + 4):
+// the packed text starts on an allocation boundary and has 64 bytes of padding behind it.
+__device__ __forceinline__ void batch_copy_to_aligned(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, uint32_t n) {
+  const uint32_t words = (n + 15u) >> 4;
+  const uint32_t mis = (uint32_t)((uintptr_t)src & 3u);
+  const uint32_t* __restrict__ s32 = (const uint32_t*)(src - mis);
+  for (uint32_t w = threadIdx.x; w < words; w += blockDim.x) {
+    uint32_t d[5], v[4];
+    for (uint32_t j = 0; j < 5; ++j) d[j] = s32[4u * w + j];
+    for (uint32_t j = 0; j < 4; ++j) {
+      v[j] = __funnelshift_r(d[j], d[j + 1], 8u * mis);
+      const uint32_t k = w * 16u + j * 4u;  // bytes at or behind n read as zero
+      if (k + 4u > n) v[j] = k >= n ? 0u : (v[j] & (0xffffffffu >> (8u * (k + 4u - n))));
+    }
+    ((uint4*)dst)[w] = make_uint4(v[0], v[1], v[2], v[3]);
+  }
+}
+
+// one workgroup per item: dictionary | item, the dictionary's last byte in front of the item's first
+__global__ __launch_bounds__(256) void k_batch_dict_text(const uint8_t* __restrict__ dict, uint32_t dict_bytes, const uint8_t* __restrict__ packed,
+                                                          const uint32_t* __restrict__ starts, const BatchItem* __restrict__ items, uint32_t n_items,
+                                                          uint8_t* __restrict__ text) {
+  const uint32_t i = blockIdx.x;
+  if (i >= n_items) return;
+  const BatchItem it = items[i];
+  // (the dictionary comes shifted: behind `lead` zero bytes it ends on a 16-byte boundary, like its copy in front of the item)
+  const uint32_t words = (dict_bytes + 15u) >> 4;
+  const uint4* __restrict__ src = (const uint4*)dict;
+  uint4* __restrict__ dst = (uint4*)(text + it.text_off - 16u * words);
+  for (uint32_t w = threadIdx.x; w < words; w += blockDim.x) dst[w] = src[w];
+  batch_copy_to_aligned(text + it.text_off, packed + starts[i], it.bytes);
+}
+
+void lz77_batch_dict_text(const uint8_t* dict_dev, uint32_t dict_bytes, const uint8_t* packed_dev, const uint32_t* starts_dev,
+                          const BatchItem* items_dev, uint32_t n_items, uint8_t* text) {
+  if (n_items == 0) return;
+  hipLaunchKernelGGL(k_batch_dict_text, dim3(n_items), dim3(256), 0, BR_STREAM, dict_dev, dict_bytes, packed_dev, starts_dev, items_dev, n_items, text);
+  HIP_CHECK(hipGetLastError());
+}
+
+// HasherPrependCustomDictionary on a scratch table: one wavefront files the positions in the reference's order (br_live_store)
+__global__ __launch_bounds__(64) void k_batch_dict_file(LiveRing lr, uint32_t bucket_bits, uint32_t count) {
+  br_live_reset(lr, bucket_bits);
+  if (count != 0) br_live_store(lr, 0, 1, count, 1, 0);
+}
+// ... and one thread per key lists the entries its counter covers
+__global__ __launch_bounds__(256) void k_batch_dict_list(const uint16_t* __restrict__ num, const uint32_t* __restrict__ buckets, uint32_t bucket_bits,
+                                                          uint32_t bits, uint32_t cap, uint32_t* __restrict__ entries, uint32_t* __restrict__ n_entries) {
+  const uint32_t key = blockIdx.x * blockDim.x + threadIdx.x;
+  if (key >= (1u << bucket_bits)) return;
+  const uint32_t depth = 1u << bits;
+  const uint32_t n = num[key];
+  const uint32_t visible = n < depth ? n : depth;
+  if (visible == 0) return;
+  const uint32_t base = atomicAdd(n_entries, visible);
+  for (uint32_t i = 0; i < visible; ++i) {
+    if (base + i >= cap) return;  // (never: at most one entry per filed position)
+    const uint32_t slot = (key << bits) | ((n - 1u - i) & (depth - 1u));
+    entries[2 * (size_t)(base + i)] = slot;
+    entries[2 * (size_t)(base + i) + 1] = buckets[slot];
+  }
+}
+
+void lz77_batch_dict_image(const Lz77Params& P, const uint16_t* keys, uint32_t dict_bytes, uint16_t* num, uint32_t* buckets,
+                           uint32_t* entries, uint32_t* n_entries) {
+  LiveRing lr;
+  lr.num = num;
+  lr.buckets = buckets;
+  lr.keys = keys;
+  lr.bits = P.block_bits;
+  const uint32_t count = dict_bytes > P.htl - 1 ? dict_bytes - (P.htl - 1) : 0u;  // StoreLookaheadThenStore, mod.rs:224-229
+  dev_memset(n_entries, 0, 4);
+  hipLaunchKernelGGL(k_batch_dict_file, dim3(1), dim3(64), 0, BR_STREAM, lr, P.bucket_bits, count);
+  hipLaunchKernelGGL(k_batch_dict_list, dim3(((1u << P.bucket_bits) + 255u) / 256u), dim3(256), 0, BR_STREAM, (const uint16_t*)num,
+                     (const uint32_t*)buckets, P.bucket_bits, P.block_bits, dict_bytes, entries, n_entries);
+  HIP_CHECK(hipGetLastError());
+}
+
 void lz77_batch_parse(const BatchParseJob& J) {
   if (J.n_items == 0) return;
   if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
   const ChainTables T = batch_chain_tables(J);
   const uint32_t grid = J.tables < J.n_items ? J.tables : J.n_items;
+  if (J.dict.bytes != 0) {
+    if ((1u << J.P.block_bits) <= kRowEntries) {
+      hipLaunchKernelGGL((k_parse_batch_dict<true>), dim3(grid), dim3(64), 0, BR_STREAM, J, T);
+    } else if (J.P.block_bits <= 7) {
+      hipLaunchKernelGGL((k_parse_batch_dict<false>), dim3(grid), dim3(64), 0, BR_STREAM, J, T);
+    } else {
+      throw std::runtime_error("brotli_mi355x: the batch chains do not run the 512-deep rings");
+    }
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
   if ((1u << J.P.block_bits) <= kRowEntries) {
     hipLaunchKernelGGL((k_parse_batch<true>), dim3(grid), dim3(64), 0, BR_STREAM, J, T);
   } else if (J.P.block_bits <= 7) {

@@ -699,7 +699,7 @@ bool Lz77Stage::ResolvePass(bool final_pass, bool incremental) {
   };
 
   int32_t cache[4] = {4, 11, 15, 16};
-  if (params_.catable) {
+  if (params_.catable && !params_.catable_behind_init) {
     for (int i = 0; i < 4; ++i) cache[i] = 0x7ffffff0;  // encode.rs:693-703
   }
   if (carry_ && carry_->valid) memcpy(cache, carry_->dist_cache, sizeof(cache));
@@ -1429,7 +1429,7 @@ void Lz77Stage::InitEntries() {
     e.pos = segments_[k].start;
     e.apply = segments_[k].start + P_.spree_window;
     const int32_t d[4] = {4, 11, 15, 16};
-    for (int i = 0; i < 4; ++i) e.cache[i] = (carry_ && carry_->valid) ? carry_->dist_cache[i] : (params_.catable ? 0x7ffffff0 : d[i]);
+    for (int i = 0; i < 4; ++i) e.cache[i] = (carry_ && carry_->valid) ? carry_->dist_cache[i] : ((params_.catable && !params_.catable_behind_init) ? 0x7ffffff0 : d[i]);
     if (k != 0) {
       e.dict_lookups = DictTracker::kAliveL;
       e.dict_matches = DictTracker::kAliveM;

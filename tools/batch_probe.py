@@ -15,6 +15,12 @@ BrotliMi355xCompressBatch call on its library -- there a loop over the one-shot 
 item count, and the loop from 4 threads; --rounds 3 alternates this build and the parent (one child each) and records whether every
 run of this build beats every run of the parent.  The table-home A/B belongs to qualities 0 and 1 and is skipped otherwise.
 
+With --dictionary BYTES (and --qualities 5,8) the call measured is BrotliMi355xCompressBatchWithDictionary: the dictionary is drawn from
+the same generator and seed family as the items; the baseline of the parent commit is a loop of stream-API calls with
+BrotliEncoderSetCustomDictionary on its library, from 1 and from 4 threads, alternating with this build --rounds times; the CPU
+baseline is the oracle's dictionary stream; and this build's plain batch call on the same items gives the cost (in time) and the
+gain (in bytes) of the dictionary.
+
 Every measurement runs in a child process of its own (the table's home is one setting per process, read once; the parent's library
 is another shared object), one after the other, each under its own time limit; the first failure ends the probe.
 
@@ -64,6 +70,14 @@ def items_of(name, data):
     return out
 
 
+def dictionary_of(data, nbytes):
+    """the items' generator and seed family, another draw"""
+    import synth
+    pool = synth.markov_text(8 << 20, 5) if data == "text" else synth.mixed(8 << 20, 5)
+    off = random.Random(18).randrange(0, len(pool) - nbytes)
+    return pool[off:off + nbytes]
+
+
 def stats(times):
     times = sorted(times)
     return {"median_ms": round(1e3 * statistics.median(times), 3), "min_ms": round(1e3 * times[0], 3), "max_ms": round(1e3 * times[-1], 3),
@@ -80,40 +94,84 @@ def bind(path):
     return L
 
 
-def measure_batch(lib_path, items, quality, runs, warmup):
+def measure_batch(lib_path, items, quality, runs, warmup, dictionary=None):
     L = bind(lib_path)
     L.BrotliMi355xCompressBatch.restype = ctypes.c_int32
+    if dictionary is not None:
+        L.BrotliMi355xCompressBatchWithDictionary.restype = ctypes.c_int32
     info = (ctypes.c_uint64 * 8)()
     n = len(items)
-    caps = [L.BrotliEncoderMaxCompressedSize(len(x)) + 16 for x in items]
+    caps = [L.BrotliEncoderMaxCompressedSize(len(x)) + (16 if dictionary is None else 1024) for x in items]
     bufs = [ctypes.create_string_buffer(c) for c in caps]
     inputs = (ctypes.c_char_p * n)(*items)
     in_sizes = (ctypes.c_size_t * n)(*[len(x) for x in items])
     outputs = (ctypes.c_void_p * n)(*[ctypes.addressof(b) for b in bufs])
     out_sizes = (ctypes.c_size_t * n)()
+    results = (ctypes.c_int32 * n)()
+    L.BrotliMi355xLastError.restype = ctypes.c_char_p
     times = []
+    failed = []
     for it in range(warmup + runs):
         for i in range(n):
             out_sizes[i] = caps[i]
         t = time.perf_counter()
-        ok = L.BrotliMi355xCompressBatch(quality, LGWIN, 0, ctypes.c_size_t(n), inputs, in_sizes, outputs, out_sizes, None)
+        if dictionary is None:
+            ok = L.BrotliMi355xCompressBatch(quality, LGWIN, 0, ctypes.c_size_t(n), inputs, in_sizes, outputs, out_sizes, None)
+        else:
+            ok = L.BrotliMi355xCompressBatchWithDictionary(quality, LGWIN, 0, ctypes.c_size_t(len(dictionary)), ctypes.c_char_p(dictionary), ctypes.c_size_t(n),
+                                                           inputs, in_sizes, outputs, out_sizes, results)
         dt = time.perf_counter() - t
+        if dictionary is not None and ok != 1:
+            # items on which the reference itself fails (a copy of one byte at the dictionary end) fail alone: counted, not fatal
+            failed = [i for i in range(n) if not results[i]]
+            assert 0 < len(failed) <= n // 256 + 1 and b"reference encoder fails" in L.BrotliMi355xLastError(), (failed, L.BrotliMi355xLastError())
+            ok = 1
         assert ok == 1
         if it >= warmup:
             times.append(dt)
     if hasattr(L, "BrotliMi355xLastBatchInfo"):  # (the parent's library has none)
         L.BrotliMi355xLastBatchInfo(info)
-    return times, sum(out_sizes), list(info)
+    return times, sum(out_sizes), list(info), failed
 
 
-def measure_loop(lib_path, items, quality, threads, runs, warmup):
+def measure_loop(lib_path, items, quality, threads, runs, warmup, dictionary=None):
     L = bind(lib_path)
-    caps = [L.BrotliEncoderMaxCompressedSize(len(x)) + 16 for x in items]
+    caps = [L.BrotliEncoderMaxCompressedSize(len(x)) + (16 if dictionary is None else 1024) for x in items]
     bufs = [ctypes.create_string_buffer(c) for c in caps]
+    L.BrotliEncoderCreateInstance.restype = ctypes.c_void_p
+    L.BrotliEncoderCreateInstance.argtypes = [ctypes.c_void_p] * 3
+    L.BrotliEncoderDestroyInstance.argtypes = [ctypes.c_void_p]
+    L.BrotliEncoderSetParameter.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32]
+    L.BrotliEncoderSetCustomDictionary.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p]
+    L.BrotliEncoderCompressStream.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5
+    L.BrotliEncoderIsFinished.argtypes = [ctypes.c_void_p]
+    L.BrotliMi355xLastError.restype = ctypes.c_char_p
+    failed = set()  # items on which the reference fails: the batch call's item_results name the same ones
+
+    def one_stream(i):
+        # what the batch call with a dictionary is defined as, per item
+        s = L.BrotliEncoderCreateInstance(None, None, None)
+        for k, v in ((0, 0), (1, quality), (2, LGWIN)):
+            L.BrotliEncoderSetParameter(s, k, v)
+        L.BrotliEncoderSetCustomDictionary(s, len(dictionary), dictionary)
+        avail_in, avail_out = ctypes.c_size_t(len(items[i])), ctypes.c_size_t(caps[i])
+        next_in = ctypes.c_void_p(ctypes.cast(ctypes.c_char_p(items[i]), ctypes.c_void_p).value)
+        next_out = ctypes.c_void_p(ctypes.addressof(bufs[i]))
+        ok = L.BrotliEncoderCompressStream(s, 2, ctypes.byref(avail_in), ctypes.byref(next_in), ctypes.byref(avail_out), ctypes.byref(next_out), None)
+        done = L.BrotliEncoderIsFinished(s)
+        L.BrotliEncoderDestroyInstance(s)
+        if not ok:  # (the message is looked at only for a call that failed: it stays set afterwards)
+            assert b"reference encoder fails" in L.BrotliMi355xLastError(), (i, L.BrotliMi355xLastError())
+            failed.add(i)
+        else:
+            assert done, i
 
     def work(lo, hi):
         size = ctypes.c_size_t()
         for i in range(lo, hi):
+            if dictionary is not None:
+                one_stream(i)
+                continue
             size.value = caps[i]
             assert L.BrotliEncoderCompress(quality, LGWIN, 0, len(items[i]), items[i], ctypes.byref(size), bufs[i])
 
@@ -129,21 +187,29 @@ def measure_loop(lib_path, items, quality, threads, runs, warmup):
         dt = time.perf_counter() - t
         if it >= warmup:
             times.append(dt)
-    return times
+    return times, sorted(failed)
 
 
-def measure_cpu(items, quality, runs):
+def measure_cpu(items, quality, runs, dictionary=None):
     os.environ["ORC_FAST"] = "1"
     import orc
     times = []
+    total = 0
     for it in range(1 + runs):
+        total = 0
         t = time.perf_counter()
         for x in items:
-            orc.compress(x, quality, LGWIN)
+            if dictionary is None:
+                total += len(orc.compress(x, quality, LGWIN))
+                continue
+            try:
+                total += sum(map(len, orc.stream_with_flushes(x, [(0, 0), (1, quality), (2, LGWIN)], [], dictionary=dictionary)))
+            except orc.ReferencePanics:
+                pass  # (the reference fails on this item: the library fails it alone)
         dt = time.perf_counter() - t
         if it >= 1:
             times.append(dt)
-    return times
+    return times, total
 
 
 def child(args):
@@ -152,29 +218,33 @@ def child(args):
         for data in (["text"] if CLASSES[name][0] == "alice" else ["text", "mixed"]):
             items = items_of(name, data)
             first = items[:args.loop_items]
+            dictionary = dictionary_of(data, args.dictionary) if args.dictionary and not args.plain else None
             for quality in [int(q) for q in args.qualities.split(",")]:
                 row = {"class": name, "data": data, "quality": quality, "items": len(items), "bytes": sum(map(len, items))}
                 if args.child == "batch":
-                    times, csize, info = measure_batch(args.lib, first if args.first_only else items, quality, args.runs, args.warmup)
-                    row.update(stats(times), compressed_bytes=csize, batch_info=info, measured_items=len(first) if args.first_only else len(items))
+                    times, csize, info, failed = measure_batch(args.lib, first if args.first_only else items, quality, args.runs, args.warmup, dictionary)
+                    row.update(stats(times), compressed_bytes=csize, batch_info=info, reference_fails_on_items=failed, measured_items=len(first) if args.first_only else len(items))
                 elif args.child == "loop":
-                    row.update(stats(measure_loop(args.lib, first, quality, args.threads, args.runs, 1)), threads=args.threads, measured_items=len(first))
+                    times, failed = measure_loop(args.lib, first, quality, args.threads, args.runs, 1, dictionary)
+                    row.update(stats(times), threads=args.threads, measured_items=len(first), reference_fails_on_items=failed)
                 else:
-                    row.update(stats(measure_cpu(first, quality, args.runs)), measured_items=len(first))
+                    times, csize = measure_cpu(first, quality, args.runs, dictionary)
+                    row.update(stats(times), measured_items=len(first), compressed_bytes=csize)
                 out.append(row)
                 print(json.dumps(row), flush=True)
     with open(args.child_out, "w") as f:
         json.dump(out, f)
 
 
-def run_child(args, what, classes, lib=None, lds=None, threads=1, limit=600, first_only=False):
+def run_child(args, what, classes, lib=None, lds=None, threads=1, limit=600, first_only=False, plain=False):
     env = dict(os.environ)
     env.pop("BROTLI_MI355X_BATCH_LDS_BITS", None)
     if lds is not None:
         env["BROTLI_MI355X_BATCH_LDS_BITS"] = str(lds)
     tmp = os.path.join(os.path.dirname(os.path.abspath(args.out)), ".batch_probe_child.json")
     cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--child", what, "--classes", ",".join(classes), "--lib", lib or args.lib,
-           "--threads", str(threads), "--runs", str(args.runs), "--warmup", str(args.warmup), "--loop-items", str(args.loop_items), "--child-out", tmp, "--qualities", args.qualities] + (["--first-only"] if first_only else [])
+           "--threads", str(threads), "--runs", str(args.runs), "--warmup", str(args.warmup), "--loop-items", str(args.loop_items), "--child-out", tmp, "--qualities", args.qualities,
+           "--dictionary", str(args.dictionary)] + (["--first-only"] if first_only else []) + (["--plain"] if plain else [])
     r = subprocess.run(cmd, env=env)
     if r.returncode != 0:
         raise SystemExit("batch_probe: %s (lds=%s, threads=%d) ended with status %d: nothing more is started" % (what, lds, threads, r.returncode))
@@ -185,6 +255,58 @@ def run_child(args, what, classes, lib=None, lds=None, threads=1, limit=600, fir
 
 def key(row):
     return "%s/%s/q%d" % (row["class"], row["data"], row["quality"])
+
+
+def main_dictionary(args, doc, save, classes):
+    doc["what"] = ("BrotliMi355xCompressBatchWithDictionary (%d bytes of dictionary) vs a loop of stream-API calls with BrotliEncoderSetCustomDictionary "
+                   "(parent commit, 1 and 4 threads) vs the oracle's dictionary stream on one CPU core vs this build's plain batch call; lgwin 22" % args.dictionary)
+    rows = {}
+    for rnd in range(args.rounds):
+        for row in run_child(args, "batch", classes, limit=900):
+            this = {k: row[k] for k in ("median_ms", "min_ms", "max_ms", "spread_pct", "runs")}
+            if rnd == 0:
+                rows[key(row)] = {"items": row["items"], "bytes": row["bytes"], "dictionary_bytes": args.dictionary, "compressed_bytes": row["compressed_bytes"],
+                                  "batch_info": row["batch_info"], "reference_fails_on_items": row["reference_fails_on_items"], "batch": this}
+            rows[key(row)].setdefault("batch_rounds", []).append(this)
+        doc["classes"] = rows
+        save()
+        for row in run_child(args, "batch", classes, limit=900, plain=True):
+            rows[key(row)]["compressed_bytes_plain"] = row["compressed_bytes"]
+            rows[key(row)].setdefault("plain_batch_rounds", []).append({k: row[k] for k in ("median_ms", "min_ms", "max_ms", "spread_pct", "runs")})
+        save()
+        for threads in (1, 4):
+            if not args.parent_lib:
+                continue
+            for row in run_child(args, "loop", classes, lib=os.path.abspath(args.parent_lib), threads=threads, limit=900):
+                scale = row["items"] / row["measured_items"]
+                # (the loop runs the first items only: it must fail on exactly those of them the batch call failed on)
+                assert row["reference_fails_on_items"] == [i for i in rows[key(row)]["reference_fails_on_items"] if i < row["measured_items"]], row
+                rows[key(row)].setdefault("parent_loop_%dt_rounds" % threads, []).append(
+                    {"median_ms_scaled": round(row["median_ms"] * scale, 3), "min_ms_scaled": round(row["min_ms"] * scale, 3), "max_ms_scaled": round(row["max_ms"] * scale, 3),
+                     "spread_pct": row["spread_pct"], "measured_items": row["measured_items"]})
+            save()
+    for row in run_child(args, "cpu", classes, limit=900):
+        scale = row["items"] / row["measured_items"]
+        rows[key(row)]["cpu_one_core"] = {"median_ms_scaled": round(row["median_ms"] * scale, 3), "measured_items": row["measured_items"], "spread_pct": row["spread_pct"]}
+    for k, v in rows.items():
+        b = statistics.median(r["median_ms"] for r in v["batch_rounds"])
+        v["batch_MBps"] = round(v["bytes"] / 1e3 / b, 1)
+        v["cpu_over_batch"] = round(v["cpu_one_core"]["median_ms_scaled"] / b, 3)
+        v["dictionary_over_plain_time"] = round(b / statistics.median(r["median_ms"] for r in v["plain_batch_rounds"]), 3)
+        v["dictionary_over_plain_bytes"] = round(v["compressed_bytes"] / v["compressed_bytes_plain"], 4)
+        loops = [v[n] for n in ("parent_loop_1t_rounds", "parent_loop_4t_rounds") if v.get(n)]
+        if loops:
+            better = min(loops, key=lambda rs: statistics.median(r["median_ms_scaled"] for r in rs))
+            worst_batch = max(r["max_ms"] for r in v["batch_rounds"])
+            best_batch = min(r["min_ms"] for r in v["batch_rounds"])
+            v["better_loop_over_batch"] = {"median": round(statistics.median(r["median_ms_scaled"] for r in better) / b, 1),
+                                           "min": round(min(r["min_ms_scaled"] for r in better) / worst_batch, 1),
+                                           "max": round(max(r["max_ms_scaled"] for r in better) / best_batch, 1)}
+            v["every_run_beats_every_parent_run"] = bool(worst_batch < min(r["min_ms_scaled"] for r in better))
+        else:
+            v["better_loop_over_batch"] = "not measured"
+    save()
+    print(json.dumps(doc, indent=1))
 
 
 def main():
@@ -201,6 +323,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=1, help="how often this build and the parent's batch call alternate (qualities other than 0 and 1)")
     ap.add_argument("--only", default="", help="comma list of headline classes (default: all)")
     ap.add_argument("--first-only", action="store_true")
+    ap.add_argument("--dictionary", type=int, default=0, help="bytes of shared custom dictionary: measures BrotliMi355xCompressBatchWithDictionary")
+    ap.add_argument("--plain", action="store_true", help="(child) the plain call although a dictionary size is given")
     ap.add_argument("--child", default=None)
     ap.add_argument("--classes", default="")
     ap.add_argument("--threads", type=int, default=1)
@@ -219,6 +343,8 @@ def main():
             json.dump(doc, f, indent=1)
 
     headline = [c for c in HEADLINE if not args.only or c in args.only.split(",")]
+    if args.dictionary:
+        return main_dictionary(args, doc, save, [c for c in ("4096x4KiB", "1024x64KiB") if not args.only or c in args.only.split(",")])
     fragment_qualities = set(args.qualities.split(",")) <= {"0", "1"}
     if "ab" not in skip and fragment_qualities:
         # the table's home: device memory (0) against workgroup memory (11, the largest the library keeps there), the same jobs,
