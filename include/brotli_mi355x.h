@@ -234,10 +234,31 @@ int32_t BrotliMi355xCompressBatchWithDictionary(int quality, int lgwin, BrotliEn
                                                 size_t count, const uint8_t* const* inputs, const size_t* input_sizes,
                                                 uint8_t* const* outputs, size_t* output_sizes /* in: capacity, out: size */,
                                                 int32_t* item_results /* may be NULL */);
-/* The last BrotliMi355xCompressBatch / BrotliMi355xCompressBatchWithDictionary call of the calling thread: info[0] items, [1] items
-   encoded side by side on the device, [2] items run one by one (the one-shot path; with a dictionary the stream path), [3] items
-   answered without an encoder (empty input, capacity 0; none with a dictionary), [4] device groups, [5] dictionary bytes in use
-   after the reference's truncation (0 for the plain call), [6..7] zero.  After a call that failed as a whole only info[0] is set. */
+/* BrotliMi355xCompressBatch with routes the caller opts into.  routes == 0 is BrotliMi355xCompressBatch in every respect.  A bit
+   this build does not know fails the whole call like a device error does (returns 0, every size 0, BrotliMi355xLastError says so,
+   only info[0] of BrotliMi355xLastBatchInfo is set), so a caller can probe for routes of later builds.
+   BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS: item i still gets exactly what BrotliEncoderCompress gives, by the rules above.  In
+   addition to the items the plain call takes side by side, an item of more than one and at most four input blocks
+   (65 536 < input_sizes[i] <= 262 144) at qualities 5 .. 8, lgwin 17 .. 24 runs on the device as ONE parse chain that walks from
+   block to block, side by side with the other such items of the call (groups of their own, under the same environment limits),
+   and leaves up to four meta-blocks.  Every other item goes as in the plain call.  When a meta-block that is not the item's last
+   turns out longer coded than stored, the reference stores it and parses on from another distance cache, which the chain could
+   not know: that item is redone through the one-shot path in the same call (info[6]).
+   When to set it: a chain is one wavefront bound by its own dependent loads, so a long item takes as long as a lone chain needs
+   for it however many run beside it; the one-shot path is faster per item and serial.  The route pays with many long items in a
+   call, or with data on which the one-shot path needs many rounds (see INTEGRATION.md for measured figures); with a few long
+   items of text it loses.  Not combined with a shared dictionary. */
+#define BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS 1u
+int32_t BrotliMi355xCompressBatchEx(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t count,
+                                    const uint8_t* const* inputs, const size_t* input_sizes, uint8_t* const* outputs,
+                                    size_t* output_sizes /* in: capacity, out: size */, int32_t* item_results /* may be NULL */);
+/* The last BrotliMi355xCompressBatch / BrotliMi355xCompressBatchEx / BrotliMi355xCompressBatchWithDictionary call of the calling
+   thread: info[0] items, [1] items encoded side by side on the device, [2] items run one by one (the one-shot path; with a
+   dictionary the stream path), [3] items answered without an encoder (empty input, capacity 0; none with a dictionary), [4] device
+   groups (those of long items included), [5] dictionary bytes in use after the reference's truncation (0 for the plain call),
+   [6] items that began side by side and were redone one by one (counted in [2], not in [1]), [7] of the items counted in [1],
+   those longer than one input block; [6] and [7] are zero unless BrotliMi355xCompressBatchEx was called with
+   BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS.  After a call that failed as a whole only info[0] is set. */
 void BrotliMi355xLastBatchInfo(uint64_t info[8]);
 /* Human-readable description of the device backing the library ("hip:gfx950 (...)"). */
 const char* BrotliMi355xDeviceName(void);

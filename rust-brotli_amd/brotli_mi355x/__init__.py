@@ -92,6 +92,10 @@ def _bind(lib):
         lib.BrotliMi355xCompressBatchWithDictionary.restype = c_int32
         lib.BrotliMi355xCompressBatchWithDictionary.argtypes = [c_int, c_int, c_int, c_size_t, c_char_p, c_size_t, POINTER(c_char_p), POINTER(c_size_t),
                                                                 POINTER(c_void_p), POINTER(c_size_t), POINTER(c_int32)]
+    if hasattr(lib, "BrotliMi355xCompressBatchEx"):
+        lib.BrotliMi355xCompressBatchEx.restype = c_int32
+        lib.BrotliMi355xCompressBatchEx.argtypes = [c_int, c_int, c_int, c_uint32, c_size_t, POINTER(c_char_p), POINTER(c_size_t), POINTER(c_void_p),
+                                                    POINTER(c_size_t), POINTER(c_int32)]
     lib.BrotliMi355xDeviceName.restype = c_char_p
     lib.BrotliMi355xLastError.restype = c_char_p
     return lib
@@ -171,7 +175,9 @@ class Library(object):
             raise BrotliCompressorException("BrotliEncoderCompress failed: " + self.last_error())
         return ctypes.string_at(out, n.value)
 
-    def compress_batch(self, items, quality=0, lgwin=22, mode=0, dictionary=None):
+    BATCH_ROUTE_LONG_ITEMS = 1  # BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS
+
+    def compress_batch(self, items, quality=0, lgwin=22, mode=0, dictionary=None, long_items=False):
         """BrotliMi355xCompressBatch: every item becomes a stream of its own, the same bytes as compress(item, quality, lgwin,
         mode), in one call.  Side by side on the device (the call for many small payloads): every item at qualities 0 and 1, and
         at qualities 5 to 8 the items of at most 65 536 bytes at lgwin 17 to 24.  Everything else runs item by item in the same
@@ -179,7 +185,13 @@ class Library(object):
 
         dictionary (bytes): BrotliMi355xCompressBatchWithDictionary -- every item is the stream of an Encoder(params, dictionary)
         that gets the item in one finish(); a decoder needs the same dictionary.  Side by side at qualities 5 to 8, lgwin 17 to 24,
-        a dictionary of 2 to 65 536 bytes and items of 1 to 65 536 bytes."""
+        a dictionary of 2 to 65 536 bytes and items of 1 to 65 536 bytes.
+
+        long_items=True: BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS -- at qualities 5 to 8 and lgwin 17
+        to 24 the items of 65 537 to 262 144 bytes run side by side as well, one chain each (the same bytes).  It pays with many
+        such items in a call; a few dozen long items of text are faster without it.  Not combined with a dictionary."""
+        if long_items and dictionary is not None:
+            raise ValueError("long_items and dictionary cannot be combined: BrotliMi355xCompressBatchWithDictionary has no routes")
         items = [bytes(x) for x in items]
         count = len(items)
         if count == 0:
@@ -199,7 +211,10 @@ class Library(object):
         outputs = (c_void_p * count)(*[base + s for s in starts])
         out_sizes = (c_size_t * count)(*caps)
         results = (c_int32 * count)()
-        if dictionary is None:
+        if long_items:
+            name = "BrotliMi355xCompressBatchEx"
+            ok = self.lib.BrotliMi355xCompressBatchEx(quality, lgwin, mode, self.BATCH_ROUTE_LONG_ITEMS, count, inputs, in_sizes, outputs, out_sizes, results)
+        elif dictionary is None:
             name = "BrotliMi355xCompressBatch"
             ok = self.lib.BrotliMi355xCompressBatch(quality, lgwin, mode, count, inputs, in_sizes, outputs, out_sizes, results)
         else:
@@ -215,7 +230,9 @@ class Library(object):
 
     def last_batch_info(self):
         """BrotliMi355xLastBatchInfo: the last compress_batch call of this thread as a list of 8 integers -- [0] items, [1] items
-        encoded side by side on the device, [2] items run one by one, [3] items answered without an encoder, [4] device groups, [5] dictionary bytes in use (0 without one)."""
+        encoded side by side on the device, [2] items run one by one, [3] items answered without an encoder, [4] device groups, [5] dictionary bytes in use (0 without one),
+        [6] items that began side by side and were redone one by one (counted in [2]), [7] of the items in [1], those longer than one
+        input block ([6] and [7]: long_items=True only)."""
         info = (c_uint64 * 8)()
         self.lib.BrotliMi355xLastBatchInfo.restype = None
         self.lib.BrotliMi355xLastBatchInfo.argtypes = [POINTER(c_uint64)]

@@ -70,6 +70,29 @@ struct BatchParseJob {
 };
 // one wavefront per table; a wavefront takes items from `counter` until none is left
 void lz77_batch_parse(const BatchParseJob& J);
+// Items of several blocks.  A meta-block of an item: a whole number of input blocks (the item's last one may be short).
+static constexpr uint32_t kBatchLongBlocks = 4;  // input blocks per item at most, hence meta-blocks
+static constexpr uint32_t kBatchLongBytes = 262144;
+struct BatchLongMetaBlock {
+  uint32_t start, bytes;  // item-local text range
+  uint32_t first_cmd;     // in the item's slab, from cmd_base: its raw commands lie contiguous, in text order
+  uint32_t n_cmds;        // raw commands (the trailing insert-only command is not in the slab)
+  uint32_t n_lits;        // literals, the trailing ones included
+  uint32_t trailing;      // literals of the trailing insert-only command (0: there is none)
+  uint32_t uncompressed;  // should_compress said no
+  uint32_t pad;
+};
+struct BatchLongRecord {
+  uint32_t n_mb;          // 1 .. kBatchLongBlocks
+  uint32_t overflow;      // the slab was too small (cannot happen: a copy is at least two bytes long); the chain stopped there
+  uint32_t bad_commands;  // always 0 (no dictionary end to cut a match at)
+  uint32_t pad;
+  BatchLongMetaBlock mb[kBatchLongBlocks];
+};
+// the same launch shape as lz77_batch_parse; J.records is not used, J.dict.bytes is 0, every item has kBatchLongBytes at most
+void lz77_batch_parse_long(const BatchParseJob& J, BatchLongRecord* records);
+// out[offsets[kBatchLongBlocks * i + m] ..) = the finished commands of meta-block m of item i and its trailing insert-only command
+void lz77_batch_gather_long(const BatchParseJob& J, const BatchLongRecord* records, const uint32_t* offsets_dev, Command* out);
 // The dictionary path.  lz77_batch_dict_text: text[items[i].text_off - dict_bytes ..) = dictionary | item i (packed + starts[i]) for
 // every item; `text` is zero where nothing is written, text_off is a multiple of 64 and at least dict_bytes rounded up to 16.
 // dict_shifted_dev: 16-byte aligned, (-dict_bytes & 15) zero bytes and then the dictionary, so that it ends on a 16-byte boundary.
@@ -95,14 +118,27 @@ bool BatchDictionaryEligible(const EncoderParams& params, size_t dict_size, size
 void BatchGreedyCompressWithDictionary(const EncoderParams& params, const uint8_t* dict, size_t dict_size, size_t count,
                                        const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
                                        std::vector<uint8_t>* reference_fails, uint32_t* groups);
+// Items of several blocks, each one chain: 1 << lgblock < size <= kBatchLongBytes, otherwise as BatchGreedyEligible.
+bool BatchLongEligible(const EncoderParams& params, size_t input_size);
+// (*demoted)[i] != 0: a meta-block of item i that is not its last took the size fallback (encode.rs:2141-2163), which the chain
+// cannot know: the stream stays empty and the caller redoes the item through the one-shot path.
+void BatchLongCompress(const EncoderParams& params, size_t count, const uint8_t* const* inputs, const size_t* sizes,
+                       std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* demoted, uint32_t* groups);
 
-// One group through the meta-block stage (encoder.cpp): meta-block i = item i, a complete stream of its own.
+// One group through the meta-block stage (encoder.cpp): an entry is one meta-block; the meta-blocks of an item follow each other
+// and make a complete stream of their own.  An item of one meta-block leaves the fields behind `uncompressed` at zero.
 struct BatchStreamItem {
   uint32_t start, bytes;         // in the group's packed text (items back to back)
   uint32_t cmd_offset, n_cmds;   // in the gathered command array
   uint32_t n_lits;
   uint32_t uncompressed;
-  uint64_t out_byte, out_bytes;  // result: where its stream lies in `out`
+  uint32_t follows;              // not the first meta-block of its item: it goes on at the bit where the one in front ended
+  uint32_t more;                 // not the last meta-block of its item
+  uint32_t item_bytes;           // the item's size, the size hint of its stream (0: `bytes`)
+  uint8_t prev_byte, prev_byte2; // follows != 0: the two text bytes in front of `start`
+  uint8_t demoted;               // result, on an item's first entry: a meta-block with `more` set took the size fallback -- the
+                                 // parse behind it does not hold, the item's stream is not to be used
+  uint64_t out_byte, out_bytes;  // result, on an item's first entry: where its stream lies in `out`
 };
 void EncodeBatchMetaBlocks(const EncoderParams& finalized, const uint8_t* packed_text_dev, const Command* cmds_dev, uint32_t n_cmds,
                            std::vector<BatchStreamItem>* items, std::vector<uint8_t>* out);

@@ -67,25 +67,20 @@ bool BatchDictionaryEligible(const EncoderParams& user, size_t dict_size, size_t
   return p.hasher.type == 5 && p.hasher.block_bits <= 7 && input_size <= ((size_t)1 << p.lgblock) && dict_size <= ((size_t)1 << p.lgwin) - 16;
 }
 
+bool BatchLongEligible(const EncoderParams& user, size_t input_size) {
+  if (input_size > kBatchLongBytes) return false;
+  if (user.quality < 5 || user.quality > 8 || user.lgwin < 17 || user.lgwin > 24 || user.large_window) return false;
+  if (user.catable || user.appendable || user.bare_stream || user.byte_align || user.magic_number) return false;
+  // (kBatchLongBytes is the ring-buffer size at lgwin 17 and below the size hint that selects another hasher)
+  const EncoderParams p = ItemParams(user, input_size);
+  return p.hasher.type == 5 && p.hasher.block_bits <= 7 && input_size > ((size_t)1 << p.lgblock) &&
+         input_size <= (size_t)kBatchLongBlocks << p.lgblock;
+}
+
 namespace {
 
-// p: the parameters the items share, finalized.  dict == nullptr: the plain call.
-void CompressGroups(const EncoderParams& p, const uint8_t* dict, uint32_t D, size_t count, const uint8_t* const* inputs, const size_t* sizes,
-                    std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* reference_fails, uint32_t* groups) {
-  // read once per process, like BROTLI_MI355X_FRAGMENT_BATCH
-  static const size_t group_items = std::max<size_t>(1, EnvSize("BROTLI_MI355X_BATCH_GROUP_ITEMS", 4096));
-  static const size_t group_bytes = std::max<size_t>(1, EnvSize("BROTLI_MI355X_BATCH_GROUP_BYTES", (size_t)64 << 20));
-  // a table is 1 MiB at quality 5 and 16 MiB at quality 8: as many as the parse kernel keeps resident (256 CUs x 4 SIMDs x 4
-  // wavefronts) within 8 GiB
-  static const size_t table_override = EnvSize("BROTLI_MI355X_BATCH_TABLES", 0);
-  streams->assign(count, std::vector<uint8_t>());
-  if (reference_fails) reference_fails->assign(count, 0);
-  *groups = 0;
-  if (count == 0) return;
-  const size_t keys_per_table = (size_t)1 << p.hasher.bucket_bits;
-  const size_t table_bytes = keys_per_table * 2 + (keys_per_table << p.hasher.block_bits) * 4;
-  const size_t tables_max = table_override ? table_override : std::max<size_t>(1, std::min<size_t>(4096, ((size_t)8 << 30) / table_bytes));
-
+// the search parameters of a chain whose stream starts at 0 and ends inside the first ring-buffer revolution
+Lz77Params ChainParams(const EncoderParams& p) {
   Lz77Params P;
   memset(&P, 0, sizeof(P));
   P.ring_mask = (1u << ComputeRbBits(p)) - 1u;
@@ -108,6 +103,27 @@ void CompressGroups(const EncoderParams& p, const uint8_t* dict, uint32_t D, siz
   P.masked_from = kNeverMasked;  // (an item ends inside the first ring-buffer revolution of its stream)
   P.block_bytes = 1u << p.lgblock;
   P.max_metablock_bytes = (uint32_t)MaxMetablockSize(p);
+  return P;
+}
+
+// p: the parameters the items share, finalized.  dict == nullptr: the plain call.
+void CompressGroups(const EncoderParams& p, const uint8_t* dict, uint32_t D, size_t count, const uint8_t* const* inputs, const size_t* sizes,
+                    std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* reference_fails, uint32_t* groups) {
+  // read once per process, like BROTLI_MI355X_FRAGMENT_BATCH
+  static const size_t group_items = std::max<size_t>(1, EnvSize("BROTLI_MI355X_BATCH_GROUP_ITEMS", 4096));
+  static const size_t group_bytes = std::max<size_t>(1, EnvSize("BROTLI_MI355X_BATCH_GROUP_BYTES", (size_t)64 << 20));
+  // a table is 1 MiB at quality 5 and 16 MiB at quality 8: as many as the parse kernel keeps resident (256 CUs x 4 SIMDs x 4
+  // wavefronts) within 8 GiB
+  static const size_t table_override = EnvSize("BROTLI_MI355X_BATCH_TABLES", 0);
+  streams->assign(count, std::vector<uint8_t>());
+  if (reference_fails) reference_fails->assign(count, 0);
+  *groups = 0;
+  if (count == 0) return;
+  const size_t keys_per_table = (size_t)1 << p.hasher.bucket_bits;
+  const size_t table_bytes = keys_per_table * 2 + (keys_per_table << p.hasher.block_bits) * 4;
+  const size_t tables_max = table_override ? table_override : std::max<size_t>(1, std::min<size_t>(4096, ((size_t)8 << 30) / table_bytes));
+
+  const Lz77Params P = ChainParams(p);
 
   // ---- the dictionary, once per call: its bytes on the device, and what the prepend leaves in a table (BatchDictImage)
   DevBlocks call_mem;
@@ -260,6 +276,150 @@ void CompressGroups(const EncoderParams& p, const uint8_t* dict, uint32_t D, siz
   }
 }
 
+// Items of several blocks: the plan of CompressGroups with up to kBatchLongBlocks meta-blocks per item.
+void CompressLongGroups(const EncoderParams& p, size_t count, const uint8_t* const* inputs, const size_t* sizes,
+                        std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* demoted, uint32_t* groups) {
+  static const size_t group_items = std::max<size_t>(1, EnvSize("BROTLI_MI355X_BATCH_GROUP_ITEMS", 4096));
+  static const size_t group_bytes = std::max<size_t>(1, EnvSize("BROTLI_MI355X_BATCH_GROUP_BYTES", (size_t)64 << 20));
+  static const size_t table_override = EnvSize("BROTLI_MI355X_BATCH_TABLES", 0);
+  streams->assign(count, std::vector<uint8_t>());
+  demoted->assign(count, 0);
+  *groups = 0;
+  if (count == 0) return;
+  const size_t keys_per_table = (size_t)1 << p.hasher.bucket_bits;
+  const size_t table_bytes = keys_per_table * 2 + (keys_per_table << p.hasher.block_bits) * 4;
+  const size_t tables_max = table_override ? table_override : std::max<size_t>(1, std::min<size_t>(4096, ((size_t)8 << 30) / table_bytes));
+  const Lz77Params P = ChainParams(p);
+
+  PinnedArray<uint8_t> staging;
+  PinnedArray<BatchItem> items;
+  PinnedArray<uint32_t> order, offsets;
+  PinnedArray<BatchLongRecord> records;
+  size_t first = 0;
+  while (first < count) {
+    size_t last = first, padded = 0, packed = 0;
+    while (last < count && last - first < group_items && (last == first || packed + sizes[last] <= group_bytes)) {
+      padded += Padded((uint32_t)sizes[last]);
+      packed += sizes[last];
+      ++last;
+    }
+    const uint32_t n = (uint32_t)(last - first);
+    ++*groups;
+    // one page-locked buffer, one upload: [padded text | 64 | packed text | 64]
+    const size_t packed_at = padded + 64;
+    const size_t text_bytes = packed_at + packed + 64;
+    staging.resize_discard(text_bytes);
+    memset(staging.data(), 0, text_bytes);
+    items.resize_discard(n);
+    order.resize_discard(n);
+    std::vector<uint32_t> starts(n);
+    {
+      uint32_t off = 0, start = 0, cmd_base = 0;
+      for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t bytes = (uint32_t)sizes[first + i];
+        memcpy(staging.data() + off, inputs[first + i], bytes);
+        memcpy(staging.data() + packed_at + start, inputs[first + i], bytes);
+        items[i] = BatchItem{off, bytes, cmd_base, bytes / 2 + 8};
+        starts[i] = start;
+        off += Padded(bytes);
+        start += bytes;
+        cmd_base += bytes / 2 + 8;
+        order[i] = i;
+      }
+      std::stable_sort(order.data(), order.data() + n, [&](uint32_t a, uint32_t b) { return items[a].bytes > items[b].bytes; });
+    }
+    const size_t cmd_slots = (size_t)items[n - 1].cmd_base + items[n - 1].cmd_cap;
+    const uint32_t tables = (uint32_t)std::min<size_t>(tables_max, n);
+
+    DevBlocks mem;
+    uint8_t* uploaded = mem.uninit<uint8_t>(text_bytes);
+    dev_h2d_bulk(uploaded, staging.data(), text_bytes);
+    BatchItem* items_dev = mem.uninit<BatchItem>((size_t)n * sizeof(BatchItem));
+    dev_h2d(items_dev, items.data(), (size_t)n * sizeof(BatchItem));
+    Lz77Buffers B{};
+    B.text = uploaded;
+    B.keys = mem.uninit<uint16_t>(padded * 2 + 256);
+    B.changed_count = mem.zeroed<uint32_t>(64);
+    B.dict_items = nullptr;
+    B.run_end = nullptr;
+    Lz77Params PK = P;
+    PK.total_bytes = (uint32_t)padded;  // (the last item's padding gives every position four bytes to hash)
+    lz77_compute_keys(PK, B);
+
+    BatchParseJob J{};
+    J.P = P;
+    J.text = uploaded;
+    J.keys = B.keys;
+    J.flags = mem.uninit<uint8_t>(padded + 64);
+    J.slabs = mem.uninit<Command>(cmd_slots * sizeof(Command) + 64);
+    uint32_t* order_dev = mem.uninit<uint32_t>((size_t)n * 4);
+    dev_h2d(order_dev, order.data(), (size_t)n * 4);
+    J.items = items_dev;
+    J.order = order_dev;
+    J.n_items = n;
+    J.tables = tables;
+    J.num = mem.uninit<uint16_t>((size_t)tables * keys_per_table * 2 + 64);
+    J.buckets = mem.uninit<uint32_t>(((size_t)tables * keys_per_table << p.hasher.block_bits) * 4 + 64);
+    J.counter = mem.zeroed<uint32_t>(64);
+    J.records = nullptr;
+    BatchLongRecord* records_dev = mem.uninit<BatchLongRecord>((size_t)n * sizeof(BatchLongRecord));
+    lz77_batch_parse_long(J, records_dev);
+    records.resize_discard(n);
+    dev_d2h(records.data(), records_dev, (size_t)n * sizeof(BatchLongRecord));
+    // ---- command gather: the offsets per meta-block from the records (one small round trip)
+    offsets.resize_discard((size_t)n * kBatchLongBlocks);
+    std::vector<BatchStreamItem> mbs;
+    std::vector<uint32_t> first_mb(n);
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+      const BatchLongRecord& r = records[i];
+      if (r.overflow) throw std::runtime_error("brotli_mi355x: a batch chain ran out of its command slab");
+      uint32_t at = 0, cmd_at = 0;
+      first_mb[i] = (uint32_t)mbs.size();
+      for (uint32_t m = 0; m < kBatchLongBlocks; ++m) offsets[(size_t)i * kBatchLongBlocks + m] = 0;
+      for (uint32_t m = 0; m < r.n_mb && m < kBatchLongBlocks; ++m) {
+        const BatchLongMetaBlock& mb = r.mb[m];
+        if (mb.start != at || mb.bytes == 0 || mb.first_cmd != cmd_at) break;
+        offsets[(size_t)i * kBatchLongBlocks + m] = (uint32_t)total;
+        BatchStreamItem e{};
+        e.start = starts[i] + mb.start;
+        e.bytes = mb.bytes;
+        e.cmd_offset = (uint32_t)total;
+        e.n_cmds = mb.n_cmds + (mb.trailing != 0 ? 1u : 0u);
+        e.n_lits = mb.n_lits;
+        e.uncompressed = mb.uncompressed;
+        e.follows = m != 0;
+        e.more = m + 1 != r.n_mb;
+        e.item_bytes = items[i].bytes;
+        if (m != 0) {
+          e.prev_byte = inputs[first + i][mb.start - 1];
+          e.prev_byte2 = inputs[first + i][mb.start - 2];
+        }
+        mbs.push_back(e);
+        total += e.n_cmds;
+        at += mb.bytes;
+        cmd_at += mb.n_cmds;
+      }
+      if (at != items[i].bytes || cmd_at > items[i].cmd_cap) throw std::runtime_error("brotli_mi355x: a batch chain left meta-block records that do not cover its item");
+    }
+    uint32_t* offsets_dev = mem.uninit<uint32_t>((size_t)n * kBatchLongBlocks * 4);
+    dev_h2d(offsets_dev, offsets.data(), (size_t)n * kBatchLongBlocks * 4);
+    Command* cmds = mem.uninit<Command>((size_t)(total + 16) * sizeof(Command));
+    lz77_batch_gather_long(J, records_dev, offsets_dev, cmds);
+    std::vector<uint8_t> out;
+    EncodeBatchMetaBlocks(p, uploaded + packed_at, cmds, (uint32_t)total, &mbs, &out);
+    for (uint32_t i = 0; i < n; ++i) {
+      const BatchStreamItem& e = mbs[first_mb[i]];
+      if (e.demoted) {
+        (*demoted)[first + i] = 1;
+        continue;
+      }
+      (*streams)[first + i].assign(out.begin() + (ptrdiff_t)e.out_byte, out.begin() + (ptrdiff_t)(e.out_byte + e.out_bytes));
+    }
+    first = last;
+  }
+}
+
 }  // namespace
 
 void BatchGreedyCompress(const EncoderParams& user, size_t count, const uint8_t* const* inputs, const size_t* sizes,
@@ -271,6 +431,12 @@ void BatchGreedyCompressWithDictionary(const EncoderParams& user, const uint8_t*
                                        const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
                                        std::vector<uint8_t>* reference_fails, uint32_t* groups) {
   CompressGroups(DictionaryItemParams(user, count ? sizes[0] : 0), dict, (uint32_t)dict_size, count, inputs, sizes, streams, reference_fails, groups);
+}
+
+void BatchLongCompress(const EncoderParams& user, size_t count, const uint8_t* const* inputs, const size_t* sizes,
+                       std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* demoted, uint32_t* groups) {
+  // (nothing in the parameters differs between items of at most kBatchLongBytes)
+  CompressLongGroups(ItemParams(user, count ? sizes[0] : 0), count, inputs, sizes, streams, demoted, groups);
 }
 
 }  // namespace brotli_mi355x

@@ -160,5 +160,178 @@ BR_DEV Command br_batch_command(const BatchParseJob& J, const BatchItem& it, con
   return br_finish_command(J.slabs[(size_t)it.cmd_base + i], J.P.num_direct_distance_codes, J.P.dist_postfix_bits);
 }
 
+// ---- items of several blocks (k_parse_batch_long) -------------------------------------------------------------------------------
+// One item of two to kBatchLongBlocks input blocks: what br_parse_live does for the blocks [0, n) of a stream that starts at 0, and at
+// the item's end what br_batch_item does for its only block.  The books between the blocks are br_parse_live's, line by line (a
+// copy, not a shared helper: that function is inlined into k_parse_live, whose code generation this leaves alone); what differs is
+// where they end up -- the chain is the only writer of its slab, so extend_last_command and the literals pending at a block's entry
+// are applied to its own raw commands in place (the host resolver's CmdPatch kinds 0 and 2), a block's commands start where the
+// block in front stopped, and every meta-block the flush rule closes leaves a record.
+template <bool kRows>
+BR_DEV void br_batch_item_long(const BatchParseJob& J, BatchLongRecord* records, const ChainTables& T, ChainScratchT<false, kRows>& s,
+                               uint32_t* histo /* 256 words */, uint32_t index, uint32_t table) {
+  BatchItem it = J.items[index];
+  it.text_off = BR_UNIFORM(it.text_off);
+  it.bytes = BR_UNIFORM(it.bytes);
+  it.cmd_base = BR_UNIFORM(it.cmd_base);
+  it.cmd_cap = BR_UNIFORM(it.cmd_cap);
+  Lz77Params P = J.P;
+  P.total_bytes = it.bytes;
+  ChainTables t = T;
+  t.text = J.text + it.text_off;
+  t.keys = J.keys + it.text_off;
+  t.flags_next = J.flags + it.text_off;
+  t.cmds = J.slabs;
+  LiveRing lr;
+  const size_t keys_per_table = (size_t)1 << P.bucket_bits;
+  lr.num = J.num + (size_t)table * keys_per_table;
+  lr.buckets = J.buckets + (((size_t)table * keys_per_table) << P.block_bits);
+  lr.keys = t.keys;
+  lr.bits = P.block_bits;
+  br_live_reset(lr, P.bucket_bits);
+  Command* slab = J.slabs + (size_t)it.cmd_base;
+  SegEntry entry;
+  entry.pos = 0;
+  entry.apply = P.spree_window;
+  entry.cache[0] = 4;
+  entry.cache[1] = 11;
+  entry.cache[2] = 15;
+  entry.cache[3] = 16;
+  entry.insert_len = 0;
+  entry.ext_allowed = 0;
+  entry.dict_lookups = entry.dict_matches = 0;
+  entry.ext_max_distance = 0;
+  entry.dict_exact = 1;
+  entry.head_kind = kHeadNone;
+  entry.head_base = entry.head_p1 = 0;
+  entry.pad = 0;
+  // the books of the open meta-block (LiveBlockState) and of the slab
+  uint32_t mb_start = 0, mb_cmds = 0, mb_lits = 0, mb_first_cmd = 0;
+  uint32_t last_valid = 0, last_dist_code = 0, last_copy_len = 0;
+  int32_t saved_cache[4] = {4, 11, 15, 16};  // the distance cache at the start of the open meta-block
+  uint32_t carry = 0;                        // literals pending at the entry of the block
+  uint32_t used = 0;                         // raw commands in the slab so far
+  uint32_t n_mb = 0, overflow = 0;
+  const uint32_t max_mb = P.max_metablock_bytes, limit = max_mb / 8;
+  for (uint32_t bs = 0; bs < it.bytes && n_mb < kBatchLongBlocks;) {
+    const uint32_t be = it.bytes - bs > P.block_bytes ? bs + P.block_bytes : it.bytes;
+    const bool last = be == it.bytes;
+    // StitchToPreviousBlockInternal (mod.rs:210-222) of the block behind this one: what kSegTailStitched stands for
+    const bool stitched = !last && it.bytes - be >= P.htl - 1 && be >= 3;
+    Segment seg;
+    seg.start = seg.blk_start = bs;
+    seg.end = seg.blk_end = be;
+    seg.flags = kSegFirstInBlock | kSegLastInBlock | (stitched ? kSegTailStitched : 0u);
+    seg.cmd_base = it.cmd_base + used;
+    seg.block_index = 0;
+    seg.cmd_cap = it.cmd_cap - used;
+    SegExit left;
+    SegEntry next;
+    BlockTail tail;
+    br_parse_segment<false, kRows, true>(P, t, s, seg, entry, left, next, &lr, &tail);
+    if (tail.n_cmds > seg.cmd_cap) {
+      overflow = 1;
+      break;
+    }
+    if (stitched) br_live_store(lr, be - 3u, 1, 3, 1, 0);
+    // ---- the books, as in br_parse_live; the fix-ups go into the slab
+    if (BR_LANE == 0) {
+      if (tail.ext_len != 0 && last_valid) slab[used - 1].copy_len_ += tail.ext_len;  // (its copy code is its length: no dictionary word is extended)
+      if (tail.n_cmds != 0 && carry != 0) slab[used].insert_len_ += carry;
+    }
+    if (tail.ext_len != 0 && last_valid) last_copy_len += tail.ext_len;
+    mb_cmds += tail.n_cmds;
+    mb_lits += tail.n_lits;
+    if (tail.n_cmds != 0) {
+      mb_lits += carry;
+      carry = tail.insert_len;
+      last_valid = 1;
+      last_dist_code = tail.last_dist_code;
+      last_copy_len = tail.last_copy_len;
+    } else {
+      carry += tail.insert_len;
+    }
+    used += tail.n_cmds;
+    const bool next_fits = (uint64_t)(be - mb_start) + P.block_bytes <= (uint64_t)max_mb;
+    if (last || !(next_fits && mb_lits < limit && mb_cmds < limit)) {  // the meta-block is closed here
+      const uint32_t bytes = be - mb_start;
+      const uint32_t cmds_all = mb_cmds + (carry != 0 ? 1u : 0u), lits_all = mb_lits + carry;  // with the trailing insert-only command
+      bool compress = true;
+      if (cmds_all < (bytes >> 8) + 2 && (float)lits_all > 0.99f * (float)bytes) {
+        BR_SYNC();
+        for (uint32_t i = BR_LANE; i < 256; i += BR_NLANES) histo[i] = 0;
+        BR_SYNC();
+        for (uint32_t q = mb_start + 13u * (uint32_t)BR_LANE; q < be; q += 13u * BR_NLANES) BR_ATOMIC_INC(&histo[t.text[q]]);
+        BR_SYNC();
+        const float threshold = (float)bytes * 7.92f / 13.0f;
+        compress = !(br_bits_entropy(t.logs, histo, 256) > threshold);
+      }
+      if (BR_LANE == 0) {
+        BatchLongMetaBlock m;
+        m.start = mb_start;
+        m.bytes = bytes;
+        m.first_cmd = mb_first_cmd;
+        m.n_cmds = mb_cmds;
+        m.n_lits = lits_all;
+        m.trailing = carry;
+        m.uncompressed = compress ? 0u : 1u;
+        m.pad = 0;
+        records[index].mb[n_mb] = m;
+      }
+      ++n_mb;
+      // a stored meta-block hands the distance cache of its START to the next one (encode.rs:1994)
+      if (!compress)
+        for (int i = 0; i < 4; ++i) next.cache[i] = saved_cache[i];
+      for (int i = 0; i < 4; ++i) saved_cache[i] = next.cache[i];
+      mb_start = be;
+      mb_cmds = mb_lits = 0;
+      mb_first_cmd = used;
+      last_valid = 0;
+      carry = 0;  // (pending literals went into its trailing insert-only command)
+    }
+    // ---- the entry of the next block
+    const uint32_t was_exact = entry.dict_exact;
+    entry = next;
+    entry.pos = be;
+    entry.insert_len = carry;
+    entry.dict_exact = was_exact;
+    entry.head_kind = kHeadNone;
+    entry.head_base = entry.head_p1 = 0;
+    entry.ext_allowed = 0;
+    if (mb_cmds != 0 && carry == 0 && last_valid) {
+      const uint64_t cmd_dist = (uint64_t)(int64_t)next.cache[0];
+      if (last_dist_code < 16 || (uint64_t)last_dist_code - 15 == cmd_dist) {
+        const uint64_t lpp = (uint64_t)be - last_copy_len;
+        const uint64_t max_distance = lpp < P.max_backward_limit ? lpp : P.max_backward_limit;
+        if (cmd_dist <= max_distance) entry.ext_allowed = 1;
+      }
+    }
+    BR_SYNC();
+    bs = be;
+  }
+  if (BR_LANE == 0) {
+    records[index].n_mb = n_mb;
+    records[index].overflow = overflow;
+    records[index].bad_commands = 0;
+    records[index].pad = 0;
+  }
+  BR_SYNC();
+}
+
+// command i of meta-block m of an item, as the meta-block stage wants it: its raw commands, then its trailing insert-only command
+BR_DEV Command br_batch_long_command(const BatchParseJob& J, const BatchItem& it, const BatchLongMetaBlock& m, uint32_t i) {
+  if (i >= m.n_cmds) {
+    // Command::init_insert, command.rs:38-44
+    Command c;
+    c.insert_len_ = m.trailing;
+    c.copy_len_ = 4u << 25;
+    c.dist_extra_ = 0;
+    c.dist_prefix_ = (uint16_t)((1u << 10) | 16u);
+    c.cmd_prefix_ = br_combine_length_codes(br_insert_length_code(m.trailing), br_copy_length_code(4), false);
+    return c;
+  }
+  return br_finish_command(J.slabs[(size_t)it.cmd_base + m.first_cmd + i], J.P.num_direct_distance_codes, J.P.dist_postfix_bits);
+}
+
 }  // namespace brotli_mi355x
 #endif

@@ -11,10 +11,8 @@
 
 namespace brotli_mi355x {
 
-void lz77_batch_parse(const BatchParseJob& J) {
-  if (J.n_items == 0) return;
-  if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
-  if (J.P.block_bits > 7) throw std::runtime_error("brotli_mi355x: the batch chains do not run the 512-deep rings");
+namespace {
+ChainTables EmuBatchChainTables(const BatchParseJob& J) {
   const DeviceTables& dt = dev_tables();
   ChainTables T;
   T.text = J.text;
@@ -35,6 +33,15 @@ void lz77_batch_parse(const BatchParseJob& J) {
   T.keys = J.keys;
   T.logs.logs_16 = dt.logs_16;
   T.logs.logs_8 = dt.logs_8;
+  return T;
+}
+}  // namespace
+
+void lz77_batch_parse(const BatchParseJob& J) {
+  if (J.n_items == 0) return;
+  if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
+  if (J.P.block_bits > 7) throw std::runtime_error("brotli_mi355x: the batch chains do not run the 512-deep rings");
+  const ChainTables T = EmuBatchChainTables(J);
   static thread_local ChainScratchT<false, false> scratch;
   uint32_t histo[256];
   for (uint32_t place = 0; place < J.n_items; ++place) {
@@ -42,6 +49,30 @@ void lz77_batch_parse(const BatchParseJob& J) {
     else br_batch_item<false>(J, T, scratch, histo, J.order[place], place % J.tables);
   }
   *J.counter = J.n_items;
+}
+
+void lz77_batch_parse_long(const BatchParseJob& J, BatchLongRecord* records) {
+  if (J.n_items == 0) return;
+  if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
+  if (J.P.block_bits > 7) throw std::runtime_error("brotli_mi355x: the batch chains do not run the 512-deep rings");
+  const ChainTables T = EmuBatchChainTables(J);
+  static thread_local ChainScratchT<false, false> scratch;
+  uint32_t histo[256];
+  for (uint32_t place = 0; place < J.n_items; ++place) br_batch_item_long<false>(J, records, T, scratch, histo, J.order[place], place % J.tables);
+  *J.counter = J.n_items;
+}
+
+void lz77_batch_gather_long(const BatchParseJob& J, const BatchLongRecord* records, const uint32_t* offsets, Command* out) {
+  for (uint32_t i = 0; i < J.n_items; ++i) {
+    const BatchLongRecord& r = records[i];
+    if (r.overflow) continue;
+    for (uint32_t m = 0; m < r.n_mb && m < kBatchLongBlocks; ++m) {
+      const BatchLongMetaBlock& mb = r.mb[m];
+      if ((uint64_t)mb.first_cmd + mb.n_cmds > J.items[i].cmd_cap) continue;
+      const uint32_t n = mb.n_cmds + (mb.trailing != 0 ? 1u : 0u);
+      for (uint32_t c = 0; c < n; ++c) out[offsets[kBatchLongBlocks * i + m] + c] = br_batch_long_command(J, J.items[i], mb, c);
+    }
+  }
 }
 
 void lz77_batch_dict_text(const uint8_t* dict, uint32_t dict_bytes, const uint8_t* packed, const uint32_t* starts, const BatchItem* items,

@@ -1005,10 +1005,19 @@ BROTLI_BOOL BrotliMi355xCompressDevice(int quality, int lgwin, BrotliEncoderMode
 // what BrotliMi355xLastBatchInfo reports: the last BrotliMi355xCompressBatch call of this thread
 static thread_local uint64_t g_batch_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
-int32_t BrotliMi355xCompressBatch(int quality, int lgwin, BrotliEncoderMode mode, size_t count, const uint8_t* const* inputs,
-                                  const size_t* input_sizes, uint8_t* const* outputs, size_t* output_sizes, int32_t* item_results) {
+// BrotliMi355xCompressBatch (routes == 0) and BrotliMi355xCompressBatchEx
+static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t count,
+                             const uint8_t* const* inputs, const size_t* input_sizes, uint8_t* const* outputs, size_t* output_sizes,
+                             int32_t* item_results) {
   uint64_t info[8] = {count, 0, 0, 0, 0, 0, 0, 0};
   memcpy(g_batch_info, info, sizeof(info));
+  if ((routes & ~(uint32_t)BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS) != 0) {
+    // a route this build does not know fails the call as a whole, like a device error: a caller can probe for later routes
+    SetError(entry, ("routes " + std::to_string(routes) + " names a route this build does not know (known: BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS = 1)").c_str());
+    for (size_t i = 0; i < count; ++i) output_sizes[i] = 0;
+    if (item_results && count) memset(item_results, 0, count * sizeof(int32_t));
+    return 0;
+  }
   if (count == 0) return 1;
   size_t total = 0;
   for (size_t i = 0; i < count; ++i) total += input_sizes[i];
@@ -1022,11 +1031,20 @@ int32_t BrotliMi355xCompressBatch(int quality, int lgwin, BrotliEncoderMode mode
     SmallCallGate gate(total);
     const bool fragments = IsFragmentStream(params);
     // The items an encoder sees and that go side by side on the device: every item of qualities 0 and 1 (fragment_stream.h), the
-    // items of one input block under an H5 hasher at qualities 5 .. 8 (batch_greedy.h).  Every other item goes through the one-shot
-    // path by itself, on this thread, in the caller's order (the same bytes, no gain in speed).
-    std::vector<size_t> item;
-    std::vector<const uint8_t*> in;
-    std::vector<size_t> in_size;
+    // items of one input block under an H5 hasher at qualities 5 .. 8 (batch_greedy.h) and, where the caller asked for that route,
+    // those of two to four blocks.  Every other item goes through the one-shot path by itself, on this thread, in the caller's
+    // order (the same bytes, no gain in speed).
+    std::vector<size_t> item, long_item;
+    std::vector<const uint8_t*> in, long_in;
+    std::vector<size_t> in_size, long_size;
+    const bool long_route = (routes & BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS) != 0;
+    auto one_by_one = [&](size_t i) {
+      std::string error;
+      results[i] = CompressOneShot(quality, lgwin, mode, input_sizes[i], inputs[i], false, &output_sizes[i], outputs[i], nullptr, &error);
+      if (!error.empty()) throw std::runtime_error(error);  // (a device error, not a buffer that is too small: the call fails as a whole)
+      if (!results[i]) output_sizes[i] = 0;
+      ++info[2];
+    };
     for (size_t i = 0; i < count; ++i) {
       const int early = OneShotWithoutEncoder(input_sizes[i], &output_sizes[i], outputs[i]);
       if (early >= 0) {
@@ -1041,11 +1059,33 @@ int32_t BrotliMi355xCompressBatch(int quality, int lgwin, BrotliEncoderMode mode
         in_size.push_back(input_sizes[i]);
         continue;
       }
-      std::string error;
-      results[i] = CompressOneShot(quality, lgwin, mode, input_sizes[i], inputs[i], false, &output_sizes[i], outputs[i], nullptr, &error);
-      if (!error.empty()) throw std::runtime_error(error);  // (a device error, not a buffer that is too small: the call fails as a whole)
-      if (!results[i]) output_sizes[i] = 0;
-      ++info[2];
+      if (long_route && BatchLongEligible(params, input_sizes[i])) {
+        long_item.push_back(i);
+        long_in.push_back(inputs[i]);
+        long_size.push_back(input_sizes[i]);
+        continue;
+      }
+      one_by_one(i);
+    }
+    // ---- the items of several blocks, one chain each, in groups of their own (BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS)
+    if (!long_item.empty()) {
+      std::vector<std::vector<uint8_t>> long_streams;
+      std::vector<uint8_t> demoted;
+      uint32_t groups = 0;
+      BatchLongCompress(params, long_item.size(), long_in.data(), long_size.data(), &long_streams, &demoted, &groups);
+      info[4] += groups;
+      for (size_t k = 0; k < long_item.size(); ++k) {
+        const size_t i = long_item[k];
+        if (demoted[k]) {
+          // a meta-block that is not the item's last took the size fallback, which its chain could not know: redone one by one
+          one_by_one(i);
+          ++info[6];
+          continue;
+        }
+        results[i] = OneShotDeliver(long_streams[k].data(), long_streams[k].size(), inputs[i], input_sizes[i], false, output_sizes[i], &output_sizes[i], outputs[i]);
+        ++info[1];
+        ++info[7];
+      }
     }
     std::vector<std::vector<uint8_t>> streams;
     if (!item.empty()) {
@@ -1055,9 +1095,9 @@ int32_t BrotliMi355xCompressBatch(int quality, int lgwin, BrotliEncoderMode mode
       } else {
         uint32_t groups = 0;
         BatchGreedyCompress(params, item.size(), in.data(), in_size.data(), &streams, &groups);
-        info[4] = groups;
+        info[4] += groups;
       }
-      info[1] = item.size();
+      info[1] += item.size();
     }
     for (size_t k = 0; k < item.size(); ++k) {
       const size_t i = item[k];
@@ -1065,7 +1105,7 @@ int32_t BrotliMi355xCompressBatch(int quality, int lgwin, BrotliEncoderMode mode
     }
   } catch (const std::exception& e) {
     // a device error fails the call as a whole
-    SetError("BrotliMi355xCompressBatch", e.what());
+    SetError(entry, e.what());
     for (size_t i = 0; i < count; ++i) output_sizes[i] = 0;
     if (item_results) memset(item_results, 0, count * sizeof(int32_t));
     return 0;
@@ -1077,6 +1117,16 @@ int32_t BrotliMi355xCompressBatch(int quality, int lgwin, BrotliEncoderMode mode
     if (!results[i]) all = 0;
   }
   return all;
+}
+
+int32_t BrotliMi355xCompressBatch(int quality, int lgwin, BrotliEncoderMode mode, size_t count, const uint8_t* const* inputs,
+                                  const size_t* input_sizes, uint8_t* const* outputs, size_t* output_sizes, int32_t* item_results) {
+  return CompressBatch("BrotliMi355xCompressBatch", quality, lgwin, mode, 0, count, inputs, input_sizes, outputs, output_sizes, item_results);
+}
+
+int32_t BrotliMi355xCompressBatchEx(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t count, const uint8_t* const* inputs,
+                                    const size_t* input_sizes, uint8_t* const* outputs, size_t* output_sizes, int32_t* item_results) {
+  return CompressBatch("BrotliMi355xCompressBatchEx", quality, lgwin, mode, routes, count, inputs, input_sizes, outputs, output_sizes, item_results);
 }
 
 // One item of BrotliMi355xCompressBatchWithDictionary by itself, through the stream state machine: the definition of the call, run as

@@ -1151,6 +1151,9 @@ void EncodeStream(const EncodeRequest& req, std::vector<uint8_t>* out, EncodeSta
 // is_last = 1, the window bits in front, and every stream on an 8-byte boundary of the group's output.  `text` holds the items
 // back to back, so that the running sum of the command lengths is the text position, as in one stream.  The size fallback
 // (encode.rs:2141-2163) is per item: nothing follows an item, so it is flipped to stored and laid out again without a second parse.
+// An item of several meta-blocks (BatchStreamItem::follows / more) is several entries in a row: only the first is preceded by the
+// window bits and the 8-byte boundary, the others go on at the bit where the one in front ended, with the context bytes of the
+// text in front and ISLAST on the last one alone.
 void EncodeBatchMetaBlocks(const EncoderParams& p, const uint8_t* text, const Command* cmds_dev, uint32_t n_cmds,
                            std::vector<BatchStreamItem>* items_io, std::vector<uint8_t>* out) {
   std::vector<BatchStreamItem>& items = *items_io;
@@ -1202,8 +1205,12 @@ void EncodeBatchMetaBlocks(const EncoderParams& p, const uint8_t* text, const Co
         default: break;
       }
       d.uncompressed = items[m].uncompressed ? 1 : 0;
-      d.is_last = 1;
+      d.is_last = items[m].more ? 0 : 1;
       d.prev_byte = d.prev_byte2 = 0;  // a stream starts here
+      if (items[m].follows) {          // ... or goes on: the context of its first literals is the text in front
+        d.prev_byte = items[m].prev_byte;
+        d.prev_byte2 = items[m].prev_byte2;
+      }
       d.num_distance_symbols = p.dist.alphabet_size;
       d.dist_postfix_bits = p.dist.distance_postfix_bits;
       d.num_direct_distance_codes = p.dist.num_direct_distance_codes;
@@ -1246,8 +1253,8 @@ void EncodeBatchMetaBlocks(const EncoderParams& p, const uint8_t* text, const Co
       if (getenv("BROTLI_MI355X_SELFTEST")) SelfTestContextStats(text, descs, cs);
       for (uint32_t m = 0; m < n_mb; ++m) {
         if (descs[m].uncompressed) continue;
-        DecideContexts(cs.data() + (size_t)m * kContextStatsWords, p.quality, items[m].bytes, items[m].bytes, &descs[m].num_contexts,
-                       &descs[m].context_map_id);
+        DecideContexts(cs.data() + (size_t)m * kContextStatsWords, p.quality, items[m].item_bytes ? items[m].item_bytes : items[m].bytes, items[m].bytes,
+                       &descs[m].num_contexts, &descs[m].context_map_id);
       }
     }
     PlanGreedyPools(&mm, &descs, &B);
@@ -1282,23 +1289,34 @@ void EncodeBatchMetaBlocks(const EncoderParams& p, const uint8_t* text, const Co
   std::vector<MbRawCopy> raws;
   std::vector<MbBitCopy> headers;
   bool flipped = false;
+  uint64_t stream_bit = 0;
+  uint32_t first_m = 0;  // the first meta-block of the item
   for (uint32_t m = 0; m < n_mb; ++m) {
     MbDesc& d = descs[m];
-    bits.pos = (bits.pos + 63) & ~(uint64_t)63;
-    const uint64_t stream_bit = bits.pos;
-    // stream header: window bits (EncodeWindowBits, encode.rs:603-625), lgwin 17 .. 24
-    if (p.lgwin == 17) {
-      bits.put(7, 1);
-    } else {
-      bits.put(4, (uint64_t)(((p.lgwin - 17) << 1) | 1));
+    const bool more = items[m].more != 0;
+    if (!items[m].follows) {
+      bits.pos = (bits.pos + 63) & ~(uint64_t)63;
+      stream_bit = bits.pos;
+      first_m = m;
+      items[m].demoted = 0;
+      // stream header: window bits (EncodeWindowBits, encode.rs:603-625), lgwin 17 .. 24
+      if (p.lgwin == 17) {
+        bits.put(7, 1);
+      } else {
+        bits.put(4, (uint64_t)(((p.lgwin - 17) << 1) | 1));
+      }
     }
     const uint32_t bytes = d.end - d.start;
     if (!d.uncompressed) {
       const uint64_t start_bit = bits.pos;
-      const uint64_t end_bit = (start_bit + results[m].header_bits + (body_off[m + 1] - body_off[m]) + 7) & ~(uint64_t)7;
+      uint64_t end_bit = start_bit + results[m].header_bits + (body_off[m + 1] - body_off[m]);
+      if (!more) end_bit = (end_bit + 7) & ~(uint64_t)7;
       if ((uint64_t)bytes + 4 + ((start_bit - stream_bit) >> 3) < ((end_bit - stream_bit) >> 3)) {  // encode.rs:2141-2163
+        // nothing follows an item's last meta-block: stored, and laid out again.  Behind any other one the parse went on from the
+        // wrong distance cache: the item's stream is laid out all the same (every position stays defined) and not used
         d.uncompressed = 1;
         flipped = true;
+        if (more) items[first_m].demoted = 1;
       } else {
         mb_out_bit[m] = start_bit;
         headers.push_back({start_bit, (uint64_t)m * B.header_stride, results[m].header_bits});
@@ -1309,13 +1327,15 @@ void EncodeBatchMetaBlocks(const EncoderParams& p, const uint8_t* text, const Co
       WriteUncompressedHeader(bytes, &bits);
       raws.push_back({bits.pos >> 3, d.start, bytes});
       bits.pos += (uint64_t)bytes * 8;
-      bits.put(1, 1);
-      bits.put(1, 1);
-      bits.jump_to_byte_boundary();
+      if (!more) {  // (a stored meta-block cannot be the last one: the empty last meta-block follows)
+        bits.put(1, 1);
+        bits.put(1, 1);
+        bits.jump_to_byte_boundary();
+      }
     }
     items[m].uncompressed = d.uncompressed;
-    items[m].out_byte = stream_bit >> 3;
-    items[m].out_bytes = (bits.pos - stream_bit) >> 3;
+    items[first_m].out_byte = stream_bit >> 3;
+    items[first_m].out_bytes = (bits.pos - stream_bit) >> 3;
   }
   // ---- emission
   const size_t all_bytes = (size_t)((bits.pos + 7) >> 3);

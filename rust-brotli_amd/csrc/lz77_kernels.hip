@@ -2681,6 +2681,58 @@ void lz77_batch_gather(const BatchParseJob& J, const uint32_t* offsets_dev, Comm
   HIP_CHECK(hipGetLastError());
 }
 
+// ---- items of several blocks (batch_greedy.h): siblings of k_parse_batch / k_batch_gather, so that those instances stay what they were
+template <bool kRows>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_parse_batch_long(BatchParseJob J, BatchLongRecord* records, ChainTables T) {
+  __shared__ ChainScratchT<false, kRows> scratch;
+  __shared__ uint32_t histo[256];
+  const uint32_t table = blockIdx.x;
+  if (table >= J.tables) return;
+  for (;;) {
+    uint32_t mine = 0;
+    if (threadIdx.x == 0) mine = atomicAdd(J.counter, 1u);
+    const uint32_t place = BR_UNIFORM(mine);
+    if (place >= J.n_items) break;
+    const uint32_t index = BR_UNIFORM(J.order[place]);
+    if (index >= J.n_items) break;  // (never: the plan's order is a permutation)
+    br_batch_item_long<kRows>(J, records, T, scratch, histo, index, table);
+  }
+}
+
+void lz77_batch_parse_long(const BatchParseJob& J, BatchLongRecord* records) {
+  if (J.n_items == 0) return;
+  if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
+  const ChainTables T = batch_chain_tables(J);
+  const uint32_t grid = J.tables < J.n_items ? J.tables : J.n_items;
+  if ((1u << J.P.block_bits) <= kRowEntries) {
+    hipLaunchKernelGGL((k_parse_batch_long<true>), dim3(grid), dim3(64), 0, BR_STREAM, J, records, T);
+  } else if (J.P.block_bits <= 7) {
+    hipLaunchKernelGGL((k_parse_batch_long<false>), dim3(grid), dim3(64), 0, BR_STREAM, J, records, T);
+  } else {
+    throw std::runtime_error("brotli_mi355x: the batch chains do not run the 512-deep rings");
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+// one workgroup per (item, meta-block): the meta-block's commands, its trailing insert-only command behind them
+__global__ __launch_bounds__(256) void k_batch_gather_long(BatchParseJob J, const BatchLongRecord* __restrict__ records, const uint32_t* __restrict__ offsets,
+                                                            Command* __restrict__ out) {
+  const uint32_t i = blockIdx.x, m = blockIdx.y;
+  const BatchItem it = J.items[i];
+  if (records[i].overflow || m >= records[i].n_mb || m >= kBatchLongBlocks) return;
+  const BatchLongMetaBlock mb = records[i].mb[m];
+  if ((uint64_t)mb.first_cmd + mb.n_cmds > it.cmd_cap) return;
+  Command* dst = out + offsets[kBatchLongBlocks * i + m];
+  const uint32_t n = mb.n_cmds + (mb.trailing != 0 ? 1u : 0u);
+  for (uint32_t c = threadIdx.x; c < n; c += blockDim.x) dst[c] = br_batch_long_command(J, it, mb, c);
+}
+
+void lz77_batch_gather_long(const BatchParseJob& J, const BatchLongRecord* records, const uint32_t* offsets_dev, Command* out) {
+  if (J.n_items == 0) return;
+  hipLaunchKernelGGL(k_batch_gather_long, dim3(J.n_items, kBatchLongBlocks), dim3(256), 0, BR_STREAM, J, records, offsets_dev, out);
+  HIP_CHECK(hipGetLastError());
+}
+
 __global__ __launch_bounds__(256) void k_live_changed_keys(const uint8_t* __restrict__ prev, const uint8_t* __restrict__ next, uint32_t n,
                                                             const uint16_t* __restrict__ keys, uint8_t* __restrict__ changed_key) {
   const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;

@@ -21,6 +21,11 @@ BrotliEncoderSetCustomDictionary on its library, from 1 and from 4 threads, alte
 baseline is the oracle's dictionary stream; and this build's plain batch call on the same items gives the cost (in time) and the
 gain (in bytes) of the dictionary.
 
+With --long-items (and --qualities 5,8) this build is called through BrotliMi355xCompressBatchEx with
+BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS: the items of two to four input blocks go side by side as well, one chain each.  The parent's
+library is still measured through its plain batch call and its 4-thread loop.  The classes 1024x128KiB and 256x256KiB (--only) are
+all long items.
+
 Every measurement runs in a child process of its own (the table's home is one setting per process, read once; the parent's library
 is another shared object), one after the other, each under its own time limit; the first failure ends the probe.
 
@@ -46,6 +51,9 @@ CLASSES = {
     "4096x16KiB": ("uniform", 4096, 16 << 10),
     "1024x64KiB": ("uniform", 1024, 64 << 10),
     "64xalice29": ("alice", 64, 0),
+    # items of several input blocks (--long-items)
+    "1024x128KiB": ("uniform", 1024, 128 << 10),
+    "256x256KiB": ("uniform", 256, 256 << 10),
     "4096xlog200B-256KiB": ("log", 4096, 0),
     # one table size each (the A/B of the table's home)
     "4096x512B": ("uniform", 4096, 512),
@@ -94,9 +102,11 @@ def bind(path):
     return L
 
 
-def measure_batch(lib_path, items, quality, runs, warmup, dictionary=None):
+def measure_batch(lib_path, items, quality, runs, warmup, dictionary=None, long_items=False):
     L = bind(lib_path)
     L.BrotliMi355xCompressBatch.restype = ctypes.c_int32
+    if long_items:
+        L.BrotliMi355xCompressBatchEx.restype = ctypes.c_int32
     if dictionary is not None:
         L.BrotliMi355xCompressBatchWithDictionary.restype = ctypes.c_int32
     info = (ctypes.c_uint64 * 8)()
@@ -115,7 +125,9 @@ def measure_batch(lib_path, items, quality, runs, warmup, dictionary=None):
         for i in range(n):
             out_sizes[i] = caps[i]
         t = time.perf_counter()
-        if dictionary is None:
+        if long_items:
+            ok = L.BrotliMi355xCompressBatchEx(quality, LGWIN, 0, ctypes.c_uint32(1), ctypes.c_size_t(n), inputs, in_sizes, outputs, out_sizes, None)
+        elif dictionary is None:
             ok = L.BrotliMi355xCompressBatch(quality, LGWIN, 0, ctypes.c_size_t(n), inputs, in_sizes, outputs, out_sizes, None)
         else:
             ok = L.BrotliMi355xCompressBatchWithDictionary(quality, LGWIN, 0, ctypes.c_size_t(len(dictionary)), ctypes.c_char_p(dictionary), ctypes.c_size_t(n),
@@ -222,7 +234,7 @@ def child(args):
             for quality in [int(q) for q in args.qualities.split(",")]:
                 row = {"class": name, "data": data, "quality": quality, "items": len(items), "bytes": sum(map(len, items))}
                 if args.child == "batch":
-                    times, csize, info, failed = measure_batch(args.lib, first if args.first_only else items, quality, args.runs, args.warmup, dictionary)
+                    times, csize, info, failed = measure_batch(args.lib, first if args.first_only else items, quality, args.runs, args.warmup, dictionary, args.long_items)
                     row.update(stats(times), compressed_bytes=csize, batch_info=info, reference_fails_on_items=failed, measured_items=len(first) if args.first_only else len(items))
                 elif args.child == "loop":
                     times, failed = measure_loop(args.lib, first, quality, args.threads, args.runs, 1, dictionary)
@@ -236,7 +248,7 @@ def child(args):
         json.dump(out, f)
 
 
-def run_child(args, what, classes, lib=None, lds=None, threads=1, limit=600, first_only=False, plain=False):
+def run_child(args, what, classes, lib=None, lds=None, threads=1, limit=600, first_only=False, plain=False, long_items=False):
     env = dict(os.environ)
     env.pop("BROTLI_MI355X_BATCH_LDS_BITS", None)
     if lds is not None:
@@ -244,7 +256,7 @@ def run_child(args, what, classes, lib=None, lds=None, threads=1, limit=600, fir
     tmp = os.path.join(os.path.dirname(os.path.abspath(args.out)), ".batch_probe_child.json")
     cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--child", what, "--classes", ",".join(classes), "--lib", lib or args.lib,
            "--threads", str(threads), "--runs", str(args.runs), "--warmup", str(args.warmup), "--loop-items", str(args.loop_items), "--child-out", tmp, "--qualities", args.qualities,
-           "--dictionary", str(args.dictionary)] + (["--first-only"] if first_only else []) + (["--plain"] if plain else [])
+           "--dictionary", str(args.dictionary)] + (["--first-only"] if first_only else []) + (["--plain"] if plain else []) + (["--long-items"] if long_items else [])
     r = subprocess.run(cmd, env=env)
     if r.returncode != 0:
         raise SystemExit("batch_probe: %s (lds=%s, threads=%d) ended with status %d: nothing more is started" % (what, lds, threads, r.returncode))
@@ -324,6 +336,7 @@ def main():
     ap.add_argument("--only", default="", help="comma list of headline classes (default: all)")
     ap.add_argument("--first-only", action="store_true")
     ap.add_argument("--dictionary", type=int, default=0, help="bytes of shared custom dictionary: measures BrotliMi355xCompressBatchWithDictionary")
+    ap.add_argument("--long-items", action="store_true", help="this build through BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS")
     ap.add_argument("--plain", action="store_true", help="(child) the plain call although a dictionary size is given")
     ap.add_argument("--child", default=None)
     ap.add_argument("--classes", default="")
@@ -342,7 +355,9 @@ def main():
         with open(args.out, "w") as f:
             json.dump(doc, f, indent=1)
 
-    headline = [c for c in HEADLINE if not args.only or c in args.only.split(",")]
+    headline = [c for c in (args.only.split(",") if args.only else HEADLINE) if c in CLASSES]
+    if args.long_items:
+        doc["what"] = "BrotliMi355xCompressBatchEx(BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS) vs the parent commit's batch call and 4-thread loop vs the oracle on one CPU core; lgwin 22"
     if args.dictionary:
         return main_dictionary(args, doc, save, [c for c in ("4096x4KiB", "1024x64KiB") if not args.only or c in args.only.split(",")])
     fragment_qualities = set(args.qualities.split(",")) <= {"0", "1"}
@@ -367,7 +382,7 @@ def main():
     if "headline" not in skip:
         rows = {}
         for rnd in range(args.rounds):
-            for row in run_child(args, "batch", headline, limit=900):
+            for row in run_child(args, "batch", headline, limit=900, long_items=args.long_items):
                 this = {k: row[k] for k in ("median_ms", "min_ms", "max_ms", "spread_pct", "runs")}
                 if rnd == 0:
                     rows[key(row)] = {"items": row["items"], "bytes": row["bytes"], "compressed_bytes": row["compressed_bytes"], "batch_info": row["batch_info"], "batch": this}
@@ -394,7 +409,7 @@ def main():
                 continue  # (the parent's batch call above is that loop)
             for row in run_child(args, "loop", headline, lib=os.path.abspath(args.parent_lib), threads=threads, limit=900):
                 scale = row["items"] / row["measured_items"]
-                rows[key(row)]["loop_%dt" % threads] = {"median_ms_scaled": round(row["median_ms"] * scale, 3), "measured_items": row["measured_items"], "spread_pct": row["spread_pct"]}
+                rows[key(row)]["loop_%dt" % threads] = {"median_ms_scaled": round(row["median_ms"] * scale, 3), "min_ms_scaled": round(row["min_ms"] * scale, 3), "measured_items": row["measured_items"], "spread_pct": row["spread_pct"]}
             save()
         for k, v in rows.items():
             b = v["batch"]["median_ms"]
@@ -406,6 +421,8 @@ def main():
                 parent = v["parent_batch_rounds"]
                 v["parent_batch_over_batch"] = round(statistics.median(r["median_ms_scaled"] for r in parent) / statistics.median(r["median_ms"] for r in v["batch_rounds"]), 2)
                 v["every_run_beats_every_parent_run"] = bool(max(r["max_ms"] for r in v["batch_rounds"]) < min(r["min_ms_scaled"] for r in parent))
+            if isinstance(v.get("loop_4t"), dict) and "min_ms_scaled" in v["loop_4t"]:
+                v["every_run_beats_every_loop_4t_run"] = bool(max(r["max_ms"] for r in v["batch_rounds"]) < v["loop_4t"]["min_ms_scaled"])
         save()
     print(json.dumps(doc, indent=1))
 
