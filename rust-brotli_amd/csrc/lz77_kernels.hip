@@ -37,40 +37,83 @@ void hip_check(hipError_t e, const char* what) {
 // dict_items (optional, candidate rows with the static dictionary on): for every position the two hash items
 // SearchInStaticDictionary would probe there (mod.rs:1942-1988: kStaticDictionaryHash[2 * hash14(first four bytes) + i]), low
 // half = probe 0.  A chain refills its window of them with one coalesced load instead of text -> hash -> table.
+// Sort tile: elements per workgroup of the key sort below.  k_compute_keys walks the text tile by tile as well, because it counts
+// the low key byte of every tile on the way (`hist`, optional: the [digit][tile] histogram of the sort's first pass).
+static constexpr uint32_t kSortTile = 4096;
+
 __global__ __launch_bounds__(256) void k_compute_keys(const uint8_t* __restrict__ text, uint16_t* __restrict__ keys,
                                                       uint32_t n, uint32_t valid_n, uint32_t kind, uint32_t bucket_bits,
                                                       uint64_t hash_mask, uint32_t* __restrict__ run_samples,
-                                                      const uint16_t* __restrict__ dict_hash, uint32_t* __restrict__ dict_items) {
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t stride = gridDim.x * blockDim.x;
-  for (; i < n; i += stride) {
-    if (dict_items != nullptr) {  // (the text is padded by 64 zero bytes)
-      const uint32_t h = ((br_load32(text + i) * 0x1e35a7bdu) >> (32 - 14)) << 1;
-      dict_items[i] = (uint32_t)dict_hash[h] | ((uint32_t)dict_hash[h + 1] << 16);
+                                                      const uint16_t* __restrict__ dict_hash, uint32_t* __restrict__ dict_items,
+                                                      uint32_t num_tiles, uint32_t* __restrict__ hist) {
+  __shared__ uint32_t h[256];
+  for (uint32_t tile = blockIdx.x; tile < num_tiles; tile += gridDim.x) {
+    const uint32_t tile_base = tile * kSortTile;
+    const uint32_t tile_n = n - tile_base < kSortTile ? n - tile_base : kSortTile;
+    if (hist != nullptr) {
+      h[threadIdx.x] = 0;
+      __syncthreads();
     }
-    uint32_t key = 0xffffu;
-    if (i < valid_n) {
-      // sample (every 64th position): does a run of one byte start here?  Enough of those switch on the run table.
-      if ((i & 63u) == 0 && i + 16 <= n) {
-        const uint64_t v = br_load64(text + i);
-        // (the count only matters up to the threshold the host compares it with: no need to hammer one address)
-        if (v == (v & 0xffull) * 0x0101010101010101ull && br_load64(text + i + 8) == v && *(volatile uint32_t*)run_samples < 4096u)
-          atomicAdd(run_samples, 1u);
+#pragma unroll 4
+    for (uint32_t e = threadIdx.x; e < tile_n; e += 256) {
+      const uint32_t i = tile_base + e;
+      if (dict_items != nullptr) {  // (the text is padded by 64 zero bytes)
+        const uint32_t dh = ((br_load32(text + i) * 0x1e35a7bdu) >> (32 - 14)) << 1;
+        dict_items[i] = (uint32_t)dict_hash[dh] | ((uint32_t)dict_hash[dh + 1] << 16);
       }
-      if (kind == 6) {
-        const uint64_t v = (br_load64(text + i) & hash_mask) * 0x1fe35a7bd3579bd3ull;
-        key = (uint32_t)(v >> (64 - bucket_bits));
-      } else {
-        const uint32_t v = br_load32(text + i) * 0x1e35a7bdu;
-        key = v >> (32 - bucket_bits);
+      uint32_t key = 0xffffu;
+      if (i < valid_n) {
+        // sample (every 64th position): does a run of one byte start here?  Enough of those switch on the run table.
+        if ((i & 63u) == 0 && i + 16 <= n) {
+          const uint64_t v = br_load64(text + i);
+          // (the count only matters up to the threshold the host compares it with: no need to hammer one address)
+          if (v == (v & 0xffull) * 0x0101010101010101ull && br_load64(text + i + 8) == v && *(volatile uint32_t*)run_samples < 4096u)
+            atomicAdd(run_samples, 1u);
+        }
+        if (kind == 6) {
+          const uint64_t v = (br_load64(text + i) & hash_mask) * 0x1fe35a7bd3579bd3ull;
+          key = (uint32_t)(v >> (64 - bucket_bits));
+        } else {
+          const uint32_t v = br_load32(text + i) * 0x1e35a7bdu;
+          key = v >> (32 - bucket_bits);
+        }
       }
+      keys[i] = (uint16_t)key;
+      if (hist != nullptr) atomicAdd(&h[key & 255u], 1u);
     }
-    keys[i] = (uint16_t)key;
+    if (hist != nullptr) {
+      __syncthreads();
+      hist[threadIdx.x * num_tiles + tile] = h[threadIdx.x];  // (every thread zeroes its own counter again, in front of the next barrier)
+    }
   }
   if (dict_items != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {  // (positions behind the end are looked up as position n)
-    const uint32_t h = ((br_load32(text + n) * 0x1e35a7bdu) >> (32 - 14)) << 1;
-    dict_items[n] = (uint32_t)dict_hash[h] | ((uint32_t)dict_hash[h + 1] << 16);
+    const uint32_t dh = ((br_load32(text + n) * 0x1e35a7bdu) >> (32 - 14)) << 1;
+    dict_items[n] = (uint32_t)dict_hash[dh] | ((uint32_t)dict_hash[dh + 1] << 16);
   }
+}
+
+// The sort's scratch inside B.sort_tmp
+struct SortScratch {
+  uint16_t* keys_tmp;
+  uint32_t* vals_tmp;
+  uint16_t* tags_tmp;
+  uint32_t* hist;     // [256][tiles]
+  uint32_t* scratch;  // of the scans
+};
+static SortScratch sort_scratch(const Lz77Buffers& B, uint32_t n) {
+  const uint32_t tiles = (n + kSortTile - 1) / kSortTile;
+  SortScratch s;
+  uint8_t* tmp = (uint8_t*)B.sort_tmp;
+  s.keys_tmp = (uint16_t*)tmp;
+  tmp += ((size_t)n * 2 + 255) & ~(size_t)255;
+  s.vals_tmp = (uint32_t*)tmp;
+  tmp += ((size_t)n * 4 + 255) & ~(size_t)255;
+  s.tags_tmp = (uint16_t*)tmp;
+  tmp += ((size_t)n * 2 + 255) & ~(size_t)255;
+  s.hist = (uint32_t*)tmp;
+  tmp += (size_t)tiles * 256 * 4;
+  s.scratch = (uint32_t*)tmp;
+  return s;
 }
 
 void lz77_compute_keys(const Lz77Params& P, const Lz77Buffers& B) {
@@ -78,11 +121,13 @@ void lz77_compute_keys(const Lz77Params& P, const Lz77Buffers& B) {
   const uint32_t valid_n = n >= P.htl ? n - P.htl + 1 : 0;
   const uint64_t hash_mask = P.hasher_kind == 6 ? (0xffffffffffffffffull >> (64 - 8 * P.hash_len)) : 0;
   if (n == 0) return;
-  uint32_t blocks = (n + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
+  const uint32_t tiles = (n + kSortTile - 1) / kSortTile;
+  // With the sort's scratch at hand (the stage calls: lz77_sort_by_key comes next) the first pass' histogram is counted here,
+  // where the digit is in a register; callers that only want the keys (batch calls) bring no scratch.
+  uint32_t* hist = (B.sort_tmp != nullptr && B.sort_tmp_bytes >= lz77_sort_tmp_bytes(n)) ? sort_scratch(B, n).hist : nullptr;
   dev_memset(B.changed_count + 8, 0, 4);
-  hipLaunchKernelGGL(k_compute_keys, dim3(blocks), dim3(256), 0, BR_STREAM, B.text, B.keys, n, valid_n, P.hasher_kind, P.bucket_bits,
-                     hash_mask, B.changed_count + 8, dev_tables().dict_hash, B.dict_items);
+  hipLaunchKernelGGL(k_compute_keys, dim3(tiles < 8192 ? tiles : 8192), dim3(256), 0, BR_STREAM, B.text, B.keys, n, valid_n, P.hasher_kind,
+                     P.bucket_bits, hash_mask, B.changed_count + 8, dev_tables().dict_hash, B.dict_items, tiles, hist);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -123,8 +168,7 @@ void lz77_init_flags(const Lz77Params& P, const Lz77Buffers& B, uint32_t first_b
 }
 
 // ------------------------------------------------------------------------------------------ radix sort
-static constexpr uint32_t kSortTile = 4096;  // elements per workgroup (16 rounds of 256)
-
+// Pass 1 counts its digits in k_compute_keys; this is the histogram of pass 2.
 __global__ __launch_bounds__(256) void k_radix_hist(const uint16_t* __restrict__ keys, uint32_t n, uint32_t shift,
                                                      uint32_t num_tiles, uint32_t* __restrict__ hist) {
   __shared__ uint32_t h[256];
@@ -142,17 +186,25 @@ __global__ __launch_bounds__(256) void k_radix_hist(const uint16_t* __restrict__
 // stable scatter: elements keep their input order inside each digit.  The tile is first reordered by digit in LDS, then
 // written out run by run, so that the lanes of a wave write neighbouring addresses (a direct scatter writes one isolated
 // 2- and 4-byte element per digit and round).
-// `tags`: optional third column (16-bit tag of every position, br_tag16): computed from the text in the first pass
-// (tags_in == nullptr, text != nullptr), carried along in the second.
-__global__ __launch_bounds__(256) void k_radix_scatter(const uint16_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
+// The whole tile is loaded into registers before anything is ranked (16 elements per thread, every load in flight at once).
+// Wave w owns the elements [1024 w, 1024 (w + 1)) of the tile, in 16 rounds of 64: it ranks them against counters of its
+// own, without a workgroup barrier; the four waves' counts are put together once, behind all the rounds.
+// `tags`: optional third column (16-bit tag of every position, br_tag16).
+// kFirstPass: the value of element i is i itself and its tag is computed from the text; otherwise both are carried along
+// from vals_in / tags_in, the output is the finished (key, position) order, and key_first / key_last (optional) receive
+// the slots of every key -- min / max over the run boundaries of all tiles; key_first starts at 0xffffffff and key_last
+// at 0 (k_key_first_absent tidies up the keys without slots).
+// (39 KB of LDS: four workgroups per CU, i.e. four waves per SIMD and 128 registers each)
+template <bool kFirstPass>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_radix_scatter(const uint16_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
                                                         uint16_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out, uint32_t n,
                                                         uint32_t shift, uint32_t num_tiles, const uint32_t* __restrict__ offsets,
                                                         const uint8_t* __restrict__ text, const uint16_t* __restrict__ tags_in,
-                                                        uint16_t* __restrict__ tags_out) {
-  __shared__ uint32_t gbase[256];   // where digit d of this tile goes in the output
-  __shared__ uint32_t lstart[256];  // where digit d starts inside the reordered tile
-  __shared__ uint32_t run[256];     // next free local slot of digit d
-  __shared__ uint32_t wcount[4][256];
+                                                        uint16_t* __restrict__ tags_out, uint32_t* __restrict__ key_first,
+                                                        uint32_t* __restrict__ key_last) {
+  __shared__ uint32_t gbase[256];       // where digit d of this tile goes in the output
+  __shared__ uint32_t lstart[257];      // where digit d starts inside the reordered tile ([256]: its end)
+  __shared__ uint32_t wbase[4][256];    // per wave: its count of digit d while ranking, then where its first such element goes
   __shared__ uint32_t wave_total[4];
   __shared__ uint16_t skey[kSortTile];
   __shared__ uint32_t sval[kSortTile];
@@ -160,39 +212,58 @@ __global__ __launch_bounds__(256) void k_radix_scatter(const uint16_t* __restric
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const uint32_t tile_base = blockIdx.x * kSortTile;
   const uint32_t tile_n = n - tile_base < kSortTile ? n - tile_base : kSortTile;
+  // digit counts of this tile out of the scanned histogram ([digit][tile] order)
+  const uint32_t hidx = (uint32_t)tid * num_tiles + blockIdx.x;
+  const uint32_t here = offsets[hidx];
+  const uint32_t next = hidx + 1 < 256u * num_tiles ? offsets[hidx + 1] : n;
+  uint32_t key[16], val[16], tag[16];  // (key: the rank inside the wave's digit group joins it in the high half)
+  const uint32_t e0 = (uint32_t)w * 1024u + (uint32_t)lane;
+  // (straight-line loads: an element behind the end of a ragged last tile reads the tile's last one and is never ranked)
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const uint32_t e = e0 + (uint32_t)r * 64u;
+    key[r] = keys_in[tile_base + (e < tile_n ? e : tile_n - 1)];
+  }
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const uint32_t e = e0 + (uint32_t)r * 64u;
+    const uint32_t i = tile_base + (e < tile_n ? e : tile_n - 1);
+    val[r] = kFirstPass ? i : vals_in[i];
+  }
+  if (tags_out != nullptr) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const uint32_t e = e0 + (uint32_t)r * 64u;
+      const uint32_t i = tile_base + (e < tile_n ? e : tile_n - 1);
+      tag[r] = kFirstPass ? br_tag16(br_load32(text + i)) : (uint32_t)tags_in[i];
+    }
+  }
+  const uint32_t count = next - here;
+  uint32_t start;
   {
-    // digit counts of this tile out of the scanned histogram ([digit][tile] order), then their exclusive scan
-    const uint32_t idx = (uint32_t)tid * num_tiles + blockIdx.x;
-    const uint32_t here = offsets[idx];
-    const uint32_t next = idx + 1 < 256u * num_tiles ? offsets[idx + 1] : n;
-    const uint32_t count = next - here;
+    // exclusive scan of the digit counts
     gbase[tid] = here;
     uint32_t incl = count;
-    for (uint32_t off = 1; off < 64; off <<= 1) {
-      const uint32_t up = (uint32_t)__shfl_up((int)incl, off, 64);
-      if ((uint32_t)lane >= off) incl += up;
+    for (uint32_t o = 1; o < 64; o <<= 1) {
+      const uint32_t up = (uint32_t)__shfl_up((int)incl, o, 64);
+      if ((uint32_t)lane >= o) incl += up;
     }
     if (lane == 63) wave_total[w] = incl;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) wbase[w][lane * 4 + j] = 0;
     __syncthreads();
     uint32_t before = 0;
     for (int i = 0; i < w; ++i) before += wave_total[i];
-    lstart[tid] = before + incl - count;
-    run[tid] = before + incl - count;
+    start = before + incl - count;
+    lstart[tid] = start;
+    if (tid == 255) lstart[256] = start + count;
   }
-  __syncthreads();
-  for (uint32_t r = 0; r < 16; ++r) {
-    const uint32_t i = tile_base + r * 256 + tid;
-    const bool valid = i < n;
-    uint32_t key = 0, val = 0, d = 0, tag = 0;
-    if (valid) {
-      key = keys_in[i];
-      val = vals_in ? vals_in[i] : i;
-      d = (key >> shift) & 255u;
-      if (tags_out) tag = tags_in ? tags_in[i] : br_tag16(br_load32(text + val));
-    }
+  // ranks inside this wave's quarter of the tile: wave-private counters, the wave's LDS accesses stay in program order
+  volatile uint32_t* mine = wbase[w];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) wcount[w][lane * 4 + j] = 0;
-    __syncthreads();
+  for (int r = 0; r < 16; ++r) {
+    const bool valid = e0 + (uint32_t)r * 64u < tile_n;
+    const uint32_t d = (key[r] >> shift) & 255u;
     // lanes of this wavefront that hold the same digit
     unsigned long long peers = __ballot(valid);
 #pragma unroll
@@ -202,27 +273,53 @@ __global__ __launch_bounds__(256) void k_radix_scatter(const uint16_t* __restric
       peers &= one ? b : ~b;
     }
     const uint32_t rank_in_wave = __popcll(peers & ((1ull << lane) - 1ull));
-    if (valid && rank_in_wave == 0) wcount[w][d] = __popcll(peers);
-    __syncthreads();
-    if (valid) {
-      uint32_t at = run[d] + rank_in_wave;
-      for (int i2 = 0; i2 < w; ++i2) at += wcount[i2][d];
-      skey[at] = (uint16_t)key;
-      sval[at] = val;
-      if (tags_out) stagv[at] = (uint16_t)tag;
+    const uint32_t seen = mine[d];
+    key[r] |= (seen + rank_in_wave) << 16;
+    __builtin_amdgcn_wave_barrier();
+    if (valid && rank_in_wave == 0) mine[d] = seen + (uint32_t)__popcll(peers);
+    __builtin_amdgcn_wave_barrier();
+  }
+  __syncthreads();
+  {
+    // counts of the four waves -> where each wave's first element of digit `tid` goes
+    const uint32_t c0 = wbase[0][tid], c1 = wbase[1][tid], c2 = wbase[2][tid];
+    wbase[0][tid] = start;
+    wbase[1][tid] = start + c0;
+    wbase[2][tid] = start + c0 + c1;
+    wbase[3][tid] = start + c0 + c1 + c2;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    if (e0 + (uint32_t)r * 64u < tile_n) {
+      const uint32_t at = wbase[w][(key[r] >> shift) & 255u] + (key[r] >> 16);
+      skey[at] = (uint16_t)key[r];
+      sval[at] = val[r];
+      if (tags_out != nullptr) stagv[at] = (uint16_t)tag[r];
     }
-    __syncthreads();
-    run[tid] += wcount[0][tid] + wcount[1][tid] + wcount[2][tid] + wcount[3][tid];
-    __syncthreads();
   }
+  __syncthreads();
   for (uint32_t at = tid; at < tile_n; at += 256) {
-    const uint32_t key = skey[at];
-    const uint32_t d = (key >> shift) & 255u;
-    const uint32_t dst = gbase[d] + (at - lstart[d]);
-    keys_out[dst] = (uint16_t)key;
+    const uint32_t k = skey[at];
+    const uint32_t d = (k >> shift) & 255u;
+    const uint32_t ls = lstart[d];
+    const uint32_t dst = gbase[d] + (at - ls);
+    keys_out[dst] = (uint16_t)k;
     vals_out[dst] = sval[at];
-    if (tags_out) tags_out[dst] = stagv[at];
+    if (tags_out != nullptr) tags_out[dst] = stagv[at];
+    if (!kFirstPass && key_first != nullptr) {
+      // a run of this tile lies in the output as it lies here, between the same digit's runs of the tiles around it: a
+      // neighbour inside the run decides a boundary, at the run's ends the other tiles have their say (min / max)
+      if (at == ls || skey[at - 1] != k) atomicMin(&key_first[k], dst);
+      if (at + 1 == lstart[d + 1] || skey[at + 1] != k) atomicMax(&key_last[k], dst + 1);
+    }
   }
+}
+
+// keys without slots: 0 / 0
+__global__ __launch_bounds__(256) void k_key_first_absent(uint32_t* __restrict__ key_first) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < 65537 && key_first[k] == 0xffffffffu) key_first[k] = 0;
 }
 
 size_t lz77_sort_tmp_bytes(uint32_t total_bytes) {
@@ -233,34 +330,28 @@ size_t lz77_sort_tmp_bytes(uint32_t total_bytes) {
   return n * 10 + 2048 + tiles * 256 * 4 + (tiles * 256 / kScanTile + 1024) * 8 + (n / kScanTile + 1024) * 8 + 4096;
 }
 
-void lz77_key_ranges(const Lz77Params& P, const Lz77Buffers& B);
-
+// Needs lz77_compute_keys(P, B) in front, with nothing else using B.sort_tmp in between: the first pass' histogram comes from there.
 void lz77_sort_by_key(const Lz77Params& P, const Lz77Buffers& B) {
   const uint32_t n = P.total_bytes;
   if (n == 0) return;
+  if (B.sort_tmp == nullptr || B.sort_tmp_bytes < lz77_sort_tmp_bytes(n)) throw std::runtime_error("brotli_mi355x: key sort without its scratch");
   const uint32_t tiles = (n + kSortTile - 1) / kSortTile;
-  uint8_t* tmp = (uint8_t*)B.sort_tmp;
-  uint16_t* keys_tmp = (uint16_t*)tmp;
-  tmp += ((size_t)n * 2 + 255) & ~(size_t)255;
-  uint32_t* vals_tmp = (uint32_t*)tmp;
-  tmp += ((size_t)n * 4 + 255) & ~(size_t)255;
-  uint16_t* tags_tmp = (uint16_t*)tmp;
-  tmp += ((size_t)n * 2 + 255) & ~(size_t)255;
-  uint32_t* hist = (uint32_t*)tmp;
-  tmp += (size_t)tiles * 256 * 4;
-  uint32_t* scratch = (uint32_t*)tmp;
+  const SortScratch s = sort_scratch(B, n);
+  // key_first / key_last come out of the second pass (min / max of slots)
+  HIP_CHECK(hipMemsetAsync(B.key_first, 0xff, 65537 * 4, BR_STREAM));
+  dev_memset(B.key_last, 0, 65537 * 4);
   // pass 1: low 8 bits, keys -> tmp
-  hipLaunchKernelGGL(k_radix_hist, dim3(tiles), dim3(256), 0, BR_STREAM, B.keys, n, 0u, tiles, hist);
-  exclusive_scan_u32(hist, tiles * 256, scratch);
-  hipLaunchKernelGGL(k_radix_scatter, dim3(tiles), dim3(256), 0, BR_STREAM, B.keys, (const uint32_t*)nullptr, keys_tmp, vals_tmp, n, 0u, tiles,
-                     hist, (const uint8_t*)B.text, (const uint16_t*)nullptr, B.stag ? tags_tmp : (uint16_t*)nullptr);
+  exclusive_scan_u32(s.hist, tiles * 256, s.scratch);
+  hipLaunchKernelGGL(k_radix_scatter<true>, dim3(tiles), dim3(256), 0, BR_STREAM, B.keys, (const uint32_t*)nullptr, s.keys_tmp, s.vals_tmp, n, 0u,
+                     tiles, s.hist, (const uint8_t*)B.text, (const uint16_t*)nullptr, B.stag ? s.tags_tmp : (uint16_t*)nullptr,
+                     (uint32_t*)nullptr, (uint32_t*)nullptr);
   // pass 2: high 8 bits, tmp -> by_key / sorted_keys
-  hipLaunchKernelGGL(k_radix_hist, dim3(tiles), dim3(256), 0, BR_STREAM, keys_tmp, n, 8u, tiles, hist);
-  exclusive_scan_u32(hist, tiles * 256, scratch);
-  hipLaunchKernelGGL(k_radix_scatter, dim3(tiles), dim3(256), 0, BR_STREAM, keys_tmp, vals_tmp, B.sorted_keys, B.by_key, n, 8u, tiles, hist,
-                     (const uint8_t*)B.text, (const uint16_t*)tags_tmp, B.stag);
+  hipLaunchKernelGGL(k_radix_hist, dim3(tiles), dim3(256), 0, BR_STREAM, s.keys_tmp, n, 8u, tiles, s.hist);
+  exclusive_scan_u32(s.hist, tiles * 256, s.scratch);
+  hipLaunchKernelGGL(k_radix_scatter<false>, dim3(tiles), dim3(256), 0, BR_STREAM, s.keys_tmp, s.vals_tmp, B.sorted_keys, B.by_key, n, 8u, tiles,
+                     s.hist, (const uint8_t*)B.text, (const uint16_t*)s.tags_tmp, B.stag, B.key_first, B.key_last);
+  hipLaunchKernelGGL(k_key_first_absent, dim3((65537 + 255) / 256), dim3(256), 0, BR_STREAM, B.key_first);
   HIP_CHECK(hipGetLastError());
-  lz77_key_ranges(P, B);
 }
 
 // ------------------------------------------------------------------------------------------ rank
@@ -269,15 +360,6 @@ void lz77_sort_by_key(const Lz77Params& P, const Lz77Buffers& B) {
 // to the front of its slots in `sorted`, and info[p] = {slot one past ... i.e. key_first + local rank, local rank}
 // where local rank = number of stored same-key positions before p.  Because a key's slots do not depend on any
 // other key, a handful of flag changes can be applied key by key (k_rerank_keys) without touching the rest.
-__global__ __launch_bounds__(256) void k_key_ranges(const uint16_t* __restrict__ sorted_keys, uint32_t n, uint32_t* __restrict__ key_first,
-                                                     uint32_t* __restrict__ key_last) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint16_t k = sorted_keys[i];
-  if (i == 0 || sorted_keys[i - 1] != k) key_first[k] = i;
-  if (i + 1 == n || sorted_keys[i + 1] != k) key_last[k] = i + 1;
-}
-
 // pass A: gather the stored bits into (key,pos) order (one byte each) and sum them per tile.
 // `initial`: the flags are still the first guess of lz77_init_flags, which is 1 everywhere except next to the block
 // ends and in front of the first block -- only positions there are fetched (a random 1-byte gather costs a 64-byte line).
@@ -406,15 +488,6 @@ __global__ __launch_bounds__(256) void k_rank_apply(const uint32_t* __restrict__
       g += f[j];
     }
   }
-}
-
-void lz77_key_ranges(const Lz77Params& P, const Lz77Buffers& B) {
-  const uint32_t n = P.total_bytes;
-  dev_memset(B.key_first, 0, 65537 * 4);
-  dev_memset(B.key_last, 0, 65537 * 4);
-  if (n == 0) return;
-  hipLaunchKernelGGL(k_key_ranges, dim3((n + 255) / 256), dim3(256), 0, BR_STREAM, B.sorted_keys, n, B.key_first, B.key_last);
-  HIP_CHECK(hipGetLastError());
 }
 
 void lz77_rank_flags(const Lz77Params& P, const Lz77Buffers& B, int which, int rbuf, const RankInitialHint* initial) {

@@ -2669,6 +2669,29 @@ void Lz77Stage::SelfTestSort() {
         throw std::runtime_error("selftest: sort not stable at slot " + std::to_string(i));
     }
   }
+  // the tag column: br_tag16 (lz77_chain.h) of the four bytes at every slot's position
+  if (B_.stag) {
+    std::vector<uint16_t> stag(n);
+    std::vector<uint8_t> text((size_t)n + 64, 0);
+    dev_d2h(stag.data(), B_.stag, (size_t)n * 2);
+    dev_d2h(text.data(), B_.text, (size_t)n + 64);
+    for (uint32_t i = 0; i < n; ++i) {
+      uint32_t v;
+      memcpy(&v, text.data() + by_key[i], 4);
+      if (stag[i] != (uint16_t)((v * 0x9E3779B1u) >> 16)) throw std::runtime_error("selftest: stag mismatch at slot " + std::to_string(i));
+    }
+  }
+  // the slots of every key (they come out of the sort's second pass): 0 / 0 for a key without slots
+  std::vector<uint32_t> first(65537), last(65537), want_first(65537, 0), want_last(65537, 0);
+  dev_d2h(first.data(), B_.key_first, 65537 * 4);
+  dev_d2h(last.data(), B_.key_last, 65537 * 4);
+  for (uint32_t i = 0; i < n; ++i) {
+    if (i == 0 || skeys[i - 1] != skeys[i]) want_first[skeys[i]] = i;
+    if (i + 1 == n || skeys[i + 1] != skeys[i]) want_last[skeys[i]] = i + 1;
+  }
+  for (uint32_t k = 0; k < 65537; ++k)
+    if (first[k] != want_first[k] || last[k] != want_last[k])
+      throw std::runtime_error("selftest: key_first / key_last mismatch for key " + std::to_string(k));
 }
 
 void Lz77Stage::SelfTestRank(int which, int rbuf) {
