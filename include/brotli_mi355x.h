@@ -202,7 +202,8 @@ BROTLI_BOOL BrotliMi355xCompressDevice(int quality, int lgwin, BrotliEncoderMode
      qualities 0 and 1: every item; the fragments of all items share one upload and one download per group of up to 4096;
      qualities 5 .. 8:  the items of at most one input block (65 536 bytes) at lgwin 17 .. 24 -- one parse chain and one
                         meta-block each, thousands of them in flight, one upload and one download per group of up to 4096 items.
-   Every other item -- qualities 2 .. 4 and 9 .. 11, lgwin <= 16 or > 24, items longer than one input block -- is accepted and
+   Every other item -- qualities 2 .. 4 (but see BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS of BrotliMi355xCompressBatchEx) and
+   9 .. 11, lgwin <= 16 or > 24, items longer than one input block -- is accepted and
    runs by itself through the one-shot path on the calling thread, in the same call and in the caller's order: the same bytes,
    no gain in speed.  Both kinds may be mixed in one call; BrotliMi355xLastBatchInfo tells how a call was taken.
    Environment (read once per process): BROTLI_MI355X_BATCH_GROUP_ITEMS / BROTLI_MI355X_BATCH_GROUP_BYTES bound a group of
@@ -247,8 +248,20 @@ int32_t BrotliMi355xCompressBatchWithDictionary(int quality, int lgwin, BrotliEn
    When to set it: a chain is one wavefront bound by its own dependent loads, so a long item takes as long as a lone chain needs
    for it however many run beside it; the one-shot path is faster per item and serial.  The route pays with many long items in a
    call, or with data on which the one-shot path needs many rounds (see INTEGRATION.md for measured figures); with a few long
-   items of text it loses.  Not combined with a shared dictionary. */
+   items of text it loses.  Not combined with a shared dictionary.
+   BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS: item i still gets exactly what BrotliEncoderCompress gives.  In addition to the items
+   the plain call takes side by side, an item of at most one input block at quality 2, 3 or 4 and lgwin 10 .. 24 -- that is
+   1 <= input_sizes[i] <= 16 384 at quality 2 / 3 and <= 65 536 at quality 4 -- runs on the device as ONE chain on a private
+   BasicHasher table (H2 / H3 / H4; 256 KiB, at quality 4 512 KiB), side by side with the other such items of the call (groups of
+   their own, under the same environment limits; 4096 tables by default), and leaves one meta-block.  Every other item goes as in
+   the plain call: longer items at these qualities still run one by one, with BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS set as well.
+   The bit changes nothing at qualities 0, 1 and 5 .. 11.  Such items count in info[1], their groups in info[4]; info[6] and
+   info[7] stay 0 for them.  When to set it: with hundreds of small items of one kind in a call (dynamic responses at the levels
+   servers use for them); a chain is one wavefront bound by its own dependent loads, so a call of a few items is no faster
+   than the one-by-one path (see INTEGRATION.md for measured figures).  Not combined with a shared dictionary.
+   The two bits may be combined.  The value 2 is reserved: it names no route and fails the call like any unknown bit. */
 #define BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS 1u
+#define BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS 4u /* (2u is reserved and stays an unknown route) */
 int32_t BrotliMi355xCompressBatchEx(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t count,
                                     const uint8_t* const* inputs, const size_t* input_sizes, uint8_t* const* outputs,
                                     size_t* output_sizes /* in: capacity, out: size */, int32_t* item_results /* may be NULL */);
@@ -258,7 +271,8 @@ int32_t BrotliMi355xCompressBatchEx(int quality, int lgwin, BrotliEncoderMode mo
    groups (those of long items included), [5] dictionary bytes in use after the reference's truncation (0 for the plain call),
    [6] items that began side by side and were redone one by one (counted in [2], not in [1]), [7] of the items counted in [1],
    those longer than one input block; [6] and [7] are zero unless BrotliMi355xCompressBatchEx was called with
-   BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS.  After a call that failed as a whole only info[0] is set. */
+   BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS (the items of BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS count in [1] and [4] only).  After a
+   call that failed as a whole only info[0] is set. */
 void BrotliMi355xLastBatchInfo(uint64_t info[8]);
 /* Human-readable description of the device backing the library ("hip:gfx950 (...)"). */
 const char* BrotliMi355xDeviceName(void);

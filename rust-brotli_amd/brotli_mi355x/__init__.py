@@ -176,8 +176,9 @@ class Library(object):
         return ctypes.string_at(out, n.value)
 
     BATCH_ROUTE_LONG_ITEMS = 1  # BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS
+    BATCH_ROUTE_QUICK_ITEMS = 4  # BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS (2 is reserved)
 
-    def compress_batch(self, items, quality=0, lgwin=22, mode=0, dictionary=None, long_items=False):
+    def compress_batch(self, items, quality=0, lgwin=22, mode=0, dictionary=None, long_items=False, quick_items=False):
         """BrotliMi355xCompressBatch: every item becomes a stream of its own, the same bytes as compress(item, quality, lgwin,
         mode), in one call.  Side by side on the device (the call for many small payloads): every item at qualities 0 and 1, and
         at qualities 5 to 8 the items of at most 65 536 bytes at lgwin 17 to 24.  Everything else runs item by item in the same
@@ -189,9 +190,18 @@ class Library(object):
 
         long_items=True: BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS -- at qualities 5 to 8 and lgwin 17
         to 24 the items of 65 537 to 262 144 bytes run side by side as well, one chain each (the same bytes).  It pays with many
-        such items in a call; a few dozen long items of text are faster without it.  Not combined with a dictionary."""
+        such items in a call; a few dozen long items of text are faster without it.  Not combined with a dictionary.
+
+        quick_items=True: BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS -- at qualities 2 to 4 and lgwin 10
+        to 24 the items of at most one input block (16 384 bytes at quality 2 and 3, 65 536 at quality 4) run side by side, one
+        chain on a private hash table each (the same bytes).  Without it these qualities run item by item; longer items at these
+        qualities still do.  It pays with hundreds of small items in a call.  May be combined with long_items, not with a
+        dictionary."""
         if long_items and dictionary is not None:
             raise ValueError("long_items and dictionary cannot be combined: BrotliMi355xCompressBatchWithDictionary has no routes")
+        if quick_items and dictionary is not None:
+            raise ValueError("quick_items and dictionary cannot be combined: BrotliMi355xCompressBatchWithDictionary has no routes")
+        routes = (self.BATCH_ROUTE_LONG_ITEMS if long_items else 0) | (self.BATCH_ROUTE_QUICK_ITEMS if quick_items else 0)
         items = [bytes(x) for x in items]
         count = len(items)
         if count == 0:
@@ -211,9 +221,9 @@ class Library(object):
         outputs = (c_void_p * count)(*[base + s for s in starts])
         out_sizes = (c_size_t * count)(*caps)
         results = (c_int32 * count)()
-        if long_items:
+        if routes:
             name = "BrotliMi355xCompressBatchEx"
-            ok = self.lib.BrotliMi355xCompressBatchEx(quality, lgwin, mode, self.BATCH_ROUTE_LONG_ITEMS, count, inputs, in_sizes, outputs, out_sizes, results)
+            ok = self.lib.BrotliMi355xCompressBatchEx(quality, lgwin, mode, routes, count, inputs, in_sizes, outputs, out_sizes, results)
         elif dictionary is None:
             name = "BrotliMi355xCompressBatch"
             ok = self.lib.BrotliMi355xCompressBatch(quality, lgwin, mode, count, inputs, in_sizes, outputs, out_sizes, results)
@@ -232,7 +242,7 @@ class Library(object):
         """BrotliMi355xLastBatchInfo: the last compress_batch call of this thread as a list of 8 integers -- [0] items, [1] items
         encoded side by side on the device, [2] items run one by one, [3] items answered without an encoder, [4] device groups, [5] dictionary bytes in use (0 without one),
         [6] items that began side by side and were redone one by one (counted in [2]), [7] of the items in [1], those longer than one
-        input block ([6] and [7]: long_items=True only)."""
+        input block ([6] and [7]: long_items=True only; the items quick_items=True takes side by side count in [1] and [4])."""
         info = (c_uint64 * 8)()
         self.lib.BrotliMi355xLastBatchInfo.restype = None
         self.lib.BrotliMi355xLastBatchInfo.argtypes = [POINTER(c_uint64)]

@@ -9,9 +9,11 @@
 #include <algorithm>
 #include <stdexcept>
 
+#include "batch_quick.h"
 #include "device_api.h"
 #if defined(BROTLI_HOST_EMU)
 #include "batch_greedy_emu.inc"  // the host emulation of lz77_batch_parse / lz77_batch_gather
+#include "batch_quick_emu.inc"   // ... and of lz77_quick_batch_parse
 #endif
 
 namespace brotli_mi355x {
@@ -420,7 +422,146 @@ void CompressLongGroups(const EncoderParams& p, size_t count, const uint8_t* con
   }
 }
 
+// Qualities 2 .. 4 (batch_quick.h): the plan of CompressGroups without the key pass and the flags -- a BasicHasher hashes from
+// the text -- and with a table of quick_table_words per wavefront.
+void CompressQuickGroups(const EncoderParams& p, size_t count, const uint8_t* const* inputs, const size_t* sizes,
+                         std::vector<std::vector<uint8_t>>* streams, uint32_t* groups) {
+  static const size_t group_items = std::max<size_t>(1, EnvSize("BROTLI_MI355X_BATCH_GROUP_ITEMS", 4096));
+  static const size_t group_bytes = std::max<size_t>(1, EnvSize("BROTLI_MI355X_BATCH_GROUP_BYTES", (size_t)64 << 20));
+  static const size_t table_override = EnvSize("BROTLI_MI355X_BATCH_TABLES", 0);
+  streams->assign(count, std::vector<uint8_t>());
+  *groups = 0;
+  if (count == 0) return;
+  QuickJob Q;  // as Lz77Stage::Setup fills it in
+  Q.kind = (uint32_t)p.hasher.type;
+  Q.bucket_bits = Q.kind == 4 ? 17 : 16;
+  Q.sweep = Q.kind == 2 ? 1 : (Q.kind == 3 ? 2 : 4);
+  Q.hash_len = 5;
+  Q.use_dictionary = (p.use_dictionary && (Q.kind == 2 || Q.kind == 4)) ? 1 : 0;
+  // a table is 256 KiB (H2, H3) or 512 KiB (H4): as many as the parse kernel keeps resident, within 8 GiB
+  const size_t table_bytes = (size_t)quick_table_words(Q) * 4;
+  const size_t tables_max = table_override ? table_override : std::max<size_t>(1, std::min<size_t>(4096, ((size_t)8 << 30) / table_bytes));
+  Lz77Params P = ChainParams(p);
+  P.hasher_kind = 6;  // (what Lz77Stage::Setup gives every hasher but H5 and H9; br_quick_block does not look at it)
+  P.htl = 8;  // HashTypeLength of every BasicHasher
+  P.use_dictionary = Q.use_dictionary;
+  P.dict_break = 0;
+
+  PinnedArray<uint8_t> staging;
+  PinnedArray<BatchItem> items;
+  PinnedArray<uint32_t> order, offsets;
+  PinnedArray<BatchRecord> records;
+  size_t first = 0;
+  while (first < count) {
+    size_t last = first, padded = 0, packed = 0;
+    while (last < count && last - first < group_items && (last == first || packed + sizes[last] <= group_bytes)) {
+      padded += Padded((uint32_t)sizes[last]);
+      packed += sizes[last];
+      ++last;
+    }
+    const uint32_t n = (uint32_t)(last - first);
+    ++*groups;
+    // one page-locked buffer, one upload: [padded text | 64 | packed text | 64]
+    const size_t packed_at = padded + 64;
+    const size_t text_bytes = packed_at + packed + 64;
+    staging.resize_discard(text_bytes);
+    memset(staging.data(), 0, text_bytes);
+    items.resize_discard(n);
+    order.resize_discard(n);
+    std::vector<BatchStreamItem> mbs(n);
+    {
+      uint32_t off = 0, start = 0, cmd_base = 0;
+      for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t bytes = (uint32_t)sizes[first + i];
+        memcpy(staging.data() + off, inputs[first + i], bytes);
+        memcpy(staging.data() + packed_at + start, inputs[first + i], bytes);
+        items[i] = BatchItem{off, bytes, cmd_base, bytes / 2 + 8};
+        mbs[i].start = start;
+        mbs[i].bytes = bytes;
+        off += Padded(bytes);
+        start += bytes;
+        cmd_base += bytes / 2 + 8;
+        order[i] = i;
+      }
+      // largest first: the large items of a group run as long as a lone wavefront takes, the small ones fill in behind them
+      std::stable_sort(order.data(), order.data() + n, [&](uint32_t a, uint32_t b) { return items[a].bytes > items[b].bytes; });
+    }
+    const size_t cmd_slots = (size_t)items[n - 1].cmd_base + items[n - 1].cmd_cap;
+    const uint32_t tables = (uint32_t)std::min<size_t>(tables_max, n);
+
+    DevBlocks mem;
+    uint8_t* uploaded = mem.uninit<uint8_t>(text_bytes);
+    dev_h2d_bulk(uploaded, staging.data(), text_bytes);
+    BatchItem* items_dev = mem.uninit<BatchItem>((size_t)n * sizeof(BatchItem));
+    dev_h2d(items_dev, items.data(), (size_t)n * sizeof(BatchItem));
+    uint32_t* order_dev = mem.uninit<uint32_t>((size_t)n * 4);
+    dev_h2d(order_dev, order.data(), (size_t)n * 4);
+
+    QuickBatchJob J{};
+    J.P = P;
+    J.Q = Q;
+    J.Q.table = mem.uninit<uint32_t>((size_t)tables * table_bytes + 64);  // (every chain zeroes its table in front of every item)
+    J.text = uploaded;
+    J.slabs = mem.uninit<Command>(cmd_slots * sizeof(Command) + 64);
+    J.items = items_dev;
+    J.order = order_dev;
+    J.n_items = n;
+    J.tables = tables;
+    J.counter = mem.zeroed<uint32_t>(64);
+    J.records = mem.uninit<BatchRecord>((size_t)n * sizeof(BatchRecord));
+    lz77_quick_batch_parse(J);
+    records.resize_discard(n);
+    dev_d2h(records.data(), J.records, (size_t)n * sizeof(BatchRecord));
+    // ---- command gather: the offsets from the per-item records (one small round trip)
+    offsets.resize_discard(n);
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+      if (records[i].overflow) throw std::runtime_error("brotli_mi355x: a batch chain ran out of its command slab");
+      offsets[i] = (uint32_t)total;
+      mbs[i].cmd_offset = (uint32_t)total;
+      mbs[i].n_cmds = records[i].n_cmds;
+      mbs[i].n_lits = records[i].n_lits;
+      mbs[i].uncompressed = records[i].uncompressed;
+      total += records[i].n_cmds;
+    }
+    uint32_t* offsets_dev = mem.uninit<uint32_t>((size_t)n * 4);
+    dev_h2d(offsets_dev, offsets.data(), (size_t)n * 4);
+    Command* cmds = mem.uninit<Command>((size_t)(total + 16) * sizeof(Command));
+    // (br_raw_command / br_finish_command are those of qualities 5 .. 8: the gather wants the slabs, the items, the records and
+    // the distance parameters)
+    BatchParseJob G{};
+    G.P = P;
+    G.slabs = J.slabs;
+    G.items = items_dev;
+    G.n_items = n;
+    G.records = J.records;
+    lz77_batch_gather(G, offsets_dev, cmds);
+    // ---- one meta-block per item
+    std::vector<uint8_t> out;
+    EncodeBatchMetaBlocks(p, uploaded + packed_at, cmds, (uint32_t)total, &mbs, &out);
+    for (uint32_t i = 0; i < n; ++i)
+      (*streams)[first + i].assign(out.begin() + (ptrdiff_t)mbs[i].out_byte, out.begin() + (ptrdiff_t)(mbs[i].out_byte + mbs[i].out_bytes));
+    first = last;
+  }
+}
+
 }  // namespace
+
+bool BatchQuickEligible(const EncoderParams& user, size_t input_size) {
+  if (input_size == 0) return false;  // (answered without an encoder)
+  if (user.quality < 2 || user.quality > 4 || user.lgwin < 10 || user.lgwin > 24 || user.large_window) return false;
+  if (user.catable || user.appendable || user.bare_stream || user.byte_align || user.magic_number) return false;
+  if (input_size > ((size_t)1 << 16)) return false;
+  // (the item's size is its stream's size hint: below the 1 MiB that selects H54)
+  const EncoderParams p = ItemParams(user, input_size);
+  return (p.hasher.type == 2 || p.hasher.type == 3 || p.hasher.type == 4) && input_size <= ((size_t)1 << p.lgblock);
+}
+
+void BatchQuickCompress(const EncoderParams& user, size_t count, const uint8_t* const* inputs, const size_t* sizes,
+                        std::vector<std::vector<uint8_t>>* streams, uint32_t* groups) {
+  // (nothing in the parameters differs between items of at most one block)
+  CompressQuickGroups(ItemParams(user, count ? sizes[0] : 0), count, inputs, sizes, streams, groups);
+}
 
 void BatchGreedyCompress(const EncoderParams& user, size_t count, const uint8_t* const* inputs, const size_t* sizes,
                          std::vector<std::vector<uint8_t>>* streams, uint32_t* groups) {

@@ -1,0 +1,45 @@
+// batch_quick.h -- the small items of a batch at qualities 2 .. 4, side by side on the device (BrotliMi355xCompressBatchEx with
+// BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS).
+//
+// An item of at most one input block under a BasicHasher (H2 / H3 / H4) is ONE chain of br_quick_block (quick_device.h) on a
+// private table and ONE meta-block: it starts on a zeroed table with the throttle books at 0, so the chain is exact on its own
+// filings and nothing is speculated or repeated.  A group shares the plan of the items of qualities 5 .. 8 (batch_greedy.h): one
+// padded text buffer, one parse launch (k_quick_batch: one wavefront per table, each zeroing its table before every item), the
+// per-item records, the command gather (lz77_batch_gather) and one pass of the meta-block stage.  There is no key pass and there
+// are no flags: a BasicHasher hashes from the text.
+#ifndef BROTLI_MI355X_BATCH_QUICK_H_
+#define BROTLI_MI355X_BATCH_QUICK_H_
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "batch_greedy.h"
+#include "quick_api.h"
+
+namespace brotli_mi355x {
+
+// ---- device seam (quick_kernels.hip; the emulation build: batch_quick_emu.inc)
+struct QuickBatchJob {
+  Lz77Params P;  // of a stream that starts at 0 and stays inside the first ring-buffer revolution; total_bytes is set per item
+  QuickJob Q;    // the hasher; Q.table = the tables of the launch, [tables][quick_table_words(Q)] (16-byte aligned)
+  const uint8_t* text;  // the group's padded text: every item at a 64-byte boundary, at least 64 zero bytes behind it
+  Command* slabs;
+  const BatchItem* items;
+  const uint32_t* order;  // largest item first
+  uint32_t n_items;
+  uint32_t tables;
+  uint32_t* counter;  // [1], zero: the next place of `order` to hand out
+  BatchRecord* records;
+};
+// one wavefront per table; a wavefront takes items from `counter` until none is left
+void lz77_quick_batch_parse(const QuickBatchJob& J);
+
+// ---- host
+// Does this item go side by side under the quick route?  `params`: the caller's parameters as set, not finalized.
+bool BatchQuickEligible(const EncoderParams& params, size_t input_size);
+// The streams of `count` eligible items.  Throws std::runtime_error on a device error.  *groups: device groups run.
+void BatchQuickCompress(const EncoderParams& params, size_t count, const uint8_t* const* inputs, const size_t* sizes,
+                        std::vector<std::vector<uint8_t>>* streams, uint32_t* groups);
+
+}  // namespace brotli_mi355x
+#endif

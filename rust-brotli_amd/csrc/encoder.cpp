@@ -1160,7 +1160,7 @@ void EncodeBatchMetaBlocks(const EncoderParams& p, const uint8_t* text, const Co
   const uint32_t n_mb = (uint32_t)items.size();
   out->clear();
   if (n_mb == 0) return;
-  if (p.quality < 5 || p.quality > 9 || p.large_window || p.appendable || p.byte_align || p.magic_number)
+  if (p.quality < 2 || p.quality > 9 || p.lgwin < 10 || p.lgwin > 24 || p.large_window || p.appendable || p.byte_align || p.magic_number)
     throw std::runtime_error("brotli_mi355x: parameters the batch meta-block stage does not take");
   uint64_t L64 = 0;
   for (const BatchStreamItem& it : items) L64 += it.n_lits;
@@ -1215,7 +1215,9 @@ void EncodeBatchMetaBlocks(const EncoderParams& p, const uint8_t* text, const Co
       d.dist_postfix_bits = p.dist.distance_postfix_bits;
       d.num_direct_distance_codes = p.dist.num_direct_distance_codes;
       d.num_contexts = 1;
-      d.simple = kMbGreedy;
+      // qualities 2 and 3 (store_meta_block_fast / _trivial, metablock_fast.h): one block type per kind, context mode bits 0
+      d.simple = p.quality <= 2 ? kMbFast : (p.quality < 4 ? kMbTrivial : kMbGreedy);
+      if (d.simple != kMbGreedy) d.context_mode = 0;
     }
   }
   std::vector<MbResult> results(n_mb);
@@ -1245,7 +1247,7 @@ void EncodeBatchMetaBlocks(const EncoderParams& p, const uint8_t* text, const Co
       B.n_dists = di[n_mb];
     }
     // literal context modelling decision, with the size hint of the item's own stream
-    if (p.disable_literal_context_modeling == 0) {
+    if (p.disable_literal_context_modeling == 0 && p.quality >= 5) {  // (DecideOverLiteralContextModeling leaves lower qualities alone)
       uint32_t* stats_dev = mm.alloc<uint32_t>((size_t)n_mb * kContextStatsWords);
       mb_context_stats(B, stats_dev);
       std::vector<uint32_t> cs((size_t)n_mb * kContextStatsWords);
@@ -1268,8 +1270,13 @@ void EncodeBatchMetaBlocks(const EncoderParams& p, const uint8_t* text, const Co
     std::vector<CodeJob> jobs;
     for (uint32_t m = 0; m < n_mb; ++m) {
       if (descs[m].uncompressed) continue;
-      for (uint32_t k = 0; k < 3; ++k)
-        for (uint32_t i = 0; i < results[m].num_histos[k]; ++i) jobs.push_back({k, descs[m].histo_base[k] + i, descs[m].num_distance_symbols, kCodeOptimized});
+      for (uint32_t k = 0; k < 3; ++k) {
+        uint32_t mode = kCodeOptimized;
+        if (descs[m].simple == kMbTrivial) mode = kCodePlain;
+        // (quality 2: up to 128 commands are written with the static command and distance codes, brotli_bit_stream.rs:2619-2687)
+        if (descs[m].simple == kMbFast) mode = (descs[m].n_cmds <= 128 && k != kSplitLiteral) ? kCodeStatic : kCodeFast;
+        for (uint32_t i = 0; i < results[m].num_histos[k]; ++i) jobs.push_back({k, descs[m].histo_base[k] + i, descs[m].num_distance_symbols, mode});
+      }
     }
     B.huff_scratch = mm.alloc<HuffmanScratch>(std::max<size_t>(jobs.size(), n_mb) + 1);
     CodeJob* jobs_dev = mm.alloc<CodeJob>(jobs.size() + 1);
@@ -1299,11 +1306,15 @@ void EncodeBatchMetaBlocks(const EncoderParams& p, const uint8_t* text, const Co
       stream_bit = bits.pos;
       first_m = m;
       items[m].demoted = 0;
-      // stream header: window bits (EncodeWindowBits, encode.rs:603-625), lgwin 17 .. 24
-      if (p.lgwin == 17) {
+      // stream header: window bits (EncodeWindowBits, encode.rs:603-625), lgwin 10 .. 24
+      if (p.lgwin == 16) {
+        bits.put(1, 0);
+      } else if (p.lgwin == 17) {
         bits.put(7, 1);
-      } else {
+      } else if (p.lgwin > 17) {
         bits.put(4, (uint64_t)(((p.lgwin - 17) << 1) | 1));
+      } else {
+        bits.put(7, (uint64_t)(((p.lgwin - 8) << 4) | 1));
       }
     }
     const uint32_t bytes = d.end - d.start;

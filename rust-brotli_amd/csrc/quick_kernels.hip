@@ -2,6 +2,9 @@
 // greedy / lazy parse, one wavefront per stream walking the reference's own hash table block by block.
 #include <hip/hip_runtime.h>
 
+#include <stdexcept>
+
+#include "batch_quick_device.h"
 #include "quick_device.h"
 #include "device_scan.h"
 
@@ -65,6 +68,38 @@ __global__ __launch_bounds__(64) void k_quick_block(QuickJob J, Lz77Params P, Qu
 void lz77_quick_block(const Lz77Params& P, const Lz77Buffers& B, const QuickJob& J, uint32_t block) {
   hipLaunchKernelGGL(k_quick_block, dim3(1), dim3(64), 0, BR_STREAM, J, P, quick_tables(), (const uint8_t*)B.text, (const Segment*)B.segments, (const SegEntry*)B.entries, B.cmds,
                      B.exits, block);
+  HIP_CHECK(hipGetLastError());
+}
+
+// ---- batch_quick.h: the small items of a batch at these qualities, one chain each.  One wavefront per table, persistent over
+// the group like k_parse_batch: it takes the next place of `order` (largest item first) from the device counter until none is
+// left, and zeroes its table in front of every item.  A chain is bound by the latency of its own dependent loads; the
+// throughput of the launch is the number of chains in flight.
+__global__ __launch_bounds__(64) void k_quick_batch(QuickBatchJob J, QuickTables T, EntropyTables logs) {
+  __shared__ uint32_t histo[256];
+  __shared__ SegExit exit_slot;
+  const uint32_t table = blockIdx.x;
+  if (table >= J.tables) return;
+  for (;;) {
+    uint32_t mine = 0;
+    if (threadIdx.x == 0) mine = atomicAdd(J.counter, 1u);
+    const uint32_t place = BR_UNIFORM(mine);
+    if (place >= J.n_items) break;
+    const uint32_t index = BR_UNIFORM(J.order[place]);
+    if (index >= J.n_items) break;  // (never: the plan's order is a permutation)
+    br_quick_batch_item(J, T, logs, histo, &exit_slot, index, table);
+  }
+}
+
+void lz77_quick_batch_parse(const QuickBatchJob& J) {
+  if (J.n_items == 0) return;
+  if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
+  const DeviceTables& dt = dev_tables();
+  EntropyTables logs;
+  logs.logs_16 = dt.logs_16;
+  logs.logs_8 = dt.logs_8;
+  const uint32_t grid = J.tables < J.n_items ? J.tables : J.n_items;
+  hipLaunchKernelGGL(k_quick_batch, dim3(grid), dim3(64), 0, BR_STREAM, J, quick_tables(), logs);
   HIP_CHECK(hipGetLastError());
 }
 

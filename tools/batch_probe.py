@@ -26,6 +26,12 @@ BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS: the items of two to four input blocks go s
 library is still measured through its plain batch call and its 4-thread loop.  The classes 1024x128KiB and 256x256KiB (--only) are
 all long items.
 
+With --quick-items (and --qualities 2,3,4) this build is called through BrotliMi355xCompressBatchEx with
+BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS: the items of at most one input block (16 KiB at quality 2 and 3, 64 KiB at quality 4) go side by
+side, one chain on a private BasicHasher table each.  The parent's library is measured through its plain batch call (a loop over the
+one-shot path) and its 4-thread loop.  The classes are 4096x4KiB, 4096x16KiB (at quality 2 and 3 every item exactly at the limit),
+1024x64KiB (side by side at quality 4 only), 4096x512B and the log-uniform mix.
+
 Every measurement runs in a child process of its own (the table's home is one setting per process, read once; the parent's library
 is another shared object), one after the other, each under its own time limit; the first failure ends the probe.
 
@@ -61,6 +67,7 @@ CLASSES = {
 }
 HEADLINE = ["4096x4KiB", "4096x16KiB", "1024x64KiB", "64xalice29", "4096xlog200B-256KiB"]
 AB = ["4096x512B", "4096x2KiB", "4096xlog200B-256KiB"]
+QUICK_HEADLINE = ["4096x4KiB", "4096x16KiB", "1024x64KiB", "4096x512B", "4096xlog200B-256KiB"]  # (--quick-items)
 
 
 def items_of(name, data):
@@ -102,10 +109,10 @@ def bind(path):
     return L
 
 
-def measure_batch(lib_path, items, quality, runs, warmup, dictionary=None, long_items=False):
+def measure_batch(lib_path, items, quality, runs, warmup, dictionary=None, routes=0):
     L = bind(lib_path)
     L.BrotliMi355xCompressBatch.restype = ctypes.c_int32
-    if long_items:
+    if routes:
         L.BrotliMi355xCompressBatchEx.restype = ctypes.c_int32
     if dictionary is not None:
         L.BrotliMi355xCompressBatchWithDictionary.restype = ctypes.c_int32
@@ -125,8 +132,8 @@ def measure_batch(lib_path, items, quality, runs, warmup, dictionary=None, long_
         for i in range(n):
             out_sizes[i] = caps[i]
         t = time.perf_counter()
-        if long_items:
-            ok = L.BrotliMi355xCompressBatchEx(quality, LGWIN, 0, ctypes.c_uint32(1), ctypes.c_size_t(n), inputs, in_sizes, outputs, out_sizes, None)
+        if routes:
+            ok = L.BrotliMi355xCompressBatchEx(quality, LGWIN, 0, ctypes.c_uint32(routes), ctypes.c_size_t(n), inputs, in_sizes, outputs, out_sizes, None)
         elif dictionary is None:
             ok = L.BrotliMi355xCompressBatch(quality, LGWIN, 0, ctypes.c_size_t(n), inputs, in_sizes, outputs, out_sizes, None)
         else:
@@ -234,7 +241,8 @@ def child(args):
             for quality in [int(q) for q in args.qualities.split(",")]:
                 row = {"class": name, "data": data, "quality": quality, "items": len(items), "bytes": sum(map(len, items))}
                 if args.child == "batch":
-                    times, csize, info, failed = measure_batch(args.lib, first if args.first_only else items, quality, args.runs, args.warmup, dictionary, args.long_items)
+                    times, csize, info, failed = measure_batch(args.lib, first if args.first_only else items, quality, args.runs, args.warmup, dictionary,
+                                                              (1 if args.long_items else 0) | (4 if args.quick_items else 0))
                     row.update(stats(times), compressed_bytes=csize, batch_info=info, reference_fails_on_items=failed, measured_items=len(first) if args.first_only else len(items))
                 elif args.child == "loop":
                     times, failed = measure_loop(args.lib, first, quality, args.threads, args.runs, 1, dictionary)
@@ -248,7 +256,7 @@ def child(args):
         json.dump(out, f)
 
 
-def run_child(args, what, classes, lib=None, lds=None, threads=1, limit=600, first_only=False, plain=False, long_items=False):
+def run_child(args, what, classes, lib=None, lds=None, threads=1, limit=600, first_only=False, plain=False, long_items=False, quick_items=False):
     env = dict(os.environ)
     env.pop("BROTLI_MI355X_BATCH_LDS_BITS", None)
     if lds is not None:
@@ -256,7 +264,7 @@ def run_child(args, what, classes, lib=None, lds=None, threads=1, limit=600, fir
     tmp = os.path.join(os.path.dirname(os.path.abspath(args.out)), ".batch_probe_child.json")
     cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--child", what, "--classes", ",".join(classes), "--lib", lib or args.lib,
            "--threads", str(threads), "--runs", str(args.runs), "--warmup", str(args.warmup), "--loop-items", str(args.loop_items), "--child-out", tmp, "--qualities", args.qualities,
-           "--dictionary", str(args.dictionary)] + (["--first-only"] if first_only else []) + (["--plain"] if plain else []) + (["--long-items"] if long_items else [])
+           "--dictionary", str(args.dictionary)] + (["--first-only"] if first_only else []) + (["--plain"] if plain else []) + (["--long-items"] if long_items else []) + (["--quick-items"] if quick_items else [])
     r = subprocess.run(cmd, env=env)
     if r.returncode != 0:
         raise SystemExit("batch_probe: %s (lds=%s, threads=%d) ended with status %d: nothing more is started" % (what, lds, threads, r.returncode))
@@ -337,6 +345,7 @@ def main():
     ap.add_argument("--first-only", action="store_true")
     ap.add_argument("--dictionary", type=int, default=0, help="bytes of shared custom dictionary: measures BrotliMi355xCompressBatchWithDictionary")
     ap.add_argument("--long-items", action="store_true", help="this build through BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS")
+    ap.add_argument("--quick-items", action="store_true", help="this build through BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS (--qualities 2,3,4)")
     ap.add_argument("--plain", action="store_true", help="(child) the plain call although a dictionary size is given")
     ap.add_argument("--child", default=None)
     ap.add_argument("--classes", default="")
@@ -355,9 +364,11 @@ def main():
         with open(args.out, "w") as f:
             json.dump(doc, f, indent=1)
 
-    headline = [c for c in (args.only.split(",") if args.only else HEADLINE) if c in CLASSES]
+    headline = [c for c in (args.only.split(",") if args.only else (QUICK_HEADLINE if args.quick_items else HEADLINE)) if c in CLASSES]
     if args.long_items:
         doc["what"] = "BrotliMi355xCompressBatchEx(BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS) vs the parent commit's batch call and 4-thread loop vs the oracle on one CPU core; lgwin 22"
+    if args.quick_items:
+        doc["what"] = "BrotliMi355xCompressBatchEx(BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS) vs the parent commit's batch call and 4-thread loop vs the oracle on one CPU core; lgwin 22"
     if args.dictionary:
         return main_dictionary(args, doc, save, [c for c in ("4096x4KiB", "1024x64KiB") if not args.only or c in args.only.split(",")])
     fragment_qualities = set(args.qualities.split(",")) <= {"0", "1"}
@@ -382,7 +393,7 @@ def main():
     if "headline" not in skip:
         rows = {}
         for rnd in range(args.rounds):
-            for row in run_child(args, "batch", headline, limit=900, long_items=args.long_items):
+            for row in run_child(args, "batch", headline, limit=900, long_items=args.long_items, quick_items=args.quick_items):
                 this = {k: row[k] for k in ("median_ms", "min_ms", "max_ms", "spread_pct", "runs")}
                 if rnd == 0:
                     rows[key(row)] = {"items": row["items"], "bytes": row["bytes"], "compressed_bytes": row["compressed_bytes"], "batch_info": row["batch_info"], "batch": this}
