@@ -254,14 +254,29 @@ int32_t BrotliMi355xCompressBatchWithDictionary(int quality, int lgwin, BrotliEn
    1 <= input_sizes[i] <= 16 384 at quality 2 / 3 and <= 65 536 at quality 4 -- runs on the device as ONE chain on a private
    BasicHasher table (H2 / H3 / H4; 256 KiB, at quality 4 512 KiB), side by side with the other such items of the call (groups of
    their own, under the same environment limits; 4096 tables by default), and leaves one meta-block.  Every other item goes as in
-   the plain call: longer items at these qualities still run one by one, with BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS set as well.
+   the plain call: longer items at these qualities still run one by one, with BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS set as well
+   (BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS takes those of up to four blocks).
    The bit changes nothing at qualities 0, 1 and 5 .. 11.  Such items count in info[1], their groups in info[4]; info[6] and
    info[7] stay 0 for them.  When to set it: with hundreds of small items of one kind in a call (dynamic responses at the levels
    servers use for them); a chain is one wavefront bound by its own dependent loads, so a call of a few items is no faster
    than the one-by-one path (see INTEGRATION.md for measured figures).  Not combined with a shared dictionary.
-   The two bits may be combined.  The value 2 is reserved: it names no route and fails the call like any unknown bit. */
+   BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS: item i still gets exactly what BrotliEncoderCompress gives.  In addition, an item
+   of more than one and at most four input blocks at quality 2, 3 or 4 and lgwin 10 .. 24 -- that is
+   16 385 <= input_sizes[i] <= 65 536 at quality 2 / 3 and 65 537 <= input_sizes[i] <= 262 144 at quality 4 -- runs on the device
+   as ONE chain on a private BasicHasher table that walks from block to block, side by side with the other such items of the call
+   (groups of their own, under the same environment limits), and leaves up to four meta-blocks.  The bit is independent of
+   BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS: alone it takes the items of several blocks only and the shorter ones run one by one;
+   both bits take both.  It changes nothing at qualities 0, 1 and 5 .. 11, and BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS together with
+   BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS does NOT stand for it.  Such items count in info[1] and info[7], their groups in info[4].
+   When a meta-block that is not the item's last turns out longer coded than stored, the item is redone through the one-shot path
+   in the same call (info[6]), as under BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS.  When to set it: a chain is one wavefront bound by
+   its own dependent loads, so an item of several blocks takes a lone chain's time however many items run beside it; the route
+   pays with many such items in a call (dynamic responses of 20 to 64 KiB at quality 2 / 3; see INTEGRATION.md for measured
+   figures) and loses with a few.  Not combined with a shared dictionary.
+   The bits may be combined.  The values 2 and 8 are reserved: they name no route and fail the call like any unknown bit. */
 #define BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS 1u
 #define BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS 4u /* (2u is reserved and stays an unknown route) */
+#define BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS 16u /* (8u stays an unknown route, like 2u) */
 int32_t BrotliMi355xCompressBatchEx(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t count,
                                     const uint8_t* const* inputs, const size_t* input_sizes, uint8_t* const* outputs,
                                     size_t* output_sizes /* in: capacity, out: size */, int32_t* item_results /* may be NULL */);
@@ -271,8 +286,8 @@ int32_t BrotliMi355xCompressBatchEx(int quality, int lgwin, BrotliEncoderMode mo
    groups (those of long items included), [5] dictionary bytes in use after the reference's truncation (0 for the plain call),
    [6] items that began side by side and were redone one by one (counted in [2], not in [1]), [7] of the items counted in [1],
    those longer than one input block; [6] and [7] are zero unless BrotliMi355xCompressBatchEx was called with
-   BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS (the items of BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS count in [1] and [4] only).  After a
-   call that failed as a whole only info[0] is set. */
+   BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS or BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS (the items of
+   BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS count in [1] and [4] only).  After a call that failed as a whole only info[0] is set. */
 void BrotliMi355xLastBatchInfo(uint64_t info[8]);
 /* Human-readable description of the device backing the library ("hip:gfx950 (...)"). */
 const char* BrotliMi355xDeviceName(void);

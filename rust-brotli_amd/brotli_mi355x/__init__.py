@@ -177,8 +177,9 @@ class Library(object):
 
     BATCH_ROUTE_LONG_ITEMS = 1  # BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS
     BATCH_ROUTE_QUICK_ITEMS = 4  # BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS (2 is reserved)
+    BATCH_ROUTE_QUICK_LONG_ITEMS = 16  # BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS (8 is reserved)
 
-    def compress_batch(self, items, quality=0, lgwin=22, mode=0, dictionary=None, long_items=False, quick_items=False):
+    def compress_batch(self, items, quality=0, lgwin=22, mode=0, dictionary=None, long_items=False, quick_items=False, quick_long_items=False):
         """BrotliMi355xCompressBatch: every item becomes a stream of its own, the same bytes as compress(item, quality, lgwin,
         mode), in one call.  Side by side on the device (the call for many small payloads): every item at qualities 0 and 1, and
         at qualities 5 to 8 the items of at most 65 536 bytes at lgwin 17 to 24.  Everything else runs item by item in the same
@@ -196,12 +197,21 @@ class Library(object):
         to 24 the items of at most one input block (16 384 bytes at quality 2 and 3, 65 536 at quality 4) run side by side, one
         chain on a private hash table each (the same bytes).  Without it these qualities run item by item; longer items at these
         qualities still do.  It pays with hundreds of small items in a call.  May be combined with long_items, not with a
-        dictionary."""
+        dictionary.
+
+        quick_long_items=True: BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS -- at qualities 2 to 4 and
+        lgwin 10 to 24 the items of more than one and at most four input blocks (16 385 to 65 536 bytes at quality 2 and 3, 65 537
+        to 262 144 at quality 4) run side by side, one chain each that walks from block to block (the same bytes).  Independent of
+        quick_items: alone it takes these items only, together they take both.  A chain is one wavefront, so such an item takes a
+        lone chain's time however many run beside it: it pays with many such items in a call.  Not combined with a dictionary."""
+        if quick_long_items and dictionary is not None:
+            raise ValueError("quick_long_items and dictionary cannot be combined: BrotliMi355xCompressBatchWithDictionary has no routes")
         if long_items and dictionary is not None:
             raise ValueError("long_items and dictionary cannot be combined: BrotliMi355xCompressBatchWithDictionary has no routes")
         if quick_items and dictionary is not None:
             raise ValueError("quick_items and dictionary cannot be combined: BrotliMi355xCompressBatchWithDictionary has no routes")
         routes = (self.BATCH_ROUTE_LONG_ITEMS if long_items else 0) | (self.BATCH_ROUTE_QUICK_ITEMS if quick_items else 0)
+        routes |= self.BATCH_ROUTE_QUICK_LONG_ITEMS if quick_long_items else 0
         items = [bytes(x) for x in items]
         count = len(items)
         if count == 0:
@@ -242,7 +252,8 @@ class Library(object):
         """BrotliMi355xLastBatchInfo: the last compress_batch call of this thread as a list of 8 integers -- [0] items, [1] items
         encoded side by side on the device, [2] items run one by one, [3] items answered without an encoder, [4] device groups, [5] dictionary bytes in use (0 without one),
         [6] items that began side by side and were redone one by one (counted in [2]), [7] of the items in [1], those longer than one
-        input block ([6] and [7]: long_items=True only; the items quick_items=True takes side by side count in [1] and [4])."""
+        input block ([6] and [7]: long_items=True and quick_long_items=True only; the items quick_items=True takes side by side
+        count in [1] and [4])."""
         info = (c_uint64 * 8)()
         self.lib.BrotliMi355xLastBatchInfo.restype = None
         self.lib.BrotliMi355xLastBatchInfo.argtypes = [POINTER(c_uint64)]

@@ -545,6 +545,155 @@ void CompressQuickGroups(const EncoderParams& p, size_t count, const uint8_t* co
   }
 }
 
+// Qualities 2 .. 4, items of two to kBatchLongBlocks input blocks (batch_quick.h): the staging, the tables and the launch shape of
+// CompressQuickGroups; the records, their validation, the gather, the meta-blocks per item and the demoted list of CompressLongGroups.
+void CompressQuickLongGroups(const EncoderParams& p, size_t count, const uint8_t* const* inputs, const size_t* sizes,
+                             std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* demoted, uint32_t* groups) {
+  static const size_t group_items = std::max<size_t>(1, EnvSize("BROTLI_MI355X_BATCH_GROUP_ITEMS", 4096));
+  static const size_t group_bytes = std::max<size_t>(1, EnvSize("BROTLI_MI355X_BATCH_GROUP_BYTES", (size_t)64 << 20));
+  static const size_t table_override = EnvSize("BROTLI_MI355X_BATCH_TABLES", 0);
+  streams->assign(count, std::vector<uint8_t>());
+  demoted->assign(count, 0);
+  *groups = 0;
+  if (count == 0) return;
+  QuickJob Q;  // as Lz77Stage::Setup fills it in
+  Q.kind = (uint32_t)p.hasher.type;
+  Q.bucket_bits = Q.kind == 4 ? 17 : 16;
+  Q.sweep = Q.kind == 2 ? 1 : (Q.kind == 3 ? 2 : 4);
+  Q.hash_len = 5;
+  Q.use_dictionary = (p.use_dictionary && (Q.kind == 2 || Q.kind == 4)) ? 1 : 0;
+  const size_t table_bytes = (size_t)quick_table_words(Q) * 4;
+  const size_t tables_max = table_override ? table_override : std::max<size_t>(1, std::min<size_t>(4096, ((size_t)8 << 30) / table_bytes));
+  Lz77Params P = ChainParams(p);  // (ring_mask: the items' own ring buffer, which an item of three blocks outruns at lgwin <= 14)
+  P.hasher_kind = 6;
+  P.htl = 8;
+  P.use_dictionary = Q.use_dictionary;
+  P.dict_break = 0;
+
+  PinnedArray<uint8_t> staging;
+  PinnedArray<BatchItem> items;
+  PinnedArray<uint32_t> order, offsets;
+  PinnedArray<BatchLongRecord> records;
+  size_t first = 0;
+  while (first < count) {
+    size_t last = first, padded = 0, packed = 0;
+    while (last < count && last - first < group_items && (last == first || packed + sizes[last] <= group_bytes)) {
+      padded += Padded((uint32_t)sizes[last]);
+      packed += sizes[last];
+      ++last;
+    }
+    const uint32_t n = (uint32_t)(last - first);
+    ++*groups;
+    // one page-locked buffer, one upload: [padded text | 64 | packed text | 64]
+    const size_t packed_at = padded + 64;
+    const size_t text_bytes = packed_at + packed + 64;
+    staging.resize_discard(text_bytes);
+    memset(staging.data(), 0, text_bytes);
+    items.resize_discard(n);
+    order.resize_discard(n);
+    std::vector<uint32_t> starts(n);
+    {
+      uint32_t off = 0, start = 0, cmd_base = 0;
+      for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t bytes = (uint32_t)sizes[first + i];
+        memcpy(staging.data() + off, inputs[first + i], bytes);
+        memcpy(staging.data() + packed_at + start, inputs[first + i], bytes);
+        items[i] = BatchItem{off, bytes, cmd_base, bytes / 2 + 8};
+        starts[i] = start;
+        off += Padded(bytes);
+        start += bytes;
+        cmd_base += bytes / 2 + 8;
+        order[i] = i;
+      }
+      std::stable_sort(order.data(), order.data() + n, [&](uint32_t a, uint32_t b) { return items[a].bytes > items[b].bytes; });
+    }
+    const size_t cmd_slots = (size_t)items[n - 1].cmd_base + items[n - 1].cmd_cap;
+    const uint32_t tables = (uint32_t)std::min<size_t>(tables_max, n);
+
+    DevBlocks mem;
+    uint8_t* uploaded = mem.uninit<uint8_t>(text_bytes);
+    dev_h2d_bulk(uploaded, staging.data(), text_bytes);
+    BatchItem* items_dev = mem.uninit<BatchItem>((size_t)n * sizeof(BatchItem));
+    dev_h2d(items_dev, items.data(), (size_t)n * sizeof(BatchItem));
+    uint32_t* order_dev = mem.uninit<uint32_t>((size_t)n * 4);
+    dev_h2d(order_dev, order.data(), (size_t)n * 4);
+
+    QuickBatchJob J{};
+    J.P = P;
+    J.Q = Q;
+    J.Q.table = mem.uninit<uint32_t>((size_t)tables * table_bytes + 64);  // (every chain zeroes its table in front of every item)
+    J.text = uploaded;
+    J.slabs = mem.uninit<Command>(cmd_slots * sizeof(Command) + 64);
+    J.items = items_dev;
+    J.order = order_dev;
+    J.n_items = n;
+    J.tables = tables;
+    J.counter = mem.zeroed<uint32_t>(64);
+    J.records = nullptr;
+    BatchLongRecord* records_dev = mem.uninit<BatchLongRecord>((size_t)n * sizeof(BatchLongRecord));
+    lz77_quick_batch_parse_long(J, records_dev);
+    records.resize_discard(n);
+    dev_d2h(records.data(), records_dev, (size_t)n * sizeof(BatchLongRecord));
+    // ---- command gather: the offsets per meta-block from the records (one small round trip)
+    offsets.resize_discard((size_t)n * kBatchLongBlocks);
+    std::vector<BatchStreamItem> mbs;
+    std::vector<uint32_t> first_mb(n);
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+      const BatchLongRecord& r = records[i];
+      if (r.overflow) throw std::runtime_error("brotli_mi355x: a batch chain ran out of its command slab");
+      uint32_t at = 0, cmd_at = 0;
+      first_mb[i] = (uint32_t)mbs.size();
+      for (uint32_t m = 0; m < kBatchLongBlocks; ++m) offsets[(size_t)i * kBatchLongBlocks + m] = 0;
+      for (uint32_t m = 0; m < r.n_mb && m < kBatchLongBlocks; ++m) {
+        const BatchLongMetaBlock& mb = r.mb[m];
+        if (mb.start != at || mb.bytes == 0 || mb.bytes > items[i].bytes - at || mb.first_cmd != cmd_at) break;
+        offsets[(size_t)i * kBatchLongBlocks + m] = (uint32_t)total;
+        BatchStreamItem e{};
+        e.start = starts[i] + mb.start;
+        e.bytes = mb.bytes;
+        e.cmd_offset = (uint32_t)total;
+        e.n_cmds = mb.n_cmds + (mb.trailing != 0 ? 1u : 0u);
+        e.n_lits = mb.n_lits;
+        e.uncompressed = mb.uncompressed;
+        e.follows = m != 0;
+        e.more = m + 1 != r.n_mb;
+        e.item_bytes = items[i].bytes;
+        if (m != 0) {
+          e.prev_byte = inputs[first + i][mb.start - 1];
+          e.prev_byte2 = inputs[first + i][mb.start - 2];
+        }
+        mbs.push_back(e);
+        total += e.n_cmds;
+        at += mb.bytes;
+        cmd_at += mb.n_cmds;
+      }
+      if (at != items[i].bytes || cmd_at > items[i].cmd_cap) throw std::runtime_error("brotli_mi355x: a batch chain left meta-block records that do not cover its item");
+    }
+    uint32_t* offsets_dev = mem.uninit<uint32_t>((size_t)n * kBatchLongBlocks * 4);
+    dev_h2d(offsets_dev, offsets.data(), (size_t)n * kBatchLongBlocks * 4);
+    Command* cmds = mem.uninit<Command>((size_t)(total + 16) * sizeof(Command));
+    // (the gather wants the slabs, the items and the distance parameters, as in CompressQuickGroups)
+    BatchParseJob G{};
+    G.P = P;
+    G.slabs = J.slabs;
+    G.items = items_dev;
+    G.n_items = n;
+    lz77_batch_gather_long(G, records_dev, offsets_dev, cmds);
+    std::vector<uint8_t> out;
+    EncodeBatchMetaBlocks(p, uploaded + packed_at, cmds, (uint32_t)total, &mbs, &out);
+    for (uint32_t i = 0; i < n; ++i) {
+      const BatchStreamItem& e = mbs[first_mb[i]];
+      if (e.demoted) {
+        (*demoted)[first + i] = 1;
+        continue;
+      }
+      (*streams)[first + i].assign(out.begin() + (ptrdiff_t)e.out_byte, out.begin() + (ptrdiff_t)(e.out_byte + e.out_bytes));
+    }
+    first = last;
+  }
+}
+
 }  // namespace
 
 bool BatchQuickEligible(const EncoderParams& user, size_t input_size) {
@@ -561,6 +710,22 @@ void BatchQuickCompress(const EncoderParams& user, size_t count, const uint8_t* 
                         std::vector<std::vector<uint8_t>>* streams, uint32_t* groups) {
   // (nothing in the parameters differs between items of at most one block)
   CompressQuickGroups(ItemParams(user, count ? sizes[0] : 0), count, inputs, sizes, streams, groups);
+}
+
+bool BatchQuickLongEligible(const EncoderParams& user, size_t input_size) {
+  if (user.quality < 2 || user.quality > 4 || user.lgwin < 10 || user.lgwin > 24 || user.large_window) return false;
+  if (user.catable || user.appendable || user.bare_stream || user.byte_align || user.magic_number) return false;
+  if (input_size > kBatchLongBytes) return false;
+  // (four blocks are 64 KiB at quality 2 / 3 and 256 KiB at quality 4: the size hint stays below the 1 MiB that selects H54)
+  const EncoderParams p = ItemParams(user, input_size);
+  return (p.hasher.type == 2 || p.hasher.type == 3 || p.hasher.type == 4) && input_size > ((size_t)1 << p.lgblock) &&
+         input_size <= (size_t)kBatchLongBlocks << p.lgblock;
+}
+
+void BatchQuickLongCompress(const EncoderParams& user, size_t count, const uint8_t* const* inputs, const size_t* sizes,
+                            std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* demoted, uint32_t* groups) {
+  // (nothing in the parameters differs between items of at most four blocks)
+  CompressQuickLongGroups(ItemParams(user, count ? sizes[0] : 0), count, inputs, sizes, streams, demoted, groups);
 }
 
 void BatchGreedyCompress(const EncoderParams& user, size_t count, const uint8_t* const* inputs, const size_t* sizes,

@@ -34,9 +34,23 @@ struct QuickBatchJob {
 // one wavefront per table; a wavefront takes items from `counter` until none is left
 void lz77_quick_batch_parse(const QuickBatchJob& J);
 
+// ---- items of several blocks (BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS): an item of two to kBatchLongBlocks input blocks is still
+// ONE chain on a private table -- br_quick_block block after block, with the books between the blocks that the host resolver keeps
+// for a one-shot call (extend_last_command, pending literals, the flush rule with the 0x2fff rule of qualities 2 and 3,
+// should_compress, the saved distance cache) kept by the chain itself, as k_parse_batch_long keeps them for H5 -- and leaves up to
+// kBatchLongBlocks meta-blocks, one BatchLongRecord per item.  J.records is not used; J.P.ring_mask is that of the items'
+// parameters (at lgwin <= 14 such an item passes the ring buffer's first lap) and J.P.quality decides the 0x2fff rule.
+// The gather is lz77_batch_gather_long.
+void lz77_quick_batch_parse_long(const QuickBatchJob& J, BatchLongRecord* records);
+
 // ---- host
 // Does this item go side by side under the quick route?  `params`: the caller's parameters as set, not finalized.
 bool BatchQuickEligible(const EncoderParams& params, size_t input_size);
+// ... under the quick-long route: the same tests for an item of more than one and at most kBatchLongBlocks input blocks
+bool BatchQuickLongEligible(const EncoderParams& params, size_t input_size);
+// The streams of `count` such items.  (*demoted)[i] != 0: as for BatchLongCompress -- no stream, the caller redoes the item.
+void BatchQuickLongCompress(const EncoderParams& params, size_t count, const uint8_t* const* inputs, const size_t* sizes,
+                            std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* demoted, uint32_t* groups);
 // The streams of `count` eligible items.  Throws std::runtime_error on a device error.  *groups: device groups run.
 void BatchQuickCompress(const EncoderParams& params, size_t count, const uint8_t* const* inputs, const size_t* sizes,
                         std::vector<std::vector<uint8_t>>* streams, uint32_t* groups);

@@ -1012,10 +1012,10 @@ static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEn
                              int32_t* item_results) {
   uint64_t info[8] = {count, 0, 0, 0, 0, 0, 0, 0};
   memcpy(g_batch_info, info, sizeof(info));
-  if ((routes & ~(uint32_t)(BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS | BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS)) != 0) {
+  if ((routes & ~(uint32_t)(BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS | BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS | BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS)) != 0) {
     // a route this build does not know fails the call as a whole, like a device error: a caller can probe for later routes
     SetError(entry, ("routes " + std::to_string(routes) + " names a route this build does not know (known: BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS = 1, "
-                     "BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS = 4; the value 2 is reserved)").c_str());
+                     "BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS = 4, BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS = 16; the values 2 and 8 are reserved)").c_str());
     for (size_t i = 0; i < count; ++i) output_sizes[i] = 0;
     if (item_results && count) memset(item_results, 0, count * sizeof(int32_t));
     return 0;
@@ -1034,13 +1034,15 @@ static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEn
     const bool fragments = IsFragmentStream(params);
     // The items an encoder sees and that go side by side on the device: every item of qualities 0 and 1 (fragment_stream.h), the
     // items of one input block under an H5 hasher at qualities 5 .. 8 (batch_greedy.h) and, where the caller asked for that route,
-    // those of two to four blocks, or those of one input block under a BasicHasher at qualities 2 .. 4 (batch_quick.h).  Every other
-    // item goes through the one-shot path by itself, on this thread, in the caller's order (the same bytes, no gain in speed).
-    std::vector<size_t> item, long_item, quick_item;
-    std::vector<const uint8_t*> in, long_in, quick_in;
-    std::vector<size_t> in_size, long_size, quick_size;
+    // those of two to four blocks, or those of one input block under a BasicHasher at qualities 2 .. 4, or those of two to four
+    // blocks at these qualities (batch_quick.h).  Every other item goes through the one-shot path by itself, on this thread, in
+    // the caller's order (the same bytes, no gain in speed).
+    std::vector<size_t> item, long_item, quick_item, quick_long_item;
+    std::vector<const uint8_t*> in, long_in, quick_in, quick_long_in;
+    std::vector<size_t> in_size, long_size, quick_size, quick_long_size;
     const bool long_route = (routes & BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS) != 0;
     const bool quick_route = (routes & BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS) != 0;
+    const bool quick_long_route = (routes & BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS) != 0;
     auto one_by_one = [&](size_t i) {
       std::string error;
       results[i] = CompressOneShot(quality, lgwin, mode, input_sizes[i], inputs[i], false, &output_sizes[i], outputs[i], nullptr, &error);
@@ -1074,6 +1076,12 @@ static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEn
         quick_size.push_back(input_sizes[i]);
         continue;
       }
+      if (quick_long_route && BatchQuickLongEligible(params, input_sizes[i])) {
+        quick_long_item.push_back(i);
+        quick_long_in.push_back(inputs[i]);
+        quick_long_size.push_back(input_sizes[i]);
+        continue;
+      }
       one_by_one(i);
     }
     // ---- the items of one block at qualities 2 .. 4, one chain each, in groups of their own (BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS)
@@ -1086,6 +1094,27 @@ static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEn
         const size_t i = quick_item[k];
         results[i] = OneShotDeliver(quick_streams[k].data(), quick_streams[k].size(), inputs[i], input_sizes[i], false, output_sizes[i], &output_sizes[i], outputs[i]);
         ++info[1];
+      }
+    }
+    // ---- the items of two to four blocks at qualities 2 .. 4, one chain each, in groups of their own
+    // (BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS)
+    if (!quick_long_item.empty()) {
+      std::vector<std::vector<uint8_t>> long_streams;
+      std::vector<uint8_t> demoted;
+      uint32_t groups = 0;
+      BatchQuickLongCompress(params, quick_long_item.size(), quick_long_in.data(), quick_long_size.data(), &long_streams, &demoted, &groups);
+      info[4] += groups;
+      for (size_t k = 0; k < quick_long_item.size(); ++k) {
+        const size_t i = quick_long_item[k];
+        if (demoted[k]) {
+          // a meta-block that is not the item's last took the size fallback, which its chain could not know: redone one by one
+          one_by_one(i);
+          ++info[6];
+          continue;
+        }
+        results[i] = OneShotDeliver(long_streams[k].data(), long_streams[k].size(), inputs[i], input_sizes[i], false, output_sizes[i], &output_sizes[i], outputs[i]);
+        ++info[1];
+        ++info[7];
       }
     }
     // ---- the items of several blocks, one chain each, in groups of their own (BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS)

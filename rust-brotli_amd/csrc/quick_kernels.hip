@@ -103,4 +103,34 @@ void lz77_quick_batch_parse(const QuickBatchJob& J) {
   HIP_CHECK(hipGetLastError());
 }
 
+// ---- items of two to kBatchLongBlocks input blocks (batch_quick.h): the launch shape of k_quick_batch, the item code walks from
+// block to block and leaves one BatchLongRecord per item.
+__global__ __launch_bounds__(64) void k_quick_batch_long(QuickBatchJob J, BatchLongRecord* __restrict__ records, QuickTables T, EntropyTables logs) {
+  __shared__ uint32_t histo[256];
+  __shared__ SegExit exit_slot;
+  const uint32_t table = blockIdx.x;
+  if (table >= J.tables) return;
+  for (;;) {
+    uint32_t mine = 0;
+    if (threadIdx.x == 0) mine = atomicAdd(J.counter, 1u);
+    const uint32_t place = BR_UNIFORM(mine);
+    if (place >= J.n_items) break;
+    const uint32_t index = BR_UNIFORM(J.order[place]);
+    if (index >= J.n_items) break;  // (never: the plan's order is a permutation)
+    br_quick_batch_item_long(J, records, T, logs, histo, &exit_slot, index, table);
+  }
+}
+
+void lz77_quick_batch_parse_long(const QuickBatchJob& J, BatchLongRecord* records) {
+  if (J.n_items == 0) return;
+  if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
+  const DeviceTables& dt = dev_tables();
+  EntropyTables logs;
+  logs.logs_16 = dt.logs_16;
+  logs.logs_8 = dt.logs_8;
+  const uint32_t grid = J.tables < J.n_items ? J.tables : J.n_items;
+  hipLaunchKernelGGL(k_quick_batch_long, dim3(grid), dim3(64), 0, BR_STREAM, J, records, quick_tables(), logs);
+  HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace brotli_mi355x

@@ -32,6 +32,12 @@ side, one chain on a private BasicHasher table each.  The parent's library is me
 one-shot path) and its 4-thread loop.  The classes are 4096x4KiB, 4096x16KiB (at quality 2 and 3 every item exactly at the limit),
 1024x64KiB (side by side at quality 4 only), 4096x512B and the log-uniform mix.
 
+With --quick-long-items this build is called with BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS | BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS: at
+qualities 2 to 4 the items of two to four input blocks go side by side as well, one chain each that walks from block to block.  The
+parent's library is measured through BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS on the same items, which takes them one by one.  The
+classes are 1024x32KiB and 1024x64KiB at quality 2 and 3, 1024x128KiB and 256x256KiB at quality 4, and the count sweep
+{16, 64, 256, 1024}x48KiB at quality 2 (QUICK_LONG_QUALITIES); --skip cpu,loop leaves out the oracle and the 4-thread loop.
+
 Every measurement runs in a child process of its own (the table's home is one setting per process, read once; the parent's library
 is another shared object), one after the other, each under its own time limit; the first failure ends the probe.
 
@@ -64,9 +70,18 @@ CLASSES = {
     # one table size each (the A/B of the table's home)
     "4096x512B": ("uniform", 4096, 512),
     "4096x2KiB": ("uniform", 4096, 2 << 10),
+    # items of two to four input blocks at qualities 2 to 4 (--quick-long-items)
+    "1024x32KiB": ("uniform", 1024, 32 << 10),
+    "16x48KiB": ("uniform", 16, 48 << 10),
+    "64x48KiB": ("uniform", 64, 48 << 10),
+    "256x48KiB": ("uniform", 256, 48 << 10),
+    "1024x48KiB": ("uniform", 1024, 48 << 10),
 }
 HEADLINE = ["4096x4KiB", "4096x16KiB", "1024x64KiB", "64xalice29", "4096xlog200B-256KiB"]
 AB = ["4096x512B", "4096x2KiB", "4096xlog200B-256KiB"]
+# (--quick-long-items) the qualities at which a class is made of items of two to four input blocks
+QUICK_LONG_QUALITIES = {"1024x32KiB": (2, 3), "1024x64KiB": (2, 3), "1024x128KiB": (4,), "256x256KiB": (4,),
+                        "16x48KiB": (2,), "64x48KiB": (2,), "256x48KiB": (2,), "1024x48KiB": (2,)}
 QUICK_HEADLINE = ["4096x4KiB", "4096x16KiB", "1024x64KiB", "4096x512B", "4096xlog200B-256KiB"]  # (--quick-items)
 
 
@@ -239,10 +254,12 @@ def child(args):
             first = items[:args.loop_items]
             dictionary = dictionary_of(data, args.dictionary) if args.dictionary and not args.plain else None
             for quality in [int(q) for q in args.qualities.split(",")]:
+                if args.quick_long_classes and quality not in QUICK_LONG_QUALITIES.get(name, ()):
+                    continue
                 row = {"class": name, "data": data, "quality": quality, "items": len(items), "bytes": sum(map(len, items))}
                 if args.child == "batch":
                     times, csize, info, failed = measure_batch(args.lib, first if args.first_only else items, quality, args.runs, args.warmup, dictionary,
-                                                              (1 if args.long_items else 0) | (4 if args.quick_items else 0))
+                                                              (1 if args.long_items else 0) | (4 if args.quick_items else 0) | (16 if args.quick_long_items else 0))
                     row.update(stats(times), compressed_bytes=csize, batch_info=info, reference_fails_on_items=failed, measured_items=len(first) if args.first_only else len(items))
                 elif args.child == "loop":
                     times, failed = measure_loop(args.lib, first, quality, args.threads, args.runs, 1, dictionary)
@@ -256,7 +273,8 @@ def child(args):
         json.dump(out, f)
 
 
-def run_child(args, what, classes, lib=None, lds=None, threads=1, limit=600, first_only=False, plain=False, long_items=False, quick_items=False):
+def run_child(args, what, classes, lib=None, lds=None, threads=1, limit=600, first_only=False, plain=False, long_items=False, quick_items=False,
+              quick_long_items=False):
     env = dict(os.environ)
     env.pop("BROTLI_MI355X_BATCH_LDS_BITS", None)
     if lds is not None:
@@ -265,6 +283,7 @@ def run_child(args, what, classes, lib=None, lds=None, threads=1, limit=600, fir
     cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--child", what, "--classes", ",".join(classes), "--lib", lib or args.lib,
            "--threads", str(threads), "--runs", str(args.runs), "--warmup", str(args.warmup), "--loop-items", str(args.loop_items), "--child-out", tmp, "--qualities", args.qualities,
            "--dictionary", str(args.dictionary)] + (["--first-only"] if first_only else []) + (["--plain"] if plain else []) + (["--long-items"] if long_items else []) + (["--quick-items"] if quick_items else [])
+    cmd += (["--quick-long-items"] if quick_long_items else []) + (["--quick-long-classes"] if args.quick_long_items else [])
     r = subprocess.run(cmd, env=env)
     if r.returncode != 0:
         raise SystemExit("batch_probe: %s (lds=%s, threads=%d) ended with status %d: nothing more is started" % (what, lds, threads, r.returncode))
@@ -338,7 +357,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--loop-items", type=int, default=256)
     ap.add_argument("--ab-rounds", type=int, default=3, help="how often the A/B alternates between the two settings")
-    ap.add_argument("--skip", default="", help="comma list of: headline, ab")
+    ap.add_argument("--skip", default="", help="comma list of: headline, ab, cpu, loop")
     ap.add_argument("--qualities", default="0,1", help="comma list of qualities")
     ap.add_argument("--rounds", type=int, default=1, help="how often this build and the parent's batch call alternate (qualities other than 0 and 1)")
     ap.add_argument("--only", default="", help="comma list of headline classes (default: all)")
@@ -346,6 +365,8 @@ def main():
     ap.add_argument("--dictionary", type=int, default=0, help="bytes of shared custom dictionary: measures BrotliMi355xCompressBatchWithDictionary")
     ap.add_argument("--long-items", action="store_true", help="this build through BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS")
     ap.add_argument("--quick-items", action="store_true", help="this build through BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS (--qualities 2,3,4)")
+    ap.add_argument("--quick-long-items", action="store_true", help="this build through routes QUICK_ITEMS | QUICK_LONG_ITEMS, the parent through QUICK_ITEMS (qualities 2,3,4 per class)")
+    ap.add_argument("--quick-long-classes", action="store_true", help="(child) only the qualities of QUICK_LONG_QUALITIES")
     ap.add_argument("--plain", action="store_true", help="(child) the plain call although a dictionary size is given")
     ap.add_argument("--child", default=None)
     ap.add_argument("--classes", default="")
@@ -364,11 +385,17 @@ def main():
         with open(args.out, "w") as f:
             json.dump(doc, f, indent=1)
 
-    headline = [c for c in (args.only.split(",") if args.only else (QUICK_HEADLINE if args.quick_items else HEADLINE)) if c in CLASSES]
+    if args.quick_long_items:
+        args.quick_items = True
+        args.qualities = "2,3,4"
+    headline = [c for c in (args.only.split(",") if args.only else (list(QUICK_LONG_QUALITIES) if args.quick_long_items else QUICK_HEADLINE if args.quick_items else HEADLINE)) if c in CLASSES]
     if args.long_items:
         doc["what"] = "BrotliMi355xCompressBatchEx(BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS) vs the parent commit's batch call and 4-thread loop vs the oracle on one CPU core; lgwin 22"
     if args.quick_items:
         doc["what"] = "BrotliMi355xCompressBatchEx(BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS) vs the parent commit's batch call and 4-thread loop vs the oracle on one CPU core; lgwin 22"
+    if args.quick_long_items:
+        doc["what"] = ("BrotliMi355xCompressBatchEx(BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS | BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS) vs the parent commit's "
+                       "BrotliMi355xCompressBatchEx(BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS), there one by one; items of two to four input blocks; lgwin 22")
     if args.dictionary:
         return main_dictionary(args, doc, save, [c for c in ("4096x4KiB", "1024x64KiB") if not args.only or c in args.only.split(",")])
     fragment_qualities = set(args.qualities.split(",")) <= {"0", "1"}
@@ -393,7 +420,7 @@ def main():
     if "headline" not in skip:
         rows = {}
         for rnd in range(args.rounds):
-            for row in run_child(args, "batch", headline, limit=900, long_items=args.long_items, quick_items=args.quick_items):
+            for row in run_child(args, "batch", headline, limit=900, long_items=args.long_items, quick_items=args.quick_items, quick_long_items=args.quick_long_items):
                 this = {k: row[k] for k in ("median_ms", "min_ms", "max_ms", "spread_pct", "runs")}
                 if rnd == 0:
                     rows[key(row)] = {"items": row["items"], "bytes": row["bytes"], "compressed_bytes": row["compressed_bytes"], "batch_info": row["batch_info"], "batch": this}
@@ -402,17 +429,18 @@ def main():
             save()
             if args.parent_lib and not fragment_qualities:
                 # the parent's own batch call: a loop over its one-shot path on the calling thread
-                for row in run_child(args, "batch", headline, lib=os.path.abspath(args.parent_lib), limit=900, first_only=True):
+                # (--quick-long-items: through the quick route, which takes these items one by one there as well)
+                for row in run_child(args, "batch", headline, lib=os.path.abspath(args.parent_lib), limit=900, first_only=True, quick_items=args.quick_long_items):
                     scale = row["items"] / row["measured_items"]
                     rows[key(row)].setdefault("parent_batch_rounds", []).append({"median_ms_scaled": round(row["median_ms"] * scale, 3), "min_ms_scaled": round(row["min_ms"] * scale, 3),
                                                                                "max_ms_scaled": round(row["max_ms"] * scale, 3), "spread_pct": row["spread_pct"], "measured_items": row["measured_items"]})
                 save()
-        for row in run_child(args, "cpu", headline):
+        for row in ([] if "cpu" in skip else run_child(args, "cpu", headline)):
             scale = row["items"] / row["measured_items"]
             rows[key(row)]["cpu_one_core"] = {"median_ms_scaled": round(row["median_ms"] * scale, 3), "measured_items": row["measured_items"], "spread_pct": row["spread_pct"]}
         save()
         for threads in (1, 4):
-            if not args.parent_lib:
+            if not args.parent_lib or "loop" in skip:
                 for v in rows.values():
                     v["loop_%dt" % threads] = "not measured"
                 continue
@@ -426,7 +454,7 @@ def main():
             b = v["batch"]["median_ms"]
             loops = [v[n]["median_ms_scaled"] for n in ("loop_1t", "loop_4t") if isinstance(v.get(n), dict)]
             v["batch_MBps"] = round(v["bytes"] / 1e3 / b, 1)
-            v["cpu_over_batch"] = round(v["cpu_one_core"]["median_ms_scaled"] / b, 3)
+            v["cpu_over_batch"] = round(v["cpu_one_core"]["median_ms_scaled"] / b, 3) if "cpu_one_core" in v else "not measured"
             v["better_loop_over_batch"] = round(min(loops) / b, 2) if loops else "not measured"
             if v.get("parent_batch_rounds"):
                 parent = v["parent_batch_rounds"]
