@@ -49,12 +49,16 @@ EncoderParams DictionaryItemParams(const EncoderParams& user, size_t input_size)
 
 uint32_t Padded(uint32_t bytes) { return ((bytes + 63u) & ~63u) + 64u; }  // at least 64 zero bytes behind every item
 
+// what every side-by-side route asks of the caller's parameters, whatever its qualities and sizes
+bool PlainStreamParams(const EncoderParams& user) {
+  return !user.large_window && !(user.catable || user.appendable || user.bare_stream || user.byte_align || user.magic_number);
+}
+
 }  // namespace
 
 bool BatchGreedyEligible(const EncoderParams& user, size_t input_size) {
   if (input_size == 0) return false;  // (answered without an encoder)
-  if (user.quality < 5 || user.quality > 8 || user.lgwin < 17 || user.lgwin > 24 || user.large_window) return false;
-  if (user.catable || user.appendable || user.bare_stream || user.byte_align || user.magic_number) return false;
+  if (user.quality < 5 || user.quality > 8 || user.lgwin < 17 || user.lgwin > 24 || !PlainStreamParams(user)) return false;
   if (input_size > ((size_t)1 << 24)) return false;
   const EncoderParams p = ItemParams(user, input_size);
   return p.hasher.type == 5 && input_size <= ((size_t)1 << p.lgblock);
@@ -62,8 +66,7 @@ bool BatchGreedyEligible(const EncoderParams& user, size_t input_size) {
 
 bool BatchDictionaryEligible(const EncoderParams& user, size_t dict_size, size_t input_size) {
   if (input_size == 0 || input_size > 65536 || dict_size < 2 || dict_size > 65536) return false;
-  if (user.quality < 5 || user.quality > 8 || user.lgwin < 17 || user.lgwin > 24 || user.large_window) return false;
-  if (user.catable || user.appendable || user.bare_stream || user.byte_align || user.magic_number) return false;
+  if (user.quality < 5 || user.quality > 8 || user.lgwin < 17 || user.lgwin > 24 || !PlainStreamParams(user)) return false;
   // (dictionary + item stay below the ring-buffer size, 1 << (lgwin + 1): no masked entry differs from its position)
   const EncoderParams p = DictionaryItemParams(user, input_size);
   return p.hasher.type == 5 && p.hasher.block_bits <= 7 && input_size <= ((size_t)1 << p.lgblock) && dict_size <= ((size_t)1 << p.lgwin) - 16;
@@ -71,8 +74,7 @@ bool BatchDictionaryEligible(const EncoderParams& user, size_t dict_size, size_t
 
 bool BatchLongEligible(const EncoderParams& user, size_t input_size) {
   if (input_size > kBatchLongBytes) return false;
-  if (user.quality < 5 || user.quality > 8 || user.lgwin < 17 || user.lgwin > 24 || user.large_window) return false;
-  if (user.catable || user.appendable || user.bare_stream || user.byte_align || user.magic_number) return false;
+  if (user.quality < 5 || user.quality > 8 || user.lgwin < 17 || user.lgwin > 24 || !PlainStreamParams(user)) return false;
   // (kBatchLongBytes is the ring-buffer size at lgwin 17 and below the size hint that selects another hasher)
   const EncoderParams p = ItemParams(user, input_size);
   return p.hasher.type == 5 && p.hasher.block_bits <= 7 && input_size > ((size_t)1 << p.lgblock) &&
@@ -108,23 +110,282 @@ Lz77Params ChainParams(const EncoderParams& p) {
   return P;
 }
 
-// p: the parameters the items share, finalized.  dict == nullptr: the plain call.
+// ---- the steps of a group: every route (CompressGroups, Batch*Compress) composes them in the same order.
+// the limits of a group, read once per process, like BROTLI_MI355X_FRAGMENT_BATCH
+struct BatchLimits {
+  size_t group_items, group_bytes;
+  size_t tables;  // 0: TablesMax works it out
+};
+const BatchLimits& Limits() {
+  static const BatchLimits limits{std::max<size_t>(1, EnvSize("BROTLI_MI355X_BATCH_GROUP_ITEMS", 4096)),
+                                  std::max<size_t>(1, EnvSize("BROTLI_MI355X_BATCH_GROUP_BYTES", (size_t)64 << 20)),
+                                  EnvSize("BROTLI_MI355X_BATCH_TABLES", 0)};
+  return limits;
+}
+// a table is 1 MiB at quality 5 and 16 MiB at quality 8, 256 KiB (H2, H3) or 512 KiB (H4) at qualities 2 .. 4: as many as the
+// parse kernel keeps resident (256 CUs x 4 SIMDs x 4 wavefronts) within 8 GiB
+size_t TablesMax(size_t table_bytes) {
+  return Limits().tables ? Limits().tables : std::max<size_t>(1, std::min<size_t>(4096, ((size_t)8 << 30) / table_bytes));
+}
+
+// Qualities 2 .. 4: the hasher and the search parameters of the chains, in a job that has no group yet (QuickGroupJob)
+QuickBatchJob QuickChains(const EncoderParams& p) {
+  QuickBatchJob J{};
+  QuickJob& Q = J.Q;  // as Lz77Stage::Setup fills it in
+  Q.kind = (uint32_t)p.hasher.type;
+  Q.bucket_bits = Q.kind == 4 ? 17 : 16;
+  Q.sweep = Q.kind == 2 ? 1 : (Q.kind == 3 ? 2 : 4);
+  Q.hash_len = 5;
+  Q.use_dictionary = (p.use_dictionary && (Q.kind == 2 || Q.kind == 4)) ? 1 : 0;
+  J.P = ChainParams(p);  // (ring_mask: the items' own ring buffer, which an item of three blocks outruns at lgwin <= 14)
+  J.P.hasher_kind = 6;  // (what Lz77Stage::Setup gives every hasher but H5 and H9; br_quick_block does not look at it)
+  J.P.htl = 8;  // HashTypeLength of every BasicHasher
+  J.P.use_dictionary = Q.use_dictionary;
+  J.P.dict_break = 0;
+  return J;
+}
+size_t QuickTableBytes(const QuickBatchJob& J) { return (size_t)quick_table_words(J.Q) * 4; }
+
+// the page-locked arrays of a call: they live across its groups and grow through resize_discard only
+struct CallArrays {
+  PinnedArray<uint8_t> staging;
+  PinnedArray<BatchItem> items;
+  PinnedArray<uint32_t> order, offsets, starts;
+  PinnedArray<BatchRecord> records;
+  PinnedArray<BatchLongRecord> long_records;
+};
+// one group, staged and uploaded: the caller's items [first, last)
+struct Group {
+  CallArrays* A;
+  DevBlocks mem;  // everything the group has on the device: freed with the group, also when a step throws
+  size_t first, last;
+  uint32_t n;
+  size_t padded;     // bytes of the padded text
+  size_t packed_at;  // where the packed text starts in `uploaded`
+  size_t cmd_slots;
+  uint32_t tables;
+  uint8_t* uploaded;  // on the device, like the two below
+  BatchItem* items_dev;
+  uint32_t* order_dev;
+};
+// D: the bytes of the call's dictionary (0: none), which go in front of every item in the padded text
+void StageGroup(size_t first, size_t count, const uint8_t* const* inputs, const size_t* sizes, uint32_t D, size_t tables_max,
+                CallArrays* arrays, Group* g) {
+  CallArrays& A = *arrays;
+  const uint32_t dict_room = (D + 63u) & ~63u;
+  // (the limit counts the dictionary copies of the padded text: scratch -- keys and flags -- grows with them)
+  size_t last = first, padded = 0, packed = 0;
+  while (last < count && last - first < Limits().group_items &&
+         (last == first || packed + (last - first + 1) * (size_t)D + sizes[last] <= Limits().group_bytes)) {
+    padded += dict_room + Padded((uint32_t)sizes[last]);
+    packed += sizes[last];
+    ++last;
+  }
+  const uint32_t n = (uint32_t)(last - first);
+  // one page-locked buffer, one upload: [padded text | 64 | packed text | 64]; with a dictionary the packed text alone -- the
+  // padded text, dictionary | item per item, is laid out on the device
+  const size_t packed_at = D != 0 ? 0 : padded + 64;
+  const size_t text_bytes = packed_at + packed + 64;
+  A.staging.resize_discard(text_bytes);
+  memset(A.staging.data(), 0, text_bytes);
+  A.items.resize_discard(n);
+  A.order.resize_discard(n);
+  A.starts.resize_discard(n);
+  uint32_t off = 0, start = 0, cmd_base = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t bytes = (uint32_t)sizes[first + i];
+    const uint32_t cmd_cap = bytes / 2 + 8;
+    off += dict_room;
+    if (D == 0) memcpy(A.staging.data() + off, inputs[first + i], bytes);
+    memcpy(A.staging.data() + packed_at + start, inputs[first + i], bytes);
+    A.items[i] = BatchItem{off, bytes, cmd_base, cmd_cap};
+    A.starts[i] = start;
+    off += Padded(bytes);
+    start += bytes;
+    cmd_base += cmd_cap;
+    A.order[i] = i;
+  }
+  // largest first: the large items of a group run as long as a lone wavefront takes, the small ones fill in behind them
+  std::stable_sort(A.order.data(), A.order.data() + n, [&](uint32_t a, uint32_t b) { return A.items[a].bytes > A.items[b].bytes; });
+
+  g->A = arrays;
+  g->first = first;
+  g->last = last;
+  g->n = n;
+  g->padded = padded;
+  g->packed_at = packed_at;
+  g->cmd_slots = (size_t)A.items[n - 1].cmd_base + A.items[n - 1].cmd_cap;
+  g->tables = (uint32_t)std::min<size_t>(tables_max, n);
+  g->uploaded = g->mem.uninit<uint8_t>(text_bytes);
+  dev_h2d_bulk(g->uploaded, A.staging.data(), text_bytes);
+  g->items_dev = g->mem.uninit<BatchItem>((size_t)n * sizeof(BatchItem));
+  dev_h2d(g->items_dev, A.items.data(), (size_t)n * sizeof(BatchItem));
+  g->order_dev = g->mem.uninit<uint32_t>((size_t)n * 4);
+  dev_h2d(g->order_dev, A.order.data(), (size_t)n * 4);
+}
+
+// the key pass over the group's padded text and the job of an H5 parse launch; `records` and `dict` are the caller's to set
+BatchParseJob GreedyJob(const EncoderParams& p, const Lz77Params& P, Group& g, uint8_t* text) {
+  const size_t keys_per_table = (size_t)1 << p.hasher.bucket_bits;
+  Lz77Buffers B{};
+  B.text = text;
+  B.keys = g.mem.uninit<uint16_t>(g.padded * 2 + 256);
+  B.changed_count = g.mem.zeroed<uint32_t>(64);
+  Lz77Params PK = P;
+  PK.total_bytes = (uint32_t)g.padded;  // (the last item's padding gives every position four bytes to hash)
+  lz77_compute_keys(PK, B);
+
+  BatchParseJob J{};
+  J.P = P;
+  J.text = text;
+  J.keys = B.keys;
+  J.flags = g.mem.uninit<uint8_t>(g.padded + 64);
+  J.slabs = g.mem.uninit<Command>(g.cmd_slots * sizeof(Command) + 64);
+  J.items = g.items_dev;
+  J.order = g.order_dev;
+  J.n_items = g.n;
+  J.tables = g.tables;
+  J.num = g.mem.uninit<uint16_t>((size_t)g.tables * keys_per_table * 2 + 64);
+  J.buckets = g.mem.uninit<uint32_t>(((size_t)g.tables * keys_per_table << p.hasher.block_bits) * 4 + 64);
+  J.counter = g.mem.zeroed<uint32_t>(64);
+  return J;
+}
+
+// the job of a BasicHasher parse launch: no key pass and no flags -- a BasicHasher hashes from the text -- and a table of
+// quick_table_words per wavefront; `records` is the caller's to set
+QuickBatchJob QuickGroupJob(const QuickBatchJob& chains, Group& g) {
+  QuickBatchJob J = chains;
+  J.Q.table = g.mem.uninit<uint32_t>((size_t)g.tables * QuickTableBytes(J) + 64);  // (every chain zeroes its table in front of every item)
+  J.text = g.uploaded;
+  J.slabs = g.mem.uninit<Command>(g.cmd_slots * sizeof(Command) + 64);
+  J.items = g.items_dev;
+  J.order = g.order_dev;
+  J.n_items = g.n;
+  J.tables = g.tables;
+  J.counter = g.mem.zeroed<uint32_t>(64);
+  return J;
+}
+// ... and what the gathers want of it: br_raw_command / br_finish_command are those of qualities 5 .. 8, and they read the
+// slabs, the items, the records and the distance parameters
+BatchParseJob GatherJobOf(const QuickBatchJob& J) {
+  BatchParseJob G{};
+  G.P = J.P;
+  G.slabs = J.slabs;
+  G.items = J.items;
+  G.n_items = J.n_items;
+  G.records = J.records;
+  return G;
+}
+
+// (cannot happen: a copy is at least two bytes long)
+void CheckSlab(uint32_t overflow) {
+  if (overflow) throw std::runtime_error("brotli_mi355x: a batch chain ran out of its command slab");
+}
+
+// One-block items, from the records on: the gather offsets and one meta-block entry per item (one small round trip), the command
+// gather, one meta-block per item, and the streams of the items the reference does not fail on.  J: the parse job, or what
+// GatherJobOf leaves of it.
+void FinishOneBlockItems(const EncoderParams& p, const BatchParseJob& J, Group& g, std::vector<std::vector<uint8_t>>* streams,
+                         std::vector<uint8_t>* reference_fails) {
+  CallArrays& A = *g.A;
+  A.records.resize_discard(g.n);
+  dev_d2h(A.records.data(), J.records, (size_t)g.n * sizeof(BatchRecord));
+  A.offsets.resize_discard(g.n);
+  std::vector<BatchStreamItem> mbs(g.n);
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < g.n; ++i) {
+    const BatchRecord& r = A.records[i];
+    CheckSlab(r.overflow);
+    A.offsets[i] = (uint32_t)total;
+    mbs[i].start = A.starts[i];
+    mbs[i].bytes = A.items[i].bytes;
+    mbs[i].cmd_offset = (uint32_t)total;
+    mbs[i].n_cmds = r.n_cmds;
+    mbs[i].n_lits = r.n_lits;
+    mbs[i].uncompressed = r.uncompressed;
+    total += r.n_cmds;
+    if (r.bad_commands != 0 && reference_fails) (*reference_fails)[g.first + i] = 1;
+  }
+  uint32_t* offsets_dev = g.mem.uninit<uint32_t>((size_t)g.n * 4);
+  dev_h2d(offsets_dev, A.offsets.data(), (size_t)g.n * 4);
+  Command* cmds = g.mem.uninit<Command>((size_t)(total + 16) * sizeof(Command));
+  lz77_batch_gather(J, offsets_dev, cmds);
+  std::vector<uint8_t> out;
+  EncodeBatchMetaBlocks(p, g.uploaded + g.packed_at, cmds, (uint32_t)total, &mbs, &out);
+  for (uint32_t i = 0; i < g.n; ++i)
+    if (A.records[i].bad_commands == 0) (*streams)[g.first + i].assign(out.begin() + (ptrdiff_t)mbs[i].out_byte, out.begin() + (ptrdiff_t)(mbs[i].out_byte + mbs[i].out_bytes));
+}
+
+// Items of several blocks, from the records on: the same with a gather offset and an entry per meta-block.  A record is taken as
+// far as its meta-blocks follow each other inside the item: one that would pass the item's end stops the walk.  (For the H5 kernel
+// that test changes no outcome: behind such a meta-block `at` cannot come back to the item's size, and the same error is thrown.)
+// An item's first entry says where its stream lies, or that a meta-block of it took the size fallback (`demoted`: no stream).
+void FinishLongItems(const EncoderParams& p, const BatchParseJob& J, const BatchLongRecord* records_dev, const uint8_t* const* inputs, Group& g,
+                     std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* demoted) {
+  CallArrays& A = *g.A;
+  A.long_records.resize_discard(g.n);
+  dev_d2h(A.long_records.data(), records_dev, (size_t)g.n * sizeof(BatchLongRecord));
+  A.offsets.resize_discard((size_t)g.n * kBatchLongBlocks);
+  std::vector<BatchStreamItem> mbs;
+  std::vector<uint32_t> first_mb(g.n);
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < g.n; ++i) {
+    const BatchLongRecord& r = A.long_records[i];
+    const BatchItem& item = A.items[i];
+    CheckSlab(r.overflow);
+    uint32_t at = 0, cmd_at = 0;
+    first_mb[i] = (uint32_t)mbs.size();
+    for (uint32_t m = 0; m < kBatchLongBlocks; ++m) A.offsets[(size_t)i * kBatchLongBlocks + m] = 0;
+    for (uint32_t m = 0; m < r.n_mb && m < kBatchLongBlocks; ++m) {
+      const BatchLongMetaBlock& mb = r.mb[m];
+      if (mb.start != at || mb.bytes == 0 || mb.bytes > item.bytes - at || mb.first_cmd != cmd_at) break;
+      A.offsets[(size_t)i * kBatchLongBlocks + m] = (uint32_t)total;
+      BatchStreamItem e{};
+      e.start = A.starts[i] + mb.start;
+      e.bytes = mb.bytes;
+      e.cmd_offset = (uint32_t)total;
+      e.n_cmds = mb.n_cmds + (mb.trailing != 0 ? 1u : 0u);
+      e.n_lits = mb.n_lits;
+      e.uncompressed = mb.uncompressed;
+      e.follows = m != 0;
+      e.more = m + 1 != r.n_mb;
+      e.item_bytes = item.bytes;
+      if (m != 0) {
+        e.prev_byte = inputs[g.first + i][mb.start - 1];
+        e.prev_byte2 = inputs[g.first + i][mb.start - 2];
+      }
+      mbs.push_back(e);
+      total += e.n_cmds;
+      at += mb.bytes;
+      cmd_at += mb.n_cmds;
+    }
+    if (at != item.bytes || cmd_at > item.cmd_cap) throw std::runtime_error("brotli_mi355x: a batch chain left meta-block records that do not cover its item");
+  }
+  uint32_t* offsets_dev = g.mem.uninit<uint32_t>((size_t)g.n * kBatchLongBlocks * 4);
+  dev_h2d(offsets_dev, A.offsets.data(), (size_t)g.n * kBatchLongBlocks * 4);
+  Command* cmds = g.mem.uninit<Command>((size_t)(total + 16) * sizeof(Command));
+  lz77_batch_gather_long(J, records_dev, offsets_dev, cmds);
+  std::vector<uint8_t> out;
+  EncodeBatchMetaBlocks(p, g.uploaded + g.packed_at, cmds, (uint32_t)total, &mbs, &out);
+  for (uint32_t i = 0; i < g.n; ++i) {
+    const BatchStreamItem& e = mbs[first_mb[i]];
+    if (e.demoted) {
+      (*demoted)[g.first + i] = 1;
+      continue;
+    }
+    (*streams)[g.first + i].assign(out.begin() + (ptrdiff_t)e.out_byte, out.begin() + (ptrdiff_t)(e.out_byte + e.out_bytes));
+  }
+}
+
+// Qualities 5 .. 8, items of one block.  p: the parameters the items share, finalized.  dict == nullptr: the plain call.
 void CompressGroups(const EncoderParams& p, const uint8_t* dict, uint32_t D, size_t count, const uint8_t* const* inputs, const size_t* sizes,
                     std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* reference_fails, uint32_t* groups) {
-  // read once per process, like BROTLI_MI355X_FRAGMENT_BATCH
-  static const size_t group_items = std::max<size_t>(1, EnvSize("BROTLI_MI355X_BATCH_GROUP_ITEMS", 4096));
-  static const size_t group_bytes = std::max<size_t>(1, EnvSize("BROTLI_MI355X_BATCH_GROUP_BYTES", (size_t)64 << 20));
-  // a table is 1 MiB at quality 5 and 16 MiB at quality 8: as many as the parse kernel keeps resident (256 CUs x 4 SIMDs x 4
-  // wavefronts) within 8 GiB
-  static const size_t table_override = EnvSize("BROTLI_MI355X_BATCH_TABLES", 0);
   streams->assign(count, std::vector<uint8_t>());
   if (reference_fails) reference_fails->assign(count, 0);
   *groups = 0;
   if (count == 0) return;
   const size_t keys_per_table = (size_t)1 << p.hasher.bucket_bits;
-  const size_t table_bytes = keys_per_table * 2 + (keys_per_table << p.hasher.block_bits) * 4;
-  const size_t tables_max = table_override ? table_override : std::max<size_t>(1, std::min<size_t>(4096, ((size_t)8 << 30) / table_bytes));
-
+  const size_t tables_max = TablesMax(keys_per_table * 2 + (keys_per_table << p.hasher.block_bits) * 4);
   const Lz77Params P = ChainParams(p);
 
   // ---- the dictionary, once per call: its bytes on the device, and what the prepend leaves in a table (BatchDictImage)
@@ -160,573 +421,30 @@ void CompressGroups(const EncoderParams& p, const uint8_t* dict, uint32_t D, siz
     image.entries = entries;
     image.n_entries = n_entries;
   }
-  const uint32_t dict_room = (D + 63u) & ~63u;  // in front of every item in the padded text
 
-  PinnedArray<uint8_t> staging;
-  PinnedArray<BatchItem> items;
-  PinnedArray<uint32_t> order, offsets, starts;
-  PinnedArray<BatchRecord> records;
+  CallArrays A;
   size_t first = 0;
   while (first < count) {
-    // ---- the group: items [first, last)
-    // (the limit counts the dictionary copies of the padded text: scratch -- keys and flags -- grows with them)
-    size_t last = first, padded = 0, packed = 0;
-    while (last < count && last - first < group_items && (last == first || packed + (last - first + 1) * (size_t)D + sizes[last] <= group_bytes)) {
-      padded += dict_room + Padded((uint32_t)sizes[last]);
-      packed += sizes[last];
-      ++last;
-    }
-    const uint32_t n = (uint32_t)(last - first);
+    Group g;
+    StageGroup(first, count, inputs, sizes, D, tables_max, &A, &g);
     ++*groups;
-    // one page-locked buffer, one upload: [padded text | 64 | packed text | 64]; with a dictionary the packed text alone -- the
-    // padded text, dictionary | item per item, is laid out on the device
-    const size_t packed_at = D != 0 ? 0 : padded + 64;
-    const size_t text_bytes = packed_at + packed + 64;
-    staging.resize_discard(text_bytes);
-    memset(staging.data(), 0, text_bytes);
-    items.resize_discard(n);
-    order.resize_discard(n);
-    starts.resize_discard(n);
-    std::vector<BatchStreamItem> mbs(n);
-    {
-      uint32_t off = 0, start = 0, cmd_base = 0;
-      for (uint32_t i = 0; i < n; ++i) {
-        const uint32_t bytes = (uint32_t)sizes[first + i];
-        off += dict_room;
-        if (D == 0) memcpy(staging.data() + off, inputs[first + i], bytes);
-        memcpy(staging.data() + packed_at + start, inputs[first + i], bytes);
-        items[i] = BatchItem{off, bytes, cmd_base, bytes / 2 + 8};
-        starts[i] = start;
-        mbs[i].start = start;
-        mbs[i].bytes = bytes;
-        off += Padded(bytes);
-        start += bytes;
-        cmd_base += bytes / 2 + 8;
-        order[i] = i;
-      }
-      // largest first: the large items of a group run as long as a lone wavefront takes, the small ones fill in behind them
-      std::stable_sort(order.data(), order.data() + n, [&](uint32_t a, uint32_t b) { return items[a].bytes > items[b].bytes; });
-    }
-    const size_t cmd_slots = (size_t)items[n - 1].cmd_base + items[n - 1].cmd_cap;
-    const uint32_t tables = (uint32_t)std::min<size_t>(tables_max, n);
-
-    DevBlocks mem;
-    uint8_t* uploaded = mem.uninit<uint8_t>(text_bytes);
-    dev_h2d_bulk(uploaded, staging.data(), text_bytes);
-    BatchItem* items_dev = mem.uninit<BatchItem>((size_t)n * sizeof(BatchItem));
-    dev_h2d(items_dev, items.data(), (size_t)n * sizeof(BatchItem));
-    uint8_t* text = uploaded;
+    uint8_t* text = g.uploaded;
     if (D != 0) {
-      text = mem.zeroed<uint8_t>(padded + 64);
-      uint32_t* starts_dev = mem.uninit<uint32_t>((size_t)n * 4);
-      dev_h2d(starts_dev, starts.data(), (size_t)n * 4);
-      lz77_batch_dict_text(dict_shifted, D, uploaded, starts_dev, items_dev, n, text);
+      text = g.mem.zeroed<uint8_t>(g.padded + 64);
+      uint32_t* starts_dev = g.mem.uninit<uint32_t>((size_t)g.n * 4);
+      dev_h2d(starts_dev, A.starts.data(), (size_t)g.n * 4);
+      lz77_batch_dict_text(dict_shifted, D, g.uploaded, starts_dev, g.items_dev, g.n, text);
     }
-    Lz77Buffers B{};
-    B.text = text;
-    B.keys = mem.uninit<uint16_t>(padded * 2 + 256);
-    B.changed_count = mem.zeroed<uint32_t>(64);
-    B.dict_items = nullptr;
-    B.run_end = nullptr;
-    Lz77Params PK = P;
-    PK.total_bytes = (uint32_t)padded;  // (the last item's padding gives every position four bytes to hash)
-    lz77_compute_keys(PK, B);
-
-    BatchParseJob J{};
-    J.P = P;
-    J.text = text;
-    J.keys = B.keys;
-    J.flags = mem.uninit<uint8_t>(padded + 64);
-    J.slabs = mem.uninit<Command>(cmd_slots * sizeof(Command) + 64);
-    uint32_t* order_dev = mem.uninit<uint32_t>((size_t)n * 4);
-    dev_h2d(order_dev, order.data(), (size_t)n * 4);
-    J.items = items_dev;
-    J.order = order_dev;
-    J.n_items = n;
-    J.tables = tables;
-    J.num = mem.uninit<uint16_t>((size_t)tables * keys_per_table * 2 + 64);
-    J.buckets = mem.uninit<uint32_t>(((size_t)tables * keys_per_table << p.hasher.block_bits) * 4 + 64);
-    J.counter = mem.zeroed<uint32_t>(64);
-    J.records = mem.uninit<BatchRecord>((size_t)n * sizeof(BatchRecord));
+    BatchParseJob J = GreedyJob(p, P, g, text);
+    J.records = g.mem.uninit<BatchRecord>((size_t)g.n * sizeof(BatchRecord));
     J.dict = image;
     lz77_batch_parse(J);
-    records.resize_discard(n);
-    dev_d2h(records.data(), J.records, (size_t)n * sizeof(BatchRecord));
-    // ---- command gather: the offsets from the per-item records (one small round trip)
-    offsets.resize_discard(n);
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-      if (records[i].overflow) throw std::runtime_error("brotli_mi355x: a batch chain ran out of its command slab");
-      offsets[i] = (uint32_t)total;
-      mbs[i].cmd_offset = (uint32_t)total;
-      mbs[i].n_cmds = records[i].n_cmds;
-      mbs[i].n_lits = records[i].n_lits;
-      mbs[i].uncompressed = records[i].uncompressed;
-      total += records[i].n_cmds;
-      if (records[i].bad_commands != 0 && reference_fails) (*reference_fails)[first + i] = 1;
-    }
-    uint32_t* offsets_dev = mem.uninit<uint32_t>((size_t)n * 4);
-    dev_h2d(offsets_dev, offsets.data(), (size_t)n * 4);
-    Command* cmds = mem.uninit<Command>((size_t)(total + 16) * sizeof(Command));
-    lz77_batch_gather(J, offsets_dev, cmds);
-    // ---- one meta-block per item
-    std::vector<uint8_t> out;
-    EncodeBatchMetaBlocks(p, uploaded + packed_at, cmds, (uint32_t)total, &mbs, &out);
-    for (uint32_t i = 0; i < n; ++i)
-      if (records[i].bad_commands == 0) (*streams)[first + i].assign(out.begin() + (ptrdiff_t)mbs[i].out_byte, out.begin() + (ptrdiff_t)(mbs[i].out_byte + mbs[i].out_bytes));
-    first = last;
-  }
-}
-
-// Items of several blocks: the plan of CompressGroups with up to kBatchLongBlocks meta-blocks per item.
-void CompressLongGroups(const EncoderParams& p, size_t count, const uint8_t* const* inputs, const size_t* sizes,
-                        std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* demoted, uint32_t* groups) {
-  static const size_t group_items = std::max<size_t>(1, EnvSize("BROTLI_MI355X_BATCH_GROUP_ITEMS", 4096));
-  static const size_t group_bytes = std::max<size_t>(1, EnvSize("BROTLI_MI355X_BATCH_GROUP_BYTES", (size_t)64 << 20));
-  static const size_t table_override = EnvSize("BROTLI_MI355X_BATCH_TABLES", 0);
-  streams->assign(count, std::vector<uint8_t>());
-  demoted->assign(count, 0);
-  *groups = 0;
-  if (count == 0) return;
-  const size_t keys_per_table = (size_t)1 << p.hasher.bucket_bits;
-  const size_t table_bytes = keys_per_table * 2 + (keys_per_table << p.hasher.block_bits) * 4;
-  const size_t tables_max = table_override ? table_override : std::max<size_t>(1, std::min<size_t>(4096, ((size_t)8 << 30) / table_bytes));
-  const Lz77Params P = ChainParams(p);
-
-  PinnedArray<uint8_t> staging;
-  PinnedArray<BatchItem> items;
-  PinnedArray<uint32_t> order, offsets;
-  PinnedArray<BatchLongRecord> records;
-  size_t first = 0;
-  while (first < count) {
-    size_t last = first, padded = 0, packed = 0;
-    while (last < count && last - first < group_items && (last == first || packed + sizes[last] <= group_bytes)) {
-      padded += Padded((uint32_t)sizes[last]);
-      packed += sizes[last];
-      ++last;
-    }
-    const uint32_t n = (uint32_t)(last - first);
-    ++*groups;
-    // one page-locked buffer, one upload: [padded text | 64 | packed text | 64]
-    const size_t packed_at = padded + 64;
-    const size_t text_bytes = packed_at + packed + 64;
-    staging.resize_discard(text_bytes);
-    memset(staging.data(), 0, text_bytes);
-    items.resize_discard(n);
-    order.resize_discard(n);
-    std::vector<uint32_t> starts(n);
-    {
-      uint32_t off = 0, start = 0, cmd_base = 0;
-      for (uint32_t i = 0; i < n; ++i) {
-        const uint32_t bytes = (uint32_t)sizes[first + i];
-        memcpy(staging.data() + off, inputs[first + i], bytes);
-        memcpy(staging.data() + packed_at + start, inputs[first + i], bytes);
-        items[i] = BatchItem{off, bytes, cmd_base, bytes / 2 + 8};
-        starts[i] = start;
-        off += Padded(bytes);
-        start += bytes;
-        cmd_base += bytes / 2 + 8;
-        order[i] = i;
-      }
-      std::stable_sort(order.data(), order.data() + n, [&](uint32_t a, uint32_t b) { return items[a].bytes > items[b].bytes; });
-    }
-    const size_t cmd_slots = (size_t)items[n - 1].cmd_base + items[n - 1].cmd_cap;
-    const uint32_t tables = (uint32_t)std::min<size_t>(tables_max, n);
-
-    DevBlocks mem;
-    uint8_t* uploaded = mem.uninit<uint8_t>(text_bytes);
-    dev_h2d_bulk(uploaded, staging.data(), text_bytes);
-    BatchItem* items_dev = mem.uninit<BatchItem>((size_t)n * sizeof(BatchItem));
-    dev_h2d(items_dev, items.data(), (size_t)n * sizeof(BatchItem));
-    Lz77Buffers B{};
-    B.text = uploaded;
-    B.keys = mem.uninit<uint16_t>(padded * 2 + 256);
-    B.changed_count = mem.zeroed<uint32_t>(64);
-    B.dict_items = nullptr;
-    B.run_end = nullptr;
-    Lz77Params PK = P;
-    PK.total_bytes = (uint32_t)padded;  // (the last item's padding gives every position four bytes to hash)
-    lz77_compute_keys(PK, B);
-
-    BatchParseJob J{};
-    J.P = P;
-    J.text = uploaded;
-    J.keys = B.keys;
-    J.flags = mem.uninit<uint8_t>(padded + 64);
-    J.slabs = mem.uninit<Command>(cmd_slots * sizeof(Command) + 64);
-    uint32_t* order_dev = mem.uninit<uint32_t>((size_t)n * 4);
-    dev_h2d(order_dev, order.data(), (size_t)n * 4);
-    J.items = items_dev;
-    J.order = order_dev;
-    J.n_items = n;
-    J.tables = tables;
-    J.num = mem.uninit<uint16_t>((size_t)tables * keys_per_table * 2 + 64);
-    J.buckets = mem.uninit<uint32_t>(((size_t)tables * keys_per_table << p.hasher.block_bits) * 4 + 64);
-    J.counter = mem.zeroed<uint32_t>(64);
-    J.records = nullptr;
-    BatchLongRecord* records_dev = mem.uninit<BatchLongRecord>((size_t)n * sizeof(BatchLongRecord));
-    lz77_batch_parse_long(J, records_dev);
-    records.resize_discard(n);
-    dev_d2h(records.data(), records_dev, (size_t)n * sizeof(BatchLongRecord));
-    // ---- command gather: the offsets per meta-block from the records (one small round trip)
-    offsets.resize_discard((size_t)n * kBatchLongBlocks);
-    std::vector<BatchStreamItem> mbs;
-    std::vector<uint32_t> first_mb(n);
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-      const BatchLongRecord& r = records[i];
-      if (r.overflow) throw std::runtime_error("brotli_mi355x: a batch chain ran out of its command slab");
-      uint32_t at = 0, cmd_at = 0;
-      first_mb[i] = (uint32_t)mbs.size();
-      for (uint32_t m = 0; m < kBatchLongBlocks; ++m) offsets[(size_t)i * kBatchLongBlocks + m] = 0;
-      for (uint32_t m = 0; m < r.n_mb && m < kBatchLongBlocks; ++m) {
-        const BatchLongMetaBlock& mb = r.mb[m];
-        if (mb.start != at || mb.bytes == 0 || mb.first_cmd != cmd_at) break;
-        offsets[(size_t)i * kBatchLongBlocks + m] = (uint32_t)total;
-        BatchStreamItem e{};
-        e.start = starts[i] + mb.start;
-        e.bytes = mb.bytes;
-        e.cmd_offset = (uint32_t)total;
-        e.n_cmds = mb.n_cmds + (mb.trailing != 0 ? 1u : 0u);
-        e.n_lits = mb.n_lits;
-        e.uncompressed = mb.uncompressed;
-        e.follows = m != 0;
-        e.more = m + 1 != r.n_mb;
-        e.item_bytes = items[i].bytes;
-        if (m != 0) {
-          e.prev_byte = inputs[first + i][mb.start - 1];
-          e.prev_byte2 = inputs[first + i][mb.start - 2];
-        }
-        mbs.push_back(e);
-        total += e.n_cmds;
-        at += mb.bytes;
-        cmd_at += mb.n_cmds;
-      }
-      if (at != items[i].bytes || cmd_at > items[i].cmd_cap) throw std::runtime_error("brotli_mi355x: a batch chain left meta-block records that do not cover its item");
-    }
-    uint32_t* offsets_dev = mem.uninit<uint32_t>((size_t)n * kBatchLongBlocks * 4);
-    dev_h2d(offsets_dev, offsets.data(), (size_t)n * kBatchLongBlocks * 4);
-    Command* cmds = mem.uninit<Command>((size_t)(total + 16) * sizeof(Command));
-    lz77_batch_gather_long(J, records_dev, offsets_dev, cmds);
-    std::vector<uint8_t> out;
-    EncodeBatchMetaBlocks(p, uploaded + packed_at, cmds, (uint32_t)total, &mbs, &out);
-    for (uint32_t i = 0; i < n; ++i) {
-      const BatchStreamItem& e = mbs[first_mb[i]];
-      if (e.demoted) {
-        (*demoted)[first + i] = 1;
-        continue;
-      }
-      (*streams)[first + i].assign(out.begin() + (ptrdiff_t)e.out_byte, out.begin() + (ptrdiff_t)(e.out_byte + e.out_bytes));
-    }
-    first = last;
-  }
-}
-
-// Qualities 2 .. 4 (batch_quick.h): the plan of CompressGroups without the key pass and the flags -- a BasicHasher hashes from
-// the text -- and with a table of quick_table_words per wavefront.
-void CompressQuickGroups(const EncoderParams& p, size_t count, const uint8_t* const* inputs, const size_t* sizes,
-                         std::vector<std::vector<uint8_t>>* streams, uint32_t* groups) {
-  static const size_t group_items = std::max<size_t>(1, EnvSize("BROTLI_MI355X_BATCH_GROUP_ITEMS", 4096));
-  static const size_t group_bytes = std::max<size_t>(1, EnvSize("BROTLI_MI355X_BATCH_GROUP_BYTES", (size_t)64 << 20));
-  static const size_t table_override = EnvSize("BROTLI_MI355X_BATCH_TABLES", 0);
-  streams->assign(count, std::vector<uint8_t>());
-  *groups = 0;
-  if (count == 0) return;
-  QuickJob Q;  // as Lz77Stage::Setup fills it in
-  Q.kind = (uint32_t)p.hasher.type;
-  Q.bucket_bits = Q.kind == 4 ? 17 : 16;
-  Q.sweep = Q.kind == 2 ? 1 : (Q.kind == 3 ? 2 : 4);
-  Q.hash_len = 5;
-  Q.use_dictionary = (p.use_dictionary && (Q.kind == 2 || Q.kind == 4)) ? 1 : 0;
-  // a table is 256 KiB (H2, H3) or 512 KiB (H4): as many as the parse kernel keeps resident, within 8 GiB
-  const size_t table_bytes = (size_t)quick_table_words(Q) * 4;
-  const size_t tables_max = table_override ? table_override : std::max<size_t>(1, std::min<size_t>(4096, ((size_t)8 << 30) / table_bytes));
-  Lz77Params P = ChainParams(p);
-  P.hasher_kind = 6;  // (what Lz77Stage::Setup gives every hasher but H5 and H9; br_quick_block does not look at it)
-  P.htl = 8;  // HashTypeLength of every BasicHasher
-  P.use_dictionary = Q.use_dictionary;
-  P.dict_break = 0;
-
-  PinnedArray<uint8_t> staging;
-  PinnedArray<BatchItem> items;
-  PinnedArray<uint32_t> order, offsets;
-  PinnedArray<BatchRecord> records;
-  size_t first = 0;
-  while (first < count) {
-    size_t last = first, padded = 0, packed = 0;
-    while (last < count && last - first < group_items && (last == first || packed + sizes[last] <= group_bytes)) {
-      padded += Padded((uint32_t)sizes[last]);
-      packed += sizes[last];
-      ++last;
-    }
-    const uint32_t n = (uint32_t)(last - first);
-    ++*groups;
-    // one page-locked buffer, one upload: [padded text | 64 | packed text | 64]
-    const size_t packed_at = padded + 64;
-    const size_t text_bytes = packed_at + packed + 64;
-    staging.resize_discard(text_bytes);
-    memset(staging.data(), 0, text_bytes);
-    items.resize_discard(n);
-    order.resize_discard(n);
-    std::vector<BatchStreamItem> mbs(n);
-    {
-      uint32_t off = 0, start = 0, cmd_base = 0;
-      for (uint32_t i = 0; i < n; ++i) {
-        const uint32_t bytes = (uint32_t)sizes[first + i];
-        memcpy(staging.data() + off, inputs[first + i], bytes);
-        memcpy(staging.data() + packed_at + start, inputs[first + i], bytes);
-        items[i] = BatchItem{off, bytes, cmd_base, bytes / 2 + 8};
-        mbs[i].start = start;
-        mbs[i].bytes = bytes;
-        off += Padded(bytes);
-        start += bytes;
-        cmd_base += bytes / 2 + 8;
-        order[i] = i;
-      }
-      // largest first: the large items of a group run as long as a lone wavefront takes, the small ones fill in behind them
-      std::stable_sort(order.data(), order.data() + n, [&](uint32_t a, uint32_t b) { return items[a].bytes > items[b].bytes; });
-    }
-    const size_t cmd_slots = (size_t)items[n - 1].cmd_base + items[n - 1].cmd_cap;
-    const uint32_t tables = (uint32_t)std::min<size_t>(tables_max, n);
-
-    DevBlocks mem;
-    uint8_t* uploaded = mem.uninit<uint8_t>(text_bytes);
-    dev_h2d_bulk(uploaded, staging.data(), text_bytes);
-    BatchItem* items_dev = mem.uninit<BatchItem>((size_t)n * sizeof(BatchItem));
-    dev_h2d(items_dev, items.data(), (size_t)n * sizeof(BatchItem));
-    uint32_t* order_dev = mem.uninit<uint32_t>((size_t)n * 4);
-    dev_h2d(order_dev, order.data(), (size_t)n * 4);
-
-    QuickBatchJob J{};
-    J.P = P;
-    J.Q = Q;
-    J.Q.table = mem.uninit<uint32_t>((size_t)tables * table_bytes + 64);  // (every chain zeroes its table in front of every item)
-    J.text = uploaded;
-    J.slabs = mem.uninit<Command>(cmd_slots * sizeof(Command) + 64);
-    J.items = items_dev;
-    J.order = order_dev;
-    J.n_items = n;
-    J.tables = tables;
-    J.counter = mem.zeroed<uint32_t>(64);
-    J.records = mem.uninit<BatchRecord>((size_t)n * sizeof(BatchRecord));
-    lz77_quick_batch_parse(J);
-    records.resize_discard(n);
-    dev_d2h(records.data(), J.records, (size_t)n * sizeof(BatchRecord));
-    // ---- command gather: the offsets from the per-item records (one small round trip)
-    offsets.resize_discard(n);
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-      if (records[i].overflow) throw std::runtime_error("brotli_mi355x: a batch chain ran out of its command slab");
-      offsets[i] = (uint32_t)total;
-      mbs[i].cmd_offset = (uint32_t)total;
-      mbs[i].n_cmds = records[i].n_cmds;
-      mbs[i].n_lits = records[i].n_lits;
-      mbs[i].uncompressed = records[i].uncompressed;
-      total += records[i].n_cmds;
-    }
-    uint32_t* offsets_dev = mem.uninit<uint32_t>((size_t)n * 4);
-    dev_h2d(offsets_dev, offsets.data(), (size_t)n * 4);
-    Command* cmds = mem.uninit<Command>((size_t)(total + 16) * sizeof(Command));
-    // (br_raw_command / br_finish_command are those of qualities 5 .. 8: the gather wants the slabs, the items, the records and
-    // the distance parameters)
-    BatchParseJob G{};
-    G.P = P;
-    G.slabs = J.slabs;
-    G.items = items_dev;
-    G.n_items = n;
-    G.records = J.records;
-    lz77_batch_gather(G, offsets_dev, cmds);
-    // ---- one meta-block per item
-    std::vector<uint8_t> out;
-    EncodeBatchMetaBlocks(p, uploaded + packed_at, cmds, (uint32_t)total, &mbs, &out);
-    for (uint32_t i = 0; i < n; ++i)
-      (*streams)[first + i].assign(out.begin() + (ptrdiff_t)mbs[i].out_byte, out.begin() + (ptrdiff_t)(mbs[i].out_byte + mbs[i].out_bytes));
-    first = last;
-  }
-}
-
-// Qualities 2 .. 4, items of two to kBatchLongBlocks input blocks (batch_quick.h): the staging, the tables and the launch shape of
-// CompressQuickGroups; the records, their validation, the gather, the meta-blocks per item and the demoted list of CompressLongGroups.
-void CompressQuickLongGroups(const EncoderParams& p, size_t count, const uint8_t* const* inputs, const size_t* sizes,
-                             std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* demoted, uint32_t* groups) {
-  static const size_t group_items = std::max<size_t>(1, EnvSize("BROTLI_MI355X_BATCH_GROUP_ITEMS", 4096));
-  static const size_t group_bytes = std::max<size_t>(1, EnvSize("BROTLI_MI355X_BATCH_GROUP_BYTES", (size_t)64 << 20));
-  static const size_t table_override = EnvSize("BROTLI_MI355X_BATCH_TABLES", 0);
-  streams->assign(count, std::vector<uint8_t>());
-  demoted->assign(count, 0);
-  *groups = 0;
-  if (count == 0) return;
-  QuickJob Q;  // as Lz77Stage::Setup fills it in
-  Q.kind = (uint32_t)p.hasher.type;
-  Q.bucket_bits = Q.kind == 4 ? 17 : 16;
-  Q.sweep = Q.kind == 2 ? 1 : (Q.kind == 3 ? 2 : 4);
-  Q.hash_len = 5;
-  Q.use_dictionary = (p.use_dictionary && (Q.kind == 2 || Q.kind == 4)) ? 1 : 0;
-  const size_t table_bytes = (size_t)quick_table_words(Q) * 4;
-  const size_t tables_max = table_override ? table_override : std::max<size_t>(1, std::min<size_t>(4096, ((size_t)8 << 30) / table_bytes));
-  Lz77Params P = ChainParams(p);  // (ring_mask: the items' own ring buffer, which an item of three blocks outruns at lgwin <= 14)
-  P.hasher_kind = 6;
-  P.htl = 8;
-  P.use_dictionary = Q.use_dictionary;
-  P.dict_break = 0;
-
-  PinnedArray<uint8_t> staging;
-  PinnedArray<BatchItem> items;
-  PinnedArray<uint32_t> order, offsets;
-  PinnedArray<BatchLongRecord> records;
-  size_t first = 0;
-  while (first < count) {
-    size_t last = first, padded = 0, packed = 0;
-    while (last < count && last - first < group_items && (last == first || packed + sizes[last] <= group_bytes)) {
-      padded += Padded((uint32_t)sizes[last]);
-      packed += sizes[last];
-      ++last;
-    }
-    const uint32_t n = (uint32_t)(last - first);
-    ++*groups;
-    // one page-locked buffer, one upload: [padded text | 64 | packed text | 64]
-    const size_t packed_at = padded + 64;
-    const size_t text_bytes = packed_at + packed + 64;
-    staging.resize_discard(text_bytes);
-    memset(staging.data(), 0, text_bytes);
-    items.resize_discard(n);
-    order.resize_discard(n);
-    std::vector<uint32_t> starts(n);
-    {
-      uint32_t off = 0, start = 0, cmd_base = 0;
-      for (uint32_t i = 0; i < n; ++i) {
-        const uint32_t bytes = (uint32_t)sizes[first + i];
-        memcpy(staging.data() + off, inputs[first + i], bytes);
-        memcpy(staging.data() + packed_at + start, inputs[first + i], bytes);
-        items[i] = BatchItem{off, bytes, cmd_base, bytes / 2 + 8};
-        starts[i] = start;
-        off += Padded(bytes);
-        start += bytes;
-        cmd_base += bytes / 2 + 8;
-        order[i] = i;
-      }
-      std::stable_sort(order.data(), order.data() + n, [&](uint32_t a, uint32_t b) { return items[a].bytes > items[b].bytes; });
-    }
-    const size_t cmd_slots = (size_t)items[n - 1].cmd_base + items[n - 1].cmd_cap;
-    const uint32_t tables = (uint32_t)std::min<size_t>(tables_max, n);
-
-    DevBlocks mem;
-    uint8_t* uploaded = mem.uninit<uint8_t>(text_bytes);
-    dev_h2d_bulk(uploaded, staging.data(), text_bytes);
-    BatchItem* items_dev = mem.uninit<BatchItem>((size_t)n * sizeof(BatchItem));
-    dev_h2d(items_dev, items.data(), (size_t)n * sizeof(BatchItem));
-    uint32_t* order_dev = mem.uninit<uint32_t>((size_t)n * 4);
-    dev_h2d(order_dev, order.data(), (size_t)n * 4);
-
-    QuickBatchJob J{};
-    J.P = P;
-    J.Q = Q;
-    J.Q.table = mem.uninit<uint32_t>((size_t)tables * table_bytes + 64);  // (every chain zeroes its table in front of every item)
-    J.text = uploaded;
-    J.slabs = mem.uninit<Command>(cmd_slots * sizeof(Command) + 64);
-    J.items = items_dev;
-    J.order = order_dev;
-    J.n_items = n;
-    J.tables = tables;
-    J.counter = mem.zeroed<uint32_t>(64);
-    J.records = nullptr;
-    BatchLongRecord* records_dev = mem.uninit<BatchLongRecord>((size_t)n * sizeof(BatchLongRecord));
-    lz77_quick_batch_parse_long(J, records_dev);
-    records.resize_discard(n);
-    dev_d2h(records.data(), records_dev, (size_t)n * sizeof(BatchLongRecord));
-    // ---- command gather: the offsets per meta-block from the records (one small round trip)
-    offsets.resize_discard((size_t)n * kBatchLongBlocks);
-    std::vector<BatchStreamItem> mbs;
-    std::vector<uint32_t> first_mb(n);
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-      const BatchLongRecord& r = records[i];
-      if (r.overflow) throw std::runtime_error("brotli_mi355x: a batch chain ran out of its command slab");
-      uint32_t at = 0, cmd_at = 0;
-      first_mb[i] = (uint32_t)mbs.size();
-      for (uint32_t m = 0; m < kBatchLongBlocks; ++m) offsets[(size_t)i * kBatchLongBlocks + m] = 0;
-      for (uint32_t m = 0; m < r.n_mb && m < kBatchLongBlocks; ++m) {
-        const BatchLongMetaBlock& mb = r.mb[m];
-        if (mb.start != at || mb.bytes == 0 || mb.bytes > items[i].bytes - at || mb.first_cmd != cmd_at) break;
-        offsets[(size_t)i * kBatchLongBlocks + m] = (uint32_t)total;
-        BatchStreamItem e{};
-        e.start = starts[i] + mb.start;
-        e.bytes = mb.bytes;
-        e.cmd_offset = (uint32_t)total;
-        e.n_cmds = mb.n_cmds + (mb.trailing != 0 ? 1u : 0u);
-        e.n_lits = mb.n_lits;
-        e.uncompressed = mb.uncompressed;
-        e.follows = m != 0;
-        e.more = m + 1 != r.n_mb;
-        e.item_bytes = items[i].bytes;
-        if (m != 0) {
-          e.prev_byte = inputs[first + i][mb.start - 1];
-          e.prev_byte2 = inputs[first + i][mb.start - 2];
-        }
-        mbs.push_back(e);
-        total += e.n_cmds;
-        at += mb.bytes;
-        cmd_at += mb.n_cmds;
-      }
-      if (at != items[i].bytes || cmd_at > items[i].cmd_cap) throw std::runtime_error("brotli_mi355x: a batch chain left meta-block records that do not cover its item");
-    }
-    uint32_t* offsets_dev = mem.uninit<uint32_t>((size_t)n * kBatchLongBlocks * 4);
-    dev_h2d(offsets_dev, offsets.data(), (size_t)n * kBatchLongBlocks * 4);
-    Command* cmds = mem.uninit<Command>((size_t)(total + 16) * sizeof(Command));
-    // (the gather wants the slabs, the items and the distance parameters, as in CompressQuickGroups)
-    BatchParseJob G{};
-    G.P = P;
-    G.slabs = J.slabs;
-    G.items = items_dev;
-    G.n_items = n;
-    lz77_batch_gather_long(G, records_dev, offsets_dev, cmds);
-    std::vector<uint8_t> out;
-    EncodeBatchMetaBlocks(p, uploaded + packed_at, cmds, (uint32_t)total, &mbs, &out);
-    for (uint32_t i = 0; i < n; ++i) {
-      const BatchStreamItem& e = mbs[first_mb[i]];
-      if (e.demoted) {
-        (*demoted)[first + i] = 1;
-        continue;
-      }
-      (*streams)[first + i].assign(out.begin() + (ptrdiff_t)e.out_byte, out.begin() + (ptrdiff_t)(e.out_byte + e.out_bytes));
-    }
-    first = last;
+    FinishOneBlockItems(p, J, g, streams, reference_fails);
+    first = g.last;
   }
 }
 
 }  // namespace
-
-bool BatchQuickEligible(const EncoderParams& user, size_t input_size) {
-  if (input_size == 0) return false;  // (answered without an encoder)
-  if (user.quality < 2 || user.quality > 4 || user.lgwin < 10 || user.lgwin > 24 || user.large_window) return false;
-  if (user.catable || user.appendable || user.bare_stream || user.byte_align || user.magic_number) return false;
-  if (input_size > ((size_t)1 << 16)) return false;
-  // (the item's size is its stream's size hint: below the 1 MiB that selects H54)
-  const EncoderParams p = ItemParams(user, input_size);
-  return (p.hasher.type == 2 || p.hasher.type == 3 || p.hasher.type == 4) && input_size <= ((size_t)1 << p.lgblock);
-}
-
-void BatchQuickCompress(const EncoderParams& user, size_t count, const uint8_t* const* inputs, const size_t* sizes,
-                        std::vector<std::vector<uint8_t>>* streams, uint32_t* groups) {
-  // (nothing in the parameters differs between items of at most one block)
-  CompressQuickGroups(ItemParams(user, count ? sizes[0] : 0), count, inputs, sizes, streams, groups);
-}
-
-bool BatchQuickLongEligible(const EncoderParams& user, size_t input_size) {
-  if (user.quality < 2 || user.quality > 4 || user.lgwin < 10 || user.lgwin > 24 || user.large_window) return false;
-  if (user.catable || user.appendable || user.bare_stream || user.byte_align || user.magic_number) return false;
-  if (input_size > kBatchLongBytes) return false;
-  // (four blocks are 64 KiB at quality 2 / 3 and 256 KiB at quality 4: the size hint stays below the 1 MiB that selects H54)
-  const EncoderParams p = ItemParams(user, input_size);
-  return (p.hasher.type == 2 || p.hasher.type == 3 || p.hasher.type == 4) && input_size > ((size_t)1 << p.lgblock) &&
-         input_size <= (size_t)kBatchLongBlocks << p.lgblock;
-}
-
-void BatchQuickLongCompress(const EncoderParams& user, size_t count, const uint8_t* const* inputs, const size_t* sizes,
-                            std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* demoted, uint32_t* groups) {
-  // (nothing in the parameters differs between items of at most four blocks)
-  CompressQuickLongGroups(ItemParams(user, count ? sizes[0] : 0), count, inputs, sizes, streams, demoted, groups);
-}
 
 void BatchGreedyCompress(const EncoderParams& user, size_t count, const uint8_t* const* inputs, const size_t* sizes,
                          std::vector<std::vector<uint8_t>>* streams, uint32_t* groups) {
@@ -739,10 +457,94 @@ void BatchGreedyCompressWithDictionary(const EncoderParams& user, const uint8_t*
   CompressGroups(DictionaryItemParams(user, count ? sizes[0] : 0), dict, (uint32_t)dict_size, count, inputs, sizes, streams, reference_fails, groups);
 }
 
+// Qualities 5 .. 8, items of two to kBatchLongBlocks blocks: one chain and up to kBatchLongBlocks meta-blocks per item.
 void BatchLongCompress(const EncoderParams& user, size_t count, const uint8_t* const* inputs, const size_t* sizes,
                        std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* demoted, uint32_t* groups) {
-  // (nothing in the parameters differs between items of at most kBatchLongBytes)
-  CompressLongGroups(ItemParams(user, count ? sizes[0] : 0), count, inputs, sizes, streams, demoted, groups);
+  streams->assign(count, std::vector<uint8_t>());
+  demoted->assign(count, 0);
+  *groups = 0;
+  if (count == 0) return;
+  const EncoderParams p = ItemParams(user, sizes[0]);  // (nothing in the parameters differs between items of at most kBatchLongBytes)
+  const size_t keys_per_table = (size_t)1 << p.hasher.bucket_bits;
+  const size_t tables_max = TablesMax(keys_per_table * 2 + (keys_per_table << p.hasher.block_bits) * 4);
+  const Lz77Params P = ChainParams(p);
+  CallArrays A;
+  size_t first = 0;
+  while (first < count) {
+    Group g;
+    StageGroup(first, count, inputs, sizes, 0, tables_max, &A, &g);
+    ++*groups;
+    const BatchParseJob J = GreedyJob(p, P, g, g.uploaded);  // (J.records is not used, J.dict.bytes is 0)
+    BatchLongRecord* records_dev = g.mem.uninit<BatchLongRecord>((size_t)g.n * sizeof(BatchLongRecord));
+    lz77_batch_parse_long(J, records_dev);
+    FinishLongItems(p, J, records_dev, inputs, g, streams, demoted);
+    first = g.last;
+  }
+}
+
+bool BatchQuickEligible(const EncoderParams& user, size_t input_size) {
+  if (input_size == 0) return false;  // (answered without an encoder)
+  if (user.quality < 2 || user.quality > 4 || user.lgwin < 10 || user.lgwin > 24 || !PlainStreamParams(user)) return false;
+  if (input_size > ((size_t)1 << 16)) return false;
+  // (the item's size is its stream's size hint: below the 1 MiB that selects H54)
+  const EncoderParams p = ItemParams(user, input_size);
+  return (p.hasher.type == 2 || p.hasher.type == 3 || p.hasher.type == 4) && input_size <= ((size_t)1 << p.lgblock);
+}
+
+// Qualities 2 .. 4 (batch_quick.h), items of one block.  (The quick kernel leaves bad_commands at 0: no stream is dropped.)
+void BatchQuickCompress(const EncoderParams& user, size_t count, const uint8_t* const* inputs, const size_t* sizes,
+                        std::vector<std::vector<uint8_t>>* streams, uint32_t* groups) {
+  streams->assign(count, std::vector<uint8_t>());
+  *groups = 0;
+  if (count == 0) return;
+  const EncoderParams p = ItemParams(user, sizes[0]);  // (nothing in the parameters differs between items of at most one block)
+  const QuickBatchJob chains = QuickChains(p);
+  const size_t tables_max = TablesMax(QuickTableBytes(chains));
+  CallArrays A;
+  size_t first = 0;
+  while (first < count) {
+    Group g;
+    StageGroup(first, count, inputs, sizes, 0, tables_max, &A, &g);
+    ++*groups;
+    QuickBatchJob J = QuickGroupJob(chains, g);
+    J.records = g.mem.uninit<BatchRecord>((size_t)g.n * sizeof(BatchRecord));
+    lz77_quick_batch_parse(J);
+    FinishOneBlockItems(p, GatherJobOf(J), g, streams, nullptr);
+    first = g.last;
+  }
+}
+
+bool BatchQuickLongEligible(const EncoderParams& user, size_t input_size) {
+  if (user.quality < 2 || user.quality > 4 || user.lgwin < 10 || user.lgwin > 24 || !PlainStreamParams(user)) return false;
+  if (input_size > kBatchLongBytes) return false;
+  // (four blocks are 64 KiB at quality 2 / 3 and 256 KiB at quality 4: the size hint stays below the 1 MiB that selects H54)
+  const EncoderParams p = ItemParams(user, input_size);
+  return (p.hasher.type == 2 || p.hasher.type == 3 || p.hasher.type == 4) && input_size > ((size_t)1 << p.lgblock) &&
+         input_size <= (size_t)kBatchLongBlocks << p.lgblock;
+}
+
+// Qualities 2 .. 4, items of two to kBatchLongBlocks input blocks (batch_quick.h).
+void BatchQuickLongCompress(const EncoderParams& user, size_t count, const uint8_t* const* inputs, const size_t* sizes,
+                            std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* demoted, uint32_t* groups) {
+  streams->assign(count, std::vector<uint8_t>());
+  demoted->assign(count, 0);
+  *groups = 0;
+  if (count == 0) return;
+  const EncoderParams p = ItemParams(user, sizes[0]);  // (nothing in the parameters differs between items of at most four blocks)
+  const QuickBatchJob chains = QuickChains(p);
+  const size_t tables_max = TablesMax(QuickTableBytes(chains));
+  CallArrays A;
+  size_t first = 0;
+  while (first < count) {
+    Group g;
+    StageGroup(first, count, inputs, sizes, 0, tables_max, &A, &g);
+    ++*groups;
+    const QuickBatchJob J = QuickGroupJob(chains, g);  // (J.records is not used)
+    BatchLongRecord* records_dev = g.mem.uninit<BatchLongRecord>((size_t)g.n * sizeof(BatchLongRecord));
+    lz77_quick_batch_parse_long(J, records_dev);
+    FinishLongItems(p, GatherJobOf(J), records_dev, inputs, g, streams, demoted);
+    first = g.last;
+  }
 }
 
 }  // namespace brotli_mi355x

@@ -1037,9 +1037,12 @@ static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEn
     // those of two to four blocks, or those of one input block under a BasicHasher at qualities 2 .. 4, or those of two to four
     // blocks at these qualities (batch_quick.h).  Every other item goes through the one-shot path by itself, on this thread, in
     // the caller's order (the same bytes, no gain in speed).
-    std::vector<size_t> item, long_item, quick_item, quick_long_item;
-    std::vector<const uint8_t*> in, long_in, quick_in, quick_long_in;
-    std::vector<size_t> in_size, long_size, quick_size, quick_long_size;
+    struct Routed {  // the items of one route: their places in the caller's arrays, their inputs and their sizes
+      std::vector<size_t> item;
+      std::vector<const uint8_t*> in;
+      std::vector<size_t> size;
+    };
+    Routed plain, long_items, quick_items, quick_long_items;
     const bool long_route = (routes & BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS) != 0;
     const bool quick_route = (routes & BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS) != 0;
     const bool quick_long_route = (routes & BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS) != 0;
@@ -1050,6 +1053,22 @@ static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEn
       if (!results[i]) output_sizes[i] = 0;
       ++info[2];
     };
+    // hands the streams of a route out, in the caller's order.  demoted != nullptr, (*demoted)[k] != 0: a meta-block that is not the
+    // item's last took the size fallback, which its chain could not know: redone one by one.  Returns the streams handed out.
+    auto deliver = [&](const Routed& r, const std::vector<std::vector<uint8_t>>& streams, const std::vector<uint8_t>* demoted) {
+      size_t delivered = 0;
+      for (size_t k = 0; k < r.item.size(); ++k) {
+        const size_t i = r.item[k];
+        if (demoted && (*demoted)[k]) {
+          one_by_one(i);
+          ++info[6];
+          continue;
+        }
+        results[i] = OneShotDeliver(streams[k].data(), streams[k].size(), inputs[i], input_sizes[i], false, output_sizes[i], &output_sizes[i], outputs[i]);
+        ++delivered;
+      }
+      return delivered;
+    };
     for (size_t i = 0; i < count; ++i) {
       const int early = OneShotWithoutEncoder(input_sizes[i], &output_sizes[i], outputs[i]);
       if (early >= 0) {
@@ -1058,100 +1077,54 @@ static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEn
         ++info[3];
         continue;
       }
-      if (fragments || BatchGreedyEligible(params, input_sizes[i])) {
-        item.push_back(i);
-        in.push_back(inputs[i]);
-        in_size.push_back(input_sizes[i]);
+      Routed* r = nullptr;
+      if (fragments || BatchGreedyEligible(params, input_sizes[i])) r = &plain;
+      else if (long_route && BatchLongEligible(params, input_sizes[i])) r = &long_items;
+      else if (quick_route && BatchQuickEligible(params, input_sizes[i])) r = &quick_items;
+      else if (quick_long_route && BatchQuickLongEligible(params, input_sizes[i])) r = &quick_long_items;
+      if (!r) {
+        one_by_one(i);
         continue;
       }
-      if (long_route && BatchLongEligible(params, input_sizes[i])) {
-        long_item.push_back(i);
-        long_in.push_back(inputs[i]);
-        long_size.push_back(input_sizes[i]);
-        continue;
-      }
-      if (quick_route && BatchQuickEligible(params, input_sizes[i])) {
-        quick_item.push_back(i);
-        quick_in.push_back(inputs[i]);
-        quick_size.push_back(input_sizes[i]);
-        continue;
-      }
-      if (quick_long_route && BatchQuickLongEligible(params, input_sizes[i])) {
-        quick_long_item.push_back(i);
-        quick_long_in.push_back(inputs[i]);
-        quick_long_size.push_back(input_sizes[i]);
-        continue;
-      }
-      one_by_one(i);
+      r->item.push_back(i);
+      r->in.push_back(inputs[i]);
+      r->size.push_back(input_sizes[i]);
     }
+    std::vector<std::vector<uint8_t>> streams;
+    std::vector<uint8_t> demoted;
+    uint32_t groups = 0;
     // ---- the items of one block at qualities 2 .. 4, one chain each, in groups of their own (BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS)
-    if (!quick_item.empty()) {
-      std::vector<std::vector<uint8_t>> quick_streams;
-      uint32_t groups = 0;
-      BatchQuickCompress(params, quick_item.size(), quick_in.data(), quick_size.data(), &quick_streams, &groups);
+    if (!quick_items.item.empty()) {
+      BatchQuickCompress(params, quick_items.item.size(), quick_items.in.data(), quick_items.size.data(), &streams, &groups);
       info[4] += groups;
-      for (size_t k = 0; k < quick_item.size(); ++k) {
-        const size_t i = quick_item[k];
-        results[i] = OneShotDeliver(quick_streams[k].data(), quick_streams[k].size(), inputs[i], input_sizes[i], false, output_sizes[i], &output_sizes[i], outputs[i]);
-        ++info[1];
-      }
+      info[1] += deliver(quick_items, streams, nullptr);
     }
     // ---- the items of two to four blocks at qualities 2 .. 4, one chain each, in groups of their own
     // (BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS)
-    if (!quick_long_item.empty()) {
-      std::vector<std::vector<uint8_t>> long_streams;
-      std::vector<uint8_t> demoted;
-      uint32_t groups = 0;
-      BatchQuickLongCompress(params, quick_long_item.size(), quick_long_in.data(), quick_long_size.data(), &long_streams, &demoted, &groups);
+    if (!quick_long_items.item.empty()) {
+      BatchQuickLongCompress(params, quick_long_items.item.size(), quick_long_items.in.data(), quick_long_items.size.data(), &streams, &demoted, &groups);
       info[4] += groups;
-      for (size_t k = 0; k < quick_long_item.size(); ++k) {
-        const size_t i = quick_long_item[k];
-        if (demoted[k]) {
-          // a meta-block that is not the item's last took the size fallback, which its chain could not know: redone one by one
-          one_by_one(i);
-          ++info[6];
-          continue;
-        }
-        results[i] = OneShotDeliver(long_streams[k].data(), long_streams[k].size(), inputs[i], input_sizes[i], false, output_sizes[i], &output_sizes[i], outputs[i]);
-        ++info[1];
-        ++info[7];
-      }
+      const size_t delivered = deliver(quick_long_items, streams, &demoted);
+      info[1] += delivered;
+      info[7] += delivered;
     }
     // ---- the items of several blocks, one chain each, in groups of their own (BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS)
-    if (!long_item.empty()) {
-      std::vector<std::vector<uint8_t>> long_streams;
-      std::vector<uint8_t> demoted;
-      uint32_t groups = 0;
-      BatchLongCompress(params, long_item.size(), long_in.data(), long_size.data(), &long_streams, &demoted, &groups);
+    if (!long_items.item.empty()) {
+      BatchLongCompress(params, long_items.item.size(), long_items.in.data(), long_items.size.data(), &streams, &demoted, &groups);
       info[4] += groups;
-      for (size_t k = 0; k < long_item.size(); ++k) {
-        const size_t i = long_item[k];
-        if (demoted[k]) {
-          // a meta-block that is not the item's last took the size fallback, which its chain could not know: redone one by one
-          one_by_one(i);
-          ++info[6];
-          continue;
-        }
-        results[i] = OneShotDeliver(long_streams[k].data(), long_streams[k].size(), inputs[i], input_sizes[i], false, output_sizes[i], &output_sizes[i], outputs[i]);
-        ++info[1];
-        ++info[7];
-      }
+      const size_t delivered = deliver(long_items, streams, &demoted);
+      info[1] += delivered;
+      info[7] += delivered;
     }
-    std::vector<std::vector<uint8_t>> streams;
-    if (!item.empty()) {
+    if (!plain.item.empty()) {
       if (fragments) {
-        FragmentBatchCompress(params, item.size(), in.data(), in_size.data(), &streams);
+        FragmentBatchCompress(params, plain.item.size(), plain.in.data(), plain.size.data(), &streams);
         info[4] = 1;
       } else {
-        uint32_t groups = 0;
-        BatchGreedyCompress(params, item.size(), in.data(), in_size.data(), &streams, &groups);
+        BatchGreedyCompress(params, plain.item.size(), plain.in.data(), plain.size.data(), &streams, &groups);
         info[4] += groups;
       }
-      info[1] += item.size();
-    }
-    for (size_t k = 0; k < item.size(); ++k) {
-      const size_t i = item[k];
-      results[i] = OneShotDeliver(streams[k].data(), streams[k].size(), inputs[i], input_sizes[i], false, output_sizes[i], &output_sizes[i], outputs[i]);
+      info[1] += deliver(plain, streams, nullptr);
     }
   } catch (const std::exception& e) {
     // a device error fails the call as a whole
