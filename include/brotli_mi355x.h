@@ -78,7 +78,8 @@ typedef enum BrotliEncoderOperation {
   BROTLI_OPERATION_EMIT_METADATA = 3
 } BrotliEncoderOperation;
 
-/* c/brotli/encode.h:138-232, src/enc/parameters.rs:3-33 */
+/* c/brotli/encode.h:138-232, src/enc/parameters.rs:3-33.  BrotliEncoderSetParameter refuses ids 7, 8 and 170 as the reference does
+ * (its setter has no arm for them, src/enc/encode.rs:196-286), although the enum names them. */
 typedef enum BrotliEncoderParameter {
   BROTLI_PARAM_MODE = 0,
   BROTLI_PARAM_QUALITY = 1,

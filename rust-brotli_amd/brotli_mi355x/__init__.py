@@ -387,8 +387,9 @@ class Encoder(object):
     def set_parameter(self, key, value):
         return bool(self._l.lib.BrotliEncoderSetParameter(self._s, int(key), int(value)))
 
-    def finish(self):
-        self._stream(BROTLI_OPERATION_FINISH, b"")
+    def finish(self, data=b""):
+        """BROTLI_OPERATION_FINISH, with the last of the input if any"""
+        self._stream(BROTLI_OPERATION_FINISH, data)
         assert self._l.lib.BrotliEncoderIsFinished(self._s)
         return bytes(self._out)  # (after flush() calls: the remainder of the stream)
 

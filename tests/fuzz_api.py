@@ -5,7 +5,10 @@ FUZZ_ZOPFLI=10 (or =11): every case at quality 10 (11) proper (row f1: H10 + Zop
 FUZZ_FRAGMENT=1: every case at quality 0 or 1 (row f3: the fragment compressors, fragment_device.h), catable streams, custom
 dictionaries and shards (the ring-buffer path of these qualities) included; no metadata block behind input on a catable stream (the
 reference does not return from that call).
-FUZZ_QUICK=1: every case at quality 2, 3 or 4 (row f3: the BasicHasher family, quick_device.h), windows down to lgwin 10."""
+FUZZ_QUICK=1: every case at quality 2, 3 or 4 (row f3: the BasicHasher family, quick_device.h), windows down to lgwin 10.
+FUZZ_PARAMS=1: behind all other draws of a case, each with probability 1/2: a mode from 2 .. 6 (FONT and the forced context modes), an
+lgblock, a literal byte score, DISABLE_LITERAL_CONTEXT_MODELING -- in every parameter list of the case, on both sides.  The writer
+pattern runs as a one-FINISH case then.  Without the switch nothing is drawn: every seed gives the cases it always gave."""
 import os, sys, time
 import synth, orc
 import test_cabi
@@ -48,7 +51,8 @@ for c in range(cases):
         q = rng.next() % 2
         w = [10, 13, 16, 17, 18, 20, 22, 24][rng.next() % 8]
         mode = rng.next() % 6
-    if q95 and mode == 5:
+    fuzz_params = bool(os.environ.get("FUZZ_PARAMS"))
+    if (q95 or fuzz_params) and mode == 5:
         mode = 4  # (orc.writer_compress takes quality and window only)
     base = [(Q, q), (W, w)] + ([(150, 1)] if q95 else [])
     extra = []
@@ -148,6 +152,15 @@ for c in range(cases):
                                                    len(fdic) if fdic else None)
         product = lambda: flushed(ops)
         oracle = lambda: orc.stream_with_flushes(d, fparams, ops, dictionary=fdic)
+    if fuzz_params:
+        # (behind every other draw of the case; product() and oracle() read base and fparams when they are called)
+        drawn = []
+        for pid, values in ((0, [2, 3, 4, 5, 6]), (3, [16, 17, 18] if zopfli else [16, 17, 18, 20]), (154, [1, 100, 340, 1000]), (4, [1])):
+            if rng.next() % 2:
+                drawn.append((pid, values[rng.next() % len(values)]))
+        fparams = fparams + drawn
+        base = base + drawn
+        what += " drawn %r" % (drawn,)
     if os.environ.get("FUZZ_ONLY") and c != int(os.environ["FUZZ_ONLY"]):
         continue
     # an input on which the reference itself fails (it panics on a copy of length 1, see orc.ReferencePanics) must make
@@ -179,5 +192,6 @@ for c in range(cases):
         bad += 1
         print("FAIL case %d n %d q %d w %d %s" % (c, n, q, w, what), flush=True)
         open("/tmp/fuzzapi_fail_%d.bin" % c, "wb").write(d)
+        open("/tmp/fuzzapi_fail_%d.txt" % c, "w").write("n %d q %d w %d %s\n" % (n, q, w, what))  # (the operations and every parameter of the case)
 print("%d cases, %d failures, %d on which the reference fails (and so does the product), %.1f s" % (cases, bad, panics, time.time() - t0))
 sys.exit(1 if bad else 0)

@@ -164,6 +164,33 @@ def decompress(comp, expected_size):
     return out.raw[:n.value]
 
 
+def decompress_large_window(comp, expected_size):
+    """a large-window stream (BROTLI_PARAM_LARGE_WINDOW) through the decoder's stream entry, where it can be told to accept one"""
+    decompress(b"\x06", 0)  # (loads the decoder library)
+    dec = _dec
+    dec.BrotliDecoderCreateInstance.restype = ctypes.c_void_p
+    dec.BrotliDecoderCreateInstance.argtypes = [ctypes.c_void_p] * 3
+    dec.BrotliDecoderSetParameter.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32]
+    dec.BrotliDecoderDestroyInstance.argtypes = [ctypes.c_void_p]
+    dec.BrotliDecoderDecompressStream.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_void_p),
+                                                  ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]
+    s = dec.BrotliDecoderCreateInstance(None, None, None)
+    try:
+        if not dec.BrotliDecoderSetParameter(s, 1, 1):  # BROTLI_DECODER_PARAM_LARGE_WINDOW
+            raise RuntimeError("the decoder does not take BROTLI_DECODER_PARAM_LARGE_WINDOW")
+        cap = expected_size + 16
+        src = ctypes.create_string_buffer(comp, len(comp))
+        out = ctypes.create_string_buffer(cap)
+        avail_in, next_in = ctypes.c_size_t(len(comp)), ctypes.c_void_p(ctypes.addressof(src))
+        avail_out, next_out = ctypes.c_size_t(cap), ctypes.c_void_p(ctypes.addressof(out))
+        r = dec.BrotliDecoderDecompressStream(s, ctypes.byref(avail_in), ctypes.byref(next_in), ctypes.byref(avail_out), ctypes.byref(next_out), None)
+        if r != 1 or avail_in.value:  # BROTLI_DECODER_RESULT_SUCCESS, all input taken
+            raise RuntimeError("decoder rejected the large-window stream (result %d)" % r)
+        return out.raw[:cap - avail_out.value]
+    finally:
+        dec.BrotliDecoderDestroyInstance(s)
+
+
 def stream_compress(data, params, prefix=None, collect_trace=False, continuation=True):
     """Generic path through the oracle's stream API: set params, optional custom dictionary
     (multi-thread continuation semantics), one FINISH call.  Returns (bytes, trace) where trace is a

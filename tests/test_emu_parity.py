@@ -266,3 +266,15 @@ def test_catable_stream_recheck_at_block_starts(L):
     assert check("catable recheck", d, 6, 24, catable=True, seg=512, lib=L)
     for q in (6, 7, 8, 9):
         assert check_bytes(L, "catable recheck q%d" % q, d, [(Q, q), (W, 24), (SH, len(d)), (167, 1)], seg=512)
+
+
+def test_few_stored_slots_in_a_long_key(L):
+    """the first 200 000 bytes of mixed(600000, 7) hold a stretch of zero fill: one hash key with tens of thousands of slots (fewer
+    than the 65 536 that force the full rebuild), few of them stored, many changed from round to round.  The emulation's
+    lz77_rows_update used to walk from every changed slot to the key's end and took 70 s here (tests/emu/device_emu.cpp: the walks now
+    end at the next changed slot, a fraction of a second).  Identity only -- no test times itself -- but this is the input to look at
+    when the CPU suite slows down; both segment sizes took the slow way."""
+    d = synth.mixed(600000, 7)[:200000]
+    assert d.count(bytes(4096)) > 0
+    assert check_bytes(L, "mixed 200k", d, [(Q, 5), (W, 22)], seg=4096, verbose=False)
+    assert check_bytes(L, "mixed 200k", d, [(Q, 5), (W, 22)], seg=0, verbose=False)

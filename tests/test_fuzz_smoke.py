@@ -95,3 +95,20 @@ def test_one_shot_sweep_device():
 @pytest.mark.gpu
 def test_api_sweep_device():
     assert " 0 failures" in _run("fuzz_api.py", 300, 6)
+
+
+def test_sweeps_with_stream_parameters_emulation():
+    """FUZZ_PARAMS=1: every case also draws a mode (FONT, the forced context modes), an lgblock, a literal byte score and
+    DISABLE_LITERAL_CONTEXT_MODELING -- shards, flushes and dictionaries carry them (tests/test_stream_params.py has the fixed cases)"""
+    import emu
+    emu.build()
+    assert " 0 failures" in _run("fuzz_api.py", 60, 41, "emu", FUZZ_PARAMS="1")
+    assert " 0 failures" in _run("fuzz_api.py", 40, 42, "emu", FUZZ_PARAMS="1", FUZZ_QUICK="1")
+    assert "0 mismatches" in _run("fuzz_gpu.py", 40, 43, "emu", 0.3, FUZZ_PARAMS="1")
+
+
+@pytest.mark.gpu
+def test_sweeps_with_stream_parameters_device():
+    assert " 0 failures" in _run("fuzz_api.py", 60, 41, FUZZ_PARAMS="1", FUZZ_MAXN="400000")
+    assert " 0 failures" in _run("fuzz_api.py", 40, 42, FUZZ_PARAMS="1", FUZZ_QUICK="1", FUZZ_MAXN="400000")
+    assert "0 mismatches" in _run("fuzz_gpu.py", 40, 43, FUZZ_PARAMS="1", FUZZ_MAXN="400000")
