@@ -230,7 +230,7 @@ int32_t BrotliMi355xCompressBatch(int quality, int lgwin, BrotliEncoderMode mode
    item on a hash table already holding the dictionary): qualities 5 .. 8, lgwin 17 .. 24, 2 <= dict_size <= 65536 and
    1 <= input_sizes[i] <= 65536.  Everything else -- other qualities and windows, longer items, longer or shorter dictionaries, the
    empty item -- is accepted and runs by itself through the stream path on the calling thread, in the same call and in the
-   caller's order: the same bytes, no gain in speed.  The environment of BrotliMi355xCompressBatch applies; a group's byte limit
+   caller's order: the same bytes, no gain in speed (qualities 2 .. 4: see BrotliMi355xCompressBatchWithDictionaryEx).  The environment of BrotliMi355xCompressBatch applies; a group's byte limit
    counts one copy of the dictionary per item. */
 int32_t BrotliMi355xCompressBatchWithDictionary(int quality, int lgwin, BrotliEncoderMode mode, size_t dict_size, const uint8_t* dict,
                                                 size_t count, const uint8_t* const* inputs, const size_t* input_sizes,
@@ -260,7 +260,8 @@ int32_t BrotliMi355xCompressBatchWithDictionary(int quality, int lgwin, BrotliEn
    The bit changes nothing at qualities 0, 1 and 5 .. 11.  Such items count in info[1], their groups in info[4]; info[6] and
    info[7] stay 0 for them.  When to set it: with hundreds of small items of one kind in a call (dynamic responses at the levels
    servers use for them); a chain is one wavefront bound by its own dependent loads, so a call of a few items is no faster
-   than the one-by-one path (see INTEGRATION.md for measured figures).  Not combined with a shared dictionary.
+   than the one-by-one path (see INTEGRATION.md for measured figures).  With a shared dictionary:
+   BrotliMi355xCompressBatchWithDictionaryEx.
    BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS: item i still gets exactly what BrotliEncoderCompress gives.  In addition, an item
    of more than one and at most four input blocks at quality 2, 3 or 4 and lgwin 10 .. 24 -- that is
    16 385 <= input_sizes[i] <= 65 536 at quality 2 / 3 and 65 537 <= input_sizes[i] <= 262 144 at quality 4 -- runs on the device
@@ -281,7 +282,37 @@ int32_t BrotliMi355xCompressBatchWithDictionary(int quality, int lgwin, BrotliEn
 int32_t BrotliMi355xCompressBatchEx(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t count,
                                     const uint8_t* const* inputs, const size_t* input_sizes, uint8_t* const* outputs,
                                     size_t* output_sizes /* in: capacity, out: size */, int32_t* item_results /* may be NULL */);
-/* The last BrotliMi355xCompressBatch / BrotliMi355xCompressBatchEx / BrotliMi355xCompressBatchWithDictionary call of the calling
+/* BrotliMi355xCompressBatchWithDictionary with routes the caller opts into.  routes == 0 is that call in every respect.  The only
+   route this call knows is BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS; any other bit -- the other routes of
+   BrotliMi355xCompressBatchEx and the reserved values 2 and 8 included -- fails the whole call as an unknown route fails that one
+   (returns 0, every size 0, BrotliMi355xLastError says so, only info[0] of BrotliMi355xLastBatchInfo is set).
+   BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS: item i is still exactly the stream of BrotliEncoderSetCustomDictionary + one
+   BrotliEncoderCompressStream(BROTLI_OPERATION_FINISH), by the rules above -- in bytes, size, success or failure.  In addition
+   to the items that call takes side by side, an item of at most one input block at quality 2, 3 or 4 and lgwin 10 .. 24 -- that
+   is 1 <= input_sizes[i] <= 16 384 at quality 2 / 3 and <= 65 536 at quality 4 -- behind a dictionary of dict_size >= 2 of which
+   at most 65 536 bytes are in use (min(dict_size, (1 << lgwin) - 16): the reference's truncation) runs on the device as ONE chain
+   on a private BasicHasher table (H2 / H3 / H4; 256 KiB, at quality 4 512 KiB), side by side with the other such items of the
+   call.  The dictionary goes up once per call, and so does the table the reference's prepend leaves for it; every chain copies
+   that table over its own in front of every item (the cost of the zero fill of the plain route), parses dictionary | item with
+   positions counted from the dictionary's first byte, and leaves one meta-block.  Every other item -- the empty one, items
+   longer than one input block, dict_size <= 1 -- runs by itself through the stream path on the calling thread, in the same call
+   and in the caller's order.  The bit changes nothing at qualities 0, 1 and 5 .. 11: at qualities 5 .. 8 the items still take the
+   dictionary route of the plain call.  Such items count in info[1], their groups in info[4]; info[5] is the dictionary bytes in
+   use; info[6] and info[7] stay 0.  An item on which the reference fails ("the reference encoder fails on this input") fails
+   alone, as does one whose stream does not fit; a device error fails the call.  At quality 2 on text behind a dictionary of the
+   same kind about 3 in 1000 items of 4 KiB are such inputs: pass item_results and expect a call of thousands
+   of items to return 0 with a few of them failed alone.  The environment of BrotliMi355xCompressBatch
+   applies (4096 tables by default; a group's byte limit counts one copy of the dictionary per item).
+   When to set it: with hundreds of small items of one kind in a call that share a dictionary (dynamic responses, messages,
+   records at the levels servers use for them).  When not: with a few items -- a chain is one wavefront bound by its own
+   dependent loads, so a call of a few items is no faster than the one-by-one path (see INTEGRATION.md for measured figures). */
+int32_t BrotliMi355xCompressBatchWithDictionaryEx(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t dict_size,
+                                                  const uint8_t* dict, size_t count, const uint8_t* const* inputs,
+                                                  const size_t* input_sizes, uint8_t* const* outputs,
+                                                  size_t* output_sizes /* in: capacity, out: size */,
+                                                  int32_t* item_results /* may be NULL */);
+/* The last BrotliMi355xCompressBatch / BrotliMi355xCompressBatchEx / BrotliMi355xCompressBatchWithDictionary /
+   BrotliMi355xCompressBatchWithDictionaryEx call of the calling
    thread: info[0] items, [1] items encoded side by side on the device, [2] items run one by one (the one-shot path; with a
    dictionary the stream path), [3] items answered without an encoder (empty input, capacity 0; none with a dictionary), [4] device
    groups (those of long items included), [5] dictionary bytes in use after the reference's truncation (0 for the plain call),

@@ -96,6 +96,10 @@ def _bind(lib):
         lib.BrotliMi355xCompressBatchEx.restype = c_int32
         lib.BrotliMi355xCompressBatchEx.argtypes = [c_int, c_int, c_int, c_uint32, c_size_t, POINTER(c_char_p), POINTER(c_size_t), POINTER(c_void_p),
                                                     POINTER(c_size_t), POINTER(c_int32)]
+    if hasattr(lib, "BrotliMi355xCompressBatchWithDictionaryEx"):
+        lib.BrotliMi355xCompressBatchWithDictionaryEx.restype = c_int32
+        lib.BrotliMi355xCompressBatchWithDictionaryEx.argtypes = [c_int, c_int, c_int, c_uint32, c_size_t, c_char_p, c_size_t, POINTER(c_char_p),
+                                                                  POINTER(c_size_t), POINTER(c_void_p), POINTER(c_size_t), POINTER(c_int32)]
     lib.BrotliMi355xDeviceName.restype = c_char_p
     lib.BrotliMi355xLastError.restype = c_char_p
     return lib
@@ -197,7 +201,7 @@ class Library(object):
         to 24 the items of at most one input block (16 384 bytes at quality 2 and 3, 65 536 at quality 4) run side by side, one
         chain on a private hash table each (the same bytes).  Without it these qualities run item by item; longer items at these
         qualities still do.  It pays with hundreds of small items in a call.  May be combined with long_items, not with a
-        dictionary.
+        dictionary (that is compress_batch_with_dictionary(..., quick_items=True)).
 
         quick_long_items=True: BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS -- at qualities 2 to 4 and
         lgwin 10 to 24 the items of more than one and at most four input blocks (16 385 to 65 536 bytes at quality 2 and 3, 65 537
@@ -209,16 +213,36 @@ class Library(object):
         if long_items and dictionary is not None:
             raise ValueError("long_items and dictionary cannot be combined: BrotliMi355xCompressBatchWithDictionary has no routes")
         if quick_items and dictionary is not None:
-            raise ValueError("quick_items and dictionary cannot be combined: BrotliMi355xCompressBatchWithDictionary has no routes")
+            raise ValueError("quick_items and dictionary cannot be combined: BrotliMi355xCompressBatchWithDictionary has no routes "
+                             "(compress_batch_with_dictionary(..., quick_items=True) calls BrotliMi355xCompressBatchWithDictionaryEx)")
         routes = (self.BATCH_ROUTE_LONG_ITEMS if long_items else 0) | (self.BATCH_ROUTE_QUICK_ITEMS if quick_items else 0)
         routes |= self.BATCH_ROUTE_QUICK_LONG_ITEMS if quick_long_items else 0
+        if dictionary is not None:
+            dictionary = bytes(dictionary)
+
+        def call(count, inputs, in_sizes, outputs, out_sizes, results):
+            if routes:
+                return "BrotliMi355xCompressBatchEx", self.lib.BrotliMi355xCompressBatchEx(quality, lgwin, mode, routes, count, inputs, in_sizes, outputs,
+                                                                                           out_sizes, results)
+            if dictionary is None:
+                return "BrotliMi355xCompressBatch", self.lib.BrotliMi355xCompressBatch(quality, lgwin, mode, count, inputs, in_sizes, outputs, out_sizes, results)
+            return "BrotliMi355xCompressBatchWithDictionary", self.lib.BrotliMi355xCompressBatchWithDictionary(
+                quality, lgwin, mode, len(dictionary), dictionary, count, inputs, in_sizes, outputs, out_sizes, results)
+
+        # (the stream API has no fallback to a stored stream at BrotliEncoderMaxCompressedSize: room beyond it)
+        return self._batch(items, 16 if dictionary is None else 1024, call)
+
+    def _batch(self, items, room, call):
+        """The buffers of a batch call, the call, its streams: every item gets BrotliEncoderMaxCompressedSize + `room` bytes;
+        call(count, inputs, in_sizes, outputs, out_sizes, results) -> (entry name, return value).  Where the call returns 0 the
+        exception carries what it left: .failed (the indices of the items that failed) and .streams (the streams of the others,
+        None for a failed item; all None after a call that failed as a whole)."""
         items = [bytes(x) for x in items]
         count = len(items)
         if count == 0:
             return []
         sizes = [len(x) for x in items]
-        # (the stream API has no fallback to a stored stream at BrotliEncoderMaxCompressedSize: room beyond it)
-        caps = [self.lib.BrotliEncoderMaxCompressedSize(n) + (16 if dictionary is None else 1024) for n in sizes]
+        caps = [self.lib.BrotliEncoderMaxCompressedSize(n) + room for n in sizes]
         starts = [0] * count
         at = 0
         for i, cap in enumerate(caps):
@@ -231,25 +255,47 @@ class Library(object):
         outputs = (c_void_p * count)(*[base + s for s in starts])
         out_sizes = (c_size_t * count)(*caps)
         results = (c_int32 * count)()
-        if routes:
-            name = "BrotliMi355xCompressBatchEx"
-            ok = self.lib.BrotliMi355xCompressBatchEx(quality, lgwin, mode, routes, count, inputs, in_sizes, outputs, out_sizes, results)
-        elif dictionary is None:
-            name = "BrotliMi355xCompressBatch"
-            ok = self.lib.BrotliMi355xCompressBatch(quality, lgwin, mode, count, inputs, in_sizes, outputs, out_sizes, results)
-        else:
-            name = "BrotliMi355xCompressBatchWithDictionary"
-            dictionary = bytes(dictionary)
-            ok = self.lib.BrotliMi355xCompressBatchWithDictionary(quality, lgwin, mode, len(dictionary), dictionary, count, inputs, in_sizes,
-                                                                  outputs, out_sizes, results)
+        name, ok = call(count, inputs, in_sizes, outputs, out_sizes, results)
+        view = memoryview(out)
+        streams = [bytes(view[starts[i]:starts[i] + out_sizes[i]]) if ok or results[i] else None for i in range(count)]
         if not ok:
             failed = [i for i in range(count) if not results[i]]
-            raise BrotliCompressorException("%s failed (items %s): %s" % (name, failed[:8], self.last_error()))
-        view = memoryview(out)
-        return [bytes(view[starts[i]:starts[i] + out_sizes[i]]) for i in range(count)]
+            e = BrotliCompressorException("%s failed (items %s): %s" % (name, failed[:8], self.last_error()))
+            e.failed, e.streams = failed, streams
+            raise e
+        return streams
+
+    def compress_batch_with_dictionary(self, items, dictionary, quality=5, lgwin=22, mode=0, quick_items=False):
+        """BrotliMi355xCompressBatchWithDictionaryEx: every item is the stream of an Encoder(params, dictionary) that gets the item
+        in one finish(), as compress_batch(..., dictionary=dictionary) gives it; a decoder needs the same dictionary.  Returns a
+        list of bytes.
+
+        quick_items=False: BrotliMi355xCompressBatchWithDictionary in every respect -- side by side at qualities 5 to 8 only.
+
+        quick_items=True: BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS -- at qualities 2 to 4 and lgwin 10 to 24 the items of at most one
+        input block (16 384 bytes at quality 2 and 3, 65 536 at quality 4) behind a dictionary of at least 2 bytes, of which at
+        most 65 536 are in use, run side by side, one chain each on a private hash table that starts as the dictionary's (the same
+        bytes).  Without it these qualities run item by item; longer items and the empty item still do.  It pays with hundreds of
+        small items of one kind in a call, not with a few: a chain is one wavefront.
+
+        Items the reference itself fails on: behind a dictionary a match cut to one byte at the dictionary's end is a copy the
+        reference cannot encode, and its stream call fails.  Such an item fails alone in the C call, which then returns 0 -- and
+        this method raises BrotliCompressorException although every other stream was produced.  It is not rare at quality 2 on
+        text behind a dictionary of the same kind: about 3 in 1000 items of 4 KiB in the measured runs, so
+        a call of thousands of such items is expected to raise.  The exception carries .failed (their indices) and .streams (the
+        streams of the others, None for a failed item): catch it, and send the failed items through another quality or without
+        the dictionary."""
+        routes = self.BATCH_ROUTE_QUICK_ITEMS if quick_items else 0
+        dictionary = bytes(dictionary)
+
+        def call(count, inputs, in_sizes, outputs, out_sizes, results):
+            return "BrotliMi355xCompressBatchWithDictionaryEx", self.lib.BrotliMi355xCompressBatchWithDictionaryEx(
+                quality, lgwin, mode, routes, len(dictionary), dictionary, count, inputs, in_sizes, outputs, out_sizes, results)
+
+        return self._batch(items, 1024, call)
 
     def last_batch_info(self):
-        """BrotliMi355xLastBatchInfo: the last compress_batch call of this thread as a list of 8 integers -- [0] items, [1] items
+        """BrotliMi355xLastBatchInfo: the last compress_batch / compress_batch_with_dictionary call of this thread as a list of 8 integers -- [0] items, [1] items
         encoded side by side on the device, [2] items run one by one, [3] items answered without an encoder, [4] device groups, [5] dictionary bytes in use (0 without one),
         [6] items that began side by side and were redone one by one (counted in [2]), [7] of the items in [1], those longer than one
         input block ([6] and [7]: long_items=True and quick_long_items=True only; the items quick_items=True takes side by side

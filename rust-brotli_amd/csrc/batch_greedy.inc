@@ -255,7 +255,7 @@ BatchParseJob GreedyJob(const EncoderParams& p, const Lz77Params& P, Group& g, u
 // quick_table_words per wavefront; `records` is the caller's to set
 QuickBatchJob QuickGroupJob(const QuickBatchJob& chains, Group& g) {
   QuickBatchJob J = chains;
-  J.Q.table = g.mem.uninit<uint32_t>((size_t)g.tables * QuickTableBytes(J) + 64);  // (every chain zeroes its table in front of every item)
+  J.Q.table = g.mem.uninit<uint32_t>((size_t)g.tables * QuickTableBytes(J) + 64);  // (every chain fills its whole table in front of every item: zeros, or the dictionary's image)
   J.text = g.uploaded;
   J.slabs = g.mem.uninit<Command>(g.cmd_slots * sizeof(Command) + 64);
   J.items = g.items_dev;
@@ -491,7 +491,7 @@ bool BatchQuickEligible(const EncoderParams& user, size_t input_size) {
   return (p.hasher.type == 2 || p.hasher.type == 3 || p.hasher.type == 4) && input_size <= ((size_t)1 << p.lgblock);
 }
 
-// Qualities 2 .. 4 (batch_quick.h), items of one block.  (The quick kernel leaves bad_commands at 0: no stream is dropped.)
+// Qualities 2 .. 4 (batch_quick.h), items of one block.  (The plain quick kernel leaves bad_commands at 0: no stream is dropped.)
 void BatchQuickCompress(const EncoderParams& user, size_t count, const uint8_t* const* inputs, const size_t* sizes,
                         std::vector<std::vector<uint8_t>>* streams, uint32_t* groups) {
   streams->assign(count, std::vector<uint8_t>());
@@ -510,6 +510,69 @@ void BatchQuickCompress(const EncoderParams& user, size_t count, const uint8_t* 
     J.records = g.mem.uninit<BatchRecord>((size_t)g.n * sizeof(BatchRecord));
     lz77_quick_batch_parse(J);
     FinishOneBlockItems(p, GatherJobOf(J), g, streams, nullptr);
+    first = g.last;
+  }
+}
+
+bool BatchQuickDictionaryEligible(const EncoderParams& user, size_t dict_size, size_t input_size) {
+  if (input_size == 0 || input_size > ((size_t)1 << 16) || dict_size < 2) return false;
+  if (user.quality < 2 || user.quality > 4 || user.lgwin < 10 || user.lgwin > 24 || !PlainStreamParams(user)) return false;
+  // (the reference cuts the dictionary to its last (1 << lgwin) - 16 bytes: dictionary + item stay inside the first lap of the
+  // ring buffer, 1 << (1 + max(lgwin, lgblock)), so no filed position differs from its ring-buffer index)
+  const EncoderParams p = DictionaryItemParams(user, input_size);
+  return (p.hasher.type == 2 || p.hasher.type == 3 || p.hasher.type == 4) && input_size <= ((size_t)1 << p.lgblock) &&
+         std::min(dict_size, ((size_t)1 << p.lgwin) - 16) <= ((size_t)1 << 16);
+}
+
+// Qualities 2 .. 4 behind a shared custom dictionary (batch_quick.h), items of one block: the steps of BatchQuickCompress with the
+// dictionary steps of CompressGroups.  Once per call the dictionary goes up and the table HasherPrependCustomDictionary leaves is
+// built on a scratch table (the image: each slot the largest position filed under it, the books 0; a dictionary of 2 .. 7 bytes
+// files nothing, but positions still count from its first byte); every chain copies it over its own table.
+void BatchQuickCompressWithDictionary(const EncoderParams& user, const uint8_t* dict, size_t dict_use, size_t count,
+                                      const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
+                                      std::vector<uint8_t>* reference_fails, uint32_t* groups) {
+  streams->assign(count, std::vector<uint8_t>());
+  reference_fails->assign(count, 0);
+  *groups = 0;
+  if (count == 0) return;
+  if (dict_use < 2 || dict_use > ((size_t)1 << 16)) throw std::runtime_error("brotli_mi355x: a dictionary the quick batch chains do not take");
+  const EncoderParams p = DictionaryItemParams(user, sizes[0]);  // (nothing in the parameters differs between items of at most one block)
+  QuickBatchJob chains = QuickChains(p);  // (no static dictionary behind a custom one: Q.use_dictionary is 0)
+  const uint32_t D = (uint32_t)dict_use;
+  chains.dict_bytes = D;
+  const size_t tables_max = TablesMax(QuickTableBytes(chains));
+
+  DevBlocks call_mem;
+  // (shifted so that it ends on a 16-byte boundary, like its copies in the padded text: k_batch_dict_text moves whole words)
+  uint8_t* dict_shifted = call_mem.zeroed<uint8_t>((size_t)D + 16 + 64);
+  uint8_t* dict_dev = dict_shifted + ((0u - D) & 15u);
+  dev_h2d_bulk(dict_dev, dict, D);
+  {
+    QuickJob image = chains.Q;
+    image.table = call_mem.uninit<uint32_t>(QuickTableBytes(chains) + 64);
+    lz77_quick_init(image);
+    Lz77Buffers B{};
+    B.text = dict_dev;  // (every filed position hashes dictionary bytes only)
+    lz77_quick_prepend(chains.P, B, image, D);
+    chains.image = image.table;
+  }
+
+  CallArrays A;
+  size_t first = 0;
+  while (first < count) {
+    Group g;
+    StageGroup(first, count, inputs, sizes, D, tables_max, &A, &g);
+    ++*groups;
+    uint8_t* text = g.mem.zeroed<uint8_t>(g.padded + 64);
+    uint32_t* starts_dev = g.mem.uninit<uint32_t>((size_t)g.n * 4);
+    dev_h2d(starts_dev, A.starts.data(), (size_t)g.n * 4);
+    lz77_batch_dict_text(dict_shifted, D, g.uploaded, starts_dev, g.items_dev, g.n, text);
+    QuickBatchJob J = QuickGroupJob(chains, g);
+    J.text = text;
+    J.records = g.mem.uninit<BatchRecord>((size_t)g.n * sizeof(BatchRecord));
+    lz77_quick_batch_parse_dict(J);
+    // (the gather reads raw commands, whose distance codes the chain took from positions that count the dictionary: it needs no D)
+    FinishOneBlockItems(p, GatherJobOf(J), g, streams, reference_fails);
     first = g.last;
   }
 }

@@ -30,9 +30,17 @@ struct QuickBatchJob {
   uint32_t tables;
   uint32_t* counter;  // [1], zero: the next place of `order` to hand out
   BatchRecord* records;
+  // behind a shared custom dictionary (lz77_quick_batch_parse_dict); 0 / nullptr for every other launch
+  uint32_t dict_bytes;    // D: every item's text is dictionary | item, text_off names the item's first byte; positions count from
+                          // the dictionary's first byte
+  const uint32_t* image;  // [quick_table_words(Q)], 16-byte aligned: the table lz77_quick_init + lz77_quick_prepend leave for the
+                          // dictionary (slots and books), which every chain copies over its own table in front of every item
 };
 // one wavefront per table; a wavefront takes items from `counter` until none is left
 void lz77_quick_batch_parse(const QuickBatchJob& J);
+// the same launch for items behind a shared custom dictionary (J.dict_bytes >= 2, J.image): a chain starts on the image instead of
+// a zeroed table and cuts its matches at the dictionary's end; BatchRecord::bad_commands flags the items the reference fails on
+void lz77_quick_batch_parse_dict(const QuickBatchJob& J);
 
 // ---- items of several blocks (BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS): an item of two to kBatchLongBlocks input blocks is still
 // ONE chain on a private table -- br_quick_block block after block, with the books between the blocks that the host resolver keeps
@@ -54,6 +62,15 @@ void BatchQuickLongCompress(const EncoderParams& params, size_t count, const uin
 // The streams of `count` eligible items.  Throws std::runtime_error on a device error.  *groups: device groups run.
 void BatchQuickCompress(const EncoderParams& params, size_t count, const uint8_t* const* inputs, const size_t* sizes,
                         std::vector<std::vector<uint8_t>>* streams, uint32_t* groups);
+// Behind a shared custom dictionary (BrotliMi355xCompressBatchWithDictionaryEx with BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS): does
+// this item of at most one input block go side by side?  dict_size: as the caller gave it, before the reference's truncation.
+bool BatchQuickDictionaryEligible(const EncoderParams& params, size_t dict_size, size_t input_size);
+// The streams of `count` such items: item i is the stream of BrotliEncoderSetCustomDictionary + one FINISH.  dict, dict_use: the
+// dictionary bytes in use (2 .. 65536, after the truncation).  (*reference_fails)[i] != 0: the reference itself fails on item i (a
+// copy of one byte at the dictionary end); its stream stays empty.
+void BatchQuickCompressWithDictionary(const EncoderParams& params, const uint8_t* dict, size_t dict_use, size_t count,
+                                      const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
+                                      std::vector<uint8_t>* reference_fails, uint32_t* groups);
 
 }  // namespace brotli_mi355x
 #endif

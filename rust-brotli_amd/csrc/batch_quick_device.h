@@ -26,8 +26,39 @@ BR_DEV void br_quick_batch_zero(uint32_t* table, uint32_t words /* a multiple of
   BR_SYNC();
 }
 
+// The hasher as HasherPrependCustomDictionary left it, on a table that the item in front has used: the image of the call
+// (QuickBatchJob::image -- what the prepend leaves hangs on the dictionary alone) goes over ALL words of the table, the books
+// included.  16 bytes per lane and step, four steps in flight: the loads of a round are issued together, then its stores.  The
+// image is read-only for the launch (plain loads; it stays in the L2); the copy is made visible as the zero fill is.
+BR_DEV void br_quick_batch_prime(uint32_t* table, const uint32_t* image, uint32_t words /* a multiple of 16 */) {
+  BR_SYNC();
+#if BR_SCALAR
+  memcpy(table, image, (size_t)words * 4);
+#else
+  uint4* w = (uint4*)table;
+  const uint4* src = (const uint4*)image;
+  const uint32_t quads = words >> 2;
+  for (uint32_t i = (uint32_t)BR_LANE; i < quads; i += 4u * BR_NLANES) {
+    const uint32_t i1 = i + BR_NLANES, i2 = i + 2u * BR_NLANES, i3 = i + 3u * BR_NLANES;
+    const uint4 v0 = src[i];
+    const uint4 v1 = src[i1 < quads ? i1 : i];
+    const uint4 v2 = src[i2 < quads ? i2 : i];
+    const uint4 v3 = src[i3 < quads ? i3 : i];
+    w[i] = v0;
+    if (i1 < quads) w[i1] = v1;
+    if (i2 < quads) w[i2] = v2;
+    if (i3 < quads) w[i3] = v3;
+  }
+  __threadfence();
+#endif
+  BR_SYNC();
+}
+
 // T: the static-dictionary tables; logs: should_compress; histo: 256 words and exit_slot: one SegExit, both the wavefront's own
 // (LDS on the device).
+// kDict: the item's text starts with J.dict_bytes bytes of custom dictionary (BrotliMi355xCompressBatchWithDictionaryEx) and its
+// chain starts on J.image.
+template <bool kDict = false>
 BR_DEV void br_quick_batch_item(const QuickBatchJob& J, const QuickTables& T, const EntropyTables& logs, uint32_t* histo, SegExit* exit_slot,
                                 uint32_t index, uint32_t table) {
   BatchItem it = J.items[index];
@@ -38,27 +69,35 @@ BR_DEV void br_quick_batch_item(const QuickBatchJob& J, const QuickTables& T, co
   QuickJob Q = J.Q;
   const uint32_t words = quick_table_words(Q);
   Q.table = J.Q.table + (size_t)table * words;
-  br_quick_batch_zero(Q.table, words);
+  if constexpr (kDict) {
+    br_quick_batch_prime(Q.table, J.image, words);
+  } else {
+    br_quick_batch_zero(Q.table, words);
+  }
   // item-local coordinates: position 0 is the item's first byte, so no distance reaches a neighbour and max_backward is what
   // the reference computes for a stream that starts at 0.  The last searched position is bytes - 9 (its lazy successor
   // bytes - 8): the 8-byte loads of q_key end inside the item, the 16-byte loads of br_match_len_wide inside its padding.
+  // (with a dictionary: position 0 is the dictionary's first byte and the item starts at D, as in the reference's ring buffer;
+  // D + bytes stays inside the first lap of the ring: D < 1 << lgwin, bytes <= 1 << lgblock, the ring has 1 + max of the two bits)
+  const uint32_t D = kDict ? BR_UNIFORM(J.dict_bytes) : 0u;
   Lz77Params P = J.P;
-  P.total_bytes = it.bytes;
-  // known here, whatever the job says: no custom dictionary in front of an item, the literal-spree window of qualities below 9,
-  // five hashed bytes (H2, H3, H4) -- constants the compiler folds, registers the chain does not hold
-  P.prefix_bytes = P.dict_break = 0;
+  P.total_bytes = D + it.bytes;
+  // known here, whatever the job says: without kDict no custom dictionary in front of an item, the literal-spree window of
+  // qualities below 9, five hashed bytes (H2, H3, H4) -- constants the compiler folds, registers the chain does not hold
+  // (with a dictionary matches may not straddle its end: q_fix_len; br_quick_block counts the copies of one byte that leaves)
+  P.prefix_bytes = P.dict_break = D;
   P.spree_window = 64;
   Q.hash_len = 5;
-  const uint8_t* text = J.text + it.text_off;
+  const uint8_t* text = J.text + it.text_off - D;
   Segment seg;
-  seg.start = seg.blk_start = 0;
-  seg.end = seg.blk_end = it.bytes;
+  seg.start = seg.blk_start = D;
+  seg.end = seg.blk_end = D + it.bytes;
   seg.flags = kSegFirstInBlock | kSegLastInBlock;
   seg.cmd_base = it.cmd_base;
   seg.block_index = 0;
   seg.cmd_cap = it.cmd_cap;
   SegEntry entry;
-  entry.pos = 0;
+  entry.pos = D;
   entry.apply = P.spree_window;
   entry.cache[0] = 4;
   entry.cache[1] = 11;
@@ -72,6 +111,7 @@ BR_DEV void br_quick_batch_item(const QuickBatchJob& J, const QuickTables& T, co
   entry.head_kind = kHeadNone;
   entry.head_base = entry.head_p1 = 0;
   entry.pad = 0;
+  // (with a dictionary br_quick_block files the last three dictionary positions itself: StitchToPreviousBlock, mod.rs:210-222)
   br_quick_block(Q, P, T, text, seg, entry, J.slabs + (size_t)it.cmd_base, exit_slot);
   BR_SYNC();  // (lane 0 wrote the exit)
   // ---- Lz77Stage::Resolve for the only block of a stream: the pending literals become the trailing insert-only command, and
@@ -85,7 +125,7 @@ BR_DEV void br_quick_batch_item(const QuickBatchJob& J, const QuickTables& T, co
     BR_SYNC();
     for (uint32_t i = BR_LANE; i < 256; i += BR_NLANES) histo[i] = 0;
     BR_SYNC();
-    for (uint32_t q = 13u * (uint32_t)BR_LANE; q < bytes; q += 13u * BR_NLANES) BR_ATOMIC_INC(&histo[text[q]]);
+    for (uint32_t q = 13u * (uint32_t)BR_LANE; q < bytes; q += 13u * BR_NLANES) BR_ATOMIC_INC(&histo[text[D + q]]);
     BR_SYNC();
     const float threshold = (float)bytes * 7.92f / 13.0f;
     compress = !(br_bits_entropy(logs, histo, 256) > threshold);
@@ -98,6 +138,17 @@ BR_DEV void br_quick_batch_item(const QuickBatchJob& J, const QuickTables& T, co
     r.uncompressed = compress ? 0u : 1u;
     r.overflow = cmds_all > it.cmd_cap ? 1u : 0u;
     r.bad_commands = 0;
+    if constexpr (kDict) {
+      // a copy of one byte: the reference cannot encode it (GetCopyLengthCode, command.rs:91-93) and neither do the tables behind
+      // br_finish_command -- the item is handed on as literals only and flagged, as br_batch_item does
+      r.bad_commands = exit_slot->bad_commands;
+      if (r.bad_commands != 0) {
+        r.n_cmds = 1;
+        r.n_lits = r.trailing = bytes;
+        r.uncompressed = 1;
+        r.overflow = 0;
+      }
+    }
     r.pad[0] = r.pad[1] = 0;
     J.records[index] = r;
   }

@@ -2,6 +2,8 @@
 // into the emulation build only (BROTLI_HOST_EMU, tests/emu; batch_greedy.inc includes it there): the same item code
 // (batch_quick_device.h) on plain memory, one item after the other in the order of the plan, the tables taken in turn -- so that
 // a table serves several items, as on the device.  The gather is lz77_batch_gather (batch_greedy_emu.inc).
+// lz77_quick_batch_parse_dict: the same loop over the item code behind a shared custom dictionary (the image is the emulation's
+// lz77_quick_init + lz77_quick_prepend, i.e. br_quick_prepend).
 // lz77_quick_batch_parse_long: the same loop over the item code of the items of several blocks; its gather is lz77_batch_gather_long.
 #include <stdexcept>
 
@@ -24,6 +26,24 @@ void lz77_quick_batch_parse(const QuickBatchJob& J) {
   uint32_t histo[256];
   SegExit exit_slot;
   for (uint32_t place = 0; place < J.n_items; ++place) br_quick_batch_item(J, T, logs, histo, &exit_slot, J.order[place], place % J.tables);
+  *J.counter = J.n_items;
+}
+
+void lz77_quick_batch_parse_dict(const QuickBatchJob& J) {
+  if (J.n_items == 0) return;
+  if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
+  if (J.dict_bytes == 0 || J.image == nullptr) throw std::runtime_error("brotli_mi355x: a dictionary batch group without its table image");
+  const DeviceTables& dt = dev_tables();
+  QuickTables T;
+  T.dict_hash = dt.dict_hash;
+  T.dict_data = dt.dict_data;
+  T.dict_offsets_by_length = dt.dict_offsets_by_length;
+  EntropyTables logs;
+  logs.logs_16 = dt.logs_16;
+  logs.logs_8 = dt.logs_8;
+  uint32_t histo[256];
+  SegExit exit_slot;
+  for (uint32_t place = 0; place < J.n_items; ++place) br_quick_batch_item<true>(J, T, logs, histo, &exit_slot, J.order[place], place % J.tables);
   *J.counter = J.n_items;
 }
 

@@ -1184,11 +1184,20 @@ static int CompressItemWithDictionary(int quality, int lgwin, BrotliEncoderMode 
   return 1;
 }
 
-int32_t BrotliMi355xCompressBatchWithDictionary(int quality, int lgwin, BrotliEncoderMode mode, size_t dict_size, const uint8_t* dict, size_t count,
-                                                const uint8_t* const* inputs, const size_t* input_sizes, uint8_t* const* outputs,
-                                                size_t* output_sizes, int32_t* item_results) {
+// BrotliMi355xCompressBatchWithDictionary (routes == 0) and BrotliMi355xCompressBatchWithDictionaryEx
+static int32_t CompressBatchWithDictionary(const char* entry, int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t dict_size,
+                                           const uint8_t* dict, size_t count, const uint8_t* const* inputs, const size_t* input_sizes,
+                                           uint8_t* const* outputs, size_t* output_sizes, int32_t* item_results) {
   uint64_t info[8] = {count, 0, 0, 0, 0, 0, 0, 0};
   memcpy(g_batch_info, info, sizeof(info));
+  if ((routes & ~(uint32_t)BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS) != 0) {
+    // a route this call does not know fails it as a whole, like an unknown route of BrotliMi355xCompressBatchEx
+    SetError(entry, ("routes " + std::to_string(routes) + " names a route this call does not know (known behind a dictionary: "
+                     "BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS = 4)").c_str());
+    for (size_t i = 0; i < count; ++i) output_sizes[i] = 0;
+    if (item_results && count) memset(item_results, 0, count * sizeof(int32_t));
+    return 0;
+  }
   if (count == 0) return 1;
   size_t total = 0;
   for (size_t i = 0; i < count; ++i) total += input_sizes[i];
@@ -1209,12 +1218,19 @@ int32_t BrotliMi355xCompressBatchWithDictionary(int quality, int lgwin, BrotliEn
     info[5] = dict_use;
     SmallCallGate gate(total);
     // Side by side: the items of 1 .. 65536 bytes at qualities 5 .. 8, lgwin 17 .. 24, behind a dictionary of 2 .. 65536 bytes
-    // (batch_greedy.h).  Every other item goes through the stream path by itself, on this thread, in the caller's order.
+    // (batch_greedy.h) and, where the caller asked for that route, the items of at most one input block at qualities 2 .. 4,
+    // lgwin 10 .. 24, behind at most 65536 dictionary bytes in use (batch_quick.h) -- a call has one quality, so its items take
+    // one of the two.  Every other item goes through the stream path by itself, on this thread, in the caller's order.
+    const bool quick_route = (routes & BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS) != 0;
+    bool quick = false;
     std::vector<size_t> item;
     std::vector<const uint8_t*> in;
     std::vector<size_t> in_size;
     for (size_t i = 0; i < count; ++i) {
-      if (BatchDictionaryEligible(params, dict_size, input_sizes[i])) {
+      const bool greedy_item = BatchDictionaryEligible(params, dict_size, input_sizes[i]);
+      const bool quick_item = !greedy_item && quick_route && BatchQuickDictionaryEligible(params, dict_size, input_sizes[i]);
+      if (quick_item) quick = true;
+      if (greedy_item || quick_item) {
         item.push_back(i);
         in.push_back(inputs[i]);
         in_size.push_back(input_sizes[i]);
@@ -1227,7 +1243,10 @@ int32_t BrotliMi355xCompressBatchWithDictionary(int quality, int lgwin, BrotliEn
       std::vector<std::vector<uint8_t>> streams;
       std::vector<uint8_t> reference_fails;
       uint32_t groups = 0;
-      BatchGreedyCompressWithDictionary(params, dict + (dict_size - dict_use), dict_use, item.size(), in.data(), in_size.data(), &streams, &reference_fails, &groups);
+      if (quick)
+        BatchQuickCompressWithDictionary(params, dict + (dict_size - dict_use), dict_use, item.size(), in.data(), in_size.data(), &streams, &reference_fails, &groups);
+      else
+        BatchGreedyCompressWithDictionary(params, dict + (dict_size - dict_use), dict_use, item.size(), in.data(), in_size.data(), &streams, &reference_fails, &groups);
       info[4] = groups;
       info[1] = item.size();
       for (size_t k = 0; k < item.size(); ++k) {
@@ -1235,7 +1254,7 @@ int32_t BrotliMi355xCompressBatchWithDictionary(int quality, int lgwin, BrotliEn
         const size_t capacity = output_sizes[i];
         output_sizes[i] = 0;
         if (reference_fails[k]) {
-          SetError("BrotliMi355xCompressBatchWithDictionary",
+          SetError(entry,
                    ("item " + std::to_string(i) + ": the reference encoder fails on this input: a match cut to one byte at the end of the custom dictionary "
                     "gives a copy it cannot encode (fix_unbroken_len, backward_references/mod.rs:42-54; GetCopyLengthCode, command.rs:91-93)").c_str());
           continue;
@@ -1248,7 +1267,7 @@ int32_t BrotliMi355xCompressBatchWithDictionary(int quality, int lgwin, BrotliEn
     }
   } catch (const std::exception& e) {
     // a device error fails the call as a whole
-    SetError("BrotliMi355xCompressBatchWithDictionary", e.what());
+    SetError(entry, e.what());
     for (size_t i = 0; i < count; ++i) output_sizes[i] = 0;
     if (item_results) memset(item_results, 0, count * sizeof(int32_t));
     return 0;
@@ -1260,6 +1279,20 @@ int32_t BrotliMi355xCompressBatchWithDictionary(int quality, int lgwin, BrotliEn
     if (!results[i]) all = 0;
   }
   return all;
+}
+
+int32_t BrotliMi355xCompressBatchWithDictionary(int quality, int lgwin, BrotliEncoderMode mode, size_t dict_size, const uint8_t* dict, size_t count,
+                                                const uint8_t* const* inputs, const size_t* input_sizes, uint8_t* const* outputs,
+                                                size_t* output_sizes, int32_t* item_results) {
+  return CompressBatchWithDictionary("BrotliMi355xCompressBatchWithDictionary", quality, lgwin, mode, 0, dict_size, dict, count, inputs, input_sizes, outputs,
+                                     output_sizes, item_results);
+}
+
+int32_t BrotliMi355xCompressBatchWithDictionaryEx(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t dict_size, const uint8_t* dict,
+                                                  size_t count, const uint8_t* const* inputs, const size_t* input_sizes, uint8_t* const* outputs,
+                                                  size_t* output_sizes, int32_t* item_results) {
+  return CompressBatchWithDictionary("BrotliMi355xCompressBatchWithDictionaryEx", quality, lgwin, mode, routes, dict_size, dict, count, inputs, input_sizes,
+                                     outputs, output_sizes, item_results);
 }
 
 void BrotliMi355xLastBatchInfo(uint64_t info[8]) { memcpy(info, g_batch_info, sizeof(g_batch_info)); }

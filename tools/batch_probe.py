@@ -38,6 +38,14 @@ parent's library is measured through BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS on th
 classes are 1024x32KiB and 1024x64KiB at quality 2 and 3, 1024x128KiB and 256x256KiB at quality 4, and the count sweep
 {16, 64, 256, 1024}x48KiB at quality 2 (QUICK_LONG_QUALITIES); --skip cpu,loop leaves out the oracle and the 4-thread loop.
 
+With --dictionary BYTES --quick-items (and --qualities 2,3,4) this build is called through BrotliMi355xCompressBatchWithDictionaryEx with
+BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS: behind the shared dictionary the items of at most one input block go side by side, one chain each on
+a table that starts as the dictionary's.  The parent's library is measured through BrotliMi355xCompressBatchWithDictionary on the first
+--loop-items items, scaled by item count -- there every item runs one by one through the stream path -- alternating with this build --rounds
+times; the CPU baseline is the oracle's dictionary stream.  The items the call fails alone (reference_fails_on_items) are checked
+against the oracle one by one: it must fail on each of them.  The classes are 4096x4KiB and 4096x512B, 1024x16KiB (qualities 2 and 3: one
+input block) and 64x4KiB, the few-items case.
+
 Every measurement runs in a child process of its own (the table's home is one setting per process, read once; the parent's library
 is another shared object), one after the other, each under its own time limit; the first failure ends the probe.
 
@@ -76,12 +84,17 @@ CLASSES = {
     "64x48KiB": ("uniform", 64, 48 << 10),
     "256x48KiB": ("uniform", 256, 48 << 10),
     "1024x48KiB": ("uniform", 1024, 48 << 10),
+    # behind a shared dictionary at qualities 2 to 4 (--dictionary N --quick-items)
+    "1024x16KiB": ("uniform", 1024, 16 << 10),
+    "64x4KiB": ("uniform", 64, 4 << 10),
 }
 HEADLINE = ["4096x4KiB", "4096x16KiB", "1024x64KiB", "64xalice29", "4096xlog200B-256KiB"]
 AB = ["4096x512B", "4096x2KiB", "4096xlog200B-256KiB"]
 # (--quick-long-items) the qualities at which a class is made of items of two to four input blocks
 QUICK_LONG_QUALITIES = {"1024x32KiB": (2, 3), "1024x64KiB": (2, 3), "1024x128KiB": (4,), "256x256KiB": (4,),
                         "16x48KiB": (2,), "64x48KiB": (2,), "256x48KiB": (2,), "1024x48KiB": (2,)}
+DICT_QUICK_HEADLINE = ["4096x4KiB", "4096x512B", "1024x16KiB", "64x4KiB"]  # (--dictionary N --quick-items)
+DICT_QUICK_QUALITIES = {"1024x16KiB": (2, 3)}  # (one input block at quality 2 and 3)
 QUICK_HEADLINE = ["4096x4KiB", "4096x16KiB", "1024x64KiB", "4096x512B", "4096xlog200B-256KiB"]  # (--quick-items)
 
 
@@ -131,6 +144,8 @@ def measure_batch(lib_path, items, quality, runs, warmup, dictionary=None, route
         L.BrotliMi355xCompressBatchEx.restype = ctypes.c_int32
     if dictionary is not None:
         L.BrotliMi355xCompressBatchWithDictionary.restype = ctypes.c_int32
+        if routes:
+            L.BrotliMi355xCompressBatchWithDictionaryEx.restype = ctypes.c_int32
     info = (ctypes.c_uint64 * 8)()
     n = len(items)
     caps = [L.BrotliEncoderMaxCompressedSize(len(x)) + (16 if dictionary is None else 1024) for x in items]
@@ -147,7 +162,10 @@ def measure_batch(lib_path, items, quality, runs, warmup, dictionary=None, route
         for i in range(n):
             out_sizes[i] = caps[i]
         t = time.perf_counter()
-        if routes:
+        if routes and dictionary is not None:
+            ok = L.BrotliMi355xCompressBatchWithDictionaryEx(quality, LGWIN, 0, ctypes.c_uint32(routes), ctypes.c_size_t(len(dictionary)), ctypes.c_char_p(dictionary),
+                                                             ctypes.c_size_t(n), inputs, in_sizes, outputs, out_sizes, results)
+        elif routes:
             ok = L.BrotliMi355xCompressBatchEx(quality, LGWIN, 0, ctypes.c_uint32(routes), ctypes.c_size_t(n), inputs, in_sizes, outputs, out_sizes, None)
         elif dictionary is None:
             ok = L.BrotliMi355xCompressBatch(quality, LGWIN, 0, ctypes.c_size_t(n), inputs, in_sizes, outputs, out_sizes, None)
@@ -256,6 +274,8 @@ def child(args):
             for quality in [int(q) for q in args.qualities.split(",")]:
                 if args.quick_long_classes and quality not in QUICK_LONG_QUALITIES.get(name, ()):
                     continue
+                if args.dictionary and quality not in DICT_QUICK_QUALITIES.get(name, (quality,)):
+                    continue
                 row = {"class": name, "data": data, "quality": quality, "items": len(items), "bytes": sum(map(len, items))}
                 if args.child == "batch":
                     times, csize, info, failed = measure_batch(args.lib, first if args.first_only else items, quality, args.runs, args.warmup, dictionary,
@@ -348,6 +368,77 @@ def main_dictionary(args, doc, save, classes):
     print(json.dumps(doc, indent=1))
 
 
+def verify_flagged_items(args, rows):
+    """The items the batch call failed alone, against the oracle, on this host's CPU: the reference's dictionary stream must fail on
+    every one of them, and on none of as many of its neighbours (the parent's loop and the CPU baseline run the first --loop-items
+    items only, which need not hold any of them)."""
+    os.environ["ORC_FAST"] = "1"
+    import orc
+    for k, v in rows.items():
+        flagged = v["reference_fails_on_items"]
+        v["reference_fails_on_items_verified"] = "none flagged"
+        if not flagged:
+            continue
+        name, data, quality = k.split("/")
+        items = items_of(name, data)
+        dictionary = dictionary_of(data, args.dictionary)
+
+        def fails(i):
+            try:
+                orc.stream_with_flushes(items[i], [(0, 0), (1, int(quality[1:])), (2, LGWIN)], [], dictionary=dictionary)
+            except orc.ReferencePanics:
+                return True
+            return False
+
+        neighbours = [i + 1 for i in flagged if i + 1 < len(items) and i + 1 not in flagged]
+        assert all(fails(i) for i in flagged), (k, "the batch call failed an item the oracle encodes")
+        assert not any(fails(i) for i in neighbours), (k, "the oracle fails on an item the batch call encoded")
+        v["reference_fails_on_items_verified"] = "the oracle fails on all %d flagged items and on none of %d neighbours" % (len(flagged), len(neighbours))
+
+
+def main_dictionary_quick(args, doc, save, classes):
+    doc["what"] = ("BrotliMi355xCompressBatchWithDictionaryEx(BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS) behind %d bytes of dictionary vs the parent commit's "
+                   "BrotliMi355xCompressBatchWithDictionary on the same items, there one by one through the stream path, vs the oracle's dictionary "
+                   "stream on one CPU core; lgwin 22" % args.dictionary)
+    rows = {}
+    for rnd in range(args.rounds):
+        for row in run_child(args, "batch", classes, limit=900, quick_items=True):
+            this = {k: row[k] for k in ("median_ms", "min_ms", "max_ms", "spread_pct", "runs")}
+            if rnd == 0:
+                rows[key(row)] = {"items": row["items"], "bytes": row["bytes"], "dictionary_bytes": args.dictionary, "compressed_bytes": row["compressed_bytes"],
+                                  "batch_info": row["batch_info"], "reference_fails_on_items": row["reference_fails_on_items"], "batch": this}
+            rows[key(row)].setdefault("batch_rounds", []).append(this)
+            assert row["reference_fails_on_items"] == rows[key(row)]["reference_fails_on_items"], row  # (the same items in every round)
+        doc["classes"] = rows
+        save()
+        if args.parent_lib:
+            for row in run_child(args, "batch", classes, lib=os.path.abspath(args.parent_lib), limit=900, first_only=True):
+                scale = row["items"] / row["measured_items"]
+                rows[key(row)].setdefault("parent_batch_rounds", []).append({"median_ms_scaled": round(row["median_ms"] * scale, 3), "min_ms_scaled": round(row["min_ms"] * scale, 3),
+                                                                           "max_ms_scaled": round(row["max_ms"] * scale, 3), "spread_pct": row["spread_pct"], "measured_items": row["measured_items"]})
+            save()
+    for row in ([] if "cpu" in args.skip.split(",") else run_child(args, "cpu", classes, limit=900)):
+        scale = row["items"] / row["measured_items"]
+        rows[key(row)]["cpu_one_core"] = {"median_ms_scaled": round(row["median_ms"] * scale, 3), "measured_items": row["measured_items"], "spread_pct": row["spread_pct"]}
+    verify_flagged_items(args, rows)
+    for k, v in rows.items():
+        b = statistics.median(r["median_ms"] for r in v["batch_rounds"])
+        # (compressed_bytes and MB/s cover the whole class: an item the reference fails on is parsed like any other and leaves no stream)
+        v["batch_MBps"] = round(v["bytes"] / 1e3 / b, 1)
+        v["cpu_over_batch"] = round(v["cpu_one_core"]["median_ms_scaled"] / b, 3) if "cpu_one_core" in v else "not measured"
+        if v.get("parent_batch_rounds"):
+            parent = v["parent_batch_rounds"]
+            worst_batch, best_batch = max(r["max_ms"] for r in v["batch_rounds"]), min(r["min_ms"] for r in v["batch_rounds"])
+            v["parent_batch_over_batch"] = {"median": round(statistics.median(r["median_ms_scaled"] for r in parent) / b, 2),
+                                            "min": round(min(r["min_ms_scaled"] for r in parent) / worst_batch, 2),
+                                            "max": round(max(r["max_ms_scaled"] for r in parent) / best_batch, 2)}
+            v["every_run_beats_every_parent_run"] = bool(worst_batch < min(r["min_ms_scaled"] for r in parent))
+        else:
+            v["parent_batch_over_batch"] = "not measured"
+    save()
+    print(json.dumps(doc, indent=1))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lib", default=os.path.join(ROOT, "rust-brotli_amd", "libbrotli_mi355x.so"))
@@ -396,6 +487,8 @@ def main():
     if args.quick_long_items:
         doc["what"] = ("BrotliMi355xCompressBatchEx(BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS | BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS) vs the parent commit's "
                        "BrotliMi355xCompressBatchEx(BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS), there one by one; items of two to four input blocks; lgwin 22")
+    if args.dictionary and args.quick_items:
+        return main_dictionary_quick(args, doc, save, [c for c in DICT_QUICK_HEADLINE if not args.only or c in args.only.split(",")])
     if args.dictionary:
         return main_dictionary(args, doc, save, [c for c in ("4096x4KiB", "1024x64KiB") if not args.only or c in args.only.split(",")])
     fragment_qualities = set(args.qualities.split(",")) <= {"0", "1"}
