@@ -204,7 +204,7 @@ BROTLI_BOOL BrotliMi355xCompressDevice(int quality, int lgwin, BrotliEncoderMode
      qualities 5 .. 8:  the items of at most one input block (65 536 bytes) at lgwin 17 .. 24 -- one parse chain and one
                         meta-block each, thousands of them in flight, one upload and one download per group of up to 4096 items.
    Every other item -- qualities 2 .. 4 (but see BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS of BrotliMi355xCompressBatchEx) and
-   9 .. 11, lgwin <= 16 or > 24, items longer than one input block -- is accepted and
+   9 .. 11 (but see BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS there), lgwin <= 16 or > 24, items longer than one input block -- is accepted and
    runs by itself through the one-shot path on the calling thread, in the same call and in the caller's order: the same bytes,
    no gain in speed.  Both kinds may be mixed in one call; BrotliMi355xLastBatchInfo tells how a call was taken.
    Environment (read once per process): BROTLI_MI355X_BATCH_GROUP_ITEMS / BROTLI_MI355X_BATCH_GROUP_BYTES bound a group of
@@ -275,10 +275,29 @@ int32_t BrotliMi355xCompressBatchWithDictionary(int quality, int lgwin, BrotliEn
    its own dependent loads, so an item of several blocks takes a lone chain's time however many items run beside it; the route
    pays with many such items in a call (dynamic responses of 20 to 64 KiB at quality 2 / 3; see INTEGRATION.md for measured
    figures) and loses with a few.  Not combined with a shared dictionary.
-   The bits may be combined.  The values 2 and 8 are reserved: they name no route and fail the call like any unknown bit. */
+   BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS: item i still gets exactly what BrotliEncoderCompress gives.  In addition, an item with
+   1 <= input_sizes[i] <= 65 536 at quality 11 and lgwin 10 .. 24 -- always at most one input block, lgblock is at least 16 at
+   this quality -- runs on the device as ONE wavefront that walks the item the reference's way (H10 trees, matches and the Zopfli
+   shortest-path programme position by position) on private trees, side by side with the other such items of the call (groups of
+   their own, of at most 1024 items: what the quality >= 10 meta-block builder sets aside per item; as many tables as stay
+   resident, 256, within 8 GiB, a table sized by its group's largest item), and leaves one meta-block.  Every other item goes as in
+   the plain call.  The bit changes nothing at qualities 0 .. 10.  Quality 10 is not taken: BrotliEncoderCompress runs it at
+   quality 9, as the reference's one-shot entry does, so the bytes an item of quality 10 is owed are not those of a Zopfli walk.  Such
+   items count in info[1], their groups in info[4]; nothing is redone, info[6] and info[7] stay 0 for them.  An item on which the
+   reference encoder itself panics fails alone with "the reference encoder fails on this input", as under
+   BrotliMi355xCompressBatchWithDictionary.  When to set it: with hundreds of small static files in a call (pre-compression at
+   the level used for it).  A walk is one wavefront bound by its own dependent loads and takes a lone walk's time however many
+   run beside it (about 37 us per byte: 150 ms for 4 KiB, 2.4 s for 64 KiB), so the call lasts as long as its largest item's walk
+   times the items per table.  Measured: 1024 items of 4 KiB in 0.6 s against 89 s one by one, 16 of them in 0.16 s against 1.4 s.
+   When not: for one or two items the one-shot path, which finds a lone item's matches side by side, is as fast or faster; and a
+   handful of small items is done sooner on one CPU core than on the device either way (see INTEGRATION.md for measured
+   figures).  Not combined with a shared dictionary.
+   The bits may be combined.  The values 2 and 8 are reserved: they name no route and fail the call like any unknown bit, as do 64
+   and above. */
 #define BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS 1u
 #define BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS 4u /* (2u is reserved and stays an unknown route) */
 #define BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS 16u /* (8u stays an unknown route, like 2u) */
+#define BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS 32u
 int32_t BrotliMi355xCompressBatchEx(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t count,
                                     const uint8_t* const* inputs, const size_t* input_sizes, uint8_t* const* outputs,
                                     size_t* output_sizes /* in: capacity, out: size */, int32_t* item_results /* may be NULL */);
@@ -319,7 +338,7 @@ int32_t BrotliMi355xCompressBatchWithDictionaryEx(int quality, int lgwin, Brotli
    [6] items that began side by side and were redone one by one (counted in [2], not in [1]), [7] of the items counted in [1],
    those longer than one input block; [6] and [7] are zero unless BrotliMi355xCompressBatchEx was called with
    BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS or BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS (the items of
-   BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS count in [1] and [4] only).  After a call that failed as a whole only info[0] is set. */
+   BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS and BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS count in [1] and [4] only).  After a call that failed as a whole only info[0] is set. */
 void BrotliMi355xLastBatchInfo(uint64_t info[8]);
 /* Human-readable description of the device backing the library ("hip:gfx950 (...)"). */
 const char* BrotliMi355xDeviceName(void);

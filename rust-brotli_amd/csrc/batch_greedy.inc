@@ -10,10 +10,12 @@
 #include <stdexcept>
 
 #include "batch_quick.h"
+#include "batch_zopfli.h"
 #include "device_api.h"
 #if defined(BROTLI_HOST_EMU)
 #include "batch_greedy_emu.inc"  // the host emulation of lz77_batch_parse / lz77_batch_gather
 #include "batch_quick_emu.inc"   // ... and of lz77_quick_batch_parse
+#include "batch_zopfli_emu.inc"  // ... and of lz77_zopfli_batch_parse
 #endif
 
 namespace brotli_mi355x {
@@ -169,13 +171,15 @@ struct Group {
   uint32_t* order_dev;
 };
 // D: the bytes of the call's dictionary (0: none), which go in front of every item in the padded text
+// max_items: a bound of the route's own on the items of a group, below BROTLI_MI355X_BATCH_GROUP_ITEMS (0: none)
 void StageGroup(size_t first, size_t count, const uint8_t* const* inputs, const size_t* sizes, uint32_t D, size_t tables_max,
-                CallArrays* arrays, Group* g) {
+                CallArrays* arrays, Group* g, size_t max_items = 0) {
   CallArrays& A = *arrays;
   const uint32_t dict_room = (D + 63u) & ~63u;
   // (the limit counts the dictionary copies of the padded text: scratch -- keys and flags -- grows with them)
   size_t last = first, padded = 0, packed = 0;
-  while (last < count && last - first < Limits().group_items &&
+  const size_t group_items = max_items ? std::min(max_items, Limits().group_items) : Limits().group_items;
+  while (last < count && last - first < group_items &&
          (last == first || packed + (last - first + 1) * (size_t)D + sizes[last] <= Limits().group_bytes)) {
     padded += dict_room + Padded((uint32_t)sizes[last]);
     packed += sizes[last];
@@ -606,6 +610,65 @@ void BatchQuickLongCompress(const EncoderParams& user, size_t count, const uint8
     BatchLongRecord* records_dev = g.mem.uninit<BatchLongRecord>((size_t)g.n * sizeof(BatchLongRecord));
     lz77_quick_batch_parse_long(J, records_dev);
     FinishLongItems(p, GatherJobOf(J), records_dev, inputs, g, streams, demoted);
+    first = g.last;
+  }
+}
+
+bool BatchZopfliEligible(const EncoderParams& user, size_t input_size) {
+  if (input_size == 0) return false;  // (answered without an encoder)
+  // Quality 11 alone.  An item is what BrotliEncoderCompress gives, and that entry runs quality 10 at quality 9
+  // (encode.rs:1468-1481): the stream of plain quality 9 -- bytes a Zopfli walk does not give.  Such items stay one by one.
+  if (user.quality != 11 || user.lgwin < 10 || user.lgwin > 24 || !PlainStreamParams(user)) return false;
+  if (input_size > ((size_t)1 << 16)) return false;  // (at most one input block: lgblock is at least 16 at this quality)
+  const EncoderParams p = ItemParams(user, input_size);
+  return p.quality == 11 && p.hasher.type == 10 && input_size <= ((size_t)1 << p.lgblock);
+}
+
+// Quality 11 (batch_zopfli.h), items of one block: StageGroup, the parse launch on tables sized by the group's largest
+// item, FinishOneBlockItems with the quality >= 10 meta-block builder.  A group holds at most kBatchHqGroupItems items (what that
+// builder sets aside per meta-block); the tables are as many as stay resident (kZopfliBatchResident) within 8 GiB.
+void BatchZopfliCompress(const EncoderParams& user, size_t count, const uint8_t* const* inputs, const size_t* sizes,
+                         std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* reference_fails, uint32_t* groups) {
+  streams->assign(count, std::vector<uint8_t>());
+  reference_fails->assign(count, 0);
+  *groups = 0;
+  if (count == 0) return;
+  const EncoderParams p = ItemParams(user, sizes[0]);  // (nothing in the parameters differs between items of at most one block)
+  ZopfliBatchJob chains{};
+  chains.P = ChainParams(p);
+  chains.P.hasher_kind = 6;  // (what Lz77Stage::Setup gives every hasher but H5 and H9; the Zopfli walk does not look at it)
+  chains.quality = (uint32_t)p.quality;
+  chains.lgwin = (uint32_t)p.lgwin;
+  chains.use_dictionary = p.use_dictionary ? 1 : 0;
+  chains.dist_alphabet_size = p.dist.alphabet_size;
+  CallArrays A;
+  size_t first = 0;
+  while (first < count) {
+    Group g;
+    // (the tables hang on the group's largest item, which the staging finds: staged for the most tables a group can have, then cut)
+    StageGroup(first, count, inputs, sizes, 0, kZopfliBatchResident, &A, &g, kBatchHqGroupItems);
+    ++*groups;
+    ZopfliBatchJob J = chains;
+    zopfli_batch_layout(&J, A.items[A.order[0]].bytes);
+    // (TablesMax: 8 GiB, or BROTLI_MI355X_BATCH_TABLES; more tables than stay resident would only wait for a CU, whoever asks)
+    g.tables = (uint32_t)std::min<size_t>(std::min<size_t>(kZopfliBatchResident, TablesMax(J.table_bytes)), g.n);
+    J.table_mem = g.mem.uninit<uint8_t>((size_t)g.tables * J.table_bytes + 256);  // (a chain empties its hasher itself; everything else it writes before it reads)
+    J.text = g.uploaded;
+    J.slabs = g.mem.uninit<Command>(g.cmd_slots * sizeof(Command) + 64);
+    J.items = g.items_dev;
+    J.order = g.order_dev;
+    J.n_items = g.n;
+    J.tables = g.tables;
+    J.counter = g.mem.zeroed<uint32_t>(64);
+    J.records = g.mem.uninit<BatchRecord>((size_t)g.n * sizeof(BatchRecord));
+    lz77_zopfli_batch_parse(J);
+    BatchParseJob G{};  // what the gather wants (GatherJobOf)
+    G.P = J.P;
+    G.slabs = J.slabs;
+    G.items = J.items;
+    G.n_items = J.n_items;
+    G.records = J.records;
+    FinishOneBlockItems(p, G, g, streams, reference_fails);
     first = g.last;
   }
 }

@@ -20,6 +20,7 @@
 
 #include "batch_greedy.h"
 #include "batch_quick.h"
+#include "batch_zopfli.h"
 #include "concat.h"
 #include "device_api.h"
 #include "encoder.h"
@@ -1012,10 +1013,12 @@ static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEn
                              int32_t* item_results) {
   uint64_t info[8] = {count, 0, 0, 0, 0, 0, 0, 0};
   memcpy(g_batch_info, info, sizeof(info));
-  if ((routes & ~(uint32_t)(BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS | BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS | BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS)) != 0) {
+  if ((routes & ~(uint32_t)(BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS | BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS | BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS |
+                            BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS)) != 0) {
     // a route this build does not know fails the call as a whole, like a device error: a caller can probe for later routes
     SetError(entry, ("routes " + std::to_string(routes) + " names a route this build does not know (known: BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS = 1, "
-                     "BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS = 4, BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS = 16; the values 2 and 8 are reserved)").c_str());
+                     "BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS = 4, BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS = 16, BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS = 32; "
+                     "the values 2 and 8 are reserved)").c_str());
     for (size_t i = 0; i < count; ++i) output_sizes[i] = 0;
     if (item_results && count) memset(item_results, 0, count * sizeof(int32_t));
     return 0;
@@ -1035,17 +1038,18 @@ static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEn
     // The items an encoder sees and that go side by side on the device: every item of qualities 0 and 1 (fragment_stream.h), the
     // items of one input block under an H5 hasher at qualities 5 .. 8 (batch_greedy.h) and, where the caller asked for that route,
     // those of two to four blocks, or those of one input block under a BasicHasher at qualities 2 .. 4, or those of two to four
-    // blocks at these qualities (batch_quick.h).  Every other item goes through the one-shot path by itself, on this thread, in
-    // the caller's order (the same bytes, no gain in speed).
+    // blocks at these qualities (batch_quick.h), or those of at most 65 536 bytes at quality 11 (batch_zopfli.h).  Every
+    // other item goes through the one-shot path by itself, on this thread, in the caller's order (the same bytes, no gain in speed).
     struct Routed {  // the items of one route: their places in the caller's arrays, their inputs and their sizes
       std::vector<size_t> item;
       std::vector<const uint8_t*> in;
       std::vector<size_t> size;
     };
-    Routed plain, long_items, quick_items, quick_long_items;
+    Routed plain, long_items, quick_items, quick_long_items, zopfli_items;
     const bool long_route = (routes & BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS) != 0;
     const bool quick_route = (routes & BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS) != 0;
     const bool quick_long_route = (routes & BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS) != 0;
+    const bool zopfli_route = (routes & BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS) != 0;
     auto one_by_one = [&](size_t i) {
       std::string error;
       results[i] = CompressOneShot(quality, lgwin, mode, input_sizes[i], inputs[i], false, &output_sizes[i], outputs[i], nullptr, &error);
@@ -1054,14 +1058,25 @@ static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEn
       ++info[2];
     };
     // hands the streams of a route out, in the caller's order.  demoted != nullptr, (*demoted)[k] != 0: a meta-block that is not the
-    // item's last took the size fallback, which its chain could not know: redone one by one.  Returns the streams handed out.
-    auto deliver = [&](const Routed& r, const std::vector<std::vector<uint8_t>>& streams, const std::vector<uint8_t>* demoted) {
+    // item's last took the size fallback, which its chain could not know: redone one by one.  reference_fails != nullptr,
+    // (*reference_fails)[k] != 0: the reference encoder panics on the item, which fails alone, like the bad_commands items of the
+    // dictionary routes.  Returns the items answered from the route's streams (all but the demoted ones).
+    auto deliver = [&](const Routed& r, const std::vector<std::vector<uint8_t>>& streams, const std::vector<uint8_t>* demoted,
+                       const std::vector<uint8_t>* reference_fails = nullptr) {
       size_t delivered = 0;
       for (size_t k = 0; k < r.item.size(); ++k) {
         const size_t i = r.item[k];
         if (demoted && (*demoted)[k]) {
           one_by_one(i);
           ++info[6];
+          continue;
+        }
+        if (reference_fails && (*reference_fails)[k]) {
+          SetError(entry, ("item " + std::to_string(i) + ": the reference encoder fails on this input: its quality 11 parse indexes past the end of "
+                           "an array there (hq.rs:1073-1160, 1310-1340)").c_str());
+          results[i] = 0;
+          output_sizes[i] = 0;
+          ++delivered;  // (it ran side by side and has its answer, as an item whose buffer is too small has: info[1], as with a dictionary)
           continue;
         }
         results[i] = OneShotDeliver(streams[k].data(), streams[k].size(), inputs[i], input_sizes[i], false, output_sizes[i], &output_sizes[i], outputs[i]);
@@ -1082,6 +1097,7 @@ static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEn
       else if (long_route && BatchLongEligible(params, input_sizes[i])) r = &long_items;
       else if (quick_route && BatchQuickEligible(params, input_sizes[i])) r = &quick_items;
       else if (quick_long_route && BatchQuickLongEligible(params, input_sizes[i])) r = &quick_long_items;
+      else if (zopfli_route && BatchZopfliEligible(params, input_sizes[i])) r = &zopfli_items;
       if (!r) {
         one_by_one(i);
         continue;
@@ -1098,6 +1114,14 @@ static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEn
       BatchQuickCompress(params, quick_items.item.size(), quick_items.in.data(), quick_items.size.data(), &streams, &groups);
       info[4] += groups;
       info[1] += deliver(quick_items, streams, nullptr);
+    }
+    // ---- the items of at most 65 536 bytes at quality 11, one sequential Zopfli walk each, in groups of their own
+    // (BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS)
+    if (!zopfli_items.item.empty()) {
+      std::vector<uint8_t> reference_fails;
+      BatchZopfliCompress(params, zopfli_items.item.size(), zopfli_items.in.data(), zopfli_items.size.data(), &streams, &reference_fails, &groups);
+      info[4] += groups;
+      info[1] += deliver(zopfli_items, streams, nullptr, &reference_fails);
     }
     // ---- the items of two to four blocks at qualities 2 .. 4, one chain each, in groups of their own
     // (BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS)

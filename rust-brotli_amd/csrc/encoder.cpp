@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <functional>
 #include <stdexcept>
 
 #include "batch_greedy.h"
@@ -366,6 +367,227 @@ uint32_t ChooseSegmentBytes(size_t input_bytes) {
   return 4096;
 }
 
+// BrotliBuildMetaBlock (metablock.rs:133-307) on the device, metablock_hq.h: the quality >= 10 meta-block builder, for the meta-blocks
+// of one stream (EncodeStream) and for those of a batch group, one per item (EncodeBatchMetaBlocks).  Comes behind the command
+// scans, the literal map and the distance counts; descs / results are the host copies of B.descs / B.results and leave as the
+// Huffman code jobs want them.  B.cmds is replaced by a private copy (the distance-parameter search re-codes distance prefixes).
+// Per meta-block it sets aside kHqHeaderWords header words, 3 x 256 histogram rows and the context-map scratch, about 4.2 MiB:
+// a caller with thousands of tiny meta-blocks bounds their number (kBatchHqGroupItems).  lap(phase, name): the caller's clock.
+namespace {
+void BuildHqMetaBlocks(const EncoderParams& p, DevMem& mm, MbBuffers& B, std::vector<MbDesc>& descs, std::vector<MbResult>& results,
+                       const std::function<void(int, const char*)>& lap) {
+  const uint32_t n_mb = B.n_mb, K = B.n_cmds, L = B.n_lits;
+  for (uint32_t m = 0; m < n_mb; ++m) {
+    descs[m].hq = 1u | (p.large_window ? 2u : 0u);
+    descs[m].hq_no_context = p.disable_literal_context_modeling ? 1 : 0;
+    descs[m].n_symbols[0] = descs[m].n_lits;
+    descs[m].n_symbols[1] = descs[m].n_cmds;
+    descs[m].n_symbols[2] = descs[m].n_dists;
+  }
+  {
+    // the distance-parameter search re-codes the distance prefixes of a meta-block: on a copy, the LZ77 stage keeps its own
+    Command* copy = mm.alloc<Command>((size_t)K + 1);
+    dev_d2d(copy, B.cmds, (size_t)K * sizeof(Command));
+    B.cmds = copy;
+    B.cmds_rw = copy;
+  }
+  dev_h2d(B.descs, descs.data(), n_mb * sizeof(MbDesc));
+  const bool census = !(p.mode == 3 || p.mode == 4 || p.mode == 5 || p.mode == 6);
+  if (census) mb_hq_utf8_census(B);
+  mb_hq_distance_params(B);
+  dev_d2h(results.data(), B.results, n_mb * sizeof(MbResult));
+  for (uint32_t m = 0; m < n_mb; ++m) {
+    MbDesc& d = descs[m];
+    if (census) d.context_mode = results[m].hq_mostly_utf8 ? 2 : 3;  // ChooseContextMode, encode.rs:1357-1377
+    d.dist_postfix_bits = results[m].hq_postfix;
+    d.num_direct_distance_codes = results[m].hq_ndirect;
+    d.num_distance_symbols = 16 + d.num_direct_distance_codes + ((p.large_window ? 62u : 24u) << (d.dist_postfix_bits + 1));
+  }
+  B.hq_sym[0] = mm.alloc<uint16_t>((size_t)L + 8);
+  B.hq_sym[1] = mm.alloc<uint16_t>((size_t)K + 8);
+  B.hq_sym[2] = mm.alloc<uint16_t>((size_t)B.n_dists + 8);
+  mb_hq_gather_symbols(B);
+  // BrotliSplitBlock, block_splitter.rs:840-929: one job per (meta-block, kind)
+  static const uint32_t kSymbolsPerHistogram[3] = {544, 530, 544}, kMaxHistograms[3] = {100, 50, 50}, kStride[3] = {70, 40, 40};
+  static const float kSwitchCost[3] = {28.1f, 13.5f, 14.6f};
+  uint8_t* block_ids[3] = {mm.alloc<uint8_t>((size_t)L + 8), mm.alloc<uint8_t>((size_t)K + 8), mm.alloc<uint8_t>((size_t)B.n_dists + 8)};
+  std::vector<HqSplitJob> jobs;
+  for (uint32_t m = 0; m < n_mb; ++m) {
+    const MbDesc& d = descs[m];
+    if (d.uncompressed) continue;
+    const uint32_t base[3] = {d.lit_base, d.cmd_offset, d.dist_base};
+    for (uint32_t k = 0; k < 3; ++k) {
+      HqSplitJob j;
+      memset(&j, 0, sizeof(j));
+      j.m = m;
+      j.kind = k;
+      j.length = d.n_symbols[k];
+      j.alphabet = kRowLen[k];
+      j.num_histograms = std::min(j.length / kSymbolsPerHistogram[k] + 1, kMaxHistograms[k]);
+      j.stride = kStride[k];
+      j.iters = p.quality <= 11 ? 3 : 10;  // block_splitter.rs:794
+      j.block_switch_cost = kSwitchCost[k];
+      j.data = B.hq_sym[k] + base[k];
+      j.block_ids = block_ids[k] + base[k];
+      if (j.length >= 128) {
+        const size_t nh = j.num_histograms, bitmaplen = (nh + 7) >> 3;
+        j.histo_data = mm.alloc<uint32_t>((nh + 1) * j.alphabet);
+        j.histo_total = mm.alloc<uint32_t>(nh + 1);
+        j.insert_cost = mm.alloc<float>((size_t)j.alphabet * nh + nh + 8);
+        j.cost = mm.alloc<float>(bitmaplen * 8 + 8);
+        j.switch_signal = mm.alloc<uint8_t>((size_t)j.length * bitmaplen + 8);
+        j.new_id = mm.alloc<uint16_t>(nh + 8);
+      }
+      jobs.push_back(j);
+    }
+  }
+  HqSplitJob* jobs_dev = mm.alloc<HqSplitJob>(jobs.size() + 1);
+  dev_h2d(jobs_dev, jobs.data(), jobs.size() * sizeof(HqSplitJob));
+  mb_hq_find_blocks(B, jobs_dev, (uint32_t)jobs.size());
+  dev_d2h(jobs.data(), jobs_dev, jobs.size() * sizeof(HqSplitJob));
+  if (lap) lap(1, "hq-find-blocks");
+  // pools sized by what FindBlocks found; ClusterBlocks
+  uint32_t block_total[3] = {0, 0, 0}, histo_total[3] = {0, 0, 0};
+  for (uint32_t m = 0; m < n_mb; ++m)
+    for (uint32_t k = 0; k < 3; ++k) {
+      descs[m].histo_base[k] = histo_total[k];
+      descs[m].max_histos[k] = 256;
+      histo_total[k] += 256;
+    }
+  {
+    // ClusterBlocks keeps one histogram per block FindBlocks found, twice (the batches' rows and the gathered clusters);
+    // a pathological input (a switch every few symbols over a 16 MiB meta-block) would ask for more than the device
+    // has.  Refuse with a message instead of dying in an allocation half-way through.
+    uint64_t need = 0;
+    for (const HqSplitJob& j : jobs)
+      if (j.length >= 128) need += (uint64_t)(j.num_blocks + 2) * (2ull * j.alphabet * 4 + 64ull * sizeof(HqPair) + 64);
+    if (need > (96ull << 30))
+      throw std::runtime_error("brotli_mi355x: quality 9.5: clustering " + std::to_string(need >> 30) +
+                               " GiB of block histograms is more than this build sets aside; feed the stream in smaller pieces");
+  }
+  for (HqSplitJob& j : jobs) {
+    MbDesc& d = descs[j.m];
+    const uint32_t nb = j.num_blocks;
+    d.block_base[j.kind] = block_total[j.kind];
+    d.max_blocks[j.kind] = nb + 1;
+    block_total[j.kind] += nb + 2;
+    if (j.length >= 128) {
+      const size_t n = nb;
+      uint64_t max_pairs = std::min<uint64_t>(64ull * n, (uint64_t)(n / 2) * n);
+      max_pairs = std::max<uint64_t>(max_pairs, kHqBatchPairs);
+      j.histogram_symbols = mm.alloc<uint32_t>(n + 8);
+      j.block_lengths = mm.alloc<uint32_t>(n + 8);
+      j.block_pos = mm.alloc<uint32_t>(n + 8);
+      j.batch_data = mm.alloc<uint32_t>((n + 2) * j.alphabet);
+      j.batch_total = mm.alloc<uint32_t>(n + 8);
+      j.batch_cost = mm.alloc<float>(n + 8);
+      j.batch_sizes = mm.alloc<uint32_t>(n + 8);
+      j.batch_clusters = mm.alloc<uint32_t>(n + 8);
+      j.batch_symbols = mm.alloc<uint32_t>(n + 8);
+      j.batch_count = mm.alloc<uint32_t>(n / kHqBatch + 8);
+      j.all_data = mm.alloc<uint32_t>((n + 2) * j.alphabet);
+      j.all_total = mm.alloc<uint32_t>(n + 2);
+      j.all_cost = mm.alloc<float>(n + 2);
+      j.cluster_size = mm.alloc<uint32_t>(n + 8);
+      j.clusters = mm.alloc<uint32_t>(n + 2 * kHqBatch + 8);  // (also the per-batch sizes / cluster lists)
+      j.new_index = mm.alloc<uint32_t>(n + 2 * kHqBatch + 8);
+      j.pairs = mm.alloc<HqPair>(max_pairs + 2);
+    }
+  }
+  for (uint32_t k = 0; k < 3; ++k) {
+    B.n_granules[k] = 0;
+    B.histo[k] = mm.alloc<uint32_t>((size_t)histo_total[k] * kRowLen[k] + 8);
+    B.depth[k] = mm.alloc<uint8_t>((size_t)histo_total[k] * kRowLen[k] + 8);
+    B.bits[k] = mm.alloc<uint16_t>((size_t)histo_total[k] * kRowLen[k] + 8);
+    B.tree_bits[k] = mm.alloc<uint64_t>((size_t)histo_total[k] * kTreeBitsWords + 8);
+    B.tree_nbits[k] = mm.alloc<uint32_t>(histo_total[k] + 8);
+    B.block_types[k] = mm.alloc<uint8_t>(block_total[k] + 8);
+    B.block_lengths[k] = mm.alloc<uint32_t>(block_total[k] + 8);
+    B.block_start[k] = mm.alloc<uint32_t>(block_total[k] + 8);
+    B.switch_bits[k] = mm.alloc<uint64_t>(block_total[k] + 8);
+    B.switch_nbits[k] = mm.alloc<uint8_t>(block_total[k] + 8);
+  }
+  B.header_words = mm.alloc<uint64_t>((size_t)n_mb * kHqHeaderWords);
+  B.ctxmap_scratch = mm.alloc<uint32_t>((size_t)n_mb * 2 * 256 * 64);
+  B.mb_out_bit = mm.alloc<uint64_t>(n_mb + 1);
+  dev_h2d(B.descs, descs.data(), n_mb * sizeof(MbDesc));
+  dev_h2d(jobs_dev, jobs.data(), jobs.size() * sizeof(HqSplitJob));
+  std::vector<HqBatchRef> batch_refs;
+  for (uint32_t ji = 0; ji < jobs.size(); ++ji)
+    if (jobs[ji].length >= 128)
+      for (uint32_t b = 0; b * kHqBatch < jobs[ji].num_blocks; ++b) batch_refs.push_back({ji, b});
+  HqBatchRef* batch_refs_dev = mm.alloc<HqBatchRef>(batch_refs.size() + 1);
+  dev_h2d(batch_refs_dev, batch_refs.data(), batch_refs.size() * sizeof(HqBatchRef));
+  mb_hq_cluster_blocks(B, jobs_dev, (uint32_t)jobs.size(), batch_refs_dev, (uint32_t)batch_refs.size());
+  dev_d2h(results.data(), B.results, n_mb * sizeof(MbResult));
+  if (lap) lap(2, "hq-cluster-blocks");
+  // context histograms and the clustered context maps (histogram.rs:465-534, cluster.rs:353-465)
+  uint32_t rows_total[2] = {0, 0}, map_total[2] = {0, 0};
+  std::vector<HqClusterJob> cjobs;
+  for (uint32_t m = 0; m < n_mb; ++m) {
+    MbDesc& d = descs[m];
+    if (d.uncompressed) continue;
+    const uint32_t nt[2] = {results[m].num_types[kSplitLiteral], results[m].num_types[kSplitDistance]};
+    const uint32_t rows[2] = {d.hq_no_context ? nt[0] : nt[0] << 6, nt[1] << 2};
+    const uint32_t maps[2] = {nt[0] << 6, nt[1] << 2};
+    for (uint32_t w = 0; w < 2; ++w) {
+      d.hq_ctx_row_base[w] = rows_total[w];
+      d.hq_ctx_map_base[w] = map_total[w];
+      rows_total[w] += rows[w];
+      map_total[w] += maps[w];
+    }
+  }
+  B.hq_ctx_histo[0] = mm.alloc<uint32_t>((size_t)rows_total[0] * 256 + 8);
+  B.hq_ctx_histo[1] = mm.alloc<uint32_t>((size_t)rows_total[1] * kNumDistanceHistoSymbols + 8);
+  B.hq_ctx_map[0] = mm.alloc<uint32_t>((size_t)map_total[0] + 8);
+  B.hq_ctx_map[1] = mm.alloc<uint32_t>((size_t)map_total[1] + 8);
+  for (uint32_t m = 0; m < n_mb; ++m) {
+    const MbDesc& d = descs[m];
+    if (d.uncompressed) continue;
+    for (uint32_t w = 0; w < 2; ++w) {
+      HqClusterJob j;
+      memset(&j, 0, sizeof(j));
+      j.m = m;
+      j.kind = w == 0 ? kSplitLiteral : kSplitDistance;
+      const uint32_t nt = results[m].num_types[j.kind];
+      j.in_size = w == 0 ? (d.hq_no_context ? nt : nt << 6) : nt << 2;
+      j.len = kRowLen[j.kind];
+      j.expand64 = (w == 0 && d.hq_no_context) ? 1 : 0;
+      j.in_data = B.hq_ctx_histo[w] + (size_t)d.hq_ctx_row_base[w] * j.len;
+      const size_t n = j.in_size, re = std::min<size_t>(n, 256);
+      j.in_total = mm.alloc<uint32_t>(n + 8);
+      j.out_data = mm.alloc<uint32_t>((n + 2) * j.len);
+      j.out_total = mm.alloc<uint32_t>(n + 2);
+      j.out_cost = mm.alloc<float>(n + 2);
+      j.cluster_size = mm.alloc<uint32_t>(n + 8);
+      j.clusters = mm.alloc<uint32_t>(n + 8);
+      j.symbols = mm.alloc<uint32_t>(n + 8);
+      j.new_index = mm.alloc<uint32_t>(n + 8);
+      j.batch_count = mm.alloc<uint32_t>(n / kHqBatch + 8);
+      j.reindex_data = mm.alloc<uint32_t>(re * j.len + 8);
+      j.reindex_total = mm.alloc<uint32_t>(re + 8);
+      j.reindex_cost = mm.alloc<float>(re + 8);
+      j.pairs = mm.alloc<HqPair>(std::max<size_t>(kHqBatchPairs, 64 * n) + 2);
+      cjobs.push_back(j);
+    }
+  }
+  dev_h2d(B.descs, descs.data(), n_mb * sizeof(MbDesc));
+  mb_hq_context_histograms(B);
+  HqClusterJob* cjobs_dev = mm.alloc<HqClusterJob>(cjobs.size() + 1);
+  dev_h2d(cjobs_dev, cjobs.data(), cjobs.size() * sizeof(HqClusterJob));
+  std::vector<HqBatchRef> cbatch_refs;
+  for (uint32_t ji = 0; ji < cjobs.size(); ++ji)
+    for (uint32_t b = 0; b * kHqBatch < cjobs[ji].in_size; ++b) cbatch_refs.push_back({ji, b});
+  HqBatchRef* cbatch_refs_dev = mm.alloc<HqBatchRef>(cbatch_refs.size() + 1);
+  dev_h2d(cbatch_refs_dev, cbatch_refs.data(), cbatch_refs.size() * sizeof(HqBatchRef));
+  mb_hq_cluster_histograms(B, cjobs_dev, (uint32_t)cjobs.size(), cbatch_refs_dev, (uint32_t)cbatch_refs.size());
+  dev_d2h(results.data(), B.results, n_mb * sizeof(MbResult));
+  for (uint32_t m = 0; m < n_mb; ++m) results[m].num_histos[kSplitCommand] = results[m].num_types[kSplitCommand];
+  dev_h2d(B.results, results.data(), n_mb * sizeof(MbResult));
+  if (lap) lap(3, "hq-context-maps");
+}
+}  // namespace
+
 void EncodeStream(const EncodeRequest& req, std::vector<uint8_t>* out, EncodeStats* stats_out) {
   EncodeStats stats;
   Clock total_clock;
@@ -703,215 +925,7 @@ void EncodeStream(const EncodeRequest& req, std::vector<uint8_t>* out, EncodeSta
       B.n_dists = di[n_mb];
     }
     if (hq) {
-      // ---- BrotliBuildMetaBlock (metablock.rs:133-307) on the device, metablock_hq.h
-      for (uint32_t m = 0; m < n_mb; ++m) {
-        descs[m].hq = 1u | (p.large_window ? 2u : 0u);
-        descs[m].hq_no_context = p.disable_literal_context_modeling ? 1 : 0;
-        descs[m].n_symbols[0] = descs[m].n_lits;
-        descs[m].n_symbols[1] = descs[m].n_cmds;
-        descs[m].n_symbols[2] = descs[m].n_dists;
-      }
-      {
-        // the distance-parameter search re-codes the distance prefixes of a meta-block: on a copy, the LZ77 stage keeps its own
-        Command* copy = mm.alloc<Command>((size_t)K + 1);
-        dev_d2d(copy, B.cmds, (size_t)K * sizeof(Command));
-        B.cmds = copy;
-        B.cmds_rw = copy;
-      }
-      dev_h2d(B.descs, descs.data(), n_mb * sizeof(MbDesc));
-      const bool census = !(p.mode == 3 || p.mode == 4 || p.mode == 5 || p.mode == 6);
-      if (census) mb_hq_utf8_census(B);
-      mb_hq_distance_params(B);
-      dev_d2h(results.data(), B.results, n_mb * sizeof(MbResult));
-      for (uint32_t m = 0; m < n_mb; ++m) {
-        MbDesc& d = descs[m];
-        if (census) d.context_mode = results[m].hq_mostly_utf8 ? 2 : 3;  // ChooseContextMode, encode.rs:1357-1377
-        d.dist_postfix_bits = results[m].hq_postfix;
-        d.num_direct_distance_codes = results[m].hq_ndirect;
-        d.num_distance_symbols = 16 + d.num_direct_distance_codes + ((p.large_window ? 62u : 24u) << (d.dist_postfix_bits + 1));
-      }
-      B.hq_sym[0] = mm.alloc<uint16_t>((size_t)L + 8);
-      B.hq_sym[1] = mm.alloc<uint16_t>((size_t)K + 8);
-      B.hq_sym[2] = mm.alloc<uint16_t>((size_t)B.n_dists + 8);
-      mb_hq_gather_symbols(B);
-      // BrotliSplitBlock, block_splitter.rs:840-929: one job per (meta-block, kind)
-      static const uint32_t kSymbolsPerHistogram[3] = {544, 530, 544}, kMaxHistograms[3] = {100, 50, 50}, kStride[3] = {70, 40, 40};
-      static const float kSwitchCost[3] = {28.1f, 13.5f, 14.6f};
-      uint8_t* block_ids[3] = {mm.alloc<uint8_t>((size_t)L + 8), mm.alloc<uint8_t>((size_t)K + 8), mm.alloc<uint8_t>((size_t)B.n_dists + 8)};
-      std::vector<HqSplitJob> jobs;
-      for (uint32_t m = 0; m < n_mb; ++m) {
-        const MbDesc& d = descs[m];
-        if (d.uncompressed) continue;
-        const uint32_t base[3] = {d.lit_base, d.cmd_offset, d.dist_base};
-        for (uint32_t k = 0; k < 3; ++k) {
-          HqSplitJob j;
-          memset(&j, 0, sizeof(j));
-          j.m = m;
-          j.kind = k;
-          j.length = d.n_symbols[k];
-          j.alphabet = kRowLen[k];
-          j.num_histograms = std::min(j.length / kSymbolsPerHistogram[k] + 1, kMaxHistograms[k]);
-          j.stride = kStride[k];
-          j.iters = p.quality <= 11 ? 3 : 10;  // block_splitter.rs:794
-          j.block_switch_cost = kSwitchCost[k];
-          j.data = B.hq_sym[k] + base[k];
-          j.block_ids = block_ids[k] + base[k];
-          if (j.length >= 128) {
-            const size_t nh = j.num_histograms, bitmaplen = (nh + 7) >> 3;
-            j.histo_data = mm.alloc<uint32_t>((nh + 1) * j.alphabet);
-            j.histo_total = mm.alloc<uint32_t>(nh + 1);
-            j.insert_cost = mm.alloc<float>((size_t)j.alphabet * nh + nh + 8);
-            j.cost = mm.alloc<float>(bitmaplen * 8 + 8);
-            j.switch_signal = mm.alloc<uint8_t>((size_t)j.length * bitmaplen + 8);
-            j.new_id = mm.alloc<uint16_t>(nh + 8);
-          }
-          jobs.push_back(j);
-        }
-      }
-      HqSplitJob* jobs_dev = mm.alloc<HqSplitJob>(jobs.size() + 1);
-      dev_h2d(jobs_dev, jobs.data(), jobs.size() * sizeof(HqSplitJob));
-      mb_hq_find_blocks(B, jobs_dev, (uint32_t)jobs.size());
-      dev_d2h(jobs.data(), jobs_dev, jobs.size() * sizeof(HqSplitJob));
-      stats.ms_phase[1] += clk.lap(prof, "hq-find-blocks");
-      // pools sized by what FindBlocks found; ClusterBlocks
-      uint32_t block_total[3] = {0, 0, 0}, histo_total[3] = {0, 0, 0};
-      for (uint32_t m = 0; m < n_mb; ++m)
-        for (uint32_t k = 0; k < 3; ++k) {
-          descs[m].histo_base[k] = histo_total[k];
-          descs[m].max_histos[k] = 256;
-          histo_total[k] += 256;
-        }
-      {
-        // ClusterBlocks keeps one histogram per block FindBlocks found, twice (the batches' rows and the gathered clusters);
-        // a pathological input (a switch every few symbols over a 16 MiB meta-block) would ask for more than the device
-        // has.  Refuse with a message instead of dying in an allocation half-way through.
-        uint64_t need = 0;
-        for (const HqSplitJob& j : jobs)
-          if (j.length >= 128) need += (uint64_t)(j.num_blocks + 2) * (2ull * j.alphabet * 4 + 64ull * sizeof(HqPair) + 64);
-        if (need > (96ull << 30))
-          throw std::runtime_error("brotli_mi355x: quality 9.5: clustering " + std::to_string(need >> 30) +
-                                   " GiB of block histograms is more than this build sets aside; feed the stream in smaller pieces");
-      }
-      for (HqSplitJob& j : jobs) {
-        MbDesc& d = descs[j.m];
-        const uint32_t nb = j.num_blocks;
-        d.block_base[j.kind] = block_total[j.kind];
-        d.max_blocks[j.kind] = nb + 1;
-        block_total[j.kind] += nb + 2;
-        if (j.length >= 128) {
-          const size_t n = nb;
-          uint64_t max_pairs = std::min<uint64_t>(64ull * n, (uint64_t)(n / 2) * n);
-          max_pairs = std::max<uint64_t>(max_pairs, kHqBatchPairs);
-          j.histogram_symbols = mm.alloc<uint32_t>(n + 8);
-          j.block_lengths = mm.alloc<uint32_t>(n + 8);
-          j.block_pos = mm.alloc<uint32_t>(n + 8);
-          j.batch_data = mm.alloc<uint32_t>((n + 2) * j.alphabet);
-          j.batch_total = mm.alloc<uint32_t>(n + 8);
-          j.batch_cost = mm.alloc<float>(n + 8);
-          j.batch_sizes = mm.alloc<uint32_t>(n + 8);
-          j.batch_clusters = mm.alloc<uint32_t>(n + 8);
-          j.batch_symbols = mm.alloc<uint32_t>(n + 8);
-          j.batch_count = mm.alloc<uint32_t>(n / kHqBatch + 8);
-          j.all_data = mm.alloc<uint32_t>((n + 2) * j.alphabet);
-          j.all_total = mm.alloc<uint32_t>(n + 2);
-          j.all_cost = mm.alloc<float>(n + 2);
-          j.cluster_size = mm.alloc<uint32_t>(n + 8);
-          j.clusters = mm.alloc<uint32_t>(n + 2 * kHqBatch + 8);  // (also the per-batch sizes / cluster lists)
-          j.new_index = mm.alloc<uint32_t>(n + 2 * kHqBatch + 8);
-          j.pairs = mm.alloc<HqPair>(max_pairs + 2);
-        }
-      }
-      for (uint32_t k = 0; k < 3; ++k) {
-        B.n_granules[k] = 0;
-        B.histo[k] = mm.alloc<uint32_t>((size_t)histo_total[k] * kRowLen[k] + 8);
-        B.depth[k] = mm.alloc<uint8_t>((size_t)histo_total[k] * kRowLen[k] + 8);
-        B.bits[k] = mm.alloc<uint16_t>((size_t)histo_total[k] * kRowLen[k] + 8);
-        B.tree_bits[k] = mm.alloc<uint64_t>((size_t)histo_total[k] * kTreeBitsWords + 8);
-        B.tree_nbits[k] = mm.alloc<uint32_t>(histo_total[k] + 8);
-        B.block_types[k] = mm.alloc<uint8_t>(block_total[k] + 8);
-        B.block_lengths[k] = mm.alloc<uint32_t>(block_total[k] + 8);
-        B.block_start[k] = mm.alloc<uint32_t>(block_total[k] + 8);
-        B.switch_bits[k] = mm.alloc<uint64_t>(block_total[k] + 8);
-        B.switch_nbits[k] = mm.alloc<uint8_t>(block_total[k] + 8);
-      }
-      B.header_words = mm.alloc<uint64_t>((size_t)n_mb * kHqHeaderWords);
-      B.ctxmap_scratch = mm.alloc<uint32_t>((size_t)n_mb * 2 * 256 * 64);
-      B.mb_out_bit = mm.alloc<uint64_t>(n_mb + 1);
-      dev_h2d(B.descs, descs.data(), n_mb * sizeof(MbDesc));
-      dev_h2d(jobs_dev, jobs.data(), jobs.size() * sizeof(HqSplitJob));
-      std::vector<HqBatchRef> batch_refs;
-      for (uint32_t ji = 0; ji < jobs.size(); ++ji)
-        if (jobs[ji].length >= 128)
-          for (uint32_t b = 0; b * kHqBatch < jobs[ji].num_blocks; ++b) batch_refs.push_back({ji, b});
-      HqBatchRef* batch_refs_dev = mm.alloc<HqBatchRef>(batch_refs.size() + 1);
-      dev_h2d(batch_refs_dev, batch_refs.data(), batch_refs.size() * sizeof(HqBatchRef));
-      mb_hq_cluster_blocks(B, jobs_dev, (uint32_t)jobs.size(), batch_refs_dev, (uint32_t)batch_refs.size());
-      dev_d2h(results.data(), B.results, n_mb * sizeof(MbResult));
-      stats.ms_phase[2] += clk.lap(prof, "hq-cluster-blocks");
-      // context histograms and the clustered context maps (histogram.rs:465-534, cluster.rs:353-465)
-      uint32_t rows_total[2] = {0, 0}, map_total[2] = {0, 0};
-      std::vector<HqClusterJob> cjobs;
-      for (uint32_t m = 0; m < n_mb; ++m) {
-        MbDesc& d = descs[m];
-        if (d.uncompressed) continue;
-        const uint32_t nt[2] = {results[m].num_types[kSplitLiteral], results[m].num_types[kSplitDistance]};
-        const uint32_t rows[2] = {d.hq_no_context ? nt[0] : nt[0] << 6, nt[1] << 2};
-        const uint32_t maps[2] = {nt[0] << 6, nt[1] << 2};
-        for (uint32_t w = 0; w < 2; ++w) {
-          d.hq_ctx_row_base[w] = rows_total[w];
-          d.hq_ctx_map_base[w] = map_total[w];
-          rows_total[w] += rows[w];
-          map_total[w] += maps[w];
-        }
-      }
-      B.hq_ctx_histo[0] = mm.alloc<uint32_t>((size_t)rows_total[0] * 256 + 8);
-      B.hq_ctx_histo[1] = mm.alloc<uint32_t>((size_t)rows_total[1] * kNumDistanceHistoSymbols + 8);
-      B.hq_ctx_map[0] = mm.alloc<uint32_t>((size_t)map_total[0] + 8);
-      B.hq_ctx_map[1] = mm.alloc<uint32_t>((size_t)map_total[1] + 8);
-      for (uint32_t m = 0; m < n_mb; ++m) {
-        const MbDesc& d = descs[m];
-        if (d.uncompressed) continue;
-        for (uint32_t w = 0; w < 2; ++w) {
-          HqClusterJob j;
-          memset(&j, 0, sizeof(j));
-          j.m = m;
-          j.kind = w == 0 ? kSplitLiteral : kSplitDistance;
-          const uint32_t nt = results[m].num_types[j.kind];
-          j.in_size = w == 0 ? (d.hq_no_context ? nt : nt << 6) : nt << 2;
-          j.len = kRowLen[j.kind];
-          j.expand64 = (w == 0 && d.hq_no_context) ? 1 : 0;
-          j.in_data = B.hq_ctx_histo[w] + (size_t)d.hq_ctx_row_base[w] * j.len;
-          const size_t n = j.in_size, re = std::min<size_t>(n, 256);
-          j.in_total = mm.alloc<uint32_t>(n + 8);
-          j.out_data = mm.alloc<uint32_t>((n + 2) * j.len);
-          j.out_total = mm.alloc<uint32_t>(n + 2);
-          j.out_cost = mm.alloc<float>(n + 2);
-          j.cluster_size = mm.alloc<uint32_t>(n + 8);
-          j.clusters = mm.alloc<uint32_t>(n + 8);
-          j.symbols = mm.alloc<uint32_t>(n + 8);
-          j.new_index = mm.alloc<uint32_t>(n + 8);
-          j.batch_count = mm.alloc<uint32_t>(n / kHqBatch + 8);
-          j.reindex_data = mm.alloc<uint32_t>(re * j.len + 8);
-          j.reindex_total = mm.alloc<uint32_t>(re + 8);
-          j.reindex_cost = mm.alloc<float>(re + 8);
-          j.pairs = mm.alloc<HqPair>(std::max<size_t>(kHqBatchPairs, 64 * n) + 2);
-          cjobs.push_back(j);
-        }
-      }
-      dev_h2d(B.descs, descs.data(), n_mb * sizeof(MbDesc));
-      mb_hq_context_histograms(B);
-      HqClusterJob* cjobs_dev = mm.alloc<HqClusterJob>(cjobs.size() + 1);
-      dev_h2d(cjobs_dev, cjobs.data(), cjobs.size() * sizeof(HqClusterJob));
-      std::vector<HqBatchRef> cbatch_refs;
-      for (uint32_t ji = 0; ji < cjobs.size(); ++ji)
-        for (uint32_t b = 0; b * kHqBatch < cjobs[ji].in_size; ++b) cbatch_refs.push_back({ji, b});
-      HqBatchRef* cbatch_refs_dev = mm.alloc<HqBatchRef>(cbatch_refs.size() + 1);
-      dev_h2d(cbatch_refs_dev, cbatch_refs.data(), cbatch_refs.size() * sizeof(HqBatchRef));
-      mb_hq_cluster_histograms(B, cjobs_dev, (uint32_t)cjobs.size(), cbatch_refs_dev, (uint32_t)cbatch_refs.size());
-      dev_d2h(results.data(), B.results, n_mb * sizeof(MbResult));
-      for (uint32_t m = 0; m < n_mb; ++m) results[m].num_histos[kSplitCommand] = results[m].num_types[kSplitCommand];
-      dev_h2d(B.results, results.data(), n_mb * sizeof(MbResult));
-      stats.ms_phase[3] += clk.lap(prof, "hq-context-maps");
+      BuildHqMetaBlocks(p, mm, B, descs, results, [&](int phase, const char* name) { stats.ms_phase[phase] += clk.lap(prof, name); });
     } else {
       // literal context modelling decision
       if (p.disable_literal_context_modeling == 0 && p.quality >= 5) {  // (DecideOverLiteralContextModeling leaves lower qualities alone)
@@ -1160,7 +1174,7 @@ void EncodeBatchMetaBlocks(const EncoderParams& p, const uint8_t* text, const Co
   const uint32_t n_mb = (uint32_t)items.size();
   out->clear();
   if (n_mb == 0) return;
-  if (p.quality < 2 || p.quality > 9 || p.lgwin < 10 || p.lgwin > 24 || p.large_window || p.appendable || p.byte_align || p.magic_number)
+  if (p.quality < 2 || p.quality > 11 || p.lgwin < 10 || p.lgwin > 24 || p.large_window || p.appendable || p.byte_align || p.magic_number)
     throw std::runtime_error("brotli_mi355x: parameters the batch meta-block stage does not take");
   uint64_t L64 = 0;
   for (const BatchStreamItem& it : items) L64 += it.n_lits;
@@ -1181,7 +1195,9 @@ void EncodeBatchMetaBlocks(const EncoderParams& p, const uint8_t* text, const Co
   B.signed_lut = dt.signed_context_lookup;
   B.et.logs_16 = dt.logs_16;
   B.et.logs_8 = dt.logs_8;
-  B.header_stride = kHeaderWords;
+  const bool hq = p.quality >= 10;  // the quality >= 10 meta-block builder, as in EncodeStream
+  if (hq && n_mb > kBatchHqGroupItems) throw std::runtime_error("brotli_mi355x: more meta-blocks than the quality >= 10 builder takes in one batch group");
+  B.header_stride = hq ? kHqHeaderWords : kHeaderWords;
   B.descs = mm.alloc<MbDesc>(n_mb);
   B.results = mm.alloc<MbResult>(n_mb);
   std::vector<MbDesc> descs(n_mb);
@@ -1211,6 +1227,7 @@ void EncodeBatchMetaBlocks(const EncoderParams& p, const uint8_t* text, const Co
         d.prev_byte = items[m].prev_byte;
         d.prev_byte2 = items[m].prev_byte2;
       }
+      if (!items[m].follows) d.census_floor = d.start;  // (quality >= 10: the UTF-8 census must not see the neighbour in front either)
       d.num_distance_symbols = p.dist.alphabet_size;
       d.dist_postfix_bits = p.dist.distance_postfix_bits;
       d.num_direct_distance_codes = p.dist.num_direct_distance_codes;
@@ -1246,26 +1263,30 @@ void EncodeBatchMetaBlocks(const EncoderParams& p, const uint8_t* text, const Co
       }
       B.n_dists = di[n_mb];
     }
-    // literal context modelling decision, with the size hint of the item's own stream
-    if (p.disable_literal_context_modeling == 0 && p.quality >= 5) {  // (DecideOverLiteralContextModeling leaves lower qualities alone)
-      uint32_t* stats_dev = mm.alloc<uint32_t>((size_t)n_mb * kContextStatsWords);
-      mb_context_stats(B, stats_dev);
-      std::vector<uint32_t> cs((size_t)n_mb * kContextStatsWords);
-      dev_d2h(cs.data(), stats_dev, cs.size() * 4);
-      if (getenv("BROTLI_MI355X_SELFTEST")) SelfTestContextStats(text, descs, cs);
-      for (uint32_t m = 0; m < n_mb; ++m) {
-        if (descs[m].uncompressed) continue;
-        DecideContexts(cs.data() + (size_t)m * kContextStatsWords, p.quality, items[m].item_bytes ? items[m].item_bytes : items[m].bytes, items[m].bytes,
-                       &descs[m].num_contexts, &descs[m].context_map_id);
+    if (hq) {
+      BuildHqMetaBlocks(p, mm, B, descs, results, nullptr);
+    } else {
+      // literal context modelling decision, with the size hint of the item's own stream
+      if (p.disable_literal_context_modeling == 0 && p.quality >= 5) {  // (DecideOverLiteralContextModeling leaves lower qualities alone)
+        uint32_t* stats_dev = mm.alloc<uint32_t>((size_t)n_mb * kContextStatsWords);
+        mb_context_stats(B, stats_dev);
+        std::vector<uint32_t> cs((size_t)n_mb * kContextStatsWords);
+        dev_d2h(cs.data(), stats_dev, cs.size() * 4);
+        if (getenv("BROTLI_MI355X_SELFTEST")) SelfTestContextStats(text, descs, cs);
+        for (uint32_t m = 0; m < n_mb; ++m) {
+          if (descs[m].uncompressed) continue;
+          DecideContexts(cs.data() + (size_t)m * kContextStatsWords, p.quality, items[m].item_bytes ? items[m].item_bytes : items[m].bytes,
+                         items[m].bytes, &descs[m].num_contexts, &descs[m].context_map_id);
+        }
       }
+      PlanGreedyPools(&mm, &descs, &B);
+      dev_h2d(B.descs, descs.data(), n_mb * sizeof(MbDesc));
+      mb_granule_histograms(B);
+      bool wide = false;
+      for (uint32_t m = 0; m < n_mb; ++m) wide = wide || (!descs[m].uncompressed && descs[m].num_contexts > 3);
+      mb_split_chains(B, wide);
+      dev_d2h(results.data(), B.results, n_mb * sizeof(MbResult));
     }
-    PlanGreedyPools(&mm, &descs, &B);
-    dev_h2d(B.descs, descs.data(), n_mb * sizeof(MbDesc));
-    mb_granule_histograms(B);
-    bool wide = false;
-    for (uint32_t m = 0; m < n_mb; ++m) wide = wide || (!descs[m].uncompressed && descs[m].num_contexts > 3);
-    mb_split_chains(B, wide);
-    dev_d2h(results.data(), B.results, n_mb * sizeof(MbResult));
     // Huffman codes: one job per histogram
     std::vector<CodeJob> jobs;
     for (uint32_t m = 0; m < n_mb; ++m) {

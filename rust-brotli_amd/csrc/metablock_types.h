@@ -23,6 +23,10 @@ static constexpr uint32_t kMaxBlockTypes = 256;
 static constexpr uint32_t kTreeBitsWords = 64;     // scratch for one serialised Huffman tree (<= 4096 bits)
 static constexpr uint32_t kHeaderWords = 16384;    // scratch for one meta-block header (<= 1 Mi bits)
 static constexpr uint32_t kHqHeaderWords = 131072; // quality >= 10: up to 3 x 256 trees of <= 4096 bits + two clustered context maps
+// The quality >= 10 builder (BuildHqMetaBlocks, encoder.cpp) sets aside about 4.2 MiB per meta-block (a header of kHqHeaderWords,
+// 3 x 256 histogram rows with their codes, the context-map scratch): a batch group hands it at most this many (4.2 GiB), and
+// EncodeBatchMetaBlocks throws beyond.
+static constexpr uint32_t kBatchHqGroupItems = 1024;
 
 enum SplitKind : uint32_t { kSplitLiteral = 0, kSplitCommand = 1, kSplitDistance = 2 };
 
@@ -59,6 +63,8 @@ struct MbDesc {
   uint32_t hq_ctx_row_base[2];  // first row of this meta-block in the context histogram pools (literal, distance)
   uint32_t hq_ctx_map_base[2];  // first entry in the context map pools (num_types << 6 literal, << 2 distance)
   uint32_t simple;              // 0: greedy splitter (quality >= 4); 1 / 2: the one-block-type writers of quality 3 / 2 (metablock_fast.h)
+  uint32_t census_floor;        // quality >= 10: the stream the meta-block belongs to starts at this text position (0: the text is one
+                                // stream; a batch group: the item's start) -- the UTF-8 census reads zeros in front of it
 };
 
 // Results of the greedy splitters and the header pass, one per meta-block.

@@ -46,6 +46,12 @@ times; the CPU baseline is the oracle's dictionary stream.  The items the call f
 against the oracle one by one: it must fail on each of them.  The classes are 4096x4KiB and 4096x512B, 1024x16KiB (qualities 2 and 3: one
 input block) and 64x4KiB, the few-items case.
 
+With --zopfli-items (and --qualities 11) this build is called through BrotliMi355xCompressBatchEx with
+BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS: the items of at most 65 536 bytes go side by side, one wavefront each that walks its item the
+reference's way on H10 trees of its own.  The parent's library is measured through its plain batch call, which takes these items one by
+one (on the first --loop-items items, scaled by item count).  The classes are 1024x4KiB, 256x16KiB, 64x64KiB and 16x4KiB, the few-items
+case.  (--qualities 10,11 is accepted: BrotliEncoderCompress runs quality 10 at quality 9, and it goes one by one in both builds.)
+
 Every measurement runs in a child process of its own (the table's home is one setting per process, read once; the parent's library
 is another shared object), one after the other, each under its own time limit; the first failure ends the probe.
 
@@ -87,6 +93,11 @@ CLASSES = {
     # behind a shared dictionary at qualities 2 to 4 (--dictionary N --quick-items)
     "1024x16KiB": ("uniform", 1024, 16 << 10),
     "64x4KiB": ("uniform", 64, 4 << 10),
+    # small static files at quality 11 (--zopfli-items)
+    "1024x4KiB": ("uniform", 1024, 4 << 10),
+    "256x16KiB": ("uniform", 256, 16 << 10),
+    "64x64KiB": ("uniform", 64, 64 << 10),
+    "16x4KiB": ("uniform", 16, 4 << 10),
 }
 HEADLINE = ["4096x4KiB", "4096x16KiB", "1024x64KiB", "64xalice29", "4096xlog200B-256KiB"]
 AB = ["4096x512B", "4096x2KiB", "4096xlog200B-256KiB"]
@@ -96,6 +107,7 @@ QUICK_LONG_QUALITIES = {"1024x32KiB": (2, 3), "1024x64KiB": (2, 3), "1024x128KiB
 DICT_QUICK_HEADLINE = ["4096x4KiB", "4096x512B", "1024x16KiB", "64x4KiB"]  # (--dictionary N --quick-items)
 DICT_QUICK_QUALITIES = {"1024x16KiB": (2, 3)}  # (one input block at quality 2 and 3)
 QUICK_HEADLINE = ["4096x4KiB", "4096x16KiB", "1024x64KiB", "4096x512B", "4096xlog200B-256KiB"]  # (--quick-items)
+ZOPFLI_HEADLINE = ["1024x4KiB", "256x16KiB", "64x64KiB", "16x4KiB"]  # (--zopfli-items)
 
 
 def items_of(name, data):
@@ -279,7 +291,8 @@ def child(args):
                 row = {"class": name, "data": data, "quality": quality, "items": len(items), "bytes": sum(map(len, items))}
                 if args.child == "batch":
                     times, csize, info, failed = measure_batch(args.lib, first if args.first_only else items, quality, args.runs, args.warmup, dictionary,
-                                                              (1 if args.long_items else 0) | (4 if args.quick_items else 0) | (16 if args.quick_long_items else 0))
+                                                              (1 if args.long_items else 0) | (4 if args.quick_items else 0) | (16 if args.quick_long_items else 0) |
+                                                              (32 if args.zopfli_items else 0))
                     row.update(stats(times), compressed_bytes=csize, batch_info=info, reference_fails_on_items=failed, measured_items=len(first) if args.first_only else len(items))
                 elif args.child == "loop":
                     times, failed = measure_loop(args.lib, first, quality, args.threads, args.runs, 1, dictionary)
@@ -294,7 +307,7 @@ def child(args):
 
 
 def run_child(args, what, classes, lib=None, lds=None, threads=1, limit=600, first_only=False, plain=False, long_items=False, quick_items=False,
-              quick_long_items=False):
+              quick_long_items=False, zopfli_items=False):
     env = dict(os.environ)
     env.pop("BROTLI_MI355X_BATCH_LDS_BITS", None)
     if lds is not None:
@@ -304,6 +317,7 @@ def run_child(args, what, classes, lib=None, lds=None, threads=1, limit=600, fir
            "--threads", str(threads), "--runs", str(args.runs), "--warmup", str(args.warmup), "--loop-items", str(args.loop_items), "--child-out", tmp, "--qualities", args.qualities,
            "--dictionary", str(args.dictionary)] + (["--first-only"] if first_only else []) + (["--plain"] if plain else []) + (["--long-items"] if long_items else []) + (["--quick-items"] if quick_items else [])
     cmd += (["--quick-long-items"] if quick_long_items else []) + (["--quick-long-classes"] if args.quick_long_items else [])
+    cmd += ["--zopfli-items"] if zopfli_items else []
     r = subprocess.run(cmd, env=env)
     if r.returncode != 0:
         raise SystemExit("batch_probe: %s (lds=%s, threads=%d) ended with status %d: nothing more is started" % (what, lds, threads, r.returncode))
@@ -457,6 +471,7 @@ def main():
     ap.add_argument("--long-items", action="store_true", help="this build through BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS")
     ap.add_argument("--quick-items", action="store_true", help="this build through BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS (--qualities 2,3,4)")
     ap.add_argument("--quick-long-items", action="store_true", help="this build through routes QUICK_ITEMS | QUICK_LONG_ITEMS, the parent through QUICK_ITEMS (qualities 2,3,4 per class)")
+    ap.add_argument("--zopfli-items", action="store_true", help="this build through BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS (--qualities 11)")
     ap.add_argument("--quick-long-classes", action="store_true", help="(child) only the qualities of QUICK_LONG_QUALITIES")
     ap.add_argument("--plain", action="store_true", help="(child) the plain call although a dictionary size is given")
     ap.add_argument("--child", default=None)
@@ -479,7 +494,7 @@ def main():
     if args.quick_long_items:
         args.quick_items = True
         args.qualities = "2,3,4"
-    headline = [c for c in (args.only.split(",") if args.only else (list(QUICK_LONG_QUALITIES) if args.quick_long_items else QUICK_HEADLINE if args.quick_items else HEADLINE)) if c in CLASSES]
+    headline = [c for c in (args.only.split(",") if args.only else (list(QUICK_LONG_QUALITIES) if args.quick_long_items else QUICK_HEADLINE if args.quick_items else ZOPFLI_HEADLINE if args.zopfli_items else HEADLINE)) if c in CLASSES]
     if args.long_items:
         doc["what"] = "BrotliMi355xCompressBatchEx(BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS) vs the parent commit's batch call and 4-thread loop vs the oracle on one CPU core; lgwin 22"
     if args.quick_items:
@@ -487,6 +502,9 @@ def main():
     if args.quick_long_items:
         doc["what"] = ("BrotliMi355xCompressBatchEx(BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS | BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS) vs the parent commit's "
                        "BrotliMi355xCompressBatchEx(BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS), there one by one; items of two to four input blocks; lgwin 22")
+    if args.zopfli_items:
+        doc["what"] = ("BrotliMi355xCompressBatchEx(BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS) vs the parent commit's batch call, there one by one (on the first "
+                       "--loop-items items, scaled by item count), vs the oracle on one CPU core; lgwin 22")
     if args.dictionary and args.quick_items:
         return main_dictionary_quick(args, doc, save, [c for c in DICT_QUICK_HEADLINE if not args.only or c in args.only.split(",")])
     if args.dictionary:
@@ -513,7 +531,8 @@ def main():
     if "headline" not in skip:
         rows = {}
         for rnd in range(args.rounds):
-            for row in run_child(args, "batch", headline, limit=900, long_items=args.long_items, quick_items=args.quick_items, quick_long_items=args.quick_long_items):
+            for row in run_child(args, "batch", headline, limit=900, long_items=args.long_items, quick_items=args.quick_items, quick_long_items=args.quick_long_items,
+                                 zopfli_items=args.zopfli_items):
                 this = {k: row[k] for k in ("median_ms", "min_ms", "max_ms", "spread_pct", "runs")}
                 if rnd == 0:
                     rows[key(row)] = {"items": row["items"], "bytes": row["bytes"], "compressed_bytes": row["compressed_bytes"], "batch_info": row["batch_info"], "batch": this}
