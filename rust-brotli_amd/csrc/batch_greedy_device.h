@@ -5,6 +5,7 @@
 
 #include "batch_greedy.h"
 #include "lz77_chain.h"
+#include "batch_item_device.h"
 
 namespace brotli_mi355x {
 
@@ -36,34 +37,35 @@ BR_DEV void br_batch_replay_dictionary(const LiveRing& lr, const BatchDictImage&
   BR_SYNC();
 }
 
-// T: the job's tables with text / keys / flags / cmds still pointing at the group's arrays.
-// kDict: the item's text starts with J.dict.bytes bytes of custom dictionary (BrotliMi355xCompressBatchWithDictionary).
-template <bool kRows, bool kDict = false>
-BR_DEV void br_batch_item(const BatchParseJob& J, const ChainTables& T, ChainScratchT<false, kRows>& s, uint32_t* histo /* 256 words */,
-                          uint32_t index, uint32_t table) {
-  BatchItem it = J.items[index];
-  it.text_off = BR_UNIFORM(it.text_off);
-  it.bytes = BR_UNIFORM(it.bytes);
-  it.cmd_base = BR_UNIFORM(it.cmd_base);
-  it.cmd_cap = BR_UNIFORM(it.cmd_cap);
-  // item-local coordinates: position 0 is the item's first byte, so no distance reaches a neighbour and max_backward is what
-  // the reference computes for a stream that starts at 0
-  // (with a dictionary: position 0 is the dictionary's first byte and the item starts at D, as in the reference's ring buffer)
-  const uint32_t D = kDict ? BR_UNIFORM(J.dict.bytes) : 0u;
-  Lz77Params P = J.P;
-  P.total_bytes = D + it.bytes;
-  if constexpr (kDict) P.prefix_bytes = P.dict_break = D;
-  ChainTables t = T;
+// Item-local coordinates on table `table`: position 0 of t.text / t.keys / t.flags_next lies D bytes in front of the item, and lr
+// is the table's bucket rings.  D == 0: position 0 is the item's first byte, so no distance reaches a neighbour and max_backward
+// is what the reference computes for a stream that starts at 0.  With a dictionary position 0 is the dictionary's first byte and
+// the item starts at D, as in the reference's ring buffer.
+BR_DEV void br_batch_item_tables(const BatchParseJob& J, const Lz77Params& P, const BatchItem& it, uint32_t D, uint32_t table, ChainTables& t, LiveRing& lr) {
   t.text = J.text + it.text_off - D;
   t.keys = J.keys + it.text_off - D;
   t.flags_next = J.flags + it.text_off - D;
   t.cmds = J.slabs;
-  LiveRing lr;
   const size_t keys_per_table = (size_t)1 << P.bucket_bits;
   lr.num = J.num + (size_t)table * keys_per_table;
   lr.buckets = J.buckets + (((size_t)table * keys_per_table) << P.block_bits);
   lr.keys = t.keys;
   lr.bits = P.block_bits;
+}
+
+// T: the job's tables with text / keys / flags / cmds still pointing at the group's arrays.
+// kDict: the item's text starts with J.dict.bytes bytes of custom dictionary (BrotliMi355xCompressBatchWithDictionary).
+template <bool kRows, bool kDict = false>
+BR_DEV void br_batch_item(const BatchParseJob& J, const ChainTables& T, ChainScratchT<false, kRows>& s, uint32_t* histo /* 256 words */,
+                          uint32_t index, uint32_t table) {
+  const BatchItem it = br_batch_load_item(J.items, index);
+  const uint32_t D = kDict ? BR_UNIFORM(J.dict.bytes) : 0u;
+  Lz77Params P = J.P;
+  P.total_bytes = D + it.bytes;
+  if constexpr (kDict) P.prefix_bytes = P.dict_break = D;
+  ChainTables t = T;
+  LiveRing lr;
+  br_batch_item_tables(J, P, it, D, table, t, lr);
   // an empty hasher: the ring counters at 0 (a walk never reads a slot its counter does not cover: `buckets` needs no fill)
   if constexpr (kDict) {
     // the hasher as HasherPrependCustomDictionary left it, then StitchToPreviousBlock of the first block (mod.rs:210-222): the
@@ -86,95 +88,35 @@ BR_DEV void br_batch_item(const BatchParseJob& J, const ChainTables& T, ChainScr
   seg.cmd_base = it.cmd_base;
   seg.block_index = 0;
   seg.cmd_cap = it.cmd_cap;
-  SegEntry entry;
+  SegEntry entry = br_stream_start_entry(P.spree_window);
   entry.pos = D;
-  entry.apply = P.spree_window;
-  entry.cache[0] = 4;
-  entry.cache[1] = 11;
-  entry.cache[2] = 15;
-  entry.cache[3] = 16;
-  entry.insert_len = 0;
-  entry.ext_allowed = 0;
-  entry.dict_lookups = entry.dict_matches = 0;
-  entry.ext_max_distance = 0;
-  entry.dict_exact = 1;
-  entry.head_kind = kHeadNone;
-  entry.head_base = entry.head_p1 = 0;
-  entry.pad = 0;
   SegExit left;
   SegEntry next;
   BlockTail tail;
   br_parse_segment<false, kRows, true>(P, t, s, seg, entry, left, next, &lr, &tail);
-  // ---- Lz77Stage::Resolve for the only block of a stream: the pending literals become the trailing insert-only command, and
-  // should_compress (encode.rs:1325-1354) gives the verdict
-  const uint32_t bytes = it.bytes;
-  const uint32_t trailing = tail.insert_len;
-  const uint32_t cmds_all = tail.n_cmds + (trailing != 0 ? 1u : 0u), lits_all = tail.n_lits + trailing;
-  bool compress = true;
-  if (cmds_all < (bytes >> 8) + 2 && (float)lits_all > 0.99f * (float)bytes) {
-    BR_SYNC();
-    for (uint32_t i = BR_LANE; i < 256; i += BR_NLANES) histo[i] = 0;
-    BR_SYNC();
-    for (uint32_t q = 13u * (uint32_t)BR_LANE; q < bytes; q += 13u * BR_NLANES) BR_ATOMIC_INC(&histo[t.text[D + q]]);
-    BR_SYNC();
-    const float threshold = (float)bytes * 7.92f / 13.0f;
-    compress = !(br_bits_entropy(t.logs, histo, 256) > threshold);
-  }
-  if (BR_LANE == 0) {
-    BatchRecord r;
-    r.n_cmds = cmds_all;
-    r.n_lits = lits_all;
-    r.trailing = trailing;
-    r.uncompressed = compress ? 0u : 1u;
-    r.overflow = cmds_all > it.cmd_cap ? 1u : 0u;
-    r.bad_commands = 0;
-    if constexpr (kDict) {
-      // a copy of one byte: the reference cannot encode it (GetCopyLengthCode, command.rs:91-93) and neither do the tables behind
-      // br_finish_command -- the item is handed on as literals only and flagged
-      r.bad_commands = left.bad_commands;  // (lane 0 holds the exit)
-      if (r.bad_commands != 0) {
-        r.n_cmds = 1;
-        r.n_lits = r.trailing = bytes;
-        r.uncompressed = 1;
-        r.overflow = 0;
-      }
-    }
-    r.pad[0] = r.pad[1] = 0;
-    J.records[index] = r;
-  }
-  BR_SYNC();
+  // (lane 0 holds the exit)
+  br_batch_close_record(J.records + index, t.logs, histo, t.text, D, it, tail.n_cmds, tail.n_lits, tail.insert_len, kDict ? left.bad_commands : 0u);
 }
 
 // command i of item `index` as the meta-block stage wants it
 BR_DEV Command br_batch_command(const BatchParseJob& J, const BatchItem& it, const BatchRecord& r, uint32_t i) {
-  if (r.trailing != 0 && i + 1 == r.n_cmds) {
-    // Command::init_insert, command.rs:38-44
-    Command c;
-    c.insert_len_ = r.trailing;
-    c.copy_len_ = 4u << 25;
-    c.dist_extra_ = 0;
-    c.dist_prefix_ = (uint16_t)((1u << 10) | 16u);
-    c.cmd_prefix_ = br_combine_length_codes(br_insert_length_code(r.trailing), br_copy_length_code(4), false);
-    return c;
-  }
+  if (r.trailing != 0 && i + 1 == r.n_cmds) return br_insert_only_command(r.trailing);
   return br_finish_command(J.slabs[(size_t)it.cmd_base + i], J.P.num_direct_distance_codes, J.P.dist_postfix_bits);
 }
 
 // ---- items of several blocks (k_parse_batch_long) -------------------------------------------------------------------------------
 // One item of two to kBatchLongBlocks input blocks: what br_parse_live does for the blocks [0, n) of a stream that starts at 0, and at
-// the item's end what br_batch_item does for its only block.  The books between the blocks are br_parse_live's, line by line (a
-// copy, not a shared helper: that function is inlined into k_parse_live, whose code generation this leaves alone); what differs is
-// where they end up -- the chain is the only writer of its slab, so extend_last_command and the literals pending at a block's entry
-// are applied to its own raw commands in place (the host resolver's CmdPatch kinds 0 and 2), a block's commands start where the
-// block in front stopped, and every meta-block the flush rule closes leaves a record.
+// the item's end what br_batch_item does for its only block.  The chain is the only writer of its slab, so extend_last_command
+// and the literals pending at a block's entry are applied to its own raw commands in place (the host resolver's CmdPatch kinds 0
+// and 2), a block's commands start where the block in front stopped, and every meta-block the flush rule closes leaves a record.
+// The books between the blocks are the steps of BatchLongBooks (batch_item_device.h: br_books_take, br_books_close, br_books_next,
+// br_books_finish), written out here in that order: behind the shared steps k_parse_batch_long<false> compiled to 92 VGPRs
+// instead of 107 and ran 1 to 2 % slower on 128 and 256 KiB items (profiles/r18_batch_item_code.json), so
+// this call site stays as it was.  A rule changed there is changed here.
 template <bool kRows>
 BR_DEV void br_batch_item_long(const BatchParseJob& J, BatchLongRecord* records, const ChainTables& T, ChainScratchT<false, kRows>& s,
                                uint32_t* histo /* 256 words */, uint32_t index, uint32_t table) {
-  BatchItem it = J.items[index];
-  it.text_off = BR_UNIFORM(it.text_off);
-  it.bytes = BR_UNIFORM(it.bytes);
-  it.cmd_base = BR_UNIFORM(it.cmd_base);
-  it.cmd_cap = BR_UNIFORM(it.cmd_cap);
+  const BatchItem it = br_batch_load_item(J.items, index);
   Lz77Params P = J.P;
   P.total_bytes = it.bytes;
   ChainTables t = T;
@@ -190,21 +132,7 @@ BR_DEV void br_batch_item_long(const BatchParseJob& J, BatchLongRecord* records,
   lr.bits = P.block_bits;
   br_live_reset(lr, P.bucket_bits);
   Command* slab = J.slabs + (size_t)it.cmd_base;
-  SegEntry entry;
-  entry.pos = 0;
-  entry.apply = P.spree_window;
-  entry.cache[0] = 4;
-  entry.cache[1] = 11;
-  entry.cache[2] = 15;
-  entry.cache[3] = 16;
-  entry.insert_len = 0;
-  entry.ext_allowed = 0;
-  entry.dict_lookups = entry.dict_matches = 0;
-  entry.ext_max_distance = 0;
-  entry.dict_exact = 1;
-  entry.head_kind = kHeadNone;
-  entry.head_base = entry.head_p1 = 0;
-  entry.pad = 0;
+  SegEntry entry = br_stream_start_entry(P.spree_window);
   // the books of the open meta-block (LiveBlockState) and of the slab
   uint32_t mb_start = 0, mb_cmds = 0, mb_lits = 0, mb_first_cmd = 0;
   uint32_t last_valid = 0, last_dist_code = 0, last_copy_len = 0;
@@ -256,16 +184,7 @@ BR_DEV void br_batch_item_long(const BatchParseJob& J, BatchLongRecord* records,
     if (last || !(next_fits && mb_lits < limit && mb_cmds < limit)) {  // the meta-block is closed here
       const uint32_t bytes = be - mb_start;
       const uint32_t cmds_all = mb_cmds + (carry != 0 ? 1u : 0u), lits_all = mb_lits + carry;  // with the trailing insert-only command
-      bool compress = true;
-      if (cmds_all < (bytes >> 8) + 2 && (float)lits_all > 0.99f * (float)bytes) {
-        BR_SYNC();
-        for (uint32_t i = BR_LANE; i < 256; i += BR_NLANES) histo[i] = 0;
-        BR_SYNC();
-        for (uint32_t q = mb_start + 13u * (uint32_t)BR_LANE; q < be; q += 13u * BR_NLANES) BR_ATOMIC_INC(&histo[t.text[q]]);
-        BR_SYNC();
-        const float threshold = (float)bytes * 7.92f / 13.0f;
-        compress = !(br_bits_entropy(t.logs, histo, 256) > threshold);
-      }
+      const bool compress = br_should_compress(t.logs, histo, t.text, mb_start, be, cmds_all, lits_all);
       if (BR_LANE == 0) {
         BatchLongMetaBlock m;
         m.start = mb_start;
@@ -320,16 +239,7 @@ BR_DEV void br_batch_item_long(const BatchParseJob& J, BatchLongRecord* records,
 
 // command i of meta-block m of an item, as the meta-block stage wants it: its raw commands, then its trailing insert-only command
 BR_DEV Command br_batch_long_command(const BatchParseJob& J, const BatchItem& it, const BatchLongMetaBlock& m, uint32_t i) {
-  if (i >= m.n_cmds) {
-    // Command::init_insert, command.rs:38-44
-    Command c;
-    c.insert_len_ = m.trailing;
-    c.copy_len_ = 4u << 25;
-    c.dist_extra_ = 0;
-    c.dist_prefix_ = (uint16_t)((1u << 10) | 16u);
-    c.cmd_prefix_ = br_combine_length_codes(br_insert_length_code(m.trailing), br_copy_length_code(4), false);
-    return c;
-  }
+  if (i >= m.n_cmds) return br_insert_only_command(m.trailing);
   return br_finish_command(J.slabs[(size_t)it.cmd_base + m.first_cmd + i], J.P.num_direct_distance_codes, J.P.dist_postfix_bits);
 }
 

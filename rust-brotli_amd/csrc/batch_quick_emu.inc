@@ -12,17 +12,22 @@
 
 namespace brotli_mi355x {
 
-void lz77_quick_batch_parse(const QuickBatchJob& J) {
-  if (J.n_items == 0) return;
+// what every entry below starts with: the group has a table, and the tables of the static dictionary and of should_compress
+static void quick_batch_emu_tables(const QuickBatchJob& J, QuickTables& T, EntropyTables& logs) {
   if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
   const DeviceTables& dt = dev_tables();
-  QuickTables T;
   T.dict_hash = dt.dict_hash;
   T.dict_data = dt.dict_data;
   T.dict_offsets_by_length = dt.dict_offsets_by_length;
-  EntropyTables logs;
   logs.logs_16 = dt.logs_16;
   logs.logs_8 = dt.logs_8;
+}
+
+void lz77_quick_batch_parse(const QuickBatchJob& J) {
+  if (J.n_items == 0) return;
+  QuickTables T;
+  EntropyTables logs;
+  quick_batch_emu_tables(J, T, logs);
   uint32_t histo[256];
   SegExit exit_slot;
   for (uint32_t place = 0; place < J.n_items; ++place) br_quick_batch_item(J, T, logs, histo, &exit_slot, J.order[place], place % J.tables);
@@ -31,16 +36,10 @@ void lz77_quick_batch_parse(const QuickBatchJob& J) {
 
 void lz77_quick_batch_parse_dict(const QuickBatchJob& J) {
   if (J.n_items == 0) return;
-  if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
-  if (J.dict_bytes == 0 || J.image == nullptr) throw std::runtime_error("brotli_mi355x: a dictionary batch group without its table image");
-  const DeviceTables& dt = dev_tables();
   QuickTables T;
-  T.dict_hash = dt.dict_hash;
-  T.dict_data = dt.dict_data;
-  T.dict_offsets_by_length = dt.dict_offsets_by_length;
   EntropyTables logs;
-  logs.logs_16 = dt.logs_16;
-  logs.logs_8 = dt.logs_8;
+  quick_batch_emu_tables(J, T, logs);
+  if (J.dict_bytes == 0 || J.image == nullptr) throw std::runtime_error("brotli_mi355x: a dictionary batch group without its table image");
   uint32_t histo[256];
   SegExit exit_slot;
   for (uint32_t place = 0; place < J.n_items; ++place) br_quick_batch_item<true>(J, T, logs, histo, &exit_slot, J.order[place], place % J.tables);
@@ -49,15 +48,9 @@ void lz77_quick_batch_parse_dict(const QuickBatchJob& J) {
 
 void lz77_quick_batch_parse_long(const QuickBatchJob& J, BatchLongRecord* records) {
   if (J.n_items == 0) return;
-  if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
-  const DeviceTables& dt = dev_tables();
   QuickTables T;
-  T.dict_hash = dt.dict_hash;
-  T.dict_data = dt.dict_data;
-  T.dict_offsets_by_length = dt.dict_offsets_by_length;
   EntropyTables logs;
-  logs.logs_16 = dt.logs_16;
-  logs.logs_8 = dt.logs_8;
+  quick_batch_emu_tables(J, T, logs);
   uint32_t histo[256];
   SegExit exit_slot;
   for (uint32_t place = 0; place < J.n_items; ++place) br_quick_batch_item_long(J, records, T, logs, histo, &exit_slot, J.order[place], place % J.tables);

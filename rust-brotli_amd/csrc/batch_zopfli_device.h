@@ -6,6 +6,7 @@
 
 #include "batch_zopfli.h"
 #include "zopfli_device.h"
+#include "batch_item_device.h"
 
 namespace brotli_mi355x {
 
@@ -42,6 +43,7 @@ BR_DEV ZopfliBuffers br_zopfli_batch_buffers(const ZopfliBatchJob& J, uint32_t t
   return B;
 }
 
+
 // A fresh H10 hasher (InitializeH10, hash_to_binary_tree.rs:149-190; what lz77_zopfli_init leaves) on a table that the item in
 // front has used: every bucket the invalid position 0 - window_mask, and the forest slots this item can reach 0 -- the children of
 // position p live at 2 * (p & window_mask), p < bytes.  The whole wavefront writes 16 bytes per lane and step; the fill is made
@@ -51,14 +53,9 @@ BR_DEV void br_zopfli_batch_reset(const ZopfliBuffers& B, uint32_t lgwin, uint32
   const uint32_t rounded = (bytes + 63u) & ~63u;
   const uint32_t slots = rounded < (1u << lgwin) ? rounded : (1u << lgwin);  // (a multiple of 64 either way: lgwin >= 10)
   BR_SYNC();
-#if BR_SCALAR
-  for (uint32_t i = 0; i < (1u << kZBucketBits); ++i) B.buckets[i] = invalid;
-  for (uint32_t i = 0; i < 2u * slots; ++i) B.forest[i] = 0u;
-#else
-  uint4* b = (uint4*)B.buckets;
-  for (uint32_t i = (uint32_t)BR_LANE; i < (1u << kZBucketBits) / 4u; i += BR_NLANES) b[i] = make_uint4(invalid, invalid, invalid, invalid);
-  uint4* f = (uint4*)B.forest;
-  for (uint32_t i = (uint32_t)BR_LANE; i < slots / 2u; i += BR_NLANES) f[i] = make_uint4(0u, 0u, 0u, 0u);
+  br_batch_fill16(B.buckets, (1u << kZBucketBits) / 4u, invalid);
+  br_batch_fill16(B.forest, slots / 2u, 0u);
+#if !BR_SCALAR
   __threadfence();
 #endif
   BR_SYNC();
@@ -67,11 +64,7 @@ BR_DEV void br_zopfli_batch_reset(const ZopfliBuffers& B, uint32_t lgwin, uint32
 // histo: 256 words and fast: the node window, the cost tables and the queue, all the wavefront's own (LDS on the device; the
 // emulation passes an array and an empty ZFast).
 BR_DEV void br_zopfli_batch_item(const ZopfliBatchJob& J, const ZopfliTables& T, uint32_t* histo, const ZFast& fast, uint32_t index, uint32_t table) {
-  BatchItem it = J.items[index];
-  it.text_off = BR_UNIFORM(it.text_off);
-  it.bytes = BR_UNIFORM(it.bytes);
-  it.cmd_base = BR_UNIFORM(it.cmd_base);
-  it.cmd_cap = BR_UNIFORM(it.cmd_cap);
+  const BatchItem it = br_batch_load_item(J.items, index);
   if (it.bytes > J.cap) {  // (never: the plan sizes a table by the group's largest item)
     if (BR_LANE == 0) {
       BatchRecord r{};
@@ -98,21 +91,7 @@ BR_DEV void br_zopfli_batch_item(const ZopfliBatchJob& J, const ZopfliTables& T,
   seg.cmd_base = it.cmd_base;
   seg.block_index = 0;
   seg.cmd_cap = it.cmd_cap;
-  SegEntry entry;
-  entry.pos = 0;
-  entry.apply = 0;
-  entry.cache[0] = 4;  // the distance cache a stream starts with
-  entry.cache[1] = 11;
-  entry.cache[2] = 15;
-  entry.cache[3] = 16;
-  entry.insert_len = 0;
-  entry.ext_allowed = 0;
-  entry.dict_lookups = entry.dict_matches = 0;
-  entry.ext_max_distance = 0;
-  entry.dict_exact = 1;
-  entry.head_kind = kHeadNone;
-  entry.head_base = entry.head_p1 = 0;
-  entry.pad = 0;
+  const SegEntry entry = br_stream_start_entry(0);
   // (what br_zopfli_begin leaves for a block at 0 without extend_last_command: nothing to stitch to)
   ctl->position = 0;
   ctl->num_bytes = it.bytes;
@@ -121,43 +100,10 @@ BR_DEV void br_zopfli_batch_item(const ZopfliBatchJob& J, const ZopfliTables& T,
   BR_SYNC();
   br_zopfli_parse(Z, T, B, text, seg, entry, ctl, /*precomputed=*/false, J.slabs + (size_t)it.cmd_base, exit_slot, fast);
   BR_SYNC();  // (the exit is written)
-  // ---- Lz77Stage::Resolve for the only block of a stream: the pending literals become the trailing insert-only command, and
-  // should_compress (encode.rs:1325-1354) gives the verdict
-  const uint32_t bytes = it.bytes;
+  // (bad_commands: where the reference panics, kZopfliReferencePanics)
   const uint32_t trailing = BR_UNIFORM(exit_slot->insert_len);
   const uint32_t raw_cmds = BR_UNIFORM(exit_slot->n_cmds), raw_lits = BR_UNIFORM(exit_slot->n_lits);
-  const uint32_t panics = BR_UNIFORM(exit_slot->bad_commands);
-  const uint32_t cmds_all = raw_cmds + (trailing != 0 ? 1u : 0u), lits_all = raw_lits + trailing;
-  bool compress = true;
-  if (cmds_all < (bytes >> 8) + 2 && (float)lits_all > 0.99f * (float)bytes) {
-    BR_SYNC();
-    for (uint32_t i = BR_LANE; i < 256; i += BR_NLANES) histo[i] = 0;
-    BR_SYNC();
-    for (uint32_t q = 13u * (uint32_t)BR_LANE; q < bytes; q += 13u * BR_NLANES) BR_ATOMIC_INC(&histo[text[q]]);
-    BR_SYNC();
-    const float threshold = (float)bytes * 7.92f / 13.0f;
-    compress = !(br_bits_entropy(T.logs, histo, 256) > threshold);
-  }
-  if (BR_LANE == 0) {
-    BatchRecord r;
-    r.n_cmds = cmds_all;
-    r.n_lits = lits_all;
-    r.trailing = trailing;
-    r.uncompressed = compress ? 0u : 1u;
-    r.overflow = cmds_all > it.cmd_cap ? 1u : 0u;
-    // where the reference panics (kZopfliReferencePanics) the item is handed on as literals only and flagged, as br_batch_item
-    // does for the copies the reference cannot encode: its stream is dropped by the host
-    r.bad_commands = panics;
-    if (panics != 0) {
-      r.n_cmds = 1;
-      r.n_lits = r.trailing = bytes;
-      r.uncompressed = 1;
-      r.overflow = 0;
-    }
-    r.pad[0] = r.pad[1] = 0;
-    J.records[index] = r;
-  }
-  BR_SYNC();
+  br_batch_close_record(J.records + index, T.logs, histo, text, 0, it, raw_cmds, raw_lits, trailing, BR_UNIFORM(exit_slot->bad_commands));
 }
 
 }  // namespace brotli_mi355x

@@ -30,15 +30,7 @@ __global__ __launch_bounds__(64) void k_zopfli_batch(ZopfliBatchJob J, ZopfliTab
   fast.cost_cmd = cost_cmd;
   fast.cost_dist = J.dist_alphabet_size <= 1136 ? cost_dist : (float*)nullptr;
   fast.queue = &queue;
-  for (;;) {
-    uint32_t mine = 0;
-    if (threadIdx.x == 0) mine = atomicAdd(J.counter, 1u);
-    const uint32_t place = BR_UNIFORM(mine);
-    if (place >= J.n_items) break;
-    const uint32_t index = BR_UNIFORM(J.order[place]);
-    if (index >= J.n_items) break;  // (never: the plan's order is a permutation)
-    br_zopfli_batch_item(J, T, histo, fast, index, table);
-  }
+  for (uint32_t index; br_batch_next_index(J.counter, J.order, J.n_items, index);) br_zopfli_batch_item(J, T, histo, fast, index, table);
 }
 
 void lz77_zopfli_batch_parse(const ZopfliBatchJob& J) {

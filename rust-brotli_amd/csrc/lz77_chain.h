@@ -2331,7 +2331,7 @@ BR_DEV void br_parse_live(const Lz77Params& P, const ChainTables& t, ChainScratc
     if (j + 1 == last) break;
     if (P.reset_pos != 0 && BR_UNIFORM(seg.blk_end) == P.reset_pos) br_live_reset(lr, P.bucket_bits);  // the block that starts there searches an empty table
     if (seg.flags & kSegTailStitched) br_live_store(lr, seg.blk_end - 3u, 1, 3, 1, 0);  // StitchToPreviousBlock, mod.rs:210-222
-    // ---- the books, as in Lz77Stage::Resolve
+    // ---- the books, as in Lz77Stage::Resolve (the batch routes keep theirs in batch_item_device.h: the same rules, change both)
     if (tail.ext_len != 0 && st.last_valid) st.last_copy_len += tail.ext_len;
     st.mb_cmds += tail.n_cmds;
     st.mb_lits += tail.n_lits;

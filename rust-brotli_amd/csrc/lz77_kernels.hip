@@ -2595,11 +2595,19 @@ static ChainTables batch_chain_tables(const BatchParseJob& J) {
   T.logs.logs_8 = dt.logs_8;
   return T;
 }
+// the kRows instance (candidate rows of up to kRowEntries entries) or the other one, by the ring depth of the job
+static bool batch_chain_rows(const Lz77Params& P) {
+  if ((1u << P.block_bits) <= kRowEntries) return true;
+  if (P.block_bits <= 7) return false;
+  throw std::runtime_error("brotli_mi355x: the batch chains do not run the 512-deep rings");
+}
 
 // One wavefront per table, persistent over the group: it takes the next place of `order` (largest item first) from the device
 // counter until none is left.  Like k_parse_live a chain is bound by the latency of its own dependent loads; the throughput of
-// the launch is the number of chains in flight.
-template <bool kRows>
+// the launch is the number of chains in flight.  kDict: the items lie behind a shared custom dictionary (J.dict) -- instances of
+// their own, so that the plain ones carry none of it.  (The loop is br_batch_next_index, batch_item_device.h, written out: behind
+// the helper each of these instances and of k_parse_batch_long spilled two to six SGPRs more)
+template <bool kRows, bool kDict>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_parse_batch(BatchParseJob J, ChainTables T) {
   __shared__ ChainScratchT<false, kRows> scratch;
   __shared__ uint32_t histo[256];
@@ -2612,25 +2620,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 4))) void
     if (place >= J.n_items) break;
     const uint32_t index = BR_UNIFORM(J.order[place]);
     if (index >= J.n_items) break;  // (never: the plan's order is a permutation)
-    br_batch_item<kRows>(J, T, scratch, histo, index, table);
-  }
-}
-
-// The same launch for items behind a shared custom dictionary (J.dict): a sibling, so that the instances above stay what they were.
-template <bool kRows>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_parse_batch_dict(BatchParseJob J, ChainTables T) {
-  __shared__ ChainScratchT<false, kRows> scratch;
-  __shared__ uint32_t histo[256];
-  const uint32_t table = blockIdx.x;
-  if (table >= J.tables) return;
-  for (;;) {
-    uint32_t mine = 0;
-    if (threadIdx.x == 0) mine = atomicAdd(J.counter, 1u);
-    const uint32_t place = BR_UNIFORM(mine);
-    if (place >= J.n_items) break;
-    const uint32_t index = BR_UNIFORM(J.order[place]);
-    if (index >= J.n_items) break;  // (never: the plan's order is a permutation)
-    br_batch_item<kRows, true>(J, T, scratch, histo, index, table);
+    br_batch_item<kRows, kDict>(J, T, scratch, histo, index, table);
   }
 }
 
@@ -2718,24 +2708,10 @@ void lz77_batch_parse(const BatchParseJob& J) {
   if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
   const ChainTables T = batch_chain_tables(J);
   const uint32_t grid = J.tables < J.n_items ? J.tables : J.n_items;
-  if (J.dict.bytes != 0) {
-    if ((1u << J.P.block_bits) <= kRowEntries) {
-      hipLaunchKernelGGL((k_parse_batch_dict<true>), dim3(grid), dim3(64), 0, BR_STREAM, J, T);
-    } else if (J.P.block_bits <= 7) {
-      hipLaunchKernelGGL((k_parse_batch_dict<false>), dim3(grid), dim3(64), 0, BR_STREAM, J, T);
-    } else {
-      throw std::runtime_error("brotli_mi355x: the batch chains do not run the 512-deep rings");
-    }
-    HIP_CHECK(hipGetLastError());
-    return;
-  }
-  if ((1u << J.P.block_bits) <= kRowEntries) {
-    hipLaunchKernelGGL((k_parse_batch<true>), dim3(grid), dim3(64), 0, BR_STREAM, J, T);
-  } else if (J.P.block_bits <= 7) {
-    hipLaunchKernelGGL((k_parse_batch<false>), dim3(grid), dim3(64), 0, BR_STREAM, J, T);
-  } else {
-    throw std::runtime_error("brotli_mi355x: the batch chains do not run the 512-deep rings");
-  }
+  const bool rows = batch_chain_rows(J.P);
+  const auto kernel = J.dict.bytes != 0 ? (rows ? k_parse_batch<true, true> : k_parse_batch<false, true>)
+                                        : (rows ? k_parse_batch<true, false> : k_parse_batch<false, false>);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), 0, BR_STREAM, J, T);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -2777,13 +2753,7 @@ void lz77_batch_parse_long(const BatchParseJob& J, BatchLongRecord* records) {
   if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
   const ChainTables T = batch_chain_tables(J);
   const uint32_t grid = J.tables < J.n_items ? J.tables : J.n_items;
-  if ((1u << J.P.block_bits) <= kRowEntries) {
-    hipLaunchKernelGGL((k_parse_batch_long<true>), dim3(grid), dim3(64), 0, BR_STREAM, J, records, T);
-  } else if (J.P.block_bits <= 7) {
-    hipLaunchKernelGGL((k_parse_batch_long<false>), dim3(grid), dim3(64), 0, BR_STREAM, J, records, T);
-  } else {
-    throw std::runtime_error("brotli_mi355x: the batch chains do not run the 512-deep rings");
-  }
+  hipLaunchKernelGGL(batch_chain_rows(J.P) ? k_parse_batch_long<true> : k_parse_batch_long<false>, dim3(grid), dim3(64), 0, BR_STREAM, J, records, T);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -80,87 +80,63 @@ __global__ __launch_bounds__(64) void k_quick_batch(QuickBatchJob J, QuickTables
   __shared__ SegExit exit_slot;
   const uint32_t table = blockIdx.x;
   if (table >= J.tables) return;
-  for (;;) {
-    uint32_t mine = 0;
-    if (threadIdx.x == 0) mine = atomicAdd(J.counter, 1u);
-    const uint32_t place = BR_UNIFORM(mine);
-    if (place >= J.n_items) break;
-    const uint32_t index = BR_UNIFORM(J.order[place]);
-    if (index >= J.n_items) break;  // (never: the plan's order is a permutation)
-    br_quick_batch_item(J, T, logs, histo, &exit_slot, index, table);
-  }
+  for (uint32_t index; br_batch_next_index(J.counter, J.order, J.n_items, index);) br_quick_batch_item<false>(J, T, logs, histo, &exit_slot, index, table);
 }
 
-// The same launch for items behind a shared custom dictionary (J.dict_bytes, J.image): a sibling, so that the kernel above stays
-// what it was.  A chain copies the call's table image over its table where that one zeroes it.
+// The same launch for items behind a shared custom dictionary (J.dict_bytes, J.image): a chain copies the call's table image over
+// its table where the one above zeroes it.  (Two kernels, not two instances of a template: the compiler cuts the exit slot of a
+// plain kernel down to the fields that are read, and leaves the one of a template instance whole.)
 __global__ __launch_bounds__(64) void k_quick_batch_dict(QuickBatchJob J, QuickTables T, EntropyTables logs) {
   __shared__ uint32_t histo[256];
   __shared__ SegExit exit_slot;
   const uint32_t table = blockIdx.x;
   if (table >= J.tables) return;
-  for (;;) {
-    uint32_t mine = 0;
-    if (threadIdx.x == 0) mine = atomicAdd(J.counter, 1u);
-    const uint32_t place = BR_UNIFORM(mine);
-    if (place >= J.n_items) break;
-    const uint32_t index = BR_UNIFORM(J.order[place]);
-    if (index >= J.n_items) break;  // (never: the plan's order is a permutation)
-    br_quick_batch_item<true>(J, T, logs, histo, &exit_slot, index, table);
-  }
+  for (uint32_t index; br_batch_next_index(J.counter, J.order, J.n_items, index);) br_quick_batch_item<true>(J, T, logs, histo, &exit_slot, index, table);
 }
 
-void lz77_quick_batch_parse(const QuickBatchJob& J) {
-  if (J.n_items == 0) return;
-  if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
-  const DeviceTables& dt = dev_tables();
-  EntropyTables logs;
-  logs.logs_16 = dt.logs_16;
-  logs.logs_8 = dt.logs_8;
-  const uint32_t grid = J.tables < J.n_items ? J.tables : J.n_items;
-  hipLaunchKernelGGL(k_quick_batch, dim3(grid), dim3(64), 0, BR_STREAM, J, quick_tables(), logs);
-  HIP_CHECK(hipGetLastError());
-}
-
-void lz77_quick_batch_parse_dict(const QuickBatchJob& J) {
-  if (J.n_items == 0) return;
-  if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
-  if (J.dict_bytes == 0 || J.image == nullptr) throw std::runtime_error("brotli_mi355x: a dictionary batch group without its table image");
-  const DeviceTables& dt = dev_tables();
-  EntropyTables logs;
-  logs.logs_16 = dt.logs_16;
-  logs.logs_8 = dt.logs_8;
-  const uint32_t grid = J.tables < J.n_items ? J.tables : J.n_items;
-  hipLaunchKernelGGL(k_quick_batch_dict, dim3(grid), dim3(64), 0, BR_STREAM, J, quick_tables(), logs);
-  HIP_CHECK(hipGetLastError());
-}
-
-// ---- items of two to kBatchLongBlocks input blocks (batch_quick.h): the launch shape of k_quick_batch, the item code walks from
+// Items of two to kBatchLongBlocks input blocks (batch_quick.h): the launch shape of k_quick_batch, the item code walks from
 // block to block and leaves one BatchLongRecord per item.
 __global__ __launch_bounds__(64) void k_quick_batch_long(QuickBatchJob J, BatchLongRecord* __restrict__ records, QuickTables T, EntropyTables logs) {
   __shared__ uint32_t histo[256];
   __shared__ SegExit exit_slot;
   const uint32_t table = blockIdx.x;
   if (table >= J.tables) return;
-  for (;;) {
-    uint32_t mine = 0;
-    if (threadIdx.x == 0) mine = atomicAdd(J.counter, 1u);
-    const uint32_t place = BR_UNIFORM(mine);
-    if (place >= J.n_items) break;
-    const uint32_t index = BR_UNIFORM(J.order[place]);
-    if (index >= J.n_items) break;  // (never: the plan's order is a permutation)
-    br_quick_batch_item_long(J, records, T, logs, histo, &exit_slot, index, table);
-  }
+  for (uint32_t index; br_batch_next_index(J.counter, J.order, J.n_items, index);) br_quick_batch_item_long(J, records, T, logs, histo, &exit_slot, index, table);
 }
 
-void lz77_quick_batch_parse_long(const QuickBatchJob& J, BatchLongRecord* records) {
-  if (J.n_items == 0) return;
-  if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
+static EntropyTables entropy_tables() {
   const DeviceTables& dt = dev_tables();
   EntropyTables logs;
   logs.logs_16 = dt.logs_16;
   logs.logs_8 = dt.logs_8;
-  const uint32_t grid = J.tables < J.n_items ? J.tables : J.n_items;
-  hipLaunchKernelGGL(k_quick_batch_long, dim3(grid), dim3(64), 0, BR_STREAM, J, records, quick_tables(), logs);
+  return logs;
+}
+// one wavefront per table, none without an item; 0: an empty group, nothing to launch
+static uint32_t quick_batch_grid(const QuickBatchJob& J) {
+  if (J.n_items == 0) return 0;
+  if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
+  return J.tables < J.n_items ? J.tables : J.n_items;
+}
+
+void lz77_quick_batch_parse(const QuickBatchJob& J) {
+  const uint32_t grid = quick_batch_grid(J);
+  if (grid == 0) return;
+  hipLaunchKernelGGL(k_quick_batch, dim3(grid), dim3(64), 0, BR_STREAM, J, quick_tables(), entropy_tables());
+  HIP_CHECK(hipGetLastError());
+}
+
+void lz77_quick_batch_parse_dict(const QuickBatchJob& J) {
+  const uint32_t grid = quick_batch_grid(J);
+  if (grid == 0) return;
+  if (J.dict_bytes == 0 || J.image == nullptr) throw std::runtime_error("brotli_mi355x: a dictionary batch group without its table image");
+  hipLaunchKernelGGL(k_quick_batch_dict, dim3(grid), dim3(64), 0, BR_STREAM, J, quick_tables(), entropy_tables());
+  HIP_CHECK(hipGetLastError());
+}
+
+void lz77_quick_batch_parse_long(const QuickBatchJob& J, BatchLongRecord* records) {
+  const uint32_t grid = quick_batch_grid(J);
+  if (grid == 0) return;
+  hipLaunchKernelGGL(k_quick_batch_long, dim3(grid), dim3(64), 0, BR_STREAM, J, records, quick_tables(), entropy_tables());
   HIP_CHECK(hipGetLastError());
 }
 

@@ -52,6 +52,10 @@ reference's way on H10 trees of its own.  The parent's library is measured throu
 one (on the first --loop-items items, scaled by item count).  The classes are 1024x4KiB, 256x16KiB, 64x64KiB and 16x4KiB, the few-items
 case.  (--qualities 10,11 is accepted: BrotliEncoderCompress runs quality 10 at quality 9, and it goes one by one in both builds.)
 
+With --same-call (and any of the above) the parent's library is measured through the very call this build is measured through, route bits
+and dictionary included, alternating with it --rounds times: the A/B of a change that keeps the routes.  Per class the result holds the
+medians of both, their difference, and the parent's own spread between its rounds as the margin; nothing else is measured.
+
 Every measurement runs in a child process of its own (the table's home is one setting per process, read once; the parent's library
 is another shared object), one after the other, each under its own time limit; the first failure ends the probe.
 
@@ -453,6 +457,33 @@ def main_dictionary_quick(args, doc, save, classes):
     print(json.dumps(doc, indent=1))
 
 
+def main_same_call(args, doc, save, classes):
+    """--same-call: this build and the parent's library through the very same call (route bits, dictionary), alternating, one child
+    each -- for a change that keeps the routes and must not cost them anything.  Per class: the median of either build's round
+    medians, and the parent's own run-to-run spread (the largest difference between its rounds) as the margin."""
+    doc["what"] = "this build against the parent commit's library through the same batch call (%s), alternating, %d rounds; lgwin 22" % (
+        ", ".join(n for n in ("long_items", "quick_items", "quick_long_items", "zopfli_items") if getattr(args, n)) or "no route bit", args.rounds)
+    routes = dict(long_items=args.long_items, quick_items=args.quick_items, quick_long_items=args.quick_long_items, zopfli_items=args.zopfli_items)
+    rows = {}
+    for rnd in range(args.rounds):
+        for name, lib in (("this_rounds", args.lib), ("parent_rounds", os.path.abspath(args.parent_lib))):
+            for row in run_child(args, "batch", classes, lib=lib, limit=900, **routes):
+                v = rows.setdefault(key(row), {"items": row["items"], "bytes": row["bytes"]})
+                v.setdefault(name, []).append({k: row[k] for k in ("median_ms", "min_ms", "max_ms", "spread_pct", "runs")})
+                # (the same streams from both builds, in every round)
+                assert v.setdefault("compressed_bytes", row["compressed_bytes"]) == row["compressed_bytes"], row
+        doc["classes"] = rows
+        save()
+    for v in rows.values():
+        this, parent = [r["median_ms"] for r in v["this_rounds"]], [r["median_ms"] for r in v["parent_rounds"]]
+        v["this_median_ms"], v["parent_median_ms"] = statistics.median(this), statistics.median(parent)
+        v["margin_ms"] = round(max(parent) - min(parent), 3)
+        v["this_minus_parent_ms"] = round(v["this_median_ms"] - v["parent_median_ms"], 3)
+        v["inside_margin"] = bool(v["this_minus_parent_ms"] <= v["margin_ms"])
+    save()
+    print(json.dumps(doc, indent=1))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lib", default=os.path.join(ROOT, "rust-brotli_amd", "libbrotli_mi355x.so"))
@@ -472,6 +503,7 @@ def main():
     ap.add_argument("--quick-items", action="store_true", help="this build through BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS (--qualities 2,3,4)")
     ap.add_argument("--quick-long-items", action="store_true", help="this build through routes QUICK_ITEMS | QUICK_LONG_ITEMS, the parent through QUICK_ITEMS (qualities 2,3,4 per class)")
     ap.add_argument("--zopfli-items", action="store_true", help="this build through BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS (--qualities 11)")
+    ap.add_argument("--same-call", action="store_true", help="the parent's library through the same call as this build, alternating --rounds times (needs --parent-lib)")
     ap.add_argument("--quick-long-classes", action="store_true", help="(child) only the qualities of QUICK_LONG_QUALITIES")
     ap.add_argument("--plain", action="store_true", help="(child) the plain call although a dictionary size is given")
     ap.add_argument("--child", default=None)
@@ -505,6 +537,9 @@ def main():
     if args.zopfli_items:
         doc["what"] = ("BrotliMi355xCompressBatchEx(BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS) vs the parent commit's batch call, there one by one (on the first "
                        "--loop-items items, scaled by item count), vs the oracle on one CPU core; lgwin 22")
+    if args.same_call:
+        dict_classes = DICT_QUICK_HEADLINE if args.quick_items else ["4096x4KiB", "1024x64KiB"]
+        return main_same_call(args, doc, save, [c for c in dict_classes if not args.only or c in args.only.split(",")] if args.dictionary else headline)
     if args.dictionary and args.quick_items:
         return main_dictionary_quick(args, doc, save, [c for c in DICT_QUICK_HEADLINE if not args.only or c in args.only.split(",")])
     if args.dictionary:
