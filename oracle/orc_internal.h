@@ -220,6 +220,9 @@ void orc_store_huffman_tree(const uint8_t* depths, size_t num, size_t* storage_i
 void orc_convert_bit_depths_to_symbols(const uint8_t* depth, size_t len, uint16_t* bits);
 void orc_build_and_store_huffman_tree_fast(const uint32_t* histogram, size_t histogram_total, size_t max_bits,
                                            uint8_t* depth, uint16_t* bits, size_t* storage_ix, uint8_t* storage);
+/* one histogram -> optimised counts, code and serialised tree (tests/test_build_codes.py) */
+void orc_build_code(size_t hist_len, size_t alphabet_size, size_t opt_len, int optimize, uint32_t* histogram, uint8_t* depth,
+                    uint16_t* bits, uint8_t* storage, size_t* storage_ix);
 /* compress_fragment_two_pass.rs (quality 1), orc_fragment.c */
 void orc_compress_fragment_two_pass(const uint8_t* input, size_t input_size, int is_last, uint32_t* command_buf,
                                     uint8_t* literal_buf, int32_t* table, size_t table_size, size_t* storage_ix,

@@ -1578,3 +1578,19 @@ void orc_build_and_store_huffman_tree_fast(const uint32_t* histogram, size_t his
                                            uint8_t* depth, uint16_t* bits, size_t* storage_ix, uint8_t* storage) {
   build_and_store_huffman_tree_fast(histogram, histogram_total, max_bits, depth, bits, storage_ix, storage);
 }
+
+/* ------------------------------------------------------------------ export for the parity tests of the prefix-code builder
+ * One histogram as the stream path treats it: optimize_huffman_counts_for_rle over the first opt_len counts (when asked), then
+ * build_and_store_huffman_tree(hist_len, alphabet_size).  depth / bits: hist_len entries, zeroed by the caller; storage: zeroed,
+ * with 8 bytes of slack behind the last bit (orc_write_bits). */
+void orc_build_code(size_t hist_len, size_t alphabet_size, size_t opt_len, int optimize, uint32_t* histogram, uint8_t* depth,
+                    uint16_t* bits, uint8_t* storage, size_t* storage_ix) {
+  HuffmanTree* tree = (HuffmanTree*)malloc((2 * 704 + 1) * sizeof(HuffmanTree));
+  if (optimize) {
+    uint8_t good_for_rle[704];
+    memset(good_for_rle, 0, sizeof(good_for_rle));
+    optimize_huffman_counts_for_rle(opt_len, histogram, good_for_rle);
+  }
+  build_and_store_huffman_tree(histogram, hist_len, alphabet_size, tree, depth, bits, storage_ix, storage);
+  free(tree);
+}

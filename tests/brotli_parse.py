@@ -251,9 +251,12 @@ def _read_context_map(br, size, ntrees):
     return dict(rlemax=rlemax, imtf=imtf, code=desc), cmap
 
 
-def parse(stream, max_metablocks=None):
+def parse(stream, max_metablocks=None, first_header_only=False):
     """-> dict(wbits, metablocks=[...], output=bytes).  Every meta-block dict holds the header fields and `cmds`:
-    a list of (insert_len, copy_len, distance_symbol or None (implicit last distance), distance, out_pos)."""
+    a list of (insert_len, copy_len, distance_symbol or None (implicit last distance), distance, out_pos).
+    `code_bits` of a compressed meta-block: the length in bits of every literal, command and distance prefix code as it stands in
+    the header (three lists).  first_header_only: stop behind the header of the first compressed meta-block (no `cmds`, no output) --
+    a body of megabytes takes this parser minutes."""
     T = _Tables.get()
     br = _Bits(stream)
     if br.read(1) == 0:
@@ -348,20 +351,30 @@ def parse(stream, max_metablocks=None):
         mb["cmap_l"], mb["cmap_d"] = cmap_l, cmap_d
         lit_codes, cmd_codes, dist_codes = [], [], []
         mb["lit_lengths"], mb["cmd_lengths"], mb["dist_lengths"] = [], [], []
+        mb["code_bits"] = ([], [], [])
         for _ in range(ntrees_l):
+            at = br.pos
             d, c = _read_prefix_code(br, 256)
+            mb["code_bits"][0].append(br.pos - at)
             lit_codes.append(c)
             mb["lit_lengths"].append(d["lengths"])
         for _ in range(nbl[1]):
+            at = br.pos
             d, c = _read_prefix_code(br, 704)
+            mb["code_bits"][1].append(br.pos - at)
             cmd_codes.append(c)
             mb["cmd_lengths"].append(d["lengths"])
         dist_alphabet = 16 + ndirect + (48 << npostfix)
         for _ in range(ntrees_d):
+            at = br.pos
             d, c = _read_prefix_code(br, dist_alphabet)
+            mb["code_bits"][2].append(br.pos - at)
             dist_codes.append(c)
             mb["dist_lengths"].append(d["lengths"])
         mb["data_bit_offset"] = br.pos
+        if first_header_only:
+            metablocks.append(mb)
+            break
         btype = [0, 0, 0]
         prev_btype = [1, 1, 1]
         cmds = []

@@ -98,3 +98,29 @@ def encode_stream(L, data, params, prefix=b"", continuation=True, segment_bytes=
     d["chains_launched"] = st[28]  # over all launches: warm-up dry runs, round 0, re-parses
     d["num_segments"] = st[29]
     return out.raw[:n], d
+
+
+ROW_LEN = (256, 704, 544)  # kRowLen: literal, command, distance histogram rows
+TREE_BITS_WORDS = 64       # kTreeBitsWords
+CODE_OPTIMIZED, CODE_PLAIN = 0, 1
+
+
+def build_codes(L, kind, num_distance_symbols, mode, histograms):
+    """brotli_mi355x_debug_build_codes: `histograms` (numpy uint32, n_rows x ROW_LEN[kind]) through the prefix-code builder of the
+    library (k_build_codes on the device, the scalar form in the emulation).  Returns (histograms after, depth, bits, tree bytes
+    [n_rows x 512], tree_nbits) as numpy arrays."""
+    import numpy as np
+    L.brotli_mi355x_debug_build_codes.restype = ctypes.c_int
+    L.brotli_mi355x_debug_build_codes.argtypes = [ctypes.c_uint32] * 4 + [ctypes.c_void_p] * 5
+    h = np.array(histograms, dtype=np.uint32, order="C")
+    n = h.shape[0]
+    assert h.shape == (n, ROW_LEN[kind])
+    depth = np.full((n, ROW_LEN[kind]), 0xee, dtype=np.uint8)
+    bits = np.full((n, ROW_LEN[kind]), 0xeeee, dtype=np.uint16)
+    words = np.full((n, TREE_BITS_WORDS), 0xeeeeeeeeeeeeeeee, dtype=np.uint64)
+    nbits = np.full(n, 0xeeeeeeee, dtype=np.uint32)
+    r = L.brotli_mi355x_debug_build_codes(kind, num_distance_symbols, mode, n, h.ctypes.data, depth.ctypes.data, bits.ctypes.data,
+                                          words.ctypes.data, nbits.ctypes.data)
+    if r != 0:
+        raise RuntimeError("brotli_mi355x_debug_build_codes returned %d" % r)
+    return h, depth, bits, words.view(np.uint8).reshape(n, TREE_BITS_WORDS * 8), nbits

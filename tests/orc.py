@@ -335,3 +335,23 @@ def concat(files, window=None, bs=4096):
     r = L.orc_concat(n, ptrs, sizes, -1 if window is None else window, bs, out, cap, ctypes.byref(got))
     assert r >= 0, "oracle concat: output buffer too small / unexpected state (%d)" % r
     return r, out.raw[:got.value]
+
+
+def build_code(hist_len, alphabet_size, opt_len, optimize, histogram, row_len):
+    """orc_build_code on one histogram (a sequence of at least hist_len counts): the reference's optimize_huffman_counts_for_rle (when
+    asked) and build_and_store_huffman_tree.  Returns (histogram after, depth, bits, tree bytes, tree bit count); the three arrays are
+    numpy rows of row_len entries, zero where the code does not reach."""
+    import numpy as np
+    L = lib()
+    L.orc_build_code.restype = None
+    L.orc_build_code.argtypes = [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t)]
+    h = np.zeros(row_len, dtype=np.uint32)
+    h[:len(histogram)] = histogram
+    depth = np.zeros(row_len, dtype=np.uint8)
+    bits = np.zeros(row_len, dtype=np.uint16)
+    storage = np.zeros(1024, dtype=np.uint8)  # (a tree is at most 4096 bits; orc_write_bits stores 8 bytes at a time)
+    ix = ctypes.c_size_t(0)
+    L.orc_build_code(hist_len, alphabet_size, opt_len, 1 if optimize else 0, h.ctypes.data, depth.ctypes.data, bits.ctypes.data,
+                     storage.ctypes.data, ctypes.byref(ix))
+    return h, depth, bits, storage, ix.value

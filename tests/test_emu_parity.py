@@ -9,6 +9,7 @@ import os
 import pytest
 
 import emu
+import header_cases
 import orc
 import synth
 from cmp_lz77 import check
@@ -60,6 +61,17 @@ def test_stream_bytes_fixtures(L):
         assert check_bytes(L, b, d, [(Q, 5), (W, 22), (168, 1), (169, 1)], verbose=False)  # appendable + magic number
         assert check_bytes(L, b, d, [(Q, 5), (W, 22), (167, 1)], verbose=False)  # catable
         assert check_bytes(L, b, d, [(Q, 6), (W, 22), (168, 1), (172, 1)], verbose=False)  # appendable + byte_align
+
+
+def test_header_above_the_workgroup_memory_threshold(L):
+    # (the device composes this header in global memory, header_cases.py; the emulation has one path)
+    d = header_cases.input_above()
+    assert check_bytes(L, "256 regimes x 6000", d, header_cases.params(d), verbose=False)
+
+
+def test_header_below_the_workgroup_memory_threshold(L):
+    d = header_cases.input_below()
+    assert check_bytes(L, "256 regimes x 2800", d, header_cases.params(d), verbose=False)
 
 
 def test_stream_bytes_synthetic(L):

@@ -7,7 +7,10 @@ the window goes to the stream by itself.  So the cases are: fewer than 64 items,
 (and a stored meta-block) inside a wavefront, pieces far behind the window (long literal runs), and the other code modes that
 share the kernels (qualities 2-4, 9, 10, "9.5").  k_context_stats samples 64 bytes every 4096: lengths around the first and second
 sample and around 256 samples (a workgroup of the earlier kernel).  Three cases run once more under BROTLI_MI355X_SELFTEST=1, where
-the library compares the stream behind mb_emit with a piece-by-piece emission and the statistics rows with a host recomputation."""
+the library compares the stream behind mb_emit with a piece-by-piece emission and the statistics rows with a host recomputation.
+
+k_write_headers composes a header in workgroup memory unless the meta-block's prefix codes exceed 163 840 bits, and in global memory
+above that: one case on either side of the line, measured on the oracle's stream (header_cases.py)."""
 import functools
 import os
 import random
@@ -17,6 +20,7 @@ import sys
 import pytest
 
 import emu
+import header_cases
 import synth
 from cmp_stream import check_bytes
 
@@ -112,6 +116,17 @@ def test_context_statistics_sample_counts(L, length):
     d = markov_1m()[:length]
     assert len(d) == length
     assert check_bytes(L, "markov %d" % length, d, [(Q, 5), (W, 22), (SH, length)])
+
+
+def test_header_composed_in_global_memory(L):
+    # k_write_headers: the prefix codes of the one meta-block exceed what the workgroup-memory buffer is sized for (header_cases.py)
+    d = header_cases.input_above()
+    assert check_bytes(L, "256 regimes x 6000", d, header_cases.params(d))
+
+
+def test_largest_header_composed_in_workgroup_memory(L):
+    d = header_cases.input_below()
+    assert check_bytes(L, "256 regimes x 2800", d, header_cases.params(d))
 
 
 _SELFTEST_CHILD = """
