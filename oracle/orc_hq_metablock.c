@@ -143,9 +143,14 @@ static float cluster_cost_diff(size_t size_a, size_t size_b) {
   return (float)size_a * orc_fast_log2(size_a) + (float)size_b * orc_fast_log2(size_b) -
          (float)size_c * orc_fast_log2(size_c);
 }
+/* Counters for the tests of the device builder (orc_split_byte_vector / orc_cluster_histograms): which corners of the
+ * clustering a given input reaches.  Null outside those two calls; nothing below reads them back. */
+static _Thread_local OrcHqCounters* hq_counters = NULL;
+
 /* cluster.rs:41-48 */
 static int histogram_pair_is_less(const HistogramPair* p1, const HistogramPair* p2) {
   if (p1->cost_diff != p2->cost_diff) return p1->cost_diff > p2->cost_diff;
+  if (hq_counters && (p1->idx1 != p2->idx1 || p1->idx2 != p2->idx2)) hq_counters->ties++; /* (the head against itself is no tie) */
   return (uint32_t)(p1->idx2 - p1->idx1) > (uint32_t)(p2->idx2 - p2->idx1);
 }
 
@@ -184,6 +189,7 @@ static void compare_and_push_to_queue(const Histo* out, size_t len, const uint32
   }
   if (is_good_pair) {
     p.cost_diff += p.cost_combo;
+    if (hq_counters && *num_pairs >= max_num_pairs) hq_counters->queue_full++;
     if (*num_pairs > 0 && histogram_pair_is_less(&pairs[0], &p)) {
       if (*num_pairs < max_num_pairs) {
         pairs[*num_pairs] = pairs[0];
@@ -215,6 +221,7 @@ static size_t histogram_combine(Histo* out, size_t len, uint32_t* cluster_size, 
       continue;
     }
     uint32_t best_idx1 = pairs[0].idx1, best_idx2 = pairs[0].idx2;
+    if (hq_counters && cost_diff_threshold != 0.0f) hq_counters->forced_merges++;
     histo_add_histo(&out[best_idx1], &out[best_idx2], len);
     out[best_idx1].bit_cost_ = pairs[0].cost_combo;
     cluster_size[best_idx1] += cluster_size[best_idx2];
@@ -271,6 +278,7 @@ static void histogram_remap(const Histo* inp, size_t in_size, const uint32_t* cl
         best_out = clusters[j];
       }
     }
+    if (hq_counters && symbols[i] != best_out) hq_counters->remapped++;
     symbols[i] = best_out;
   }
   for (size_t i = 0; i < num_clusters; ++i) histo_clear(&out[clusters[i]], len);
@@ -283,8 +291,12 @@ static size_t histogram_reindex(Histo* out, size_t len, uint32_t* symbols, size_
   uint32_t* new_index = (uint32_t*)malloc((length ? length : 1) * sizeof(uint32_t));
   uint32_t next_index = 0;
   for (size_t i = 0; i < length; ++i) new_index[i] = kInvalidIndex;
+  uint32_t last_first = 0;
   for (size_t i = 0; i < length; ++i) {
     if (new_index[symbols[i]] == kInvalidIndex) {
+      /* a cluster that first appears behind one with a higher index: the new order is not the old one */
+      if (hq_counters && next_index != 0 && symbols[i] < last_first) hq_counters->reindex_permuted = 1;
+      last_first = symbols[i];
       new_index[symbols[i]] = next_index;
       ++next_index;
     }
@@ -304,9 +316,11 @@ static size_t histogram_reindex(Histo* out, size_t len, uint32_t* symbols, size_
   return next_index;
 }
 
-/* cluster.rs:353-465.  `out` has room for in_size histograms. */
+/* cluster.rs:353-465.  `out` has room for in_size histograms.  slot_cost (optional, in_size entries): the cached cost of every
+ * slot of `out` behind BrotliHistogramRemap, in front of the reindexing -- 3.402e+38 (HistogramClear) where a cluster survived,
+ * elsewhere what the slot cost when it was merged away. */
 static void cluster_histograms(const Histo* inp, size_t in_size, size_t max_histograms, size_t len, Histo* out,
-                               size_t* out_size, uint32_t* histogram_symbols) {
+                               size_t* out_size, uint32_t* histogram_symbols, float* slot_cost) {
   uint32_t* cluster_size = (uint32_t*)calloc(in_size ? in_size : 1, sizeof(uint32_t));
   uint32_t* clusters = (uint32_t*)calloc(in_size ? in_size : 1, sizeof(uint32_t));
   size_t num_clusters = 0;
@@ -338,6 +352,7 @@ static void cluster_histograms(const Histo* inp, size_t in_size, size_t max_hist
       free(pairs);
       pairs = np;
     }
+    if (hq_counters) hq_counters->clusters_before_final = num_clusters;
     num_clusters = histogram_combine(out, len, cluster_size, histogram_symbols, clusters, pairs, num_clusters, in_size,
                                      max_histograms, max_num_pairs, scratch);
   }
@@ -346,6 +361,8 @@ static void cluster_histograms(const Histo* inp, size_t in_size, size_t max_hist
   histogram_remap(inp, in_size, clusters, num_clusters, len, out, histogram_symbols, scratch);
   free(clusters);
   free(scratch);
+  if (slot_cost)
+    for (size_t i = 0; i < in_size; ++i) slot_cost[i] = out[i].bit_cost_;
   *out_size = histogram_reindex(out, len, histogram_symbols, in_size);
 }
 
@@ -560,6 +577,7 @@ static void cluster_blocks(const uint16_t* data, size_t length, size_t num_block
   }
   uint32_t* clusters = (uint32_t*)malloc((num_clusters ? num_clusters : 1) * sizeof(uint32_t));
   for (size_t i = 0; i < num_clusters; ++i) clusters[i] = (uint32_t)i;
+  if (hq_counters) hq_counters->clusters_before_final = num_clusters;
   size_t num_final_clusters = histogram_combine(all_histograms, len, cluster_size, histogram_symbols, clusters, pairs,
                                                 num_clusters, num_blocks, 256, max_num_pairs, scratch);
   free(pairs);
@@ -617,7 +635,7 @@ static void cluster_blocks(const uint16_t* data, size_t length, size_t num_block
 /* block_splitter.rs:690-838 */
 static void split_byte_vector(const uint16_t* data, size_t length, size_t literals_per_histogram, size_t max_histograms,
                               size_t sampling_stride_length, float block_switch_cost, int quality, size_t data_size,
-                              BlockSplit* split) {
+                              BlockSplit* split, uint8_t* phase1_ids, size_t* phase1_blocks) {
   size_t num_histograms = length / literals_per_histogram + 1;
   if (num_histograms > max_histograms) num_histograms = max_histograms;
   if (length == 0) {
@@ -654,6 +672,8 @@ static void split_byte_vector(const uint16_t* data, size_t length, size_t litera
     free(switch_signal);
     free(new_id);
     free(histograms);
+    if (phase1_ids) memcpy(phase1_ids, block_ids, length);
+    if (phase1_blocks) *phase1_blocks = num_blocks;
     cluster_blocks(data, length, num_blocks, block_ids, data_size, split);
     free(block_ids);
   }
@@ -674,14 +694,14 @@ static void split_block(const Command* cmds, size_t num_commands, const uint8_t*
       from_pos = (from_pos + cmds[i].insert_len_ + orc_command_copy_len(&cmds[i])) & mask;
     }
     split_byte_vector(literals, literals_count, kSymbolsPerLiteralHistogram, kMaxLiteralHistograms, kLiteralStrideLength,
-                      kLiteralBlockSwitchCost, quality, 256, literal_split);
+                      kLiteralBlockSwitchCost, quality, 256, literal_split, NULL, NULL);
     free(literals);
   }
   {
     uint16_t* codes = (uint16_t*)malloc((num_commands ? num_commands : 1) * sizeof(uint16_t));
     for (size_t i = 0; i < num_commands; ++i) codes[i] = cmds[i].cmd_prefix_;
     split_byte_vector(codes, num_commands, kSymbolsPerCommandHistogram, kMaxCommandHistograms, kCommandStrideLength,
-                      kCommandBlockSwitchCost, quality, 704, insert_and_copy_split);
+                      kCommandBlockSwitchCost, quality, 704, insert_and_copy_split, NULL, NULL);
     free(codes);
   }
   {
@@ -692,7 +712,7 @@ static void split_block(const Command* cmds, size_t num_commands, const uint8_t*
       if (orc_command_copy_len(cmd) != 0 && cmd->cmd_prefix_ >= 128) prefixes[j++] = cmd->dist_prefix_ & 0x03ff;
     }
     split_byte_vector(prefixes, j, kSymbolsPerDistanceHistogram, kMaxCommandHistograms, kCommandStrideLength,
-                      kDistanceBlockSwitchCost, quality, ORC_NUM_DISTANCE_HISTO_SYMBOLS, dist_split);
+                      kDistanceBlockSwitchCost, quality, ORC_NUM_DISTANCE_HISTO_SYMBOLS, dist_split, NULL, NULL);
     free(prefixes);
   }
 }
@@ -856,7 +876,7 @@ void orc_build_meta_block(const uint8_t* ringbuffer, size_t pos, size_t mask, En
   {
     Histo* out = (Histo*)malloc((literal_histograms_size ? literal_histograms_size : 1) * sizeof(Histo));
     cluster_histograms(literal_histograms, literal_histograms_size, kMaxNumberOfHistograms, 256, out,
-                       &mb->literal_histograms_size, mb->literal_context_map);
+                       &mb->literal_histograms_size, mb->literal_context_map, NULL);
     mb->literal_histograms = (uint32_t*)calloc(mb->literal_histograms_size * 256, sizeof(uint32_t));
     for (size_t i = 0; i < mb->literal_histograms_size; ++i)
       memcpy(mb->literal_histograms + i * 256, out[i].data_, 256 * sizeof(uint32_t));
@@ -877,7 +897,8 @@ void orc_build_meta_block(const uint8_t* ringbuffer, size_t pos, size_t mask, En
   {
     Histo* out = (Histo*)malloc((distance_histograms_size ? distance_histograms_size : 1) * sizeof(Histo));
     cluster_histograms(distance_histograms, mb->distance_context_map_size, kMaxNumberOfHistograms,
-                       ORC_NUM_DISTANCE_HISTO_SYMBOLS, out, &mb->distance_histograms_size, mb->distance_context_map);
+                       ORC_NUM_DISTANCE_HISTO_SYMBOLS, out, &mb->distance_histograms_size, mb->distance_context_map,
+                       NULL);
     mb->distance_histograms =
         (uint32_t*)calloc(mb->distance_histograms_size * ORC_NUM_DISTANCE_HISTO_SYMBOLS, sizeof(uint32_t));
     for (size_t i = 0; i < mb->distance_histograms_size; ++i)
@@ -886,4 +907,63 @@ void orc_build_meta_block(const uint8_t* ringbuffer, size_t pos, size_t mask, En
     free(out);
   }
   free(distance_histograms);
+}
+
+/* ------------------------------------------------------------------ seams for tests/test_hq_builder.py */
+/* SplitByteVector of one symbol vector with the constants BrotliSplitBlock gives its kind (0 literals, 1 commands, 2 distance
+ * prefixes).  phase1_ids (length entries) / phase1_blocks: the block ids and the block count behind the FindBlocks iterations,
+ * in front of ClusterBlocks (no symbols: 0 blocks; fewer than 128: one block of id 0, no search).  types / lengths: room for
+ * `length` blocks.  counters: optional. */
+void orc_split_byte_vector(int kind, const uint16_t* data, size_t length, int quality, uint8_t* phase1_ids,
+                           size_t* phase1_blocks, size_t* num_types, size_t* num_blocks, uint8_t* types, uint32_t* lengths,
+                           OrcHqCounters* counters) {
+  static const size_t per_histogram[3] = {544, 530, 544}, max_histograms[3] = {100, 50, 50}, stride[3] = {70, 40, 40};
+  static const size_t alphabet[3] = {256, 704, ORC_NUM_DISTANCE_HISTO_SYMBOLS};
+  const float switch_cost[3] = {kLiteralBlockSwitchCost, kCommandBlockSwitchCost, kDistanceBlockSwitchCost};
+  BlockSplit split;
+  memset(&split, 0, sizeof(split));
+  if (counters) memset(counters, 0, sizeof(*counters));
+  if (phase1_ids) memset(phase1_ids, 0, length);
+  *phase1_blocks = length == 0 ? 0 : 1;
+  hq_counters = counters;
+  split_byte_vector(data, length, per_histogram[kind], max_histograms[kind], stride[kind], switch_cost[kind], quality,
+                    alphabet[kind], &split, phase1_ids, phase1_blocks);
+  hq_counters = NULL;
+  *num_types = split.num_types;
+  *num_blocks = split.num_blocks;
+  for (size_t i = 0; i < split.num_blocks; ++i) {
+    types[i] = split.types[i];
+    lengths[i] = split.lengths[i];
+  }
+  free(split.types);
+  free(split.lengths);
+}
+
+/* BrotliClusterHistograms of in_size rows of `len` counters.  out_rows: room for in_size rows; out_total / out_cost: per output
+ * histogram; slot_cost: see cluster_histograms; symbols: in_size entries.  Returns the number of output histograms. */
+size_t orc_cluster_histograms(const uint32_t* rows, size_t in_size, size_t len, size_t max_histograms, uint32_t* out_rows,
+                              uint32_t* out_total, float* out_cost, float* slot_cost, uint32_t* symbols,
+                              OrcHqCounters* counters) {
+  Histo* inp = (Histo*)malloc((in_size ? in_size : 1) * sizeof(Histo));
+  Histo* out = (Histo*)malloc((in_size ? in_size : 1) * sizeof(Histo));
+  size_t out_size = 0;
+  for (size_t i = 0; i < in_size; ++i) {
+    histo_clear(&inp[i], len);
+    for (size_t k = 0; k < len; ++k) {
+      inp[i].data_[k] = rows[i * len + k];
+      inp[i].total_count_ += rows[i * len + k];
+    }
+  }
+  if (counters) memset(counters, 0, sizeof(*counters));
+  hq_counters = counters;
+  cluster_histograms(inp, in_size, max_histograms, len, out, &out_size, symbols, slot_cost);
+  hq_counters = NULL;
+  for (size_t i = 0; i < out_size; ++i) {
+    memcpy(out_rows + i * len, out[i].data_, len * sizeof(uint32_t));
+    out_total[i] = (uint32_t)out[i].total_count_;
+    out_cost[i] = out[i].bit_cost_;
+  }
+  free(inp);
+  free(out);
+  return out_size;
 }

@@ -208,6 +208,21 @@ void orc_build_meta_block(const uint8_t* ringbuffer, size_t pos, size_t mask, En
                           uint8_t prev_byte2, Command* cmds, size_t num_commands, int literal_context_mode,
                           MetaBlockSplit* mb);
 float orc_population_cost(const uint32_t* data, size_t data_size, size_t total_count); /* bit_cost.rs:76-211 */
+/* which corners of the clustering an input reaches (tests/test_hq_builder.py); filled by the two calls below when non-null */
+typedef struct {
+  uint64_t queue_full;            /* pairs refused, or pushed at the cost of the old head, because the pair queue was full */
+  uint64_t forced_merges;         /* merges made after cost_diff_threshold went to 1e38 (more clusters left than allowed) */
+  uint64_t clusters_before_final; /* clusters the batches left for the final BrotliHistogramCombine */
+  uint64_t ties;                  /* histogram_pair_is_less decided by idx2 - idx1 (equal cost_diff, two different pairs) */
+  uint64_t remapped;              /* inputs BrotliHistogramRemap moved to another cluster */
+  uint64_t reindex_permuted;      /* BrotliHistogramReindex changed the order of the clusters */
+} OrcHqCounters;
+void orc_split_byte_vector(int kind, const uint16_t* data, size_t length, int quality, uint8_t* phase1_ids,
+                           size_t* phase1_blocks, size_t* num_types, size_t* num_blocks, uint8_t* types, uint32_t* lengths,
+                           OrcHqCounters* counters);
+size_t orc_cluster_histograms(const uint32_t* rows, size_t in_size, size_t len, size_t max_histograms, uint32_t* out_rows,
+                              uint32_t* out_total, float* out_cost, float* slot_cost, uint32_t* symbols,
+                              OrcHqCounters* counters);
 void orc_init_distance_params(EncoderParams* params, uint32_t npostfix, uint32_t ndirect); /* metablock.rs:28-60 */
 void orc_prefix_encode_copy_distance(size_t distance_code, size_t num_direct_codes, uint64_t postfix_bits,
                                      uint16_t* code, uint32_t* extra_bits); /* command.rs:134-173 */

@@ -127,6 +127,27 @@ class DevBlocks {
   std::vector<void*> blocks_;
 };
 
+// Zero-filled device memory for the many small arrays of one call; everything goes when the owner does.
+struct DevMem {
+  DevBlocks blocks;
+  // small buffers are carved out of zero-filled arenas (one fill per arena instead of one tiny fill kernel each)
+  static constexpr size_t kArenaBytes = (size_t)4 << 20, kSmall = (size_t)256 << 10;
+  uint8_t* arena = nullptr;
+  size_t arena_used = kArenaBytes;
+  template <typename T>
+  T* alloc(size_t count) {
+    const size_t bytes = (count * sizeof(T) + 64 + 255) & ~(size_t)255;
+    if (bytes > kSmall) return blocks.zeroed<T>(bytes);
+    if (arena_used + bytes > kArenaBytes) {
+      arena = blocks.zeroed<uint8_t>(kArenaBytes);
+      arena_used = 0;
+    }
+    T* p = (T*)(arena + arena_used);
+    arena_used += bytes;
+    return p;
+  }
+};
+
 // Static read-only tables resident on the device (dictionary, dictionary hash, log tables ...).
 struct DeviceTables {
   const uint16_t* dict_hash;

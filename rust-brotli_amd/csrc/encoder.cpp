@@ -17,31 +17,12 @@
 #include "metablock_api.h"
 #include "metablock_device.h"
 #include "metablock_hq.h"
+#include "metablock_hq_jobs.h"
 #include "metablock_items.h"
 
 namespace brotli_mi355x {
 
 namespace {
-
-struct DevMem {
-  DevBlocks blocks;
-  // small buffers are carved out of zero-filled arenas (one fill per arena instead of one tiny fill kernel each)
-  static constexpr size_t kArenaBytes = (size_t)4 << 20, kSmall = (size_t)256 << 10;
-  uint8_t* arena = nullptr;
-  size_t arena_used = kArenaBytes;
-  template <typename T>
-  T* alloc(size_t count) {
-    const size_t bytes = (count * sizeof(T) + 64 + 255) & ~(size_t)255;
-    if (bytes > kSmall) return blocks.zeroed<T>(bytes);
-    if (arena_used + bytes > kArenaBytes) {
-      arena = blocks.zeroed<uint8_t>(kArenaBytes);
-      arena_used = 0;
-    }
-    T* p = (T*)(arena + arena_used);
-    arena_used += bytes;
-    return p;
-  }
-};
 
 // Bring-up checks of the meta-block kernels (BROTLI_MI355X_SELFTEST=1), in the manner of Lz77Stage::SelfTestSort.
 // The rows of k_context_stats against a recomputation from the text (encode.rs:1802-1927).
@@ -408,38 +389,14 @@ void BuildHqMetaBlocks(const EncoderParams& p, DevMem& mm, MbBuffers& B, std::ve
   B.hq_sym[2] = mm.alloc<uint16_t>((size_t)B.n_dists + 8);
   mb_hq_gather_symbols(B);
   // BrotliSplitBlock, block_splitter.rs:840-929: one job per (meta-block, kind)
-  static const uint32_t kSymbolsPerHistogram[3] = {544, 530, 544}, kMaxHistograms[3] = {100, 50, 50}, kStride[3] = {70, 40, 40};
-  static const float kSwitchCost[3] = {28.1f, 13.5f, 14.6f};
   uint8_t* block_ids[3] = {mm.alloc<uint8_t>((size_t)L + 8), mm.alloc<uint8_t>((size_t)K + 8), mm.alloc<uint8_t>((size_t)B.n_dists + 8)};
   std::vector<HqSplitJob> jobs;
   for (uint32_t m = 0; m < n_mb; ++m) {
     const MbDesc& d = descs[m];
     if (d.uncompressed) continue;
     const uint32_t base[3] = {d.lit_base, d.cmd_offset, d.dist_base};
-    for (uint32_t k = 0; k < 3; ++k) {
-      HqSplitJob j;
-      memset(&j, 0, sizeof(j));
-      j.m = m;
-      j.kind = k;
-      j.length = d.n_symbols[k];
-      j.alphabet = kRowLen[k];
-      j.num_histograms = std::min(j.length / kSymbolsPerHistogram[k] + 1, kMaxHistograms[k]);
-      j.stride = kStride[k];
-      j.iters = p.quality <= 11 ? 3 : 10;  // block_splitter.rs:794
-      j.block_switch_cost = kSwitchCost[k];
-      j.data = B.hq_sym[k] + base[k];
-      j.block_ids = block_ids[k] + base[k];
-      if (j.length >= 128) {
-        const size_t nh = j.num_histograms, bitmaplen = (nh + 7) >> 3;
-        j.histo_data = mm.alloc<uint32_t>((nh + 1) * j.alphabet);
-        j.histo_total = mm.alloc<uint32_t>(nh + 1);
-        j.insert_cost = mm.alloc<float>((size_t)j.alphabet * nh + nh + 8);
-        j.cost = mm.alloc<float>(bitmaplen * 8 + 8);
-        j.switch_signal = mm.alloc<uint8_t>((size_t)j.length * bitmaplen + 8);
-        j.new_id = mm.alloc<uint16_t>(nh + 8);
-      }
-      jobs.push_back(j);
-    }
+    for (uint32_t k = 0; k < 3; ++k)
+      jobs.push_back(HqMakeSplitJob(mm, m, k, d.n_symbols[k], p.quality, B.hq_sym[k] + base[k], block_ids[k] + base[k]));
   }
   HqSplitJob* jobs_dev = mm.alloc<HqSplitJob>(jobs.size() + 1);
   dev_h2d(jobs_dev, jobs.data(), jobs.size() * sizeof(HqSplitJob));
@@ -454,45 +411,14 @@ void BuildHqMetaBlocks(const EncoderParams& p, DevMem& mm, MbBuffers& B, std::ve
       descs[m].max_histos[k] = 256;
       histo_total[k] += 256;
     }
-  {
-    // ClusterBlocks keeps one histogram per block FindBlocks found, twice (the batches' rows and the gathered clusters);
-    // a pathological input (a switch every few symbols over a 16 MiB meta-block) would ask for more than the device
-    // has.  Refuse with a message instead of dying in an allocation half-way through.
-    uint64_t need = 0;
-    for (const HqSplitJob& j : jobs)
-      if (j.length >= 128) need += (uint64_t)(j.num_blocks + 2) * (2ull * j.alphabet * 4 + 64ull * sizeof(HqPair) + 64);
-    if (need > (96ull << 30))
-      throw std::runtime_error("brotli_mi355x: quality 9.5: clustering " + std::to_string(need >> 30) +
-                               " GiB of block histograms is more than this build sets aside; feed the stream in smaller pieces");
-  }
+  HqCheckClusterRoom(jobs);
   for (HqSplitJob& j : jobs) {
     MbDesc& d = descs[j.m];
     const uint32_t nb = j.num_blocks;
     d.block_base[j.kind] = block_total[j.kind];
     d.max_blocks[j.kind] = nb + 1;
     block_total[j.kind] += nb + 2;
-    if (j.length >= 128) {
-      const size_t n = nb;
-      uint64_t max_pairs = std::min<uint64_t>(64ull * n, (uint64_t)(n / 2) * n);
-      max_pairs = std::max<uint64_t>(max_pairs, kHqBatchPairs);
-      j.histogram_symbols = mm.alloc<uint32_t>(n + 8);
-      j.block_lengths = mm.alloc<uint32_t>(n + 8);
-      j.block_pos = mm.alloc<uint32_t>(n + 8);
-      j.batch_data = mm.alloc<uint32_t>((n + 2) * j.alphabet);
-      j.batch_total = mm.alloc<uint32_t>(n + 8);
-      j.batch_cost = mm.alloc<float>(n + 8);
-      j.batch_sizes = mm.alloc<uint32_t>(n + 8);
-      j.batch_clusters = mm.alloc<uint32_t>(n + 8);
-      j.batch_symbols = mm.alloc<uint32_t>(n + 8);
-      j.batch_count = mm.alloc<uint32_t>(n / kHqBatch + 8);
-      j.all_data = mm.alloc<uint32_t>((n + 2) * j.alphabet);
-      j.all_total = mm.alloc<uint32_t>(n + 2);
-      j.all_cost = mm.alloc<float>(n + 2);
-      j.cluster_size = mm.alloc<uint32_t>(n + 8);
-      j.clusters = mm.alloc<uint32_t>(n + 2 * kHqBatch + 8);  // (also the per-batch sizes / cluster lists)
-      j.new_index = mm.alloc<uint32_t>(n + 2 * kHqBatch + 8);
-      j.pairs = mm.alloc<HqPair>(max_pairs + 2);
-    }
+    HqAllocClusterBlocks(mm, j);
   }
   for (uint32_t k = 0; k < 3; ++k) {
     B.n_granules[k] = 0;
@@ -512,10 +438,7 @@ void BuildHqMetaBlocks(const EncoderParams& p, DevMem& mm, MbBuffers& B, std::ve
   B.mb_out_bit = mm.alloc<uint64_t>(n_mb + 1);
   dev_h2d(B.descs, descs.data(), n_mb * sizeof(MbDesc));
   dev_h2d(jobs_dev, jobs.data(), jobs.size() * sizeof(HqSplitJob));
-  std::vector<HqBatchRef> batch_refs;
-  for (uint32_t ji = 0; ji < jobs.size(); ++ji)
-    if (jobs[ji].length >= 128)
-      for (uint32_t b = 0; b * kHqBatch < jobs[ji].num_blocks; ++b) batch_refs.push_back({ji, b});
+  const std::vector<HqBatchRef> batch_refs = HqSplitBatches(jobs);
   HqBatchRef* batch_refs_dev = mm.alloc<HqBatchRef>(batch_refs.size() + 1);
   dev_h2d(batch_refs_dev, batch_refs.data(), batch_refs.size() * sizeof(HqBatchRef));
   mb_hq_cluster_blocks(B, jobs_dev, (uint32_t)jobs.size(), batch_refs_dev, (uint32_t)batch_refs.size());
@@ -545,29 +468,11 @@ void BuildHqMetaBlocks(const EncoderParams& p, DevMem& mm, MbBuffers& B, std::ve
     const MbDesc& d = descs[m];
     if (d.uncompressed) continue;
     for (uint32_t w = 0; w < 2; ++w) {
-      HqClusterJob j;
-      memset(&j, 0, sizeof(j));
-      j.m = m;
-      j.kind = w == 0 ? kSplitLiteral : kSplitDistance;
-      const uint32_t nt = results[m].num_types[j.kind];
-      j.in_size = w == 0 ? (d.hq_no_context ? nt : nt << 6) : nt << 2;
-      j.len = kRowLen[j.kind];
-      j.expand64 = (w == 0 && d.hq_no_context) ? 1 : 0;
-      j.in_data = B.hq_ctx_histo[w] + (size_t)d.hq_ctx_row_base[w] * j.len;
-      const size_t n = j.in_size, re = std::min<size_t>(n, 256);
-      j.in_total = mm.alloc<uint32_t>(n + 8);
-      j.out_data = mm.alloc<uint32_t>((n + 2) * j.len);
-      j.out_total = mm.alloc<uint32_t>(n + 2);
-      j.out_cost = mm.alloc<float>(n + 2);
-      j.cluster_size = mm.alloc<uint32_t>(n + 8);
-      j.clusters = mm.alloc<uint32_t>(n + 8);
-      j.symbols = mm.alloc<uint32_t>(n + 8);
-      j.new_index = mm.alloc<uint32_t>(n + 8);
-      j.batch_count = mm.alloc<uint32_t>(n / kHqBatch + 8);
-      j.reindex_data = mm.alloc<uint32_t>(re * j.len + 8);
-      j.reindex_total = mm.alloc<uint32_t>(re + 8);
-      j.reindex_cost = mm.alloc<float>(re + 8);
-      j.pairs = mm.alloc<HqPair>(std::max<size_t>(kHqBatchPairs, 64 * n) + 2);
+      const uint32_t kind = w == 0 ? kSplitLiteral : kSplitDistance;
+      const uint32_t nt = results[m].num_types[kind];
+      const uint32_t in_size = w == 0 ? (d.hq_no_context ? nt : nt << 6) : nt << 2;
+      const HqClusterJob j = HqMakeClusterJob(mm, m, kind, in_size, (w == 0 && d.hq_no_context) ? 1 : 0,
+                                              B.hq_ctx_histo[w] + (size_t)d.hq_ctx_row_base[w] * kRowLen[kind]);
       cjobs.push_back(j);
     }
   }
@@ -575,9 +480,7 @@ void BuildHqMetaBlocks(const EncoderParams& p, DevMem& mm, MbBuffers& B, std::ve
   mb_hq_context_histograms(B);
   HqClusterJob* cjobs_dev = mm.alloc<HqClusterJob>(cjobs.size() + 1);
   dev_h2d(cjobs_dev, cjobs.data(), cjobs.size() * sizeof(HqClusterJob));
-  std::vector<HqBatchRef> cbatch_refs;
-  for (uint32_t ji = 0; ji < cjobs.size(); ++ji)
-    for (uint32_t b = 0; b * kHqBatch < cjobs[ji].in_size; ++b) cbatch_refs.push_back({ji, b});
+  const std::vector<HqBatchRef> cbatch_refs = HqClusterBatches(cjobs);
   HqBatchRef* cbatch_refs_dev = mm.alloc<HqBatchRef>(cbatch_refs.size() + 1);
   dev_h2d(cbatch_refs_dev, cbatch_refs.data(), cbatch_refs.size() * sizeof(HqBatchRef));
   mb_hq_cluster_histograms(B, cjobs_dev, (uint32_t)cjobs.size(), cbatch_refs_dev, (uint32_t)cbatch_refs.size());

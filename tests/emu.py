@@ -124,3 +124,89 @@ def build_codes(L, kind, num_distance_symbols, mode, histograms):
     if r != 0:
         raise RuntimeError("brotli_mi355x_debug_build_codes returned %d" % r)
     return h, depth, bits, words.view(np.uint8).reshape(n, TREE_BITS_WORDS * 8), nbits
+
+
+def hq_split_raw(L, kind, n_jobs, lengths, symbols):
+    """brotli_mi355x_debug_hq_split as it is: returns (status, phase1_blocks, phase1_ids, num_types, num_blocks, types, block_lengths)."""
+    import numpy as np
+    L.brotli_mi355x_debug_hq_split.restype = ctypes.c_int
+    L.brotli_mi355x_debug_hq_split.argtypes = [ctypes.c_uint32] * 2 + [ctypes.c_void_p] * 8
+    lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+    symbols = np.ascontiguousarray(symbols, dtype=np.uint16)
+    total = max(1, len(symbols))
+    n = max(1, len(lengths))
+    p1n = np.full(n, 0xeeeeeeee, dtype=np.uint32)
+    p1 = np.full(total, 0xee, dtype=np.uint8)
+    nt = np.full(n, 0xeeeeeeee, dtype=np.uint32)
+    nb = np.full(n, 0xeeeeeeee, dtype=np.uint32)
+    types = np.full(total, 0xee, dtype=np.uint8)
+    bl = np.full(total, 0xeeeeeeee, dtype=np.uint32)
+    r = L.brotli_mi355x_debug_hq_split(kind, n_jobs, lengths.ctypes.data, symbols.ctypes.data, p1n.ctypes.data, p1.ctypes.data,
+                                       nt.ctypes.data, nb.ctypes.data, types.ctypes.data, bl.ctypes.data)
+    return r, p1n, p1, nt, nb, types, bl
+
+
+def hq_split(L, kind, vectors):
+    """`vectors` (sequences of symbols of one kind: 0 literals, 1 commands, 2 distance prefixes) through FindBlocks + ClusterBlocks of
+    the library (k_hq_* on the device, the scalar twins in the emulation), side by side in one launch.  Returns one dict per vector:
+    phase1_blocks, phase1_ids (numpy uint8, after mb_hq_find_blocks), num_types, num_blocks, types, lengths (the final split)."""
+    import numpy as np
+    vectors = [np.asarray(v, dtype=np.uint16) for v in vectors]
+    lengths = np.array([len(v) for v in vectors], dtype=np.uint32)
+    symbols = np.concatenate(vectors) if vectors else np.zeros(0, dtype=np.uint16)
+    r, p1n, p1, nt, nb, types, bl = hq_split_raw(L, kind, len(vectors), lengths, symbols)
+    if r != 0:
+        raise RuntimeError("brotli_mi355x_debug_hq_split returned %d" % r)
+    out, at = [], 0
+    for i, v in enumerate(vectors):
+        out.append(dict(phase1_blocks=int(p1n[i]), phase1_ids=p1[at:at + len(v)].copy(), num_types=int(nt[i]), num_blocks=int(nb[i]),
+                        types=types[at:at + int(nb[i])].copy(), lengths=bl[at:at + int(nb[i])].copy()))
+        at += len(v)
+    return out
+
+
+def hq_cluster_raw(L, kind, n_jobs, in_sizes, rows, expand64):
+    """brotli_mi355x_debug_hq_cluster as it is: returns (status, out_count, out_rows, out_total, out_cost, slot_cost, map)."""
+    import numpy as np
+    L.brotli_mi355x_debug_hq_cluster.restype = ctypes.c_int
+    L.brotli_mi355x_debug_hq_cluster.argtypes = [ctypes.c_uint32] * 2 + [ctypes.c_void_p] * 9
+    in_sizes = np.ascontiguousarray(in_sizes, dtype=np.uint32)
+    rows = np.ascontiguousarray(rows, dtype=np.uint32)
+    expand64 = np.ascontiguousarray(expand64, dtype=np.uint32)
+    total = max(1, rows.shape[0] if rows.ndim == 2 else 0)
+    count = np.full(max(1, len(in_sizes)), 0xeeeeeeee, dtype=np.uint32)
+    out_rows = np.full((total, ROW_LEN[kind] if kind < 3 else 1), 0xeeeeeeee, dtype=np.uint32)
+    out_total = np.full(total, 0xeeeeeeee, dtype=np.uint32)
+    out_cost = np.full(total, 0xeeeeeeee, dtype=np.uint32)
+    slot_cost = np.full(total, 0xeeeeeeee, dtype=np.uint32)
+    cmap = np.full(total * 64, 0xeeeeeeee, dtype=np.uint32)
+    r = L.brotli_mi355x_debug_hq_cluster(kind, n_jobs, in_sizes.ctypes.data, rows.ctypes.data, expand64.ctypes.data, count.ctypes.data,
+                                         out_rows.ctypes.data, out_total.ctypes.data, out_cost.ctypes.data, slot_cost.ctypes.data,
+                                         cmap.ctypes.data)
+    return r, count, out_rows, out_total, out_cost, slot_cost, cmap
+
+
+def hq_cluster(L, kind, jobs, expand64=None):
+    """`jobs` (numpy uint32 arrays of in_size x ROW_LEN[kind], kind 0 literal or 2 distance) through BrotliClusterHistograms of the
+    library, side by side in one launch.  Returns one dict per job: rows (out_count x len), totals, costs (uint32 bit patterns of the
+    output rows' cached costs), slot_costs (bit patterns, one per input slot, behind the remap) and map (in_size entries, 64 x in_size
+    where expand64[i] is set)."""
+    import numpy as np
+    jobs = [np.ascontiguousarray(j, dtype=np.uint32) for j in jobs]
+    for j in jobs:
+        assert j.ndim == 2 and j.shape[1] == ROW_LEN[kind], j.shape
+    if expand64 is None:
+        expand64 = [0] * len(jobs)
+    in_sizes = [j.shape[0] for j in jobs]
+    r, count, out_rows, out_total, out_cost, slot_cost, cmap = hq_cluster_raw(L, kind, len(jobs), in_sizes, np.concatenate(jobs),
+                                                                              expand64)
+    if r != 0:
+        raise RuntimeError("brotli_mi355x_debug_hq_cluster returned %d" % r)
+    out, at, mat = [], 0, 0
+    for i, j in enumerate(jobs):
+        n, msz = int(count[i]), in_sizes[i] * (64 if expand64[i] else 1)
+        out.append(dict(rows=out_rows[at:at + n].copy(), totals=out_total[at:at + n].copy(), costs=out_cost[at:at + n].copy(),
+                        slot_costs=slot_cost[at:at + in_sizes[i]].copy(), map=cmap[mat:mat + msz].copy()))
+        at += in_sizes[i]
+        mat += msz
+    return out

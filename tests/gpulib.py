@@ -16,3 +16,9 @@ def lib():
             raise RuntimeError("product library not built: run `python -c 'import __graft_entry__ as g; g.build()'`")
         _lib = emu.bind_trace(ctypes.CDLL(LIB_PATH))
     return _lib
+
+
+# the introspection seams are the same flat entry points in both libraries: the bindings of emu.py serve lib() as well
+build_codes = emu.build_codes
+hq_split = emu.hq_split
+hq_cluster = emu.hq_cluster

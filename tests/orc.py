@@ -355,3 +355,65 @@ def build_code(hist_len, alphabet_size, opt_len, optimize, histogram, row_len):
     L.orc_build_code(hist_len, alphabet_size, opt_len, 1 if optimize else 0, h.ctypes.data, depth.ctypes.data, bits.ctypes.data,
                      storage.ctypes.data, ctypes.byref(ix))
     return h, depth, bits, storage, ix.value
+
+
+class OrcHqCounters(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in ("queue_full", "forced_merges", "clusters_before_final", "ties", "remapped",
+                                               "reindex_permuted")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+def population_cost(row):
+    """BrotliPopulationCost of one histogram row (numpy uint32), as the uint32 bit pattern of the f32"""
+    import numpy as np
+    L = lib()
+    L.orc_population_cost.restype = ctypes.c_float
+    L.orc_population_cost.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t]
+    row = np.ascontiguousarray(row, dtype=np.uint32)
+    c = np.array([L.orc_population_cost(row.ctypes.data, len(row), int(row.sum(dtype=np.uint64)))], dtype=np.float32)
+    return int(c.view(np.uint32)[0])
+
+
+def split_byte_vector(kind, symbols):
+    """SplitByteVector of the quality 10 / 11 block splitter on one symbol vector (kind 0 literals, 1 commands, 2 distance prefixes).
+    Returns a dict like emu.hq_split's plus `counters`."""
+    import numpy as np
+    L = lib()
+    L.orc_split_byte_vector.restype = None
+    L.orc_split_byte_vector.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p,
+                                        ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t),
+                                        ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(OrcHqCounters)]
+    v = np.ascontiguousarray(symbols, dtype=np.uint16)
+    n = max(1, len(v))
+    ids = np.zeros(n, dtype=np.uint8)
+    types = np.zeros(n, dtype=np.uint8)
+    lengths = np.zeros(n, dtype=np.uint32)
+    p1n, nt, nb = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    cnt = OrcHqCounters()
+    L.orc_split_byte_vector(kind, v.ctypes.data, len(v), 11, ids.ctypes.data, ctypes.byref(p1n), ctypes.byref(nt), ctypes.byref(nb),
+                            types.ctypes.data, lengths.ctypes.data, ctypes.byref(cnt))
+    return dict(phase1_blocks=p1n.value, phase1_ids=ids[:len(v)], num_types=nt.value, num_blocks=nb.value, types=types[:nb.value],
+                lengths=lengths[:nb.value], counters=cnt.as_dict())
+
+
+def cluster_histograms(rows, max_histograms=256):
+    """BrotliClusterHistograms of the rows (numpy uint32, in_size x len).  Returns a dict like emu.hq_cluster's plus `counters`."""
+    import numpy as np
+    L = lib()
+    L.orc_cluster_histograms.restype = ctypes.c_size_t
+    L.orc_cluster_histograms.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t] + [ctypes.c_void_p] * 5 + [
+        ctypes.POINTER(OrcHqCounters)]
+    rows = np.ascontiguousarray(rows, dtype=np.uint32)
+    n, ln = rows.shape
+    out_rows = np.zeros((n, ln), dtype=np.uint32)
+    totals = np.zeros(n, dtype=np.uint32)
+    costs = np.zeros(n, dtype=np.float32)
+    slots = np.zeros(n, dtype=np.float32)
+    symbols = np.zeros(n, dtype=np.uint32)
+    cnt = OrcHqCounters()
+    k = L.orc_cluster_histograms(rows.ctypes.data, n, ln, max_histograms, out_rows.ctypes.data, totals.ctypes.data, costs.ctypes.data,
+                                 slots.ctypes.data, symbols.ctypes.data, ctypes.byref(cnt))
+    return dict(rows=out_rows[:k], totals=totals[:k], costs=costs[:k].view(np.uint32), slot_costs=slots.view(np.uint32), map=symbols,
+                counters=cnt.as_dict())

@@ -9,9 +9,11 @@ roundtrip_helper(.., 10, 28, q9_5) == 130 036 bytes and (.., 11, 22, q9_5) == 12
 (oracle/orc_hq_metablock.c, itself pinned on those sizes and on 47 488 / 46 493).
 
 CPU: the emulation build (the same item code compiled for the host).  -m gpu: the product library."""
+import functools
 import glob
 import os
 
+import numpy as np
 import pytest
 
 import orc
@@ -37,6 +39,24 @@ def _kat(lib):
         assert orc.decompress(got, len(d)) == d
 
 
+@functools.lru_cache(maxsize=None)
+def _segmented_alphabets(segments=512, segment_bytes=600):
+    """300 KiB of random bytes, every 600-byte segment drawn from its own 16-symbol alphabet: LZ77 leaves it as literals (it is not
+    stored raw: four bits a byte), and the literal splitter finds hundreds of blocks in one meta-block -- more than 64 clusters through
+    ClusterBlocks, the header writer and the emitters.  The block count is read off the ORACLE's stream."""
+    import brotli_parse
+    rng = np.random.default_rng(5)
+    data = np.concatenate([rng.choice(256, 16, replace=False).astype(np.uint8)[rng.integers(0, 16, segment_bytes)]
+                           for _ in range(segments)]).tobytes()
+    params = P + [(W, 22)]
+    stream, _ = orc.stream_compress(data, params)
+    mbs = [mb for mb in brotli_parse.parse(stream)["metablocks"] if "mlen" in mb]
+    assert mbs and not any(mb["uncompressed"] for mb in mbs) and len(stream) < len(data) * 3 // 4
+    assert max(len(mb["splits"][0]) for mb in mbs) > 64, [len(mb["splits"][0]) for mb in mbs]
+    assert sum(len(mb["cmds"]) for mb in mbs) < len(data) // 50  # left as literals
+    return data, params
+
+
 def _cases(small):
     a = synth.alice()
     yield "alice w22 hint", a, P + [(W, 22), (SH, len(a))], b""
@@ -52,6 +72,7 @@ def _cases(small):
         yield os.path.basename(f), d, P + [(W, 22), (SH, len(d))], b""
     yield "random 300k (stored raw)", synth.random_bytes(300000), P + [(W, 22)], b""
     yield "zeros 300k", bytes(300000), P + [(W, 22)], b""
+    yield ("segment alphabets 300 KiB (literal split of more than 64 blocks)",) + _segmented_alphabets() + (b"",)
     yield "stretches 1 MiB", synth.stretches(1 << 20, 9), P + [(W, 22)], b""
     yield "Silesia-like 2 MiB", synth.silesia_like(2 << 20, min_segment=1 << 18, max_segment=1 << 20), P + [(W, 22)], b""
     yield "mixed %s" % ("1 MiB" if small else "3 MiB"), synth.mixed((1 if small else 3) << 20), P + [(W, 22)], b""
