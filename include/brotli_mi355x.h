@@ -204,12 +204,13 @@ BROTLI_BOOL BrotliMi355xCompressDevice(int quality, int lgwin, BrotliEncoderMode
      qualities 5 .. 8:  the items of at most one input block (65 536 bytes) at lgwin 17 .. 24 -- one parse chain and one
                         meta-block each, thousands of them in flight, one upload and one download per group of up to 4096 items.
    Every other item -- qualities 2 .. 4 (but see BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS of BrotliMi355xCompressBatchEx) and
-   9 .. 11 (but see BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS there), lgwin <= 16 or > 24, items longer than one input block -- is accepted and
+   9 .. 11 (but see BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS and BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS there), lgwin <= 16 or > 24, items longer than one input block -- is accepted and
    runs by itself through the one-shot path on the calling thread, in the same call and in the caller's order: the same bytes,
    no gain in speed.  Both kinds may be mixed in one call; BrotliMi355xLastBatchInfo tells how a call was taken.
    Environment (read once per process): BROTLI_MI355X_BATCH_GROUP_ITEMS / BROTLI_MI355X_BATCH_GROUP_BYTES bound a group of
    qualities 5 .. 8 (4096 items, 64 MiB), BROTLI_MI355X_BATCH_TABLES the number of hash tables, i.e. of chains in flight
-   (default: as many as stay resident, within 8 GiB; a table is 1 MiB at quality 5 and 16 MiB at quality 8). */
+   (default: as many as stay resident, within 8 GiB; a table is 1 MiB at quality 5 and 16 MiB at quality 8, 32 MiB at qualities
+   9 and 10 under BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS). */
 int32_t BrotliMi355xCompressBatch(int quality, int lgwin, BrotliEncoderMode mode, size_t count, const uint8_t* const* inputs,
                                   const size_t* input_sizes, uint8_t* const* outputs,
                                   size_t* output_sizes /* in: capacity, out: size */, int32_t* item_results /* may be NULL */);
@@ -282,7 +283,8 @@ int32_t BrotliMi355xCompressBatchWithDictionary(int quality, int lgwin, BrotliEn
    their own, of at most 1024 items: what the quality >= 10 meta-block builder sets aside per item; as many tables as stay
    resident, 256, within 8 GiB, a table sized by its group's largest item), and leaves one meta-block.  Every other item goes as in
    the plain call.  The bit changes nothing at qualities 0 .. 10.  Quality 10 is not taken: BrotliEncoderCompress runs it at
-   quality 9, as the reference's one-shot entry does, so the bytes an item of quality 10 is owed are not those of a Zopfli walk.  Such
+   quality 9, as the reference's one-shot entry does, so the bytes an item of quality 10 is owed are not those of a Zopfli walk
+   (BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS takes such items).  Such
    items count in info[1], their groups in info[4]; nothing is redone, info[6] and info[7] stay 0 for them.  An item on which the
    reference encoder itself panics fails alone with "the reference encoder fails on this input", as under
    BrotliMi355xCompressBatchWithDictionary.  When to set it: with hundreds of small static files in a call (pre-compression at
@@ -292,18 +294,36 @@ int32_t BrotliMi355xCompressBatchWithDictionary(int quality, int lgwin, BrotliEn
    When not: for one or two items the one-shot path, which finds a lone item's matches side by side, is as fast or faster; and a
    handful of small items is done sooner on one CPU core than on the device either way (see INTEGRATION.md for measured
    figures).  Not combined with a shared dictionary.
-   The bits may be combined.  The values 2 and 8 are reserved: they name no route and fail the call like any unknown bit, as do 64
-   and above. */
+   BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS: item i still gets exactly what BrotliEncoderCompress gives.  In addition, an item of at
+   most one input block at quality 9 or 10 and lgwin 17 .. 24 -- that is 1 <= input_sizes[i] <= 131 072 at lgwin 17 and
+   <= 262 144 from lgwin 18 on -- runs on the device as ONE chain on a private H9 hash table (32 768 keys with rings 256 deep:
+   64 KiB of counters and 32 MiB of buckets), side by side with the other such items of the call (groups of their own, under the
+   same environment limits; 255 tables by default, what 8 GiB hold), and leaves one meta-block.  Quality 10 goes as quality 9:
+   BrotliEncoderCompress runs it so, as the reference's one-shot entry does.  Every other item goes as in the plain call; at
+   lgwin <= 16 the reference selects another hasher and the items stay one by one.  The bit changes nothing at qualities 0 .. 8
+   and 11, so with BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS beside it quality 10 goes this way and quality 11 the Zopfli way.  Such
+   items count in info[1], their groups in info[4]; nothing is redone and no item fails like the reference, info[5] .. info[7]
+   stay 0 for them.  When to set it: with dozens to thousands of small items in a call at the strongest greedy
+   level.  A chain is one wavefront bound by its own dependent loads -- about 1.07 us per byte of text, 6 ms for 4 KiB, 70 ms for
+   64 KiB, 258 ms for 256 KiB -- and takes a lone chain's time however many run beside it, so the call lasts as long as its
+   largest item's chain times the items per table; the one-by-one path takes about 2 ms per item whatever its size.  Measured:
+   4096 items of 4 KiB in 0.10 s against 6.8 s one by one, 1024 of 16 KiB in 0.10 s against 1.8 s, 256 of 64 KiB in 0.14 s against
+   0.47 s, 16 of 4 KiB in 6.7 ms against 26 ms.  When not: 64 items of 256 KiB of text LOSE (258 ms against 142 ms one by one, 74 ms
+   from four threads), and so does a call of one or two items of any size; by the same figures the break-even is near 40 items of
+   64 KiB and 120 of 256 KiB (see INTEGRATION.md for measured figures).  Not combined with a shared dictionary.
+   The bits may be combined.  The values 2, 8 and 64 are reserved: they name no route and fail the call like any unknown bit, as
+   do 256 and above. */
 #define BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS 1u
 #define BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS 4u /* (2u is reserved and stays an unknown route) */
 #define BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS 16u /* (8u stays an unknown route, like 2u) */
 #define BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS 32u
+#define BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS 128u /* (64u stays an unknown route, like 2u and 8u) */
 int32_t BrotliMi355xCompressBatchEx(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t count,
                                     const uint8_t* const* inputs, const size_t* input_sizes, uint8_t* const* outputs,
                                     size_t* output_sizes /* in: capacity, out: size */, int32_t* item_results /* may be NULL */);
 /* BrotliMi355xCompressBatchWithDictionary with routes the caller opts into.  routes == 0 is that call in every respect.  The only
    route this call knows is BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS; any other bit -- the other routes of
-   BrotliMi355xCompressBatchEx and the reserved values 2 and 8 included -- fails the whole call as an unknown route fails that one
+   BrotliMi355xCompressBatchEx and the reserved values 2, 8 and 64 included -- fails the whole call as an unknown route fails that one
    (returns 0, every size 0, BrotliMi355xLastError says so, only info[0] of BrotliMi355xLastBatchInfo is set).
    BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS: item i is still exactly the stream of BrotliEncoderSetCustomDictionary + one
    BrotliEncoderCompressStream(BROTLI_OPERATION_FINISH), by the rules above -- in bytes, size, success or failure.  In addition
@@ -338,7 +358,8 @@ int32_t BrotliMi355xCompressBatchWithDictionaryEx(int quality, int lgwin, Brotli
    [6] items that began side by side and were redone one by one (counted in [2], not in [1]), [7] of the items counted in [1],
    those longer than one input block; [6] and [7] are zero unless BrotliMi355xCompressBatchEx was called with
    BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS or BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS (the items of
-   BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS and BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS count in [1] and [4] only).  After a call that failed as a whole only info[0] is set. */
+   BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS, BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS and BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS count in
+   [1] and [4] only).  After a call that failed as a whole only info[0] is set. */
 void BrotliMi355xLastBatchInfo(uint64_t info[8]);
 /* Human-readable description of the device backing the library ("hip:gfx950 (...)"). */
 const char* BrotliMi355xDeviceName(void);

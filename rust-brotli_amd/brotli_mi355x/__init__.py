@@ -183,9 +183,10 @@ class Library(object):
     BATCH_ROUTE_QUICK_ITEMS = 4  # BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS (2 is reserved)
     BATCH_ROUTE_QUICK_LONG_ITEMS = 16  # BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS (8 is reserved)
     BATCH_ROUTE_ZOPFLI_ITEMS = 32  # BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS
+    BATCH_ROUTE_Q9_ITEMS = 128  # BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS (64 is reserved)
 
     def compress_batch(self, items, quality=0, lgwin=22, mode=0, dictionary=None, long_items=False, quick_items=False, quick_long_items=False,
-                       zopfli_items=False):
+                       zopfli_items=False, q9_items=False):
         """BrotliMi355xCompressBatch: every item becomes a stream of its own, the same bytes as compress(item, quality, lgwin,
         mode), in one call.  Side by side on the device (the call for many small payloads): every item at qualities 0 and 1, and
         at qualities 5 to 8 the items of at most 65 536 bytes at lgwin 17 to 24.  Everything else runs item by item in the same
@@ -213,11 +214,22 @@ class Library(object):
 
         zopfli_items=True: BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS -- at quality 11 and lgwin 10 to
         24 the items of at most 65 536 bytes run side by side, one wavefront each that walks the item the reference's way on H10
-        trees of its own (the same bytes).  Without it this quality runs item by item; quality 10 still does (compress() runs it
+        trees of its own (the same bytes).  Without it this quality runs item by item; quality 10 is not taken by it (compress() runs it
         at quality 9, as the reference's one-shot entry does).  A walk takes a lone walk's time however many run beside it (about
         37 us per byte): it pays with hundreds of small items in a call (pre-compressing static files: 1024 items of 4 KiB in
         0.6 s against 89 s); for one or two items the one-by-one path is as fast or faster.  May be combined with the other
-        flags, not with a dictionary."""
+        flags, not with a dictionary.
+
+        q9_items=True: BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS -- at qualities 9 and 10 and lgwin 17 to
+        24 the items of at most one input block (131 072 bytes at lgwin 17, 262 144 from lgwin 18 on) run side by side, one chain
+        each on a private H9 hash table of 32 MiB (the same bytes; quality 10 is quality 9 for compress(), as for the reference's
+        one-shot entry).  Without it these qualities run item by item.  A chain takes a lone chain's time however many run beside it (about
+        1 us per byte of text): it pays with dozens to thousands of small items in a call (4096 items of 4 KiB in 0.10 s against
+        6.8 s, 16 of them in 6.7 ms against 26 ms); 64 items of 256 KiB of text lose (258 ms against 142 ms), as do one or two
+        items of any size.  May be combined with the other flags (with
+        zopfli_items quality 10 goes this way and quality 11 the Zopfli way), not with a dictionary."""
+        if q9_items and dictionary is not None:
+            raise ValueError("q9_items and dictionary cannot be combined: BrotliMi355xCompressBatchWithDictionary has no routes")
         if zopfli_items and dictionary is not None:
             raise ValueError("zopfli_items and dictionary cannot be combined: BrotliMi355xCompressBatchWithDictionary has no routes")
         if quick_long_items and dictionary is not None:
@@ -230,6 +242,7 @@ class Library(object):
         routes = (self.BATCH_ROUTE_LONG_ITEMS if long_items else 0) | (self.BATCH_ROUTE_QUICK_ITEMS if quick_items else 0)
         routes |= self.BATCH_ROUTE_QUICK_LONG_ITEMS if quick_long_items else 0
         routes |= self.BATCH_ROUTE_ZOPFLI_ITEMS if zopfli_items else 0
+        routes |= self.BATCH_ROUTE_Q9_ITEMS if q9_items else 0
         if dictionary is not None:
             dictionary = bytes(dictionary)
 
@@ -311,8 +324,8 @@ class Library(object):
         """BrotliMi355xLastBatchInfo: the last compress_batch / compress_batch_with_dictionary call of this thread as a list of 8 integers -- [0] items, [1] items
         encoded side by side on the device, [2] items run one by one, [3] items answered without an encoder, [4] device groups, [5] dictionary bytes in use (0 without one),
         [6] items that began side by side and were redone one by one (counted in [2]), [7] of the items in [1], those longer than one
-        input block ([6] and [7]: long_items=True and quick_long_items=True only; the items quick_items=True and zopfli_items=True take side by side
-        count in [1] and [4])."""
+        input block ([6] and [7]: long_items=True and quick_long_items=True only; the items quick_items=True, zopfli_items=True and
+        q9_items=True take side by side count in [1] and [4])."""
         info = (c_uint64 * 8)()
         self.lib.BrotliMi355xLastBatchInfo.restype = None
         self.lib.BrotliMi355xLastBatchInfo.argtypes = [POINTER(c_uint64)]

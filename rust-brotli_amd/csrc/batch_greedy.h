@@ -70,6 +70,9 @@ struct BatchParseJob {
 };
 // one wavefront per table; a wavefront takes items from `counter` until none is left
 void lz77_batch_parse(const BatchParseJob& J);
+// The same launch shape for the H9 hasher of qualities 9 and 10 (batch_q9_kernels.hip: k_parse_batch_h9).  J.P is that of an H9
+// chain (hasher_kind 9, bucket_bits 15, block_bits 8, ndist 16), J.keys the H9 keys, J.dict.bytes is 0.
+void lz77_batch_parse_h9(const BatchParseJob& J);
 // Items of several blocks.  A meta-block of an item: a whole number of input blocks (the item's last one may be short).
 static constexpr uint32_t kBatchLongBlocks = 4;  // input blocks per item at most, hence meta-blocks
 static constexpr uint32_t kBatchLongBytes = 262144;
@@ -124,6 +127,13 @@ bool BatchLongEligible(const EncoderParams& params, size_t input_size);
 // cannot know: the stream stays empty and the caller redoes the item through the one-shot path.
 void BatchLongCompress(const EncoderParams& params, size_t count, const uint8_t* const* inputs, const size_t* sizes,
                        std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* demoted, uint32_t* groups);
+
+// Qualities 9 and 10 (BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS): an item of at most one input block under the H9 hasher, lgwin 17 .. 24,
+// is one live chain on a private H9 table (64 KiB of counters, 32 MiB of buckets) and one meta-block, like an H5 item.  Quality 10
+// is taken as quality 9 first, as BrotliEncoderCompress does (encode.rs:1468-1481).  No item is demoted and none fails.
+bool BatchQ9Eligible(const EncoderParams& params, size_t input_size);
+void BatchQ9Compress(const EncoderParams& params, size_t count, const uint8_t* const* inputs, const size_t* sizes,
+                     std::vector<std::vector<uint8_t>>* streams, uint32_t* groups);
 
 // One group through the meta-block stage (encoder.cpp): an entry is one meta-block; the meta-blocks of an item follow each other
 // and make a complete stream of their own.  An item of one meta-block leaves the fields behind `uncompressed` at zero.

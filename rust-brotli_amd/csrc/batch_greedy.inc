@@ -91,7 +91,7 @@ Lz77Params ChainParams(const EncoderParams& p) {
   memset(&P, 0, sizeof(P));
   P.ring_mask = (1u << ComputeRbBits(p)) - 1u;
   P.max_backward_limit = (1u << p.lgwin) - 16u;
-  P.hasher_kind = 5;
+  P.hasher_kind = p.hasher.type == 9 ? 9 : 5;  // as Lz77Stage::Setup: H9 (qualities 9 and 10) hashes like H5, onto 15 bits
   P.bucket_bits = (uint32_t)p.hasher.bucket_bits;
   P.block_bits = (uint32_t)p.hasher.block_bits;
   P.hash_len = (uint32_t)p.hasher.hash_len;
@@ -100,7 +100,7 @@ Lz77Params ChainParams(const EncoderParams& p) {
   P.literal_byte_score = (uint32_t)(p.hasher.literal_byte_score ? p.hasher.literal_byte_score : 540);
   P.score_per_byte = P.literal_byte_score >> 2;
   P.use_dictionary = p.use_dictionary ? 1 : 0;
-  P.spree_window = 64;
+  P.spree_window = p.hasher.type == 9 ? 512 : 64;  // (Lz77Stage::Setup: 512 from quality 9 on; the Zopfli walk has no use for it)
   P.dist_max_distance = (uint32_t)p.dist.max_distance;
   P.quality = (uint32_t)p.quality;
   P.num_segments = 1;
@@ -124,8 +124,8 @@ const BatchLimits& Limits() {
                                   EnvSize("BROTLI_MI355X_BATCH_TABLES", 0)};
   return limits;
 }
-// a table is 1 MiB at quality 5 and 16 MiB at quality 8, 256 KiB (H2, H3) or 512 KiB (H4) at qualities 2 .. 4: as many as the
-// parse kernel keeps resident (256 CUs x 4 SIMDs x 4 wavefronts) within 8 GiB
+// a table is 1 MiB at quality 5 and 16 MiB at quality 8, 256 KiB (H2, H3) or 512 KiB (H4) at qualities 2 .. 4, 32 MiB + 64 KiB
+// at qualities 9 and 10 (255 of them): as many as the parse kernel keeps resident (256 CUs x 4 SIMDs x 4 wavefronts) within 8 GiB
 size_t TablesMax(size_t table_bytes) {
   return Limits().tables ? Limits().tables : std::max<size_t>(1, std::min<size_t>(4096, ((size_t)8 << 30) / table_bytes));
 }
@@ -381,7 +381,8 @@ void FinishLongItems(const EncoderParams& p, const BatchParseJob& J, const Batch
   }
 }
 
-// Qualities 5 .. 8, items of one block.  p: the parameters the items share, finalized.  dict == nullptr: the plain call.
+// Qualities 5 .. 8, items of one block, and qualities 9 / 10 on the H9 hasher (BatchQ9Compress: p.hasher.type == 9, no dictionary).
+// p: the parameters the items share, finalized.  dict == nullptr: the plain call.
 void CompressGroups(const EncoderParams& p, const uint8_t* dict, uint32_t D, size_t count, const uint8_t* const* inputs, const size_t* sizes,
                     std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* reference_fails, uint32_t* groups) {
   streams->assign(count, std::vector<uint8_t>());
@@ -442,7 +443,7 @@ void CompressGroups(const EncoderParams& p, const uint8_t* dict, uint32_t D, siz
     BatchParseJob J = GreedyJob(p, P, g, text);
     J.records = g.mem.uninit<BatchRecord>((size_t)g.n * sizeof(BatchRecord));
     J.dict = image;
-    lz77_batch_parse(J);
+    if (P.hasher_kind == 9) lz77_batch_parse_h9(J); else lz77_batch_parse(J);
     FinishOneBlockItems(p, J, g, streams, reference_fails);
     first = g.last;
   }
@@ -459,6 +460,34 @@ void BatchGreedyCompressWithDictionary(const EncoderParams& user, const uint8_t*
                                        const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
                                        std::vector<uint8_t>* reference_fails, uint32_t* groups) {
   CompressGroups(DictionaryItemParams(user, count ? sizes[0] : 0), dict, (uint32_t)dict_size, count, inputs, sizes, streams, reference_fails, groups);
+}
+
+namespace {
+// BrotliEncoderCompress runs quality 10 at quality 9 (encode.rs:1468-1481; CompressOneShot, cabi.cpp): the parameters of an item
+// of either quality are those of quality 9
+EncoderParams Q9ItemParams(const EncoderParams& user, size_t input_size) {
+  EncoderParams u = user;
+  if (u.quality == 10) u.quality = 9;
+  return ItemParams(u, input_size);
+}
+}  // namespace
+
+bool BatchQ9Eligible(const EncoderParams& user, size_t input_size) {
+  if (input_size == 0) return false;  // (answered without an encoder)
+  // (lgwin <= 16 is hasher 42 in the reference: one by one)
+  if ((user.quality != 9 && user.quality != 10) || user.lgwin < 17 || user.lgwin > 24 || !PlainStreamParams(user)) return false;
+  if (input_size > ((size_t)1 << 18)) return false;  // (lgblock is 18 at most at this quality)
+  // one block of a stream that starts at 0: the item ends inside the first half of its ring buffer, 1 << (1 + max(lgwin, lgblock)),
+  // so no filed position differs from its ring-buffer index and H9's ring-end case (SearchResult::stored) does not come up
+  const EncoderParams p = Q9ItemParams(user, input_size);
+  return p.hasher.type == 9 && p.hasher.bucket_bits == 15 && p.hasher.block_bits == 8 && input_size <= ((size_t)1 << p.lgblock);
+}
+
+// Qualities 9 and 10, items of one block: the steps of BatchGreedyCompress on H9 tables, parsed by k_parse_batch_h9.
+void BatchQ9Compress(const EncoderParams& user, size_t count, const uint8_t* const* inputs, const size_t* sizes,
+                     std::vector<std::vector<uint8_t>>* streams, uint32_t* groups) {
+  // (nothing in the parameters differs between items of at most one block)
+  CompressGroups(Q9ItemParams(user, count ? sizes[0] : 0), nullptr, 0, count, inputs, sizes, streams, nullptr, groups);
 }
 
 // Qualities 5 .. 8, items of two to kBatchLongBlocks blocks: one chain and up to kBatchLongBlocks meta-blocks per item.

@@ -98,6 +98,48 @@ BR_DEV void br_batch_item(const BatchParseJob& J, const ChainTables& T, ChainScr
   br_batch_close_record(J.records + index, t.logs, histo, t.text, D, it, tail.n_cmds, tail.n_lits, tail.insert_len, kDict ? left.bad_commands : 0u);
 }
 
+#if !BR_SCALAR
+// the group's arrays and the device's static-dictionary and entropy tables as a batch chain takes them (lz77_kernels.hip)
+ChainTables batch_chain_tables(const BatchParseJob& J);
+#endif
+
+// ---- qualities 9 and 10 (k_parse_batch_h9,BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS) --------------------------------------------------
+// br_batch_item without a dictionary on the H9 hasher: 1 << 15 keys, rings 256 deep, sixteen cache distances, the H9 scores, the
+// static dictionary behind H9's own throttle.  The chain is the first br_parse_segment<true, false, true>: it reads the rings of its
+// private table (probe_pair's non-rows live path: every ring entry in reach has its text looked at, the table keeps no tags) and
+// files with plain Store in ascending order -- J.P.masked_from is kNeverMasked, so br_live_store_copy masks nothing.
+//
+// The table is reused by the next item of its wavefront with only its counters emptied (br_live_reset).  What the item in front
+// left in the buckets cannot be reached, at this depth and with u16 counters as at the others: a walk over key k reads the
+// min(num[k], 256) slots in front of num[k] and nothing else; num[k] is 0 after the reset and every filing writes slot num[k] & 255
+// before it moves the counter on by one, so while the counter has not wrapped those slots are the item's own last filings.  A counter
+// that wraps at 65 536 filings (one key filed that often: a run of one byte) comes back to 0 with all 256 slots of the ring
+// written by this item, 256 times over, and goes on from there exactly as after the reset -- the reference's own u16 arithmetic,
+// under which such a key shows no candidate until it is filed again.  Either way a walk never sees a slot this item did not write.
+BR_DEV void br_batch_item_h9(const BatchParseJob& J, const ChainTables& T, ChainScratchT<true, false>& s, uint32_t* histo /* 256 words */,
+                             uint32_t index, uint32_t table) {
+  const BatchItem it = br_batch_load_item(J.items, index);
+  Lz77Params P = J.P;
+  P.total_bytes = it.bytes;
+  ChainTables t = T;
+  LiveRing lr;
+  br_batch_item_tables(J, P, it, 0, table, t, lr);
+  br_live_reset(lr, P.bucket_bits);
+  Segment seg;
+  seg.start = seg.blk_start = 0;
+  seg.end = seg.blk_end = it.bytes;
+  seg.flags = kSegFirstInBlock | kSegLastInBlock;
+  seg.cmd_base = it.cmd_base;
+  seg.block_index = 0;
+  seg.cmd_cap = it.cmd_cap;
+  const SegEntry entry = br_stream_start_entry(P.spree_window);
+  SegExit left;
+  SegEntry next;
+  BlockTail tail;
+  br_parse_segment<true, false, true>(P, t, s, seg, entry, left, next, &lr, &tail);
+  br_batch_close_record(J.records + index, t.logs, histo, t.text, 0, it, tail.n_cmds, tail.n_lits, tail.insert_len, 0u);
+}
+
 // command i of item `index` as the meta-block stage wants it
 BR_DEV Command br_batch_command(const BatchParseJob& J, const BatchItem& it, const BatchRecord& r, uint32_t i) {
   if (r.trailing != 0 && i + 1 == r.n_cmds) return br_insert_only_command(r.trailing);

@@ -51,6 +51,18 @@ void lz77_batch_parse(const BatchParseJob& J) {
   *J.counter = J.n_items;
 }
 
+// qualities 9 and 10: the same plan on the H9 item code and its own scratch (the 256-deep rings' candidates)
+void lz77_batch_parse_h9(const BatchParseJob& J) {
+  if (J.n_items == 0) return;
+  if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
+  if (J.P.hasher_kind != 9 || J.P.block_bits != 8 || J.P.ndist > 16 || J.dict.bytes != 0) throw std::runtime_error("brotli_mi355x: not the job of an H9 batch chain");
+  const ChainTables T = EmuBatchChainTables(J);
+  static thread_local ChainScratchT<true, false> scratch;
+  uint32_t histo[256];
+  for (uint32_t place = 0; place < J.n_items; ++place) br_batch_item_h9(J, T, scratch, histo, J.order[place], place % J.tables);
+  *J.counter = J.n_items;
+}
+
 void lz77_batch_parse_long(const BatchParseJob& J, BatchLongRecord* records) {
   if (J.n_items == 0) return;
   if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");

@@ -2,7 +2,8 @@
 // BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS).
 //
 // (Quality 11 alone: BrotliEncoderCompress, which defines an item's bytes, runs quality 10 at quality 9 -- encode.rs:1468-1481:
-// the stream is byte for byte that of plain quality 9 -- and a Zopfli walk does not give those bytes.  Items of quality 10 stay one by one.)
+// the stream is byte for byte that of plain quality 9 -- and a Zopfli walk does not give those bytes.  Items of quality 10 are not this route's: they go
+// one by one, or side by side as quality 9 under BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS, batch_greedy.h.)
 // An item of at most 65 536 bytes -- at most one input block, lgblock is at least 16 at this quality -- is ONE sequential walk of
 // br_zopfli_parse (zopfli_device.h, precomputed = false: matching, tree updates and the dynamic programme position by position, the
 // reference's way) on H10 trees of its own, and ONE meta-block.  The sequential form handles the positions skipped behind a match

@@ -1014,11 +1014,11 @@ static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEn
   uint64_t info[8] = {count, 0, 0, 0, 0, 0, 0, 0};
   memcpy(g_batch_info, info, sizeof(info));
   if ((routes & ~(uint32_t)(BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS | BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS | BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS |
-                            BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS)) != 0) {
+                            BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS | BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS)) != 0) {
     // a route this build does not know fails the call as a whole, like a device error: a caller can probe for later routes
     SetError(entry, ("routes " + std::to_string(routes) + " names a route this build does not know (known: BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS = 1, "
-                     "BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS = 4, BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS = 16, BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS = 32; "
-                     "the values 2 and 8 are reserved)").c_str());
+                     "BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS = 4, BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS = 16, BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS = 32, "
+                     "BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS = 128; the values 2, 8 and 64 are reserved)").c_str());
     for (size_t i = 0; i < count; ++i) output_sizes[i] = 0;
     if (item_results && count) memset(item_results, 0, count * sizeof(int32_t));
     return 0;
@@ -1038,18 +1038,19 @@ static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEn
     // The items an encoder sees and that go side by side on the device: every item of qualities 0 and 1 (fragment_stream.h), the
     // items of one input block under an H5 hasher at qualities 5 .. 8 (batch_greedy.h) and, where the caller asked for that route,
     // those of two to four blocks, or those of one input block under a BasicHasher at qualities 2 .. 4, or those of two to four
-    // blocks at these qualities (batch_quick.h), or those of at most 65 536 bytes at quality 11 (batch_zopfli.h).  Every
-    // other item goes through the one-shot path by itself, on this thread, in the caller's order (the same bytes, no gain in speed).
+    // blocks at these qualities (batch_quick.h), or those of at most 65 536 bytes at quality 11 (batch_zopfli.h), or those of
+    // one input block under the H9 hasher at qualities 9 and 10 (batch_greedy.h: BatchQ9Compress).  Every other item goes through the one-shot path by itself, on this thread, in the caller's order (the same bytes, no gain in speed).
     struct Routed {  // the items of one route: their places in the caller's arrays, their inputs and their sizes
       std::vector<size_t> item;
       std::vector<const uint8_t*> in;
       std::vector<size_t> size;
     };
-    Routed plain, long_items, quick_items, quick_long_items, zopfli_items;
+    Routed plain, long_items, quick_items, quick_long_items, zopfli_items, q9_items;
     const bool long_route = (routes & BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS) != 0;
     const bool quick_route = (routes & BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS) != 0;
     const bool quick_long_route = (routes & BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS) != 0;
     const bool zopfli_route = (routes & BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS) != 0;
+    const bool q9_route = (routes & BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS) != 0;
     auto one_by_one = [&](size_t i) {
       std::string error;
       results[i] = CompressOneShot(quality, lgwin, mode, input_sizes[i], inputs[i], false, &output_sizes[i], outputs[i], nullptr, &error);
@@ -1098,6 +1099,7 @@ static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEn
       else if (quick_route && BatchQuickEligible(params, input_sizes[i])) r = &quick_items;
       else if (quick_long_route && BatchQuickLongEligible(params, input_sizes[i])) r = &quick_long_items;
       else if (zopfli_route && BatchZopfliEligible(params, input_sizes[i])) r = &zopfli_items;
+      else if (q9_route && BatchQ9Eligible(params, input_sizes[i])) r = &q9_items;
       if (!r) {
         one_by_one(i);
         continue;
@@ -1122,6 +1124,13 @@ static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEn
       BatchZopfliCompress(params, zopfli_items.item.size(), zopfli_items.in.data(), zopfli_items.size.data(), &streams, &reference_fails, &groups);
       info[4] += groups;
       info[1] += deliver(zopfli_items, streams, nullptr, &reference_fails);
+    }
+    // ---- the items of one block at qualities 9 and 10, one chain each on an H9 table, in groups of their own
+    // (BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS)
+    if (!q9_items.item.empty()) {
+      BatchQ9Compress(params, q9_items.item.size(), q9_items.in.data(), q9_items.size.data(), &streams, &groups);
+      info[4] += groups;
+      info[1] += deliver(q9_items, streams, nullptr);
     }
     // ---- the items of two to four blocks at qualities 2 .. 4, one chain each, in groups of their own
     // (BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS)

@@ -1437,8 +1437,14 @@ BR_DEV SearchResult br_search(const Lz77Params& P, const ChainTables& t, ChainSc
   } else {
     r = br_fold_probe<kH9, kRows>(P, t, s, m, w, ds, blk_end);
   }
-  // FindLongestMatch files the position it has just searched (mod.rs:1794-1795)
-  if constexpr (kLive) br_live_insert(*live, m.live_key[w], m.live_n[w], x);
+  // FindLongestMatch files the position it has just searched (mod.rs:1794-1795).  H9 leaves that out together with its bucket stage
+  // where a cache match reaches the ring-buffer end (SearchResult::stored); the probe's second slot took the position for filed,
+  // so it is dropped.  (Unreachable in the one kH9 live chain there is, k_parse_batch_h9: its items start at 0 and end inside the
+  // first half of their ring buffer.)
+  if constexpr (kLive) {
+    if (!kH9 || r.stored) br_live_insert(*live, m.live_key[w], m.live_n[w], x);
+    else m.pos = 0xffffffffu;
+  }
 #if defined(BR_CHAIN_PROFILE)
   m.t_fold += BR_TICK() - t1;
   m.n_fold++;

@@ -2571,7 +2571,7 @@ void lz77_live_parse(const Lz77Params& P, const Lz77Buffers& B, const LiveBuffer
 }
 
 // ---- batch_greedy.h: the small items of a batch, one live chain each
-static ChainTables batch_chain_tables(const BatchParseJob& J) {
+ChainTables batch_chain_tables(const BatchParseJob& J) {  // (batch_greedy_device.h: batch_q9_kernels.hip calls it too)
   const DeviceTables& dt = dev_tables();
   ChainTables T;
   T.text = J.text;

@@ -52,6 +52,12 @@ reference's way on H10 trees of its own.  The parent's library is measured throu
 one (on the first --loop-items items, scaled by item count).  The classes are 1024x4KiB, 256x16KiB, 64x64KiB and 16x4KiB, the few-items
 case.  (--qualities 10,11 is accepted: BrotliEncoderCompress runs quality 10 at quality 9, and it goes one by one in both builds.)
 
+With --q9-items (and --qualities 9,10) this build is called through BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS:
+the items of at most one input block (256 KiB at lgwin 22) go side by side, one chain each on a private H9 table of 32 MiB, 255 of
+them in flight.  The parent's library is measured through its plain batch call, which takes these items one by one (on the first
+--loop-items items, scaled by item count), and through its 4-thread loop; the CPU baseline is the oracle on one core.  The classes
+are 4096x4KiB, 1024x16KiB, 256x64KiB and 64x256KiB, the few-items cases 16x4KiB and 64x4KiB, and the log-uniform mix.
+
 With --same-call (and any of the above) the parent's library is measured through the very call this build is measured through, route bits
 and dictionary included, alternating with it --rounds times: the A/B of a change that keeps the routes.  Per class the result holds the
 medians of both, their difference, and the parent's own spread between its rounds as the margin; nothing else is measured.
@@ -102,6 +108,9 @@ CLASSES = {
     "256x16KiB": ("uniform", 256, 16 << 10),
     "64x64KiB": ("uniform", 64, 64 << 10),
     "16x4KiB": ("uniform", 16, 4 << 10),
+    # qualities 9 and 10 (--q9-items)
+    "256x64KiB": ("uniform", 256, 64 << 10),
+    "64x256KiB": ("uniform", 64, 256 << 10),
 }
 HEADLINE = ["4096x4KiB", "4096x16KiB", "1024x64KiB", "64xalice29", "4096xlog200B-256KiB"]
 AB = ["4096x512B", "4096x2KiB", "4096xlog200B-256KiB"]
@@ -112,6 +121,7 @@ DICT_QUICK_HEADLINE = ["4096x4KiB", "4096x512B", "1024x16KiB", "64x4KiB"]  # (--
 DICT_QUICK_QUALITIES = {"1024x16KiB": (2, 3)}  # (one input block at quality 2 and 3)
 QUICK_HEADLINE = ["4096x4KiB", "4096x16KiB", "1024x64KiB", "4096x512B", "4096xlog200B-256KiB"]  # (--quick-items)
 ZOPFLI_HEADLINE = ["1024x4KiB", "256x16KiB", "64x64KiB", "16x4KiB"]  # (--zopfli-items)
+Q9_HEADLINE = ["4096x4KiB", "1024x16KiB", "256x64KiB", "64x256KiB", "16x4KiB", "64x4KiB", "4096xlog200B-256KiB"]  # (--q9-items)
 
 
 def items_of(name, data):
@@ -296,7 +306,7 @@ def child(args):
                 if args.child == "batch":
                     times, csize, info, failed = measure_batch(args.lib, first if args.first_only else items, quality, args.runs, args.warmup, dictionary,
                                                               (1 if args.long_items else 0) | (4 if args.quick_items else 0) | (16 if args.quick_long_items else 0) |
-                                                              (32 if args.zopfli_items else 0))
+                                                              (32 if args.zopfli_items else 0) | (128 if args.q9_items else 0))
                     row.update(stats(times), compressed_bytes=csize, batch_info=info, reference_fails_on_items=failed, measured_items=len(first) if args.first_only else len(items))
                 elif args.child == "loop":
                     times, failed = measure_loop(args.lib, first, quality, args.threads, args.runs, 1, dictionary)
@@ -311,7 +321,7 @@ def child(args):
 
 
 def run_child(args, what, classes, lib=None, lds=None, threads=1, limit=600, first_only=False, plain=False, long_items=False, quick_items=False,
-              quick_long_items=False, zopfli_items=False):
+              quick_long_items=False, zopfli_items=False, q9_items=False):
     env = dict(os.environ)
     env.pop("BROTLI_MI355X_BATCH_LDS_BITS", None)
     if lds is not None:
@@ -322,6 +332,7 @@ def run_child(args, what, classes, lib=None, lds=None, threads=1, limit=600, fir
            "--dictionary", str(args.dictionary)] + (["--first-only"] if first_only else []) + (["--plain"] if plain else []) + (["--long-items"] if long_items else []) + (["--quick-items"] if quick_items else [])
     cmd += (["--quick-long-items"] if quick_long_items else []) + (["--quick-long-classes"] if args.quick_long_items else [])
     cmd += ["--zopfli-items"] if zopfli_items else []
+    cmd += ["--q9-items"] if q9_items else []
     r = subprocess.run(cmd, env=env)
     if r.returncode != 0:
         raise SystemExit("batch_probe: %s (lds=%s, threads=%d) ended with status %d: nothing more is started" % (what, lds, threads, r.returncode))
@@ -462,8 +473,9 @@ def main_same_call(args, doc, save, classes):
     each -- for a change that keeps the routes and must not cost them anything.  Per class: the median of either build's round
     medians, and the parent's own run-to-run spread (the largest difference between its rounds) as the margin."""
     doc["what"] = "this build against the parent commit's library through the same batch call (%s), alternating, %d rounds; lgwin 22" % (
-        ", ".join(n for n in ("long_items", "quick_items", "quick_long_items", "zopfli_items") if getattr(args, n)) or "no route bit", args.rounds)
-    routes = dict(long_items=args.long_items, quick_items=args.quick_items, quick_long_items=args.quick_long_items, zopfli_items=args.zopfli_items)
+        ", ".join(n for n in ("long_items", "quick_items", "quick_long_items", "zopfli_items", "q9_items") if getattr(args, n)) or "no route bit", args.rounds)
+    routes = dict(long_items=args.long_items, quick_items=args.quick_items, quick_long_items=args.quick_long_items, zopfli_items=args.zopfli_items,
+                  q9_items=args.q9_items)
     rows = {}
     for rnd in range(args.rounds):
         for name, lib in (("this_rounds", args.lib), ("parent_rounds", os.path.abspath(args.parent_lib))):
@@ -503,6 +515,7 @@ def main():
     ap.add_argument("--quick-items", action="store_true", help="this build through BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS (--qualities 2,3,4)")
     ap.add_argument("--quick-long-items", action="store_true", help="this build through routes QUICK_ITEMS | QUICK_LONG_ITEMS, the parent through QUICK_ITEMS (qualities 2,3,4 per class)")
     ap.add_argument("--zopfli-items", action="store_true", help="this build through BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS (--qualities 11)")
+    ap.add_argument("--q9-items", action="store_true", help="this build through BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS (--qualities 9,10)")
     ap.add_argument("--same-call", action="store_true", help="the parent's library through the same call as this build, alternating --rounds times (needs --parent-lib)")
     ap.add_argument("--quick-long-classes", action="store_true", help="(child) only the qualities of QUICK_LONG_QUALITIES")
     ap.add_argument("--plain", action="store_true", help="(child) the plain call although a dictionary size is given")
@@ -526,7 +539,7 @@ def main():
     if args.quick_long_items:
         args.quick_items = True
         args.qualities = "2,3,4"
-    headline = [c for c in (args.only.split(",") if args.only else (list(QUICK_LONG_QUALITIES) if args.quick_long_items else QUICK_HEADLINE if args.quick_items else ZOPFLI_HEADLINE if args.zopfli_items else HEADLINE)) if c in CLASSES]
+    headline = [c for c in (args.only.split(",") if args.only else (list(QUICK_LONG_QUALITIES) if args.quick_long_items else QUICK_HEADLINE if args.quick_items else ZOPFLI_HEADLINE if args.zopfli_items else Q9_HEADLINE if args.q9_items else HEADLINE)) if c in CLASSES]
     if args.long_items:
         doc["what"] = "BrotliMi355xCompressBatchEx(BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS) vs the parent commit's batch call and 4-thread loop vs the oracle on one CPU core; lgwin 22"
     if args.quick_items:
@@ -537,6 +550,9 @@ def main():
     if args.zopfli_items:
         doc["what"] = ("BrotliMi355xCompressBatchEx(BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS) vs the parent commit's batch call, there one by one (on the first "
                        "--loop-items items, scaled by item count), vs the oracle on one CPU core; lgwin 22")
+    if args.q9_items:
+        doc["what"] = ("BrotliMi355xCompressBatchEx(BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS) vs the parent commit's batch call, there one by one (on the first "
+                       "--loop-items items, scaled by item count), and its 4-thread loop vs the oracle on one CPU core; lgwin 22")
     if args.same_call:
         dict_classes = DICT_QUICK_HEADLINE if args.quick_items else ["4096x4KiB", "1024x64KiB"]
         return main_same_call(args, doc, save, [c for c in dict_classes if not args.only or c in args.only.split(",")] if args.dictionary else headline)
@@ -567,7 +583,7 @@ def main():
         rows = {}
         for rnd in range(args.rounds):
             for row in run_child(args, "batch", headline, limit=900, long_items=args.long_items, quick_items=args.quick_items, quick_long_items=args.quick_long_items,
-                                 zopfli_items=args.zopfli_items):
+                                 zopfli_items=args.zopfli_items, q9_items=args.q9_items):
                 this = {k: row[k] for k in ("median_ms", "min_ms", "max_ms", "spread_pct", "runs")}
                 if rnd == 0:
                     rows[key(row)] = {"items": row["items"], "bytes": row["bytes"], "compressed_bytes": row["compressed_bytes"], "batch_info": row["batch_info"], "batch": this}
