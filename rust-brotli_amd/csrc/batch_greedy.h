@@ -67,6 +67,9 @@ struct BatchParseJob {
   uint32_t* counter;  // [1], zero: the next place of `order` to hand out
   BatchRecord* records;
   BatchDictImage dict;  // bytes == 0: the plain call
+  // a dictionary per item (BrotliMi355xCompressBatchWithDictionaries, lz77_batch_parse_dicts): [n_items], the dictionary bytes in
+  // front of item i, 2 .. 65536; nullptr: every other caller.  No image: every chain files its dictionary itself.
+  const uint32_t* item_dict_bytes;
 };
 // one wavefront per table; a wavefront takes items from `counter` until none is left
 void lz77_batch_parse(const BatchParseJob& J);
@@ -101,6 +104,14 @@ void lz77_batch_gather_long(const BatchParseJob& J, const BatchLongRecord* recor
 // dict_shifted_dev: 16-byte aligned, (-dict_bytes & 15) zero bytes and then the dictionary, so that it ends on a 16-byte boundary.
 void lz77_batch_dict_text(const uint8_t* dict_shifted_dev, uint32_t dict_bytes, const uint8_t* packed_dev, const uint32_t* starts_dev,
                           const BatchItem* items_dev, uint32_t n_items, uint8_t* text);
+// A dictionary per item.  lz77_batch_dicts_text: text[items[i].text_off - dict_bytes[i] ..) = dictionary i | item i for every item,
+// the dictionary's dict_bytes[i] bytes read from pool_dev + dict_off[i]; `text` is zero where nothing is written, text_off is a multiple
+// of 64 and at least dict_bytes[i] rounded up to 16.  pool_dev: 16-byte aligned, every dictionary in it ENDS on a 16-byte boundary (the
+// dict_shifted convention: dict_off[i] + dict_bytes[i] is a multiple of 16) behind at least 15 bytes that may be read.
+void lz77_batch_dicts_text(const uint8_t* pool_dev, const uint32_t* dict_off_dev, const uint32_t* dict_bytes_dev, const uint8_t* packed_dev,
+                           const uint32_t* starts_dev, const BatchItem* items_dev, uint32_t n_items, uint8_t* text);
+// the launch shape of lz77_batch_parse for J.item_dict_bytes != nullptr (J.dict is not used): k_parse_batch_dicts
+void lz77_batch_parse_dicts(const BatchParseJob& J);
 // lz77_batch_dict_image: files the positions [0, dict_bytes - 3) of a text whose keys are `keys` on the scratch table (num, buckets)
 // -- `num` ends up as the image's counters -- and lists the covered entries: entries[2 * i], entries[2 * i + 1], *n_entries.
 void lz77_batch_dict_image(const Lz77Params& P, const uint16_t* keys, uint32_t dict_bytes, uint16_t* num, uint32_t* buckets,
@@ -121,6 +132,12 @@ bool BatchDictionaryEligible(const EncoderParams& params, size_t dict_size, size
 void BatchGreedyCompressWithDictionary(const EncoderParams& params, const uint8_t* dict, size_t dict_size, size_t count,
                                        const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
                                        std::vector<uint8_t>* reference_fails, uint32_t* groups);
+// The same with a dictionary per item: item i lies behind dicts[i] (dict_sizes[i] bytes, after the reference's truncation; several
+// items may share a pointer -- dictionaries are told apart by pointer and size, and each goes up once per group).  Every
+// (dict_sizes[i], sizes[i]) is BatchDictionaryEligible.
+void BatchGreedyCompressWithDictionaries(const EncoderParams& params, size_t count, const uint8_t* const* dicts, const size_t* dict_sizes,
+                                         const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
+                                         std::vector<uint8_t>* reference_fails, uint32_t* groups);
 // Items of several blocks, each one chain: 1 << lgblock < size <= kBatchLongBytes, otherwise as BatchGreedyEligible.
 bool BatchLongEligible(const EncoderParams& params, size_t input_size);
 // (*demoted)[i] != 0: a meta-block of item i that is not its last took the size fallback (encode.rs:2141-2163), which the chain

@@ -7,7 +7,9 @@
 #include <string.h>
 
 #include <algorithm>
+#include <map>
 #include <stdexcept>
+#include <utility>
 
 #include "batch_quick.h"
 #include "batch_zopfli.h"
@@ -153,6 +155,8 @@ struct CallArrays {
   PinnedArray<uint8_t> staging;
   PinnedArray<BatchItem> items;
   PinnedArray<uint32_t> order, offsets, starts;
+  PinnedArray<uint32_t> dict_bytes, dict_off;  // a dictionary per item: its bytes, and where it starts in `dict_pool`
+  PinnedArray<uint8_t> dict_pool;
   PinnedArray<BatchRecord> records;
   PinnedArray<BatchLongRecord> long_records;
 };
@@ -170,37 +174,50 @@ struct Group {
   BatchItem* items_dev;
   uint32_t* order_dev;
 };
-// D: the bytes of the call's dictionary (0: none), which go in front of every item in the padded text
+// The dictionary bytes that go in front of every item of a call in the padded text: one size for all of them (the calls with a
+// shared dictionary; 0: none) or a size per item, of which "all equal" is the former.
+struct DictSizes {
+  uint32_t all;
+  const size_t* each;  // [count], nullptr: `all`
+  DictSizes(uint32_t all_items) : all(all_items), each(nullptr) {}
+  explicit DictSizes(const size_t* per_item) : all(0), each(per_item) {}
+  bool any() const { return each != nullptr || all != 0; }
+  uint32_t of(size_t i) const { return each ? (uint32_t)each[i] : all; }
+};
+uint32_t DictRoom(uint32_t D) { return (D + 63u) & ~63u; }
+// dict: the dictionary bytes of every item of the call; with a size per item g->A->dict_bytes holds those of the group's items
 // max_items: a bound of the route's own on the items of a group, below BROTLI_MI355X_BATCH_GROUP_ITEMS (0: none)
-void StageGroup(size_t first, size_t count, const uint8_t* const* inputs, const size_t* sizes, uint32_t D, size_t tables_max,
+void StageGroup(size_t first, size_t count, const uint8_t* const* inputs, const size_t* sizes, const DictSizes& dict, size_t tables_max,
                 CallArrays* arrays, Group* g, size_t max_items = 0) {
   CallArrays& A = *arrays;
-  const uint32_t dict_room = (D + 63u) & ~63u;
   // (the limit counts the dictionary copies of the padded text: scratch -- keys and flags -- grows with them)
-  size_t last = first, padded = 0, packed = 0;
+  size_t last = first, padded = 0, packed = 0, dict_copies = 0;
   const size_t group_items = max_items ? std::min(max_items, Limits().group_items) : Limits().group_items;
   while (last < count && last - first < group_items &&
-         (last == first || packed + (last - first + 1) * (size_t)D + sizes[last] <= Limits().group_bytes)) {
-    padded += dict_room + Padded((uint32_t)sizes[last]);
+         (last == first || packed + dict_copies + dict.of(last) + sizes[last] <= Limits().group_bytes)) {
+    padded += DictRoom(dict.of(last)) + Padded((uint32_t)sizes[last]);
     packed += sizes[last];
+    dict_copies += dict.of(last);
     ++last;
   }
   const uint32_t n = (uint32_t)(last - first);
   // one page-locked buffer, one upload: [padded text | 64 | packed text | 64]; with a dictionary the packed text alone -- the
   // padded text, dictionary | item per item, is laid out on the device
-  const size_t packed_at = D != 0 ? 0 : padded + 64;
+  const size_t packed_at = dict.any() ? 0 : padded + 64;
   const size_t text_bytes = packed_at + packed + 64;
   A.staging.resize_discard(text_bytes);
   memset(A.staging.data(), 0, text_bytes);
   A.items.resize_discard(n);
   A.order.resize_discard(n);
   A.starts.resize_discard(n);
+  A.dict_bytes.resize_discard(n);
   uint32_t off = 0, start = 0, cmd_base = 0;
   for (uint32_t i = 0; i < n; ++i) {
     const uint32_t bytes = (uint32_t)sizes[first + i];
     const uint32_t cmd_cap = bytes / 2 + 8;
-    off += dict_room;
-    if (D == 0) memcpy(A.staging.data() + off, inputs[first + i], bytes);
+    A.dict_bytes[i] = dict.of(first + i);
+    off += DictRoom(A.dict_bytes[i]);
+    if (!dict.any()) memcpy(A.staging.data() + off, inputs[first + i], bytes);
     memcpy(A.staging.data() + packed_at + start, inputs[first + i], bytes);
     A.items[i] = BatchItem{off, bytes, cmd_base, cmd_cap};
     A.starts[i] = start;
@@ -209,8 +226,11 @@ void StageGroup(size_t first, size_t count, const uint8_t* const* inputs, const 
     cmd_base += cmd_cap;
     A.order[i] = i;
   }
-  // largest first: the large items of a group run as long as a lone wavefront takes, the small ones fill in behind them
-  std::stable_sort(A.order.data(), A.order.data() + n, [&](uint32_t a, uint32_t b) { return A.items[a].bytes > A.items[b].bytes; });
+  // largest first: the large items of a group run as long as a lone wavefront takes, the small ones fill in behind them.  The
+  // length of a chain's work is dictionary + item where the chain files its dictionary itself; behind a shared dictionary the
+  // sum orders the items as their sizes do.
+  std::stable_sort(A.order.data(), A.order.data() + n,
+                   [&](uint32_t a, uint32_t b) { return A.dict_bytes[a] + A.items[a].bytes > A.dict_bytes[b] + A.items[b].bytes; });
 
   g->A = arrays;
   g->first = first;
@@ -449,7 +469,76 @@ void CompressGroups(const EncoderParams& p, const uint8_t* dict, uint32_t D, siz
   }
 }
 
+// Qualities 5 .. 8 behind a dictionary per item: the steps of CompressGroups' dictionary path without an image -- there is none
+// to share, so every chain files its own dictionary (br_batch_item<kRows, true, true>).  A group uploads its packed items and,
+// once each, the dictionaries its items name: a pool in which every dictionary ends on a 16-byte boundary behind zero bytes of
+// its own (the dict_shifted convention of lz77_batch_dict_text), with the place and the size of item i's dictionary beside it.
+// dicts[i] / dict_sizes[i]: the dictionary of item i as in use; two items share one where pointer and size agree.
+void CompressGroupsWithDictionaries(const EncoderParams& p, size_t count, const uint8_t* const* dicts, const size_t* dict_sizes,
+                                    const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
+                                    std::vector<uint8_t>* reference_fails, uint32_t* groups) {
+  streams->assign(count, std::vector<uint8_t>());
+  reference_fails->assign(count, 0);
+  *groups = 0;
+  if (count == 0) return;
+  const size_t keys_per_table = (size_t)1 << p.hasher.bucket_bits;
+  const size_t tables_max = TablesMax(keys_per_table * 2 + (keys_per_table << p.hasher.block_bits) * 4);
+  const Lz77Params P = ChainParams(p);
+
+  CallArrays A;
+  size_t first = 0;
+  while (first < count) {
+    Group g;
+    StageGroup(first, count, inputs, sizes, DictSizes(dict_sizes), tables_max, &A, &g);
+    ++*groups;
+    // ---- the pool (the group's byte limit counts a dictionary per item, so the pool stays below it)
+    std::map<std::pair<const uint8_t*, size_t>, uint32_t> placed;
+    A.dict_off.resize_discard(g.n);
+    size_t pool_bytes = 0;
+    for (uint32_t i = 0; i < g.n; ++i)
+      if (placed.emplace(std::make_pair(dicts[first + i], dict_sizes[first + i]), 0u).second) pool_bytes += (dict_sizes[first + i] + 15) & ~(size_t)15;
+    A.dict_pool.resize_discard(pool_bytes + 64);
+    placed.clear();
+    uint32_t at = 0;
+    for (uint32_t i = 0; i < g.n; ++i) {
+      const uint32_t D = A.dict_bytes[i], lead = (0u - D) & 15u;
+      const auto slot = placed.emplace(std::make_pair(dicts[first + i], dict_sizes[first + i]), at + lead);
+      if (slot.second) {
+        memset(A.dict_pool.data() + at, 0, lead);
+        memcpy(A.dict_pool.data() + at + lead, dicts[first + i], D);
+        at += lead + D;
+      }
+      A.dict_off[i] = slot.first->second;
+    }
+    memset(A.dict_pool.data() + at, 0, 64);
+    uint8_t* pool_dev = g.mem.uninit<uint8_t>(pool_bytes + 64);
+    dev_h2d_bulk(pool_dev, A.dict_pool.data(), pool_bytes + 64);
+    uint32_t* dict_off_dev = g.mem.uninit<uint32_t>((size_t)g.n * 4);
+    dev_h2d(dict_off_dev, A.dict_off.data(), (size_t)g.n * 4);
+    uint32_t* dict_bytes_dev = g.mem.uninit<uint32_t>((size_t)g.n * 4);
+    dev_h2d(dict_bytes_dev, A.dict_bytes.data(), (size_t)g.n * 4);
+    uint32_t* starts_dev = g.mem.uninit<uint32_t>((size_t)g.n * 4);
+    dev_h2d(starts_dev, A.starts.data(), (size_t)g.n * 4);
+    uint8_t* text = g.mem.zeroed<uint8_t>(g.padded + 64);
+    lz77_batch_dicts_text(pool_dev, dict_off_dev, dict_bytes_dev, g.uploaded, starts_dev, g.items_dev, g.n, text);
+
+    BatchParseJob J = GreedyJob(p, P, g, text);
+    J.records = g.mem.uninit<BatchRecord>((size_t)g.n * sizeof(BatchRecord));
+    J.item_dict_bytes = dict_bytes_dev;
+    lz77_batch_parse_dicts(J);
+    FinishOneBlockItems(p, J, g, streams, reference_fails);
+    first = g.last;
+  }
+}
+
 }  // namespace
+
+void BatchGreedyCompressWithDictionaries(const EncoderParams& user, size_t count, const uint8_t* const* dicts, const size_t* dict_sizes,
+                                         const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
+                                         std::vector<uint8_t>* reference_fails, uint32_t* groups) {
+  CompressGroupsWithDictionaries(DictionaryItemParams(user, count ? sizes[0] : 0), count, dicts, dict_sizes, inputs, sizes, streams, reference_fails,
+                                 groups);
+}
 
 void BatchGreedyCompress(const EncoderParams& user, size_t count, const uint8_t* const* inputs, const size_t* sizes,
                          std::vector<std::vector<uint8_t>>* streams, uint32_t* groups) {

@@ -55,11 +55,23 @@ BR_DEV void br_batch_item_tables(const BatchParseJob& J, const Lz77Params& P, co
 
 // T: the job's tables with text / keys / flags / cmds still pointing at the group's arrays.
 // kDict: the item's text starts with J.dict.bytes bytes of custom dictionary (BrotliMi355xCompressBatchWithDictionary).
-template <bool kRows, bool kDict = false>
+// kDicts (with kDict): a dictionary per item (BrotliMi355xCompressBatchWithDictionaries) -- the item's text starts with
+// J.item_dict_bytes[index] bytes of its own dictionary, J.dict is not looked at and the chain files the dictionary itself.  A
+// parameter of the template, not a test of J.item_dict_bytes, so that the instances of the other calls stay what they were.
+//
+// The table under kDicts is reused by the next item of its wavefront with only its counters emptied (br_live_reset), and that item's
+// dictionary may be shorter or longer than the one in front -- 2 bytes behind 65 536, say.  Nothing the item in front left can be
+// reached, by the argument above br_batch_replay_dictionary and br_batch_item_h9: a walk over a key reads the min(counter, depth)
+// slots in front of the key's counter and nothing else; every counter is 0 after the reset, and every filing -- the dictionary's
+// by br_live_store, the three stitched positions, the chain's own -- writes its slot before it moves the counter on by one.  So
+// every slot in reach was written by THIS item, whatever the length of its dictionary or of the one before.  (A key filed 65 536
+// times wraps its u16 counter to 0 with the whole ring written by this item: br_batch_item_h9.  Dictionary + item stay below that.)
+template <bool kRows, bool kDict = false, bool kDicts = false>
 BR_DEV void br_batch_item(const BatchParseJob& J, const ChainTables& T, ChainScratchT<false, kRows>& s, uint32_t* histo /* 256 words */,
                           uint32_t index, uint32_t table) {
+  static_assert(kDict || !kDicts, "a dictionary per item is a dictionary");
   const BatchItem it = br_batch_load_item(J.items, index);
-  const uint32_t D = kDict ? BR_UNIFORM(J.dict.bytes) : 0u;
+  const uint32_t D = kDicts ? BR_UNIFORM(J.item_dict_bytes[index]) : (kDict ? BR_UNIFORM(J.dict.bytes) : 0u);
   Lz77Params P = J.P;
   P.total_bytes = D + it.bytes;
   if constexpr (kDict) P.prefix_bytes = P.dict_break = D;
@@ -70,10 +82,11 @@ BR_DEV void br_batch_item(const BatchParseJob& J, const ChainTables& T, ChainScr
   if constexpr (kDict) {
     // the hasher as HasherPrependCustomDictionary left it, then StitchToPreviousBlock of the first block (mod.rs:210-222): the
     // last three dictionary positions, whose four bytes reach into the item
-    if (J.dict.entries != nullptr) {
+    if (!kDicts && J.dict.entries != nullptr) {
       br_batch_replay_dictionary(lr, J.dict, P.bucket_bits);
     } else {
-      // (the A/B of DESIGN.md section 10, BROTLI_MI355X_BATCH_DICT_SELF_FILE: every chain files the dictionary itself)
+      // (the A/B of DESIGN.md section 10, BROTLI_MI355X_BATCH_DICT_SELF_FILE, and every item of kDicts: the chain files the
+      // dictionary itself, wave-wide, in the reference's order)
       br_live_reset(lr, P.bucket_bits);
       if (D > P.htl - 1) br_live_store(lr, 0, 1, D - (P.htl - 1), 1, 0);
     }

@@ -51,6 +51,19 @@ void lz77_batch_parse(const BatchParseJob& J) {
   *J.counter = J.n_items;
 }
 
+// a dictionary per item: the same plan, every chain filing its own dictionary
+void lz77_batch_parse_dicts(const BatchParseJob& J) {
+  if (J.n_items == 0) return;
+  if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
+  if (J.item_dict_bytes == nullptr) throw std::runtime_error("brotli_mi355x: a batch group without its dictionary sizes");
+  if (J.P.block_bits > 7) throw std::runtime_error("brotli_mi355x: the batch chains do not run the 512-deep rings");
+  const ChainTables T = EmuBatchChainTables(J);
+  static thread_local ChainScratchT<false, false> scratch;
+  uint32_t histo[256];
+  for (uint32_t place = 0; place < J.n_items; ++place) br_batch_item<false, true, true>(J, T, scratch, histo, J.order[place], place % J.tables);
+  *J.counter = J.n_items;
+}
+
 // qualities 9 and 10: the same plan on the H9 item code and its own scratch (the 256-deep rings' candidates)
 void lz77_batch_parse_h9(const BatchParseJob& J) {
   if (J.n_items == 0) return;
@@ -91,6 +104,17 @@ void lz77_batch_dict_text(const uint8_t* dict, uint32_t dict_bytes, const uint8_
                           uint32_t n_items, uint8_t* text) {
   for (uint32_t i = 0; i < n_items; ++i) {
     memcpy(text + items[i].text_off - dict_bytes, dict + ((0u - dict_bytes) & 15u), dict_bytes);
+    memcpy(text + items[i].text_off, packed + starts[i], items[i].bytes);
+  }
+}
+
+void lz77_batch_dicts_text(const uint8_t* pool, const uint32_t* dict_off, const uint32_t* dict_bytes, const uint8_t* packed,
+                           const uint32_t* starts, const BatchItem* items, uint32_t n_items, uint8_t* text) {
+  for (uint32_t i = 0; i < n_items; ++i) {
+    // whole 16-byte words, as the kernel moves them: the dictionary's own zero lead comes along
+    const uint32_t words = (dict_bytes[i] + 15u) >> 4;
+    if (items[i].text_off < 16u * words || dict_off[i] + dict_bytes[i] < 16u * words) throw std::runtime_error("brotli_mi355x: a batch item without room for its dictionary");
+    memcpy(text + items[i].text_off - 16u * words, pool + (dict_off[i] + dict_bytes[i] - 16u * words), 16u * words);
     memcpy(text + items[i].text_off, packed + starts[i], items[i].bytes);
   }
 }

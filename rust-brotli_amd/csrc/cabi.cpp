@@ -1328,6 +1328,122 @@ int32_t BrotliMi355xCompressBatchWithDictionaryEx(int quality, int lgwin, Brotli
                                      outputs, output_sizes, item_results);
 }
 
+int32_t BrotliMi355xCompressBatchWithDictionaries(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t num_dicts,
+                                                  const uint8_t* const* dicts, const size_t* dict_sizes, size_t count, const size_t* item_dicts,
+                                                  const uint8_t* const* inputs, const size_t* input_sizes, uint8_t* const* outputs,
+                                                  size_t* output_sizes, int32_t* item_results) {
+  const char* entry = "BrotliMi355xCompressBatchWithDictionaries";
+  uint64_t info[8] = {count, 0, 0, 0, 0, 0, 0, 0};
+  memcpy(g_batch_info, info, sizeof(info));
+  // what fails the call as a whole before any work is done, like an unknown route of BrotliMi355xCompressBatchEx
+  std::string refused;
+  if (routes != 0) {
+    refused = "routes " + std::to_string(routes) + " names a route this call does not know (this build knows none behind a dictionary per item)";
+  } else if (item_dicts == nullptr && num_dicts != count) {
+    refused = "item_dicts is NULL (item i takes dicts[i]) but num_dicts, " + std::to_string(num_dicts) + ", is not count, " + std::to_string(count);
+  } else if (item_dicts != nullptr) {
+    for (size_t i = 0; i < count && refused.empty(); ++i)
+      if (item_dicts[i] >= num_dicts)
+        refused = "item " + std::to_string(i) + " names dictionary " + std::to_string(item_dicts[i]) + " of " + std::to_string(num_dicts);
+  }
+  if (!refused.empty()) {
+    SetError(entry, refused.c_str());
+    for (size_t i = 0; i < count; ++i) output_sizes[i] = 0;
+    if (item_results && count) memset(item_results, 0, count * sizeof(int32_t));
+    return 0;
+  }
+  if (count == 0) return 1;
+  // one index named by every item: the shared-dictionary call, whose chains replay one image instead of filing the dictionary
+  {
+    const size_t k0 = item_dicts ? item_dicts[0] : 0;
+    bool one = item_dicts != nullptr || count == 1;
+    for (size_t i = 1; i < count && one; ++i) one = item_dicts[i] == k0;
+    if (one)
+      return CompressBatchWithDictionary(entry, quality, lgwin, mode, 0, dict_sizes[k0], dicts[k0], count, inputs, input_sizes, outputs, output_sizes,
+                                         item_results);
+  }
+  size_t total = 0;
+  for (size_t i = 0; i < count; ++i) total += input_sizes[i];
+  std::vector<int32_t> results(count, 0);
+  try {
+    EncoderParams params;
+    SetParameter(&params, kParamQuality, (uint32_t)quality);
+    SetParameter(&params, kParamLgwin, (uint32_t)lgwin);
+    SetParameter(&params, kParamMode, (uint32_t)mode);
+    // set_custom_dictionary (encode.rs:1196-1270), per dictionary, as in CompressBatchWithDictionary: info[5] sums the bytes in
+    // use over the distinct indices that an item names
+    EncoderParams fin = params;
+    FinalizeParams(&fin);
+    const auto in_use = [&](size_t k) -> size_t {
+      return dict_sizes[k] > 1 && fin.quality != 0 && fin.quality != 1 ? std::min(dict_sizes[k], ((size_t)1 << fin.lgwin) - 16) : 0;
+    };
+    {
+      std::vector<uint8_t> named(num_dicts, 0);
+      for (size_t i = 0; i < count; ++i) {
+        const size_t k = item_dicts ? item_dicts[i] : i;
+        if (!named[k]) info[5] += in_use(k);
+        named[k] = 1;
+      }
+    }
+    SmallCallGate gate(total);
+    // Side by side: the items of 1 .. 65536 bytes at qualities 5 .. 8, lgwin 17 .. 24, behind a dictionary of 2 .. 65536 bytes in
+    // use (batch_greedy.h: a chain per item that files the item's dictionary itself).  Every other item goes through the stream
+    // path by itself with its own dictionary, on this thread, in the caller's order.
+    std::vector<size_t> item, in_size, d_size;
+    std::vector<const uint8_t*> in, d;
+    for (size_t i = 0; i < count; ++i) {
+      const size_t k = item_dicts ? item_dicts[i] : i;
+      if (BatchDictionaryEligible(params, dict_sizes[k], input_sizes[i])) {
+        const size_t use = in_use(k);  // (dict_sizes[k] itself: an eligible dictionary is below every window's limit)
+        item.push_back(i);
+        in.push_back(inputs[i]);
+        in_size.push_back(input_sizes[i]);
+        d.push_back(dicts[k] + (dict_sizes[k] - use));
+        d_size.push_back(use);
+        continue;
+      }
+      results[i] = CompressItemWithDictionary(quality, lgwin, mode, dict_sizes[k], dicts[k], input_sizes[i], inputs[i], &output_sizes[i], outputs[i]);
+      ++info[2];
+    }
+    if (!item.empty()) {
+      std::vector<std::vector<uint8_t>> streams;
+      std::vector<uint8_t> reference_fails;
+      uint32_t groups = 0;
+      BatchGreedyCompressWithDictionaries(params, item.size(), d.data(), d_size.data(), in.data(), in_size.data(), &streams, &reference_fails, &groups);
+      info[4] = groups;
+      info[1] = item.size();
+      for (size_t n = 0; n < item.size(); ++n) {
+        const size_t i = item[n];
+        const size_t capacity = output_sizes[i];
+        output_sizes[i] = 0;
+        if (reference_fails[n]) {
+          SetError(entry,
+                   ("item " + std::to_string(i) + ": the reference encoder fails on this input: a match cut to one byte at the end of the custom dictionary "
+                    "gives a copy it cannot encode (fix_unbroken_len, backward_references/mod.rs:42-54; GetCopyLengthCode, command.rs:91-93)").c_str());
+          continue;
+        }
+        if (streams[n].size() > capacity) continue;  // (no fallback to a stored stream: the stream API has none)
+        memcpy(outputs[i], streams[n].data(), streams[n].size());
+        output_sizes[i] = streams[n].size();
+        results[i] = 1;
+      }
+    }
+  } catch (const std::exception& e) {
+    // a device error fails the call as a whole
+    SetError(entry, e.what());
+    for (size_t i = 0; i < count; ++i) output_sizes[i] = 0;
+    if (item_results) memset(item_results, 0, count * sizeof(int32_t));
+    return 0;
+  }
+  memcpy(g_batch_info, info, sizeof(info));
+  int32_t all = 1;
+  for (size_t i = 0; i < count; ++i) {
+    if (item_results) item_results[i] = results[i];
+    if (!results[i]) all = 0;
+  }
+  return all;
+}
+
 void BrotliMi355xLastBatchInfo(uint64_t info[8]) { memcpy(info, g_batch_info, sizeof(g_batch_info)); }
 
 int32_t BrotliEncoderCompressMulti(size_t num_params, const BrotliEncoderParameter* param_keys, const uint32_t* param_values,

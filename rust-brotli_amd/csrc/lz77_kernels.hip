@@ -2665,6 +2665,33 @@ void lz77_batch_dict_text(const uint8_t* dict_dev, uint32_t dict_bytes, const ui
   HIP_CHECK(hipGetLastError());
 }
 
+// A dictionary per item (BrotliMi355xCompressBatchWithDictionaries).  One workgroup per item: dictionary i | item i.  Every dictionary
+// of the pool ends on a 16-byte boundary behind (-bytes & 15) zero bytes of its own, as the shared one does, so whole words move and
+// the bytes in front of the dictionary's first stay zero.  (One lane per item would not do: a copy is up to 128 KiB.)
+__global__ __launch_bounds__(256) void k_batch_dicts_text(const uint8_t* __restrict__ pool, const uint32_t* __restrict__ dict_off,
+                                                           const uint32_t* __restrict__ dict_bytes, const uint8_t* __restrict__ packed,
+                                                           const uint32_t* __restrict__ starts, const BatchItem* __restrict__ items, uint32_t n_items,
+                                                           uint8_t* __restrict__ text) {
+  const uint32_t i = blockIdx.x;
+  if (i >= n_items) return;
+  const BatchItem it = items[i];
+  const uint32_t D = dict_bytes[i];
+  const uint32_t words = (D + 15u) >> 4;
+  if (it.text_off < 16u * words || dict_off[i] + D < 16u * words) return;  // (never: the plan leaves the room, the pool the lead)
+  const uint4* __restrict__ src = (const uint4*)(pool + (dict_off[i] + D - 16u * words));
+  uint4* __restrict__ dst = (uint4*)(text + it.text_off - 16u * words);
+  for (uint32_t w = threadIdx.x; w < words; w += blockDim.x) dst[w] = src[w];
+  batch_copy_to_aligned(text + it.text_off, packed + starts[i], it.bytes);
+}
+
+void lz77_batch_dicts_text(const uint8_t* pool_dev, const uint32_t* dict_off_dev, const uint32_t* dict_bytes_dev, const uint8_t* packed_dev,
+                           const uint32_t* starts_dev, const BatchItem* items_dev, uint32_t n_items, uint8_t* text) {
+  if (n_items == 0) return;
+  hipLaunchKernelGGL(k_batch_dicts_text, dim3(n_items), dim3(256), 0, BR_STREAM, pool_dev, dict_off_dev, dict_bytes_dev, packed_dev, starts_dev,
+                     items_dev, n_items, text);
+  HIP_CHECK(hipGetLastError());
+}
+
 // HasherPrependCustomDictionary on a scratch table: one wavefront files the positions in the reference's order (br_live_store)
 __global__ __launch_bounds__(64) void k_batch_dict_file(LiveRing lr, uint32_t bucket_bits, uint32_t count) {
   br_live_reset(lr, bucket_bits);
@@ -2712,6 +2739,35 @@ void lz77_batch_parse(const BatchParseJob& J) {
   const auto kernel = J.dict.bytes != 0 ? (rows ? k_parse_batch<true, true> : k_parse_batch<false, true>)
                                         : (rows ? k_parse_batch<true, false> : k_parse_batch<false, false>);
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), 0, BR_STREAM, J, T);
+  HIP_CHECK(hipGetLastError());
+}
+
+// k_parse_batch's launch shape for items behind a dictionary of their own (J.item_dict_bytes): a sibling of k_parse_batch, so that
+// its instances stay what they were.  Every chain files its dictionary itself: there is no image to share.
+template <bool kRows>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_parse_batch_dicts(BatchParseJob J, ChainTables T) {
+  __shared__ ChainScratchT<false, kRows> scratch;
+  __shared__ uint32_t histo[256];
+  const uint32_t table = blockIdx.x;
+  if (table >= J.tables) return;
+  for (;;) {
+    uint32_t mine = 0;
+    if (threadIdx.x == 0) mine = atomicAdd(J.counter, 1u);
+    const uint32_t place = BR_UNIFORM(mine);
+    if (place >= J.n_items) break;
+    const uint32_t index = BR_UNIFORM(J.order[place]);
+    if (index >= J.n_items) break;  // (never: the plan's order is a permutation)
+    br_batch_item<kRows, true, true>(J, T, scratch, histo, index, table);
+  }
+}
+
+void lz77_batch_parse_dicts(const BatchParseJob& J) {
+  if (J.n_items == 0) return;
+  if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
+  if (J.item_dict_bytes == nullptr) throw std::runtime_error("brotli_mi355x: a batch group without its dictionary sizes");
+  const ChainTables T = batch_chain_tables(J);
+  const uint32_t grid = J.tables < J.n_items ? J.tables : J.n_items;
+  hipLaunchKernelGGL(batch_chain_rows(J.P) ? k_parse_batch_dicts<true> : k_parse_batch_dicts<false>, dim3(grid), dim3(64), 0, BR_STREAM, J, T);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -62,6 +62,15 @@ With --same-call (and any of the above) the parent's library is measured through
 and dictionary included, alternating with it --rounds times: the A/B of a change that keeps the routes.  Per class the result holds the
 medians of both, their difference, and the parent's own spread between its rounds as the margin; nothing else is measured.
 
+With --dicts (and --qualities 5,8) the call measured is BrotliMi355xCompressBatchWithDictionaries, a custom dictionary per item: text items,
+and per item a dictionary that is another draw from the items' own source (DICTS_CLASSES: 4096 items of 4 KiB behind 4 and 16 KiB, 1024 of
+16 KiB behind 16 and 64 KiB, 64 of 4 KiB behind 16 KiB).  It is measured against the only way the parent commit has -- the loop of stream
+calls with BrotliEncoderSetCustomDictionary, each item with its own dictionary, on the calling thread and from four threads (--parent-lib, or
+this build's library: the loop is the same code), on the first --loop-items items, scaled by item count -- against the oracle's dictionary
+stream on one core, and against the shared-dictionary call on the same items: for that ONE dictionary is given as `count` distinct
+indices (the chains file it themselves) and to BrotliMi355xCompressBatchWithDictionary (the chains replay its image), which prices
+self-filing against the image.
+
 Every measurement runs in a child process of its own (the table's home is one setting per process, read once; the parent's library
 is another shared object), one after the other, each under its own time limit; the first failure ends the probe.
 
@@ -121,6 +130,9 @@ DICT_QUICK_HEADLINE = ["4096x4KiB", "4096x512B", "1024x16KiB", "64x4KiB"]  # (--
 DICT_QUICK_QUALITIES = {"1024x16KiB": (2, 3)}  # (one input block at quality 2 and 3)
 QUICK_HEADLINE = ["4096x4KiB", "4096x16KiB", "1024x64KiB", "4096x512B", "4096xlog200B-256KiB"]  # (--quick-items)
 ZOPFLI_HEADLINE = ["1024x4KiB", "256x16KiB", "64x64KiB", "16x4KiB"]  # (--zopfli-items)
+# (--dicts) class -> (items, item bytes, dictionary bytes per item)
+DICTS_CLASSES = {"4096x4KiB+4KiB": (4096, 4 << 10, 4 << 10), "4096x4KiB+16KiB": (4096, 4 << 10, 16 << 10), "1024x16KiB+16KiB": (1024, 16 << 10, 16 << 10),
+                 "1024x16KiB+64KiB": (1024, 16 << 10, 64 << 10), "64x4KiB+16KiB": (64, 4 << 10, 16 << 10)}
 Q9_HEADLINE = ["4096x4KiB", "1024x16KiB", "256x64KiB", "64x256KiB", "16x4KiB", "64x4KiB", "4096xlog200B-256KiB"]  # (--q9-items)
 
 
@@ -145,6 +157,21 @@ def dictionary_of(data, nbytes):
     pool = synth.markov_text(8 << 20, 5) if data == "text" else synth.mixed(8 << 20, 5)
     off = random.Random(18).randrange(0, len(pool) - nbytes)
     return pool[off:off + nbytes]
+
+
+def dicts_of(name):
+    """(items, a dictionary per item): text, the dictionaries further draws from the items' source"""
+    import synth
+    count, size, dict_bytes = DICTS_CLASSES[name]
+    pool = synth.markov_text(8 << 20, 5)
+    rng = random.Random(19)
+    items, dictionaries = [], []
+    for _ in range(count):
+        off = rng.randrange(0, len(pool) - size)
+        items.append(pool[off:off + size])
+        off = rng.randrange(0, len(pool) - dict_bytes)
+        dictionaries.append(pool[off:off + dict_bytes])
+    return items, dictionaries
 
 
 def stats(times):
@@ -212,7 +239,47 @@ def measure_batch(lib_path, items, quality, runs, warmup, dictionary=None, route
     return times, sum(out_sizes), list(info), failed
 
 
-def measure_loop(lib_path, items, quality, threads, runs, warmup, dictionary=None):
+def measure_dicts(lib_path, items, dictionaries, quality, runs, warmup, shared=False):
+    """BrotliMi355xCompressBatchWithDictionaries with dictionaries[i] for item i; shared: BrotliMi355xCompressBatchWithDictionary with
+    dictionaries[0]"""
+    L = bind(lib_path)
+    L.BrotliMi355xCompressBatchWithDictionaries.restype = ctypes.c_int32
+    L.BrotliMi355xCompressBatchWithDictionary.restype = ctypes.c_int32
+    L.BrotliMi355xLastError.restype = ctypes.c_char_p
+    n = len(items)
+    caps = [L.BrotliEncoderMaxCompressedSize(len(x)) + 1024 for x in items]
+    bufs = [ctypes.create_string_buffer(c) for c in caps]
+    inputs = (ctypes.c_char_p * n)(*items)
+    in_sizes = (ctypes.c_size_t * n)(*[len(x) for x in items])
+    outputs = (ctypes.c_void_p * n)(*[ctypes.addressof(b) for b in bufs])
+    out_sizes = (ctypes.c_size_t * n)()
+    results = (ctypes.c_int32 * n)()
+    dicts = (ctypes.c_char_p * n)(*dictionaries)
+    dict_sizes = (ctypes.c_size_t * n)(*[len(d) for d in dictionaries])
+    info = (ctypes.c_uint64 * 8)()
+    times, failed = [], []
+    for it in range(warmup + runs):
+        for i in range(n):
+            out_sizes[i] = caps[i]
+        t = time.perf_counter()
+        if shared:
+            ok = L.BrotliMi355xCompressBatchWithDictionary(quality, LGWIN, 0, ctypes.c_size_t(len(dictionaries[0])), ctypes.c_char_p(dictionaries[0]), ctypes.c_size_t(n),
+                                                           inputs, in_sizes, outputs, out_sizes, results)
+        else:
+            ok = L.BrotliMi355xCompressBatchWithDictionaries(quality, LGWIN, 0, ctypes.c_uint32(0), ctypes.c_size_t(n), dicts, dict_sizes, ctypes.c_size_t(n), None,
+                                                             inputs, in_sizes, outputs, out_sizes, results)
+        dt = time.perf_counter() - t
+        if ok != 1:
+            # items on which the reference itself fails (a copy of one byte at the dictionary end) fail alone: counted, not fatal
+            failed = [i for i in range(n) if not results[i]]
+            assert 0 < len(failed) <= n // 64 + 1 and b"reference encoder fails" in L.BrotliMi355xLastError(), (failed, L.BrotliMi355xLastError())
+        if it >= warmup:
+            times.append(dt)
+    L.BrotliMi355xLastBatchInfo(info)
+    return times, sum(out_sizes), list(info), failed
+
+
+def measure_loop(lib_path, items, quality, threads, runs, warmup, dictionary=None, dictionaries=None):
     L = bind(lib_path)
     caps = [L.BrotliEncoderMaxCompressedSize(len(x)) + (16 if dictionary is None else 1024) for x in items]
     bufs = [ctypes.create_string_buffer(c) for c in caps]
@@ -231,7 +298,8 @@ def measure_loop(lib_path, items, quality, threads, runs, warmup, dictionary=Non
         s = L.BrotliEncoderCreateInstance(None, None, None)
         for k, v in ((0, 0), (1, quality), (2, LGWIN)):
             L.BrotliEncoderSetParameter(s, k, v)
-        L.BrotliEncoderSetCustomDictionary(s, len(dictionary), dictionary)
+        own = dictionaries[i] if dictionaries is not None else dictionary
+        L.BrotliEncoderSetCustomDictionary(s, len(own), own)
         avail_in, avail_out = ctypes.c_size_t(len(items[i])), ctypes.c_size_t(caps[i])
         next_in = ctypes.c_void_p(ctypes.cast(ctypes.c_char_p(items[i]), ctypes.c_void_p).value)
         next_out = ctypes.c_void_p(ctypes.addressof(bufs[i]))
@@ -247,7 +315,7 @@ def measure_loop(lib_path, items, quality, threads, runs, warmup, dictionary=Non
     def work(lo, hi):
         size = ctypes.c_size_t()
         for i in range(lo, hi):
-            if dictionary is not None:
+            if dictionary is not None or dictionaries is not None:
                 one_stream(i)
                 continue
             size.value = caps[i]
@@ -268,7 +336,7 @@ def measure_loop(lib_path, items, quality, threads, runs, warmup, dictionary=Non
     return times, sorted(failed)
 
 
-def measure_cpu(items, quality, runs, dictionary=None):
+def measure_cpu(items, quality, runs, dictionary=None, dictionaries=None):
     os.environ["ORC_FAST"] = "1"
     import orc
     times = []
@@ -276,12 +344,13 @@ def measure_cpu(items, quality, runs, dictionary=None):
     for it in range(1 + runs):
         total = 0
         t = time.perf_counter()
-        for x in items:
-            if dictionary is None:
+        for i, x in enumerate(items):
+            if dictionary is None and dictionaries is None:
                 total += len(orc.compress(x, quality, LGWIN))
                 continue
             try:
-                total += sum(map(len, orc.stream_with_flushes(x, [(0, 0), (1, quality), (2, LGWIN)], [], dictionary=dictionary)))
+                total += sum(map(len, orc.stream_with_flushes(x, [(0, 0), (1, quality), (2, LGWIN)], [],
+                                                              dictionary=dictionaries[i] if dictionaries is not None else dictionary)))
             except orc.ReferencePanics:
                 pass  # (the reference fails on this item: the library fails it alone)
         dt = time.perf_counter() - t
@@ -290,7 +359,33 @@ def measure_cpu(items, quality, runs, dictionary=None):
     return times, total
 
 
+def child_dicts(args):
+    """--dicts: the children of main_dicts -- batch (own dictionaries), same (one dictionary as count indices), shared, loop, cpu"""
+    out = []
+    for name in args.classes.split(","):
+        items, dictionaries = dicts_of(name)
+        n = args.loop_items
+        for quality in [int(q) for q in args.qualities.split(",")]:
+            row = {"class": name, "data": "text", "quality": quality, "items": len(items), "bytes": sum(map(len, items)), "dictionary_bytes": len(dictionaries[0])}
+            if args.child in ("batch", "same", "shared"):
+                ds = dictionaries if args.child == "batch" else [dictionaries[0]] * len(items)
+                times, csize, info, failed = measure_dicts(args.lib, items, ds, quality, args.runs, args.warmup, shared=args.child == "shared")
+                row.update(stats(times), compressed_bytes=csize, batch_info=info, reference_fails_on_items=failed)
+            elif args.child == "loop":
+                times, failed = measure_loop(args.lib, items[:n], quality, args.threads, args.runs, 1, dictionaries=dictionaries[:n])
+                row.update(stats(times), threads=args.threads, measured_items=min(n, len(items)), reference_fails_on_items=failed)
+            else:
+                times, csize = measure_cpu(items[:n], quality, args.runs, dictionaries=dictionaries[:n])
+                row.update(stats(times), measured_items=min(n, len(items)), compressed_bytes=csize)
+            out.append(row)
+            print(json.dumps(row), flush=True)
+    with open(args.child_out, "w") as f:
+        json.dump(out, f)
+
+
 def child(args):
+    if args.dicts:
+        return child_dicts(args)
     out = []
     for name in args.classes.split(","):
         for data in (["text"] if CLASSES[name][0] == "alice" else ["text", "mixed"]):
@@ -333,6 +428,7 @@ def run_child(args, what, classes, lib=None, lds=None, threads=1, limit=600, fir
     cmd += (["--quick-long-items"] if quick_long_items else []) + (["--quick-long-classes"] if args.quick_long_items else [])
     cmd += ["--zopfli-items"] if zopfli_items else []
     cmd += ["--q9-items"] if q9_items else []
+    cmd += ["--dicts"] if args.dicts else []
     r = subprocess.run(cmd, env=env)
     if r.returncode != 0:
         raise SystemExit("batch_probe: %s (lds=%s, threads=%d) ended with status %d: nothing more is started" % (what, lds, threads, r.returncode))
@@ -468,6 +564,75 @@ def main_dictionary_quick(args, doc, save, classes):
     print(json.dumps(doc, indent=1))
 
 
+def main_dicts(args, doc, save, classes):
+    doc["what"] = ("BrotliMi355xCompressBatchWithDictionaries (a custom dictionary per item, every chain files its own) vs the loop of stream-API calls with "
+                   "BrotliEncoderSetCustomDictionary, each item with its own dictionary (1 and 4 threads, first --loop-items items scaled by item count) vs the "
+                   "oracle's dictionary stream on one CPU core; and, on the same items behind ONE dictionary, the call with that dictionary as `count` "
+                   "distinct indices (self-filing) vs BrotliMi355xCompressBatchWithDictionary (the shared image); text, lgwin 22")
+    rows = {}
+    short = ("median_ms", "min_ms", "max_ms", "spread_pct", "runs")
+    for rnd in range(args.rounds):
+        for what in ("batch", "same", "shared"):
+            for row in run_child(args, what, classes, limit=900):
+                v = rows.setdefault(key(row), {"items": row["items"], "bytes": row["bytes"], "dictionary_bytes": row["dictionary_bytes"]})
+                v.setdefault(what + "_rounds", []).append({k: row[k] for k in short})
+                if rnd == 0:
+                    v[what + "_info"] = row["batch_info"]
+                    v[what + "_compressed_bytes"] = row["compressed_bytes"]
+                    v[what + "_reference_fails_on_items"] = row["reference_fails_on_items"]
+            doc["classes"] = rows
+            save()
+        for threads in (1, 4):
+            if "loop" in args.skip.split(","):
+                continue
+            for row in run_child(args, "loop", classes, lib=os.path.abspath(args.parent_lib) if args.parent_lib else None, threads=threads, limit=900):
+                scale = row["items"] / row["measured_items"]
+                rows[key(row)].setdefault("loop_%dt_rounds" % threads, []).append(
+                    {"median_ms_scaled": round(row["median_ms"] * scale, 3), "min_ms_scaled": round(row["min_ms"] * scale, 3), "max_ms_scaled": round(row["max_ms"] * scale, 3),
+                     "spread_pct": row["spread_pct"], "measured_items": row["measured_items"]})
+            save()
+    for row in ([] if "cpu" in args.skip.split(",") else run_child(args, "cpu", classes, limit=900)):
+        scale = row["items"] / row["measured_items"]
+        rows[key(row)]["cpu_one_core"] = {"median_ms_scaled": round(row["median_ms"] * scale, 3), "measured_items": row["measured_items"], "spread_pct": row["spread_pct"]}
+    # the items the call failed alone, against the oracle on this host's CPU: its dictionary stream must fail on every one of them and
+    # on none of their neighbours (the loop and the CPU baseline run the first --loop-items items only)
+    os.environ["ORC_FAST"] = "1"
+    import orc
+    for k, v in rows.items():
+        flagged = v["batch_reference_fails_on_items"]
+        v["batch_reference_fails_on_items_verified"] = "none flagged"
+        if not flagged:
+            continue
+        items, dictionaries = dicts_of(k.split("/")[0])
+
+        def fails(i):
+            try:
+                orc.stream_with_flushes(items[i], [(0, 0), (1, int(k.split("/")[2][1:])), (2, LGWIN)], [], dictionary=dictionaries[i])
+            except orc.ReferencePanics:
+                return True
+            return False
+
+        neighbours = [i + 1 for i in flagged if i + 1 < len(items) and i + 1 not in flagged]
+        assert all(fails(i) for i in flagged), (k, "the batch call failed an item the oracle encodes")
+        assert not any(fails(i) for i in neighbours), (k, "the oracle fails on an item the batch call encoded")
+        v["batch_reference_fails_on_items_verified"] = "the oracle fails on all %d flagged items and on none of %d neighbours" % (len(flagged), len(neighbours))
+    for v in rows.values():
+        med = {w: statistics.median(r["median_ms"] for r in v[w + "_rounds"]) for w in ("batch", "same", "shared")}
+        v["batch_median_ms"], v["same_median_ms"], v["shared_median_ms"] = med["batch"], med["same"], med["shared"]
+        v["batch_MBps"] = round(v["bytes"] / 1e3 / med["batch"], 1)
+        v["self_filing_over_image"] = round(med["same"] / med["shared"], 3)
+        v["same_bytes_as_shared"] = bool(v["same_compressed_bytes"] == v["shared_compressed_bytes"])
+        v["cpu_over_batch"] = round(v["cpu_one_core"]["median_ms_scaled"] / med["batch"], 3) if "cpu_one_core" in v else "not measured"
+        for threads in (1, 4):
+            loop = v.get("loop_%dt_rounds" % threads)
+            v["loop_%dt_over_batch" % threads] = round(statistics.median(r["median_ms_scaled"] for r in loop) / med["batch"], 2) if loop else "not measured"
+        loops = [v[n] for n in ("loop_1t_rounds", "loop_4t_rounds") if v.get(n)]
+        if loops:
+            v["every_run_beats_every_loop_run"] = bool(max(r["max_ms"] for r in v["batch_rounds"]) < min(r["min_ms_scaled"] for rs in loops for r in rs))
+    save()
+    print(json.dumps(doc, indent=1))
+
+
 def main_same_call(args, doc, save, classes):
     """--same-call: this build and the parent's library through the very same call (route bits, dictionary), alternating, one child
     each -- for a change that keeps the routes and must not cost them anything.  Per class: the median of either build's round
@@ -516,6 +681,7 @@ def main():
     ap.add_argument("--quick-long-items", action="store_true", help="this build through routes QUICK_ITEMS | QUICK_LONG_ITEMS, the parent through QUICK_ITEMS (qualities 2,3,4 per class)")
     ap.add_argument("--zopfli-items", action="store_true", help="this build through BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS (--qualities 11)")
     ap.add_argument("--q9-items", action="store_true", help="this build through BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS (--qualities 9,10)")
+    ap.add_argument("--dicts", action="store_true", help="BrotliMi355xCompressBatchWithDictionaries: a dictionary per item (--qualities 5,8)")
     ap.add_argument("--same-call", action="store_true", help="the parent's library through the same call as this build, alternating --rounds times (needs --parent-lib)")
     ap.add_argument("--quick-long-classes", action="store_true", help="(child) only the qualities of QUICK_LONG_QUALITIES")
     ap.add_argument("--plain", action="store_true", help="(child) the plain call although a dictionary size is given")
@@ -553,6 +719,8 @@ def main():
     if args.q9_items:
         doc["what"] = ("BrotliMi355xCompressBatchEx(BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS) vs the parent commit's batch call, there one by one (on the first "
                        "--loop-items items, scaled by item count), and its 4-thread loop vs the oracle on one CPU core; lgwin 22")
+    if args.dicts:
+        return main_dicts(args, doc, save, [c for c in DICTS_CLASSES if not args.only or c in args.only.split(",")])
     if args.same_call:
         dict_classes = DICT_QUICK_HEADLINE if args.quick_items else ["4096x4KiB", "1024x64KiB"]
         return main_same_call(args, doc, save, [c for c in dict_classes if not args.only or c in args.only.split(",")] if args.dictionary else headline)
