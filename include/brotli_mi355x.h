@@ -363,10 +363,36 @@ int32_t BrotliMi355xCompressBatchWithDictionaryEx(int quality, int lgwin, Brotli
    and the call then returns 0; a device error fails the whole call.
    item_dicts == NULL: item i takes dicts[i], and num_dicts must be count.  Several items may name one index.  Dictionaries are
    told apart by index, not by content.  dicts[k] may be NULL when dict_sizes[k] is 0.  count == 0 returns 1.
-   An index >= num_dicts, item_dicts == NULL with num_dicts != count, or any bit in routes fails the whole call before any work is
-   done, as an unknown route fails BrotliMi355xCompressBatchEx (returns 0, every size 0, BrotliMi355xLastError says why, only
-   info[0] of BrotliMi355xLastBatchInfo is set).  routes is there for later builds to add routes (those of qualities 2 .. 4, say):
-   this build knows none, so a caller can probe.
+   An index >= num_dicts, item_dicts == NULL with num_dicts != count, or any bit in routes other than
+   BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS fails the whole call before any work is done, as an unknown route fails
+   BrotliMi355xCompressBatchEx (returns 0, every size 0, BrotliMi355xLastError says why, only info[0] of BrotliMi355xLastBatchInfo
+   is set).  routes == 0 is the call as described below in every respect.  The one route this call knows, so a caller can probe:
+   BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS (512; the bits of the other batch calls, 4 and 256 among them, stay unknown
+   here, and 512 stays unknown there): item i is still exactly the stream described above.  In addition to the items the call
+   takes side by side without it, an item of at most one input block at quality 2, 3 or 4 and lgwin 10 .. 24 -- 1 <=
+   input_sizes[i] <= 16 384 at quality 2 / 3 and <= 65 536 at quality 4 -- behind a dictionary of dict_sizes[k] >= 2 of which at
+   most 65 536 bytes are in use (the rule of BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS of BrotliMi355xCompressBatchWithDictionaryEx,
+   applied per item) runs on the device as ONE chain on a private BasicHasher table.  There is no table image per dictionary and
+   no device memory per dictionary beyond its bytes: in front of every item the chain zeroes its table and files the item's
+   dictionary itself, 64 positions per step with an atomic maximum (what the reference's prepend leaves in a slot is the largest
+   position filed under it), then parses the item.  Every other item -- the empty one, longer items, dict_sizes[k] <= 1, more than
+   65 536 bytes in use -- runs by itself through the stream path with its own dictionary.  The bit changes nothing at qualities 0,
+   1 and 5 .. 11.  Such items count in info[1], their groups in info[4]; info[2], info[5] as below; info[6] and info[7] stay 0.
+   When every item names one index the call is BrotliMi355xCompressBatchWithDictionaryEx with
+   BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS and that dictionary (same bytes, same info, the shared image).  As there, at quality 2 on
+   text behind a dictionary of the same kind a few in 1000 items are inputs the reference fails on: pass item_results.
+   When to set it: hundreds to thousands of small items at these qualities whose dictionaries differ.  Measured (text, lgwin 22,
+   every item behind a dictionary of its own; profiles/r21_batch_dictionaries_quick.json): 4096 items of 4 KiB behind 16 KiB each
+   at quality 2 / 3 / 4 in 24 .. 26 / 25 .. 27 / 31 .. 33 ms against 3.8 .. 5.4 s for the same call without the bit and 1.8 .. 2.4 s
+   for the loop of stream calls from four threads (one CPU core: 0.55 .. 0.63 s); 1024 items of 16 KiB behind 64 KiB each in 34 ..
+   45 ms against 1.0 .. 1.6 s; 1024 items of 64 KiB behind 64 KiB each at quality 4 in 146 .. 149 ms against 1.8 .. 1.9 s (5.3 x the
+   four threads, 6.1 x one core: the narrowest large shape); 4096 items of 512 bytes behind 16 KiB each in 12 .. 16 ms against
+   3.3 .. 4.2 s.  No measured shape loses to the call without the bit or to one CPU core.  When not: a call of a few items -- a
+   chain is one wavefront bound by its own dependent loads; 64 items of 4 KiB take 3.5 .. 4.9 ms, 18 x the call without the bit
+   but only 2.0 .. 2.4 x one CPU core, and fewer items gain less -- and items that share ONE dictionary, for which
+   BrotliMi355xCompressBatchWithDictionaryEx copies one image instead of filing the dictionary per item: self-filing is within
+   5 % of it where the item is at least as long as the dictionary, 1.13 .. 1.15 x slower for 4 KiB items behind 16 KiB, and
+   1.4 .. 1.6 x slower for 512-byte items behind 16 KiB.
    Side by side on the device: quality 5 .. 8, lgwin 17 .. 24, 2 <= D_i <= 65536 (the bytes of the item's dictionary in use) and
    1 <= input_sizes[i] <= 65536.  A group uploads its items and, once each, the dictionaries they name; the text
    dictionary | item is laid out on the device per item, and one chain per item files the dictionary into a private hash table and
@@ -381,12 +407,14 @@ int32_t BrotliMi355xCompressBatchWithDictionaryEx(int quality, int lgwin, Brotli
    When to use it: hundreds to thousands of small items in a call whose dictionaries differ.  When not: items that all share
    one dictionary (BrotliMi355xCompressBatchWithDictionary: its chains replay one image instead of filing 64 KiB each), and calls of
    a few items -- a chain is one wavefront bound by its own dependent loads.  Measured (text, lgwin 22, every
-   item behind a dictionary of its own; profiles/r20_batch_dictionaries.json): 4096 items of 4 KiB behind 16 KiB each at quality 5
+   item behind a dictionary of its own, qualities 5 .. 8; profiles/r20_batch_dictionaries.json): 4096 items of 4 KiB behind 16 KiB each at quality 5
    in 26 ms against 5.6 s for the loop of stream calls and 2.4 s from four threads (one CPU core: 0.80 s), at quality 8 in 63 ms;
    1024 items of 16 KiB behind 64 KiB each in 39 / 68 ms at quality 5 / 8 against 1.4 / 1.7 s (four threads 0.64 / 0.68 s); 64 items
    of 4 KiB behind 16 KiB each in 4.7 / 6.1 ms against 88 / 97 ms -- and only 2.7 / 3.6 x one CPU core.  No measured shape loses to
    the loop or to one core.  Against the shared image, on the same items behind ONE dictionary given as count indices: level at
    4 KiB of dictionary, 1.14 .. 1.22 x slower at 16 KiB with 4 KiB items, 1.20 x at 64 KiB with 16 KiB items. */
+/* known to BrotliMi355xCompressBatchWithDictionaries only; 4u and 256u stay unknown routes of this call */
+#define BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS 512u
 int32_t BrotliMi355xCompressBatchWithDictionaries(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t num_dicts,
                                                   const uint8_t* const* dicts, const size_t* dict_sizes, size_t count,
                                                   const size_t* item_dicts /* may be NULL */, const uint8_t* const* inputs,

@@ -189,6 +189,7 @@ class Library(object):
     BATCH_ROUTE_QUICK_LONG_ITEMS = 16  # BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS (8 is reserved)
     BATCH_ROUTE_ZOPFLI_ITEMS = 32  # BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS
     BATCH_ROUTE_Q9_ITEMS = 128  # BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS (64 is reserved)
+    BATCH_ROUTE_QUICK_DICTIONARY_ITEMS = 512  # BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS (compress_batch_with_dictionaries only)
 
     def compress_batch(self, items, quality=0, lgwin=22, mode=0, dictionary=None, long_items=False, quick_items=False, quick_long_items=False,
                        zopfli_items=False, q9_items=False):
@@ -325,7 +326,7 @@ class Library(object):
 
         return self._batch(items, 1024, call)
 
-    def compress_batch_with_dictionaries(self, items, dictionaries, item_dictionaries=None, quality=5, lgwin=22, mode=0):
+    def compress_batch_with_dictionaries(self, items, dictionaries, item_dictionaries=None, quality=5, lgwin=22, mode=0, quick_items=False):
         """BrotliMi355xCompressBatchWithDictionaries: item i is the stream of an Encoder(params, dictionaries[k]) with
         k = item_dictionaries[i] that gets the item in one finish(); a decoder needs that dictionary.  item_dictionaries=None:
         item i takes dictionaries[i], and there must be as many dictionaries as items.  Several items may name one index.
@@ -339,8 +340,26 @@ class Library(object):
         in 26 ms against 5.6 s for the loop of stream calls, 64 of them in 4.7 ms against 88 ms); items that share one dictionary
         are up to 1.2 x faster through compress_batch_with_dictionary, whose chains replay one image of the dictionary.
 
+        quick_items=False: side by side at qualities 5 to 8 only.
+
+        quick_items=True: BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS -- at qualities 2 to 4 and lgwin 10 to 24 the items of
+        at most one input block (16 384 bytes at quality 2 and 3, 65 536 at quality 4) behind a dictionary of at least 2 bytes, of
+        which at most 65 536 are in use, run side by side too: one chain each on a private hash table that the chain zeroes and
+        into which it files its item's dictionary itself (the same bytes).  Without it these qualities run item by item; longer
+        items, the empty item and dictionaries of 0 or 1 bytes still do.  It changes nothing at the other qualities.  When every
+        item names the same index the call is compress_batch_with_dictionary(items, that dictionary, quick_items=True).
+
+        Items the reference itself fails on: behind a dictionary a match cut to one byte at the dictionary's end is a copy the
+        reference cannot encode, and its stream call fails.  Such an item fails alone in the C call, which then returns 0 -- and
+        this method raises BrotliCompressorException although every other stream was produced.  It is not rare at quality 2 on
+        text behind a dictionary of the same kind: about 3 in 1000 items of 4 KiB in the measured runs, so
+        a call of thousands of such items is expected to raise.  The exception carries .failed (their indices) and .streams (the
+        streams of the others, None for a failed item): catch it, and send the failed items through another quality or without
+        the dictionary.
+
         Raises BrotliCompressorException like compress_batch_with_dictionary (.failed, .streams), also for an index out of range
         and for a dictionary count that does not match -- both fail the whole call."""
+        routes = self.BATCH_ROUTE_QUICK_DICTIONARY_ITEMS if quick_items else 0
         items = list(items)
         dictionaries = [bytes(d) for d in dictionaries]
         num = len(dictionaries)
@@ -358,16 +377,17 @@ class Library(object):
 
         def call(count, inputs, in_sizes, outputs, out_sizes, results):
             return "BrotliMi355xCompressBatchWithDictionaries", self.lib.BrotliMi355xCompressBatchWithDictionaries(
-                quality, lgwin, mode, 0, num, dicts, dict_sizes, count, item_dicts, inputs, in_sizes, outputs, out_sizes, results)
+                quality, lgwin, mode, routes, num, dicts, dict_sizes, count, item_dicts, inputs, in_sizes, outputs, out_sizes, results)
 
         return self._batch(items, 1024, call)
 
     def last_batch_info(self):
-        """BrotliMi355xLastBatchInfo: the last compress_batch / compress_batch_with_dictionary call of this thread as a list of 8 integers -- [0] items, [1] items
+        """BrotliMi355xLastBatchInfo: the last compress_batch / compress_batch_with_dictionary / compress_batch_with_dictionaries call of this thread as a list of 8 integers -- [0] items, [1] items
         encoded side by side on the device, [2] items run one by one, [3] items answered without an encoder, [4] device groups, [5] dictionary bytes in use (0 without one; with a dictionary per item their sum over the indices named),
         [6] items that began side by side and were redone one by one (counted in [2]), [7] of the items in [1], those longer than one
         input block ([6] and [7]: long_items=True and quick_long_items=True only; the items quick_items=True, zopfli_items=True and
-        q9_items=True take side by side count in [1] and [4])."""
+        q9_items=True take side by side count in [1] and [4], and so do those of compress_batch_with_dictionaries(...,
+        quick_items=True))."""
         info = (c_uint64 * 8)()
         self.lib.BrotliMi355xLastBatchInfo.restype = None
         self.lib.BrotliMi355xLastBatchInfo.argtypes = [POINTER(c_uint64)]

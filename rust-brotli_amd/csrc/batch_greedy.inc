@@ -469,11 +469,55 @@ void CompressGroups(const EncoderParams& p, const uint8_t* dict, uint32_t D, siz
   }
 }
 
+// A dictionary per item, one step for the routes of qualities 5 .. 8 and 2 .. 4: a group uploads, once each, the dictionaries its
+// items name -- a pool in which every dictionary ends on a 16-byte boundary behind zero bytes of its own (the dict_shifted
+// convention of lz77_batch_dict_text), with the place and the size of item i's dictionary beside it -- and lays out the padded
+// text, dictionary | item per item, on the device.  (The group's byte limit counts a dictionary per item, so the pool stays
+// below it.)  dicts[i] / dict_sizes[i]: the dictionary of the call's item i as in use; two items share one where pointer and
+// size agree.
+struct DictsText {
+  uint8_t* text;             // the group's padded text
+  uint32_t* dict_bytes_dev;  // [g.n]: A.dict_bytes on the device
+};
+DictsText StageDictsText(Group& g, const uint8_t* const* dicts, const size_t* dict_sizes) {
+  CallArrays& A = *g.A;
+  const size_t first = g.first;
+  std::map<std::pair<const uint8_t*, size_t>, uint32_t> placed;
+  A.dict_off.resize_discard(g.n);
+  size_t pool_bytes = 0;
+  for (uint32_t i = 0; i < g.n; ++i)
+    if (placed.emplace(std::make_pair(dicts[first + i], dict_sizes[first + i]), 0u).second) pool_bytes += (dict_sizes[first + i] + 15) & ~(size_t)15;
+  A.dict_pool.resize_discard(pool_bytes + 64);
+  placed.clear();
+  uint32_t at = 0;
+  for (uint32_t i = 0; i < g.n; ++i) {
+    const uint32_t D = A.dict_bytes[i], lead = (0u - D) & 15u;
+    const auto slot = placed.emplace(std::make_pair(dicts[first + i], dict_sizes[first + i]), at + lead);
+    if (slot.second) {
+      memset(A.dict_pool.data() + at, 0, lead);
+      memcpy(A.dict_pool.data() + at + lead, dicts[first + i], D);
+      at += lead + D;
+    }
+    A.dict_off[i] = slot.first->second;
+  }
+  memset(A.dict_pool.data() + at, 0, 64);
+  uint8_t* pool_dev = g.mem.uninit<uint8_t>(pool_bytes + 64);
+  dev_h2d_bulk(pool_dev, A.dict_pool.data(), pool_bytes + 64);
+  uint32_t* dict_off_dev = g.mem.uninit<uint32_t>((size_t)g.n * 4);
+  dev_h2d(dict_off_dev, A.dict_off.data(), (size_t)g.n * 4);
+  DictsText out;
+  out.dict_bytes_dev = g.mem.uninit<uint32_t>((size_t)g.n * 4);
+  dev_h2d(out.dict_bytes_dev, A.dict_bytes.data(), (size_t)g.n * 4);
+  uint32_t* starts_dev = g.mem.uninit<uint32_t>((size_t)g.n * 4);
+  dev_h2d(starts_dev, A.starts.data(), (size_t)g.n * 4);
+  out.text = g.mem.zeroed<uint8_t>(g.padded + 64);
+  lz77_batch_dicts_text(pool_dev, dict_off_dev, out.dict_bytes_dev, g.uploaded, starts_dev, g.items_dev, g.n, out.text);
+  return out;
+}
+
 // Qualities 5 .. 8 behind a dictionary per item: the steps of CompressGroups' dictionary path without an image -- there is none
-// to share, so every chain files its own dictionary (br_batch_item<kRows, true, true>).  A group uploads its packed items and,
-// once each, the dictionaries its items name: a pool in which every dictionary ends on a 16-byte boundary behind zero bytes of
-// its own (the dict_shifted convention of lz77_batch_dict_text), with the place and the size of item i's dictionary beside it.
-// dicts[i] / dict_sizes[i]: the dictionary of item i as in use; two items share one where pointer and size agree.
+// to share, so every chain files its own dictionary (br_batch_item<kRows, true, true>) in the text StageDictsText lays out.
+// dicts[i] / dict_sizes[i]: the dictionary of item i as in use.
 void CompressGroupsWithDictionaries(const EncoderParams& p, size_t count, const uint8_t* const* dicts, const size_t* dict_sizes,
                                     const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
                                     std::vector<uint8_t>* reference_fails, uint32_t* groups) {
@@ -491,40 +535,11 @@ void CompressGroupsWithDictionaries(const EncoderParams& p, size_t count, const 
     Group g;
     StageGroup(first, count, inputs, sizes, DictSizes(dict_sizes), tables_max, &A, &g);
     ++*groups;
-    // ---- the pool (the group's byte limit counts a dictionary per item, so the pool stays below it)
-    std::map<std::pair<const uint8_t*, size_t>, uint32_t> placed;
-    A.dict_off.resize_discard(g.n);
-    size_t pool_bytes = 0;
-    for (uint32_t i = 0; i < g.n; ++i)
-      if (placed.emplace(std::make_pair(dicts[first + i], dict_sizes[first + i]), 0u).second) pool_bytes += (dict_sizes[first + i] + 15) & ~(size_t)15;
-    A.dict_pool.resize_discard(pool_bytes + 64);
-    placed.clear();
-    uint32_t at = 0;
-    for (uint32_t i = 0; i < g.n; ++i) {
-      const uint32_t D = A.dict_bytes[i], lead = (0u - D) & 15u;
-      const auto slot = placed.emplace(std::make_pair(dicts[first + i], dict_sizes[first + i]), at + lead);
-      if (slot.second) {
-        memset(A.dict_pool.data() + at, 0, lead);
-        memcpy(A.dict_pool.data() + at + lead, dicts[first + i], D);
-        at += lead + D;
-      }
-      A.dict_off[i] = slot.first->second;
-    }
-    memset(A.dict_pool.data() + at, 0, 64);
-    uint8_t* pool_dev = g.mem.uninit<uint8_t>(pool_bytes + 64);
-    dev_h2d_bulk(pool_dev, A.dict_pool.data(), pool_bytes + 64);
-    uint32_t* dict_off_dev = g.mem.uninit<uint32_t>((size_t)g.n * 4);
-    dev_h2d(dict_off_dev, A.dict_off.data(), (size_t)g.n * 4);
-    uint32_t* dict_bytes_dev = g.mem.uninit<uint32_t>((size_t)g.n * 4);
-    dev_h2d(dict_bytes_dev, A.dict_bytes.data(), (size_t)g.n * 4);
-    uint32_t* starts_dev = g.mem.uninit<uint32_t>((size_t)g.n * 4);
-    dev_h2d(starts_dev, A.starts.data(), (size_t)g.n * 4);
-    uint8_t* text = g.mem.zeroed<uint8_t>(g.padded + 64);
-    lz77_batch_dicts_text(pool_dev, dict_off_dev, dict_bytes_dev, g.uploaded, starts_dev, g.items_dev, g.n, text);
+    const DictsText staged = StageDictsText(g, dicts, dict_sizes);
 
-    BatchParseJob J = GreedyJob(p, P, g, text);
+    BatchParseJob J = GreedyJob(p, P, g, staged.text);
     J.records = g.mem.uninit<BatchRecord>((size_t)g.n * sizeof(BatchRecord));
-    J.item_dict_bytes = dict_bytes_dev;
+    J.item_dict_bytes = staged.dict_bytes_dev;
     lz77_batch_parse_dicts(J);
     FinishOneBlockItems(p, J, g, streams, reference_fails);
     first = g.last;
@@ -693,6 +708,40 @@ void BatchQuickCompressWithDictionary(const EncoderParams& user, const uint8_t* 
     J.text = text;
     J.records = g.mem.uninit<BatchRecord>((size_t)g.n * sizeof(BatchRecord));
     lz77_quick_batch_parse_dict(J);
+    // (the gather reads raw commands, whose distance codes the chain took from positions that count the dictionary: it needs no D)
+    FinishOneBlockItems(p, GatherJobOf(J), g, streams, reference_fails);
+    first = g.last;
+  }
+}
+
+// Qualities 2 .. 4 behind a dictionary per item (batch_quick.h), items of one block: the steps of BatchQuickCompressWithDictionary
+// with the pool step of CompressGroupsWithDictionaries (StageDictsText) in place of the one dictionary and its image -- a chain
+// zeroes its table and files its item's dictionary itself (br_quick_batch_file), so nothing is built per dictionary.
+void BatchQuickCompressWithDictionaries(const EncoderParams& user, size_t count, const uint8_t* const* dicts, const size_t* dict_sizes,
+                                        const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
+                                        std::vector<uint8_t>* reference_fails, uint32_t* groups) {
+  streams->assign(count, std::vector<uint8_t>());
+  reference_fails->assign(count, 0);
+  *groups = 0;
+  if (count == 0) return;
+  for (size_t i = 0; i < count; ++i)
+    if (dict_sizes[i] < 2 || dict_sizes[i] > ((size_t)1 << 16)) throw std::runtime_error("brotli_mi355x: a dictionary the quick batch chains do not take");
+  const EncoderParams p = DictionaryItemParams(user, sizes[0]);  // (nothing in the parameters differs between items of at most one block)
+  const QuickBatchJob chains = QuickChains(p);  // (no static dictionary behind a custom one: Q.use_dictionary is 0)
+  const size_t tables_max = TablesMax(QuickTableBytes(chains));
+
+  CallArrays A;
+  size_t first = 0;
+  while (first < count) {
+    Group g;
+    StageGroup(first, count, inputs, sizes, DictSizes(dict_sizes), tables_max, &A, &g);
+    ++*groups;
+    const DictsText staged = StageDictsText(g, dicts, dict_sizes);
+    QuickBatchJob J = QuickGroupJob(chains, g);
+    J.text = staged.text;
+    J.records = g.mem.uninit<BatchRecord>((size_t)g.n * sizeof(BatchRecord));
+    J.item_dict_bytes = staged.dict_bytes_dev;
+    lz77_quick_batch_parse_dicts(J);
     // (the gather reads raw commands, whose distance codes the chain took from positions that count the dictionary: it needs no D)
     FinishOneBlockItems(p, GatherJobOf(J), g, streams, reference_fails);
     first = g.last;

@@ -35,12 +35,18 @@ struct QuickBatchJob {
                           // the dictionary's first byte
   const uint32_t* image;  // [quick_table_words(Q)], 16-byte aligned: the table lz77_quick_init + lz77_quick_prepend leave for the
                           // dictionary (slots and books), which every chain copies over its own table in front of every item
+  // behind a custom dictionary per item (lz77_quick_batch_parse_dicts); nullptr for every other launch
+  const uint32_t* item_dict_bytes;  // [n_items]: item i's text is its own dictionary | item, as above; dict_bytes and image are not
+                                    // looked at -- a chain files its item's dictionary into its zeroed table itself
 };
 // one wavefront per table; a wavefront takes items from `counter` until none is left
 void lz77_quick_batch_parse(const QuickBatchJob& J);
 // the same launch for items behind a shared custom dictionary (J.dict_bytes >= 2, J.image): a chain starts on the image instead of
 // a zeroed table and cuts its matches at the dictionary's end; BatchRecord::bad_commands flags the items the reference fails on
 void lz77_quick_batch_parse_dict(const QuickBatchJob& J);
+// the same launch for items behind a dictionary of their own (J.item_dict_bytes: 2 .. 65536 bytes each): a chain zeroes its table
+// and files its item's dictionary itself (br_quick_batch_file), since there is no image to share, then runs as the one above
+void lz77_quick_batch_parse_dicts(const QuickBatchJob& J);
 
 // ---- items of several blocks (BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS): an item of two to kBatchLongBlocks input blocks is still
 // ONE chain on a private table -- br_quick_block block after block, with the books between the blocks that the host resolver keeps
@@ -71,6 +77,13 @@ bool BatchQuickDictionaryEligible(const EncoderParams& params, size_t dict_size,
 void BatchQuickCompressWithDictionary(const EncoderParams& params, const uint8_t* dict, size_t dict_use, size_t count,
                                       const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
                                       std::vector<uint8_t>* reference_fails, uint32_t* groups);
+// Behind a custom dictionary per item (BrotliMi355xCompressBatchWithDictionaries with
+// BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS): item i is eligible by BatchQuickDictionaryEligible with its own dictionary.
+// dicts[i] / dict_sizes[i]: the dictionary of item i as in use (2 .. 65536 bytes, after the truncation); two items share one
+// where pointer and size agree.  streams, reference_fails, groups: as above.
+void BatchQuickCompressWithDictionaries(const EncoderParams& params, size_t count, const uint8_t* const* dicts, const size_t* dict_sizes,
+                                        const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
+                                        std::vector<uint8_t>* reference_fails, uint32_t* groups);
 
 }  // namespace brotli_mi355x
 #endif

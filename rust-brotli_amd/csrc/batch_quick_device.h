@@ -51,6 +51,29 @@ BR_DEV void br_quick_batch_prime(uint32_t* table, const uint32_t* image, uint32_
   BR_SYNC();
 }
 
+// The hasher as HasherPrependCustomDictionary leaves it for a dictionary of the item's own (text: its D bytes), on a table that
+// br_quick_batch_zero has just emptied: the prepend files the positions 0 .. D - kQuickHtl in ascending order, so what a slot ends
+// up with is the LARGEST position filed under it (k_quick_prepend relies on the same).  The wavefront files 64 consecutive
+// positions per step, one per lane, with a device-scope atomic maximum whose result nobody reads; lanes of one step that meet in a
+// slot (runs, periodic text) are settled by the maximum, whatever their order.  Every 8-byte load ends inside the dictionary.
+// Made visible like the zero fill: q_get and the book loads of br_quick_block are device-scope loads.
+BR_DEV void br_quick_batch_file(const QuickJob& Q, const uint8_t* text, uint32_t D) {
+#if BR_SCALAR
+  br_quick_prepend(Q, text, D);
+#else
+  if (D >= kQuickHtl) {
+    const uint32_t count = D - (kQuickHtl - 1u);
+    for (uint32_t i = (uint32_t)BR_LANE; i < count; i += BR_NLANES) {
+      const uint64_t v = (br_load64(text + i) << (64u - 8u * Q.hash_len)) * kQuickHashMul64;
+      const uint32_t key = (uint32_t)(v >> (64u - Q.bucket_bits));
+      atomicMax(Q.table + key + ((i >> 3) & (Q.sweep - 1u)), i);
+    }
+  }
+  __threadfence();
+#endif
+  BR_SYNC();
+}
+
 // The job of one item on table `table`, in item-local coordinates: position 0 is the item's first byte (D == 0), so no distance
 // reaches a neighbour and max_backward is what the reference computes for a stream that starts at 0; behind a custom dictionary
 // position 0 is the dictionary's first byte and the item starts at D, as in the reference's ring buffer.  Known here, whatever
@@ -72,16 +95,22 @@ BR_DEV void br_quick_batch_job(const QuickBatchJob& J, uint32_t table, uint32_t 
 // (LDS on the device).
 // kDict: the item's text starts with J.dict_bytes bytes of custom dictionary (BrotliMi355xCompressBatchWithDictionaryEx) and its
 // chain starts on J.image.
-template <bool kDict = false>
+// kDicts (with kDict): the dictionary is the item's own, J.item_dict_bytes[index] bytes (BrotliMi355xCompressBatchWithDictionaries);
+// the chain zeroes its table and files that dictionary itself, J.dict_bytes and J.image are not looked at.
+template <bool kDict = false, bool kDicts = false>
 BR_DEV void br_quick_batch_item(const QuickBatchJob& J, const QuickTables& T, const EntropyTables& logs, uint32_t* histo, SegExit* exit_slot,
                                 uint32_t index, uint32_t table) {
   const BatchItem it = br_batch_load_item(J.items, index);
   // (D + bytes stays inside the first lap of the ring: D < 1 << lgwin, bytes <= 1 << lgblock, the ring has 1 + max of the two bits)
-  const uint32_t D = kDict ? BR_UNIFORM(J.dict_bytes) : 0u;
+  const uint32_t D = kDicts ? BR_UNIFORM(J.item_dict_bytes[index]) : (kDict ? BR_UNIFORM(J.dict_bytes) : 0u);
   QuickJob Q;
   Lz77Params P;
   br_quick_batch_job(J, table, D, it.bytes, Q, P);
-  if constexpr (kDict) {
+  if constexpr (kDicts) {
+    static_assert(kDict || !kDicts, "kDicts goes with kDict");
+    br_quick_batch_zero(Q.table, quick_table_words(Q));
+    br_quick_batch_file(Q, J.text + it.text_off - D, D);
+  } else if constexpr (kDict) {
     br_quick_batch_prime(Q.table, J.image, quick_table_words(Q));
   } else {
     br_quick_batch_zero(Q.table, quick_table_words(Q));

@@ -4,6 +4,7 @@
 // a table serves several items, as on the device.  The gather is lz77_batch_gather (batch_greedy_emu.inc).
 // lz77_quick_batch_parse_dict: the same loop over the item code behind a shared custom dictionary (the image is the emulation's
 // lz77_quick_init + lz77_quick_prepend, i.e. br_quick_prepend).
+// lz77_quick_batch_parse_dicts: the same loop behind a dictionary per item; a chain files its dictionary with br_quick_prepend.
 // lz77_quick_batch_parse_long: the same loop over the item code of the items of several blocks; its gather is lz77_batch_gather_long.
 #include <stdexcept>
 
@@ -43,6 +44,18 @@ void lz77_quick_batch_parse_dict(const QuickBatchJob& J) {
   uint32_t histo[256];
   SegExit exit_slot;
   for (uint32_t place = 0; place < J.n_items; ++place) br_quick_batch_item<true>(J, T, logs, histo, &exit_slot, J.order[place], place % J.tables);
+  *J.counter = J.n_items;
+}
+
+void lz77_quick_batch_parse_dicts(const QuickBatchJob& J) {
+  if (J.n_items == 0) return;
+  QuickTables T;
+  EntropyTables logs;
+  quick_batch_emu_tables(J, T, logs);
+  if (J.item_dict_bytes == nullptr) throw std::runtime_error("brotli_mi355x: a batch group with a dictionary per item without their sizes");
+  uint32_t histo[256];
+  SegExit exit_slot;
+  for (uint32_t place = 0; place < J.n_items; ++place) br_quick_batch_item<true, true>(J, T, logs, histo, &exit_slot, J.order[place], place % J.tables);
   *J.counter = J.n_items;
 }
 

@@ -1337,8 +1337,9 @@ int32_t BrotliMi355xCompressBatchWithDictionaries(int quality, int lgwin, Brotli
   memcpy(g_batch_info, info, sizeof(info));
   // what fails the call as a whole before any work is done, like an unknown route of BrotliMi355xCompressBatchEx
   std::string refused;
-  if (routes != 0) {
-    refused = "routes " + std::to_string(routes) + " names a route this call does not know (this build knows none behind a dictionary per item)";
+  if ((routes & ~(uint32_t)BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS) != 0) {
+    refused = "routes " + std::to_string(routes) + " names a route this call does not know (known behind a dictionary per item: "
+              "BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS = 512)";
   } else if (item_dicts == nullptr && num_dicts != count) {
     refused = "item_dicts is NULL (item i takes dicts[i]) but num_dicts, " + std::to_string(num_dicts) + ", is not count, " + std::to_string(count);
   } else if (item_dicts != nullptr) {
@@ -1353,14 +1354,15 @@ int32_t BrotliMi355xCompressBatchWithDictionaries(int quality, int lgwin, Brotli
     return 0;
   }
   if (count == 0) return 1;
+  const bool quick_route = (routes & BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS) != 0;
   // one index named by every item: the shared-dictionary call, whose chains replay one image instead of filing the dictionary
   {
     const size_t k0 = item_dicts ? item_dicts[0] : 0;
     bool one = item_dicts != nullptr || count == 1;
     for (size_t i = 1; i < count && one; ++i) one = item_dicts[i] == k0;
     if (one)
-      return CompressBatchWithDictionary(entry, quality, lgwin, mode, 0, dict_sizes[k0], dicts[k0], count, inputs, input_sizes, outputs, output_sizes,
-                                         item_results);
+      return CompressBatchWithDictionary(entry, quality, lgwin, mode, quick_route ? BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS : 0u, dict_sizes[k0], dicts[k0],
+                                         count, inputs, input_sizes, outputs, output_sizes, item_results);
   }
   size_t total = 0;
   for (size_t i = 0; i < count; ++i) total += input_sizes[i];
@@ -1387,14 +1389,22 @@ int32_t BrotliMi355xCompressBatchWithDictionaries(int quality, int lgwin, Brotli
     }
     SmallCallGate gate(total);
     // Side by side: the items of 1 .. 65536 bytes at qualities 5 .. 8, lgwin 17 .. 24, behind a dictionary of 2 .. 65536 bytes in
-    // use (batch_greedy.h: a chain per item that files the item's dictionary itself).  Every other item goes through the stream
+    // use (batch_greedy.h: a chain per item that files the item's dictionary itself) and, where the caller asked for that route,
+    // the items of at most one input block at qualities 2 .. 4, lgwin 10 .. 24, behind at most 65536 dictionary bytes in use
+    // (batch_quick.h) -- a call has one quality, so its items take one of the two.  Every other item goes through the stream
     // path by itself with its own dictionary, on this thread, in the caller's order.
+    bool quick = false;
     std::vector<size_t> item, in_size, d_size;
     std::vector<const uint8_t*> in, d;
     for (size_t i = 0; i < count; ++i) {
       const size_t k = item_dicts ? item_dicts[i] : i;
-      if (BatchDictionaryEligible(params, dict_sizes[k], input_sizes[i])) {
-        const size_t use = in_use(k);  // (dict_sizes[k] itself: an eligible dictionary is below every window's limit)
+      const bool greedy_item = BatchDictionaryEligible(params, dict_sizes[k], input_sizes[i]);
+      const bool quick_item = !greedy_item && quick_route && BatchQuickDictionaryEligible(params, dict_sizes[k], input_sizes[i]);
+      if (quick_item) quick = true;
+      if (greedy_item || quick_item) {
+        // (at qualities 5 .. 8 dict_sizes[k] itself: an eligible dictionary is below every window's limit; at lgwin 10 .. 16 its
+        // last (1 << lgwin) - 16 bytes)
+        const size_t use = in_use(k);
         item.push_back(i);
         in.push_back(inputs[i]);
         in_size.push_back(input_sizes[i]);
@@ -1409,7 +1419,10 @@ int32_t BrotliMi355xCompressBatchWithDictionaries(int quality, int lgwin, Brotli
       std::vector<std::vector<uint8_t>> streams;
       std::vector<uint8_t> reference_fails;
       uint32_t groups = 0;
-      BatchGreedyCompressWithDictionaries(params, item.size(), d.data(), d_size.data(), in.data(), in_size.data(), &streams, &reference_fails, &groups);
+      if (quick)
+        BatchQuickCompressWithDictionaries(params, item.size(), d.data(), d_size.data(), in.data(), in_size.data(), &streams, &reference_fails, &groups);
+      else
+        BatchGreedyCompressWithDictionaries(params, item.size(), d.data(), d_size.data(), in.data(), in_size.data(), &streams, &reference_fails, &groups);
       info[4] = groups;
       info[1] = item.size();
       for (size_t n = 0; n < item.size(); ++n) {

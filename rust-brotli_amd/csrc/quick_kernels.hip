@@ -94,6 +94,16 @@ __global__ __launch_bounds__(64) void k_quick_batch_dict(QuickBatchJob J, QuickT
   for (uint32_t index; br_batch_next_index(J.counter, J.order, J.n_items, index);) br_quick_batch_item<true>(J, T, logs, histo, &exit_slot, index, table);
 }
 
+// The same launch for items behind a custom dictionary each (J.item_dict_bytes): a chain zeroes its table and files its item's
+// dictionary itself, 64 positions per step (br_quick_batch_file).  (A kernel of its own for the reason above.)
+__global__ __launch_bounds__(64) void k_quick_batch_dicts(QuickBatchJob J, QuickTables T, EntropyTables logs) {
+  __shared__ uint32_t histo[256];
+  __shared__ SegExit exit_slot;
+  const uint32_t table = blockIdx.x;
+  if (table >= J.tables) return;
+  for (uint32_t index; br_batch_next_index(J.counter, J.order, J.n_items, index);) br_quick_batch_item<true, true>(J, T, logs, histo, &exit_slot, index, table);
+}
+
 // Items of two to kBatchLongBlocks input blocks (batch_quick.h): the launch shape of k_quick_batch, the item code walks from
 // block to block and leaves one BatchLongRecord per item.
 __global__ __launch_bounds__(64) void k_quick_batch_long(QuickBatchJob J, BatchLongRecord* __restrict__ records, QuickTables T, EntropyTables logs) {
@@ -130,6 +140,14 @@ void lz77_quick_batch_parse_dict(const QuickBatchJob& J) {
   if (grid == 0) return;
   if (J.dict_bytes == 0 || J.image == nullptr) throw std::runtime_error("brotli_mi355x: a dictionary batch group without its table image");
   hipLaunchKernelGGL(k_quick_batch_dict, dim3(grid), dim3(64), 0, BR_STREAM, J, quick_tables(), entropy_tables());
+  HIP_CHECK(hipGetLastError());
+}
+
+void lz77_quick_batch_parse_dicts(const QuickBatchJob& J) {
+  const uint32_t grid = quick_batch_grid(J);
+  if (grid == 0) return;
+  if (J.item_dict_bytes == nullptr) throw std::runtime_error("brotli_mi355x: a batch group with a dictionary per item without their sizes");
+  hipLaunchKernelGGL(k_quick_batch_dicts, dim3(grid), dim3(64), 0, BR_STREAM, J, quick_tables(), entropy_tables());
   HIP_CHECK(hipGetLastError());
 }
 

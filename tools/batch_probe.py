@@ -62,14 +62,16 @@ With --same-call (and any of the above) the parent's library is measured through
 and dictionary included, alternating with it --rounds times: the A/B of a change that keeps the routes.  Per class the result holds the
 medians of both, their difference, and the parent's own spread between its rounds as the margin; nothing else is measured.
 
-With --dicts (and --qualities 5,8) the call measured is BrotliMi355xCompressBatchWithDictionaries, a custom dictionary per item: text items,
+With --dicts (and --qualities 5,8, or 2,3,4) the call measured is BrotliMi355xCompressBatchWithDictionaries, a custom dictionary per item: text items,
 and per item a dictionary that is another draw from the items' own source (DICTS_CLASSES: 4096 items of 4 KiB behind 4 and 16 KiB, 1024 of
 16 KiB behind 16 and 64 KiB, 64 of 4 KiB behind 16 KiB).  It is measured against the only way the parent commit has -- the loop of stream
 calls with BrotliEncoderSetCustomDictionary, each item with its own dictionary, on the calling thread and from four threads (--parent-lib, or
 this build's library: the loop is the same code), on the first --loop-items items, scaled by item count -- against the oracle's dictionary
 stream on one core, and against the shared-dictionary call on the same items: for that ONE dictionary is given as `count` distinct
 indices (the chains file it themselves) and to BrotliMi355xCompressBatchWithDictionary (the chains replay its image), which prices
-self-filing against the image.
+self-filing against the image.  At qualities 2 to 4 this build is called with BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS, and the shared call
+is BrotliMi355xCompressBatchWithDictionaryEx with BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS; two more classes are measured there (4096 items of
+512 bytes behind 16 KiB; at quality 4, where that is one input block, 1024 items of 64 KiB behind 64 KiB).
 
 Every measurement runs in a child process of its own (the table's home is one setting per process, read once; the parent's library
 is another shared object), one after the other, each under its own time limit; the first failure ends the probe.
@@ -132,7 +134,10 @@ QUICK_HEADLINE = ["4096x4KiB", "4096x16KiB", "1024x64KiB", "4096x512B", "4096xlo
 ZOPFLI_HEADLINE = ["1024x4KiB", "256x16KiB", "64x64KiB", "16x4KiB"]  # (--zopfli-items)
 # (--dicts) class -> (items, item bytes, dictionary bytes per item)
 DICTS_CLASSES = {"4096x4KiB+4KiB": (4096, 4 << 10, 4 << 10), "4096x4KiB+16KiB": (4096, 4 << 10, 16 << 10), "1024x16KiB+16KiB": (1024, 16 << 10, 16 << 10),
-                 "1024x16KiB+64KiB": (1024, 16 << 10, 64 << 10), "64x4KiB+16KiB": (64, 4 << 10, 16 << 10)}
+                 "1024x16KiB+64KiB": (1024, 16 << 10, 64 << 10), "64x4KiB+16KiB": (64, 4 << 10, 16 << 10),
+                 # qualities 2 to 4 only (BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS)
+                 "1024x64KiB+64KiB": (1024, 64 << 10, 64 << 10), "4096x512B+16KiB": (4096, 512, 16 << 10)}
+DICTS_QUALITIES = {"1024x64KiB+64KiB": (4,), "4096x512B+16KiB": (2, 3, 4)}  # (64 KiB is one input block at quality 4 only)
 Q9_HEADLINE = ["4096x4KiB", "1024x16KiB", "256x64KiB", "64x256KiB", "16x4KiB", "64x4KiB", "4096xlog200B-256KiB"]  # (--q9-items)
 
 
@@ -241,8 +246,10 @@ def measure_batch(lib_path, items, quality, runs, warmup, dictionary=None, route
 
 def measure_dicts(lib_path, items, dictionaries, quality, runs, warmup, shared=False):
     """BrotliMi355xCompressBatchWithDictionaries with dictionaries[i] for item i; shared: BrotliMi355xCompressBatchWithDictionary with
-    dictionaries[0]"""
+    dictionaries[0].  At qualities 2 to 4 both with the route that takes such items side by side (512, and 4 through the Ex entry)."""
     L = bind(lib_path)
+    quick = 2 <= quality <= 4
+    L.BrotliMi355xCompressBatchWithDictionaryEx.restype = ctypes.c_int32
     L.BrotliMi355xCompressBatchWithDictionaries.restype = ctypes.c_int32
     L.BrotliMi355xCompressBatchWithDictionary.restype = ctypes.c_int32
     L.BrotliMi355xLastError.restype = ctypes.c_char_p
@@ -262,11 +269,14 @@ def measure_dicts(lib_path, items, dictionaries, quality, runs, warmup, shared=F
         for i in range(n):
             out_sizes[i] = caps[i]
         t = time.perf_counter()
-        if shared:
+        if shared and quick:
+            ok = L.BrotliMi355xCompressBatchWithDictionaryEx(quality, LGWIN, 0, ctypes.c_uint32(4), ctypes.c_size_t(len(dictionaries[0])), ctypes.c_char_p(dictionaries[0]),
+                                                             ctypes.c_size_t(n), inputs, in_sizes, outputs, out_sizes, results)
+        elif shared:
             ok = L.BrotliMi355xCompressBatchWithDictionary(quality, LGWIN, 0, ctypes.c_size_t(len(dictionaries[0])), ctypes.c_char_p(dictionaries[0]), ctypes.c_size_t(n),
                                                            inputs, in_sizes, outputs, out_sizes, results)
         else:
-            ok = L.BrotliMi355xCompressBatchWithDictionaries(quality, LGWIN, 0, ctypes.c_uint32(0), ctypes.c_size_t(n), dicts, dict_sizes, ctypes.c_size_t(n), None,
+            ok = L.BrotliMi355xCompressBatchWithDictionaries(quality, LGWIN, 0, ctypes.c_uint32(512 if quick else 0), ctypes.c_size_t(n), dicts, dict_sizes, ctypes.c_size_t(n), None,
                                                              inputs, in_sizes, outputs, out_sizes, results)
         dt = time.perf_counter() - t
         if ok != 1:
@@ -366,6 +376,8 @@ def child_dicts(args):
         items, dictionaries = dicts_of(name)
         n = args.loop_items
         for quality in [int(q) for q in args.qualities.split(",")]:
+            if quality not in DICTS_QUALITIES.get(name, (quality,)):
+                continue
             row = {"class": name, "data": "text", "quality": quality, "items": len(items), "bytes": sum(map(len, items)), "dictionary_bytes": len(dictionaries[0])}
             if args.child in ("batch", "same", "shared"):
                 ds = dictionaries if args.child == "batch" else [dictionaries[0]] * len(items)
@@ -568,7 +580,8 @@ def main_dicts(args, doc, save, classes):
     doc["what"] = ("BrotliMi355xCompressBatchWithDictionaries (a custom dictionary per item, every chain files its own) vs the loop of stream-API calls with "
                    "BrotliEncoderSetCustomDictionary, each item with its own dictionary (1 and 4 threads, first --loop-items items scaled by item count) vs the "
                    "oracle's dictionary stream on one CPU core; and, on the same items behind ONE dictionary, the call with that dictionary as `count` "
-                   "distinct indices (self-filing) vs BrotliMi355xCompressBatchWithDictionary (the shared image); text, lgwin 22")
+                   "distinct indices (self-filing) vs BrotliMi355xCompressBatchWithDictionary (the shared image); at qualities 2 to 4 with "
+                   "BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS, the shared call with BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS; text, lgwin 22")
     rows = {}
     short = ("median_ms", "min_ms", "max_ms", "spread_pct", "runs")
     for rnd in range(args.rounds):
@@ -681,7 +694,7 @@ def main():
     ap.add_argument("--quick-long-items", action="store_true", help="this build through routes QUICK_ITEMS | QUICK_LONG_ITEMS, the parent through QUICK_ITEMS (qualities 2,3,4 per class)")
     ap.add_argument("--zopfli-items", action="store_true", help="this build through BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS (--qualities 11)")
     ap.add_argument("--q9-items", action="store_true", help="this build through BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS (--qualities 9,10)")
-    ap.add_argument("--dicts", action="store_true", help="BrotliMi355xCompressBatchWithDictionaries: a dictionary per item (--qualities 5,8)")
+    ap.add_argument("--dicts", action="store_true", help="BrotliMi355xCompressBatchWithDictionaries: a dictionary per item (--qualities 5,8; 2,3,4 through BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS)")
     ap.add_argument("--same-call", action="store_true", help="the parent's library through the same call as this build, alternating --rounds times (needs --parent-lib)")
     ap.add_argument("--quick-long-classes", action="store_true", help="(child) only the qualities of QUICK_LONG_QUALITIES")
     ap.add_argument("--plain", action="store_true", help="(child) the plain call although a dictionary size is given")
