@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "lz77_types.h"
+#include "lz77_warmup.h"
 
 // Every thread of the host program works on its own HIP stream (hipStreamPerThread): independent encoder calls from
 // different threads overlap on the GPU, nothing ever runs on the synchronising null stream.
@@ -269,6 +270,21 @@ void lz77_parse_round(const Lz77Params& P, const Lz77Buffers& B, int which, int 
 // changes (br_parse_chain), rewrites B.entries for them and marks them 3
 void lz77_parse_list(const Lz77Params& P, const Lz77Buffers& B, int which, int rbuf, const uint32_t* list_dev, uint8_t* sched_dev,
                      uint32_t count);
+// ---- the dry runs in front of round 0, entries composed on the device (lz77_warmup.h; the emulation build: lz77_warmup_emu.inc)
+// lz77_warmup_prepare: B.entries := the first guess of every entry (Lz77Stage::InitEntries: segment start, `base_cache`, counters
+// "alive" behind segment 0) and W.segs / W.entries := the dry run over the tail of every segment but the last.  The caller then
+// parses them (lz77_parse_custom into W.exits).  lz77_warmup_compose: B.entries[k + 1] from W.exits[k] as WarmupEnd and the
+// forecast of RunRounds do on the host; W.fc_death[0] := the segment in which the static dictionary is forecast to go off
+// (num_segments: never).  Nothing is read back.
+struct WarmupBuffers {
+  Segment* segs;        // [num_segments - 1]
+  SegEntry* entries;    // [num_segments - 1]
+  SegExit* exits;       // [num_segments - 1]
+  WarmupOp* tile_ops;   // [2 * tiles], tiles = ceil((num_segments - 1) / kWarmupTile): aggregate of every tile, then what lies in front of it
+  uint32_t* fc_death;   // [1]
+};
+void lz77_warmup_prepare(const Lz77Params& P, const Lz77Buffers& B, const WarmupShape& S, const WarmupBuffers& W, const int32_t base_cache[4]);
+void lz77_warmup_compose(const Lz77Params& P, const Lz77Buffers& B, const WarmupShape& S, const WarmupBuffers& W);
 // list rounds move only what changed between host and device:
 // B.entries[index_dev[i]] = entries_dev[i] for i < count
 void lz77_scatter_entries(const Lz77Buffers& B, const uint32_t* index_dev, const SegEntry* entries_dev, uint32_t count);

@@ -41,55 +41,89 @@ void hip_check(hipError_t e, const char* what) {
 // the low key byte of every tile on the way (`hist`, optional: the [digit][tile] histogram of the sort's first pass).
 static constexpr uint32_t kSortTile = 4096;
 
-__global__ __launch_bounds__(256) void k_compute_keys(const uint8_t* __restrict__ text, uint16_t* __restrict__ keys,
-                                                      uint32_t n, uint32_t valid_n, uint32_t kind, uint32_t bucket_bits,
-                                                      uint64_t hash_mask, uint32_t* __restrict__ run_samples,
-                                                      const uint16_t* __restrict__ dict_hash, uint32_t* __restrict__ dict_items,
-                                                      uint32_t num_tiles, uint32_t* __restrict__ hist) {
-  __shared__ uint32_t h[256];
-  for (uint32_t tile = blockIdx.x; tile < num_tiles; tile += gridDim.x) {
-    const uint32_t tile_base = tile * kSortTile;
-    const uint32_t tile_n = n - tile_base < kSortTile ? n - tile_base : kSortTile;
-    if (hist != nullptr) {
-      h[threadIdx.x] = 0;
-      __syncthreads();
-    }
-#pragma unroll 4
-    for (uint32_t e = threadIdx.x; e < tile_n; e += 256) {
-      const uint32_t i = tile_base + e;
-      if (dict_items != nullptr) {  // (the text is padded by 64 zero bytes)
-        const uint32_t dh = ((br_load32(text + i) * 0x1e35a7bdu) >> (32 - 14)) << 1;
-        dict_items[i] = (uint32_t)dict_hash[dh] | ((uint32_t)dict_hash[dh + 1] << 16);
+// The grid is sized to the device (two workgroups per CU) and every workgroup walks its tiles with the 64 KiB dict_hash table in
+// LDS: an item pair is the 32-bit word 2 * hash14 / 2 of the table, one ds_read instead of two 2-byte gathers from global memory.
+// 1024 threads x 4 consecutive positions = one sort tile per step.  A lane reads the three aligned dwords that hold the 5-to-8-byte
+// windows of its four positions and shifts the windows together in registers; it stores 8 B of keys and 16 B of items.  Two
+// workgroups of 16 waves fill a CU's 32 wave slots (the kernel needs fewer than 64 VGPRs) and its LDS (2 x 66 KiB of 160 KiB).
+static constexpr uint32_t kKeysThreads = 1024;
+static_assert(kKeysThreads * 4 == kSortTile, "one sort tile per step of a workgroup");
+
+__global__ __launch_bounds__(kKeysThreads) void k_compute_keys(const uint8_t* __restrict__ text, uint16_t* __restrict__ keys,
+                                                               uint32_t n, uint32_t valid_n, uint32_t kind, uint32_t bucket_bits,
+                                                               uint64_t hash_mask, uint32_t* __restrict__ run_samples,
+                                                               const uint16_t* __restrict__ dict_hash, uint32_t* __restrict__ dict_items,
+                                                               uint32_t num_tiles, uint32_t* __restrict__ hist) {
+  __shared__ uint32_t tab[16384];  // kStaticDictionaryHash, item pairs
+  __shared__ uint32_t h[2][256];   // digit counters of this tile and of the one before (written out while the next one counts)
+  const uint32_t t = threadIdx.x;
+  if (dict_items != nullptr) {
+    const uint4* src = (const uint4*)dict_hash;
+    for (uint32_t q = t; q < 4096; q += kKeysThreads) ((uint4*)tab)[q] = src[q];
+  }
+  if (t < 512) (&h[0][0])[t] = 0;
+  __syncthreads();
+  // (the text is padded by 64 zero bytes; a text that starts inside a dword -- a custom dictionary shifted to END on a 16-byte
+  // boundary -- is read from the dword it starts in, and every dword of the lane shifted into place)
+  const uint32_t mis = (uint32_t)((uintptr_t)text & 3u), sh = 8 * mis;
+  const uint32_t* text32 = (const uint32_t*)(text - mis);
+  uint32_t b = 0;
+  for (uint32_t tile = blockIdx.x; tile < num_tiles; tile += gridDim.x, b ^= 1u) {
+    const uint32_t i = tile * kSortTile + 4 * t;
+    if (i < n) {
+      uint32_t w0 = text32[i >> 2], w1 = text32[(i >> 2) + 1], w2 = text32[(i >> 2) + 2];
+      if (mis != 0) {
+        const uint32_t w3 = text32[(i >> 2) + 3];
+        w0 = (w0 >> sh) | (w1 << (32 - sh));
+        w1 = (w1 >> sh) | (w2 << (32 - sh));
+        w2 = (w2 >> sh) | (w3 << (32 - sh));
       }
-      uint32_t key = 0xffffu;
-      if (i < valid_n) {
-        // sample (every 64th position): does a run of one byte start here?  Enough of those switch on the run table.
-        if ((i & 63u) == 0 && i + 16 <= n) {
-          const uint64_t v = br_load64(text + i);
-          // (the count only matters up to the threshold the host compares it with: no need to hammer one address)
-          if (v == (v & 0xffull) * 0x0101010101010101ull && br_load64(text + i + 8) == v && *(volatile uint32_t*)run_samples < 4096u)
-            atomicAdd(run_samples, 1u);
+      // sample (every 64th position): does a run of one byte start here?  Enough of those switch on the run table.
+      if ((i & 63u) == 0 && i < valid_n && i + 16 <= n) {
+        // (the count only matters up to the threshold the host compares it with: no need to hammer one address)
+        if (w0 == (w0 & 0xffu) * 0x01010101u && w1 == w0 && w2 == w0 && br_load32(text + i + 12) == w0 && *(volatile uint32_t*)run_samples < 4096u)
+          atomicAdd(run_samples, 1u);
+      }
+      uint32_t key[4], item[4];
+#pragma unroll
+      for (uint32_t j = 0; j < 4; ++j) {
+        const uint32_t lo = j ? (w0 >> (8 * j)) | (w1 << (32 - 8 * j)) : w0;
+        const uint32_t hi = j ? (w1 >> (8 * j)) | (w2 << (32 - 8 * j)) : w1;
+        item[j] = dict_items != nullptr ? tab[(lo * 0x1e35a7bdu) >> (32 - 14)] : 0u;
+        uint32_t k = 0xffffu;
+        if (i + j < valid_n) {
+          if (kind == 6) {
+            const uint64_t v = ((((uint64_t)hi << 32) | lo) & hash_mask) * 0x1fe35a7bd3579bd3ull;
+            k = (uint32_t)(v >> (64 - bucket_bits)) & 0xffffu;
+          } else {
+            k = ((lo * 0x1e35a7bdu) >> (32 - bucket_bits)) & 0xffffu;
+          }
         }
-        if (kind == 6) {
-          const uint64_t v = (br_load64(text + i) & hash_mask) * 0x1fe35a7bd3579bd3ull;
-          key = (uint32_t)(v >> (64 - bucket_bits));
-        } else {
-          const uint32_t v = br_load32(text + i) * 0x1e35a7bdu;
-          key = v >> (32 - bucket_bits);
+        key[j] = k;
+        if (hist != nullptr && i + j < n) atomicAdd(&h[b][k & 255u], 1u);
+      }
+      if (i + 4 <= n) {
+        *(uint2*)(keys + i) = make_uint2(key[0] | (key[1] << 16), key[2] | (key[3] << 16));
+        if (dict_items != nullptr) *(uint4*)(dict_items + i) = make_uint4(item[0], item[1], item[2], item[3]);
+      } else {
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+          if (i + j >= n) break;
+          keys[i + j] = (uint16_t)key[j];
+          if (dict_items != nullptr) dict_items[i + j] = item[j];
         }
       }
-      keys[i] = (uint16_t)key;
-      if (hist != nullptr) atomicAdd(&h[key & 255u], 1u);
     }
     if (hist != nullptr) {
       __syncthreads();
-      hist[threadIdx.x * num_tiles + tile] = h[threadIdx.x];  // (every thread zeroes its own counter again, in front of the next barrier)
+      if (t < 256) {
+        hist[t * num_tiles + tile] = h[b][t];
+        h[b][t] = 0;  // (counted into again two tiles on, behind the next barrier)
+      }
     }
   }
-  if (dict_items != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {  // (positions behind the end are looked up as position n)
-    const uint32_t dh = ((br_load32(text + n) * 0x1e35a7bdu) >> (32 - 14)) << 1;
-    dict_items[n] = (uint32_t)dict_hash[dh] | ((uint32_t)dict_hash[dh + 1] << 16);
-  }
+  if (dict_items != nullptr && blockIdx.x == 0 && t == 0)  // (positions behind the end are looked up as position n)
+    dict_items[n] = tab[(br_load32(text + n) * 0x1e35a7bdu) >> (32 - 14)];
 }
 
 // The sort's scratch inside B.sort_tmp
@@ -125,8 +159,17 @@ void lz77_compute_keys(const Lz77Params& P, const Lz77Buffers& B) {
   // With the sort's scratch at hand (the stage calls: lz77_sort_by_key comes next) the first pass' histogram is counted here,
   // where the digit is in a register; callers that only want the keys (batch calls) bring no scratch.
   uint32_t* hist = (B.sort_tmp != nullptr && B.sort_tmp_bytes >= lz77_sort_tmp_bytes(n)) ? sort_scratch(B, n).hist : nullptr;
+  // (aligned vector stores: every caller hands in the bases of device blocks; the text may start anywhere)
+  if (((uintptr_t)B.keys & 7) || ((uintptr_t)B.dict_items & 15))
+    throw std::runtime_error("brotli_mi355x: lz77_compute_keys needs keys aligned to 8 and dict_items to 16 bytes");
+  static const uint32_t workgroups = [] {
+    int dev = 0, cus = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    return cus > 0 ? 2u * (uint32_t)cus : 512u;
+  }();
   dev_memset(B.changed_count + 8, 0, 4);
-  hipLaunchKernelGGL(k_compute_keys, dim3(tiles < 8192 ? tiles : 8192), dim3(256), 0, BR_STREAM, B.text, B.keys, n, valid_n, P.hasher_kind,
+  hipLaunchKernelGGL(k_compute_keys, dim3(tiles < workgroups ? tiles : workgroups), dim3(kKeysThreads), 0, BR_STREAM, B.text, B.keys, n, valid_n, P.hasher_kind,
                      P.bucket_bits, hash_mask, B.changed_count + 8, dev_tables().dict_hash, B.dict_items, tiles, hist);
   HIP_CHECK(hipGetLastError());
 }
@@ -1759,6 +1802,161 @@ void lz77_parse_custom(const Lz77Params& P, const Lz77Buffers& B, int which, int
                        SegEntry* entries_dev, SegExit* exits_dev, uint32_t count) {
   if (count == 0) return;
   launch_parse(P, B, which, which ^ 1, rbuf, segments_dev, entries_dev, exits_dev, 0, nullptr, nullptr, count);
+}
+
+// ------------------------------------------------------------------------------------------ entries from the dry runs
+// (lz77_warmup.h has the item code and the reasoning; device_api.h the seam)
+__global__ __launch_bounds__(kWarmupTile) void k_warmup_prepare(const Segment* __restrict__ segments, SegEntry* __restrict__ entries,
+                                                                uint32_t num_segments, uint32_t warmup_bytes, uint32_t spree_window,
+                                                                int32_t c0, int32_t c1, int32_t c2, int32_t c3, WarmupBuffers W) {
+  const uint32_t k = blockIdx.x * kWarmupTile + threadIdx.x;
+  if (k >= num_segments) return;
+  if (k == 0) W.fc_death[0] = num_segments;
+  const Segment g = segments[k];
+  SegEntry e{};
+  e.pos = g.start;
+  e.apply = g.start + spree_window;
+  e.cache[0] = c0;
+  e.cache[1] = c1;
+  e.cache[2] = c2;
+  e.cache[3] = c3;
+  if (k != 0) {
+    e.dict_lookups = kWarmAliveL;
+    e.dict_matches = kWarmAliveM;
+  }
+  entries[k] = e;
+  if (k + 1 < num_segments) {
+    const Segment dry = warmup_segment(g, warmup_bytes);
+    W.segs[k] = dry;
+    W.entries[k] = warmup_entry(e, dry, spree_window, false);
+  }
+}
+
+// inclusive scan of one op per thread over the workgroup (kWarmupTile threads); sh: [2 * kWarmupTile]
+__device__ __forceinline__ WarmupOp warmup_block_scan(WarmupOp v, WarmupOp* sh) {
+  const uint32_t t = threadIdx.x;
+  uint32_t cur = 0;
+  __syncthreads();  // (the scan in front of this one has been read)
+  sh[t] = v;
+  __syncthreads();
+  for (uint32_t off = 1; off < kWarmupTile; off <<= 1) {
+    WarmupOp r = sh[cur * kWarmupTile + t];
+    if (t >= off) r = warmup_combine(sh[cur * kWarmupTile + t - off], r);
+    cur ^= 1u;
+    sh[cur * kWarmupTile + t] = r;
+    __syncthreads();
+  }
+  return sh[cur * kWarmupTile + t];
+}
+
+__device__ __forceinline__ WarmupOp warmup_op_of(const Segment* segments, const WarmupBuffers& W, uint32_t i, uint32_t count, uint32_t warmup_bytes) {
+  if (i >= count) return warmup_identity();
+  return warmup_op(segments[i], W.exits[i], W.entries[i].dict_lookups, W.entries[i].dict_matches, warmup_bytes);
+}
+
+// the aggregate of every tile of dry runs
+__global__ __launch_bounds__(kWarmupTile) void k_warmup_tile_ops(const Segment* __restrict__ segments, WarmupShape S, WarmupBuffers W) {
+  __shared__ WarmupOp sh[2 * kWarmupTile];
+  const uint32_t count = S.num_segments - 1;
+  const WarmupOp o = warmup_block_scan(warmup_op_of(segments, W, blockIdx.x * kWarmupTile + threadIdx.x, count, S.warmup_bytes), sh);
+  if (threadIdx.x == kWarmupTile - 1) W.tile_ops[blockIdx.x] = o;
+}
+
+// what lies in front of every tile: an exclusive scan of the aggregates, kWarmupTile tiles at a time with a carry (one workgroup)
+__global__ __launch_bounds__(kWarmupTile) void k_warmup_tile_carry(uint32_t tiles, WarmupBuffers W) {
+  __shared__ WarmupOp sh[2 * kWarmupTile];
+  __shared__ WarmupOp carry;
+  if (threadIdx.x == 0) carry = warmup_identity();
+  for (uint32_t base = 0; base < tiles; base += kWarmupTile) {
+    const uint32_t i = base + threadIdx.x;
+    const WarmupOp own = i < tiles ? W.tile_ops[i] : warmup_identity();
+    const WarmupOp incl = warmup_block_scan(own, sh);  // (its first barrier also publishes `carry`)
+    const WarmupOp upto = warmup_combine(carry, incl);
+    // exclusive: everything up to the tile in front
+    __syncthreads();
+    sh[threadIdx.x] = upto;
+    __syncthreads();
+    if (i < tiles) W.tile_ops[tiles + i] = threadIdx.x == 0 ? carry : sh[threadIdx.x - 1];
+    __syncthreads();
+    if (threadIdx.x == kWarmupTile - 1) carry = upto;
+  }
+}
+
+// the entry of segment i + 1 from the dry run of segment i (all but the phase of a literal spree), and the forecast
+__global__ __launch_bounds__(kWarmupTile) void k_warmup_entries(const Segment* __restrict__ segments, SegEntry* __restrict__ entries,
+                                                                WarmupShape S, uint32_t max_backward_limit, uint32_t use_dictionary,
+                                                                uint32_t tiles, WarmupBuffers W) {
+  __shared__ WarmupOp sh[2 * kWarmupTile];
+  const uint32_t count = S.num_segments - 1;
+  const uint32_t i = blockIdx.x * kWarmupTile + threadIdx.x;
+  const WarmupOp incl = warmup_block_scan(warmup_op_of(segments, W, i, count, S.warmup_bytes), sh);
+  if (i >= count) return;
+  const WarmupOp upto = warmup_combine(W.tile_ops[tiles + blockIdx.x], incl);
+  SegEntry e = entries[i + 1];
+  int32_t base[4];
+  for (int c = 0; c < 4; ++c) base[c] = entries[0].cache[c];  // (entry 0 is nobody's to write)
+  warmup_apply_cache(upto, base, e.cache);
+  warmup_entry_from_exit(segments[i], segments[i + 1], W.exits[i], max_backward_limit, &e);
+  entries[i + 1] = e;
+  if (use_dictionary && warmup_dictionary_dies(upto.sl, upto.sm, S.warmup_bytes, S.segment_bytes)) atomicMin(W.fc_death, i);
+}
+
+// "dead" counters behind the forecast death, and the phase of a literal spree carried through every run of segments without
+// commands: the thread of a run's first segment walks it (a run ends with its block at the latest)
+__global__ __launch_bounds__(kWarmupTile) void k_warmup_finish(const Segment* __restrict__ segments, SegEntry* __restrict__ entries,
+                                                               WarmupShape S, uint32_t htl, uint32_t spree_window, uint32_t use_dictionary,
+                                                               WarmupBuffers W) {
+  const uint32_t k = blockIdx.x * kWarmupTile + threadIdx.x;
+  if (k >= S.num_segments) return;
+  if (use_dictionary && k > W.fc_death[0]) {
+    entries[k].dict_lookups = kWarmDeadL;
+    entries[k].dict_matches = kWarmDeadM;
+  }
+  const uint32_t count = S.num_segments - 1;
+  if (!S.spree_guess || k >= count) return;
+  // (of the entries this kernel reads ext_allowed, which it does not write, everywhere; position and head only at a run's start,
+  // where no walk writes them)
+  auto carries = [&](uint32_t j) {
+    SegEntry probe{};
+    probe.ext_allowed = entries[j].ext_allowed;
+    return warmup_spree_carries(segments[j], segments[j + 1], probe, W.exits[j]);
+  };
+  if (!carries(k) || (k > 0 && carries(k - 1))) return;
+  SegEntry cur{};
+  cur.pos = entries[k].pos;
+  cur.apply = entries[k].apply;
+  cur.head_kind = entries[k].head_kind;
+  cur.head_base = entries[k].head_base;
+  cur.head_p1 = entries[k].head_p1;
+  for (uint32_t j = k; j < count && (j == k || carries(j)); ++j) {
+    SegEntry next{};
+    warmup_spree_step(htl, spree_window, segments[j], cur, &next);
+    entries[j + 1].pos = next.pos;
+    entries[j + 1].apply = next.apply;
+    entries[j + 1].head_kind = next.head_kind;
+    entries[j + 1].head_base = next.head_base;
+    entries[j + 1].head_p1 = next.head_p1;
+    cur = next;
+  }
+}
+
+void lz77_warmup_prepare(const Lz77Params& P, const Lz77Buffers& B, const WarmupShape& S, const WarmupBuffers& W, const int32_t base_cache[4]) {
+  if (S.num_segments == 0) return;
+  hipLaunchKernelGGL(k_warmup_prepare, dim3((S.num_segments + kWarmupTile - 1) / kWarmupTile), dim3(kWarmupTile), 0, BR_STREAM, B.segments,
+                     B.entries, S.num_segments, S.warmup_bytes, P.spree_window, base_cache[0], base_cache[1], base_cache[2], base_cache[3], W);
+  HIP_CHECK(hipGetLastError());
+}
+
+void lz77_warmup_compose(const Lz77Params& P, const Lz77Buffers& B, const WarmupShape& S, const WarmupBuffers& W) {
+  if (S.num_segments < 2) return;
+  const uint32_t tiles = (S.num_segments - 1 + kWarmupTile - 1) / kWarmupTile;
+  hipLaunchKernelGGL(k_warmup_tile_ops, dim3(tiles), dim3(kWarmupTile), 0, BR_STREAM, B.segments, S, W);
+  hipLaunchKernelGGL(k_warmup_tile_carry, dim3(1), dim3(kWarmupTile), 0, BR_STREAM, tiles, W);
+  hipLaunchKernelGGL(k_warmup_entries, dim3(tiles), dim3(kWarmupTile), 0, BR_STREAM, B.segments, B.entries, S, P.max_backward_limit,
+                     P.use_dictionary, tiles, W);
+  hipLaunchKernelGGL(k_warmup_finish, dim3((S.num_segments + kWarmupTile - 1) / kWarmupTile), dim3(kWarmupTile), 0, BR_STREAM, B.segments,
+                     B.entries, S, P.htl, P.spree_window, P.use_dictionary, W);
+  HIP_CHECK(hipGetLastError());
 }
 
 // ------------------------------------------------------------------------------------------ flag diff

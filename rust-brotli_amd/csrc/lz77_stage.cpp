@@ -17,6 +17,10 @@
 
 #include <cmath>
 
+#if defined(BROTLI_HOST_EMU)
+#include "lz77_warmup_emu.inc"  // the host emulation of lz77_warmup_prepare / lz77_warmup_compose
+#endif
+
 namespace brotli_mi355x {
 
 void Lz77Stage::Release() {
@@ -391,10 +395,10 @@ struct DictTracker {
   int64_t slack = 0;
   uint32_t left_alive_at = 0xffffffffu;  // segment at which the dictionary (probably) went off
   uint32_t flips = 0;        // chains behind that point that ran with a live dictionary and must be redone
-  static constexpr uint32_t kDeadL = 0x40000000u, kDeadM = 0;
+  static constexpr uint32_t kDeadL = kWarmDeadL, kDeadM = kWarmDeadM;  // (lz77_warmup.h: the device writes the same guesses)
   // first guess for chains whose true counters are not known yet: alive with a margin no chain can use up, so
   // that the chain reports its own deficit (dict_maxdef) instead of tripping over a made-up start of stream
-  static constexpr uint32_t kAliveL = 0, kAliveM = 0x01000000u;
+  static constexpr uint32_t kAliveL = kWarmAliveL, kAliveM = kWarmAliveM;
   static constexpr int64_t kSlackPerChain = 256;
   void Hint(SegEntry* e) const {
     switch (state) {
@@ -537,44 +541,7 @@ static void PredictLiteralRunStepwise(const Lz77Params& P, const Segment& seg, c
 }
 
 static void PredictLiteralRun(const Lz77Params& P, const Segment& seg, const SegEntry& e, SegExit* x) {
-  const uint64_t pos_end = seg.blk_end, htl = P.htl, window = P.spree_window;
-  const uint64_t margin = htl - 1 > 4 ? htl - 1 : 4;
-  uint64_t position = e.pos;
-  const uint64_t apply = e.apply;
-  uint32_t tail_kind = e.head_kind;
-  uint64_t tail_base = e.head_base;
-  // the loop runs while position < stop
-  const uint64_t stop = std::min<uint64_t>(pos_end > htl ? pos_end - htl : 0, seg.end);
-  // one position at a time up to `apply`
-  if (position < stop && position < apply) position = std::min(stop, apply);
-  // strides: a step from p looks at p' = p + 1.  p' + 16 >= pos_end - margin ends the block; p' <= apply + 4 * window
-  // jumps 8 on (stride 9), anything later 16 (stride 17).
-  const uint64_t block_tail = pos_end > margin + 16 ? pos_end - margin - 16 : 0;  // p' >= block_tail: the end-of-block step
-  auto stride = [&](uint64_t step, uint64_t p_limit, uint32_t kind) {
-    // steps from positions p = position, position + step, ... while p < stop, p + 1 < block_tail and p + 1 <= p_limit
-    uint64_t bound = stop;                                         // p < bound
-    bound = std::min(bound, block_tail > 0 ? block_tail - 1 : 0);  // p + 1 < block_tail
-    bound = std::min(bound, p_limit);                              // p + 1 <= p_limit  <=>  p < p_limit
-    if (position >= bound) return;
-    const uint64_t n = (bound - position + step - 1) / step;
-    tail_kind = kind;
-    tail_base = position + (n - 1) * step + 1;
-    position += n * step;
-  };
-  if (position < stop) stride(9, apply + 4 * window, kHeadEven4);
-  if (position < stop && position + 1 > apply + 4 * window) stride(17, ~0ull >> 1, kHeadVec4);
-  if (position < stop && position + 1 >= block_tail && position + 1 > apply) {
-    tail_kind = kHeadUnstored;
-    tail_base = position + 1;
-    position = pos_end;
-  }
-  if (seg.flags & kSegLastInBlock) position = pos_end;
-  x->pos = (uint32_t)position;
-  x->apply = (uint32_t)apply;
-  x->insert_len = (uint32_t)position - e.pos;
-  x->tail_kind = position > seg.end ? tail_kind : (uint32_t)kHeadNone;
-  x->tail_base = position > seg.end ? (uint32_t)tail_base : 0u;
-  x->tail_p1 = position > seg.end ? e.head_p1 : 0u;
+  warmup_predict_literal_run(P.htl, P.spree_window, seg, e, x);
   static const bool selftest = getenv("BROTLI_MI355X_SELFTEST") != nullptr || getenv("BROTLI_MI355X_SELFTEST_RESOLVE") != nullptr;
   if (selftest) {
     SegExit y = *x;
@@ -1118,14 +1085,12 @@ void Lz77Stage::Warmup(uint32_t first_seg, bool dict_dead, int which, int rbuf, 
 
 // The dry runs of segments [first_seg, end_seg) are queued (WarmupBegin) and their results turned into entries (WarmupEnd) in
 // two steps: the host works on one half of the input's dry runs while the device is busy with the other half's (RunRounds).
-void Lz77Stage::WarmupBegin(WarmupJob* job, uint32_t first_seg, uint32_t end_seg, bool dict_dead, int which, int rbuf,
-                            const std::vector<uint8_t>* only_after_dirty, int mark) {
+uint32_t Lz77Stage::WarmupPlan(WarmupJob* job, uint32_t first_seg, uint32_t end_seg, bool dict_dead, const std::vector<uint8_t>* only_after_dirty) {
   const uint32_t nseg = (uint32_t)segments_.size();
   job->count = 0;
   job->dict_dead = dict_dead;
   job->whole_input = only_after_dirty == nullptr;
-  job->mark = mark;
-  if (first_seg + 1 >= nseg) return;
+  if (first_seg + 1 >= nseg) return 0;
   // dry-run segment k to get a guess for the entry of k + 1; with only_after_dirty, just where both k and k + 1 are
   // about to be re-parsed (otherwise the resolver already chained the exact entry from a valid parse of k)
   std::vector<uint32_t>& ks = job->ks;
@@ -1134,28 +1099,28 @@ void Lz77Stage::WarmupBegin(WarmupJob* job, uint32_t first_seg, uint32_t end_seg
     if (!only_after_dirty || ((*only_after_dirty)[k] && (*only_after_dirty)[k + 1])) ks.push_back(k);
   const uint32_t count = (uint32_t)ks.size();
   job->count = count;
-  if (count == 0) return;
+  if (count == 0) return 0;
   // (page-locked like everything that moves every call: copies from pageable memory go through the runtime's staging)
+  job->wsegs.resize_discard(count);
+  job->wentries.resize_discard(count);
+  job->wexits.resize_discard(count);
+  for (uint32_t i = 0; i < count; ++i) {
+    const uint32_t k = ks[i];
+    job->wsegs[i] = warmup_segment(segments_[k], warmup_bytes_);
+    job->wentries[i] = warmup_entry(entries_[k], job->wsegs[i], P_.spree_window, dict_dead);
+  }
+  return count;
+}
+
+void Lz77Stage::WarmupBegin(WarmupJob* job, uint32_t first_seg, uint32_t end_seg, bool dict_dead, int which, int rbuf,
+                            const std::vector<uint8_t>* only_after_dirty, int mark) {
+  job->mark = mark;
+  job->launched = true;
+  const uint32_t count = WarmupPlan(job, first_seg, end_seg, dict_dead, only_after_dirty);
+  if (count == 0) return;
   PinnedArray<Segment>& wsegs = job->wsegs;
   PinnedArray<SegEntry>& wentries = job->wentries;
   PinnedArray<SegExit>& wexits = job->wexits;
-  wsegs.resize_discard(count);
-  wentries.resize_discard(count);
-  wexits.resize_discard(count);
-  for (uint32_t i = 0; i < count; ++i) {
-    const uint32_t k = ks[i];
-    Segment g = segments_[k];
-    const uint32_t len = g.end - g.start;
-    if (len > warmup_bytes_) g.start = g.end - warmup_bytes_;
-    g.flags = (g.flags & kSegTailStitched) | kSegWarmup;
-    wsegs[i] = g;
-    SegEntry e = entries_[k];
-    e.pos = g.start;
-    e.apply = g.start + P_.spree_window;
-    e.dict_lookups = dict_dead ? DictTracker::kDeadL : DictTracker::kAliveL;
-    e.dict_matches = dict_dead ? DictTracker::kDeadM : DictTracker::kAliveM;
-    wentries[i] = e;
-  }
   timeline().stamp("wu-prepared");
   Segment* wsegs_dev = job->mem.zeroed<Segment>(count * sizeof(Segment));
   SegEntry* wentries_dev = job->mem.zeroed<SegEntry>(count * sizeof(SegEntry));
@@ -1173,24 +1138,26 @@ void Lz77Stage::WarmupEnd(WarmupJob* job) {
   const uint32_t count = job->count;
   if (count == 0) return;
   const std::vector<uint32_t>& ks = job->ks;
-  PinnedArray<Segment>& wsegs = job->wsegs;
   PinnedArray<SegEntry>& wentries = job->wentries;
   PinnedArray<SegExit>& wexits = job->wexits;
   const bool dict_dead = job->dict_dead;
   const bool only_after_dirty = !job->whole_input;
-  dev_wait_mark_n(job->mark);
-  timeline().stamp("wu-exits");
-  job->mem.clear();
+  if (job->launched) {
+    dev_wait_mark_n(job->mark);
+    timeline().stamp("wu-exits");
+    job->mem.clear();
+  }
   if (!dict_dead && !only_after_dirty) {
-    // lookups / matches the dry runs saw, scaled to the whole segment: a forecast of where the throttle trips
+    // lookups / matches the dry runs saw, scaled to the whole segment: a forecast of where the throttle trips.  Exact integers
+    // in units of 1 / warmup_bytes_ (lz77_warmup.h): the device sums the same numbers in another order.
     if (warm_lookups_.size() != nseg || ks[0] == 0) {
-      warm_lookups_.assign(nseg, 0.0);
-      warm_matches_.assign(nseg, 0.0);
+      warm_lookups_.assign(nseg, 0);
+      warm_matches_.assign(nseg, 0);
     }
     for (uint32_t i = 0; i < count; ++i) {
-      const double scale = (double)(segments_[ks[i]].end - segments_[ks[i]].start) / (double)(wsegs[i].end - wsegs[i].start);
-      warm_lookups_[ks[i]] = scale * (double)(wexits[i].dict_lookups - wentries[i].dict_lookups);
-      warm_matches_[ks[i]] = scale * (double)(wexits[i].dict_matches - wentries[i].dict_matches);
+      const WarmupOp o = warmup_op(segments_[ks[i]], wexits[i], wentries[i].dict_lookups, wentries[i].dict_matches, warmup_bytes_);
+      warm_lookups_[ks[i]] = o.sl;
+      warm_matches_[ks[i]] = o.sm;
     }
   }
   for (uint32_t i = 0; i < count; ++i) {
@@ -2094,59 +2061,6 @@ void Lz77Stage::RunRounds(bool allow_restart) {
   if (selftest) {
     if (use_rows_) SelfTestRows(which); else SelfTestRank(which, rbuf);
   }
-  // ---- warm-up: a dry run over the tail of every segment gives a good first guess of the state in which the
-  // parse leaves it (greedy parses re-synchronise quickly), so that the first full round already starts
-  // almost every chain from its true entry.
-  if (const char* w = getenv("BROTLI_MI355X_WARMUP")) warmup_bytes_ = (uint32_t)atoi(w);
-  double fc_L = 0, fc_M = 0;  // the forecast's running sums
-  uint32_t fc_death = nseg;
-  bool fc_found = false;
-  // forecast of the segment in which the static dictionary gets switched off (matches < lookups >> 7,
-  // mod.rs:1957-1960); chains behind it start with the "off" guess.  A wrong forecast only costs re-parses of
-  // the chains that actually used / could have used a dictionary match (DictTracker::Consume).
-  // Guessing "off" too early is the expensive mistake (a chain that ran without the dictionary cannot tell what
-  // it would have counted, so the exact counters can only advance one redone chain per round), guessing "on" too
-  // long only costs the re-parse of the chains that really used a dictionary match.  Hence a forecast three
-  // standard deviations of the sampled match count on the late side.
-  auto forecast = [&](uint32_t from, uint32_t upto) {  // segments [from, upto), in order
-    if (!(P_.use_dictionary && warm_lookups_.size() == nseg)) return;
-    const double sample = (double)warmup_bytes_ / (double)segment_bytes_;
-    for (uint32_t k = from; k < upto && !fc_found; ++k) {
-      fc_L += warm_lookups_[k];
-      fc_M += warm_matches_[k];
-      const double sigma = std::sqrt(std::max(1.0, fc_M * sample)) / sample;
-      if (fc_L >= 256.0 && fc_M + 3.0 * sigma < fc_L / 128.0) {
-        fc_death = k;
-        fc_found = true;
-      }
-    }
-    if (upto == nseg || fc_found) {
-      for (uint32_t k = fc_death + 1; k < nseg; ++k) {
-        entries_[k].dict_lookups = DictTracker::kDeadL;
-        entries_[k].dict_matches = DictTracker::kDeadM;
-      }
-      touch_all_ = true;
-      predicted_death_ = fc_death;
-    }
-  };
-  if (nseg > 1 && warmup_bytes_ > 0) {
-    Warmup(0, false, which, rbuf, nullptr);
-    timeline().stamp("warmed-up");
-    forecast(0, nseg);
-    tm.stop(&stats_.ms_warmup);
-  }
-  if (!allow_restart && !saved_block_guess_.empty()) {
-    // second pass after a coarse restart: the first pass chained the distance cache through every segment of the
-    // input, which beats the dry run's view of the last few hundred bytes of each block
-    for (uint32_t k = 0; k < nseg; ++k) {
-      if (!(segments_[k].flags & kSegFirstInBlock)) continue;
-      auto it = saved_block_guess_.find(segments_[k].blk_start);
-      if (it == saved_block_guess_.end()) continue;
-      memcpy(entries_[k].cache, it->second.cache, sizeof(entries_[k].cache));
-      entries_[k].ext_allowed = it->second.ext_allowed;
-      touch_all_ = true;
-    }
-  }
   // ---- rounds.  Round 0 parses every segment; later rounds re-parse only the segments whose entry state
   // changed or that searched a position whose candidate list changed with the flags (lz77_validate).
   SegGeometry geo{};
@@ -2228,13 +2142,97 @@ void Lz77Stage::RunRounds(bool allow_restart) {
   bool full_round = true;
   uint32_t last_death_seg = 0xffffffffu;
   auto stamp = [&](const char* what) { timeline().stamp(what); };  // BROTLI_MI355X_TIMELINE
+  // Everything above is queued (and allocated) in front of the dry runs: between their launch and round 0 the stream holds nothing
+  // but what depends on them (the kernels that compose the entries; on the host path the exits coming down and the entries going
+  // up).  Round 0's copy of the flags goes first as well: a dry run writes nothing but its exit (lz77_chain.h,
+  // FlagWriter::enabled), so the two arrays still agree when round 0 starts.
+  dev_d2d(B_.flags[which ^ 1], B_.flags[which], (size_t)P_.total_bytes + 64);
+  bool flags_copied = true;
+  // ---- warm-up: a dry run over the tail of every segment gives a good first guess of the state in which the
+  // parse leaves it (greedy parses re-synchronise quickly), so that the first full round already starts
+  // almost every chain from its true entry.
+  if (const char* w = getenv("BROTLI_MI355X_WARMUP")) warmup_bytes_ = (uint32_t)atoi(w);
+  uint64_t fc_L = 0, fc_M = 0;  // the forecast's running sums (WarmupOp::sl / sm, lz77_warmup.h)
+  uint32_t fc_death = nseg;
+  bool fc_found = false;
+  // forecast of the segment in which the static dictionary gets switched off (matches < lookups >> 7,
+  // mod.rs:1957-1960); chains behind it start with the "off" guess.  A wrong forecast only costs re-parses of
+  // the chains that actually used / could have used a dictionary match (DictTracker::Consume).
+  // Guessing "off" too early is the expensive mistake (a chain that ran without the dictionary cannot tell what
+  // it would have counted, so the exact counters can only advance one redone chain per round), guessing "on" too
+  // long only costs the re-parse of the chains that really used a dictionary match.  Hence a forecast three
+  // standard deviations of the sampled match count on the late side (warmup_dictionary_dies).
+  auto forecast = [&](uint32_t from, uint32_t upto) {  // segments [from, upto), in order
+    if (!(P_.use_dictionary && warm_lookups_.size() == nseg)) return;
+    for (uint32_t k = from; k < upto && !fc_found; ++k) {
+      fc_L += warm_lookups_[k];
+      fc_M += warm_matches_[k];
+      if (warmup_dictionary_dies(fc_L, fc_M, warmup_bytes_, segment_bytes_)) {
+        fc_death = k;
+        fc_found = true;
+      }
+    }
+    if (upto == nseg || fc_found) {
+      for (uint32_t k = fc_death + 1; k < nseg; ++k) {
+        entries_[k].dict_lookups = DictTracker::kDeadL;
+        entries_[k].dict_matches = DictTracker::kDeadM;
+      }
+      touch_all_ = true;
+      predicted_death_ = fc_death;
+    }
+  };
+  // Where the entries of round 0 are composed.  On the device (lz77_warmup.h): the dry runs' segments and entries are derived
+  // there, kernels behind the dry runs write B.entries from their exits, and round 0 is queued behind those without the host
+  // having waited for anything; entries_, the forecast and (under the self-test) the dry runs' exits come back with the exits of
+  // round 0.  On the host (Warmup + forecast): after a coarse restart, whose saved guesses go on top of the dry runs', and with
+  // BROTLI_MI355X_HOST_WARMUP=1; the regime flips of later rounds dry-run a few segments the same way.
+  static const bool host_warmup = getenv("BROTLI_MI355X_HOST_WARMUP") != nullptr;
+  static const bool no_spree_guess = getenv("BROTLI_MI355X_NO_SPREE_GUESS") != nullptr;
+  const bool warm = nseg > 1 && warmup_bytes_ > 0;
+  bool entries_on_device = warm && !host_warmup && (allow_restart || saved_block_guess_.empty());
+  DevBlocks warm_mem;
+  WarmupBuffers WB{};
+  std::vector<SegEntry> warm_entries_dev;  // self-test: what the device composed
+  WarmupJob warm_check;                    // self-test: the same dry runs, for the host's WarmupEnd
+  if (entries_on_device) {
+    const uint32_t dry = nseg - 1, tiles = (dry + kWarmupTile - 1) / kWarmupTile;
+    WarmupShape shape{nseg, warmup_bytes_, segment_bytes_, no_spree_guess ? 0u : 1u};
+    WB.segs = warm_mem.uninit<Segment>((size_t)dry * sizeof(Segment) + 64);
+    WB.entries = warm_mem.uninit<SegEntry>((size_t)dry * sizeof(SegEntry) + 64);
+    WB.exits = warm_mem.zeroed<SegExit>((size_t)dry * sizeof(SegExit) + 64);
+    WB.tile_ops = warm_mem.uninit<WarmupOp>((size_t)tiles * 2 * sizeof(WarmupOp) + 64);
+    WB.fc_death = warm_mem.zeroed<uint32_t>(64);
+    lz77_warmup_prepare(P_, B_, shape, WB, entries_[0].cache);
+    lz77_parse_custom(P_, B_, which, rbuf, WB.segs, WB.entries, WB.exits, dry);
+    lz77_warmup_compose(P_, B_, shape, WB);
+    timeline().stamp("warm-up queued");
+    if (!selftest) stats_.segments_parsed += (uint64_t)dry * warmup_bytes_ / segment_bytes_;  // (the self-test's WarmupEnd counts them)
+    touch_all_ = true;
+  } else if (warm) {
+    Warmup(0, false, which, rbuf, nullptr);
+    timeline().stamp("warmed-up");
+    forecast(0, nseg);
+    tm.stop(&stats_.ms_warmup);
+  }
+  if (!allow_restart && !saved_block_guess_.empty()) {
+    // second pass after a coarse restart: the first pass chained the distance cache through every segment of the
+    // input, which beats the dry run's view of the last few hundred bytes of each block
+    for (uint32_t k = 0; k < nseg; ++k) {
+      if (!(segments_[k].flags & kSegFirstInBlock)) continue;
+      auto it = saved_block_guess_.find(segments_[k].blk_start);
+      if (it == saved_block_guess_.end()) continue;
+      memcpy(entries_[k].cache, it->second.cache, sizeof(entries_[k].cache));
+      entries_[k].ext_allowed = it->second.ext_allowed;
+      touch_all_ = true;
+    }
+  }
   for (uint32_t round = 0; round < max_rounds && !done; ++round) {
     stats_.rounds++;
     stamp("| round");
     tm.stop(&stats_.ms_resolve);
     // upload the entries of the segments to parse, run them, fetch their exits
     if (full_round) {
-      dev_h2d(B_.entries, entries_.data(), (size_t)nseg * sizeof(SegEntry));
+      if (!entries_on_device) dev_h2d(B_.entries, entries_.data(), (size_t)nseg * sizeof(SegEntry));
     } else {
       // only the entries the host changed since the last launch: those of the listed segments and those whose distance
       // cache RecheckCacheOnly() accepted
@@ -2305,7 +2303,8 @@ void Lz77Stage::RunRounds(bool allow_restart) {
       dev_sync();
       stamp("burst-done");
     } else {
-    dev_d2d(B_.flags[which ^ 1], B_.flags[which], (size_t)P_.total_bytes + 64);
+    if (!flags_copied) dev_d2d(B_.flags[which ^ 1], B_.flags[which], (size_t)P_.total_bytes + 64);
+    flags_copied = false;
     stamp("uploaded");
     if (full_round) {
       lz77_parse_round(P_, B_, which, rbuf, 0);
@@ -2344,6 +2343,17 @@ void Lz77Stage::RunRounds(bool allow_restart) {
     if (full_round) {
       dev_d2h_async(exits_.data(), B_.exits, (size_t)nseg * sizeof(SegExit));
       touch_all_ = true;
+      if (entries_on_device) {
+        // what the kernels behind the dry runs composed (a full round rewrites no entry): behind round 0, off the path between
+        // the two launches
+        if (selftest) {
+          warm_entries_dev.resize(nseg);
+          WarmupPlan(&warm_check, 0, nseg, false, nullptr);
+          dev_d2h_async(warm_check.wexits.data(), WB.exits, (size_t)(nseg - 1) * sizeof(SegExit));
+        }
+        dev_d2h_async(selftest ? warm_entries_dev.data() : entries_.data(), B_.entries, (size_t)nseg * sizeof(SegEntry));
+        dev_d2h_async(&warm_fc_death_, WB.fc_death, 4);
+      }
     } else {
       // the exits of the listed segments, and exit + rewritten entry of the segments that chains continued into (the
       // first kContFirst of them ride along; more are rare and fetched afterwards)
@@ -2372,6 +2382,30 @@ void Lz77Stage::RunRounds(bool allow_restart) {
     }
     }
     const uint32_t n_changed = counts[0], n_cont = counts[1];
+    if (entries_on_device) {
+      entries_on_device = false;
+      if (selftest) {
+        // the host's WarmupEnd and forecast on the same exits: all 16 words of every entry and the forecast must agree
+        warm_check.launched = false;
+        WarmupEnd(&warm_check);
+        forecast(0, nseg);
+        static_assert(sizeof(SegEntry) == 64, "16 words");
+        for (uint32_t k = 0; k < nseg; ++k) {
+          uint32_t host_words[16], dev_words[16];
+          memcpy(host_words, &entries_[k], 64);
+          memcpy(dev_words, &warm_entries_dev[k], 64);
+          for (uint32_t w = 0; w < 16; ++w)
+            if (host_words[w] != dev_words[w])
+              throw std::runtime_error("selftest: entry composed on the device differs from the host's (segment " + std::to_string(k) + ", word " +
+                                       std::to_string(w) + ": " + std::to_string(dev_words[w]) + " vs " + std::to_string(host_words[w]) + ")");
+        }
+        if (fc_death != warm_fc_death_)
+          throw std::runtime_error("selftest: forecast of the dictionary's death differs (device segment " + std::to_string(warm_fc_death_) +
+                                   ", host " + std::to_string(fc_death) + ")");
+      }
+      if (P_.use_dictionary) predicted_death_ = warm_fc_death_;
+      warm_mem.clear();
+    }
     if (!full_round && !burst) {
       for (uint32_t i = 0; i < count; ++i) {
         exits_[list[i]] = got_exits[i];

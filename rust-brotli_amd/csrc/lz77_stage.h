@@ -182,8 +182,11 @@ class Lz77Stage {
     DevBlocks mem;  // the device side of the three, from WarmupBegin to WarmupEnd
     uint32_t count = 0;
     bool dict_dead = false, whole_input = true;
+    bool launched = true;  // false: the exits were fetched some other way (self-test of the entries composed on the device)
     int mark = 0;
   };
+  // fills ks / wsegs / wentries of the job; returns the number of dry runs
+  uint32_t WarmupPlan(WarmupJob* job, uint32_t first_seg, uint32_t end_seg, bool dict_dead, const std::vector<uint8_t>* only_after_dirty);
   void Warmup(uint32_t first_seg, bool dict_dead, int which, int rbuf, const std::vector<uint8_t>* only_after_dirty);
   void WarmupBegin(WarmupJob* job, uint32_t first_seg, uint32_t end_seg, bool dict_dead, int which, int rbuf,
                    const std::vector<uint8_t>* only_after_dirty, int mark);
@@ -228,7 +231,9 @@ class Lz77Stage {
   std::vector<uint32_t> block_first_segment_, block_segment_bytes_;  // per input block (+ one-past-the-end entry)
   std::vector<uint8_t> coarse_blocks_;  // blocks that are parsed by a single chain
   uint32_t total_cmd_slots_ = 0;
-  std::vector<double> warm_lookups_, warm_matches_;  // per segment, forecast from the warm-up dry run
+  // per segment, from the warm-up dry run: lookups / matches x bytes of the segment (WarmupOp::sl / sm, lz77_warmup.h)
+  std::vector<uint64_t> warm_lookups_, warm_matches_;
+  uint32_t warm_fc_death_ = 0;  // fetched with the exits of round 0 when the device composed the entries
   uint32_t predicted_death_ = 0xffffffffu;
   int final_flags_ = 0;
   const StreamCarry* carry_ = nullptr;
