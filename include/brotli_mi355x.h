@@ -189,7 +189,9 @@ int32_t BrotliMi355xConcatChunkEnds(size_t num_chunks, const uint8_t* heads, con
                                     const size_t* chunk_sizes, size_t* encoded_size, uint8_t* encoded,
                                     size_t* body_copies);
 /* One-shot compression of a buffer that is already resident in device memory; per-stage timings (ms) are
-   returned in stats[0..32) (may be NULL).  Same stream as BrotliEncoderCompress on the same bytes. */
+   returned in stats[0..32) (may be NULL).  Same stream as BrotliEncoderCompress on the same bytes.
+   Ordering: the call works on the calling thread's stream; whatever produced the input must be complete before the call (it does
+   not wait for other streams), and the call returns when the stream is in `encoded_host`. */
 BROTLI_BOOL BrotliMi355xCompressDevice(int quality, int lgwin, BrotliEncoderMode mode, size_t input_size,
                                        const uint8_t* input_device, size_t* encoded_size, uint8_t* encoded_host,
                                        double* stats);
@@ -321,6 +323,39 @@ int32_t BrotliMi355xCompressBatchWithDictionary(int quality, int lgwin, BrotliEn
 int32_t BrotliMi355xCompressBatchEx(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t count,
                                     const uint8_t* const* inputs, const size_t* input_sizes, uint8_t* const* outputs,
                                     size_t* output_sizes /* in: capacity, out: size */, int32_t* item_results /* may be NULL */);
+/* BrotliMi355xCompressBatchEx on device memory: many items that lie in device memory, their streams left in device memory.  It is
+   that call in every respect but one: inputs_device[i] and outputs_device[i] are device addresses on the calling thread's current
+   device.  The four arrays themselves (inputs_device, input_sizes, outputs_device, output_sizes) and item_results are host memory,
+   as there.  The addresses may have any alignment, and several may point into one allocation (one tensor of items, one of streams).
+   Per item: exactly what BrotliEncoderCompress(quality, lgwin, mode, input_sizes[i], <the bytes at inputs_device[i]>,
+   &output_sizes[i], ...) gives -- bytes, size, success or failure: the empty item is the byte 0x06 (written to device memory), an
+   item of capacity 0 or with a buffer too small fails alone (size 0), and an item whose stream exceeds
+   BrotliEncoderMaxCompressedSize goes out as the stored stream of its input where the capacity allows (produced on the device).
+   `routes` takes the same five bits with the same eligibility rules, the same reserved or unknown values fail the whole call,
+   BrotliMi355xLastBatchInfo means what it means there, and a device error fails the whole call in the same way.
+   On the side-by-side routes (info[1], qualities 2 .. 11) no item byte and no stream byte crosses the bus: one launch gathers a
+   group's items from their addresses, one launch scatters its streams to theirs.  The other items:
+     - at qualities 2 .. 11 an item that does not go side by side runs through the device one-shot path by itself, as
+       BrotliMi355xCompressDevice does; its stream passes through host memory on its way to outputs_device[i];
+     - at qualities 0 and 1 the fragment path takes its input from host memory: the items are downloaded once per call and their
+       streams uploaded -- the same bytes and the same info as the host call, and no gain over it.
+   Memory contract.  The library reads only the aligned 4-byte words that hold at least one byte of an item; it never reads behind an
+   item's last word.  On return it has written exactly outputs_device[i][0 .. output_sizes[i]), and never a byte outside
+   [0, capacity); an item that fails leaves the contents of its buffer unspecified, but stays inside it.  Outputs must not overlap
+   each other or any input; they may abut.
+   Ordering.  The call works on the calling thread's stream and returns after everything it wrote has landed (one synchronisation
+   at the end).  Whatever produced the inputs must be complete before the call: it does not wait for other streams.
+   No dictionary: the three dictionary batch calls take host memory only.
+   When to use it: when the payloads already lie in device memory, or the streams are wanted there.  Measured on an MI355X against
+   BrotliMi355xCompressBatchEx on the same items from page-locked host memory, min .. max of five alternating runs, text: 4096 items
+   of 4 KiB at quality 5 in 12.3 .. 12.4 ms against 16.0 .. 16.3 ms (and 16.7 .. 17.1 ms for download + host call + upload), at
+   quality 2 with BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS 11.1 .. 11.2 against 14.8 .. 14.9 ms, 1024 items of 16 KiB at quality 5
+   18.0 .. 18.1 against 20.8 .. 21.1 ms.  Where the parse dominates the staging is nothing: 256 items of 64 KiB at quality 9 with
+   BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS 137.3 .. 137.9 against 139.8 .. 144.9 ms, 64 items of 4 KiB at quality 5 4.31 .. 4.33 against
+   4.30 .. 4.33 ms -- no gain there, and none at qualities 0 and 1.  No measured shape is slower than the host call. */
+int32_t BrotliMi355xCompressBatchDevice(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t count,
+                                        const uint8_t* const* inputs_device, const size_t* input_sizes, uint8_t* const* outputs_device,
+                                        size_t* output_sizes /* in: capacity, out: size */, int32_t* item_results /* may be NULL */);
 /* BrotliMi355xCompressBatchWithDictionary with routes the caller opts into.  routes == 0 is that call in every respect.  The only
    route this call knows is BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS; any other bit -- the other routes of
    BrotliMi355xCompressBatchEx and the reserved values 2, 8 and 64 included -- fails the whole call as an unknown route fails that one

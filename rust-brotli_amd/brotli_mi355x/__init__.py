@@ -105,6 +105,10 @@ def _bind(lib):
         lib.BrotliMi355xCompressBatchWithDictionaries.argtypes = [c_int, c_int, c_int, c_uint32, c_size_t, POINTER(c_char_p), POINTER(c_size_t), c_size_t,
                                                                   POINTER(c_size_t), POINTER(c_char_p), POINTER(c_size_t), POINTER(c_void_p),
                                                                   POINTER(c_size_t), POINTER(c_int32)]
+    if hasattr(lib, "BrotliMi355xCompressBatchDevice"):
+        lib.BrotliMi355xCompressBatchDevice.restype = c_int32
+        lib.BrotliMi355xCompressBatchDevice.argtypes = [c_int, c_int, c_int, c_uint32, c_size_t, POINTER(c_void_p), POINTER(c_size_t), POINTER(c_void_p),
+                                                        POINTER(c_size_t), POINTER(c_int32)]
     lib.BrotliMi355xDeviceName.restype = c_char_p
     lib.BrotliMi355xLastError.restype = c_char_p
     return lib
@@ -380,6 +384,44 @@ class Library(object):
                 quality, lgwin, mode, routes, num, dicts, dict_sizes, count, item_dicts, inputs, in_sizes, outputs, out_sizes, results)
 
         return self._batch(items, 1024, call)
+
+    def compress_batch_device(self, inputs, outputs, quality=5, lgwin=22, mode=0, long_items=False, quick_items=False, quick_long_items=False,
+                              zopfli_items=False, q9_items=False):
+        """BrotliMi355xCompressBatchDevice: compress_batch for items that lie in device memory, their streams left in device
+        memory.  inputs: a sequence of (address, size), outputs: a sequence of (address, capacity), all plain integers (e.g.
+        t.data_ptr() + offset); the addresses may have any alignment and may point into one tensor each, outputs must not
+        overlap each other or any input.  Item i becomes the bytes compress(item, quality, lgwin, mode) gives, at outputs[i];
+        the flags are those of compress_batch, and last_batch_info() tells how the items were taken.  On the side-by-side
+        routes nothing crosses the bus; qualities 0 and 1 are staged through the host once per call (no gain over
+        compress_batch), and no dictionary is taken.  Whatever produced the inputs must be complete before the call
+        (torch.cuda.synchronize()); the call returns when every stream has landed.  Returns the list of stream sizes.
+
+        An item whose capacity is too small fails alone in the C call, which then returns 0: this method raises
+        BrotliCompressorException with .failed (the indices) and .sizes (the sizes of the others, 0 for a failed item; all 0
+        after a call that failed as a whole)."""
+        routes = (self.BATCH_ROUTE_LONG_ITEMS if long_items else 0) | (self.BATCH_ROUTE_QUICK_ITEMS if quick_items else 0)
+        routes |= self.BATCH_ROUTE_QUICK_LONG_ITEMS if quick_long_items else 0
+        routes |= self.BATCH_ROUTE_ZOPFLI_ITEMS if zopfli_items else 0
+        routes |= self.BATCH_ROUTE_Q9_ITEMS if q9_items else 0
+        inputs, outputs = list(inputs), list(outputs)
+        count = len(inputs)
+        if len(outputs) != count:
+            raise ValueError("%d inputs, %d outputs" % (count, len(outputs)))
+        if count == 0:
+            return []
+        in_ptrs = (c_void_p * count)(*[int(a) for a, _ in inputs])
+        in_sizes = (c_size_t * count)(*[int(n) for _, n in inputs])
+        out_ptrs = (c_void_p * count)(*[int(a) for a, _ in outputs])
+        out_sizes = (c_size_t * count)(*[int(n) for _, n in outputs])
+        results = (c_int32 * count)()
+        ok = self.lib.BrotliMi355xCompressBatchDevice(quality, lgwin, mode, routes, count, in_ptrs, in_sizes, out_ptrs, out_sizes, results)
+        sizes = [int(out_sizes[i]) if ok or results[i] else 0 for i in range(count)]
+        if not ok:
+            failed = [i for i in range(count) if not results[i]]
+            e = BrotliCompressorException("BrotliMi355xCompressBatchDevice failed (items %s): %s" % (failed[:8], self.last_error()))
+            e.failed, e.sizes = failed, sizes
+            raise e
+        return sizes
 
     def last_batch_info(self):
         """BrotliMi355xLastBatchInfo: the last compress_batch / compress_batch_with_dictionary / compress_batch_with_dictionaries call of this thread as a list of 8 integers -- [0] items, [1] items

@@ -120,11 +120,35 @@ void lz77_batch_dict_image(const Lz77Params& P, const uint16_t* keys, uint32_t d
 void lz77_batch_gather(const BatchParseJob& J, const uint32_t* offsets_dev, Command* out);
 
 // ---- host
+// What encoder_compress does with the stream its encoder made (encode.rs:1521-1538), decided from sizes alone: the stream goes out
+// if it fits the buffer and is no larger than BrotliEncoderMaxCompressedSize; otherwise the input goes out as a stored stream if
+// the buffer holds BrotliEncoderMaxCompressedSize bytes; otherwise the item fails.  One copy for every sink: the host buffers of
+// the batch and one-shot calls (cabi.cpp: OneShotDeliver) and the device buffers of BrotliMi355xCompressBatchDevice.
+enum class Delivery { kStream, kStored, kFails };
+inline Delivery DeliveryRule(size_t stream_size, size_t input_size, size_t capacity) {
+  const size_t max_out_size = MaxCompressedSize(input_size);
+  if (stream_size <= capacity && !(max_out_size != 0 && stream_size > max_out_size)) return Delivery::kStream;
+  return (max_out_size != 0 && capacity >= max_out_size) ? Delivery::kStored : Delivery::kFails;
+}
+// The device mode of the Batch*Compress calls below (BrotliMi355xCompressBatchDevice): inputs[i] is a device address, the group's
+// items come out of device memory (batch_device.h: batch_stage_device) and its output stays there; no stream comes to the host
+// (`streams` stays empty).  Every item the route answers -- all but the demoted ones and those the reference fails on -- gets
+// sizes[i] and results[i] by DeliveryRule, and its stream, or the stored stream of its input, at outputs[i].
+struct BatchDeviceSink {
+  uint8_t* const* outputs;   // [count] device addresses, any alignment
+  const size_t* capacities;  // [count]
+  size_t* sizes;             // [count], result
+  int32_t* results;          // [count], result: 1 = the item's stream lies at outputs[i], 0 = it fails alone
+};
+// MakeUncompressedStream (encode.rs:1388-1433) for an input that lies on the device: the header bytes go down with dev_h2d and the
+// body with dev_d2d, one pair per chunk of at most 1 << 24 bytes, and the final byte 3.  Returns the stream's size; the caller's
+// buffer holds BrotliEncoderMaxCompressedSize(input_size) bytes.
+size_t StoredStreamToDevice(const uint8_t* input_dev, size_t input_size, uint8_t* output_dev);
 // Does this item go side by side?  `params`: the caller's parameters as set (quality, lgwin, mode), not finalized.
 bool BatchGreedyEligible(const EncoderParams& params, size_t input_size);
 // The streams of `count` eligible items.  Throws std::runtime_error on a device error.  *groups: device groups run.
 void BatchGreedyCompress(const EncoderParams& params, size_t count, const uint8_t* const* inputs, const size_t* sizes,
-                         std::vector<std::vector<uint8_t>>* streams, uint32_t* groups);
+                         std::vector<std::vector<uint8_t>>* streams, uint32_t* groups, const BatchDeviceSink* sink = nullptr);
 // The same with a custom dictionary of 2 .. 65536 bytes (after the reference's truncation): item i is the stream of
 // BrotliEncoderSetCustomDictionary + one BrotliEncoderCompressStream(FINISH).  (*reference_fails)[i] != 0: the reference itself
 // fails on item i (a copy of one byte at the dictionary end); its stream stays empty.
@@ -143,14 +167,14 @@ bool BatchLongEligible(const EncoderParams& params, size_t input_size);
 // (*demoted)[i] != 0: a meta-block of item i that is not its last took the size fallback (encode.rs:2141-2163), which the chain
 // cannot know: the stream stays empty and the caller redoes the item through the one-shot path.
 void BatchLongCompress(const EncoderParams& params, size_t count, const uint8_t* const* inputs, const size_t* sizes,
-                       std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* demoted, uint32_t* groups);
+                       std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* demoted, uint32_t* groups, const BatchDeviceSink* sink = nullptr);
 
 // Qualities 9 and 10 (BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS): an item of at most one input block under the H9 hasher, lgwin 17 .. 24,
 // is one live chain on a private H9 table (64 KiB of counters, 32 MiB of buckets) and one meta-block, like an H5 item.  Quality 10
 // is taken as quality 9 first, as BrotliEncoderCompress does (encode.rs:1468-1481).  No item is demoted and none fails.
 bool BatchQ9Eligible(const EncoderParams& params, size_t input_size);
 void BatchQ9Compress(const EncoderParams& params, size_t count, const uint8_t* const* inputs, const size_t* sizes,
-                     std::vector<std::vector<uint8_t>>* streams, uint32_t* groups);
+                     std::vector<std::vector<uint8_t>>* streams, uint32_t* groups, const BatchDeviceSink* sink = nullptr);
 
 // One group through the meta-block stage (encoder.cpp): an entry is one meta-block; the meta-blocks of an item follow each other
 // and make a complete stream of their own.  An item of one meta-block leaves the fields behind `uncompressed` at zero.
@@ -167,8 +191,15 @@ struct BatchStreamItem {
                                  // parse behind it does not hold, the item's stream is not to be used
   uint64_t out_byte, out_bytes;  // result, on an item's first entry: where its stream lies in `out`
 };
+// keep != nullptr: the group's output is not downloaded (`out` stays empty); it stays on the device in a block of keep->owner, and
+// keep->bytes says where: BatchStreamItem::out_byte counts from there.
+class DevBlocks;
+struct BatchOutputOnDevice {
+  DevBlocks* owner;
+  const uint8_t* bytes;  // result
+};
 void EncodeBatchMetaBlocks(const EncoderParams& finalized, const uint8_t* packed_text_dev, const Command* cmds_dev, uint32_t n_cmds,
-                           std::vector<BatchStreamItem>* items, std::vector<uint8_t>* out);
+                           std::vector<BatchStreamItem>* items, std::vector<uint8_t>* out, BatchOutputOnDevice* keep = nullptr);
 
 }  // namespace brotli_mi355x
 #endif

@@ -11,10 +11,12 @@
 #include <stdexcept>
 #include <utility>
 
+#include "batch_device.h"
 #include "batch_quick.h"
 #include "batch_zopfli.h"
 #include "device_api.h"
 #if defined(BROTLI_HOST_EMU)
+#include "batch_device_emu.inc"  // the host emulation of batch_stage_device / batch_deliver / batch_gather_context
 #include "batch_greedy_emu.inc"  // the host emulation of lz77_batch_parse / lz77_batch_gather
 #include "batch_quick_emu.inc"   // ... and of lz77_quick_batch_parse
 #include "batch_zopfli_emu.inc"  // ... and of lz77_zopfli_batch_parse
@@ -159,6 +161,7 @@ struct CallArrays {
   PinnedArray<uint8_t> dict_pool;
   PinnedArray<BatchRecord> records;
   PinnedArray<BatchLongRecord> long_records;
+  PinnedArray<const uint8_t*> sources;  // items in device memory: their addresses
 };
 // one group, staged and uploaded: the caller's items [first, last)
 struct Group {
@@ -171,6 +174,7 @@ struct Group {
   size_t cmd_slots;
   uint32_t tables;
   uint8_t* uploaded;  // on the device, like the two below
+  bool on_device;     // the caller's items lie in device memory: `uploaded` was filled there (batch_stage_device)
   BatchItem* items_dev;
   uint32_t* order_dev;
 };
@@ -187,8 +191,11 @@ struct DictSizes {
 uint32_t DictRoom(uint32_t D) { return (D + 63u) & ~63u; }
 // dict: the dictionary bytes of every item of the call; with a size per item g->A->dict_bytes holds those of the group's items
 // max_items: a bound of the route's own on the items of a group, below BROTLI_MI355X_BATCH_GROUP_ITEMS (0: none)
+// on_device: inputs[i] is a device address (no dictionary).  The same buffer with the same layout is allocated zeroed on the device
+// and filled there by one launch from an array of the group's source addresses: no staging buffer, no memcpy, no bulk upload.
 void StageGroup(size_t first, size_t count, const uint8_t* const* inputs, const size_t* sizes, const DictSizes& dict, size_t tables_max,
-                CallArrays* arrays, Group* g, size_t max_items = 0) {
+                CallArrays* arrays, Group* g, size_t max_items = 0, bool on_device = false) {
+  if (on_device && dict.any()) throw std::runtime_error("brotli_mi355x: the dictionary routes take their items from host memory");
   CallArrays& A = *arrays;
   // (the limit counts the dictionary copies of the padded text: scratch -- keys and flags -- grows with them)
   size_t last = first, padded = 0, packed = 0, dict_copies = 0;
@@ -205,8 +212,11 @@ void StageGroup(size_t first, size_t count, const uint8_t* const* inputs, const 
   // padded text, dictionary | item per item, is laid out on the device
   const size_t packed_at = dict.any() ? 0 : padded + 64;
   const size_t text_bytes = packed_at + packed + 64;
-  A.staging.resize_discard(text_bytes);
-  memset(A.staging.data(), 0, text_bytes);
+  if (!on_device) {
+    A.staging.resize_discard(text_bytes);
+    memset(A.staging.data(), 0, text_bytes);
+  }
+  A.sources.resize_discard(on_device ? n : 0);
   A.items.resize_discard(n);
   A.order.resize_discard(n);
   A.starts.resize_discard(n);
@@ -217,8 +227,12 @@ void StageGroup(size_t first, size_t count, const uint8_t* const* inputs, const 
     const uint32_t cmd_cap = bytes / 2 + 8;
     A.dict_bytes[i] = dict.of(first + i);
     off += DictRoom(A.dict_bytes[i]);
-    if (!dict.any()) memcpy(A.staging.data() + off, inputs[first + i], bytes);
-    memcpy(A.staging.data() + packed_at + start, inputs[first + i], bytes);
+    if (on_device) {
+      A.sources[i] = inputs[first + i];
+    } else {
+      if (!dict.any()) memcpy(A.staging.data() + off, inputs[first + i], bytes);
+      memcpy(A.staging.data() + packed_at + start, inputs[first + i], bytes);
+    }
     A.items[i] = BatchItem{off, bytes, cmd_base, cmd_cap};
     A.starts[i] = start;
     off += Padded(bytes);
@@ -240,12 +254,59 @@ void StageGroup(size_t first, size_t count, const uint8_t* const* inputs, const 
   g->packed_at = packed_at;
   g->cmd_slots = (size_t)A.items[n - 1].cmd_base + A.items[n - 1].cmd_cap;
   g->tables = (uint32_t)std::min<size_t>(tables_max, n);
-  g->uploaded = g->mem.uninit<uint8_t>(text_bytes);
-  dev_h2d_bulk(g->uploaded, A.staging.data(), text_bytes);
+  g->on_device = on_device;
+  if (on_device) {
+    g->uploaded = g->mem.zeroed<uint8_t>(text_bytes);
+  } else {
+    g->uploaded = g->mem.uninit<uint8_t>(text_bytes);
+    dev_h2d_bulk(g->uploaded, A.staging.data(), text_bytes);
+  }
   g->items_dev = g->mem.uninit<BatchItem>((size_t)n * sizeof(BatchItem));
   dev_h2d(g->items_dev, A.items.data(), (size_t)n * sizeof(BatchItem));
   g->order_dev = g->mem.uninit<uint32_t>((size_t)n * 4);
   dev_h2d(g->order_dev, A.order.data(), (size_t)n * 4);
+  if (on_device) {
+    const uint8_t** sources_dev = g->mem.uninit<const uint8_t*>((size_t)n * sizeof(const uint8_t*));
+    dev_h2d(sources_dev, A.sources.data(), (size_t)n * sizeof(const uint8_t*));
+    uint32_t* starts_dev = g->mem.uninit<uint32_t>((size_t)n * 4);
+    dev_h2d(starts_dev, A.starts.data(), (size_t)n * 4);
+    batch_stage_device(sources_dev, g->items_dev, starts_dev, n, g->uploaded, g->uploaded + packed_at);
+  }
+}
+
+// The device sink of a group: the streams that go out leave the group's output (out_dev, still on the device) for the caller's
+// device buffers by one launch, the others get their answer by DeliveryRule.  An item that takes the stored fallback is copied from
+// the group's packed text.  item: the group's; out_byte / out_bytes: where its stream lies in out_dev.
+struct Outgoing {
+  uint32_t item;
+  uint64_t out_byte, out_bytes;
+};
+void DeliverGroup(Group& g, const uint8_t* out_dev, const std::vector<Outgoing>& outgoing, const BatchDeviceSink& sink) {
+  CallArrays& A = *g.A;
+  std::vector<BatchDeliverOp> ops;
+  for (const Outgoing& o : outgoing) {
+    const size_t k = g.first + o.item;
+    const uint32_t bytes = A.items[o.item].bytes;
+    switch (DeliveryRule((size_t)o.out_bytes, bytes, sink.capacities[k])) {
+      case Delivery::kStream:
+        ops.push_back({(uint64_t)(uintptr_t)sink.outputs[k], o.out_byte, o.out_bytes});
+        sink.sizes[k] = (size_t)o.out_bytes;
+        sink.results[k] = 1;
+        break;
+      case Delivery::kStored:
+        sink.sizes[k] = StoredStreamToDevice(g.uploaded + g.packed_at + A.starts[o.item], bytes, sink.outputs[k]);
+        sink.results[k] = 1;
+        break;
+      case Delivery::kFails:
+        sink.sizes[k] = 0;
+        sink.results[k] = 0;
+        break;
+    }
+  }
+  if (ops.empty()) return;
+  BatchDeliverOp* ops_dev = g.mem.uninit<BatchDeliverOp>(ops.size() * sizeof(BatchDeliverOp));
+  dev_h2d(ops_dev, ops.data(), ops.size() * sizeof(BatchDeliverOp));
+  batch_deliver(out_dev, ops_dev, (uint32_t)ops.size());
 }
 
 // the key pass over the group's padded text and the job of an H5 parse launch; `records` and `dict` are the caller's to set
@@ -309,8 +370,9 @@ void CheckSlab(uint32_t overflow) {
 // One-block items, from the records on: the gather offsets and one meta-block entry per item (one small round trip), the command
 // gather, one meta-block per item, and the streams of the items the reference does not fail on.  J: the parse job, or what
 // GatherJobOf leaves of it.
+// sink != nullptr: the device mode (BatchDeviceSink).
 void FinishOneBlockItems(const EncoderParams& p, const BatchParseJob& J, Group& g, std::vector<std::vector<uint8_t>>* streams,
-                         std::vector<uint8_t>* reference_fails) {
+                         std::vector<uint8_t>* reference_fails, const BatchDeviceSink* sink = nullptr) {
   CallArrays& A = *g.A;
   A.records.resize_discard(g.n);
   dev_d2h(A.records.data(), J.records, (size_t)g.n * sizeof(BatchRecord));
@@ -335,6 +397,15 @@ void FinishOneBlockItems(const EncoderParams& p, const BatchParseJob& J, Group& 
   Command* cmds = g.mem.uninit<Command>((size_t)(total + 16) * sizeof(Command));
   lz77_batch_gather(J, offsets_dev, cmds);
   std::vector<uint8_t> out;
+  if (sink) {
+    BatchOutputOnDevice keep{&g.mem, nullptr};
+    EncodeBatchMetaBlocks(p, g.uploaded + g.packed_at, cmds, (uint32_t)total, &mbs, &out, &keep);
+    std::vector<Outgoing> outgoing;
+    for (uint32_t i = 0; i < g.n; ++i)
+      if (A.records[i].bad_commands == 0) outgoing.push_back({i, mbs[i].out_byte, mbs[i].out_bytes});
+    DeliverGroup(g, keep.bytes, outgoing, *sink);
+    return;
+  }
   EncodeBatchMetaBlocks(p, g.uploaded + g.packed_at, cmds, (uint32_t)total, &mbs, &out);
   for (uint32_t i = 0; i < g.n; ++i)
     if (A.records[i].bad_commands == 0) (*streams)[g.first + i].assign(out.begin() + (ptrdiff_t)mbs[i].out_byte, out.begin() + (ptrdiff_t)(mbs[i].out_byte + mbs[i].out_bytes));
@@ -344,8 +415,10 @@ void FinishOneBlockItems(const EncoderParams& p, const BatchParseJob& J, Group& 
 // far as its meta-blocks follow each other inside the item: one that would pass the item's end stops the walk.  (For the H5 kernel
 // that test changes no outcome: behind such a meta-block `at` cannot come back to the item's size, and the same error is thrown.)
 // An item's first entry says where its stream lies, or that a meta-block of it took the size fallback (`demoted`: no stream).
+// sink != nullptr: the device mode (BatchDeviceSink) -- `inputs` are device addresses and are not read here: the context bytes of
+// the follow-on meta-blocks come from the group's packed text, one small gather and one download per group.
 void FinishLongItems(const EncoderParams& p, const BatchParseJob& J, const BatchLongRecord* records_dev, const uint8_t* const* inputs, Group& g,
-                     std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* demoted) {
+                     std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* demoted, const BatchDeviceSink* sink = nullptr) {
   CallArrays& A = *g.A;
   A.long_records.resize_discard(g.n);
   dev_d2h(A.long_records.data(), records_dev, (size_t)g.n * sizeof(BatchLongRecord));
@@ -374,7 +447,7 @@ void FinishLongItems(const EncoderParams& p, const BatchParseJob& J, const Batch
       e.follows = m != 0;
       e.more = m + 1 != r.n_mb;
       e.item_bytes = item.bytes;
-      if (m != 0) {
+      if (m != 0 && !g.on_device) {
         e.prev_byte = inputs[g.first + i][mb.start - 1];
         e.prev_byte2 = inputs[g.first + i][mb.start - 2];
       }
@@ -389,7 +462,38 @@ void FinishLongItems(const EncoderParams& p, const BatchParseJob& J, const Batch
   dev_h2d(offsets_dev, A.offsets.data(), (size_t)g.n * kBatchLongBlocks * 4);
   Command* cmds = g.mem.uninit<Command>((size_t)(total + 16) * sizeof(Command));
   lz77_batch_gather_long(J, records_dev, offsets_dev, cmds);
+  if (g.on_device) {
+    std::vector<uint32_t> at;
+    for (const BatchStreamItem& e : mbs)
+      if (e.follows) at.push_back(e.start);  // (mb.start is a whole number of input blocks: at least 2)
+    if (!at.empty()) {
+      uint32_t* at_dev = g.mem.uninit<uint32_t>(at.size() * 4);
+      dev_h2d(at_dev, at.data(), at.size() * 4);
+      uint8_t* context_dev = g.mem.zeroed<uint8_t>(at.size() * 2);
+      batch_gather_context(g.uploaded + g.packed_at, at_dev, (uint32_t)at.size(), context_dev);
+      std::vector<uint8_t> context(at.size() * 2);
+      dev_d2h(context.data(), context_dev, context.size());
+      size_t k = 0;
+      for (BatchStreamItem& e : mbs)
+        if (e.follows) {
+          e.prev_byte = context[2 * k];
+          e.prev_byte2 = context[2 * k + 1];
+          ++k;
+        }
+    }
+  }
   std::vector<uint8_t> out;
+  if (sink) {
+    BatchOutputOnDevice keep{&g.mem, nullptr};
+    EncodeBatchMetaBlocks(p, g.uploaded + g.packed_at, cmds, (uint32_t)total, &mbs, &out, &keep);
+    std::vector<Outgoing> outgoing;
+    for (uint32_t i = 0; i < g.n; ++i) {
+      const BatchStreamItem& e = mbs[first_mb[i]];
+      if (e.demoted) (*demoted)[g.first + i] = 1; else outgoing.push_back({i, e.out_byte, e.out_bytes});
+    }
+    DeliverGroup(g, keep.bytes, outgoing, *sink);
+    return;
+  }
   EncodeBatchMetaBlocks(p, g.uploaded + g.packed_at, cmds, (uint32_t)total, &mbs, &out);
   for (uint32_t i = 0; i < g.n; ++i) {
     const BatchStreamItem& e = mbs[first_mb[i]];
@@ -404,7 +508,8 @@ void FinishLongItems(const EncoderParams& p, const BatchParseJob& J, const Batch
 // Qualities 5 .. 8, items of one block, and qualities 9 / 10 on the H9 hasher (BatchQ9Compress: p.hasher.type == 9, no dictionary).
 // p: the parameters the items share, finalized.  dict == nullptr: the plain call.
 void CompressGroups(const EncoderParams& p, const uint8_t* dict, uint32_t D, size_t count, const uint8_t* const* inputs, const size_t* sizes,
-                    std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* reference_fails, uint32_t* groups) {
+                    std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* reference_fails, uint32_t* groups,
+                    const BatchDeviceSink* sink = nullptr) {
   streams->assign(count, std::vector<uint8_t>());
   if (reference_fails) reference_fails->assign(count, 0);
   *groups = 0;
@@ -451,7 +556,7 @@ void CompressGroups(const EncoderParams& p, const uint8_t* dict, uint32_t D, siz
   size_t first = 0;
   while (first < count) {
     Group g;
-    StageGroup(first, count, inputs, sizes, D, tables_max, &A, &g);
+    StageGroup(first, count, inputs, sizes, D, tables_max, &A, &g, 0, sink != nullptr);
     ++*groups;
     uint8_t* text = g.uploaded;
     if (D != 0) {
@@ -464,7 +569,7 @@ void CompressGroups(const EncoderParams& p, const uint8_t* dict, uint32_t D, siz
     J.records = g.mem.uninit<BatchRecord>((size_t)g.n * sizeof(BatchRecord));
     J.dict = image;
     if (P.hasher_kind == 9) lz77_batch_parse_h9(J); else lz77_batch_parse(J);
-    FinishOneBlockItems(p, J, g, streams, reference_fails);
+    FinishOneBlockItems(p, J, g, streams, reference_fails, sink);
     first = g.last;
   }
 }
@@ -556,8 +661,8 @@ void BatchGreedyCompressWithDictionaries(const EncoderParams& user, size_t count
 }
 
 void BatchGreedyCompress(const EncoderParams& user, size_t count, const uint8_t* const* inputs, const size_t* sizes,
-                         std::vector<std::vector<uint8_t>>* streams, uint32_t* groups) {
-  CompressGroups(ItemParams(user, count ? sizes[0] : 0), nullptr, 0, count, inputs, sizes, streams, nullptr, groups);
+                         std::vector<std::vector<uint8_t>>* streams, uint32_t* groups, const BatchDeviceSink* sink) {
+  CompressGroups(ItemParams(user, count ? sizes[0] : 0), nullptr, 0, count, inputs, sizes, streams, nullptr, groups, sink);
 }
 
 void BatchGreedyCompressWithDictionary(const EncoderParams& user, const uint8_t* dict, size_t dict_size, size_t count,
@@ -589,14 +694,14 @@ bool BatchQ9Eligible(const EncoderParams& user, size_t input_size) {
 
 // Qualities 9 and 10, items of one block: the steps of BatchGreedyCompress on H9 tables, parsed by k_parse_batch_h9.
 void BatchQ9Compress(const EncoderParams& user, size_t count, const uint8_t* const* inputs, const size_t* sizes,
-                     std::vector<std::vector<uint8_t>>* streams, uint32_t* groups) {
+                     std::vector<std::vector<uint8_t>>* streams, uint32_t* groups, const BatchDeviceSink* sink) {
   // (nothing in the parameters differs between items of at most one block)
-  CompressGroups(Q9ItemParams(user, count ? sizes[0] : 0), nullptr, 0, count, inputs, sizes, streams, nullptr, groups);
+  CompressGroups(Q9ItemParams(user, count ? sizes[0] : 0), nullptr, 0, count, inputs, sizes, streams, nullptr, groups, sink);
 }
 
 // Qualities 5 .. 8, items of two to kBatchLongBlocks blocks: one chain and up to kBatchLongBlocks meta-blocks per item.
 void BatchLongCompress(const EncoderParams& user, size_t count, const uint8_t* const* inputs, const size_t* sizes,
-                       std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* demoted, uint32_t* groups) {
+                       std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* demoted, uint32_t* groups, const BatchDeviceSink* sink) {
   streams->assign(count, std::vector<uint8_t>());
   demoted->assign(count, 0);
   *groups = 0;
@@ -609,12 +714,12 @@ void BatchLongCompress(const EncoderParams& user, size_t count, const uint8_t* c
   size_t first = 0;
   while (first < count) {
     Group g;
-    StageGroup(first, count, inputs, sizes, 0, tables_max, &A, &g);
+    StageGroup(first, count, inputs, sizes, 0, tables_max, &A, &g, 0, sink != nullptr);
     ++*groups;
     const BatchParseJob J = GreedyJob(p, P, g, g.uploaded);  // (J.records is not used, J.dict.bytes is 0)
     BatchLongRecord* records_dev = g.mem.uninit<BatchLongRecord>((size_t)g.n * sizeof(BatchLongRecord));
     lz77_batch_parse_long(J, records_dev);
-    FinishLongItems(p, J, records_dev, inputs, g, streams, demoted);
+    FinishLongItems(p, J, records_dev, inputs, g, streams, demoted, sink);
     first = g.last;
   }
 }
@@ -630,7 +735,7 @@ bool BatchQuickEligible(const EncoderParams& user, size_t input_size) {
 
 // Qualities 2 .. 4 (batch_quick.h), items of one block.  (The plain quick kernel leaves bad_commands at 0: no stream is dropped.)
 void BatchQuickCompress(const EncoderParams& user, size_t count, const uint8_t* const* inputs, const size_t* sizes,
-                        std::vector<std::vector<uint8_t>>* streams, uint32_t* groups) {
+                        std::vector<std::vector<uint8_t>>* streams, uint32_t* groups, const BatchDeviceSink* sink) {
   streams->assign(count, std::vector<uint8_t>());
   *groups = 0;
   if (count == 0) return;
@@ -641,12 +746,12 @@ void BatchQuickCompress(const EncoderParams& user, size_t count, const uint8_t* 
   size_t first = 0;
   while (first < count) {
     Group g;
-    StageGroup(first, count, inputs, sizes, 0, tables_max, &A, &g);
+    StageGroup(first, count, inputs, sizes, 0, tables_max, &A, &g, 0, sink != nullptr);
     ++*groups;
     QuickBatchJob J = QuickGroupJob(chains, g);
     J.records = g.mem.uninit<BatchRecord>((size_t)g.n * sizeof(BatchRecord));
     lz77_quick_batch_parse(J);
-    FinishOneBlockItems(p, GatherJobOf(J), g, streams, nullptr);
+    FinishOneBlockItems(p, GatherJobOf(J), g, streams, nullptr, sink);
     first = g.last;
   }
 }
@@ -759,7 +864,8 @@ bool BatchQuickLongEligible(const EncoderParams& user, size_t input_size) {
 
 // Qualities 2 .. 4, items of two to kBatchLongBlocks input blocks (batch_quick.h).
 void BatchQuickLongCompress(const EncoderParams& user, size_t count, const uint8_t* const* inputs, const size_t* sizes,
-                            std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* demoted, uint32_t* groups) {
+                            std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* demoted, uint32_t* groups,
+                            const BatchDeviceSink* sink) {
   streams->assign(count, std::vector<uint8_t>());
   demoted->assign(count, 0);
   *groups = 0;
@@ -771,12 +877,12 @@ void BatchQuickLongCompress(const EncoderParams& user, size_t count, const uint8
   size_t first = 0;
   while (first < count) {
     Group g;
-    StageGroup(first, count, inputs, sizes, 0, tables_max, &A, &g);
+    StageGroup(first, count, inputs, sizes, 0, tables_max, &A, &g, 0, sink != nullptr);
     ++*groups;
     const QuickBatchJob J = QuickGroupJob(chains, g);  // (J.records is not used)
     BatchLongRecord* records_dev = g.mem.uninit<BatchLongRecord>((size_t)g.n * sizeof(BatchLongRecord));
     lz77_quick_batch_parse_long(J, records_dev);
-    FinishLongItems(p, GatherJobOf(J), records_dev, inputs, g, streams, demoted);
+    FinishLongItems(p, GatherJobOf(J), records_dev, inputs, g, streams, demoted, sink);
     first = g.last;
   }
 }
@@ -795,7 +901,8 @@ bool BatchZopfliEligible(const EncoderParams& user, size_t input_size) {
 // item, FinishOneBlockItems with the quality >= 10 meta-block builder.  A group holds at most kBatchHqGroupItems items (what that
 // builder sets aside per meta-block); the tables are as many as stay resident (kZopfliBatchResident) within 8 GiB.
 void BatchZopfliCompress(const EncoderParams& user, size_t count, const uint8_t* const* inputs, const size_t* sizes,
-                         std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* reference_fails, uint32_t* groups) {
+                         std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* reference_fails, uint32_t* groups,
+                         const BatchDeviceSink* sink) {
   streams->assign(count, std::vector<uint8_t>());
   reference_fails->assign(count, 0);
   *groups = 0;
@@ -813,7 +920,7 @@ void BatchZopfliCompress(const EncoderParams& user, size_t count, const uint8_t*
   while (first < count) {
     Group g;
     // (the tables hang on the group's largest item, which the staging finds: staged for the most tables a group can have, then cut)
-    StageGroup(first, count, inputs, sizes, 0, kZopfliBatchResident, &A, &g, kBatchHqGroupItems);
+    StageGroup(first, count, inputs, sizes, 0, kZopfliBatchResident, &A, &g, kBatchHqGroupItems, sink != nullptr);
     ++*groups;
     ZopfliBatchJob J = chains;
     zopfli_batch_layout(&J, A.items[A.order[0]].bytes);
@@ -835,9 +942,38 @@ void BatchZopfliCompress(const EncoderParams& user, size_t count, const uint8_t*
     G.items = J.items;
     G.n_items = J.n_items;
     G.records = J.records;
-    FinishOneBlockItems(p, G, g, streams, reference_fails);
+    FinishOneBlockItems(p, G, g, streams, reference_fails, sink);
     first = g.last;
   }
+}
+
+size_t StoredStreamToDevice(const uint8_t* input_dev, size_t input_size, uint8_t* output_dev) {
+  size_t size = input_size, result = 0, offset = 0;
+  if (input_size == 0) {
+    const uint8_t empty = 6;
+    dev_h2d(output_dev, &empty, 1);
+    return 1;
+  }
+  const uint8_t window[2] = {0x21, 0x03};
+  dev_h2d(output_dev, window, 2);
+  result = 2;
+  while (size > 0) {
+    uint32_t nibbles = 0;
+    const uint32_t chunk_size = size > (1u << 24) ? (1u << 24) : (uint32_t)size;
+    if (chunk_size > (1u << 16)) nibbles = chunk_size > (1u << 20) ? 2 : 1;
+    const uint32_t bits = (nibbles << 1) | ((chunk_size - 1) << 3) | (1u << (19 + 4 * nibbles));
+    const uint8_t header[4] = {(uint8_t)bits, (uint8_t)(bits >> 8), (uint8_t)(bits >> 16), (uint8_t)(bits >> 24)};
+    const size_t header_bytes = nibbles == 2 ? 4 : 3;
+    dev_h2d(output_dev + result, header, header_bytes);
+    result += header_bytes;
+    dev_d2d(output_dev + result, input_dev + offset, chunk_size);
+    result += chunk_size;
+    offset += chunk_size;
+    size -= chunk_size;
+  }
+  const uint8_t last = 3;
+  dev_h2d(output_dev + result, &last, 1);
+  return result + 1;
 }
 
 }  // namespace brotli_mi355x

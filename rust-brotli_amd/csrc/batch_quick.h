@@ -64,10 +64,11 @@ bool BatchQuickEligible(const EncoderParams& params, size_t input_size);
 bool BatchQuickLongEligible(const EncoderParams& params, size_t input_size);
 // The streams of `count` such items.  (*demoted)[i] != 0: as for BatchLongCompress -- no stream, the caller redoes the item.
 void BatchQuickLongCompress(const EncoderParams& params, size_t count, const uint8_t* const* inputs, const size_t* sizes,
-                            std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* demoted, uint32_t* groups);
+                            std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* demoted, uint32_t* groups,
+                            const BatchDeviceSink* sink = nullptr);
 // The streams of `count` eligible items.  Throws std::runtime_error on a device error.  *groups: device groups run.
 void BatchQuickCompress(const EncoderParams& params, size_t count, const uint8_t* const* inputs, const size_t* sizes,
-                        std::vector<std::vector<uint8_t>>* streams, uint32_t* groups);
+                        std::vector<std::vector<uint8_t>>* streams, uint32_t* groups, const BatchDeviceSink* sink = nullptr);
 // Behind a shared custom dictionary (BrotliMi355xCompressBatchWithDictionaryEx with BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS): does
 // this item of at most one input block go side by side?  dict_size: as the caller gave it, before the reference's truncation.
 bool BatchQuickDictionaryEligible(const EncoderParams& params, size_t dict_size, size_t input_size);

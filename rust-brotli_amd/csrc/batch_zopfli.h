@@ -98,7 +98,8 @@ bool BatchZopfliEligible(const EncoderParams& params, size_t input_size);
 // The streams of `count` eligible items.  Throws std::runtime_error on a device error.  *groups: device groups run.
 // (*reference_fails)[i] != 0: the reference itself fails on item i; its stream stays empty.
 void BatchZopfliCompress(const EncoderParams& params, size_t count, const uint8_t* const* inputs, const size_t* sizes,
-                         std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* reference_fails, uint32_t* groups);
+                         std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* reference_fails, uint32_t* groups,
+                         const BatchDeviceSink* sink = nullptr);
 
 }  // namespace brotli_mi355x
 #endif

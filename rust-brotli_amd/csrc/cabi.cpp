@@ -891,21 +891,28 @@ static int OneShotWithoutEncoder(size_t input_size, size_t* encoded_size, uint8_
 
 // What encoder_compress does with the stream its encoder made (encode.rs:1521-1538): it goes out if it fits the buffer and is no
 // larger than BrotliEncoderMaxCompressedSize; otherwise the input goes out as an uncompressed stream if the buffer holds that.
+// The host sink of DeliveryRule (batch_greedy.h); an input on the device has no stored stream here.
 static BROTLI_BOOL OneShotDeliver(const uint8_t* stream, size_t stream_size, const uint8_t* input, size_t input_size, bool input_on_device,
                                   size_t out_size, size_t* encoded_size, uint8_t* encoded) {
-  const size_t max_out_size = MaxCompressedSize(input_size);
-  if (stream_size <= out_size && !(max_out_size != 0 && stream_size > max_out_size)) {
-    memcpy(encoded, stream, stream_size);
-    *encoded_size = stream_size;
-    return BROTLI_TRUE;
-  }
   *encoded_size = 0;
-  if (max_out_size == 0) return BROTLI_FALSE;
-  if (out_size >= max_out_size && !input_on_device) {
-    *encoded_size = MakeUncompressedStream(input, input_size, encoded);
-    return BROTLI_TRUE;
+  switch (DeliveryRule(stream_size, input_size, out_size)) {
+    case Delivery::kStream:
+      memcpy(encoded, stream, stream_size);
+      *encoded_size = stream_size;
+      return BROTLI_TRUE;
+    case Delivery::kStored:
+      if (input_on_device) return BROTLI_FALSE;
+      *encoded_size = MakeUncompressedStream(input, input_size, encoded);
+      return BROTLI_TRUE;
+    case Delivery::kFails:
+      break;
   }
   return BROTLI_FALSE;
+}
+
+// quality: behind the step from 10 to 9
+static bool OneShotRefusesPositionWrap(int quality, size_t input_size) {
+  return ((quality >= 2 && quality <= 4) || quality == 11) && (uint64_t)input_size > FirstPositionWrap();
 }
 
 // batch_item_error != nullptr: the call is an item of BrotliMi355xCompressBatch -- its caller sits in the small-call gate already, and
@@ -924,7 +931,7 @@ static BROTLI_BOOL CompressOneShot(int quality, int lgwin, BrotliEncoderMode mod
   // Qualities 2 .. 4 and 11 (the BasicHasher table / the H10 trees travel through the stream as they are) do not reproduce the
   // hasher reset of the reference's 3 GiB position wrap (encode.rs:1623-1631, 1705-1710): a one-shot input that would reach it is
   // refused here, before any work is done, rather than after gigabytes (include/brotli_mi355x.h, "Limits").
-  if (((quality >= 2 && quality <= 4) || quality == 11) && (uint64_t)input_size > FirstPositionWrap()) {
+  if (OneShotRefusesPositionWrap(quality, input_size)) {
     SetError("BrotliEncoderCompress", "qualities 2..4 and 10/11: inputs that cross the reference's position wrap at 3 GiB are not supported (split the input, e.g. BrotliEncoderCompressMulti)");
     *encoded_size = 0;
     return BROTLI_FALSE;
@@ -1007,10 +1014,12 @@ BROTLI_BOOL BrotliMi355xCompressDevice(int quality, int lgwin, BrotliEncoderMode
 // what BrotliMi355xLastBatchInfo reports: the last BrotliMi355xCompressBatch call of this thread
 static thread_local uint64_t g_batch_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
-// BrotliMi355xCompressBatch (routes == 0) and BrotliMi355xCompressBatchEx
+// BrotliMi355xCompressBatch (routes == 0), BrotliMi355xCompressBatchEx and, with on_device, BrotliMi355xCompressBatchDevice: there
+// inputs[i] and outputs[i] are device addresses -- the side-by-side routes take the items from device memory and leave the streams
+// there (BatchDeviceSink), every other answer goes down with a small copy, and one dev_sync() ends the call.
 static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t count,
                              const uint8_t* const* inputs, const size_t* input_sizes, uint8_t* const* outputs, size_t* output_sizes,
-                             int32_t* item_results) {
+                             int32_t* item_results, bool on_device = false) {
   uint64_t info[8] = {count, 0, 0, 0, 0, 0, 0, 0};
   memcpy(g_batch_info, info, sizeof(info));
   if ((routes & ~(uint32_t)(BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS | BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS | BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS |
@@ -1044,6 +1053,18 @@ static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEn
       std::vector<size_t> item;
       std::vector<const uint8_t*> in;
       std::vector<size_t> size;
+      // on_device: their buffers, and what the route's groups answered (BatchDeviceSink)
+      std::vector<uint8_t*> out;
+      std::vector<size_t> cap, out_size;
+      std::vector<int32_t> result;
+      BatchDeviceSink sink{nullptr, nullptr, nullptr, nullptr};
+      const BatchDeviceSink* Sink(bool on_device) {
+        if (!on_device) return nullptr;
+        out_size.assign(item.size(), 0);
+        result.assign(item.size(), 0);
+        sink = BatchDeviceSink{out.data(), cap.data(), out_size.data(), result.data()};
+        return &sink;
+      }
     };
     Routed plain, long_items, quick_items, quick_long_items, zopfli_items, q9_items;
     const bool long_route = (routes & BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS) != 0;
@@ -1053,6 +1074,25 @@ static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEn
     const bool q9_route = (routes & BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS) != 0;
     auto one_by_one = [&](size_t i) {
       std::string error;
+      if (on_device) {
+        // the device one-shot path into host memory, as BrotliMi355xCompressDevice runs it, and the stream down with one copy.  The
+        // host buffer holds what DeliveryRule lets out at most; where that path gives nothing, the rule's other two answers are left.
+        const size_t capacity = output_sizes[i], max_out_size = MaxCompressedSize(input_sizes[i]);
+        std::vector<uint8_t> stream(max_out_size != 0 ? std::min(capacity, max_out_size) : capacity);
+        size_t n = stream.size();
+        results[i] = CompressOneShot(quality, lgwin, mode, input_sizes[i], inputs[i], true, &n, stream.data(), nullptr, &error);
+        if (!error.empty()) throw std::runtime_error(error);
+        output_sizes[i] = 0;
+        if (results[i]) {
+          dev_h2d(outputs[i], stream.data(), n);
+          output_sizes[i] = n;
+        } else if (!OneShotRefusesPositionWrap(quality == 10 ? 9 : quality, input_sizes[i]) && max_out_size != 0 && capacity >= max_out_size) {
+          output_sizes[i] = StoredStreamToDevice(inputs[i], input_sizes[i], outputs[i]);
+          results[i] = 1;
+        }
+        ++info[2];
+        return;
+      }
       results[i] = CompressOneShot(quality, lgwin, mode, input_sizes[i], inputs[i], false, &output_sizes[i], outputs[i], nullptr, &error);
       if (!error.empty()) throw std::runtime_error(error);  // (a device error, not a buffer that is too small: the call fails as a whole)
       if (!results[i]) output_sizes[i] = 0;
@@ -1080,13 +1120,20 @@ static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEn
           ++delivered;  // (it ran side by side and has its answer, as an item whose buffer is too small has: info[1], as with a dictionary)
           continue;
         }
-        results[i] = OneShotDeliver(streams[k].data(), streams[k].size(), inputs[i], input_sizes[i], false, output_sizes[i], &output_sizes[i], outputs[i]);
+        if (on_device) {  // (the route's groups have answered it)
+          results[i] = r.result[k];
+          output_sizes[i] = r.out_size[k];
+        } else {
+          results[i] = OneShotDeliver(streams[k].data(), streams[k].size(), inputs[i], input_sizes[i], false, output_sizes[i], &output_sizes[i], outputs[i]);
+        }
         ++delivered;
       }
       return delivered;
     };
     for (size_t i = 0; i < count; ++i) {
-      const int early = OneShotWithoutEncoder(input_sizes[i], &output_sizes[i], outputs[i]);
+      uint8_t first_byte = 0;  // (on_device: the one byte OneShotWithoutEncoder may write goes down with a copy)
+      const int early = OneShotWithoutEncoder(input_sizes[i], &output_sizes[i], on_device ? &first_byte : outputs[i]);
+      if (early > 0 && on_device) dev_h2d(outputs[i], &first_byte, 1);
       if (early >= 0) {
         results[i] = early;
         if (!early) output_sizes[i] = 0;
@@ -1107,13 +1154,17 @@ static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEn
       r->item.push_back(i);
       r->in.push_back(inputs[i]);
       r->size.push_back(input_sizes[i]);
+      if (on_device) {
+        r->out.push_back(outputs[i]);
+        r->cap.push_back(output_sizes[i]);
+      }
     }
     std::vector<std::vector<uint8_t>> streams;
     std::vector<uint8_t> demoted;
     uint32_t groups = 0;
     // ---- the items of one block at qualities 2 .. 4, one chain each, in groups of their own (BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS)
     if (!quick_items.item.empty()) {
-      BatchQuickCompress(params, quick_items.item.size(), quick_items.in.data(), quick_items.size.data(), &streams, &groups);
+      BatchQuickCompress(params, quick_items.item.size(), quick_items.in.data(), quick_items.size.data(), &streams, &groups, quick_items.Sink(on_device));
       info[4] += groups;
       info[1] += deliver(quick_items, streams, nullptr);
     }
@@ -1121,21 +1172,23 @@ static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEn
     // (BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS)
     if (!zopfli_items.item.empty()) {
       std::vector<uint8_t> reference_fails;
-      BatchZopfliCompress(params, zopfli_items.item.size(), zopfli_items.in.data(), zopfli_items.size.data(), &streams, &reference_fails, &groups);
+      BatchZopfliCompress(params, zopfli_items.item.size(), zopfli_items.in.data(), zopfli_items.size.data(), &streams, &reference_fails, &groups,
+                          zopfli_items.Sink(on_device));
       info[4] += groups;
       info[1] += deliver(zopfli_items, streams, nullptr, &reference_fails);
     }
     // ---- the items of one block at qualities 9 and 10, one chain each on an H9 table, in groups of their own
     // (BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS)
     if (!q9_items.item.empty()) {
-      BatchQ9Compress(params, q9_items.item.size(), q9_items.in.data(), q9_items.size.data(), &streams, &groups);
+      BatchQ9Compress(params, q9_items.item.size(), q9_items.in.data(), q9_items.size.data(), &streams, &groups, q9_items.Sink(on_device));
       info[4] += groups;
       info[1] += deliver(q9_items, streams, nullptr);
     }
     // ---- the items of two to four blocks at qualities 2 .. 4, one chain each, in groups of their own
     // (BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS)
     if (!quick_long_items.item.empty()) {
-      BatchQuickLongCompress(params, quick_long_items.item.size(), quick_long_items.in.data(), quick_long_items.size.data(), &streams, &demoted, &groups);
+      BatchQuickLongCompress(params, quick_long_items.item.size(), quick_long_items.in.data(), quick_long_items.size.data(), &streams, &demoted, &groups,
+                             quick_long_items.Sink(on_device));
       info[4] += groups;
       const size_t delivered = deliver(quick_long_items, streams, &demoted);
       info[1] += delivered;
@@ -1143,27 +1196,74 @@ static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEn
     }
     // ---- the items of several blocks, one chain each, in groups of their own (BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS)
     if (!long_items.item.empty()) {
-      BatchLongCompress(params, long_items.item.size(), long_items.in.data(), long_items.size.data(), &streams, &demoted, &groups);
+      BatchLongCompress(params, long_items.item.size(), long_items.in.data(), long_items.size.data(), &streams, &demoted, &groups, long_items.Sink(on_device));
       info[4] += groups;
       const size_t delivered = deliver(long_items, streams, &demoted);
       info[1] += delivered;
       info[7] += delivered;
     }
     if (!plain.item.empty()) {
-      if (fragments) {
-        FragmentBatchCompress(params, plain.item.size(), plain.in.data(), plain.size.data(), &streams);
+      if (fragments && on_device) {
+        // Qualities 0 and 1: the fragment path takes its input from host memory.  The items come down once, go through it
+        // unchanged, and their streams go up: the same bytes and the same info, no gain over the host call.
+        size_t bytes = 0;
+        for (size_t n : plain.size) bytes += n;
+        std::vector<uint8_t> host(bytes);
+        std::vector<const uint8_t*> in(plain.item.size());
+        bytes = 0;
+        for (size_t k = 0; k < plain.item.size(); ++k) {
+          in[k] = host.data() + bytes;
+          dev_d2h_async(host.data() + bytes, plain.in[k], plain.size[k]);
+          bytes += plain.size[k];
+        }
+        dev_sync();
+        FragmentBatchCompress(params, plain.item.size(), in.data(), plain.size.data(), &streams);
         info[4] = 1;
+        std::vector<uint8_t> stored;
+        for (size_t k = 0; k < plain.item.size(); ++k) {
+          const size_t i = plain.item[k];
+          results[i] = 0;
+          output_sizes[i] = 0;
+          switch (DeliveryRule(streams[k].size(), plain.size[k], plain.cap[k])) {
+            case Delivery::kStream:
+              dev_h2d(outputs[i], streams[k].data(), streams[k].size());
+              output_sizes[i] = streams[k].size();
+              results[i] = 1;
+              break;
+            case Delivery::kStored:
+              stored.resize(MaxCompressedSize(plain.size[k]));
+              output_sizes[i] = MakeUncompressedStream(in[k], plain.size[k], stored.data());
+              dev_h2d(outputs[i], stored.data(), output_sizes[i]);
+              results[i] = 1;
+              break;
+            case Delivery::kFails:
+              break;
+          }
+        }
+        info[1] += plain.item.size();
       } else {
-        BatchGreedyCompress(params, plain.item.size(), plain.in.data(), plain.size.data(), &streams, &groups);
-        info[4] += groups;
+        if (fragments) {
+          FragmentBatchCompress(params, plain.item.size(), plain.in.data(), plain.size.data(), &streams);
+          info[4] = 1;
+        } else {
+          BatchGreedyCompress(params, plain.item.size(), plain.in.data(), plain.size.data(), &streams, &groups, plain.Sink(on_device));
+          info[4] += groups;
+        }
+        info[1] += deliver(plain, streams, nullptr);
       }
-      info[1] += deliver(plain, streams, nullptr);
     }
+    if (on_device) dev_sync();  // everything the call wrote has landed
   } catch (const std::exception& e) {
     // a device error fails the call as a whole
     SetError(entry, e.what());
     for (size_t i = 0; i < count; ++i) output_sizes[i] = 0;
     if (item_results) memset(item_results, 0, count * sizeof(int32_t));
+    if (on_device) {  // (what the groups in front of the error queued for the caller's buffers has landed when the call returns)
+      try {
+        dev_sync();
+      } catch (const std::exception&) {
+      }
+    }
     return 0;
   }
   memcpy(g_batch_info, info, sizeof(info));
@@ -1183,6 +1283,13 @@ int32_t BrotliMi355xCompressBatch(int quality, int lgwin, BrotliEncoderMode mode
 int32_t BrotliMi355xCompressBatchEx(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t count, const uint8_t* const* inputs,
                                     const size_t* input_sizes, uint8_t* const* outputs, size_t* output_sizes, int32_t* item_results) {
   return CompressBatch("BrotliMi355xCompressBatchEx", quality, lgwin, mode, routes, count, inputs, input_sizes, outputs, output_sizes, item_results);
+}
+
+int32_t BrotliMi355xCompressBatchDevice(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t count,
+                                        const uint8_t* const* inputs_device, const size_t* input_sizes, uint8_t* const* outputs_device,
+                                        size_t* output_sizes, int32_t* item_results) {
+  return CompressBatch("BrotliMi355xCompressBatchDevice", quality, lgwin, mode, routes, count, inputs_device, input_sizes, outputs_device, output_sizes,
+                       item_results, true);
 }
 
 // One item of BrotliMi355xCompressBatchWithDictionary by itself, through the stream state machine: the definition of the call, run as

@@ -1071,11 +1071,13 @@ void EncodeStream(const EncodeRequest& req, std::vector<uint8_t>* out, EncodeSta
 // An item of several meta-blocks (BatchStreamItem::follows / more) is several entries in a row: only the first is preceded by the
 // window bits and the 8-byte boundary, the others go on at the bit where the one in front ended, with the context bytes of the
 // text in front and ISLAST on the last one alone.
+// keep != nullptr: the output is not downloaded.  It lies in a block of the caller's owner, which outlives this call's DevMem.
 void EncodeBatchMetaBlocks(const EncoderParams& p, const uint8_t* text, const Command* cmds_dev, uint32_t n_cmds,
-                           std::vector<BatchStreamItem>* items_io, std::vector<uint8_t>* out) {
+                           std::vector<BatchStreamItem>* items_io, std::vector<uint8_t>* out, BatchOutputOnDevice* keep) {
   std::vector<BatchStreamItem>& items = *items_io;
   const uint32_t n_mb = (uint32_t)items.size();
   out->clear();
+  if (keep) keep->bytes = nullptr;
   if (n_mb == 0) return;
   if (p.quality < 2 || p.quality > 11 || p.lgwin < 10 || p.lgwin > 24 || p.large_window || p.appendable || p.byte_align || p.magic_number)
     throw std::runtime_error("brotli_mi355x: parameters the batch meta-block stage does not take");
@@ -1275,7 +1277,7 @@ void EncodeBatchMetaBlocks(const EncoderParams& p, const uint8_t* text, const Co
   // ---- emission
   const size_t all_bytes = (size_t)((bits.pos + 7) >> 3);
   const size_t out_words = all_bytes / 8 + 4;
-  B.out_words = mm.alloc<uint64_t>(out_words);
+  B.out_words = keep ? keep->owner->zeroed<uint64_t>((out_words * 8 + 64 + 255) & ~(size_t)255) : mm.alloc<uint64_t>(out_words);
   if (!all_raw) {
     if (flipped) dev_h2d(B.descs, descs.data(), n_mb * sizeof(MbDesc));
     dev_h2d(B.mb_out_bit, mb_out_bit.data(), (n_mb + 1) * 8);
@@ -1286,6 +1288,10 @@ void EncodeBatchMetaBlocks(const EncoderParams& p, const uint8_t* text, const Co
     std::vector<MbBitPiece> pieces;
     for (const BitPiece& bp : bits.pieces) pieces.push_back({bp.pos, bp.nbits, 0, bp.bits});
     PlaceHostPieces(&mm, B, text, headers, raws, pieces);
+  }
+  if (keep) {
+    keep->bytes = (const uint8_t*)B.out_words;
+    return;
   }
   out->resize(all_bytes);
   dev_d2h_bulk(out->data(), B.out_words, all_bytes);

@@ -73,6 +73,13 @@ self-filing against the image.  At qualities 2 to 4 this build is called with BR
 is BrotliMi355xCompressBatchWithDictionaryEx with BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS; two more classes are measured there (4096 items of
 512 bytes behind 16 KiB; at quality 4, where that is one input block, 1024 items of 64 KiB behind 64 KiB).
 
+With --device (and --parent-lib) the call measured is BrotliMi355xCompressBatchDevice on torch tensors -- one uint8 tensor of items in,
+one of streams out -- beside the parent's BrotliMi355xCompressBatchEx on the same items from host memory and beside the "honest
+alternative" a caller with device-resident payloads has without the call: the items down (one D2H), the parent's host call, the
+streams up (one H2D of the output buffer's used part).  The three alternate inside one child per shape, --runs times each behind
+--warmup rounds of all three; the shapes are DEVICE_SHAPES (text).  Per shape: min .. max of each, and whether the device call's
+minimum stays at or below the host call's maximum (the bound: the two differ only by work that was removed).
+
 Every measurement runs in a child process of its own (the table's home is one setting per process, read once; the parent's library
 is another shared object), one after the other, each under its own time limit; the first failure ends the probe.
 
@@ -395,7 +402,128 @@ def child_dicts(args):
         json.dump(out, f)
 
 
+# (--device) class, quality, route bits
+DEVICE_SHAPES = [("4096x4KiB", 5, 0), ("4096x4KiB", 2, 4), ("1024x16KiB", 5, 0), ("256x64KiB", 9, 128), ("64x4KiB", 5, 0)]
+
+
+def child_device(args):
+    """--device: one shape -- the device call of this build, the parent's host call, and D2H + that host call + H2D, alternating"""
+    import torch
+    name, quality, routes = args.classes, int(args.qualities), args.routes
+    items = items_of(name, "text")
+    n = len(items)
+    L, P = bind(args.lib), bind(args.parent_lib or args.lib)
+    L.BrotliMi355xCompressBatchDevice.restype = ctypes.c_int32
+    P.BrotliMi355xCompressBatchEx.restype = ctypes.c_int32
+    caps = [L.BrotliEncoderMaxCompressedSize(len(x)) + 16 for x in items]
+    in_at, out_at, a, b = [], [], 0, 0
+    for x, c in zip(items, caps):
+        in_at.append(a)
+        out_at.append(b)
+        a += len(x)
+        b += c
+    src = torch.frombuffer(bytearray(b"".join(items)), dtype=torch.uint8).cuda()
+    dst = torch.zeros(b, dtype=torch.uint8, device="cuda")
+    in_sizes = (ctypes.c_size_t * n)(*[len(x) for x in items])
+    out_sizes = (ctypes.c_size_t * n)()
+    d_in = (ctypes.c_void_p * n)(*[src.data_ptr() + o for o in in_at])
+    d_out = (ctypes.c_void_p * n)(*[dst.data_ptr() + o for o in out_at])
+    # the host call's buffers: page-locked, like those of a caller that stages for a device
+    h_src = torch.empty(a, dtype=torch.uint8).pin_memory()
+    h_dst = torch.empty(b, dtype=torch.uint8).pin_memory()
+    h_src.copy_(src)
+    h_in = (ctypes.c_void_p * n)(*[h_src.data_ptr() + o for o in in_at])
+    h_out = (ctypes.c_void_p * n)(*[h_dst.data_ptr() + o for o in out_at])
+    P.BrotliMi355xCompressBatchEx.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_void_p]
+    L.BrotliMi355xCompressBatchDevice.argtypes = P.BrotliMi355xCompressBatchEx.argtypes
+
+    def reset():
+        for i in range(n):
+            out_sizes[i] = caps[i]
+
+    def device_call():
+        reset()
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        ok = L.BrotliMi355xCompressBatchDevice(quality, LGWIN, 0, routes, n, d_in, in_sizes, d_out, out_sizes, None)
+        dt = time.perf_counter() - t
+        assert ok == 1
+        return dt, list(out_sizes)
+
+    def host_call():
+        reset()
+        t = time.perf_counter()
+        ok = P.BrotliMi355xCompressBatchEx(quality, LGWIN, 0, routes, n, h_in, in_sizes, h_out, out_sizes, None)
+        dt = time.perf_counter() - t
+        assert ok == 1
+        return dt, list(out_sizes)
+
+    def alternative():
+        reset()
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        h_src.copy_(src)  # (synchronous: device to page-locked host memory)
+        ok = P.BrotliMi355xCompressBatchEx(quality, LGWIN, 0, routes, n, h_in, in_sizes, h_out, out_sizes, None)
+        used = out_at[-1] + out_sizes[n - 1]
+        dst[:used].copy_(h_dst[:used])
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t
+        assert ok == 1
+        return dt, list(out_sizes)
+
+    times = {"device": [], "host": [], "alternative": []}
+    sizes = None
+    for it in range(args.warmup + args.runs):
+        for what, call in (("device", device_call), ("host", host_call), ("alternative", alternative)):
+            dt, got = call()
+            assert sizes is None or got == sizes, (what, it)  # (the same streams from every way)
+            sizes = got
+            if it >= args.warmup:
+                times[what].append(dt)
+    # the streams themselves: the device call's against the host call's
+    device_call()
+    image = dst.cpu().numpy().tobytes()
+    host_call()
+    host_image = h_dst.numpy().tobytes()
+    assert all(image[o:o + k] == host_image[o:o + k] for o, k in zip(out_at, sizes))
+    info = (ctypes.c_uint64 * 8)()
+    device_call()
+    L.BrotliMi355xLastBatchInfo(info)
+    row = {"class": name, "data": "text", "quality": quality, "routes": routes, "items": n, "bytes": a, "compressed_bytes": sum(sizes), "batch_info": list(info)}
+    for what in times:
+        row[what] = stats(times[what])
+    row["device_min_within_host_max"] = bool(row["device"]["min_ms"] <= row["host"]["max_ms"])
+    print(json.dumps(row), flush=True)
+    with open(args.child_out, "w") as f:
+        json.dump([row], f)
+
+
+def main_device(args, doc, save):
+    doc["what"] = ("BrotliMi355xCompressBatchDevice (torch tensors in, tensors out) vs the parent commit's BrotliMi355xCompressBatchEx on the same items from "
+                   "page-locked host memory vs D2H of the items + that host call + H2D of the streams; text, lgwin 22; alternating inside one process per shape")
+    doc["method"] = "host clock around each synchronous way, %d warm-up rounds of all three, then %d rounds; min .. max of the repeats" % (args.warmup, args.runs)
+    doc["shapes"] = []
+    tmp = os.path.join(os.path.dirname(os.path.abspath(args.out)), ".batch_probe_child.json")
+    for name, quality, routes in DEVICE_SHAPES:
+        if args.only and name + "/q%d" % quality not in args.only.split(","):
+            continue
+        cmd = ["timeout", "-k", "10", "300", sys.executable, os.path.abspath(__file__), "--child", "device", "--classes", name, "--qualities", str(quality), "--routes", str(routes),
+               "--lib", args.lib, "--runs", str(args.runs), "--warmup", str(args.warmup), "--child-out", tmp] + (["--parent-lib", os.path.abspath(args.parent_lib)] if args.parent_lib else [])
+        r = subprocess.run(cmd)
+        if r.returncode != 0:
+            raise SystemExit("batch_probe: the device shape %s at quality %d ended with status %d: nothing more is started" % (name, quality, r.returncode))
+        doc["shapes"] += json.load(open(tmp))
+        os.remove(tmp)
+        save()
+    doc["device_min_within_host_max_on_every_shape"] = all(r["device_min_within_host_max"] for r in doc["shapes"])
+    save()
+    print(json.dumps(doc, indent=1))
+
+
 def child(args):
+    if args.child == "device":
+        return child_device(args)
     if args.dicts:
         return child_dicts(args)
     out = []
@@ -695,6 +823,8 @@ def main():
     ap.add_argument("--zopfli-items", action="store_true", help="this build through BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS (--qualities 11)")
     ap.add_argument("--q9-items", action="store_true", help="this build through BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS (--qualities 9,10)")
     ap.add_argument("--dicts", action="store_true", help="BrotliMi355xCompressBatchWithDictionaries: a dictionary per item (--qualities 5,8; 2,3,4 through BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS)")
+    ap.add_argument("--device", action="store_true", help="BrotliMi355xCompressBatchDevice on torch tensors beside the parent's host call on the same items (DEVICE_SHAPES)")
+    ap.add_argument("--routes", type=int, default=0, help="(child) route bits of the device shape")
     ap.add_argument("--same-call", action="store_true", help="the parent's library through the same call as this build, alternating --rounds times (needs --parent-lib)")
     ap.add_argument("--quick-long-classes", action="store_true", help="(child) only the qualities of QUICK_LONG_QUALITIES")
     ap.add_argument("--plain", action="store_true", help="(child) the plain call although a dictionary size is given")
@@ -715,6 +845,8 @@ def main():
         with open(args.out, "w") as f:
             json.dump(doc, f, indent=1)
 
+    if args.device:
+        return main_device(args, doc, save)
     if args.quick_long_items:
         args.quick_items = True
         args.qualities = "2,3,4"
