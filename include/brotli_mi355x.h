@@ -345,7 +345,8 @@ int32_t BrotliMi355xCompressBatchEx(int quality, int lgwin, BrotliEncoderMode mo
    each other or any input; they may abut.
    Ordering.  The call works on the calling thread's stream and returns after everything it wrote has landed (one synchronisation
    at the end).  Whatever produced the inputs must be complete before the call: it does not wait for other streams.
-   No dictionary: the three dictionary batch calls take host memory only.
+   No dictionary: behind a dictionary per item, or one shared by all, the call is BrotliMi355xCompressBatchWithDictionariesDevice;
+   the other dictionary batch calls take host memory only.
    When to use it: when the payloads already lie in device memory, or the streams are wanted there.  Measured on an MI355X against
    BrotliMi355xCompressBatchEx on the same items from page-locked host memory, min .. max of five alternating runs, text: 4096 items
    of 4 KiB at quality 5 in 12.3 .. 12.4 ms against 16.0 .. 16.3 ms (and 16.7 .. 17.1 ms for download + host call + upload), at
@@ -456,8 +457,55 @@ int32_t BrotliMi355xCompressBatchWithDictionaries(int quality, int lgwin, Brotli
                                                   const size_t* input_sizes, uint8_t* const* outputs,
                                                   size_t* output_sizes /* in: capacity, out: size */,
                                                   int32_t* item_results /* may be NULL */);
+/* BrotliMi355xCompressBatchWithDictionaries on device memory: items and dictionaries that lie in device memory -- the new and the
+   previous version of many resources, say -- and their streams left in device memory.  It is that call in every respect but one:
+   dicts_device[k], inputs_device[i] and outputs_device[i] are device addresses on the calling thread's current device, with any
+   alignment; several may point into one allocation.  All the arrays themselves (dicts_device, dict_sizes, item_dicts,
+   inputs_device, input_sizes, outputs_device, output_sizes) and item_results are host memory, as there.
+   Per item: the same bytes, size, success or failure as the host call on the same bytes -- item i is the stream of
+   BrotliEncoderSetCustomDictionary(<the bytes at dicts_device[item_dicts[i]]>) followed by one FINISH, under the stream API's rules:
+   no size hint, NO fallback to a stored stream and no BrotliEncoderMaxCompressedSize cap (an item goes out if and only if its
+   stream fits its capacity, otherwise it fails alone with size 0), a dictionary cut to its last (1 << lgwin) - 16 bytes, no
+   dictionary taken with dict_sizes[k] <= 1 or at qualities 0 and 1.  The rules of the call are the host call's: `routes` knows
+   BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS only; item_dicts == NULL means item i takes dicts_device[i] and num_dicts must be
+   count; any other route bit, an index >= num_dicts, or item_dicts == NULL with num_dicts != count fails the whole call before any
+   work is done (returns 0, every size 0, only info[0] set, nothing written to device memory); when every item names one index the
+   call takes the shared-image path (the shared route of qualities 5 .. 8, with the bit the quick shared route), the dictionary
+   reaching its image by one copy on the device; BrotliMi355xLastBatchInfo means what it means for the host call and has the same
+   values on the same data; BrotliMi355xLastError carries "the reference encoder fails on this input" for the items that fail that way.
+   On the four side-by-side routes (info[1]) nothing crosses the bus: one launch per group reads every item and every dictionary
+   where it lies -- no page-locked staging, no dictionary pool, no upload -- and lays out dictionary | item per item on the device;
+   one launch scatters the group's streams to their addresses.  Every other item -- the empty one, items longer than one input
+   block, other qualities or windows, dict_sizes[k] <= 1, more than 65 536 dictionary bytes in use, qualities 2 .. 4 without the bit
+   -- is downloaded, the bytes in use of the dictionary it names are downloaded once per call however many items name it, the item
+   runs through the stream path in the caller's order and its stream is uploaded if it fits: the same bytes and the same info as the
+   host call, and no gain over it.  If every item of a call goes this way no dictionary is touched on the device but by these downloads.
+   Memory contract.  The library reads only the aligned 4-byte words that hold at least one byte of an item or of the part of a
+   dictionary in use: it never reads the bytes in front of a truncated dictionary's last (1 << lgwin) - 16 (beyond the word that
+   holds the first byte in use), and never behind the last word of an item or a dictionary.  On return it has written exactly
+   outputs_device[i][0 .. output_sizes[i]), and never a byte outside [0, capacity); an item that fails leaves the contents of its
+   buffer unspecified, but stays inside it.  Outputs must not overlap each other, any input or any dictionary; they may abut.
+   Inputs and dictionaries may overlap each other freely: an item may lie behind a dictionary that is the previous item.
+   Ordering.  As for BrotliMi355xCompressBatchDevice: the call works on the calling thread's stream and returns after everything it
+   wrote has landed (one synchronisation at the end); whatever produced the inputs and dictionaries must be complete before it.
+   When to use it: when both versions already lie in device memory, or the streams are wanted there.
+   Measured on an MI355X against the same job done the way there was before -- dictionaries and items down to page-locked memory, the
+   parent commit's BrotliMi355xCompressBatchWithDictionaries, the streams up -- min .. max of five alternating runs, text, lgwin 22
+   (profiles/r24_batch_dictionaries_device.json): 4096 items of 4 KiB behind 16 KiB each at quality 5 in 17.0 .. 17.3 ms against
+   25.1 .. 26.0 ms (the host call alone, from page-locked memory: 23.1 .. 23.8 ms), at quality 2 with
+   BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS 16.0 .. 16.3 against 24.0 .. 25.2 ms; 1024 items of 16 KiB behind 64 KiB each at
+   quality 5 31.6 .. 31.7 against 38.6 .. 39.0 ms; 4096 items of 4 KiB behind ONE shared 16 KiB dictionary 15.6 .. 15.9 against
+   18.5 .. 18.7 ms.  No measured shape is slower.  When not: a call of a few items -- 64 items of 4 KiB behind 16 KiB each take
+   4.55 .. 4.60 ms against 4.68 .. 4.73 ms, launches and round trips either way -- and the items that run one by one, which are staged
+   through the host by the call itself. */
+int32_t BrotliMi355xCompressBatchWithDictionariesDevice(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t num_dicts,
+                                                        const uint8_t* const* dicts_device, const size_t* dict_sizes, size_t count,
+                                                        const size_t* item_dicts /* may be NULL */, const uint8_t* const* inputs_device,
+                                                        const size_t* input_sizes, uint8_t* const* outputs_device,
+                                                        size_t* output_sizes /* in: capacity, out: size */,
+                                                        int32_t* item_results /* may be NULL */);
 /* The last BrotliMi355xCompressBatch / BrotliMi355xCompressBatchEx / BrotliMi355xCompressBatchWithDictionary /
-   BrotliMi355xCompressBatchWithDictionaryEx / BrotliMi355xCompressBatchWithDictionaries call of the calling
+   BrotliMi355xCompressBatchWithDictionaryEx / BrotliMi355xCompressBatchWithDictionaries call (or device form of one) of the calling
    thread: info[0] items, [1] items encoded side by side on the device, [2] items run one by one (the one-shot path; with a
    dictionary the stream path), [3] items answered without an encoder (empty input, capacity 0; none with a dictionary), [4] device
    groups (those of long items included), [5] dictionary bytes in use after the reference's truncation (0 for the plain call; with a

@@ -109,6 +109,11 @@ def _bind(lib):
         lib.BrotliMi355xCompressBatchDevice.restype = c_int32
         lib.BrotliMi355xCompressBatchDevice.argtypes = [c_int, c_int, c_int, c_uint32, c_size_t, POINTER(c_void_p), POINTER(c_size_t), POINTER(c_void_p),
                                                         POINTER(c_size_t), POINTER(c_int32)]
+    if hasattr(lib, "BrotliMi355xCompressBatchWithDictionariesDevice"):
+        lib.BrotliMi355xCompressBatchWithDictionariesDevice.restype = c_int32
+        lib.BrotliMi355xCompressBatchWithDictionariesDevice.argtypes = [c_int, c_int, c_int, c_uint32, c_size_t, POINTER(c_void_p), POINTER(c_size_t),
+                                                                        c_size_t, POINTER(c_size_t), POINTER(c_void_p), POINTER(c_size_t),
+                                                                        POINTER(c_void_p), POINTER(c_size_t), POINTER(c_int32)]
     lib.BrotliMi355xDeviceName.restype = c_char_p
     lib.BrotliMi355xLastError.restype = c_char_p
     return lib
@@ -393,7 +398,8 @@ class Library(object):
         overlap each other or any input.  Item i becomes the bytes compress(item, quality, lgwin, mode) gives, at outputs[i];
         the flags are those of compress_batch, and last_batch_info() tells how the items were taken.  On the side-by-side
         routes nothing crosses the bus; qualities 0 and 1 are staged through the host once per call (no gain over
-        compress_batch), and no dictionary is taken.  Whatever produced the inputs must be complete before the call
+        compress_batch), and no dictionary is taken (behind dictionaries:
+        compress_batch_with_dictionaries_device).  Whatever produced the inputs must be complete before the call
         (torch.cuda.synchronize()); the call returns when every stream has landed.  Returns the list of stream sizes.
 
         An item whose capacity is too small fails alone in the C call, which then returns 0: this method raises
@@ -422,6 +428,63 @@ class Library(object):
             e.failed, e.sizes = failed, sizes
             raise e
         return sizes
+
+    def compress_batch_with_dictionaries_device(self, inputs, outputs, dictionaries, item_dictionaries=None, quality=5, lgwin=22, mode=0,
+                                                quick_items=False):
+        """BrotliMi355xCompressBatchWithDictionariesDevice: compress_batch_with_dictionaries for items and dictionaries that lie
+        in device memory (the new and the previous version of many resources, say), their streams left in device memory.
+        inputs and dictionaries: sequences of (address, size), outputs: a sequence of (address, capacity), all plain integers as
+        for compress_batch_device; any alignment.  Inputs and dictionaries may overlap each other (item i - 1 may be item i's
+        dictionary); outputs must not overlap each other, any input or any dictionary.  item_dictionaries and quick_items are
+        those of compress_batch_with_dictionaries; item i becomes the bytes that method gives, at outputs[i], under the stream
+        API's rules: there is no fallback to a stored stream, an item whose stream does not fit its capacity fails alone.  On the
+        side-by-side routes nothing crosses the bus; every other item (see compress_batch_with_dictionaries) is staged through
+        the host with the dictionary it names -- the same bytes, no gain.  Whatever produced the inputs must be complete before
+        the call (torch.cuda.synchronize()); the call returns when every stream has landed.  Returns the list of stream sizes.
+
+        Raises BrotliCompressorException like compress_batch_device, with .failed (the indices) and .sizes (the sizes of the
+        others, 0 for a failed item; all 0 after a call that failed as a whole: an index out of range, a dictionary count that
+        does not match).  As with compress_batch_with_dictionaries, a call of thousands of text items at quality 2 is expected
+        to hold a few the reference itself fails on."""
+        routes = self.BATCH_ROUTE_QUICK_DICTIONARY_ITEMS if quick_items else 0
+        inputs, outputs, dictionaries = list(inputs), list(outputs), list(dictionaries)
+        count, num = len(inputs), len(dictionaries)
+        if len(outputs) != count:
+            raise ValueError("%d inputs, %d outputs" % (count, len(outputs)))
+        if item_dictionaries is None:
+            item_dicts = ctypes.cast(None, POINTER(c_size_t))
+        else:
+            item_dictionaries = [int(k) for k in item_dictionaries]
+            if len(item_dictionaries) != count:
+                raise ValueError("item_dictionaries names %d items, there are %d" % (len(item_dictionaries), count))
+            if any(k < 0 for k in item_dictionaries):
+                raise ValueError("a dictionary index is negative")
+            item_dicts = (c_size_t * max(1, count))(*item_dictionaries)
+        if count == 0:
+            return []
+        dict_ptrs = (c_void_p * max(1, num))(*[int(a) for a, _ in dictionaries])
+        dict_sizes = (c_size_t * max(1, num))(*[int(n) for _, n in dictionaries])
+        in_ptrs = (c_void_p * count)(*[int(a) for a, _ in inputs])
+        in_sizes = (c_size_t * count)(*[int(n) for _, n in inputs])
+        out_ptrs = (c_void_p * count)(*[int(a) for a, _ in outputs])
+        out_sizes = (c_size_t * count)(*[int(n) for _, n in outputs])
+        results = (c_int32 * count)()
+        ok = self.lib.BrotliMi355xCompressBatchWithDictionariesDevice(quality, lgwin, mode, routes, num, dict_ptrs, dict_sizes, count, item_dicts, in_ptrs,
+                                                                      in_sizes, out_ptrs, out_sizes, results)
+        sizes = [int(out_sizes[i]) if ok or results[i] else 0 for i in range(count)]
+        if not ok:
+            failed = [i for i in range(count) if not results[i]]
+            e = BrotliCompressorException("BrotliMi355xCompressBatchWithDictionariesDevice failed (items %s): %s" % (failed[:8], self.last_error()))
+            e.failed, e.sizes = failed, sizes
+            raise e
+        return sizes
+
+    def compress_batch_with_dictionary_device(self, inputs, outputs, dictionary, quality=5, lgwin=22, mode=0, quick_items=False):
+        """compress_batch_with_dictionaries_device with ONE dictionary, (address, size) in device memory, named by every item: the
+        call takes the shared-image path -- the streams of compress_batch_with_dictionary(items, dictionary, ..., quick_items),
+        the dictionary reaching its image by one copy on the device.  Returns the list of stream sizes."""
+        inputs = list(inputs)
+        return self.compress_batch_with_dictionaries_device(inputs, outputs, [dictionary], [0] * len(inputs), quality, lgwin, mode, quick_items)
 
     def last_batch_info(self):
         """BrotliMi355xLastBatchInfo: the last compress_batch / compress_batch_with_dictionary / compress_batch_with_dictionaries call of this thread as a list of 8 integers -- [0] items, [1] items

@@ -1,7 +1,7 @@
 // batch_device_kernels.hip -- the gfx950 kernels of BrotliMi355xCompressBatchDevice (batch_device.h): the items of a group come
-// out of the caller's device memory into the group's two texts (k_batch_stage_device), and the streams of a group go from its
-// output to the caller's device memory (k_batch_deliver).  A translation unit of its own, so that the kernels of lz77_kernels.hip
-// compile as they did.
+// out of the caller's device memory into the group's two texts (k_batch_stage_device; behind dictionaries that lie there too:
+// k_batch_stage_dicts_device), and the streams of a group go from its output to the caller's device memory (k_batch_deliver).
+// A translation unit of its own, so that the kernels of lz77_kernels.hip compile as they did.
 #include <hip/hip_runtime.h>
 
 #include "batch_device.h"
@@ -66,6 +66,42 @@ void batch_stage_device(const uint8_t* const* srcs_dev, const BatchItem* items_d
                         uint8_t* packed) {
   if (n_items == 0) return;
   hipLaunchKernelGGL(k_batch_stage_device, dim3(n_items), dim3(256), 0, BR_STREAM, srcs_dev, items_dev, starts_dev, n_items, text, packed);
+  HIP_CHECK(hipGetLastError());
+}
+
+// Kernel A behind a dictionary per item.  One workgroup per item lays out `dictionary | item` in the padded text -- the dictionary
+// ends where the item starts, a 64-byte boundary -- and the item in the packed text.  A dictionary is read where it lies, by every
+// item that names it; nothing is pooled.  (text_off >= dict_bytes[i] rounded up to 64: the host plan's DictRoom.)
+__global__ __launch_bounds__(256) void k_batch_stage_dicts_device(const uint8_t* const* __restrict__ srcs, const uint8_t* const* __restrict__ dicts,
+                                                                   const uint32_t* __restrict__ dict_bytes, const BatchItem* __restrict__ items,
+                                                                   const uint32_t* __restrict__ starts, uint32_t n_items, uint8_t* __restrict__ text,
+                                                                   uint8_t* __restrict__ packed) {
+  const uint32_t i = blockIdx.x;
+  if (i >= n_items) return;
+  const BatchItem it = items[i];
+  const uint32_t D = dict_bytes[i];
+  const uint8_t* src = srcs[i];
+  if (D <= it.text_off) batch_copy_any(text + (it.text_off - D), dicts[i], D);
+  batch_copy_any(text + it.text_off, src, it.bytes);
+  batch_copy_any(packed + starts[i], src, it.bytes);
+}
+
+void batch_stage_dicts_device(const uint8_t* const* srcs_dev, const uint8_t* const* dicts_dev, const uint32_t* dict_bytes_dev,
+                              const BatchItem* items_dev, const uint32_t* starts_dev, uint32_t n_items, uint8_t* text, uint8_t* packed) {
+  if (n_items == 0) return;
+  hipLaunchKernelGGL(k_batch_stage_dicts_device, dim3(n_items), dim3(256), 0, BR_STREAM, srcs_dev, dicts_dev, dict_bytes_dev, items_dev, starts_dev,
+                     n_items, text, packed);
+  HIP_CHECK(hipGetLastError());
+}
+
+// one workgroup, one copy: the shared dictionary of a call (at most 65 536 bytes)
+__global__ __launch_bounds__(256) void k_batch_copy_device(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, uint32_t bytes) {
+  batch_copy_any(dst, src, bytes);
+}
+
+void batch_copy_device(uint8_t* dst, const uint8_t* src, uint32_t bytes) {
+  if (bytes == 0) return;
+  hipLaunchKernelGGL(k_batch_copy_device, dim3(1), dim3(256), 0, BR_STREAM, dst, src, bytes);
   HIP_CHECK(hipGetLastError());
 }
 

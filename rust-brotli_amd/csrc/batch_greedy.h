@@ -130,15 +130,24 @@ inline Delivery DeliveryRule(size_t stream_size, size_t input_size, size_t capac
   if (stream_size <= capacity && !(max_out_size != 0 && stream_size > max_out_size)) return Delivery::kStream;
   return (max_out_size != 0 && capacity >= max_out_size) ? Delivery::kStored : Delivery::kFails;
 }
-// The device mode of the Batch*Compress calls below (BrotliMi355xCompressBatchDevice): inputs[i] is a device address, the group's
-// items come out of device memory (batch_device.h: batch_stage_device) and its output stays there; no stream comes to the host
-// (`streams` stays empty).  Every item the route answers -- all but the demoted ones and those the reference fails on -- gets
-// sizes[i] and results[i] by DeliveryRule, and its stream, or the stored stream of its input, at outputs[i].
+// What the stream API owes a caller who offers `capacity` bytes for a finished stream (the dictionary batch calls: item i is
+// BrotliEncoderSetCustomDictionary + one FINISH): the stream goes out if and only if it fits.  There is no stored stream to fall
+// back to and no BrotliEncoderMaxCompressedSize to hold it against; input_size is not looked at.  The same signature as
+// DeliveryRule, so that a sink names the one its call is owed.
+inline Delivery StreamDeliveryRule(size_t stream_size, size_t /*input_size*/, size_t capacity) {
+  return stream_size <= capacity ? Delivery::kStream : Delivery::kFails;
+}
+// The device mode of the Batch*Compress calls below (BrotliMi355xCompressBatchDevice, BrotliMi355xCompressBatchWithDictionariesDevice):
+// inputs[i] is a device address, the group's items come out of device memory (batch_device.h: batch_stage_device,
+// batch_stage_dicts_device) and its output stays there; no stream comes to the host (`streams` stays empty).  Every item the route
+// answers -- all but the demoted ones and those the reference fails on -- gets sizes[i] and results[i] by `rule`, and its stream,
+// or the stored stream of its input, at outputs[i].
 struct BatchDeviceSink {
   uint8_t* const* outputs;   // [count] device addresses, any alignment
   const size_t* capacities;  // [count]
   size_t* sizes;             // [count], result
   int32_t* results;          // [count], result: 1 = the item's stream lies at outputs[i], 0 = it fails alone
+  Delivery (*rule)(size_t stream_size, size_t input_size, size_t capacity) = DeliveryRule;  // the dictionary calls: StreamDeliveryRule
 };
 // MakeUncompressedStream (encode.rs:1388-1433) for an input that lies on the device: the header bytes go down with dev_h2d and the
 // body with dev_d2d, one pair per chunk of at most 1 << 24 bytes, and the final byte 3.  Returns the stream's size; the caller's
@@ -155,13 +164,16 @@ void BatchGreedyCompress(const EncoderParams& params, size_t count, const uint8_
 bool BatchDictionaryEligible(const EncoderParams& params, size_t dict_size, size_t input_size);
 void BatchGreedyCompressWithDictionary(const EncoderParams& params, const uint8_t* dict, size_t dict_size, size_t count,
                                        const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
-                                       std::vector<uint8_t>* reference_fails, uint32_t* groups);
+                                       std::vector<uint8_t>* reference_fails, uint32_t* groups, const BatchDeviceSink* sink = nullptr);
 // The same with a dictionary per item: item i lies behind dicts[i] (dict_sizes[i] bytes, after the reference's truncation; several
 // items may share a pointer -- dictionaries are told apart by pointer and size, and each goes up once per group).  Every
 // (dict_sizes[i], sizes[i]) is BatchDictionaryEligible.
+// sink != nullptr, for both: the device mode (BatchDeviceSink, with StreamDeliveryRule) -- `dict`, dicts[i] and inputs[i] are device
+// addresses of any alignment; every item reads its dictionary where it lies (batch_device.h: batch_stage_dicts_device), and the
+// shared dictionary reaches its image by a copy on the device.
 void BatchGreedyCompressWithDictionaries(const EncoderParams& params, size_t count, const uint8_t* const* dicts, const size_t* dict_sizes,
                                          const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
-                                         std::vector<uint8_t>* reference_fails, uint32_t* groups);
+                                         std::vector<uint8_t>* reference_fails, uint32_t* groups, const BatchDeviceSink* sink = nullptr);
 // Items of several blocks, each one chain: 1 << lgblock < size <= kBatchLongBytes, otherwise as BatchGreedyEligible.
 bool BatchLongEligible(const EncoderParams& params, size_t input_size);
 // (*demoted)[i] != 0: a meta-block of item i that is not its last took the size fallback (encode.rs:2141-2163), which the chain

@@ -177,25 +177,34 @@ struct Group {
   bool on_device;     // the caller's items lie in device memory: `uploaded` was filled there (batch_stage_device)
   BatchItem* items_dev;
   uint32_t* order_dev;
+  // on_device behind dictionaries: the padded text, dictionary | item per item, laid out by the same launch that filled `uploaded`
+  // (batch_stage_dicts_device), and A->dict_bytes on the device; nullptr for every other group
+  uint8_t* dict_text = nullptr;
+  uint32_t* dict_bytes_dev = nullptr;
 };
 // The dictionary bytes that go in front of every item of a call in the padded text: one size for all of them (the calls with a
 // shared dictionary; 0: none) or a size per item, of which "all equal" is the former.
+// Where the items lie in device memory the dictionaries do too: their device addresses stand beside the sizes, first byte in use.
 struct DictSizes {
   uint32_t all;
   const size_t* each;  // [count], nullptr: `all`
-  DictSizes(uint32_t all_items) : all(all_items), each(nullptr) {}
-  explicit DictSizes(const size_t* per_item) : all(0), each(per_item) {}
+  const uint8_t* all_dev = nullptr;          // the device mode: the one dictionary ...
+  const uint8_t* const* each_dev = nullptr;  // ... or [count], that of every item
+  DictSizes(uint32_t all_items, const uint8_t* all_items_dev = nullptr) : all(all_items), each(nullptr), all_dev(all_items_dev) {}
+  explicit DictSizes(const size_t* per_item, const uint8_t* const* per_item_dev = nullptr) : all(0), each(per_item), each_dev(per_item_dev) {}
   bool any() const { return each != nullptr || all != 0; }
   uint32_t of(size_t i) const { return each ? (uint32_t)each[i] : all; }
+  const uint8_t* dev(size_t i) const { return each_dev ? each_dev[i] : all_dev; }
 };
 uint32_t DictRoom(uint32_t D) { return (D + 63u) & ~63u; }
 // dict: the dictionary bytes of every item of the call; with a size per item g->A->dict_bytes holds those of the group's items
 // max_items: a bound of the route's own on the items of a group, below BROTLI_MI355X_BATCH_GROUP_ITEMS (0: none)
-// on_device: inputs[i] is a device address (no dictionary).  The same buffer with the same layout is allocated zeroed on the device
-// and filled there by one launch from an array of the group's source addresses: no staging buffer, no memcpy, no bulk upload.
+// on_device: inputs[i] is a device address.  The same buffer with the same layout is allocated zeroed on the device and filled
+// there by one launch from an array of the group's source addresses: no staging buffer, no memcpy, no bulk upload.  Behind
+// dictionaries (dict.dev(i): their device addresses) the same launch lays out the padded text as well (g->dict_text), every
+// dictionary read where it lies: no pool, no upload, and no lz77_batch_dict_text / lz77_batch_dicts_text for the route to run.
 void StageGroup(size_t first, size_t count, const uint8_t* const* inputs, const size_t* sizes, const DictSizes& dict, size_t tables_max,
                 CallArrays* arrays, Group* g, size_t max_items = 0, bool on_device = false) {
-  if (on_device && dict.any()) throw std::runtime_error("brotli_mi355x: the dictionary routes take their items from host memory");
   CallArrays& A = *arrays;
   // (the limit counts the dictionary copies of the padded text: scratch -- keys and flags -- grows with them)
   size_t last = first, padded = 0, packed = 0, dict_copies = 0;
@@ -216,7 +225,8 @@ void StageGroup(size_t first, size_t count, const uint8_t* const* inputs, const 
     A.staging.resize_discard(text_bytes);
     memset(A.staging.data(), 0, text_bytes);
   }
-  A.sources.resize_discard(on_device ? n : 0);
+  const bool dicts_on_device = on_device && dict.any();
+  A.sources.resize_discard(on_device ? (dicts_on_device ? 2 * (size_t)n : n) : 0);  // (the items' addresses, then the dictionaries')
   A.items.resize_discard(n);
   A.order.resize_discard(n);
   A.starts.resize_discard(n);
@@ -229,6 +239,7 @@ void StageGroup(size_t first, size_t count, const uint8_t* const* inputs, const 
     off += DictRoom(A.dict_bytes[i]);
     if (on_device) {
       A.sources[i] = inputs[first + i];
+      if (dicts_on_device) A.sources[n + i] = dict.dev(first + i);
     } else {
       if (!dict.any()) memcpy(A.staging.data() + off, inputs[first + i], bytes);
       memcpy(A.staging.data() + packed_at + start, inputs[first + i], bytes);
@@ -266,16 +277,23 @@ void StageGroup(size_t first, size_t count, const uint8_t* const* inputs, const 
   g->order_dev = g->mem.uninit<uint32_t>((size_t)n * 4);
   dev_h2d(g->order_dev, A.order.data(), (size_t)n * 4);
   if (on_device) {
-    const uint8_t** sources_dev = g->mem.uninit<const uint8_t*>((size_t)n * sizeof(const uint8_t*));
-    dev_h2d(sources_dev, A.sources.data(), (size_t)n * sizeof(const uint8_t*));
+    const uint8_t** sources_dev = g->mem.uninit<const uint8_t*>(A.sources.size() * sizeof(const uint8_t*));
+    dev_h2d(sources_dev, A.sources.data(), A.sources.size() * sizeof(const uint8_t*));
     uint32_t* starts_dev = g->mem.uninit<uint32_t>((size_t)n * 4);
     dev_h2d(starts_dev, A.starts.data(), (size_t)n * 4);
-    batch_stage_device(sources_dev, g->items_dev, starts_dev, n, g->uploaded, g->uploaded + packed_at);
+    if (dicts_on_device) {
+      g->dict_bytes_dev = g->mem.uninit<uint32_t>((size_t)n * 4);
+      dev_h2d(g->dict_bytes_dev, A.dict_bytes.data(), (size_t)n * 4);
+      g->dict_text = g->mem.zeroed<uint8_t>(padded + 64);
+      batch_stage_dicts_device(sources_dev, sources_dev + n, g->dict_bytes_dev, g->items_dev, starts_dev, n, g->dict_text, g->uploaded + packed_at);
+    } else {
+      batch_stage_device(sources_dev, g->items_dev, starts_dev, n, g->uploaded, g->uploaded + packed_at);
+    }
   }
 }
 
 // The device sink of a group: the streams that go out leave the group's output (out_dev, still on the device) for the caller's
-// device buffers by one launch, the others get their answer by DeliveryRule.  An item that takes the stored fallback is copied from
+// device buffers by one launch, the others get their answer by the sink's rule.  An item that takes the stored fallback is copied from
 // the group's packed text.  item: the group's; out_byte / out_bytes: where its stream lies in out_dev.
 struct Outgoing {
   uint32_t item;
@@ -287,7 +305,7 @@ void DeliverGroup(Group& g, const uint8_t* out_dev, const std::vector<Outgoing>&
   for (const Outgoing& o : outgoing) {
     const size_t k = g.first + o.item;
     const uint32_t bytes = A.items[o.item].bytes;
-    switch (DeliveryRule((size_t)o.out_bytes, bytes, sink.capacities[k])) {
+    switch (sink.rule((size_t)o.out_bytes, bytes, sink.capacities[k])) {
       case Delivery::kStream:
         ops.push_back({(uint64_t)(uintptr_t)sink.outputs[k], o.out_byte, o.out_bytes});
         sink.sizes[k] = (size_t)o.out_bytes;
@@ -528,7 +546,7 @@ void CompressGroups(const EncoderParams& p, const uint8_t* dict, uint32_t D, siz
     // (shifted so that it ends on a 16-byte boundary, like its copies in the padded text: k_batch_dict_text moves whole words)
     dict_shifted = call_mem.zeroed<uint8_t>((size_t)D + 16 + 64);
     dict_dev = dict_shifted + ((0u - D) & 15u);
-    dev_h2d_bulk(dict_dev, dict, D);
+    if (sink) batch_copy_device(dict_dev, dict, D); else dev_h2d_bulk(dict_dev, dict, D);  // (the device mode: `dict` is a device address)
     image.bytes = D;
   }
   if (D != 0 && !self_file) {
@@ -556,10 +574,12 @@ void CompressGroups(const EncoderParams& p, const uint8_t* dict, uint32_t D, siz
   size_t first = 0;
   while (first < count) {
     Group g;
-    StageGroup(first, count, inputs, sizes, D, tables_max, &A, &g, 0, sink != nullptr);
+    StageGroup(first, count, inputs, sizes, DictSizes(D, dict_dev), tables_max, &A, &g, 0, sink != nullptr);
     ++*groups;
     uint8_t* text = g.uploaded;
-    if (D != 0) {
+    if (g.dict_text) {
+      text = g.dict_text;  // (the device mode: laid out with the staging, from the call's own copy of the dictionary)
+    } else if (D != 0) {
       text = g.mem.zeroed<uint8_t>(g.padded + 64);
       uint32_t* starts_dev = g.mem.uninit<uint32_t>((size_t)g.n * 4);
       dev_h2d(starts_dev, A.starts.data(), (size_t)g.n * 4);
@@ -579,12 +599,13 @@ void CompressGroups(const EncoderParams& p, const uint8_t* dict, uint32_t D, siz
 // convention of lz77_batch_dict_text), with the place and the size of item i's dictionary beside it -- and lays out the padded
 // text, dictionary | item per item, on the device.  (The group's byte limit counts a dictionary per item, so the pool stays
 // below it.)  dicts[i] / dict_sizes[i]: the dictionary of the call's item i as in use; two items share one where pointer and
-// size agree.
+// size agree.  In the device mode every item reads its dictionary where it lies, and the step hands on what StageGroup left.
 struct DictsText {
   uint8_t* text;             // the group's padded text
   uint32_t* dict_bytes_dev;  // [g.n]: A.dict_bytes on the device
 };
 DictsText StageDictsText(Group& g, const uint8_t* const* dicts, const size_t* dict_sizes) {
+  if (g.dict_text) return DictsText{g.dict_text, g.dict_bytes_dev};  // the device mode: StageGroup has laid the text out
   CallArrays& A = *g.A;
   const size_t first = g.first;
   std::map<std::pair<const uint8_t*, size_t>, uint32_t> placed;
@@ -625,7 +646,7 @@ DictsText StageDictsText(Group& g, const uint8_t* const* dicts, const size_t* di
 // dicts[i] / dict_sizes[i]: the dictionary of item i as in use.
 void CompressGroupsWithDictionaries(const EncoderParams& p, size_t count, const uint8_t* const* dicts, const size_t* dict_sizes,
                                     const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
-                                    std::vector<uint8_t>* reference_fails, uint32_t* groups) {
+                                    std::vector<uint8_t>* reference_fails, uint32_t* groups, const BatchDeviceSink* sink = nullptr) {
   streams->assign(count, std::vector<uint8_t>());
   reference_fails->assign(count, 0);
   *groups = 0;
@@ -638,7 +659,7 @@ void CompressGroupsWithDictionaries(const EncoderParams& p, size_t count, const 
   size_t first = 0;
   while (first < count) {
     Group g;
-    StageGroup(first, count, inputs, sizes, DictSizes(dict_sizes), tables_max, &A, &g);
+    StageGroup(first, count, inputs, sizes, DictSizes(dict_sizes, sink ? dicts : nullptr), tables_max, &A, &g, 0, sink != nullptr);
     ++*groups;
     const DictsText staged = StageDictsText(g, dicts, dict_sizes);
 
@@ -646,7 +667,7 @@ void CompressGroupsWithDictionaries(const EncoderParams& p, size_t count, const 
     J.records = g.mem.uninit<BatchRecord>((size_t)g.n * sizeof(BatchRecord));
     J.item_dict_bytes = staged.dict_bytes_dev;
     lz77_batch_parse_dicts(J);
-    FinishOneBlockItems(p, J, g, streams, reference_fails);
+    FinishOneBlockItems(p, J, g, streams, reference_fails, sink);
     first = g.last;
   }
 }
@@ -655,9 +676,9 @@ void CompressGroupsWithDictionaries(const EncoderParams& p, size_t count, const 
 
 void BatchGreedyCompressWithDictionaries(const EncoderParams& user, size_t count, const uint8_t* const* dicts, const size_t* dict_sizes,
                                          const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
-                                         std::vector<uint8_t>* reference_fails, uint32_t* groups) {
+                                         std::vector<uint8_t>* reference_fails, uint32_t* groups, const BatchDeviceSink* sink) {
   CompressGroupsWithDictionaries(DictionaryItemParams(user, count ? sizes[0] : 0), count, dicts, dict_sizes, inputs, sizes, streams, reference_fails,
-                                 groups);
+                                 groups, sink);
 }
 
 void BatchGreedyCompress(const EncoderParams& user, size_t count, const uint8_t* const* inputs, const size_t* sizes,
@@ -667,8 +688,8 @@ void BatchGreedyCompress(const EncoderParams& user, size_t count, const uint8_t*
 
 void BatchGreedyCompressWithDictionary(const EncoderParams& user, const uint8_t* dict, size_t dict_size, size_t count,
                                        const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
-                                       std::vector<uint8_t>* reference_fails, uint32_t* groups) {
-  CompressGroups(DictionaryItemParams(user, count ? sizes[0] : 0), dict, (uint32_t)dict_size, count, inputs, sizes, streams, reference_fails, groups);
+                                       std::vector<uint8_t>* reference_fails, uint32_t* groups, const BatchDeviceSink* sink) {
+  CompressGroups(DictionaryItemParams(user, count ? sizes[0] : 0), dict, (uint32_t)dict_size, count, inputs, sizes, streams, reference_fails, groups, sink);
 }
 
 namespace {
@@ -772,7 +793,7 @@ bool BatchQuickDictionaryEligible(const EncoderParams& user, size_t dict_size, s
 // files nothing, but positions still count from its first byte); every chain copies it over its own table.
 void BatchQuickCompressWithDictionary(const EncoderParams& user, const uint8_t* dict, size_t dict_use, size_t count,
                                       const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
-                                      std::vector<uint8_t>* reference_fails, uint32_t* groups) {
+                                      std::vector<uint8_t>* reference_fails, uint32_t* groups, const BatchDeviceSink* sink) {
   streams->assign(count, std::vector<uint8_t>());
   reference_fails->assign(count, 0);
   *groups = 0;
@@ -788,7 +809,7 @@ void BatchQuickCompressWithDictionary(const EncoderParams& user, const uint8_t* 
   // (shifted so that it ends on a 16-byte boundary, like its copies in the padded text: k_batch_dict_text moves whole words)
   uint8_t* dict_shifted = call_mem.zeroed<uint8_t>((size_t)D + 16 + 64);
   uint8_t* dict_dev = dict_shifted + ((0u - D) & 15u);
-  dev_h2d_bulk(dict_dev, dict, D);
+  if (sink) batch_copy_device(dict_dev, dict, D); else dev_h2d_bulk(dict_dev, dict, D);  // (the device mode: `dict` is a device address)
   {
     QuickJob image = chains.Q;
     image.table = call_mem.uninit<uint32_t>(QuickTableBytes(chains) + 64);
@@ -803,18 +824,21 @@ void BatchQuickCompressWithDictionary(const EncoderParams& user, const uint8_t* 
   size_t first = 0;
   while (first < count) {
     Group g;
-    StageGroup(first, count, inputs, sizes, D, tables_max, &A, &g);
+    StageGroup(first, count, inputs, sizes, DictSizes(D, dict_dev), tables_max, &A, &g, 0, sink != nullptr);
     ++*groups;
-    uint8_t* text = g.mem.zeroed<uint8_t>(g.padded + 64);
-    uint32_t* starts_dev = g.mem.uninit<uint32_t>((size_t)g.n * 4);
-    dev_h2d(starts_dev, A.starts.data(), (size_t)g.n * 4);
-    lz77_batch_dict_text(dict_shifted, D, g.uploaded, starts_dev, g.items_dev, g.n, text);
+    uint8_t* text = g.dict_text;  // (the device mode: laid out with the staging, from the call's own copy of the dictionary)
+    if (!text) {
+      text = g.mem.zeroed<uint8_t>(g.padded + 64);
+      uint32_t* starts_dev = g.mem.uninit<uint32_t>((size_t)g.n * 4);
+      dev_h2d(starts_dev, A.starts.data(), (size_t)g.n * 4);
+      lz77_batch_dict_text(dict_shifted, D, g.uploaded, starts_dev, g.items_dev, g.n, text);
+    }
     QuickBatchJob J = QuickGroupJob(chains, g);
     J.text = text;
     J.records = g.mem.uninit<BatchRecord>((size_t)g.n * sizeof(BatchRecord));
     lz77_quick_batch_parse_dict(J);
     // (the gather reads raw commands, whose distance codes the chain took from positions that count the dictionary: it needs no D)
-    FinishOneBlockItems(p, GatherJobOf(J), g, streams, reference_fails);
+    FinishOneBlockItems(p, GatherJobOf(J), g, streams, reference_fails, sink);
     first = g.last;
   }
 }
@@ -824,7 +848,7 @@ void BatchQuickCompressWithDictionary(const EncoderParams& user, const uint8_t* 
 // zeroes its table and files its item's dictionary itself (br_quick_batch_file), so nothing is built per dictionary.
 void BatchQuickCompressWithDictionaries(const EncoderParams& user, size_t count, const uint8_t* const* dicts, const size_t* dict_sizes,
                                         const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
-                                        std::vector<uint8_t>* reference_fails, uint32_t* groups) {
+                                        std::vector<uint8_t>* reference_fails, uint32_t* groups, const BatchDeviceSink* sink) {
   streams->assign(count, std::vector<uint8_t>());
   reference_fails->assign(count, 0);
   *groups = 0;
@@ -839,7 +863,7 @@ void BatchQuickCompressWithDictionaries(const EncoderParams& user, size_t count,
   size_t first = 0;
   while (first < count) {
     Group g;
-    StageGroup(first, count, inputs, sizes, DictSizes(dict_sizes), tables_max, &A, &g);
+    StageGroup(first, count, inputs, sizes, DictSizes(dict_sizes, sink ? dicts : nullptr), tables_max, &A, &g, 0, sink != nullptr);
     ++*groups;
     const DictsText staged = StageDictsText(g, dicts, dict_sizes);
     QuickBatchJob J = QuickGroupJob(chains, g);
@@ -848,7 +872,7 @@ void BatchQuickCompressWithDictionaries(const EncoderParams& user, size_t count,
     J.item_dict_bytes = staged.dict_bytes_dev;
     lz77_quick_batch_parse_dicts(J);
     // (the gather reads raw commands, whose distance codes the chain took from positions that count the dictionary: it needs no D)
-    FinishOneBlockItems(p, GatherJobOf(J), g, streams, reference_fails);
+    FinishOneBlockItems(p, GatherJobOf(J), g, streams, reference_fails, sink);
     first = g.last;
   }
 }

@@ -77,14 +77,15 @@ bool BatchQuickDictionaryEligible(const EncoderParams& params, size_t dict_size,
 // copy of one byte at the dictionary end); its stream stays empty.
 void BatchQuickCompressWithDictionary(const EncoderParams& params, const uint8_t* dict, size_t dict_use, size_t count,
                                       const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
-                                      std::vector<uint8_t>* reference_fails, uint32_t* groups);
+                                      std::vector<uint8_t>* reference_fails, uint32_t* groups, const BatchDeviceSink* sink = nullptr);
 // Behind a custom dictionary per item (BrotliMi355xCompressBatchWithDictionaries with
 // BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS): item i is eligible by BatchQuickDictionaryEligible with its own dictionary.
 // dicts[i] / dict_sizes[i]: the dictionary of item i as in use (2 .. 65536 bytes, after the truncation); two items share one
 // where pointer and size agree.  streams, reference_fails, groups: as above.
+// sink != nullptr, for both: the device mode, as for the dictionary routes of batch_greedy.h.
 void BatchQuickCompressWithDictionaries(const EncoderParams& params, size_t count, const uint8_t* const* dicts, const size_t* dict_sizes,
                                         const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
-                                        std::vector<uint8_t>* reference_fails, uint32_t* groups);
+                                        std::vector<uint8_t>* reference_fails, uint32_t* groups, const BatchDeviceSink* sink = nullptr);
 
 }  // namespace brotli_mi355x
 #endif

@@ -1294,9 +1294,10 @@ int32_t BrotliMi355xCompressBatchDevice(int quality, int lgwin, BrotliEncoderMod
 
 // One item of BrotliMi355xCompressBatchWithDictionary by itself, through the stream state machine: the definition of the call, run as
 // it reads.  1 = done; 0 = the item fails alone (its stream does not fit, or the reference fails on it: message set); throws on
-// anything else (a device error fails the whole call).
+// anything else (a device error fails the whole call).  output_on_device: `encoded` is a device address (dictionary and input are
+// host memory all the same); the stream goes up with one copy if it fits, and nothing is written otherwise.
 static int CompressItemWithDictionary(int quality, int lgwin, BrotliEncoderMode mode, size_t dict_size, const uint8_t* dict, size_t input_size,
-                                      const uint8_t* input, size_t* encoded_size, uint8_t* encoded) {
+                                      const uint8_t* input, size_t* encoded_size, uint8_t* encoded, bool output_on_device = false) {
   const size_t capacity = *encoded_size;
   *encoded_size = 0;
   BrotliEncoderState* s = BrotliEncoderCreateInstance(nullptr, nullptr, nullptr);
@@ -1312,22 +1313,51 @@ static int CompressItemWithDictionary(int quality, int lgwin, BrotliEncoderMode 
   // (no room offered: the whole stream stays in the state's buffer, and goes out only if it fits)
   size_t available_in = input_size, available_out = 0;
   const uint8_t* next_in = input;
-  uint8_t* next_out = encoded;
+  uint8_t* next_out = output_on_device ? nullptr : encoded;
   if (!BrotliEncoderCompressStream(s, BROTLI_OPERATION_FINISH, &available_in, &next_in, &available_out, &next_out, nullptr)) {
     if (g_last_error.find("reference encoder fails") != std::string::npos) return 0;
     throw std::runtime_error(g_last_error.empty() ? std::string("BrotliEncoderCompressStream failed") : g_last_error);
   }
   const size_t n = AvailableOut(s);
-  if (n > capacity) return 0;
-  memcpy(encoded, s->output.data() + s->output_pos, n);
+  if (StreamDeliveryRule(n, input_size, capacity) != Delivery::kStream) return 0;
+  if (output_on_device) dev_h2d(encoded, s->output.data() + s->output_pos, n); else memcpy(encoded, s->output.data() + s->output_pos, n);
   *encoded_size = n;
   return 1;
 }
 
-// BrotliMi355xCompressBatchWithDictionary (routes == 0) and BrotliMi355xCompressBatchWithDictionaryEx
+// The items of a dictionary route in the device mode: their buffers, and what the route's groups answered by StreamDeliveryRule
+struct DictionarySink {
+  std::vector<uint8_t*> out;
+  std::vector<size_t> cap, out_size;
+  std::vector<int32_t> result;
+  BatchDeviceSink sink{nullptr, nullptr, nullptr, nullptr};
+  void Add(uint8_t* output, size_t capacity) {
+    out.push_back(output);
+    cap.push_back(capacity);
+  }
+  const BatchDeviceSink* Sink(bool on_device) {
+    if (!on_device) return nullptr;
+    out_size.assign(out.size(), 0);
+    result.assign(out.size(), 0);
+    sink = BatchDeviceSink{out.data(), cap.data(), out_size.data(), result.data(), StreamDeliveryRule};
+    return &sink;
+  }
+};
+// `bytes` bytes at a device address, on the host when the call returns
+static std::vector<uint8_t> DownloadBytes(const uint8_t* device, size_t bytes) {
+  std::vector<uint8_t> host(bytes);
+  if (bytes) dev_d2h(host.data(), device, bytes);
+  return host;
+}
+
+// BrotliMi355xCompressBatchWithDictionary (routes == 0) and BrotliMi355xCompressBatchWithDictionaryEx; with on_device the
+// shared-image path of BrotliMi355xCompressBatchWithDictionariesDevice: dict, inputs[i] and outputs[i] are device addresses -- the
+// side-by-side routes take dictionary and items from device memory and leave the streams there (BatchDeviceSink), an item that runs
+// one by one comes down, runs through the stream path behind the dictionary's bytes in use (down once per call) and its stream
+// goes up, and one dev_sync() ends the call.
 static int32_t CompressBatchWithDictionary(const char* entry, int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t dict_size,
                                            const uint8_t* dict, size_t count, const uint8_t* const* inputs, const size_t* input_sizes,
-                                           uint8_t* const* outputs, size_t* output_sizes, int32_t* item_results) {
+                                           uint8_t* const* outputs, size_t* output_sizes, int32_t* item_results, bool on_device = false) {
   uint64_t info[8] = {count, 0, 0, 0, 0, 0, 0, 0};
   memcpy(g_batch_info, info, sizeof(info));
   if ((routes & ~(uint32_t)BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS) != 0) {
@@ -1366,6 +1396,9 @@ static int32_t CompressBatchWithDictionary(const char* entry, int quality, int l
     std::vector<size_t> item;
     std::vector<const uint8_t*> in;
     std::vector<size_t> in_size;
+    DictionarySink device;
+    std::vector<uint8_t> host_dict;  // on_device: the dictionary's bytes in use, down with the first item that runs one by one
+    bool have_host_dict = false;
     for (size_t i = 0; i < count; ++i) {
       const bool greedy_item = BatchDictionaryEligible(params, dict_size, input_sizes[i]);
       const bool quick_item = !greedy_item && quick_route && BatchQuickDictionaryEligible(params, dict_size, input_sizes[i]);
@@ -1374,9 +1407,19 @@ static int32_t CompressBatchWithDictionary(const char* entry, int quality, int l
         item.push_back(i);
         in.push_back(inputs[i]);
         in_size.push_back(input_sizes[i]);
+        if (on_device) device.Add(outputs[i], output_sizes[i]);
         continue;
       }
-      results[i] = CompressItemWithDictionary(quality, lgwin, mode, dict_size, dict, input_sizes[i], inputs[i], &output_sizes[i], outputs[i]);
+      if (on_device) {
+        // (the stream path cuts the dictionary to the same bytes; dict_use == 0: it takes none, and none comes down)
+        if (!have_host_dict) host_dict = DownloadBytes(dict + (dict_size - dict_use), dict_use);
+        have_host_dict = true;
+        const std::vector<uint8_t> host_item = DownloadBytes(inputs[i], input_sizes[i]);
+        results[i] = CompressItemWithDictionary(quality, lgwin, mode, host_dict.size(), host_dict.data(), host_item.size(), host_item.data(),
+                                                &output_sizes[i], outputs[i], true);
+      } else {
+        results[i] = CompressItemWithDictionary(quality, lgwin, mode, dict_size, dict, input_sizes[i], inputs[i], &output_sizes[i], outputs[i]);
+      }
       ++info[2];
     }
     if (!item.empty()) {
@@ -1384,9 +1427,11 @@ static int32_t CompressBatchWithDictionary(const char* entry, int quality, int l
       std::vector<uint8_t> reference_fails;
       uint32_t groups = 0;
       if (quick)
-        BatchQuickCompressWithDictionary(params, dict + (dict_size - dict_use), dict_use, item.size(), in.data(), in_size.data(), &streams, &reference_fails, &groups);
+        BatchQuickCompressWithDictionary(params, dict + (dict_size - dict_use), dict_use, item.size(), in.data(), in_size.data(), &streams, &reference_fails, &groups,
+                                         device.Sink(on_device));
       else
-        BatchGreedyCompressWithDictionary(params, dict + (dict_size - dict_use), dict_use, item.size(), in.data(), in_size.data(), &streams, &reference_fails, &groups);
+        BatchGreedyCompressWithDictionary(params, dict + (dict_size - dict_use), dict_use, item.size(), in.data(), in_size.data(), &streams, &reference_fails, &groups,
+                                          device.Sink(on_device));
       info[4] = groups;
       info[1] = item.size();
       for (size_t k = 0; k < item.size(); ++k) {
@@ -1399,17 +1444,29 @@ static int32_t CompressBatchWithDictionary(const char* entry, int quality, int l
                     "gives a copy it cannot encode (fix_unbroken_len, backward_references/mod.rs:42-54; GetCopyLengthCode, command.rs:91-93)").c_str());
           continue;
         }
-        if (streams[k].size() > capacity) continue;  // (no fallback to a stored stream: the stream API has none)
+        if (on_device) {  // (the route's groups have answered it, by the same rule)
+          results[i] = device.result[k];
+          output_sizes[i] = device.out_size[k];
+          continue;
+        }
+        if (StreamDeliveryRule(streams[k].size(), input_sizes[i], capacity) != Delivery::kStream) continue;  // (no fallback to a stored stream: the stream API has none)
         memcpy(outputs[i], streams[k].data(), streams[k].size());
         output_sizes[i] = streams[k].size();
         results[i] = 1;
       }
     }
+    if (on_device) dev_sync();  // everything the call wrote has landed
   } catch (const std::exception& e) {
     // a device error fails the call as a whole
     SetError(entry, e.what());
     for (size_t i = 0; i < count; ++i) output_sizes[i] = 0;
     if (item_results) memset(item_results, 0, count * sizeof(int32_t));
+    if (on_device) {  // (what the groups in front of the error queued for the caller's buffers has landed when the call returns)
+      try {
+        dev_sync();
+      } catch (const std::exception&) {
+      }
+    }
     return 0;
   }
   memcpy(g_batch_info, info, sizeof(info));
@@ -1435,11 +1492,15 @@ int32_t BrotliMi355xCompressBatchWithDictionaryEx(int quality, int lgwin, Brotli
                                      outputs, output_sizes, item_results);
 }
 
-int32_t BrotliMi355xCompressBatchWithDictionaries(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t num_dicts,
-                                                  const uint8_t* const* dicts, const size_t* dict_sizes, size_t count, const size_t* item_dicts,
-                                                  const uint8_t* const* inputs, const size_t* input_sizes, uint8_t* const* outputs,
-                                                  size_t* output_sizes, int32_t* item_results) {
-  const char* entry = "BrotliMi355xCompressBatchWithDictionaries";
+// BrotliMi355xCompressBatchWithDictionaries and, with on_device, BrotliMi355xCompressBatchWithDictionariesDevice: there dicts[k],
+// inputs[i] and outputs[i] are device addresses (the arrays themselves are host memory) -- the side-by-side routes read every
+// dictionary and item where it lies and leave the streams in device memory (BatchDeviceSink with StreamDeliveryRule); an item that
+// runs one by one comes down, its dictionary's bytes in use come down once per call, it runs through the stream path and its stream
+// goes up; one dev_sync() ends the call.  What is refused is refused before any device address is looked at.
+static int32_t CompressBatchWithDictionaries(const char* entry, int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t num_dicts,
+                                             const uint8_t* const* dicts, const size_t* dict_sizes, size_t count, const size_t* item_dicts,
+                                             const uint8_t* const* inputs, const size_t* input_sizes, uint8_t* const* outputs,
+                                             size_t* output_sizes, int32_t* item_results, bool on_device) {
   uint64_t info[8] = {count, 0, 0, 0, 0, 0, 0, 0};
   memcpy(g_batch_info, info, sizeof(info));
   // what fails the call as a whole before any work is done, like an unknown route of BrotliMi355xCompressBatchEx
@@ -1469,7 +1530,7 @@ int32_t BrotliMi355xCompressBatchWithDictionaries(int quality, int lgwin, Brotli
     for (size_t i = 1; i < count && one; ++i) one = item_dicts[i] == k0;
     if (one)
       return CompressBatchWithDictionary(entry, quality, lgwin, mode, quick_route ? BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS : 0u, dict_sizes[k0], dicts[k0],
-                                         count, inputs, input_sizes, outputs, output_sizes, item_results);
+                                         count, inputs, input_sizes, outputs, output_sizes, item_results, on_device);
   }
   size_t total = 0;
   for (size_t i = 0; i < count; ++i) total += input_sizes[i];
@@ -1503,6 +1564,10 @@ int32_t BrotliMi355xCompressBatchWithDictionaries(int quality, int lgwin, Brotli
     bool quick = false;
     std::vector<size_t> item, in_size, d_size;
     std::vector<const uint8_t*> in, d;
+    DictionarySink device;
+    // on_device: the bytes in use of the dictionaries that items running one by one name, each down once per call
+    std::vector<std::vector<uint8_t>> host_dicts(on_device ? num_dicts : 0);
+    std::vector<uint8_t> have_host_dict(on_device ? num_dicts : 0, 0);
     for (size_t i = 0; i < count; ++i) {
       const size_t k = item_dicts ? item_dicts[i] : i;
       const bool greedy_item = BatchDictionaryEligible(params, dict_sizes[k], input_sizes[i]);
@@ -1517,9 +1582,19 @@ int32_t BrotliMi355xCompressBatchWithDictionaries(int quality, int lgwin, Brotli
         in_size.push_back(input_sizes[i]);
         d.push_back(dicts[k] + (dict_sizes[k] - use));
         d_size.push_back(use);
+        if (on_device) device.Add(outputs[i], output_sizes[i]);
         continue;
       }
-      results[i] = CompressItemWithDictionary(quality, lgwin, mode, dict_sizes[k], dicts[k], input_sizes[i], inputs[i], &output_sizes[i], outputs[i]);
+      if (on_device) {
+        // (the stream path cuts the dictionary to the same bytes; in_use(k) == 0: it takes none, and none comes down)
+        if (!have_host_dict[k]) host_dicts[k] = DownloadBytes(dicts[k] + (dict_sizes[k] - in_use(k)), in_use(k));
+        have_host_dict[k] = 1;
+        const std::vector<uint8_t> host_item = DownloadBytes(inputs[i], input_sizes[i]);
+        results[i] = CompressItemWithDictionary(quality, lgwin, mode, host_dicts[k].size(), host_dicts[k].data(), host_item.size(), host_item.data(),
+                                                &output_sizes[i], outputs[i], true);
+      } else {
+        results[i] = CompressItemWithDictionary(quality, lgwin, mode, dict_sizes[k], dicts[k], input_sizes[i], inputs[i], &output_sizes[i], outputs[i]);
+      }
       ++info[2];
     }
     if (!item.empty()) {
@@ -1527,9 +1602,11 @@ int32_t BrotliMi355xCompressBatchWithDictionaries(int quality, int lgwin, Brotli
       std::vector<uint8_t> reference_fails;
       uint32_t groups = 0;
       if (quick)
-        BatchQuickCompressWithDictionaries(params, item.size(), d.data(), d_size.data(), in.data(), in_size.data(), &streams, &reference_fails, &groups);
+        BatchQuickCompressWithDictionaries(params, item.size(), d.data(), d_size.data(), in.data(), in_size.data(), &streams, &reference_fails, &groups,
+                                           device.Sink(on_device));
       else
-        BatchGreedyCompressWithDictionaries(params, item.size(), d.data(), d_size.data(), in.data(), in_size.data(), &streams, &reference_fails, &groups);
+        BatchGreedyCompressWithDictionaries(params, item.size(), d.data(), d_size.data(), in.data(), in_size.data(), &streams, &reference_fails, &groups,
+                                            device.Sink(on_device));
       info[4] = groups;
       info[1] = item.size();
       for (size_t n = 0; n < item.size(); ++n) {
@@ -1542,17 +1619,29 @@ int32_t BrotliMi355xCompressBatchWithDictionaries(int quality, int lgwin, Brotli
                     "gives a copy it cannot encode (fix_unbroken_len, backward_references/mod.rs:42-54; GetCopyLengthCode, command.rs:91-93)").c_str());
           continue;
         }
-        if (streams[n].size() > capacity) continue;  // (no fallback to a stored stream: the stream API has none)
+        if (on_device) {  // (the route's groups have answered it, by the same rule)
+          results[i] = device.result[n];
+          output_sizes[i] = device.out_size[n];
+          continue;
+        }
+        if (StreamDeliveryRule(streams[n].size(), input_sizes[i], capacity) != Delivery::kStream) continue;  // (no fallback to a stored stream: the stream API has none)
         memcpy(outputs[i], streams[n].data(), streams[n].size());
         output_sizes[i] = streams[n].size();
         results[i] = 1;
       }
     }
+    if (on_device) dev_sync();  // everything the call wrote has landed
   } catch (const std::exception& e) {
     // a device error fails the call as a whole
     SetError(entry, e.what());
     for (size_t i = 0; i < count; ++i) output_sizes[i] = 0;
     if (item_results) memset(item_results, 0, count * sizeof(int32_t));
+    if (on_device) {  // (what the groups in front of the error queued for the caller's buffers has landed when the call returns)
+      try {
+        dev_sync();
+      } catch (const std::exception&) {
+      }
+    }
     return 0;
   }
   memcpy(g_batch_info, info, sizeof(info));
@@ -1562,6 +1651,22 @@ int32_t BrotliMi355xCompressBatchWithDictionaries(int quality, int lgwin, Brotli
     if (!results[i]) all = 0;
   }
   return all;
+}
+
+int32_t BrotliMi355xCompressBatchWithDictionaries(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t num_dicts,
+                                                  const uint8_t* const* dicts, const size_t* dict_sizes, size_t count, const size_t* item_dicts,
+                                                  const uint8_t* const* inputs, const size_t* input_sizes, uint8_t* const* outputs,
+                                                  size_t* output_sizes, int32_t* item_results) {
+  return CompressBatchWithDictionaries("BrotliMi355xCompressBatchWithDictionaries", quality, lgwin, mode, routes, num_dicts, dicts, dict_sizes, count,
+                                       item_dicts, inputs, input_sizes, outputs, output_sizes, item_results, false);
+}
+
+int32_t BrotliMi355xCompressBatchWithDictionariesDevice(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t num_dicts,
+                                                        const uint8_t* const* dicts_device, const size_t* dict_sizes, size_t count,
+                                                        const size_t* item_dicts, const uint8_t* const* inputs_device, const size_t* input_sizes,
+                                                        uint8_t* const* outputs_device, size_t* output_sizes, int32_t* item_results) {
+  return CompressBatchWithDictionaries("BrotliMi355xCompressBatchWithDictionariesDevice", quality, lgwin, mode, routes, num_dicts, dicts_device, dict_sizes,
+                                       count, item_dicts, inputs_device, input_sizes, outputs_device, output_sizes, item_results, true);
 }
 
 void BrotliMi355xLastBatchInfo(uint64_t info[8]) { memcpy(info, g_batch_info, sizeof(g_batch_info)); }

@@ -80,6 +80,13 @@ streams up (one H2D of the output buffer's used part).  The three alternate insi
 --warmup rounds of all three; the shapes are DEVICE_SHAPES (text).  Per shape: min .. max of each, and whether the device call's
 minimum stays at or below the host call's maximum (the bound: the two differ only by work that was removed).
 
+With --device-dicts (and --parent-lib) the call measured is BrotliMi355xCompressBatchWithDictionariesDevice -- dictionaries and items in one
+uint8 tensor, streams into another -- beside the only way the parent commit has for the same job: dictionaries and items down to
+page-locked memory (one D2H), its BrotliMi355xCompressBatchWithDictionaries, the streams up (one H2D); and beside that host call alone,
+which tells what the staging around it costs.  The shapes are DEVICE_DICTS_SHAPES (text; one of them behind ONE shared dictionary: the
+shared image); the three ways alternate inside one child per shape as for --device.  Per shape: min .. max of each, and whether the
+device call's minimum stays at or below the alternative's maximum.
+
 Every measurement runs in a child process of its own (the table's home is one setting per process, read once; the parent's library
 is another shared object), one after the other, each under its own time limit; the first failure ends the probe.
 
@@ -521,9 +528,153 @@ def main_device(args, doc, save):
     print(json.dumps(doc, indent=1))
 
 
+# (--device-dicts) DICTS_CLASSES class, quality, route bits of the device call, one shared dictionary instead of one per item
+DEVICE_DICTS_SHAPES = [("4096x4KiB+16KiB", 5, 0, False), ("4096x4KiB+16KiB", 2, 512, False), ("1024x16KiB+64KiB", 5, 0, False),
+                       ("4096x4KiB+16KiB", 5, 0, True), ("64x4KiB+16KiB", 5, 0, False)]
+
+
+def child_device_dicts(args):
+    """--device-dicts: one shape -- BrotliMi355xCompressBatchWithDictionariesDevice of this build on tensors, beside the only way the
+    parent commit has for dictionaries and items in device memory: both down to page-locked memory, its host dictionary call, the
+    streams up; and that host call alone (what the staging around it costs).  The three alternate."""
+    import torch
+    name, quality, routes, shared = args.classes, int(args.qualities), args.routes, bool(args.shared)
+    items, dictionaries = dicts_of(name)
+    n = len(items)
+    if shared:
+        dictionaries = dictionaries[:1]
+    nd = len(dictionaries)
+    named = [0] * n if shared else list(range(n))
+    L, P = bind(args.lib), bind(args.parent_lib or args.lib)
+    caps = [L.BrotliEncoderMaxCompressedSize(len(x)) + 1024 for x in items]
+    dict_at, in_at, out_at, a, b = [], [], [], 0, 0
+    for d in dictionaries:
+        dict_at.append(a)
+        a += len(d)
+    for x, c in zip(items, caps):
+        in_at.append(a)
+        out_at.append(b)
+        a += len(x)
+        b += c
+    src = torch.frombuffer(bytearray(b"".join(dictionaries) + b"".join(items)), dtype=torch.uint8).cuda()
+    dst = torch.zeros(b, dtype=torch.uint8, device="cuda")
+    h_src = torch.empty(a, dtype=torch.uint8).pin_memory()
+    h_dst = torch.empty(b, dtype=torch.uint8).pin_memory()
+    h_src.copy_(src)
+    dict_sizes = (ctypes.c_size_t * nd)(*[len(d) for d in dictionaries])
+    item_dicts = (ctypes.c_size_t * n)(*named)
+    in_sizes = (ctypes.c_size_t * n)(*[len(x) for x in items])
+    out_sizes = (ctypes.c_size_t * n)()
+    results = (ctypes.c_int32 * n)()
+    d_dicts = (ctypes.c_void_p * nd)(*[src.data_ptr() + o for o in dict_at])
+    d_in = (ctypes.c_void_p * n)(*[src.data_ptr() + o for o in in_at])
+    d_out = (ctypes.c_void_p * n)(*[dst.data_ptr() + o for o in out_at])
+    h_dicts = (ctypes.c_void_p * nd)(*[h_src.data_ptr() + o for o in dict_at])
+    h_in = (ctypes.c_void_p * n)(*[h_src.data_ptr() + o for o in in_at])
+    h_out = (ctypes.c_void_p * n)(*[h_dst.data_ptr() + o for o in out_at])
+    for lib, entry in ((L, "BrotliMi355xCompressBatchWithDictionariesDevice"), (P, "BrotliMi355xCompressBatchWithDictionaries")):
+        f = getattr(lib, entry)
+        f.restype = ctypes.c_int32
+        f.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+
+    def reset():
+        for i in range(n):
+            out_sizes[i] = caps[i]
+
+    def answer():
+        # (at quality 2 the reference fails on a few text items in a thousand: they fail alone, the same ones every way)
+        return [out_sizes[i] if results[i] else 0 for i in range(n)]
+
+    def device_call():
+        reset()
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        L.BrotliMi355xCompressBatchWithDictionariesDevice(quality, LGWIN, 0, routes, nd, d_dicts, dict_sizes, n, item_dicts, d_in, in_sizes, d_out, out_sizes, results)
+        dt = time.perf_counter() - t
+        return dt, answer()
+
+    def host_call():
+        reset()
+        t = time.perf_counter()
+        P.BrotliMi355xCompressBatchWithDictionaries(quality, LGWIN, 0, routes, nd, h_dicts, dict_sizes, n, item_dicts, h_in, in_sizes, h_out, out_sizes, results)
+        dt = time.perf_counter() - t
+        return dt, answer()
+
+    def alternative():
+        reset()
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        h_src.copy_(src)  # (synchronous: dictionaries and items, device to page-locked host memory)
+        P.BrotliMi355xCompressBatchWithDictionaries(quality, LGWIN, 0, routes, nd, h_dicts, dict_sizes, n, item_dicts, h_in, in_sizes, h_out, out_sizes, results)
+        used = out_at[-1] + out_sizes[n - 1]
+        dst[:used].copy_(h_dst[:used])
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t
+        return dt, answer()
+
+    times = {"device": [], "host": [], "alternative": []}
+    sizes = None
+    for it in range(args.warmup + args.runs):
+        for what, call in (("device", device_call), ("alternative", alternative), ("host", host_call)):
+            dt, got = call()
+            assert sizes is None or got == sizes, (what, it)  # (the same answers from every way)
+            sizes = got
+            if it >= args.warmup:
+                times[what].append(dt)
+    assert sum(1 for k in sizes if k == 0) <= n // 50, "more items fail than the reference fails on"
+    # the streams themselves: the device call's against the parent's host call's
+    dst.zero_()
+    device_call()
+    image = dst.cpu().numpy().tobytes()
+    info = (ctypes.c_uint64 * 8)()
+    L.BrotliMi355xLastBatchInfo(info)
+    host_call()
+    host_image = h_dst.numpy().tobytes()
+    host_info = (ctypes.c_uint64 * 8)()
+    P.BrotliMi355xLastBatchInfo(host_info)
+    assert all(image[o:o + k] == host_image[o:o + k] for o, k in zip(out_at, sizes))
+    assert list(info) == list(host_info), (list(info), list(host_info))
+    row = {"class": name, "data": "text", "quality": quality, "routes": routes, "shared_dictionary": shared, "items": n, "item_bytes": a - in_at[0],
+           "dictionary_bytes": in_at[0], "compressed_bytes": sum(sizes), "items_the_reference_fails_on": sum(1 for k in sizes if k == 0), "batch_info": list(info)}
+    for what in times:
+        row[what] = stats(times[what])
+    row["device_min_within_alternative_max"] = bool(row["device"]["min_ms"] <= row["alternative"]["max_ms"])
+    print(json.dumps(row), flush=True)
+    with open(args.child_out, "w") as f:
+        json.dump([row], f)
+
+
+def main_device_dicts(args, doc, save):
+    doc["what"] = ("BrotliMi355xCompressBatchWithDictionariesDevice (dictionaries and items in one tensor, streams into another) vs the parent commit's only "
+                   "way for the same job: dictionaries and items down to page-locked memory, its BrotliMi355xCompressBatchWithDictionaries, the streams up "
+                   "('alternative'); 'host' is that host call alone from page-locked memory; text, lgwin 22; alternating inside one process per shape")
+    doc["method"] = "host clock around each synchronous way, %d warm-up rounds of all three, then %d rounds; min .. max of the repeats" % (args.warmup, args.runs)
+    doc["shapes"] = []
+    tmp = os.path.join(os.path.dirname(os.path.abspath(args.out)), ".batch_probe_child.json")
+    for name, quality, routes, shared in DEVICE_DICTS_SHAPES:
+        tag = name + "/q%d" % quality + ("/shared" if shared else "")
+        if args.only and tag not in args.only.split(","):
+            continue
+        cmd = ["timeout", "-k", "10", "300", sys.executable, os.path.abspath(__file__), "--child", "device-dicts", "--classes", name, "--qualities", str(quality),
+               "--routes", str(routes), "--lib", args.lib, "--runs", str(args.runs), "--warmup", str(args.warmup), "--child-out", tmp]
+        cmd += (["--shared"] if shared else []) + (["--parent-lib", os.path.abspath(args.parent_lib)] if args.parent_lib else [])
+        r = subprocess.run(cmd)
+        if r.returncode != 0:
+            raise SystemExit("batch_probe: the shape %s ended with status %d: nothing more is started" % (tag, r.returncode))
+        doc["shapes"] += json.load(open(tmp))
+        os.remove(tmp)
+        save()
+    doc["device_min_within_alternative_max_on_every_shape"] = all(r["device_min_within_alternative_max"] for r in doc["shapes"])
+    save()
+    print(json.dumps(doc, indent=1))
+
+
 def child(args):
     if args.child == "device":
         return child_device(args)
+    if args.child == "device-dicts":
+        return child_device_dicts(args)
     if args.dicts:
         return child_dicts(args)
     out = []
@@ -824,7 +975,9 @@ def main():
     ap.add_argument("--q9-items", action="store_true", help="this build through BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS (--qualities 9,10)")
     ap.add_argument("--dicts", action="store_true", help="BrotliMi355xCompressBatchWithDictionaries: a dictionary per item (--qualities 5,8; 2,3,4 through BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS)")
     ap.add_argument("--device", action="store_true", help="BrotliMi355xCompressBatchDevice on torch tensors beside the parent's host call on the same items (DEVICE_SHAPES)")
+    ap.add_argument("--device-dicts", action="store_true", help="BrotliMi355xCompressBatchWithDictionariesDevice on torch tensors beside download + the parent's host dictionary call + upload (DEVICE_DICTS_SHAPES)")
     ap.add_argument("--routes", type=int, default=0, help="(child) route bits of the device shape")
+    ap.add_argument("--shared", action="store_true", help="(child, device-dicts) one dictionary named by every item")
     ap.add_argument("--same-call", action="store_true", help="the parent's library through the same call as this build, alternating --rounds times (needs --parent-lib)")
     ap.add_argument("--quick-long-classes", action="store_true", help="(child) only the qualities of QUICK_LONG_QUALITIES")
     ap.add_argument("--plain", action="store_true", help="(child) the plain call although a dictionary size is given")
@@ -847,6 +1000,8 @@ def main():
 
     if args.device:
         return main_device(args, doc, save)
+    if args.device_dicts:
+        return main_device_dicts(args, doc, save)
     if args.quick_long_items:
         args.quick_items = True
         args.qualities = "2,3,4"
