@@ -244,8 +244,17 @@ void PlanGreedyPools(DevMem* mm, std::vector<MbDesc>* descs, MbBuffers* B) {
     B->switch_nbits[k] = mm->alloc<uint8_t>(block_total[k] + 8);
   }
   B->header_words = mm->alloc<uint64_t>((size_t)n_mb * kHeaderWords);
+  B->header_prefix_bits = mm->alloc<uint32_t>(n_mb + 1);
   B->ctxmap_scratch = mm->alloc<uint32_t>((size_t)n_mb * 2 * 256 * 64);
   B->mb_out_bit = mm->alloc<uint64_t>(n_mb + 1);
+}
+
+// How the prefix code of a histogram of kind k is made (CodeJob::mode, metablock_fast.h)
+uint32_t CodeModeOf(const MbDesc& d, uint32_t k) {
+  if (d.simple == kMbTrivial) return kCodePlain;
+  // (quality 2: up to 128 commands are written with the static command and distance codes, brotli_bit_stream.rs:2619-2687)
+  if (d.simple == kMbFast) return (d.n_cmds <= 128 && k != kSplitLiteral) ? kCodeStatic : kCodeFast;
+  return kCodeOptimized;
 }
 
 // The tail of the emission: the headers of the compressed meta-blocks, the bytes of the stored ones and what the host composed, in
@@ -434,6 +443,7 @@ void BuildHqMetaBlocks(const EncoderParams& p, DevMem& mm, MbBuffers& B, std::ve
     B.switch_nbits[k] = mm.alloc<uint8_t>(block_total[k] + 8);
   }
   B.header_words = mm.alloc<uint64_t>((size_t)n_mb * kHqHeaderWords);
+  B.header_prefix_bits = mm.alloc<uint32_t>(n_mb + 1);
   B.ctxmap_scratch = mm.alloc<uint32_t>((size_t)n_mb * 2 * 256 * 64);
   B.mb_out_bit = mm.alloc<uint64_t>(n_mb + 1);
   dev_h2d(B.descs, descs.data(), n_mb * sizeof(MbDesc));
@@ -782,26 +792,6 @@ void EncodeStream(const EncodeRequest& req, std::vector<uint8_t>* out, EncodeSta
       d.simple = p.quality <= 2 ? kMbFast : (p.quality < 4 ? kMbTrivial : kMbGreedy);
       if (d.simple != kMbGreedy) d.context_mode = 0;
     }
-    // prev bytes (encode.rs:2526-2534): bytes preceding the meta-block in the stream, 0 at the very start
-    if (!all_raw) {
-      std::vector<uint32_t> where((size_t)n_mb * 2, 0xffffffffu);
-      for (uint32_t m = 0; m < n_mb; ++m) {
-        const uint32_t s = descs[m].start;
-        const uint32_t lo = prev_floor;
-        if (s >= lo + 2) where[2 * m] = s - 2;
-        if (s >= lo + 1) where[2 * m + 1] = s - 1;
-      }
-      uint32_t* where_dev = mm.alloc<uint32_t>((size_t)n_mb * 2);
-      uint8_t* tails_dev = mm.alloc<uint8_t>((size_t)n_mb * 2);
-      std::vector<uint8_t> tails((size_t)n_mb * 2, 0);
-      dev_h2d(where_dev, where.data(), where.size() * 4);
-      mb_gather_bytes(text, where_dev, n_mb * 2, tails_dev);
-      dev_d2h(tails.data(), tails_dev, tails.size());
-      for (uint32_t m = 0; m < n_mb; ++m) {
-        descs[m].prev_byte = tails[2 * m + 1];
-        descs[m].prev_byte2 = tails[2 * m];
-      }
-    }
     {
       uint32_t lit_base = 0;
       for (uint32_t m = 0; m < n_mb; ++m) {
@@ -812,34 +802,57 @@ void EncodeStream(const EncodeRequest& req, std::vector<uint8_t>* out, EncodeSta
     std::vector<MbResult> results(n_mb);
     std::vector<uint32_t> body_off(n_mb + 1);
     if (!all_raw) {
+    // Three small results come back from the device in front of the splitters: the two bytes in front of every meta-block, the
+    // distance-symbol boundaries and the context statistics.  None of the kernels that make them needs another's result (the
+    // statistics read start / end / uncompressed of a descriptor only), so they are queued one after the other and fetched with
+    // one wait.
+    const bool context_stats = !hq && p.disable_literal_context_modeling == 0 && p.quality >= 5;  // (DecideOverLiteralContextModeling leaves lower qualities alone)
+    // prev bytes (encode.rs:2526-2534): bytes preceding the meta-block in the stream, 0 at the very start
+    std::vector<uint32_t> where((size_t)n_mb * 2, 0xffffffffu);
+    for (uint32_t m = 0; m < n_mb; ++m) {
+      const uint32_t s = descs[m].start;
+      const uint32_t lo = prev_floor;
+      if (s >= lo + 2) where[2 * m] = s - 2;
+      if (s >= lo + 1) where[2 * m + 1] = s - 1;
+    }
+    uint32_t* where_dev = mm.alloc<uint32_t>((size_t)n_mb * 2);
+    // (one block for the three, so that one copy brings them down: boundaries, statistics rows, bytes)
+    const size_t stats_words = context_stats ? (size_t)n_mb * kContextStatsWords : 0;
+    const size_t fetch_words = (size_t)n_mb + 1 + stats_words + ((size_t)n_mb * 2 + 3) / 4;
+    uint32_t* fetch_dev = mm.alloc<uint32_t>(fetch_words);
+    uint32_t* boundary_words = fetch_dev;
+    uint32_t* stats_dev = fetch_dev + n_mb + 1;
+    uint8_t* tails_dev = (uint8_t*)(stats_dev + stats_words);
+    std::vector<uint32_t> fetched(fetch_words);
+    const uint32_t* di = fetched.data();  // distance symbol counts per meta-block
+    const uint32_t* cs = fetched.data() + n_mb + 1;
+    const uint8_t* tails = (const uint8_t*)(cs + stats_words);
     dev_h2d(B.descs, descs.data(), n_mb * sizeof(MbDesc));
-    uint32_t* boundary_words = mm.alloc<uint32_t>(n_mb + 1);
+    dev_h2d(where_dev, where.data(), where.size() * 4);
     mb_command_scans(B, scan_scratch);
     mb_literal_map(B);
-    // distance symbol counts per meta-block
-    {
-      std::vector<uint32_t> di(n_mb + 1);
-      mb_gather_at_metablock_starts(B, B.cmd_dist_index, boundary_words);
-      dev_d2h(di.data(), boundary_words, (n_mb + 1) * 4);
-      for (uint32_t m = 0; m < n_mb; ++m) {
-        descs[m].dist_base = di[m];
-        descs[m].n_dists = di[m + 1] - di[m];
-      }
-      B.n_dists = di[n_mb];
+    mb_gather_at_metablock_starts(B, B.cmd_dist_index, boundary_words);
+    mb_gather_bytes(text, where_dev, n_mb * 2, tails_dev);
+    if (context_stats) mb_context_stats(B, stats_dev);
+    dev_d2h(fetched.data(), fetch_dev, fetch_words * 4);
+    for (uint32_t m = 0; m < n_mb; ++m) {
+      descs[m].prev_byte = tails[2 * m + 1];
+      descs[m].prev_byte2 = tails[2 * m];
+      descs[m].dist_base = di[m];
+      descs[m].n_dists = di[m + 1] - di[m];
     }
+    B.n_dists = di[n_mb];
+    std::vector<CodeJob> jobs;
+    CodeJob* jobs_dev = nullptr;
     if (hq) {
       BuildHqMetaBlocks(p, mm, B, descs, results, [&](int phase, const char* name) { stats.ms_phase[phase] += clk.lap(prof, name); });
     } else {
       // literal context modelling decision
-      if (p.disable_literal_context_modeling == 0 && p.quality >= 5) {  // (DecideOverLiteralContextModeling leaves lower qualities alone)
-        uint32_t* stats_dev = mm.alloc<uint32_t>((size_t)n_mb * kContextStatsWords);
-        mb_context_stats(B, stats_dev);
-        std::vector<uint32_t> cs((size_t)n_mb * kContextStatsWords);
-        dev_d2h(cs.data(), stats_dev, cs.size() * 4);
-        if (getenv("BROTLI_MI355X_SELFTEST")) SelfTestContextStats(text, descs, cs);
+      if (context_stats) {
+        if (getenv("BROTLI_MI355X_SELFTEST")) SelfTestContextStats(text, descs, std::vector<uint32_t>(cs, cs + stats_words));
         for (uint32_t m = 0; m < n_mb; ++m) {
           if (descs[m].uncompressed) continue;
-          DecideContexts(cs.data() + (size_t)m * kContextStatsWords, p.quality, p.size_hint, descs[m].end - descs[m].start,
+          DecideContexts(cs + (size_t)m * kContextStatsWords, p.quality, p.size_hint, descs[m].end - descs[m].start,
                          &descs[m].num_contexts, &descs[m].context_map_id);
         }
       }
@@ -850,25 +863,41 @@ void EncodeStream(const EncodeRequest& req, std::vector<uint8_t>* out, EncodeSta
       stats.ms_phase[2] += clk.lap(prof, "mb2");
       bool wide = false;
       for (uint32_t m = 0; m < n_mb; ++m) wide = wide || (!descs[m].uncompressed && descs[m].num_contexts > 3);
+      // Huffman codes: how many histograms a splitter ends with is known on the device only, and the host does not wait for it:
+      // one job per slot of the pools handed out above (at most 257 slots per kind and context), listed and uploaded in front
+      // of the splitters; a job whose slot stays empty returns at once (CodeJob::mb_plus_1).  Slot by slot across the
+      // meta-blocks, so that the jobs with work to do -- the low slots -- are the first workgroups of the launch.
+      // (The emulation's loop carries out every job it is handed: an empty slot's row is zeros, or a histogram the splitter left
+      // behind, and gets a code that nothing reads.)
+      uint32_t most_slots = 0;
+      for (uint32_t m = 0; m < n_mb; ++m)
+        if (!descs[m].uncompressed)
+          for (uint32_t k = 0; k < 3; ++k) most_slots = std::max(most_slots, descs[m].max_histos[k]);
+      for (uint32_t slot = 0; slot < most_slots; ++slot)
+        for (uint32_t m = 0; m < n_mb; ++m) {
+          if (descs[m].uncompressed) continue;
+          for (uint32_t k = 0; k < 3; ++k)
+            if (slot < descs[m].max_histos[k])
+              jobs.push_back({k, descs[m].histo_base[k] + slot, descs[m].num_distance_symbols, CodeModeOf(descs[m], k), m + 1, slot});
+        }
+      B.huff_scratch = mm.alloc<HuffmanScratch>(n_mb + 1);
+      jobs_dev = mm.alloc<CodeJob>(jobs.size() + 1);
+      dev_h2d(jobs_dev, jobs.data(), jobs.size() * sizeof(CodeJob));
       mb_split_chains(B, wide);
-      dev_d2h(results.data(), B.results, n_mb * sizeof(MbResult));
       stats.ms_phase[3] += clk.lap(prof, "mb3");
     }
-    // Huffman codes: one job per histogram
-    std::vector<CodeJob> jobs;
-    for (uint32_t m = 0; m < n_mb; ++m) {
-      if (descs[m].uncompressed) continue;
-      for (uint32_t k = 0; k < 3; ++k) {
-        uint32_t mode = kCodeOptimized;
-        if (descs[m].simple == kMbTrivial) mode = kCodePlain;
-        // (quality 2: up to 128 commands are written with the static command and distance codes, brotli_bit_stream.rs:2619-2687)
-        if (descs[m].simple == kMbFast) mode = (descs[m].n_cmds <= 128 && k != kSplitLiteral) ? kCodeStatic : kCodeFast;
-        for (uint32_t i = 0; i < results[m].num_histos[k]; ++i) jobs.push_back({k, descs[m].histo_base[k] + i, descs[m].num_distance_symbols, mode});
+    if (hq) {
+      // (the quality >= 10 builder has fetched its results: one job per histogram)
+      for (uint32_t m = 0; m < n_mb; ++m) {
+        if (descs[m].uncompressed) continue;
+        for (uint32_t k = 0; k < 3; ++k)
+          for (uint32_t i = 0; i < results[m].num_histos[k]; ++i)
+            jobs.push_back({k, descs[m].histo_base[k] + i, descs[m].num_distance_symbols, CodeModeOf(descs[m], k), 0, 0});
       }
+      B.huff_scratch = mm.alloc<HuffmanScratch>(n_mb + 1);
+      jobs_dev = mm.alloc<CodeJob>(jobs.size() + 1);
+      dev_h2d(jobs_dev, jobs.data(), jobs.size() * sizeof(CodeJob));
     }
-    B.huff_scratch = mm.alloc<HuffmanScratch>(std::max<size_t>(jobs.size(), n_mb) + 1);
-    CodeJob* jobs_dev = mm.alloc<CodeJob>(jobs.size() + 1);
-    dev_h2d(jobs_dev, jobs.data(), jobs.size() * sizeof(CodeJob));
     mb_build_codes(B, jobs_dev, (uint32_t)jobs.size());
     stats.ms_phase[4] += clk.lap(prof, "mb4");
     mb_write_headers(B);
@@ -878,12 +907,15 @@ void EncodeStream(const EncodeRequest& req, std::vector<uint8_t>* out, EncodeSta
     dev_d2h_async(results.data(), B.results, n_mb * sizeof(MbResult));
     dev_d2h_async(body_off.data(), boundary_words, (n_mb + 1) * 4);
     dev_sync();
-    if (getenv("BROTLI_MI355X_DEBUG_MB"))
+    if (getenv("BROTLI_MI355X_DEBUG_MB")) {
+      std::vector<uint32_t> prefix_bits(n_mb);
+      dev_d2h(prefix_bits.data(), B.header_prefix_bits, n_mb * 4);
       for (uint32_t m = 0; m < n_mb; ++m)
-        fprintf(stderr, "  meta-block %u [%u,%u) cmds %u lits %u contexts %u | literal blocks %u types %u | command blocks %u types %u | distance blocks %u types %u | header %u bits\n",
+        fprintf(stderr, "  meta-block %u [%u,%u) cmds %u lits %u contexts %u | literal blocks %u types %u | command blocks %u types %u | distance blocks %u types %u | header %u bits, %u in front of the trees\n",
                 m, descs[m].start, descs[m].end, descs[m].n_symbols[1], descs[m].n_symbols[0], descs[m].num_contexts, results[m].num_blocks[0],
                 results[m].num_types[0], results[m].num_blocks[1], results[m].num_types[1], results[m].num_blocks[2], results[m].num_types[2],
-                results[m].header_bits);
+                results[m].header_bits, prefix_bits[m]);
+    }
     stats.ms_phase[6] += clk.lap(prof, "mb6");
     }  // !all_raw
 
@@ -1196,13 +1228,9 @@ void EncodeBatchMetaBlocks(const EncoderParams& p, const uint8_t* text, const Co
     std::vector<CodeJob> jobs;
     for (uint32_t m = 0; m < n_mb; ++m) {
       if (descs[m].uncompressed) continue;
-      for (uint32_t k = 0; k < 3; ++k) {
-        uint32_t mode = kCodeOptimized;
-        if (descs[m].simple == kMbTrivial) mode = kCodePlain;
-        // (quality 2: up to 128 commands are written with the static command and distance codes, brotli_bit_stream.rs:2619-2687)
-        if (descs[m].simple == kMbFast) mode = (descs[m].n_cmds <= 128 && k != kSplitLiteral) ? kCodeStatic : kCodeFast;
-        for (uint32_t i = 0; i < results[m].num_histos[k]; ++i) jobs.push_back({k, descs[m].histo_base[k] + i, descs[m].num_distance_symbols, mode});
-      }
+      for (uint32_t k = 0; k < 3; ++k)
+        for (uint32_t i = 0; i < results[m].num_histos[k]; ++i)
+          jobs.push_back({k, descs[m].histo_base[k] + i, descs[m].num_distance_symbols, CodeModeOf(descs[m], k), 0, 0});
     }
     B.huff_scratch = mm.alloc<HuffmanScratch>(std::max<size_t>(jobs.size(), n_mb) + 1);
     CodeJob* jobs_dev = mm.alloc<CodeJob>(jobs.size() + 1);

@@ -34,6 +34,8 @@ void Lz77Stage::Release() {
   histo_dev_ = gather_offsets_dev_ = gather_counts_dev_ = nullptr;
   gathered_cmds_ = nullptr;
   gathered_capacity_ = 0;
+  gather_fix_dev_[0] = gather_fix_dev_[1] = nullptr;
+  gather_fix_capacity_[0] = gather_fix_capacity_[1] = 0;
 }
 
 // What every path of Setup() ends with: the command slabs, the per-segment arrays and the arrays of Gather()
@@ -2900,18 +2902,33 @@ void Lz77Stage::Gather() {
     gathered_capacity_ = total + total / 8 + 1024;
     gathered_cmds_ = mem_.zeroed<Command>(gathered_capacity_ * sizeof(Command));
   }
-  dev_h2d(gather_offsets_dev_, offsets.data(), nseg * 4);
-  dev_h2d(gather_counts_dev_, counts.data(), nseg * 4);
-  lz77_gather_commands(P_, B_, nseg, gather_offsets_dev_, gather_counts_dev_, gathered_cmds_);
-  for (const std::vector<CmdPatch>* batch : {&fix, &fix_ext}) {
-    if (batch->empty()) continue;
-    DevBlocks tmp;
-    CmdPatch* fix_dev = tmp.zeroed<CmdPatch>(batch->size() * sizeof(CmdPatch));
-    dev_h2d(fix_dev, batch->data(), batch->size() * sizeof(CmdPatch));
-    lz77_patch_commands(gathered_cmds_, fix_dev, (uint32_t)batch->size());
-    dev_sync();
+  // Nothing below is waited for.  The uploads read page-locked memory of the stage (Run() has fetched the segments' exits, and so
+  // waited for the stream, since the last call wrote it); the patches' device memory is the stage's own; and the stream orders
+  // the gather in front of both patch launches and the first batch in front of the second.
+  gather_words_upload_.resize_discard((size_t)nseg * 2);
+  if (nseg) {
+    memcpy(gather_words_upload_.data(), offsets.data(), (size_t)nseg * 4);
+    memcpy(gather_words_upload_.data() + nseg, counts.data(), (size_t)nseg * 4);
   }
-  dev_sync();
+  dev_h2d(gather_offsets_dev_, gather_words_upload_.data(), nseg * 4);
+  dev_h2d(gather_counts_dev_, gather_words_upload_.data() + nseg, nseg * 4);
+  lz77_gather_commands(P_, B_, nseg, gather_offsets_dev_, gather_counts_dev_, gathered_cmds_);
+  gather_fix_upload_.resize_discard(fix.size() + fix_ext.size());
+  size_t at = 0;
+  int i = 0;
+  for (const std::vector<CmdPatch>* batch : {&fix, &fix_ext}) {
+    const int which = i++;
+    if (batch->empty()) continue;
+    if (gather_fix_capacity_[which] < batch->size()) {
+      mem_.drop(gather_fix_dev_[which]);
+      gather_fix_capacity_[which] = batch->size() + batch->size() / 4 + 64;
+      gather_fix_dev_[which] = mem_.uninit<CmdPatch>(gather_fix_capacity_[which] * sizeof(CmdPatch));
+    }
+    memcpy(gather_fix_upload_.data() + at, batch->data(), batch->size() * sizeof(CmdPatch));
+    dev_h2d(gather_fix_dev_[which], gather_fix_upload_.data() + at, batch->size() * sizeof(CmdPatch));
+    lz77_patch_commands(gathered_cmds_, gather_fix_dev_[which], (uint32_t)batch->size());
+    at += batch->size();
+  }
 }
 
 }  // namespace brotli_mi355x

@@ -279,6 +279,12 @@ class Lz77Stage {
   uint32_t* histo_dev_ = nullptr;
   uint32_t* gather_offsets_dev_ = nullptr;
   uint32_t* gather_counts_dev_ = nullptr;
+  // Gather() queues its uploads and launches and does not wait for them: what it uploads from (offsets and counts; the two
+  // patch batches) is page-locked memory of the stage, the patches' device memory is in mem_ (grow-only)
+  PinnedArray<uint32_t> gather_words_upload_;
+  PinnedArray<CmdPatch> gather_fix_upload_;
+  CmdPatch* gather_fix_dev_[2] = {nullptr, nullptr};
+  size_t gather_fix_capacity_[2] = {0, 0};
   Lz77Stats stats_;
   uint32_t dbg_counts_[4] = {0, 0, 0, 0};
   uint32_t dbg_first_[4] = {0, 0, 0, 0};

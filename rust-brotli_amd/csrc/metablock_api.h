@@ -23,6 +23,11 @@ struct CodeJob {
   uint32_t row_index;
   uint32_t num_distance_symbols;
   uint32_t mode;  // kCodeOptimized / kCodePlain / kCodeFast / kCodeStatic (metablock_fast.h)
+  // A job listed for a slot of a meta-block's histogram pool before the splitter has run: meta-block + 1 and the slot's number
+  // inside the pool of its kind; the job has nothing to do when the splitter ends with num_histos[kind] <= slot.
+  // mb_plus_1 == 0: a job listed from the results themselves, always carried out.
+  uint32_t mb_plus_1;
+  uint32_t slot;
 };
 
 size_t mb_scan_scratch_bytes(size_t n);
@@ -36,6 +41,8 @@ void mb_literal_map(const MbBuffers& B);
 void mb_context_stats(const MbBuffers& B, uint32_t* stats_dev);
 void mb_granule_histograms(const MbBuffers& B);
 void mb_split_chains(const MbBuffers& B, bool wide = false);
+// the prefix codes of the jobs and, in the same launch, the header prefix of each of the B.n_mb meta-blocks (mb_item_header_prefix:
+// it needs the splitter's results only); mb_write_headers then appends the serialised trees
 void mb_build_codes(const MbBuffers& B, const CodeJob* jobs_dev, uint32_t n_jobs);
 void mb_write_headers(const MbBuffers& B);
 void mb_symbol_bits(const MbBuffers& B, void* scan_scratch);

@@ -64,6 +64,7 @@ struct MbBuffers {
   uint32_t* block_start[3];  // per block: index of its first symbol inside the meta-block (one extra entry = the total)
   uint32_t* hq_ctx_histo[2]; // context histograms before clustering: literal rows of 256, distance rows of 544
   uint32_t* hq_ctx_map[2];   // clustered context maps
+  uint32_t* header_prefix_bits;  // [n_mb] bits of a header in front of its serialised trees (mb_item_header_prefix)
 };
 
 static constexpr uint32_t kRowLen[3] = {256, 704, 544};
@@ -516,22 +517,19 @@ BR_DEV void mb_append_bits(BitSink& out, const uint64_t* words, uint32_t nbits) 
 }
 
 // ---- K6: header of one meta-block (store_meta_block up to the entropy codes, brotli_bit_stream.rs:2074-2191)
-// staging != nullptr: the bits are composed there (zeroed by the caller, e.g. in LDS) instead of in B.header_words
-// what the wave of k_write_headers counts in front of the header's composition and takes over behind it
+// what the wave of a header's prefix job counts in front of the composition and takes over behind it
 struct MbSplitPrepared {
   uint32_t histograms[3][258 + 26];  // per kind: block type codes, then block length codes
   BlockSplitCode code[3];
 };
-BR_DEV void mb_item_write_header(const MbBuffers& B, uint32_t m, HuffmanScratch* sc, uint64_t* staging = nullptr, MbSplitPrepared* prepared = nullptr) {
+// The header in two items.  The prefix -- meta-block header, block-split codes, distance parameters, context modes and context
+// maps -- hangs on the splitter's results alone; the serialised trees behind it on the code builder's.  So the prefix of every
+// meta-block is composed beside the code jobs (k_build_codes) and only the append waits for both (k_write_headers).
+// mb_item_header_prefix: `words` are zeroed by the caller; returns the bit position behind the context maps and leaves it in
+// header_prefix_bits[m].  Not for a stored meta-block.
+BR_DEV uint32_t mb_item_header_prefix(const MbBuffers& B, uint32_t m, HuffmanScratch* sc, uint64_t* words, MbSplitPrepared* prepared = nullptr) {
   const MbDesc d = B.descs[m];
-  MbResult& r = B.results[m];
-  if (d.uncompressed) {
-    r.header_bits = 0;
-    return;
-  }
-  uint64_t* words = staging ? staging : B.header_words + (size_t)m * B.header_stride;
-  if (!staging)
-    for (uint32_t i = 0; i < B.header_stride; ++i) words[i] = 0;
+  const MbResult& r = B.results[m];
   BitSink out;
   out.words = words;
   out.pos = 0;
@@ -576,6 +574,18 @@ BR_DEV void mb_item_write_header(const MbBuffers& B, uint32_t m, HuffmanScratch*
     br_store_trivial_context_map(r.num_histos[kSplitDistance], 2, sc, out);
   }
   BR_HEADER_PHASE(1);  // context maps
+  B.header_prefix_bits[m] = (uint32_t)out.pos;
+  return (uint32_t)out.pos;
+}
+
+// mb_item_header_trees: the serialised trees appended to `words` at bit `pos` (the words behind the prefix are zero); writes header_bits
+BR_DEV void mb_item_header_trees(const MbBuffers& B, uint32_t m, uint64_t* words, uint32_t pos) {
+  const MbDesc d = B.descs[m];
+  MbResult& r = B.results[m];
+  BitSink out;
+  out.words = words;
+  out.pos = pos;
+  BR_HEADER_PHASE_CLOCK();
   for (uint32_t kind = 0; kind < 3; ++kind) {
     for (uint32_t i = 0; i < r.num_histos[kind]; ++i) {
       const uint32_t row_index = d.histo_base[kind] + i;
@@ -584,6 +594,20 @@ BR_DEV void mb_item_write_header(const MbBuffers& B, uint32_t m, HuffmanScratch*
   }
   BR_HEADER_PHASE(2);  // the serialised trees
   r.header_bits = (uint32_t)out.pos;
+}
+
+// the two in sequence (the emulation, a stored meta-block).  staging != nullptr: the bits are composed there (zeroed by the caller)
+// instead of in B.header_words
+BR_DEV void mb_item_write_header(const MbBuffers& B, uint32_t m, HuffmanScratch* sc, uint64_t* staging = nullptr, MbSplitPrepared* prepared = nullptr) {
+  if (B.descs[m].uncompressed) {
+    B.header_prefix_bits[m] = 0;
+    B.results[m].header_bits = 0;
+    return;
+  }
+  uint64_t* words = staging ? staging : B.header_words + (size_t)m * B.header_stride;
+  if (!staging)
+    for (uint32_t i = 0; i < B.header_stride; ++i) words[i] = 0;
+  mb_item_header_trees(B, m, words, mb_item_header_prefix(B, m, sc, words, prepared));
 }
 
 BR_DEV uint32_t mb_find_by_lit(const MbBuffers& B, uint32_t i) {

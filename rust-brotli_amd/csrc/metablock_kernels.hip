@@ -1,9 +1,13 @@
 // metablock_kernels.hip -- gfx950 kernels of the meta-block stage: per-granule histograms, greedy block
 // splitting (one workgroup per splitter, strictly ordered f32 entropy sums), Huffman code construction
-// (one thread per histogram), header serialisation (one thread per meta-block) and the parallel symbol
+// (one wavefront per histogram), header serialisation (one wavefront per meta-block: the prefix beside the code jobs, the
+// serialised trees appended behind them) and the parallel symbol
 // emission (bit length per symbol -> prefix sums -> pieces ORed together per wavefront in LDS -> 64-bit atomic OR per stream
 // word).  Integer/byte work, no MFMA.
 #include <hip/hip_runtime.h>
+#include <stdlib.h>
+
+#include <exception>
 
 #include "device_api.h"
 #include "device_scan.h"
@@ -12,7 +16,7 @@
 
 namespace brotli_mi355x {
 
-size_t mb_scan_scratch_bytes(size_t n) { return scan_scratch_words(n) * 4 + 256; }
+size_t mb_scan_scratch_bytes(size_t n) { return scan_scratch_words(n) * 4 * 3 + 256; }  // (three arrays at once: exclusive_scan3_u32)
 
 template <typename F>
 __global__ __launch_bounds__(256) void k_for_each(uint32_t n, F f) {
@@ -41,16 +45,98 @@ void mb_gather_bytes(const uint8_t* text, const uint32_t* positions_dev, uint32_
   HIP_CHECK(hipGetLastError());
 }
 
+// ---- exclusive prefix sums of three uint32 arrays of one length (in place), with the tiling of exclusive_scan_u32 (device_scan.h):
+// a workgroup takes the same tile of all three, the tile sums are three arrays again.  The three command scans are one pass of
+// 5 launches at 64 MiB instead of three passes of 5.
+struct ScanTriple {
+  uint32_t* a[3];
+};
+__global__ __launch_bounds__(256) void k_scan3_tiles(ScanTriple data, uint32_t n, ScanTriple tile_sums, uint32_t want_sums) {
+  __shared__ uint32_t wave_sum[3][4];
+  const uint32_t base = blockIdx.x * kScanTile + threadIdx.x * 4;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  uint32_t v[3][4], local[3], x[3];
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[q][j] = (base + j < n) ? data.a[q][base + j] : 0;
+    local[q] = v[q][0] + v[q][1] + v[q][2] + v[q][3];
+    x[q] = local[q];
+    // inclusive scan across the wavefront
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const uint32_t y = __shfl_up(x[q], off, 64);
+      if (lane >= off) x[q] += y;
+    }
+    if (lane == 63) wave_sum[q][w] = x[q];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    uint32_t wave_off = 0;
+    for (int i = 0; i < w; ++i) wave_off += wave_sum[q][i];
+    uint32_t excl = wave_off + x[q] - local[q];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (base + j < n) data.a[q][base + j] = excl;
+      excl += v[q][j];
+    }
+    if (threadIdx.x == 255 && want_sums) tile_sums.a[q][blockIdx.x] = wave_off + x[q];
+  }
+}
+__global__ __launch_bounds__(256) void k_scan3_add(ScanTriple data, uint32_t n, ScanTriple tile_offsets) {
+  const uint32_t base = blockIdx.x * kScanTile + threadIdx.x * 4;
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    const uint32_t add = tile_offsets.a[q][blockIdx.x];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (base + j < n) data.a[q][base + j] += add;
+  }
+}
+// scratch: three times what exclusive_scan_u32 wants for n
+static void exclusive_scan3_u32(const ScanTriple& data, uint32_t n, uint32_t* scratch) {
+  if (n == 0) return;
+  const uint32_t tiles = (n + kScanTile - 1) / kScanTile;
+  const ScanTriple sums = {{scratch, scratch + tiles, scratch + 2 * (size_t)tiles}};
+  hipLaunchKernelGGL(k_scan3_tiles, dim3(tiles), dim3(256), 0, BR_STREAM, data, n, sums, tiles > 1 ? 1u : 0u);
+  if (tiles > 1) {
+    exclusive_scan3_u32(sums, tiles, scratch + 3 * (size_t)tiles);
+    hipLaunchKernelGGL(k_scan3_add, dim3(tiles), dim3(256), 0, BR_STREAM, data, n, sums);
+  }
+}
+// C-ABI test entry (tests/test_header_prefix_gpu.py): the three arrays of n words each, back to back in `host`, scanned in place
+extern "C" int brotli_mi355x_debug_scan3(uint32_t* host, uint32_t n) {
+  if (!host || n == 0 || n > (1u << 26)) return -1;
+  try {
+    DevBlocks tmp;
+    uint32_t* dev = tmp.uninit<uint32_t>(((size_t)n + 4) * 3 * 4);
+    uint32_t* scratch = tmp.uninit<uint32_t>(mb_scan_scratch_bytes(n));
+    const size_t stride = ((size_t)n + 3) & ~(size_t)3;
+    for (int q = 0; q < 3; ++q) dev_h2d(dev + q * stride, host + (size_t)q * n, (size_t)n * 4);
+    exclusive_scan3_u32(ScanTriple{{dev, dev + stride, dev + 2 * stride}}, n, scratch);
+    HIP_CHECK(hipGetLastError());
+    for (int q = 0; q < 3; ++q) dev_d2h(host + (size_t)q * n, dev + q * stride, (size_t)n * 4);
+    tmp.clear();
+    return 0;
+  } catch (const std::exception&) {
+    return -2;
+  }
+}
+
 void mb_command_scans(const MbBuffers& B, void* scan_scratch) {
   const MbBuffers b = B;
-  for_each(b.n_cmds, [b] __device__(uint32_t c) { mb_item_command_counts(b, c); });
-  // element [K] = 0 so that the exclusive scan leaves the totals there
-  dev_memset(b.cmd_lit_start + b.n_cmds, 0, 4);
-  dev_memset(b.cmd_pos + b.n_cmds, 0, 4);
-  dev_memset(b.cmd_dist_index + b.n_cmds, 0, 4);
-  exclusive_scan_u32(b.cmd_lit_start, b.n_cmds + 1, (uint32_t*)scan_scratch);
-  exclusive_scan_u32(b.cmd_pos, b.n_cmds + 1, (uint32_t*)scan_scratch);
-  exclusive_scan_u32(b.cmd_dist_index, b.n_cmds + 1, (uint32_t*)scan_scratch);
+  // (element [K] = 0 so that the exclusive scans leave the totals there)
+  for_each(b.n_cmds + 1, [b] __device__(uint32_t c) {
+    if (c < b.n_cmds) {
+      mb_item_command_counts(b, c);
+    } else {
+      b.cmd_lit_start[c] = 0;
+      b.cmd_pos[c] = 0;
+      b.cmd_dist_index[c] = 0;
+    }
+  });
+  exclusive_scan3_u32(ScanTriple{{b.cmd_lit_start, b.cmd_pos, b.cmd_dist_index}}, b.n_cmds + 1, (uint32_t*)scan_scratch);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -160,42 +246,112 @@ void mb_split_chains(const MbBuffers& B, bool wide) {
 // The Huffman construction is sequential, data-dependent control flow: 64 different histograms in the lanes of one
 // wavefront would serialise on every divergent branch.  One histogram per wavefront (lane 0 works) puts the jobs
 // on different SIMDs instead, where they really run concurrently.
-__global__ __launch_bounds__(64) void k_build_codes(MbBuffers B, const CodeJob* jobs, uint32_t n_jobs) {
-  // everything the sequential builder touches is staged in LDS (its loads/stores are dependent, so their latency is
-  // what the job costs); the 64 lanes only help with the copies
-  __shared__ HuffmanScratch sc;
-  __shared__ uint32_t h[704];
-  __shared__ uint16_t bits[704];
-  __shared__ uint8_t depth[704];
-  __shared__ uint64_t words[kTreeBitsWords];
-  __shared__ uint32_t nbits;
-  const uint32_t i = blockIdx.x;
-  if (i >= n_jobs) return;
-  const CodeJob j = jobs[i];
+// everything the sequential builder touches is staged in LDS (its loads/stores are dependent, so their latency is
+// what the job costs); the 64 lanes only help with the copies
+struct CodeJobLds {
+  HuffmanScratch sc;
+  uint32_t h[704];
+  uint16_t bits[704];
+  uint8_t depth[704];
+  uint64_t words[kTreeBitsWords];
+  uint32_t nbits;
+};
+// The prefix of a meta-block's header (everything in front of the serialised trees, mb_item_header_prefix) is a sequential bit
+// string that hangs on the splitter's results alone: one lane composes it -- in LDS, where a read-modify-write of the word under
+// the cursor costs a few cycles instead of a trip to L2 -- beside the code jobs, in workgroups of their launch.
+static constexpr uint32_t kHeaderPrefixWords = 2560;  // 20 KiB: the 160 Kibit bound for everything but the trees (a 16 Ki-entry context map)
+struct HeaderPrefixLds {
+  uint64_t window[kHeaderPrefixWords];
+  HuffmanScratch sc;  // (the scratch of the small trees -- block-split codes, context map)
+  MbSplitPrepared prep;
+  uint32_t bits;
+};
+union BuildCodesLds {
+  CodeJobLds code;
+  HeaderPrefixLds prefix;
+};
+
+__device__ __forceinline__ void mb_code_job(const MbBuffers& B, const CodeJob& j, CodeJobLds& S) {
   const uint32_t row = kRowLen[j.kind];
   uint32_t* gh = B.histo[j.kind] + (size_t)j.row_index * row;
-  for (uint32_t k = threadIdx.x; k < row; k += 64) h[k] = gh[k];
+  for (uint32_t k = threadIdx.x; k < row; k += 64) S.h[k] = gh[k];
   __syncthreads();
   {
-    const uint32_t nb = mb_build_code_core(j.kind, j.num_distance_symbols, h, depth, bits, words, &sc, true, j.mode);
-    if (threadIdx.x == 0) nbits = nb;
+    const uint32_t nb = mb_build_code_core(j.kind, j.num_distance_symbols, S.h, S.depth, S.bits, S.words, &S.sc, true, j.mode);
+    if (threadIdx.x == 0) S.nbits = nb;
   }
   __syncthreads();
   uint8_t* gd = B.depth[j.kind] + (size_t)j.row_index * row;
   uint16_t* gb = B.bits[j.kind] + (size_t)j.row_index * row;
   uint64_t* gw = B.tree_bits[j.kind] + (size_t)j.row_index * kTreeBitsWords;
   for (uint32_t k = threadIdx.x; k < row; k += 64) {
-    gh[k] = h[k];
-    gd[k] = depth[k];
-    gb[k] = bits[k];
+    gh[k] = S.h[k];
+    gd[k] = S.depth[k];
+    gb[k] = S.bits[k];
   }
-  for (uint32_t k = threadIdx.x; k < kTreeBitsWords; k += 64) gw[k] = words[k];
-  if (threadIdx.x == 0) B.tree_nbits[j.kind][j.row_index] = nbits;
+  for (uint32_t k = threadIdx.x; k < kTreeBitsWords; k += 64) gw[k] = S.words[k];
+  if (threadIdx.x == 0) B.tree_nbits[j.kind][j.row_index] = S.nbits;
+}
+
+// The block-split codes (BuildAndStoreBlockSplitCode) walk all blocks of a kind twice -- the histograms of the type and length
+// codes, then the switch command of every block: a block per lane in front of and behind the one lane that composes the prefix
+// (a meta-block of a mix has thousands of blocks: 4.8 ms of a 256 MiB Silesia-like call were this walk in one lane).
+__device__ __forceinline__ void mb_header_prefix_job(const MbBuffers& B, uint32_t m, HeaderPrefixLds& S) {
+  const MbDesc d = B.descs[m];
+  if (d.uncompressed) {  // (the whole workgroup)
+    if (threadIdx.x == 0) B.header_prefix_bits[m] = 0;
+    return;
+  }
+  for (uint32_t i = threadIdx.x; i < kHeaderPrefixWords; i += 64) S.window[i] = 0;
+  for (uint32_t i = threadIdx.x; i < 3 * (258 + 26); i += 64) (&S.prep.histograms[0][0])[i] = 0;
+  __syncthreads();
+  for (uint32_t kind = 0; kind < 3; ++kind) {
+    const uint8_t* types = B.block_types[kind] + d.block_base[kind];
+    const uint32_t* lengths = B.block_lengths[kind] + d.block_base[kind];
+    const uint32_t nb = B.results[m].num_blocks[kind];
+    for (uint32_t i = threadIdx.x; i < nb; i += 64) {
+      if (i != 0) atomicAdd(&S.prep.histograms[kind][br_block_type_code_at(types, i)], 1u);
+      atomicAdd(&S.prep.histograms[kind][258 + br_block_length_prefix_code(lengths[i])], 1u);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) S.bits = mb_item_header_prefix(B, m, &S.sc, S.window, &S.prep);
+  __syncthreads();
+  for (uint32_t kind = 0; kind < 3; ++kind) {
+    if (B.results[m].num_types[kind] <= 1) continue;
+    const uint8_t* types = B.block_types[kind] + d.block_base[kind];
+    const uint32_t* lengths = B.block_lengths[kind] + d.block_base[kind];
+    uint64_t* switch_bits = B.switch_bits[kind] + d.block_base[kind];
+    uint8_t* switch_nbits = B.switch_nbits[kind] + d.block_base[kind];
+    const uint32_t nb = B.results[m].num_blocks[kind];
+    for (uint32_t i = 1 + threadIdx.x; i < nb; i += 64) {
+      uint32_t nbits;
+      switch_bits[i] = br_block_switch_bits(S.prep.code[kind], br_block_type_code_at(types, i), lengths[i], false, &nbits);
+      switch_nbits[i] = (uint8_t)nbits;
+    }
+  }
+  uint64_t* global_words = B.header_words + (size_t)m * B.header_stride;
+  const uint32_t words = (S.bits + 63) / 64;
+  for (uint32_t i = threadIdx.x; i < words && i < kHeaderPrefixWords; i += 64) global_words[i] = S.window[i];
+}
+
+// workgroups [0, n_jobs): a code job each; the workgroups behind them: the header prefix of meta-block blockIdx.x - n_jobs.
+// (The branches are workgroup-uniform, so is every return: no barrier is reached by a part of a workgroup.)
+__global__ __launch_bounds__(64) void k_build_codes(MbBuffers B, const CodeJob* jobs, uint32_t n_jobs) {
+  __shared__ BuildCodesLds S;
+  const uint32_t i = blockIdx.x;
+  if (i >= n_jobs) {
+    if (i - n_jobs < B.n_mb) mb_header_prefix_job(B, i - n_jobs, S.prefix);
+    return;
+  }
+  const CodeJob j = jobs[i];
+  if (j.mb_plus_1 != 0 && j.slot >= B.results[j.mb_plus_1 - 1].num_histos[j.kind]) return;  // a pool slot the splitter left empty
+  mb_code_job(B, j, S.code);
 }
 
 void mb_build_codes(const MbBuffers& B, const CodeJob* jobs_dev, uint32_t n_jobs) {
-  if (n_jobs == 0) return;
-  hipLaunchKernelGGL(k_build_codes, dim3(n_jobs), dim3(64), 0, BR_STREAM, B, jobs_dev, n_jobs);
+  if (n_jobs + B.n_mb == 0) return;
+  hipLaunchKernelGGL(k_build_codes, dim3(n_jobs + B.n_mb), dim3(64), 0, BR_STREAM, B, jobs_dev, n_jobs);
   HIP_CHECK(hipGetLastError());
 #if defined(BR_CODES_PROFILE)
   {
@@ -211,76 +367,61 @@ void mb_build_codes(const MbBuffers& B, const CodeJob* jobs_dev, uint32_t n_jobs
 #endif
 }
 
-// The header of a meta-block is a sequential bit string (block-split codes, context map, then the serialised trees that
-// k_build_codes prepared): one lane composes it -- in LDS, where a read-modify-write of the word under the cursor costs
-// a few cycles instead of a trip to L2 -- and the wave copies the finished words out.  Headers that might not fit the
-// LDS buffer (hundreds of literal histograms) are composed in global memory as before.
-__global__ __launch_bounds__(64) void k_write_headers(MbBuffers B) {
-  constexpr uint32_t kLdsWords = 5120;            // 40 KiB
-  constexpr uint64_t kOtherBits = 160u * 1024u;   // generous bound for everything but the trees (a 16 Ki-entry context map)
+// Behind the code jobs and the header prefixes: the serialised trees appended to every prefix.  One lane appends -- in LDS,
+// as the prefix was composed -- and the wave brings the prefix in and the finished words out.  Headers that do not fit the
+// LDS buffer (hundreds of literal histograms) are finished in global memory.
+// lds_bits: the longest header (prefix + trees) that is staged in LDS, at most the buffer's kHeaderLdsWords * 64
+static constexpr uint32_t kHeaderLdsWords = 5120;  // 40 KiB
+__global__ __launch_bounds__(64) void k_write_headers(MbBuffers B, uint32_t lds_bits) {
+  constexpr uint32_t kLdsWords = kHeaderLdsWords;
   __shared__ uint64_t lw[kLdsWords];
-  __shared__ HuffmanScratch sc_lds;  // (the scratch of the small trees -- block-split codes, context map -- as well)
-  __shared__ MbSplitPrepared prep;
   __shared__ uint32_t s_bits;
   const uint32_t m = blockIdx.x;
   if (m >= B.n_mb) return;
   const MbDesc d = B.descs[m];
-  uint64_t* global_words = B.header_words + (size_t)m * B.header_stride;
   if (d.uncompressed) {
-    if (threadIdx.x == 0) mb_item_write_header(B, m, B.huff_scratch + m, global_words);
+    if (threadIdx.x == 0) B.results[m].header_bits = 0;
     return;
   }
+  uint64_t* global_words = B.header_words + (size_t)m * B.header_stride;
   uint32_t trees = 0;
   for (uint32_t kind = 0; kind < 3; ++kind)
     for (uint32_t i = threadIdx.x; i < B.results[m].num_histos[kind]; i += 64) trees += B.tree_nbits[kind][d.histo_base[kind] + i];
   for (int off = 32; off > 0; off >>= 1) trees += __shfl_down(trees, off, 64);
   trees = (uint32_t)__shfl((int)trees, 0, 64);
-  const bool in_lds = (uint64_t)trees + kOtherBits <= (uint64_t)kLdsWords * 64;
+  const uint32_t prefix_bits = B.header_prefix_bits[m];
+  const uint64_t all_bits = (uint64_t)prefix_bits + trees;
+  const bool in_lds = all_bits <= (uint64_t)lds_bits;
+  // the words the header ends in (and one behind them, which the bit writer may OR a zero into), inside the staging
+  const uint32_t limit = in_lds ? kLdsWords : B.header_stride;
+  const uint32_t all_words = all_bits / 64 + 2 < limit ? (uint32_t)(all_bits / 64 + 2) : limit;
+  const uint32_t prefix_words = (prefix_bits + 63) / 64;
   uint64_t* stage = in_lds ? lw : global_words;
-  const uint32_t clear_words = in_lds ? kLdsWords : B.header_stride;
-  for (uint32_t i = threadIdx.x; i < clear_words; i += 64) stage[i] = 0;
-  // The block-split codes (BuildAndStoreBlockSplitCode) walk all blocks of a kind twice -- the histograms of the type and length
-  // codes, then the switch command of every block: a block per lane in front of and behind the one lane that composes the header
-  // (a meta-block of a mix has thousands of blocks: 4.8 ms of a 256 MiB Silesia-like call were this kernel).
-  for (uint32_t i = threadIdx.x; i < 3 * (258 + 26); i += 64) (&prep.histograms[0][0])[i] = 0;
-  __syncthreads();
-  for (uint32_t kind = 0; kind < 3; ++kind) {
-    const uint8_t* types = B.block_types[kind] + d.block_base[kind];
-    const uint32_t* lengths = B.block_lengths[kind] + d.block_base[kind];
-    const uint32_t nb = B.results[m].num_blocks[kind];
-    for (uint32_t i = threadIdx.x; i < nb; i += 64) {
-      if (i != 0) atomicAdd(&prep.histograms[kind][br_block_type_code_at(types, i)], 1u);
-      atomicAdd(&prep.histograms[kind][258 + br_block_length_prefix_code(lengths[i])], 1u);
-    }
-  }
+  if (in_lds)
+    for (uint32_t i = threadIdx.x; i < prefix_words; i += 64) lw[i] = global_words[i];
+  for (uint32_t i = prefix_words + threadIdx.x; i < all_words; i += 64) stage[i] = 0;
   __syncthreads();
   if (threadIdx.x == 0) {
-    mb_item_write_header(B, m, &sc_lds, stage, &prep);
+    mb_item_header_trees(B, m, stage, prefix_bits);
     s_bits = B.results[m].header_bits;
   }
   __syncthreads();
-  for (uint32_t kind = 0; kind < 3; ++kind) {
-    if (B.results[m].num_types[kind] <= 1) continue;
-    const uint8_t* types = B.block_types[kind] + d.block_base[kind];
-    const uint32_t* lengths = B.block_lengths[kind] + d.block_base[kind];
-    uint64_t* switch_bits = B.switch_bits[kind] + d.block_base[kind];
-    uint8_t* switch_nbits = B.switch_nbits[kind] + d.block_base[kind];
-    const uint32_t nb = B.results[m].num_blocks[kind];
-    for (uint32_t i = 1 + threadIdx.x; i < nb; i += 64) {
-      uint32_t nbits;
-      switch_bits[i] = br_block_switch_bits(prep.code[kind], br_block_type_code_at(types, i), lengths[i], false, &nbits);
-      switch_nbits[i] = (uint8_t)nbits;
-    }
-  }
   if (in_lds) {
-    const uint32_t words = (s_bits + 63) / 64 + 1;
-    for (uint32_t i = threadIdx.x; i < words && i < kLdsWords; i += 64) global_words[i] = lw[i];
+    const uint32_t words = (s_bits + 63) / 64;
+    for (uint32_t i = prefix_bits / 64 + threadIdx.x; i < words && i < kLdsWords; i += 64) global_words[i] = lw[i];
   }
 }
 
 void mb_write_headers(const MbBuffers& B) {
   if (B.n_mb == 0) return;
-  hipLaunchKernelGGL(k_write_headers, dim3(B.n_mb), dim3(64), 0, BR_STREAM, B);
+  // BROTLI_MI355X_TEST_HEADER_LDS_BITS (tests): a lower line between the two stagings -- a header past the buffer's 327 680 bits
+  // takes hundreds of prefix codes of every kind, more than a quick test can bring about
+  static const uint32_t lds_bits = [] {
+    const char* e = getenv("BROTLI_MI355X_TEST_HEADER_LDS_BITS");
+    const unsigned long v = e ? strtoul(e, nullptr, 10) : kHeaderLdsWords * 64ul;
+    return (uint32_t)(v < kHeaderLdsWords * 64ul ? v : kHeaderLdsWords * 64ul);
+  }();
+  hipLaunchKernelGGL(k_write_headers, dim3(B.n_mb), dim3(64), 0, BR_STREAM, B, lds_bits);
   HIP_CHECK(hipGetLastError());
 #if defined(BR_CODES_PROFILE)
   {
