@@ -1011,25 +1011,62 @@ BROTLI_BOOL BrotliMi355xCompressDevice(int quality, int lgwin, BrotliEncoderMode
   return CompressOneShot(quality, lgwin, mode, input_size, input_device, true, encoded_size, encoded_host, stats);
 }
 
-// what BrotliMi355xLastBatchInfo reports: the last BrotliMi355xCompressBatch call of this thread
+// what BrotliMi355xLastBatchInfo reports: the last batch call of this thread
 static thread_local uint64_t g_batch_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
-// BrotliMi355xCompressBatch (routes == 0), BrotliMi355xCompressBatchEx and, with on_device, BrotliMi355xCompressBatchDevice: there
-// inputs[i] and outputs[i] are device addresses -- the side-by-side routes take the items from device memory and leave the streams
-// there (BatchDeviceSink), every other answer goes down with a small copy, and one dev_sync() ends the call.
-static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t count,
-                             const uint8_t* const* inputs, const size_t* input_sizes, uint8_t* const* outputs, size_t* output_sizes,
-                             int32_t* item_results, bool on_device = false) {
+using BatchStreams = std::vector<std::vector<uint8_t>>;
+using BatchFlags = std::vector<uint8_t>;
+
+// The items a batch call sends through one side-by-side route: their places in the caller's arrays, their inputs and their sizes
+struct BatchItems {
+  std::vector<size_t> item;
+  std::vector<const uint8_t*> in;
+  std::vector<size_t> size;
+  // behind a dictionary per item: each item's dictionary bytes in use (filled by the caller, empty otherwise)
+  std::vector<const uint8_t*> dict;
+  std::vector<size_t> dict_size;
+  // on_device: their buffers, and what the route's groups answered (BatchDeviceSink)
+  std::vector<uint8_t*> out;
+  std::vector<size_t> cap, out_size;
+  std::vector<int32_t> result;
+  BatchDeviceSink sink{nullptr, nullptr, nullptr, nullptr};
+  void Add(size_t i, const uint8_t* input, size_t input_size, uint8_t* output, size_t capacity, bool on_device) {
+    item.push_back(i);
+    in.push_back(input);
+    size.push_back(input_size);
+    if (on_device) {
+      out.push_back(output);
+      cap.push_back(capacity);
+    }
+  }
+  // rule: what the call owes its caller -- DeliveryRule for the plain call, StreamDeliveryRule behind a dictionary
+  const BatchDeviceSink* Sink(bool on_device, Delivery (*rule)(size_t, size_t, size_t)) {
+    if (!on_device) return nullptr;
+    out_size.assign(item.size(), 0);
+    result.assign(item.size(), 0);
+    sink = BatchDeviceSink{out.data(), cap.data(), out_size.data(), result.data(), rule};
+    return &sink;
+  }
+};
+
+// The frame of every batch call.  `refused` not empty: the call fails as a whole before any work is done, like a device error -- a
+// caller can probe for later routes that way --, and that is looked at before count == 0.  Otherwise body(params, info, results)
+// takes the items: it leaves results[i] and output_sizes[i] and counts into info (BrotliMi355xLastBatchInfo; info[0] is set),
+// which is published only where nothing throws.  A std::exception out of the body fails the call as a whole.  on_device: one
+// dev_sync() ends the call, so that everything it wrote has landed -- also what the groups in front of an error queued for the
+// caller's buffers.  large_window: kParamLargeWindow is set (the plain call at lgwin > 24; the dictionary calls do not).
+using BatchBody = std::function<void(const EncoderParams& params, uint64_t* info, std::vector<int32_t>& results)>;
+static int32_t RunBatchCall(const char* entry, int quality, int lgwin, BrotliEncoderMode mode, bool large_window, size_t count, const size_t* input_sizes,
+                            size_t* output_sizes, int32_t* item_results, bool on_device, const std::string& refused, const BatchBody& body) {
   uint64_t info[8] = {count, 0, 0, 0, 0, 0, 0, 0};
   memcpy(g_batch_info, info, sizeof(info));
-  if ((routes & ~(uint32_t)(BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS | BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS | BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS |
-                            BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS | BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS)) != 0) {
-    // a route this build does not know fails the call as a whole, like a device error: a caller can probe for later routes
-    SetError(entry, ("routes " + std::to_string(routes) + " names a route this build does not know (known: BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS = 1, "
-                     "BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS = 4, BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS = 16, BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS = 32, "
-                     "BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS = 128; the values 2, 8 and 64 are reserved)").c_str());
+  const auto fails = [&](const char* what) {
+    SetError(entry, what);
     for (size_t i = 0; i < count; ++i) output_sizes[i] = 0;
     if (item_results && count) memset(item_results, 0, count * sizeof(int32_t));
+  };
+  if (!refused.empty()) {
+    fails(refused.c_str());
     return 0;
   }
   if (count == 0) return 1;
@@ -1041,37 +1078,96 @@ static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEn
     SetParameter(&params, kParamQuality, (uint32_t)quality);
     SetParameter(&params, kParamLgwin, (uint32_t)lgwin);
     SetParameter(&params, kParamMode, (uint32_t)mode);
-    if (lgwin > 24) SetParameter(&params, kParamLargeWindow, 1);
+    if (large_window) SetParameter(&params, kParamLargeWindow, 1);
     SmallCallGate gate(total);
-    const bool fragments = IsFragmentStream(params);
-    // The items an encoder sees and that go side by side on the device: every item of qualities 0 and 1 (fragment_stream.h), the
-    // items of one input block under an H5 hasher at qualities 5 .. 8 (batch_greedy.h) and, where the caller asked for that route,
-    // those of two to four blocks, or those of one input block under a BasicHasher at qualities 2 .. 4, or those of two to four
-    // blocks at these qualities (batch_quick.h), or those of at most 65 536 bytes at quality 11 (batch_zopfli.h), or those of
-    // one input block under the H9 hasher at qualities 9 and 10 (batch_greedy.h: BatchQ9Compress).  Every other item goes through the one-shot path by itself, on this thread, in the caller's order (the same bytes, no gain in speed).
-    struct Routed {  // the items of one route: their places in the caller's arrays, their inputs and their sizes
-      std::vector<size_t> item;
-      std::vector<const uint8_t*> in;
-      std::vector<size_t> size;
-      // on_device: their buffers, and what the route's groups answered (BatchDeviceSink)
-      std::vector<uint8_t*> out;
-      std::vector<size_t> cap, out_size;
-      std::vector<int32_t> result;
-      BatchDeviceSink sink{nullptr, nullptr, nullptr, nullptr};
-      const BatchDeviceSink* Sink(bool on_device) {
-        if (!on_device) return nullptr;
-        out_size.assign(item.size(), 0);
-        result.assign(item.size(), 0);
-        sink = BatchDeviceSink{out.data(), cap.data(), out_size.data(), result.data()};
-        return &sink;
+    body(params, info, results);
+    if (on_device) dev_sync();
+  } catch (const std::exception& e) {
+    fails(e.what());
+    if (on_device) {
+      try {
+        dev_sync();
+      } catch (const std::exception&) {
       }
-    };
-    Routed plain, long_items, quick_items, quick_long_items, zopfli_items, q9_items;
-    const bool long_route = (routes & BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS) != 0;
-    const bool quick_route = (routes & BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS) != 0;
-    const bool quick_long_route = (routes & BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS) != 0;
-    const bool zopfli_route = (routes & BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS) != 0;
-    const bool q9_route = (routes & BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS) != 0;
+    }
+    return 0;
+  }
+  memcpy(g_batch_info, info, sizeof(info));
+  int32_t all = 1;
+  for (size_t i = 0; i < count; ++i) {
+    if (item_results) item_results[i] = results[i];
+    if (!results[i]) all = 0;
+  }
+  return all;
+}
+
+// The side-by-side routes of BrotliMi355xCompressBatch, in the order in which an item is offered to them: the first route that is
+// asked for and takes the item gets it; an item that none takes goes through the one-shot path by itself, on the calling thread,
+// in the caller's order (the same bytes, no gain in speed).  A new route is one line here and its Batch*Compress.
+struct BatchRoute {
+  uint32_t bit;  // BROTLI_MI355X_BATCH_ROUTE_*; 0: taken without being asked for
+  bool (*eligible)(const EncoderParams& params, size_t input_size);
+  // the route's Batch*Compress, handed what it has of: (*demoted)[k] != 0, the item is to be redone one by one;
+  // (*reference_fails)[k] != 0, the reference encoder fails on it
+  void (*run)(const EncoderParams& params, const BatchItems& r, BatchStreams* streams, BatchFlags* demoted, BatchFlags* reference_fails, uint32_t* groups,
+              const BatchDeviceSink* sink);
+  bool long_items;  // its items are longer than one input block: those delivered count into info[7] as well
+};
+static const BatchRoute kBatchRoutes[] = {
+    // one input block under an H5 hasher at qualities 5 .. 8 (batch_greedy.h)
+    {0, BatchGreedyEligible,
+     [](const EncoderParams& p, const BatchItems& r, BatchStreams* s, BatchFlags*, BatchFlags*, uint32_t* g, const BatchDeviceSink* sink) {
+       BatchGreedyCompress(p, r.item.size(), r.in.data(), r.size.data(), s, g, sink);
+     }, false},
+    // two to four blocks at these qualities, one chain each
+    {BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS, BatchLongEligible,
+     [](const EncoderParams& p, const BatchItems& r, BatchStreams* s, BatchFlags* demoted, BatchFlags*, uint32_t* g, const BatchDeviceSink* sink) {
+       BatchLongCompress(p, r.item.size(), r.in.data(), r.size.data(), s, demoted, g, sink);
+     }, true},
+    // one input block under a BasicHasher at qualities 2 .. 4 (batch_quick.h)
+    {BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS, BatchQuickEligible,
+     [](const EncoderParams& p, const BatchItems& r, BatchStreams* s, BatchFlags*, BatchFlags*, uint32_t* g, const BatchDeviceSink* sink) {
+       BatchQuickCompress(p, r.item.size(), r.in.data(), r.size.data(), s, g, sink);
+     }, false},
+    // two to four blocks at these qualities, one chain each
+    {BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS, BatchQuickLongEligible,
+     [](const EncoderParams& p, const BatchItems& r, BatchStreams* s, BatchFlags* demoted, BatchFlags*, uint32_t* g, const BatchDeviceSink* sink) {
+       BatchQuickLongCompress(p, r.item.size(), r.in.data(), r.size.data(), s, demoted, g, sink);
+     }, true},
+    // at most 65 536 bytes at quality 11, one sequential Zopfli walk each (batch_zopfli.h)
+    {BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS, BatchZopfliEligible,
+     [](const EncoderParams& p, const BatchItems& r, BatchStreams* s, BatchFlags*, BatchFlags* reference_fails, uint32_t* g, const BatchDeviceSink* sink) {
+       BatchZopfliCompress(p, r.item.size(), r.in.data(), r.size.data(), s, reference_fails, g, sink);
+     }, false},
+    // one input block under the H9 hasher at qualities 9 and 10, one chain each (batch_greedy.h: BatchQ9Compress)
+    {BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS, BatchQ9Eligible,
+     [](const EncoderParams& p, const BatchItems& r, BatchStreams* s, BatchFlags*, BatchFlags*, uint32_t* g, const BatchDeviceSink* sink) {
+       BatchQ9Compress(p, r.item.size(), r.in.data(), r.size.data(), s, g, sink);
+     }, false},
+};
+static const size_t kNumBatchRoutes = sizeof(kBatchRoutes) / sizeof(kBatchRoutes[0]);
+// ... and the order in which the routes run, each in groups of its own: quick, zopfli, q9, quick-long, long, plain.  (Both orders
+// show: an item goes to the first route that takes it, the last failing item's text stays in the last error.)
+static const size_t kBatchRunOrder[kNumBatchRoutes] = {2, 4, 5, 3, 1, 0};
+
+// BrotliMi355xCompressBatch (routes == 0), BrotliMi355xCompressBatchEx and, with on_device, BrotliMi355xCompressBatchDevice: there
+// inputs[i] and outputs[i] are device addresses -- the side-by-side routes take the items from device memory and leave the streams
+// there (BatchDeviceSink), every other answer goes down with a small copy, and the frame's dev_sync() ends the call.  Every item of
+// qualities 0 and 1 goes side by side through the fragment path (fragment_stream.h), which is no route: it takes the place of the
+// plain one.
+static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t count,
+                             const uint8_t* const* inputs, const size_t* input_sizes, uint8_t* const* outputs, size_t* output_sizes,
+                             int32_t* item_results, bool on_device = false) {
+  uint32_t known = 0;
+  for (const BatchRoute& route : kBatchRoutes) known |= route.bit;
+  std::string refused;
+  if ((routes & ~known) != 0) {
+    refused = "routes " + std::to_string(routes) + " names a route this build does not know (known: BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS = 1, "
+              "BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS = 4, BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS = 16, BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS = 32, "
+              "BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS = 128; the values 2, 8 and 64 are reserved)";
+  }
+  const auto body = [&](const EncoderParams& params, uint64_t* info, std::vector<int32_t>& results) {
+    const bool fragments = IsFragmentStream(params);
     auto one_by_one = [&](size_t i) {
       std::string error;
       if (on_device) {
@@ -1098,21 +1194,20 @@ static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEn
       if (!results[i]) output_sizes[i] = 0;
       ++info[2];
     };
-    // hands the streams of a route out, in the caller's order.  demoted != nullptr, (*demoted)[k] != 0: a meta-block that is not the
-    // item's last took the size fallback, which its chain could not know: redone one by one.  reference_fails != nullptr,
-    // (*reference_fails)[k] != 0: the reference encoder panics on the item, which fails alone, like the bad_commands items of the
-    // dictionary routes.  Returns the items answered from the route's streams (all but the demoted ones).
-    auto deliver = [&](const Routed& r, const std::vector<std::vector<uint8_t>>& streams, const std::vector<uint8_t>* demoted,
-                       const std::vector<uint8_t>* reference_fails = nullptr) {
+    // hands the streams of a route out, in the caller's order.  `demoted` and `reference_fails` are empty where the route has no
+    // such items.  demoted[k] != 0: a meta-block that is not the item's last took the size fallback, which its chain could not
+    // know: redone one by one.  reference_fails[k] != 0: the reference encoder panics on the item, which fails alone, like the
+    // bad_commands items of the dictionary routes.  Returns the items answered from the route's streams (all but the demoted ones).
+    auto deliver = [&](const BatchItems& r, const BatchStreams& streams, const BatchFlags& demoted, const BatchFlags& reference_fails) {
       size_t delivered = 0;
       for (size_t k = 0; k < r.item.size(); ++k) {
         const size_t i = r.item[k];
-        if (demoted && (*demoted)[k]) {
+        if (!demoted.empty() && demoted[k]) {
           one_by_one(i);
           ++info[6];
           continue;
         }
-        if (reference_fails && (*reference_fails)[k]) {
+        if (!reference_fails.empty() && reference_fails[k]) {
           SetError(entry, ("item " + std::to_string(i) + ": the reference encoder fails on this input: its quality 11 parse indexes past the end of "
                            "an array there (hq.rs:1073-1160, 1310-1340)").c_str());
           results[i] = 0;
@@ -1130,6 +1225,8 @@ static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEn
       }
       return delivered;
     };
+    BatchItems list[kNumBatchRoutes];
+    BatchItems& plain = list[0];
     for (size_t i = 0; i < count; ++i) {
       uint8_t first_byte = 0;  // (on_device: the one byte OneShotWithoutEncoder may write goes down with a copy)
       const int early = OneShotWithoutEncoder(input_sizes[i], &output_sizes[i], on_device ? &first_byte : outputs[i]);
@@ -1140,70 +1237,21 @@ static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEn
         ++info[3];
         continue;
       }
-      Routed* r = nullptr;
-      if (fragments || BatchGreedyEligible(params, input_sizes[i])) r = &plain;
-      else if (long_route && BatchLongEligible(params, input_sizes[i])) r = &long_items;
-      else if (quick_route && BatchQuickEligible(params, input_sizes[i])) r = &quick_items;
-      else if (quick_long_route && BatchQuickLongEligible(params, input_sizes[i])) r = &quick_long_items;
-      else if (zopfli_route && BatchZopfliEligible(params, input_sizes[i])) r = &zopfli_items;
-      else if (q9_route && BatchQ9Eligible(params, input_sizes[i])) r = &q9_items;
-      if (!r) {
+      size_t r = 0;  // (qualities 0 and 1: every item, in the plain route's place)
+      if (!fragments) {
+        const auto takes = [&](const BatchRoute& route) { return (route.bit == 0 || (routes & route.bit) != 0) && route.eligible(params, input_sizes[i]); };
+        r = std::find_if(kBatchRoutes, kBatchRoutes + kNumBatchRoutes, takes) - kBatchRoutes;
+      }
+      if (r == kNumBatchRoutes) {
         one_by_one(i);
         continue;
       }
-      r->item.push_back(i);
-      r->in.push_back(inputs[i]);
-      r->size.push_back(input_sizes[i]);
+      list[r].Add(i, inputs[i], input_sizes[i], outputs[i], output_sizes[i], on_device);
+    }
+    BatchStreams streams;
+    BatchFlags demoted, reference_fails;
+    if (fragments && !plain.item.empty()) {
       if (on_device) {
-        r->out.push_back(outputs[i]);
-        r->cap.push_back(output_sizes[i]);
-      }
-    }
-    std::vector<std::vector<uint8_t>> streams;
-    std::vector<uint8_t> demoted;
-    uint32_t groups = 0;
-    // ---- the items of one block at qualities 2 .. 4, one chain each, in groups of their own (BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS)
-    if (!quick_items.item.empty()) {
-      BatchQuickCompress(params, quick_items.item.size(), quick_items.in.data(), quick_items.size.data(), &streams, &groups, quick_items.Sink(on_device));
-      info[4] += groups;
-      info[1] += deliver(quick_items, streams, nullptr);
-    }
-    // ---- the items of at most 65 536 bytes at quality 11, one sequential Zopfli walk each, in groups of their own
-    // (BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS)
-    if (!zopfli_items.item.empty()) {
-      std::vector<uint8_t> reference_fails;
-      BatchZopfliCompress(params, zopfli_items.item.size(), zopfli_items.in.data(), zopfli_items.size.data(), &streams, &reference_fails, &groups,
-                          zopfli_items.Sink(on_device));
-      info[4] += groups;
-      info[1] += deliver(zopfli_items, streams, nullptr, &reference_fails);
-    }
-    // ---- the items of one block at qualities 9 and 10, one chain each on an H9 table, in groups of their own
-    // (BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS)
-    if (!q9_items.item.empty()) {
-      BatchQ9Compress(params, q9_items.item.size(), q9_items.in.data(), q9_items.size.data(), &streams, &groups, q9_items.Sink(on_device));
-      info[4] += groups;
-      info[1] += deliver(q9_items, streams, nullptr);
-    }
-    // ---- the items of two to four blocks at qualities 2 .. 4, one chain each, in groups of their own
-    // (BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS)
-    if (!quick_long_items.item.empty()) {
-      BatchQuickLongCompress(params, quick_long_items.item.size(), quick_long_items.in.data(), quick_long_items.size.data(), &streams, &demoted, &groups,
-                             quick_long_items.Sink(on_device));
-      info[4] += groups;
-      const size_t delivered = deliver(quick_long_items, streams, &demoted);
-      info[1] += delivered;
-      info[7] += delivered;
-    }
-    // ---- the items of several blocks, one chain each, in groups of their own (BROTLI_MI355X_BATCH_ROUTE_LONG_ITEMS)
-    if (!long_items.item.empty()) {
-      BatchLongCompress(params, long_items.item.size(), long_items.in.data(), long_items.size.data(), &streams, &demoted, &groups, long_items.Sink(on_device));
-      info[4] += groups;
-      const size_t delivered = deliver(long_items, streams, &demoted);
-      info[1] += delivered;
-      info[7] += delivered;
-    }
-    if (!plain.item.empty()) {
-      if (fragments && on_device) {
         // Qualities 0 and 1: the fragment path takes its input from host memory.  The items come down once, go through it
         // unchanged, and their streams go up: the same bytes and the same info, no gain over the host call.
         size_t bytes = 0;
@@ -1242,37 +1290,26 @@ static int32_t CompressBatch(const char* entry, int quality, int lgwin, BrotliEn
         }
         info[1] += plain.item.size();
       } else {
-        if (fragments) {
-          FragmentBatchCompress(params, plain.item.size(), plain.in.data(), plain.size.data(), &streams);
-          info[4] = 1;
-        } else {
-          BatchGreedyCompress(params, plain.item.size(), plain.in.data(), plain.size.data(), &streams, &groups, plain.Sink(on_device));
-          info[4] += groups;
-        }
-        info[1] += deliver(plain, streams, nullptr);
+        FragmentBatchCompress(params, plain.item.size(), plain.in.data(), plain.size.data(), &streams);
+        info[4] = 1;
+        info[1] += deliver(plain, streams, demoted, reference_fails);
       }
     }
-    if (on_device) dev_sync();  // everything the call wrote has landed
-  } catch (const std::exception& e) {
-    // a device error fails the call as a whole
-    SetError(entry, e.what());
-    for (size_t i = 0; i < count; ++i) output_sizes[i] = 0;
-    if (item_results) memset(item_results, 0, count * sizeof(int32_t));
-    if (on_device) {  // (what the groups in front of the error queued for the caller's buffers has landed when the call returns)
-      try {
-        dev_sync();
-      } catch (const std::exception&) {
-      }
+    for (size_t n = 0; n < kNumBatchRoutes; ++n) {
+      BatchItems& r = list[kBatchRunOrder[n]];
+      if (fragments || r.item.empty()) continue;  // (the fragment path has answered every item of qualities 0 and 1)
+      const BatchRoute& route = kBatchRoutes[kBatchRunOrder[n]];
+      uint32_t groups = 0;
+      demoted.clear();
+      reference_fails.clear();
+      route.run(params, r, &streams, &demoted, &reference_fails, &groups, r.Sink(on_device, DeliveryRule));
+      info[4] += groups;
+      const size_t delivered = deliver(r, streams, demoted, reference_fails);
+      info[1] += delivered;
+      if (route.long_items) info[7] += delivered;
     }
-    return 0;
-  }
-  memcpy(g_batch_info, info, sizeof(info));
-  int32_t all = 1;
-  for (size_t i = 0; i < count; ++i) {
-    if (item_results) item_results[i] = results[i];
-    if (!results[i]) all = 0;
-  }
-  return all;
+  };
+  return RunBatchCall(entry, quality, lgwin, mode, lgwin > 24, count, input_sizes, output_sizes, item_results, on_device, refused, std::ref(body));
 }
 
 int32_t BrotliMi355xCompressBatch(int quality, int lgwin, BrotliEncoderMode mode, size_t count, const uint8_t* const* inputs,
@@ -1325,24 +1362,6 @@ static int CompressItemWithDictionary(int quality, int lgwin, BrotliEncoderMode 
   return 1;
 }
 
-// The items of a dictionary route in the device mode: their buffers, and what the route's groups answered by StreamDeliveryRule
-struct DictionarySink {
-  std::vector<uint8_t*> out;
-  std::vector<size_t> cap, out_size;
-  std::vector<int32_t> result;
-  BatchDeviceSink sink{nullptr, nullptr, nullptr, nullptr};
-  void Add(uint8_t* output, size_t capacity) {
-    out.push_back(output);
-    cap.push_back(capacity);
-  }
-  const BatchDeviceSink* Sink(bool on_device) {
-    if (!on_device) return nullptr;
-    out_size.assign(out.size(), 0);
-    result.assign(out.size(), 0);
-    sink = BatchDeviceSink{out.data(), cap.data(), out_size.data(), result.data(), StreamDeliveryRule};
-    return &sink;
-  }
-};
 // `bytes` bytes at a device address, on the host when the call returns
 static std::vector<uint8_t> DownloadBytes(const uint8_t* device, size_t bytes) {
   std::vector<uint8_t> host(bytes);
@@ -1350,239 +1369,64 @@ static std::vector<uint8_t> DownloadBytes(const uint8_t* device, size_t bytes) {
   return host;
 }
 
-// BrotliMi355xCompressBatchWithDictionary (routes == 0) and BrotliMi355xCompressBatchWithDictionaryEx; with on_device the
-// shared-image path of BrotliMi355xCompressBatchWithDictionariesDevice: dict, inputs[i] and outputs[i] are device addresses -- the
-// side-by-side routes take dictionary and items from device memory and leave the streams there (BatchDeviceSink), an item that runs
-// one by one comes down, runs through the stream path behind the dictionary's bytes in use (down once per call) and its stream
-// goes up, and one dev_sync() ends the call.
-static int32_t CompressBatchWithDictionary(const char* entry, int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t dict_size,
-                                           const uint8_t* dict, size_t count, const uint8_t* const* inputs, const size_t* input_sizes,
-                                           uint8_t* const* outputs, size_t* output_sizes, int32_t* item_results, bool on_device = false) {
-  uint64_t info[8] = {count, 0, 0, 0, 0, 0, 0, 0};
-  memcpy(g_batch_info, info, sizeof(info));
-  if ((routes & ~(uint32_t)BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS) != 0) {
-    // a route this call does not know fails it as a whole, like an unknown route of BrotliMi355xCompressBatchEx
-    SetError(entry, ("routes " + std::to_string(routes) + " names a route this call does not know (known behind a dictionary: "
-                     "BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS = 4)").c_str());
-    for (size_t i = 0; i < count; ++i) output_sizes[i] = 0;
-    if (item_results && count) memset(item_results, 0, count * sizeof(int32_t));
-    return 0;
-  }
-  if (count == 0) return 1;
-  size_t total = 0;
-  for (size_t i = 0; i < count; ++i) total += input_sizes[i];
-  std::vector<int32_t> results(count, 0);
-  try {
-    EncoderParams params;
-    SetParameter(&params, kParamQuality, (uint32_t)quality);
-    SetParameter(&params, kParamLgwin, (uint32_t)lgwin);
-    SetParameter(&params, kParamMode, (uint32_t)mode);
+// The one body of the dictionary batch calls, entered with what its entry refuses (`refused`, made before any device address is
+// looked at) and with quick_route, the entry's own bit for the side-by-side route of qualities 2 .. 4.  Item i lies behind
+// dicts[all_first ? 0 : item_dicts ? item_dicts[i] : i].  on_device: dicts[k], inputs[i] and outputs[i] are device addresses (the
+// arrays themselves are host memory) -- the side-by-side routes read every dictionary and item where it lies and leave the streams
+// in device memory (BatchDeviceSink with StreamDeliveryRule); an item that runs one by one comes down, its dictionary's bytes in
+// use come down once per call, it runs through the stream path and its stream goes up; the frame's dev_sync() ends the call.
+static int32_t CompressBatchWithDictionaries(const char* entry, int quality, int lgwin, BrotliEncoderMode mode, bool quick_route, const std::string& refused,
+                                             size_t num_dicts, const uint8_t* const* dicts, const size_t* dict_sizes, size_t count,
+                                             const size_t* item_dicts, bool all_first, const uint8_t* const* inputs, const size_t* input_sizes,
+                                             uint8_t* const* outputs, size_t* output_sizes, int32_t* item_results, bool on_device) {
+  const auto body = [&](const EncoderParams& params, uint64_t* info, std::vector<int32_t>& results) {
+    // one index named by every item: the shared dictionary, whose chains replay one image instead of filing the dictionary
+    size_t k0 = 0;
+    bool one = all_first;
+    if (!one) {
+      k0 = item_dicts ? item_dicts[0] : 0;
+      one = item_dicts != nullptr || count == 1;
+      for (size_t i = 1; i < count && one; ++i) one = item_dicts[i] == k0;
+    }
+    const auto named = [&](size_t i) { return one ? k0 : item_dicts ? item_dicts[i] : i; };
     // set_custom_dictionary (encode.rs:1196-1270): qualities 0 / 1 and dictionaries of less than two bytes take none; a longer one
-    // is cut to its last (1 << lgwin) - 16 bytes
-    size_t dict_use = 0;
-    {
-      EncoderParams fin = params;
-      FinalizeParams(&fin);
-      if (dict_size > 1 && fin.quality != 0 && fin.quality != 1) dict_use = std::min(dict_size, ((size_t)1 << fin.lgwin) - 16);
-    }
-    info[5] = dict_use;
-    SmallCallGate gate(total);
-    // Side by side: the items of 1 .. 65536 bytes at qualities 5 .. 8, lgwin 17 .. 24, behind a dictionary of 2 .. 65536 bytes
-    // (batch_greedy.h) and, where the caller asked for that route, the items of at most one input block at qualities 2 .. 4,
-    // lgwin 10 .. 24, behind at most 65536 dictionary bytes in use (batch_quick.h) -- a call has one quality, so its items take
-    // one of the two.  Every other item goes through the stream path by itself, on this thread, in the caller's order.
-    const bool quick_route = (routes & BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS) != 0;
-    bool quick = false;
-    std::vector<size_t> item;
-    std::vector<const uint8_t*> in;
-    std::vector<size_t> in_size;
-    DictionarySink device;
-    std::vector<uint8_t> host_dict;  // on_device: the dictionary's bytes in use, down with the first item that runs one by one
-    bool have_host_dict = false;
-    for (size_t i = 0; i < count; ++i) {
-      const bool greedy_item = BatchDictionaryEligible(params, dict_size, input_sizes[i]);
-      const bool quick_item = !greedy_item && quick_route && BatchQuickDictionaryEligible(params, dict_size, input_sizes[i]);
-      if (quick_item) quick = true;
-      if (greedy_item || quick_item) {
-        item.push_back(i);
-        in.push_back(inputs[i]);
-        in_size.push_back(input_sizes[i]);
-        if (on_device) device.Add(outputs[i], output_sizes[i]);
-        continue;
-      }
-      if (on_device) {
-        // (the stream path cuts the dictionary to the same bytes; dict_use == 0: it takes none, and none comes down)
-        if (!have_host_dict) host_dict = DownloadBytes(dict + (dict_size - dict_use), dict_use);
-        have_host_dict = true;
-        const std::vector<uint8_t> host_item = DownloadBytes(inputs[i], input_sizes[i]);
-        results[i] = CompressItemWithDictionary(quality, lgwin, mode, host_dict.size(), host_dict.data(), host_item.size(), host_item.data(),
-                                                &output_sizes[i], outputs[i], true);
-      } else {
-        results[i] = CompressItemWithDictionary(quality, lgwin, mode, dict_size, dict, input_sizes[i], inputs[i], &output_sizes[i], outputs[i]);
-      }
-      ++info[2];
-    }
-    if (!item.empty()) {
-      std::vector<std::vector<uint8_t>> streams;
-      std::vector<uint8_t> reference_fails;
-      uint32_t groups = 0;
-      if (quick)
-        BatchQuickCompressWithDictionary(params, dict + (dict_size - dict_use), dict_use, item.size(), in.data(), in_size.data(), &streams, &reference_fails, &groups,
-                                         device.Sink(on_device));
-      else
-        BatchGreedyCompressWithDictionary(params, dict + (dict_size - dict_use), dict_use, item.size(), in.data(), in_size.data(), &streams, &reference_fails, &groups,
-                                          device.Sink(on_device));
-      info[4] = groups;
-      info[1] = item.size();
-      for (size_t k = 0; k < item.size(); ++k) {
-        const size_t i = item[k];
-        const size_t capacity = output_sizes[i];
-        output_sizes[i] = 0;
-        if (reference_fails[k]) {
-          SetError(entry,
-                   ("item " + std::to_string(i) + ": the reference encoder fails on this input: a match cut to one byte at the end of the custom dictionary "
-                    "gives a copy it cannot encode (fix_unbroken_len, backward_references/mod.rs:42-54; GetCopyLengthCode, command.rs:91-93)").c_str());
-          continue;
-        }
-        if (on_device) {  // (the route's groups have answered it, by the same rule)
-          results[i] = device.result[k];
-          output_sizes[i] = device.out_size[k];
-          continue;
-        }
-        if (StreamDeliveryRule(streams[k].size(), input_sizes[i], capacity) != Delivery::kStream) continue;  // (no fallback to a stored stream: the stream API has none)
-        memcpy(outputs[i], streams[k].data(), streams[k].size());
-        output_sizes[i] = streams[k].size();
-        results[i] = 1;
-      }
-    }
-    if (on_device) dev_sync();  // everything the call wrote has landed
-  } catch (const std::exception& e) {
-    // a device error fails the call as a whole
-    SetError(entry, e.what());
-    for (size_t i = 0; i < count; ++i) output_sizes[i] = 0;
-    if (item_results) memset(item_results, 0, count * sizeof(int32_t));
-    if (on_device) {  // (what the groups in front of the error queued for the caller's buffers has landed when the call returns)
-      try {
-        dev_sync();
-      } catch (const std::exception&) {
-      }
-    }
-    return 0;
-  }
-  memcpy(g_batch_info, info, sizeof(info));
-  int32_t all = 1;
-  for (size_t i = 0; i < count; ++i) {
-    if (item_results) item_results[i] = results[i];
-    if (!results[i]) all = 0;
-  }
-  return all;
-}
-
-int32_t BrotliMi355xCompressBatchWithDictionary(int quality, int lgwin, BrotliEncoderMode mode, size_t dict_size, const uint8_t* dict, size_t count,
-                                                const uint8_t* const* inputs, const size_t* input_sizes, uint8_t* const* outputs,
-                                                size_t* output_sizes, int32_t* item_results) {
-  return CompressBatchWithDictionary("BrotliMi355xCompressBatchWithDictionary", quality, lgwin, mode, 0, dict_size, dict, count, inputs, input_sizes, outputs,
-                                     output_sizes, item_results);
-}
-
-int32_t BrotliMi355xCompressBatchWithDictionaryEx(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t dict_size, const uint8_t* dict,
-                                                  size_t count, const uint8_t* const* inputs, const size_t* input_sizes, uint8_t* const* outputs,
-                                                  size_t* output_sizes, int32_t* item_results) {
-  return CompressBatchWithDictionary("BrotliMi355xCompressBatchWithDictionaryEx", quality, lgwin, mode, routes, dict_size, dict, count, inputs, input_sizes,
-                                     outputs, output_sizes, item_results);
-}
-
-// BrotliMi355xCompressBatchWithDictionaries and, with on_device, BrotliMi355xCompressBatchWithDictionariesDevice: there dicts[k],
-// inputs[i] and outputs[i] are device addresses (the arrays themselves are host memory) -- the side-by-side routes read every
-// dictionary and item where it lies and leave the streams in device memory (BatchDeviceSink with StreamDeliveryRule); an item that
-// runs one by one comes down, its dictionary's bytes in use come down once per call, it runs through the stream path and its stream
-// goes up; one dev_sync() ends the call.  What is refused is refused before any device address is looked at.
-static int32_t CompressBatchWithDictionaries(const char* entry, int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t num_dicts,
-                                             const uint8_t* const* dicts, const size_t* dict_sizes, size_t count, const size_t* item_dicts,
-                                             const uint8_t* const* inputs, const size_t* input_sizes, uint8_t* const* outputs,
-                                             size_t* output_sizes, int32_t* item_results, bool on_device) {
-  uint64_t info[8] = {count, 0, 0, 0, 0, 0, 0, 0};
-  memcpy(g_batch_info, info, sizeof(info));
-  // what fails the call as a whole before any work is done, like an unknown route of BrotliMi355xCompressBatchEx
-  std::string refused;
-  if ((routes & ~(uint32_t)BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS) != 0) {
-    refused = "routes " + std::to_string(routes) + " names a route this call does not know (known behind a dictionary per item: "
-              "BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS = 512)";
-  } else if (item_dicts == nullptr && num_dicts != count) {
-    refused = "item_dicts is NULL (item i takes dicts[i]) but num_dicts, " + std::to_string(num_dicts) + ", is not count, " + std::to_string(count);
-  } else if (item_dicts != nullptr) {
-    for (size_t i = 0; i < count && refused.empty(); ++i)
-      if (item_dicts[i] >= num_dicts)
-        refused = "item " + std::to_string(i) + " names dictionary " + std::to_string(item_dicts[i]) + " of " + std::to_string(num_dicts);
-  }
-  if (!refused.empty()) {
-    SetError(entry, refused.c_str());
-    for (size_t i = 0; i < count; ++i) output_sizes[i] = 0;
-    if (item_results && count) memset(item_results, 0, count * sizeof(int32_t));
-    return 0;
-  }
-  if (count == 0) return 1;
-  const bool quick_route = (routes & BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS) != 0;
-  // one index named by every item: the shared-dictionary call, whose chains replay one image instead of filing the dictionary
-  {
-    const size_t k0 = item_dicts ? item_dicts[0] : 0;
-    bool one = item_dicts != nullptr || count == 1;
-    for (size_t i = 1; i < count && one; ++i) one = item_dicts[i] == k0;
-    if (one)
-      return CompressBatchWithDictionary(entry, quality, lgwin, mode, quick_route ? BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS : 0u, dict_sizes[k0], dicts[k0],
-                                         count, inputs, input_sizes, outputs, output_sizes, item_results, on_device);
-  }
-  size_t total = 0;
-  for (size_t i = 0; i < count; ++i) total += input_sizes[i];
-  std::vector<int32_t> results(count, 0);
-  try {
-    EncoderParams params;
-    SetParameter(&params, kParamQuality, (uint32_t)quality);
-    SetParameter(&params, kParamLgwin, (uint32_t)lgwin);
-    SetParameter(&params, kParamMode, (uint32_t)mode);
-    // set_custom_dictionary (encode.rs:1196-1270), per dictionary, as in CompressBatchWithDictionary: info[5] sums the bytes in
-    // use over the distinct indices that an item names
+    // is cut to its last (1 << lgwin) - 16 bytes.  info[5] sums the bytes in use over the distinct indices that an item names.
     EncoderParams fin = params;
     FinalizeParams(&fin);
     const auto in_use = [&](size_t k) -> size_t {
       return dict_sizes[k] > 1 && fin.quality != 0 && fin.quality != 1 ? std::min(dict_sizes[k], ((size_t)1 << fin.lgwin) - 16) : 0;
     };
     {
-      std::vector<uint8_t> named(num_dicts, 0);
+      std::vector<uint8_t> seen(num_dicts, 0);
       for (size_t i = 0; i < count; ++i) {
-        const size_t k = item_dicts ? item_dicts[i] : i;
-        if (!named[k]) info[5] += in_use(k);
-        named[k] = 1;
+        const size_t k = named(i);
+        if (!seen[k]) info[5] += in_use(k);
+        seen[k] = 1;
       }
     }
-    SmallCallGate gate(total);
     // Side by side: the items of 1 .. 65536 bytes at qualities 5 .. 8, lgwin 17 .. 24, behind a dictionary of 2 .. 65536 bytes in
-    // use (batch_greedy.h: a chain per item that files the item's dictionary itself) and, where the caller asked for that route,
-    // the items of at most one input block at qualities 2 .. 4, lgwin 10 .. 24, behind at most 65536 dictionary bytes in use
-    // (batch_quick.h) -- a call has one quality, so its items take one of the two.  Every other item goes through the stream
-    // path by itself with its own dictionary, on this thread, in the caller's order.
+    // use (batch_greedy.h) and, where the caller asked for that route, the items of at most one input block at qualities 2 .. 4,
+    // lgwin 10 .. 24, behind at most 65536 dictionary bytes in use (batch_quick.h) -- a call has one quality, so its items take
+    // one of the two.  Every other item goes through the stream path by itself with its own dictionary, on this thread, in the
+    // caller's order.
     bool quick = false;
-    std::vector<size_t> item, in_size, d_size;
-    std::vector<const uint8_t*> in, d;
-    DictionarySink device;
+    BatchItems r;
     // on_device: the bytes in use of the dictionaries that items running one by one name, each down once per call
     std::vector<std::vector<uint8_t>> host_dicts(on_device ? num_dicts : 0);
     std::vector<uint8_t> have_host_dict(on_device ? num_dicts : 0, 0);
     for (size_t i = 0; i < count; ++i) {
-      const size_t k = item_dicts ? item_dicts[i] : i;
+      const size_t k = named(i);
       const bool greedy_item = BatchDictionaryEligible(params, dict_sizes[k], input_sizes[i]);
       const bool quick_item = !greedy_item && quick_route && BatchQuickDictionaryEligible(params, dict_sizes[k], input_sizes[i]);
       if (quick_item) quick = true;
       if (greedy_item || quick_item) {
-        // (at qualities 5 .. 8 dict_sizes[k] itself: an eligible dictionary is below every window's limit; at lgwin 10 .. 16 its
-        // last (1 << lgwin) - 16 bytes)
-        const size_t use = in_use(k);
-        item.push_back(i);
-        in.push_back(inputs[i]);
-        in_size.push_back(input_sizes[i]);
-        d.push_back(dicts[k] + (dict_sizes[k] - use));
-        d_size.push_back(use);
-        if (on_device) device.Add(outputs[i], output_sizes[i]);
+        r.Add(i, inputs[i], input_sizes[i], outputs[i], output_sizes[i], on_device);
+        if (!one) {
+          // (at qualities 5 .. 8 dict_sizes[k] itself: an eligible dictionary is below every window's limit; at lgwin 10 .. 16 its
+          // last (1 << lgwin) - 16 bytes)
+          r.dict.push_back(dicts[k] + (dict_sizes[k] - in_use(k)));
+          r.dict_size.push_back(in_use(k));
+        }
         continue;
       }
       if (on_device) {
@@ -1597,76 +1441,106 @@ static int32_t CompressBatchWithDictionaries(const char* entry, int quality, int
       }
       ++info[2];
     }
-    if (!item.empty()) {
-      std::vector<std::vector<uint8_t>> streams;
-      std::vector<uint8_t> reference_fails;
-      uint32_t groups = 0;
-      if (quick)
-        BatchQuickCompressWithDictionaries(params, item.size(), d.data(), d_size.data(), in.data(), in_size.data(), &streams, &reference_fails, &groups,
-                                           device.Sink(on_device));
-      else
-        BatchGreedyCompressWithDictionaries(params, item.size(), d.data(), d_size.data(), in.data(), in_size.data(), &streams, &reference_fails, &groups,
-                                            device.Sink(on_device));
-      info[4] = groups;
-      info[1] = item.size();
-      for (size_t n = 0; n < item.size(); ++n) {
-        const size_t i = item[n];
-        const size_t capacity = output_sizes[i];
-        output_sizes[i] = 0;
-        if (reference_fails[n]) {
-          SetError(entry,
-                   ("item " + std::to_string(i) + ": the reference encoder fails on this input: a match cut to one byte at the end of the custom dictionary "
-                    "gives a copy it cannot encode (fix_unbroken_len, backward_references/mod.rs:42-54; GetCopyLengthCode, command.rs:91-93)").c_str());
-          continue;
-        }
-        if (on_device) {  // (the route's groups have answered it, by the same rule)
-          results[i] = device.result[n];
-          output_sizes[i] = device.out_size[n];
-          continue;
-        }
-        if (StreamDeliveryRule(streams[n].size(), input_sizes[i], capacity) != Delivery::kStream) continue;  // (no fallback to a stored stream: the stream API has none)
-        memcpy(outputs[i], streams[n].data(), streams[n].size());
-        output_sizes[i] = streams[n].size();
-        results[i] = 1;
+    if (r.item.empty()) return;
+    BatchStreams streams;
+    BatchFlags reference_fails;
+    uint32_t groups = 0;
+    const BatchDeviceSink* sink = r.Sink(on_device, StreamDeliveryRule);
+    if (one)
+      (quick ? BatchQuickCompressWithDictionary : BatchGreedyCompressWithDictionary)(params, dicts[k0] + (dict_sizes[k0] - in_use(k0)), in_use(k0), r.item.size(),
+                                                                                     r.in.data(), r.size.data(), &streams, &reference_fails, &groups, sink);
+    else
+      (quick ? BatchQuickCompressWithDictionaries : BatchGreedyCompressWithDictionaries)(params, r.item.size(), r.dict.data(), r.dict_size.data(), r.in.data(),
+                                                                                         r.size.data(), &streams, &reference_fails, &groups, sink);
+    info[4] = groups;
+    info[1] = r.item.size();
+    for (size_t n = 0; n < r.item.size(); ++n) {
+      const size_t i = r.item[n];
+      const size_t capacity = output_sizes[i];
+      output_sizes[i] = 0;
+      if (reference_fails[n]) {
+        SetError(entry,
+                 ("item " + std::to_string(i) + ": the reference encoder fails on this input: a match cut to one byte at the end of the custom dictionary "
+                  "gives a copy it cannot encode (fix_unbroken_len, backward_references/mod.rs:42-54; GetCopyLengthCode, command.rs:91-93)").c_str());
+        continue;
       }
-    }
-    if (on_device) dev_sync();  // everything the call wrote has landed
-  } catch (const std::exception& e) {
-    // a device error fails the call as a whole
-    SetError(entry, e.what());
-    for (size_t i = 0; i < count; ++i) output_sizes[i] = 0;
-    if (item_results) memset(item_results, 0, count * sizeof(int32_t));
-    if (on_device) {  // (what the groups in front of the error queued for the caller's buffers has landed when the call returns)
-      try {
-        dev_sync();
-      } catch (const std::exception&) {
+      if (on_device) {  // (the route's groups have answered it, by the same rule)
+        results[i] = r.result[n];
+        output_sizes[i] = r.out_size[n];
+        continue;
       }
+      if (StreamDeliveryRule(streams[n].size(), input_sizes[i], capacity) != Delivery::kStream) continue;  // (no fallback to a stored stream: the stream API has none)
+      memcpy(outputs[i], streams[n].data(), streams[n].size());
+      output_sizes[i] = streams[n].size();
+      results[i] = 1;
     }
-    return 0;
+  };
+  return RunBatchCall(entry, quality, lgwin, mode, false, count, input_sizes, output_sizes, item_results, on_device, refused, std::ref(body));
+}
+
+// BrotliMi355xCompressBatchWithDictionary (routes == 0) and BrotliMi355xCompressBatchWithDictionaryEx: the body above with one
+// dictionary that every item names
+static int32_t CompressBatchWithSharedDictionary(const char* entry, int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t dict_size,
+                                                 const uint8_t* dict, size_t count, const uint8_t* const* inputs, const size_t* input_sizes,
+                                                 uint8_t* const* outputs, size_t* output_sizes, int32_t* item_results) {
+  std::string refused;
+  if ((routes & ~(uint32_t)BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS) != 0) {
+    refused = "routes " + std::to_string(routes) + " names a route this call does not know (known behind a dictionary: "
+              "BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS = 4)";
   }
-  memcpy(g_batch_info, info, sizeof(info));
-  int32_t all = 1;
-  for (size_t i = 0; i < count; ++i) {
-    if (item_results) item_results[i] = results[i];
-    if (!results[i]) all = 0;
+  return CompressBatchWithDictionaries(entry, quality, lgwin, mode, (routes & BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS) != 0, refused, 1, &dict, &dict_size, count,
+                                       nullptr, true, inputs, input_sizes, outputs, output_sizes, item_results, false);
+}
+
+int32_t BrotliMi355xCompressBatchWithDictionary(int quality, int lgwin, BrotliEncoderMode mode, size_t dict_size, const uint8_t* dict, size_t count,
+                                                const uint8_t* const* inputs, const size_t* input_sizes, uint8_t* const* outputs,
+                                                size_t* output_sizes, int32_t* item_results) {
+  return CompressBatchWithSharedDictionary("BrotliMi355xCompressBatchWithDictionary", quality, lgwin, mode, 0, dict_size, dict, count, inputs, input_sizes,
+                                           outputs, output_sizes, item_results);
+}
+
+int32_t BrotliMi355xCompressBatchWithDictionaryEx(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t dict_size, const uint8_t* dict,
+                                                  size_t count, const uint8_t* const* inputs, const size_t* input_sizes, uint8_t* const* outputs,
+                                                  size_t* output_sizes, int32_t* item_results) {
+  return CompressBatchWithSharedDictionary("BrotliMi355xCompressBatchWithDictionaryEx", quality, lgwin, mode, routes, dict_size, dict, count, inputs,
+                                           input_sizes, outputs, output_sizes, item_results);
+}
+
+// BrotliMi355xCompressBatchWithDictionaries and, with on_device, BrotliMi355xCompressBatchWithDictionariesDevice: the body above
+// with a dictionary per item.  What is refused is refused before any device address is looked at.
+static int32_t CompressBatchWithItemDictionaries(const char* entry, int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t num_dicts,
+                                                 const uint8_t* const* dicts, const size_t* dict_sizes, size_t count, const size_t* item_dicts,
+                                                 const uint8_t* const* inputs, const size_t* input_sizes, uint8_t* const* outputs, size_t* output_sizes,
+                                                 int32_t* item_results, bool on_device) {
+  std::string refused;
+  if ((routes & ~(uint32_t)BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS) != 0) {
+    refused = "routes " + std::to_string(routes) + " names a route this call does not know (known behind a dictionary per item: "
+              "BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS = 512)";
+  } else if (item_dicts == nullptr && num_dicts != count) {
+    refused = "item_dicts is NULL (item i takes dicts[i]) but num_dicts, " + std::to_string(num_dicts) + ", is not count, " + std::to_string(count);
+  } else if (item_dicts != nullptr) {
+    for (size_t i = 0; i < count && refused.empty(); ++i)
+      if (item_dicts[i] >= num_dicts)
+        refused = "item " + std::to_string(i) + " names dictionary " + std::to_string(item_dicts[i]) + " of " + std::to_string(num_dicts);
   }
-  return all;
+  return CompressBatchWithDictionaries(entry, quality, lgwin, mode, (routes & BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS) != 0, refused, num_dicts, dicts,
+                                       dict_sizes, count, item_dicts, false, inputs, input_sizes, outputs, output_sizes, item_results, on_device);
 }
 
 int32_t BrotliMi355xCompressBatchWithDictionaries(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t num_dicts,
                                                   const uint8_t* const* dicts, const size_t* dict_sizes, size_t count, const size_t* item_dicts,
                                                   const uint8_t* const* inputs, const size_t* input_sizes, uint8_t* const* outputs,
                                                   size_t* output_sizes, int32_t* item_results) {
-  return CompressBatchWithDictionaries("BrotliMi355xCompressBatchWithDictionaries", quality, lgwin, mode, routes, num_dicts, dicts, dict_sizes, count,
-                                       item_dicts, inputs, input_sizes, outputs, output_sizes, item_results, false);
+  return CompressBatchWithItemDictionaries("BrotliMi355xCompressBatchWithDictionaries", quality, lgwin, mode, routes, num_dicts, dicts, dict_sizes, count,
+                                           item_dicts, inputs, input_sizes, outputs, output_sizes, item_results, false);
 }
 
 int32_t BrotliMi355xCompressBatchWithDictionariesDevice(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t num_dicts,
                                                         const uint8_t* const* dicts_device, const size_t* dict_sizes, size_t count,
                                                         const size_t* item_dicts, const uint8_t* const* inputs_device, const size_t* input_sizes,
                                                         uint8_t* const* outputs_device, size_t* output_sizes, int32_t* item_results) {
-  return CompressBatchWithDictionaries("BrotliMi355xCompressBatchWithDictionariesDevice", quality, lgwin, mode, routes, num_dicts, dicts_device, dict_sizes,
-                                       count, item_dicts, inputs_device, input_sizes, outputs_device, output_sizes, item_results, true);
+  return CompressBatchWithItemDictionaries("BrotliMi355xCompressBatchWithDictionariesDevice", quality, lgwin, mode, routes, num_dicts, dicts_device,
+                                           dict_sizes, count, item_dicts, inputs_device, input_sizes, outputs_device, output_sizes, item_results, true);
 }
 
 void BrotliMi355xLastBatchInfo(uint64_t info[8]) { memcpy(info, g_batch_info, sizeof(g_batch_info)); }

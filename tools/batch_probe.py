@@ -60,7 +60,9 @@ are 4096x4KiB, 1024x16KiB, 256x64KiB and 64x256KiB, the few-items cases 16x4KiB 
 
 With --same-call (and any of the above) the parent's library is measured through the very call this build is measured through, route bits
 and dictionary included, alternating with it --rounds times: the A/B of a change that keeps the routes.  Per class the result holds the
-medians of both, their difference, and the parent's own spread between its rounds as the margin; nothing else is measured.
+medians of both, their difference, and the parent's own spread between its rounds as the margin; nothing else is measured.  With
+--dictionary N the classes are those --only names; with --dicts the call is BrotliMi355xCompressBatchWithDictionaries on the
+DICTS_CLASSES, every item behind its own dictionary.
 
 With --dicts (and --qualities 5,8, or 2,3,4) the call measured is BrotliMi355xCompressBatchWithDictionaries, a custom dictionary per item: text items,
 and per item a dictionary that is another draw from the items' own source (DICTS_CLASSES: 4096 items of 4 KiB behind 4 and 16 KiB, 1024 of
@@ -930,7 +932,9 @@ def main_same_call(args, doc, save, classes):
     each -- for a change that keeps the routes and must not cost them anything.  Per class: the median of either build's round
     medians, and the parent's own run-to-run spread (the largest difference between its rounds) as the margin."""
     doc["what"] = "this build against the parent commit's library through the same batch call (%s), alternating, %d rounds; lgwin 22" % (
-        ", ".join(n for n in ("long_items", "quick_items", "quick_long_items", "zopfli_items", "q9_items") if getattr(args, n)) or "no route bit", args.rounds)
+        ", ".join([n for n in ("long_items", "quick_items", "quick_long_items", "zopfli_items", "q9_items") if getattr(args, n)] +
+                  (["a dictionary per item"] if args.dicts else ["a shared dictionary of %d bytes" % args.dictionary] if args.dictionary else [])) or "no route bit",
+        args.rounds)
     routes = dict(long_items=args.long_items, quick_items=args.quick_items, quick_long_items=args.quick_long_items, zopfli_items=args.zopfli_items,
                   q9_items=args.q9_items)
     rows = {}
@@ -1019,11 +1023,13 @@ def main():
     if args.q9_items:
         doc["what"] = ("BrotliMi355xCompressBatchEx(BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS) vs the parent commit's batch call, there one by one (on the first "
                        "--loop-items items, scaled by item count), and its 4-thread loop vs the oracle on one CPU core; lgwin 22")
-    if args.dicts:
+    if args.dicts and not args.same_call:
         return main_dicts(args, doc, save, [c for c in DICTS_CLASSES if not args.only or c in args.only.split(",")])
     if args.same_call:
+        if args.dicts:  # (the per-item call, every item behind its own dictionary)
+            return main_same_call(args, doc, save, [c for c in DICTS_CLASSES if not args.only or c in args.only.split(",")])
         dict_classes = DICT_QUICK_HEADLINE if args.quick_items else ["4096x4KiB", "1024x64KiB"]
-        return main_same_call(args, doc, save, [c for c in dict_classes if not args.only or c in args.only.split(",")] if args.dictionary else headline)
+        return main_same_call(args, doc, save, (headline if args.only else dict_classes) if args.dictionary else headline)
     if args.dictionary and args.quick_items:
         return main_dictionary_quick(args, doc, save, [c for c in DICT_QUICK_HEADLINE if not args.only or c in args.only.split(",")])
     if args.dictionary:
