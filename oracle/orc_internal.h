@@ -121,6 +121,10 @@ void orc_create_hq_zopfli_backward_references(size_t num_bytes, size_t position,
                                               size_t* num_literals);
 int orc_find_all_static_dictionary_matches(const uint8_t* data, size_t min_length, size_t max_length,
                                            uint32_t* matches); /* static_dict.rs:309-1300 */
+/* the literal-cost model, SetCost and FastLog2 on their own (orc_zopfli.c; tests/test_zopfli_parts.py) */
+void orc_debug_literal_costs(const uint8_t* data, size_t len, float* cost, float* prefix, int* mostly_utf8, int* stats_level);
+void orc_debug_cost_from_histogram(const uint32_t* histogram, size_t size, int literal, float* cost);
+void orc_debug_fast_log2(const uint64_t* values, size_t n, float* out);
 uint16_t orc_combine_length_codes(uint16_t inscode, uint16_t copycode, int use_last_distance); /* command.rs:110-125 */
 extern int orc_reference_would_panic;
 

@@ -915,3 +915,27 @@ void orc_create_hq_zopfli_backward_references(size_t num_bytes, size_t position,
   free(matches);
   free(num_matches);
 }
+
+/* ------------------------------------------------------------------ the cost model, stage by stage (tests/test_zopfli_parts.py)
+   Thin wrappers: each calls the static function the streams go through. */
+void orc_debug_literal_costs(const uint8_t* data, size_t len, float* cost, float* prefix, int* mostly_utf8, int* stats_level) {
+  /* cost: len entries, BrotliEstimateBitCostsForLiterals(pos 0, mask ~0); prefix: len + 1 entries, literal_costs_ behind
+     set_from_literal_costs; the verdict of BrotliIsMostlyUTF8 and the level of DecideMultiByteStatsLevel on the same bytes */
+  DistanceParams dist;
+  ZopfliCostModel model;
+  memset(&dist, 0, sizeof(dist));
+  dist.alphabet_size = ORC_NUM_DISTANCE_HISTO_SYMBOLS;
+  estimate_bit_costs_for_literals(0, len, ~(size_t)0, data, cost);
+  cost_model_init(&model, &dist, len);
+  cost_model_set_from_literal_costs(&model, 0, data, ~(size_t)0);
+  memcpy(prefix, model.literal_costs_, (len + 1) * sizeof(float));
+  cost_model_cleanup(&model);
+  *mostly_utf8 = orc_is_mostly_utf8(data, 0, ~(size_t)0, len, 0.75f);
+  *stats_level = (int)decide_multi_byte_stats_level(0, len, ~(size_t)0, data);
+}
+void orc_debug_cost_from_histogram(const uint32_t* histogram, size_t size, int literal, float* cost) {
+  set_cost_from_histogram(histogram, size, literal, cost);
+}
+void orc_debug_fast_log2(const uint64_t* values, size_t n, float* out) {
+  for (size_t i = 0; i < n; ++i) out[i] = orc_fast_log2(values[i]);
+}

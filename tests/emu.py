@@ -210,3 +210,86 @@ def hq_cluster(L, kind, jobs, expand64=None):
         at += in_sizes[i]
         mat += msz
     return out
+
+
+DICT_WORDS = 38  # dict_matches[0 .. 37]
+
+
+def dictionary_matches_raw(L, text, at, min_length, max_length):
+    """brotli_mi355x_debug_dictionary_matches as it is: returns (status, matches [n x 38], any [n])."""
+    import numpy as np
+    f = L.brotli_mi355x_debug_dictionary_matches
+    f.restype = ctypes.c_int
+    f.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32] + [ctypes.c_void_p] * 5
+    text = bytes(text)
+    at = np.ascontiguousarray(at, dtype=np.uint32)
+    lo = np.ascontiguousarray(min_length, dtype=np.uint32)
+    hi = np.ascontiguousarray(max_length, dtype=np.uint32)
+    n = len(at)
+    assert len(lo) == n and len(hi) == n
+    out = np.full((max(n, 1), DICT_WORDS), 0xeeeeeeee, dtype=np.uint32)
+    anyv = np.full(max(n, 1), 0xeeeeeeee, dtype=np.uint32)
+    r = f(text, len(text), n, at.ctypes.data, lo.ctypes.data, hi.ctypes.data, out.ctypes.data, anyv.ctypes.data)
+    return r, out[:n], anyv[:n]
+
+
+def dictionary_matches(L, text, at, min_length, max_length):
+    """z_find_all_dictionary_matches of the library at every text + at[q] (one query per lane on the device), one launch.  Returns
+    (matches [n x 38] numpy uint32 -- 0x0fffffff where no word matches that length --, any [n])."""
+    r, out, anyv = dictionary_matches_raw(L, text, at, min_length, max_length)
+    if r != 0:
+        raise RuntimeError("brotli_mi355x_debug_dictionary_matches returned %d" % r)
+    return out, anyv
+
+
+def fast_log2(L, mode, values):
+    """brotli_mi355x_debug_fast_log2: mode 0 z_fast_log2, 1 br_fast_log2 of the low 32 bits, 2 logs_16[v & 0xffff]; bit patterns"""
+    import numpy as np
+    f = L.brotli_mi355x_debug_fast_log2
+    f.restype = ctypes.c_int
+    f.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
+    v = np.ascontiguousarray(values, dtype=np.uint64)
+    out = np.full(max(1, len(v)), 0xeeeeeeee, dtype=np.uint32)
+    r = f(mode, len(v), v.ctypes.data, out.ctypes.data)
+    if r != 0:
+        raise RuntimeError("brotli_mi355x_debug_fast_log2 returned %d" % r)
+    return out[:len(v)]
+
+
+def literal_costs(L, blocks):
+    """brotli_mi355x_debug_literal_costs of the blocks (bytes, 1 .. 65536 each), one launch.  Returns one (cost bits [len], prefix bits
+    [len + 1]) pair per block."""
+    import numpy as np
+    f = L.brotli_mi355x_debug_literal_costs
+    f.restype = ctypes.c_int
+    f.argtypes = [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p]
+    lengths = np.array([len(b) for b in blocks], dtype=np.uint32)
+    data = b"".join(bytes(b) for b in blocks)
+    cost = np.full(max(1, len(data)), 0xeeeeeeee, dtype=np.uint32)
+    prefix = np.full(len(data) + len(blocks) + 1, 0xeeeeeeee, dtype=np.uint32)
+    r = f(len(blocks), lengths.ctypes.data, data, cost.ctypes.data, prefix.ctypes.data)
+    if r != 0:
+        raise RuntimeError("brotli_mi355x_debug_literal_costs returned %d" % r)
+    out, at = [], 0
+    for j, b in enumerate(blocks):
+        out.append((cost[at:at + len(b)].copy(), prefix[at + j:at + j + len(b) + 1].copy()))
+        at += len(b)
+    return out
+
+
+def cost_from_histogram(L, rows, literal):
+    """brotli_mi355x_debug_cost_from_histogram of the rows (numpy uint32, 1 .. 1200 counts each; literal[j]: a literal histogram), one
+    launch.  Returns the bit patterns of the costs, one array per row."""
+    import numpy as np
+    f = L.brotli_mi355x_debug_cost_from_histogram
+    f.restype = ctypes.c_int
+    f.argtypes = [ctypes.c_uint32] + [ctypes.c_void_p] * 4
+    rows = [np.ascontiguousarray(r, dtype=np.uint32) for r in rows]
+    sizes = np.array([len(r) for r in rows], dtype=np.uint32)
+    lit = np.array([1 if x else 0 for x in literal], dtype=np.uint32)
+    flat = np.concatenate(rows)
+    cost = np.full(len(flat), 0xeeeeeeee, dtype=np.uint32)
+    r = f(len(rows), sizes.ctypes.data, lit.ctypes.data, flat.ctypes.data, cost.ctypes.data)
+    if r != 0:
+        raise RuntimeError("brotli_mi355x_debug_cost_from_histogram returned %d" % r)
+    return np.split(cost, np.cumsum(sizes)[:-1])

@@ -18,6 +18,7 @@
 #include "../../rust-brotli_amd/csrc/lz77_rows.h"
 #include "../../rust-brotli_amd/csrc/lz77_groups.h"
 #include "../../rust-brotli_amd/csrc/zopfli_device.h"
+#include "../../rust-brotli_amd/csrc/zopfli_entry_api.h"
 #include "../../rust-brotli_amd/csrc/quick_device.h"
 #include "../../rust-brotli_amd/csrc/quick_spec.h"
 #include "../../rust-brotli_amd/csrc/fragment_device.h"
@@ -856,6 +857,61 @@ bool lz77_zopfli_block(const Lz77Params& P, const Lz77Buffers& B, const ZopfliJo
   }
   if (redo) br_zopfli_parse(Z, T, ZB, B.text, seg, B.entries[block], ctl, false, B.cmds + seg.cmd_base, B.exits + block);
   return redo;
+}
+
+// ---- introspection of zopfli_device.h (zopfli_entry.inc): the same functions, one query / value / job after the other
+static ZopfliTables emu_zopfli_tables() {
+  const DeviceTables& dt = dev_tables();
+  ZopfliTables T;
+  T.lut_buckets = dt.dict_lut_buckets;
+  T.lut_words = dt.dict_lut_words;
+  T.dict_data = dt.dict_data;
+  T.dict_offsets_by_length = dt.dict_offsets_by_length;
+  T.dict_size_bits_by_length = dt.dict_size_bits_by_length;
+  T.logs.logs_16 = dt.logs_16;
+  T.logs.logs_8 = dt.logs_8;
+  return T;
+}
+void zopfli_debug_dictionary_matches(const uint8_t* text, uint32_t n_queries, const uint32_t* at, const uint32_t* min_length,
+                                     const uint32_t* max_length, uint32_t* matches, uint32_t* any) {
+  const ZopfliTables T = emu_zopfli_tables();
+  for (uint32_t q = 0; q < n_queries; ++q) {
+    uint32_t found[38];
+    for (uint32_t i = 0; i <= 37; ++i) found[i] = kZInvalidMatch;
+    any[q] = z_find_all_dictionary_matches(T, text + at[q], min_length[q], max_length[q], found) ? 1u : 0u;
+    for (uint32_t i = 0; i <= 37; ++i) matches[(size_t)q * 38 + i] = found[i];
+  }
+}
+void zopfli_debug_fast_log2(uint32_t mode, uint32_t n, const unsigned long long* values, uint32_t* out_bits) {
+  const ZopfliTables T = emu_zopfli_tables();
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint64_t v = values[i];
+    const float r = mode == 0 ? z_fast_log2(T.logs, v) : (mode == 1 ? br_fast_log2(T.logs, (uint32_t)v) : T.logs.logs_16[v & 0xffffu]);
+    out_bits[i] = z_to_bits(r);
+  }
+}
+void zopfli_debug_literal_costs(uint32_t n_jobs, const uint32_t* lengths, const unsigned long long* offsets, const uint8_t* data,
+                                uint32_t* histo, float* cost, float* prefix) {
+  const ZopfliTables T = emu_zopfli_tables();
+  std::vector<float> cost_cmd(704), cost_dist(544);
+  for (uint32_t j = 0; j < n_jobs; ++j) {
+    const uint8_t* d = data + offsets[j];
+    uint32_t* h = histo + (size_t)j * 768;
+    z_literal_costs(T, d, lengths[j], h, cost + offsets[j]);
+    ZCostModel model;
+    model.cost_cmd = cost_cmd.data();
+    model.cost_dist = cost_dist.data();
+    model.literal_costs = prefix + offsets[j] + 2 * (size_t)j;
+    model.distance_histogram_size = 544;
+    model.min_cost_cmd = 0.0f;
+    model.num_bytes = lengths[j];
+    z_model_from_literal_costs(model, T, d, h);
+  }
+}
+void zopfli_debug_cost_from_histogram(uint32_t n_jobs, const uint32_t* sizes, const uint32_t* literal, const unsigned long long* offsets,
+                                      const uint32_t* histograms, float* cost) {
+  const ZopfliTables T = emu_zopfli_tables();
+  for (uint32_t j = 0; j < n_jobs; ++j) z_set_cost_from_histogram(T, histograms + offsets[j], sizes[j], literal[j] != 0, cost + offsets[j]);
 }
 
 // ---- qualities 2 .. 4 (quick_device.h): the same item code, called directly

@@ -22,3 +22,7 @@ def lib():
 build_codes = emu.build_codes
 hq_split = emu.hq_split
 hq_cluster = emu.hq_cluster
+dictionary_matches = emu.dictionary_matches
+fast_log2 = emu.fast_log2
+literal_costs = emu.literal_costs
+cost_from_histogram = emu.cost_from_histogram

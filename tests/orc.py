@@ -417,3 +417,78 @@ def cluster_histograms(rows, max_histograms=256):
                                  slots.ctypes.data, symbols.ctypes.data, ctypes.byref(cnt))
     return dict(rows=out_rows[:k], totals=totals[:k], costs=costs[:k].view(np.uint32), slot_costs=slots.view(np.uint32), map=symbols,
                 counters=cnt.as_dict())
+
+
+# ---- the parts of the quality 10 / 11 backward-reference stage on their own (tests/test_zopfli_parts.py)
+DICT_WORDS = 38                # dict_matches[0 .. 37] of FindAllMatchesH10
+INVALID_MATCH = 0x0fffffff     # kInvalidMatch
+
+
+def find_all_static_dictionary_matches(text, at, min_length, max_length):
+    """BrotliFindAllStaticDictionaryMatches (orc_static_dict.c) at every text + at[q] with min_length[q] / max_length[q].  `text` must
+    carry at least three bytes behind the last place asked (the search hashes the four bytes at its place whatever max_length is).
+    Returns (matches [n x 38] numpy uint32, any [n] numpy uint32)."""
+    import numpy as np
+    L = lib()
+    f = L.orc_find_all_static_dictionary_matches
+    f.restype = ctypes.c_int
+    f.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]
+    buf = np.frombuffer(bytes(text), dtype=np.uint8)
+    n = len(at)
+    assert n == len(min_length) == len(max_length)
+    assert n == 0 or int(np.max(np.asarray(at, dtype=np.int64))) + 4 <= len(buf)
+    out = np.full((max(n, 1), DICT_WORDS), INVALID_MATCH, dtype=np.uint32)
+    anyv = np.zeros(max(n, 1), dtype=np.uint32)
+    base, obase = buf.ctypes.data, out.ctypes.data
+    for q, (a, lo, hi) in enumerate(zip(np.asarray(at).tolist(), np.asarray(min_length).tolist(), np.asarray(max_length).tolist())):
+        anyv[q] = 1 if f(base + a, lo, hi, obase + q * DICT_WORDS * 4) else 0
+    return out[:n], anyv[:n]
+
+
+def debug_literal_costs(data):
+    """BrotliEstimateBitCostsForLiterals and the running sum of set_from_literal_costs on one block.  Returns (cost bits [len], prefix
+    bits [len + 1], verdict of BrotliIsMostlyUTF8, level of DecideMultiByteStatsLevel)."""
+    import numpy as np
+    L = lib()
+    L.orc_debug_literal_costs.restype = None
+    L.orc_debug_literal_costs.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),
+                                          ctypes.POINTER(ctypes.c_int)]
+    data = bytes(data)
+    cost = np.zeros(len(data), dtype=np.float32)
+    prefix = np.zeros(len(data) + 1, dtype=np.float32)
+    utf8, level = ctypes.c_int(-1), ctypes.c_int(-1)
+    L.orc_debug_literal_costs(data, len(data), cost.ctypes.data, prefix.ctypes.data, ctypes.byref(utf8), ctypes.byref(level))
+    return cost.view(np.uint32), prefix.view(np.uint32), bool(utf8.value), level.value
+
+
+def debug_cost_from_histogram(histogram, literal):
+    """SetCost (hq.rs:1043-1071) of one row of counts (numpy uint32): the bit patterns of the costs"""
+    import numpy as np
+    L = lib()
+    L.orc_debug_cost_from_histogram.restype = None
+    L.orc_debug_cost_from_histogram.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
+    h = np.ascontiguousarray(histogram, dtype=np.uint32)
+    cost = np.zeros(len(h), dtype=np.float32)
+    L.orc_debug_cost_from_histogram(h.ctypes.data, len(h), 1 if literal else 0, cost.ctypes.data)
+    return cost.view(np.uint32)
+
+
+def debug_fast_log2(values):
+    """FastLog2 / FastLog2f64 of every value (numpy uint64): the table below 256, libm's log2f of the value as f32 from there on.
+    Returns the bit patterns."""
+    import numpy as np
+    L = lib()
+    L.orc_debug_fast_log2.restype = None
+    L.orc_debug_fast_log2.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    v = np.ascontiguousarray(values, dtype=np.uint64)
+    out = np.zeros(len(v), dtype=np.float32)
+    L.orc_debug_fast_log2(v.ctypes.data, len(v), out.ctypes.data)
+    return out.view(np.uint32)
+
+
+def logs_16():
+    """the 65 536-entry log table of the entropy sums, as bit patterns"""
+    import numpy as np
+    L = lib()
+    L.orc_logs_16.restype = ctypes.c_void_p
+    return np.ctypeslib.as_array(ctypes.cast(L.orc_logs_16(), ctypes.POINTER(ctypes.c_uint32)), shape=(65536,)).copy()

@@ -290,3 +290,10 @@ def test_few_stored_slots_in_a_long_key(L):
     assert d.count(bytes(4096)) > 0
     assert check_bytes(L, "mixed 200k", d, [(Q, 5), (W, 22)], seg=4096, verbose=False)
     assert check_bytes(L, "mixed 200k", d, [(Q, 5), (W, 22)], seg=0, verbose=False)
+
+
+def test_streams_of_dictionary_words(L):
+    """qualities 5 and 9 on a text made of the static dictionary's words (dict_words.py): the oracle's streams carry 357 / 356
+    dictionary references over exactly the ten transforms SearchInStaticDictionary can produce, asserted before the comparison"""
+    import dict_words
+    dict_words.check_streams(L, (5, 9))

@@ -160,3 +160,10 @@ def test_candidate_rows_equal_a_rebuild_after_every_update():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     p = subprocess.run([sys.executable, os.path.join(root, "tools", "rows_selftest_gpu.py"), "quick"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
     assert p.returncode == 0 and b"ROWS SELFTEST OK" in p.stdout, p.stdout.decode()[-2000:]
+
+
+def test_streams_of_dictionary_words(L):
+    """qualities 5 and 9 on a text made of the static dictionary's words (dict_words.py): the oracle's streams carry 357 / 356
+    dictionary references over exactly the ten transforms SearchInStaticDictionary can produce, asserted before the comparison"""
+    import dict_words
+    dict_words.check_streams(L, (5, 9))

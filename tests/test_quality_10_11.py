@@ -181,3 +181,23 @@ def test_multi_shard_gpu():
 def test_flushes_gpu():
     import test_cabi
     _flushes(test_cabi._load("gpu"), small=True)
+
+
+def _dictionary_words(L):
+    """12 288 bytes made of the static dictionary's words under the 113 transforms BrotliFindAllStaticDictionaryMatches knows
+    (dict_words.py): the oracle's streams of it carry 663 (quality 10, through the stream entry used here) and 677 (quality 11)
+    dictionary references over 112 / 113 transforms -- asserted on the oracle's stream before the comparison -- so the rows of the
+    device's affix tables show in the bytes, which alice (79 transforms in the match finder, fewer in the stream) cannot do"""
+    import dict_words
+    dict_words.check_streams(L, (10, 11))
+
+
+def test_streams_of_dictionary_words_emu():
+    import emu
+    _dictionary_words(emu.lib())
+
+
+@pytest.mark.gpu
+def test_streams_of_dictionary_words_gpu():
+    import gpulib
+    _dictionary_words(gpulib.lib())
