@@ -400,9 +400,11 @@ int32_t BrotliMi355xCompressBatchWithDictionaryEx(int quality, int lgwin, Brotli
    item_dicts == NULL: item i takes dicts[i], and num_dicts must be count.  Several items may name one index.  Dictionaries are
    told apart by index, not by content.  dicts[k] may be NULL when dict_sizes[k] is 0.  count == 0 returns 1.
    An index >= num_dicts, item_dicts == NULL with num_dicts != count, or any bit in routes other than
-   BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS fails the whole call before any work is done, as an unknown route fails
-   BrotliMi355xCompressBatchEx (returns 0, every size 0, BrotliMi355xLastError says why, only info[0] of BrotliMi355xLastBatchInfo
-   is set).  routes == 0 is the call as described below in every respect.  The one route this call knows, so a caller can probe:
+   BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS and BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS fails the whole call
+   before any work is done, as an unknown route fails BrotliMi355xCompressBatchEx (returns 0, every size 0, BrotliMi355xLastError
+   says why, only info[0] of BrotliMi355xLastBatchInfo is set).  routes == 0 is the call as described below in every respect.
+   The two routes this call knows, so a caller can probe; they may be combined, and since a call has one quality at most one of
+   them takes items.
    BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS (512; the bits of the other batch calls, 4 and 256 among them, stay unknown
    here, and 512 stays unknown there): item i is still exactly the stream described above.  In addition to the items the call
    takes side by side without it, an item of at most one input block at quality 2, 3 or 4 and lgwin 10 .. 24 -- 1 <=
@@ -429,6 +431,34 @@ int32_t BrotliMi355xCompressBatchWithDictionaryEx(int quality, int lgwin, Brotli
    BrotliMi355xCompressBatchWithDictionaryEx copies one image instead of filing the dictionary per item: self-filing is within
    5 % of it where the item is at least as long as the dictionary, 1.13 .. 1.15 x slower for 4 KiB items behind 16 KiB, and
    1.4 .. 1.6 x slower for 512-byte items behind 16 KiB.
+   BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS (1024; unknown to the other five batch entry points): item i is still exactly
+   the stream described above, at quality 10 AND at quality 11 -- through the stream API, which defines these items, both qualities
+   are Zopfli (the one-shot entry runs quality 10 as the parse of quality 9, which is why BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS
+   takes quality 11 alone; this route takes both).  An item of 1 <= input_sizes[i] <= 65 536 bytes at quality 10 or 11 and lgwin
+   10 .. 24 behind a dictionary of dict_sizes[k] >= 2 of which at most 65 536 bytes are in use (min(dict_sizes[k], (1 << lgwin) -
+   16)) runs on the device as ONE wavefront: it empties H10 trees of its own, files its item's dictionary into them -- every
+   position with 127 bytes behind it, the 64 lanes each owning the hash keys of one class, which leaves exactly the trees of the
+   reference's one loop --, stitches, and walks the item the reference's way from position D.  There is no tree image per
+   dictionary: a call in which every item names one index takes this route all the same, every chain with its own copy.  Every
+   other item -- the empty one, longer items, dict_sizes[k] <= 1, more than 65 536 bytes in use -- runs by itself through the
+   stream path.  The bit changes nothing at qualities 0 .. 9.  Such items count in info[1], their groups (at most 1024 items) in
+   info[4]; info[2], info[5] as below; info[6] and info[7] stay 0.  An item on which the reference's quality 10 / 11 parse itself
+   fails fails alone ("the reference encoder fails on this input"); none was met in 316 000 drawn pairs.
+   Memory: a table per item in flight, at most 256 -- 512 KiB of buckets, 8 bytes of forest per byte of the group's largest
+   dictionary + item (at most 8 << lgwin) and about 1.05 KiB per byte of its largest item: 4.8 MiB for 4 KiB items behind 16 KiB,
+   17.7 MiB for 16 KiB items behind 64 KiB, 67.8 MiB for 64 KiB items behind 64 KiB.
+   When to set it: tens to thousands of small (old version, new file) pairs at the level static files are pre-compressed at.
+   Measured (text, lgwin 22, every item behind a dictionary of its own, min .. max of five alternating runs;
+   profiles/r27_batch_dictionaries_zopfli.json; the one-by-one baselines timed on 8 items and scaled): 1024 items of 4 KiB behind
+   16 KiB each at quality 10 / 11 in 320 .. 321 / 587 .. 588 ms against 67 / 110 .. 112 s for the same call without the bit (the
+   parent build), 30 .. 50 / 58 .. 77 s for the loop of stream calls from four threads and 1.8 / 3.9 s on one CPU core; 256 items
+   of 16 KiB behind 64 KiB each in 338 / 629 .. 633 ms against 65 .. 66 / 112 .. 114 s (one core 2.0 / 4.2 s); 256 items of 4 KiB
+   behind 64 KiB each in 155 .. 159 / 228 .. 229 ms against 43 / 55 s (one core 1.2 / 1.7 s); 64 items of 4 KiB behind 16 KiB each
+   in 85 .. 86 / 156 .. 157 ms against 4.2 / 6.9 .. 7.0 s -- and only 1.3 / 1.5 x one CPU core.  When not: a call of a few items --
+   a walk is one wavefront and lasts its item's time however many run beside it: 16 items of 4 KiB behind 16 KiB each take 84 ..
+   85 / 155 .. 156 ms, 11 .. 12 x faster than without the bit and still LOSE to one CPU core (29 / 61 ms, 0.34 / 0.39 x).  No
+   measured shape loses to the call without the bit or to the four-thread loop.  (The wave-wide filing against lane 0 filing the
+   dictionary alone inside the same kernel: 1.04 .. 1.08 x faster with 16 KiB dictionaries, 1.32 .. 1.47 x with 64 KiB.)
    Side by side on the device: quality 5 .. 8, lgwin 17 .. 24, 2 <= D_i <= 65536 (the bytes of the item's dictionary in use) and
    1 <= input_sizes[i] <= 65536.  A group uploads its items and, once each, the dictionaries they name; the text
    dictionary | item is laid out on the device per item, and one chain per item files the dictionary into a private hash table and
@@ -449,8 +479,11 @@ int32_t BrotliMi355xCompressBatchWithDictionaryEx(int quality, int lgwin, Brotli
    of 4 KiB behind 16 KiB each in 4.7 / 6.1 ms against 88 / 97 ms -- and only 2.7 / 3.6 x one CPU core.  No measured shape loses to
    the loop or to one core.  Against the shared image, on the same items behind ONE dictionary given as count indices: level at
    4 KiB of dictionary, 1.14 .. 1.22 x slower at 16 KiB with 4 KiB items, 1.20 x at 64 KiB with 16 KiB items. */
-/* known to BrotliMi355xCompressBatchWithDictionaries only; 4u and 256u stay unknown routes of this call */
+/* known to BrotliMi355xCompressBatchWithDictionaries and its device form only; 4u and 256u stay unknown routes of this call */
 #define BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS 512u
+/* known to BrotliMi355xCompressBatchWithDictionaries and its device form only, like 512u; may be combined with it (a call has one
+   quality, so at most one of the two takes items) */
+#define BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS 1024u
 int32_t BrotliMi355xCompressBatchWithDictionaries(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t num_dicts,
                                                   const uint8_t* const* dicts, const size_t* dict_sizes, size_t count,
                                                   const size_t* item_dicts /* may be NULL */, const uint8_t* const* inputs,
@@ -467,17 +500,17 @@ int32_t BrotliMi355xCompressBatchWithDictionaries(int quality, int lgwin, Brotli
    no size hint, NO fallback to a stored stream and no BrotliEncoderMaxCompressedSize cap (an item goes out if and only if its
    stream fits its capacity, otherwise it fails alone with size 0), a dictionary cut to its last (1 << lgwin) - 16 bytes, no
    dictionary taken with dict_sizes[k] <= 1 or at qualities 0 and 1.  The rules of the call are the host call's: `routes` knows
-   BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS only; item_dicts == NULL means item i takes dicts_device[i] and num_dicts must be
+   BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS and BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS only; item_dicts == NULL means item i takes dicts_device[i] and num_dicts must be
    count; any other route bit, an index >= num_dicts, or item_dicts == NULL with num_dicts != count fails the whole call before any
    work is done (returns 0, every size 0, only info[0] set, nothing written to device memory); when every item names one index the
-   call takes the shared-image path (the shared route of qualities 5 .. 8, with the bit the quick shared route), the dictionary
-   reaching its image by one copy on the device; BrotliMi355xLastBatchInfo means what it means for the host call and has the same
+   call takes the shared-image path (the shared route of qualities 5 .. 8, with the bit the quick shared route; the Zopfli route
+   of qualities 10 / 11 has no image and files a copy per chain), the dictionary reaching its image by one copy on the device; BrotliMi355xLastBatchInfo means what it means for the host call and has the same
    values on the same data; BrotliMi355xLastError carries "the reference encoder fails on this input" for the items that fail that way.
-   On the four side-by-side routes (info[1]) nothing crosses the bus: one launch per group reads every item and every dictionary
+   On the side-by-side routes (info[1]) nothing crosses the bus: one launch per group reads every item and every dictionary
    where it lies -- no page-locked staging, no dictionary pool, no upload -- and lays out dictionary | item per item on the device;
    one launch scatters the group's streams to their addresses.  Every other item -- the empty one, items longer than one input
-   block, other qualities or windows, dict_sizes[k] <= 1, more than 65 536 dictionary bytes in use, qualities 2 .. 4 without the bit
-   -- is downloaded, the bytes in use of the dictionary it names are downloaded once per call however many items name it, the item
+   block, other qualities or windows, dict_sizes[k] <= 1, more than 65 536 dictionary bytes in use, qualities 2 .. 4 and 10 / 11
+   without their bits -- is downloaded, the bytes in use of the dictionary it names are downloaded once per call however many items name it, the item
    runs through the stream path in the caller's order and its stream is uploaded if it fits: the same bytes and the same info as the
    host call, and no gain over it.  If every item of a call goes this way no dictionary is touched on the device but by these downloads.
    Memory contract.  The library reads only the aligned 4-byte words that hold at least one byte of an item or of the part of a

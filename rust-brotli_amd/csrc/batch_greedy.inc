@@ -407,6 +407,10 @@ void FinishOneBlockItems(const EncoderParams& p, const BatchParseJob& J, Group& 
     mbs[i].n_cmds = r.n_cmds;
     mbs[i].n_lits = r.n_lits;
     mbs[i].uncompressed = r.uncompressed;
+    // (the Zopfli chains behind a dictionary per item leave their dictionary's last two bytes in pad[0], every other chain 0: what
+    // the quality >= 10 UTF-8 census reads in front of the stream, EncodeBatchMetaBlocks)
+    mbs[i].prev_byte2 = (uint8_t)(r.pad[0] & 0xffu);
+    mbs[i].prev_byte = (uint8_t)((r.pad[0] >> 8) & 0xffu);
     total += r.n_cmds;
     if (r.bad_commands != 0 && reference_fails) (*reference_fails)[g.first + i] = 1;
   }
@@ -961,6 +965,74 @@ void BatchZopfliCompress(const EncoderParams& user, size_t count, const uint8_t*
     J.records = g.mem.uninit<BatchRecord>((size_t)g.n * sizeof(BatchRecord));
     lz77_zopfli_batch_parse(J);
     BatchParseJob G{};  // what the gather wants (GatherJobOf)
+    G.P = J.P;
+    G.slabs = J.slabs;
+    G.items = J.items;
+    G.n_items = J.n_items;
+    G.records = J.records;
+    FinishOneBlockItems(p, G, g, streams, reference_fails, sink);
+    first = g.last;
+  }
+}
+
+bool BatchZopfliDictionaryEligible(const EncoderParams& user, size_t dict_size, size_t input_size) {
+  if (input_size == 0 || input_size > ((size_t)1 << 16) || dict_size < 2) return false;
+  // (both qualities: through the stream API, which defines these items, quality 10 is a Zopfli walk as well)
+  if ((user.quality != 10 && user.quality != 11) || user.lgwin < 10 || user.lgwin > 24 || !PlainStreamParams(user)) return false;
+  // (dictionary in use + item stay inside the first lap of the ring buffer, 1 << (1 + max(lgwin, lgblock)), lgblock >= 16)
+  const EncoderParams p = DictionaryItemParams(user, input_size);
+  return p.hasher.type == 10 && input_size <= ((size_t)1 << p.lgblock) && std::min(dict_size, ((size_t)1 << p.lgwin) - 16) <= ((size_t)1 << 16);
+}
+
+// Qualities 10 and 11 behind a dictionary per item (batch_zopfli.h), items of one block: the steps of BatchZopfliCompress with the
+// pool step of CompressGroupsWithDictionaries (StageDictsText).  There is no tree image to share: every chain empties its hasher
+// and files its item's dictionary itself (br_zopfli_batch_prepend), also where every item names the same one.
+void BatchZopfliCompressWithDictionaries(const EncoderParams& user, size_t count, const uint8_t* const* dicts, const size_t* dict_sizes,
+                                         const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
+                                         std::vector<uint8_t>* reference_fails, uint32_t* groups, const BatchDeviceSink* sink) {
+  streams->assign(count, std::vector<uint8_t>());
+  reference_fails->assign(count, 0);
+  *groups = 0;
+  if (count == 0) return;
+  const EncoderParams p = DictionaryItemParams(user, sizes[0]);  // (nothing in the parameters differs between items of at most one block)
+  for (size_t i = 0; i < count; ++i)
+    if (dict_sizes[i] < 2 || dict_sizes[i] > ((size_t)1 << 16) || dict_sizes[i] > ((size_t)1 << p.lgwin) - 16)
+      throw std::runtime_error("brotli_mi355x: a dictionary the Zopfli batch chains do not take");
+  // the measured alternative of the wave-wide prepend (profiles/r27_batch_dictionaries_zopfli.json), read once per process
+  static const bool prepend_lane0 = EnvSize("BROTLI_MI355X_ZOPFLI_PREPEND_LANE0", 0) != 0;
+  ZopfliBatchJob chains{};
+  chains.P = ChainParams(p);
+  chains.P.hasher_kind = 6;  // (as BatchZopfliCompress)
+  chains.quality = (uint32_t)p.quality;
+  chains.lgwin = (uint32_t)p.lgwin;
+  chains.use_dictionary = 0;  // (no static dictionary behind a custom one)
+  chains.dist_alphabet_size = p.dist.alphabet_size;
+  chains.prepend_lane0 = prepend_lane0 ? 1 : 0;
+  CallArrays A;
+  size_t first = 0;
+  while (first < count) {
+    Group g;
+    StageGroup(first, count, inputs, sizes, DictSizes(dict_sizes, sink ? dicts : nullptr), kZopfliBatchResident, &A, &g, kBatchHqGroupItems, sink != nullptr);
+    ++*groups;
+    const DictsText staged = StageDictsText(g, dicts, dict_sizes);
+    // (the order is by dictionary + item, which sizes the forest; everything else hangs on the largest item)
+    uint32_t largest_item = 0;
+    for (uint32_t i = 0; i < g.n; ++i) largest_item = std::max(largest_item, A.items[i].bytes);
+    ZopfliBatchJob J = chains;
+    zopfli_batch_layout(&J, largest_item, A.dict_bytes[A.order[0]] + A.items[A.order[0]].bytes);
+    g.tables = (uint32_t)std::min<size_t>(std::min<size_t>(kZopfliBatchResident, TablesMax(J.table_bytes)), g.n);
+    J.table_mem = g.mem.uninit<uint8_t>((size_t)g.tables * J.table_bytes + 256);
+    J.text = staged.text;
+    J.item_dict_bytes = staged.dict_bytes_dev;
+    J.slabs = g.mem.uninit<Command>(g.cmd_slots * sizeof(Command) + 64);
+    J.items = g.items_dev;
+    J.order = g.order_dev;
+    J.n_items = g.n;
+    J.tables = g.tables;
+    J.counter = g.mem.zeroed<uint32_t>(64);
+    J.records = g.mem.uninit<BatchRecord>((size_t)g.n * sizeof(BatchRecord));
+    lz77_zopfli_batch_parse_dicts(J);
+    BatchParseJob G{};  // what the gather wants (GatherJobOf); the raw commands carry distances, so it needs no D
     G.P = J.P;
     G.slabs = J.slabs;
     G.items = J.items;

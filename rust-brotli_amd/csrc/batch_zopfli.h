@@ -15,6 +15,7 @@
 // Memory of a table, sized by the group's largest item rounded up to 64 bytes (cap), every part on a 256-byte boundary:
 //   buckets        4 << 17                         (512 KiB)
 //   forest         8 * min(cap, 1 << lgwin)        only the slots 2 * (pos & window mask) of the item's positions are touched
+//                  (behind a dictionary per item: 8 * min(largest dictionary + item rounded up to 64, 1 << lgwin))
 //   nodes          20 * (cap + 2)
 //   literal costs  4 * (cap + 4)
 //   cost tables    4 * (dist alphabet + 64) + 4 * 704, histograms 4 * 2048
@@ -57,16 +58,25 @@ struct ZopfliBatchJob {
   uint32_t* counter;  // [1], zero: the next place of `order` to hand out
   BatchRecord* records;
   uint8_t* table_mem;  // [tables][table_bytes], 256-byte aligned
+  // a dictionary per item (k_zopfli_batch_dicts): `text` is the staged text, dictionary | item per item, and item i's dictionary
+  // is the item_dict_bytes[i] bytes that end where the item starts.  nullptr: no dictionaries (k_zopfli_batch)
+  const uint32_t* item_dict_bytes;  // [n_items], device
+  uint32_t prepend_lane0;           // the dictionary goes into the trees on lane 0 alone (the measured alternative), not wave-wide
   // the layout of a table (zopfli_batch_layout): byte offsets, multiples of 256
-  uint32_t cap;  // the group's largest item rounded up to 64
+  uint32_t cap;   // the group's largest item rounded up to 64
+  uint32_t span;  // the positions the forest has slots for: the group's largest dictionary + item rounded up to 64, at most 1 << lgwin
   size_t table_bytes;
   size_t off_forest, off_nodes, off_literal_costs, off_cost_dist, off_cost_cmd, off_histo, off_matches, off_num_matches, off_tmp_cmds,
       off_ctl, off_exit;
 };
-// fills in cap, the offsets and table_bytes from lgwin, dist_alphabet_size and the largest item of the group
-inline void zopfli_batch_layout(ZopfliBatchJob* J, uint32_t largest_item) {
+// fills in cap, span, the offsets and table_bytes from lgwin, dist_alphabet_size and the largest item of the group.  largest_text:
+// the group's largest dictionary + item where the items lie behind dictionaries of their own -- the forest alone grows with it,
+// everything else is indexed by the position inside the item; 0: no dictionaries, the largest item.
+inline void zopfli_batch_layout(ZopfliBatchJob* J, uint32_t largest_item, uint32_t largest_text = 0) {
   const size_t cap = ((size_t)largest_item + 63) & ~(size_t)63;
   const size_t window = (size_t)1 << J->lgwin;
+  const size_t text = largest_text ? ((size_t)largest_text + 63) & ~(size_t)63 : cap;
+  const size_t span = text < window ? text : window;
   size_t at = 0;
   auto take = [&](size_t bytes) {
     const size_t here = at;
@@ -74,8 +84,9 @@ inline void zopfli_batch_layout(ZopfliBatchJob* J, uint32_t largest_item) {
     return here;
   };
   J->cap = (uint32_t)cap;
+  J->span = (uint32_t)span;
   take((size_t)4 << 17);  // buckets, at 0
-  J->off_forest = take(8 * (cap < window ? cap : window));
+  J->off_forest = take(8 * span);
   J->off_nodes = take(20 * (cap + 2));
   J->off_literal_costs = take(4 * (cap + 4));
   J->off_cost_dist = take(4 * ((size_t)J->dist_alphabet_size + 64));
@@ -91,6 +102,9 @@ inline void zopfli_batch_layout(ZopfliBatchJob* J, uint32_t largest_item) {
 // one wavefront per table; a wavefront takes items from `counter` until none is left.  BatchRecord::bad_commands flags the items
 // the reference encoder panics on (kZopfliReferencePanics).  The gather is lz77_batch_gather.
 void lz77_zopfli_batch_parse(const ZopfliBatchJob& J);
+// ... behind a dictionary per item (J.item_dict_bytes): every chain empties its hasher, files its item's dictionary wave-wide
+// (br_zopfli_batch_prepend), stitches and walks the item from position D
+void lz77_zopfli_batch_parse_dicts(const ZopfliBatchJob& J);
 
 // ---- host
 // Does this item go side by side under the Zopfli route?  `params`: the caller's parameters as set, not finalized.
@@ -100,6 +114,16 @@ bool BatchZopfliEligible(const EncoderParams& params, size_t input_size);
 void BatchZopfliCompress(const EncoderParams& params, size_t count, const uint8_t* const* inputs, const size_t* sizes,
                          std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* reference_fails, uint32_t* groups,
                          const BatchDeviceSink* sink = nullptr);
+
+// BrotliMi355xCompressBatchWithDictionaries under BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS: qualities 10 AND 11 -- an
+// item is the stream of BrotliEncoderSetCustomDictionary + one FINISH, and the stream API runs both as Zopfli.  Does this item go
+// side by side?  dict_size: the dictionary as handed in (the reference cuts it to its last (1 << lgwin) - 16 bytes).
+bool BatchZopfliDictionaryEligible(const EncoderParams& params, size_t dict_size, size_t input_size);
+// The streams of `count` eligible items; dicts[i] / dict_sizes[i]: the dictionary of item i as in use.  A table's forest is sized
+// by the group's largest dictionary + item (8 bytes per position, at most 8 << lgwin), everything else as above.
+void BatchZopfliCompressWithDictionaries(const EncoderParams& params, size_t count, const uint8_t* const* dicts, const size_t* dict_sizes,
+                                         const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
+                                         std::vector<uint8_t>* reference_fails, uint32_t* groups, const BatchDeviceSink* sink = nullptr);
 
 }  // namespace brotli_mi355x
 #endif

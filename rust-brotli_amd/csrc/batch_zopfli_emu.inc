@@ -9,7 +9,8 @@
 
 namespace brotli_mi355x {
 
-void lz77_zopfli_batch_parse(const ZopfliBatchJob& J) {
+namespace {
+void zopfli_batch_emu(const ZopfliBatchJob& J, bool dicts) {
   if (J.n_items == 0) return;
   if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
   const DeviceTables& dt = dev_tables();
@@ -22,8 +23,22 @@ void lz77_zopfli_batch_parse(const ZopfliBatchJob& J) {
   T.logs.logs_16 = dt.logs_16;
   T.logs.logs_8 = dt.logs_8;
   uint32_t histo[256];
-  for (uint32_t place = 0; place < J.n_items; ++place) br_zopfli_batch_item(J, T, histo, ZFast(), J.order[place], place % J.tables);
+  for (uint32_t place = 0; place < J.n_items; ++place) {
+    if (dicts)
+      br_zopfli_batch_item<true>(J, T, histo, ZFast(), J.order[place], place % J.tables);
+    else
+      br_zopfli_batch_item(J, T, histo, ZFast(), J.order[place], place % J.tables);
+  }
   *J.counter = J.n_items;
+}
+}  // namespace
+
+void lz77_zopfli_batch_parse(const ZopfliBatchJob& J) { zopfli_batch_emu(J, false); }
+
+// (the scalar build of br_zopfli_batch_prepend runs the 64 key classes of the wave-wide partition one after the other)
+void lz77_zopfli_batch_parse_dicts(const ZopfliBatchJob& J) {
+  if (J.n_items != 0 && J.item_dict_bytes == nullptr) throw std::runtime_error("brotli_mi355x: a dictionary batch group without its dictionary sizes");
+  zopfli_batch_emu(J, true);
 }
 
 }  // namespace brotli_mi355x

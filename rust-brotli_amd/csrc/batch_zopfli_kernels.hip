@@ -33,7 +33,26 @@ __global__ __launch_bounds__(64) void k_zopfli_batch(ZopfliBatchJob J, ZopfliTab
   for (uint32_t index; br_batch_next_index(J.counter, J.order, J.n_items, index);) br_zopfli_batch_item(J, T, histo, fast, index, table);
 }
 
-void lz77_zopfli_batch_parse(const ZopfliBatchJob& J) {
+// The same behind a dictionary per item (br_zopfli_batch_item<true>): an instance of its own, so that k_zopfli_batch carries none
+// of the dictionary steps.  Launch shape and workgroup memory are those of k_zopfli_batch.
+__global__ __launch_bounds__(64) void k_zopfli_batch_dicts(ZopfliBatchJob J, ZopfliTables T) {
+  __shared__ ZNode window[kZWin];
+  __shared__ float lc_window[kZWin];
+  __shared__ float cost_cmd[704], cost_dist[1200];
+  __shared__ ZQueue queue;
+  __shared__ uint32_t histo[256];
+  const uint32_t table = blockIdx.x;
+  if (table >= J.tables) return;
+  ZFast fast;
+  fast.window = window;
+  fast.lc_window = lc_window;
+  fast.cost_cmd = cost_cmd;
+  fast.cost_dist = J.dist_alphabet_size <= 1136 ? cost_dist : (float*)nullptr;
+  fast.queue = &queue;
+  for (uint32_t index; br_batch_next_index(J.counter, J.order, J.n_items, index);) br_zopfli_batch_item<true>(J, T, histo, fast, index, table);
+}
+
+static void zopfli_batch_launch(const ZopfliBatchJob& J, bool dicts) {
   if (J.n_items == 0) return;
   if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
   const DeviceTables& dt = dev_tables();
@@ -46,8 +65,18 @@ void lz77_zopfli_batch_parse(const ZopfliBatchJob& J) {
   T.logs.logs_16 = dt.logs_16;
   T.logs.logs_8 = dt.logs_8;
   const uint32_t grid = J.tables < J.n_items ? J.tables : J.n_items;
-  hipLaunchKernelGGL(k_zopfli_batch, dim3(grid), dim3(64), 0, BR_STREAM, J, T);
+  if (dicts)
+    hipLaunchKernelGGL(k_zopfli_batch_dicts, dim3(grid), dim3(64), 0, BR_STREAM, J, T);
+  else
+    hipLaunchKernelGGL(k_zopfli_batch, dim3(grid), dim3(64), 0, BR_STREAM, J, T);
   HIP_CHECK(hipGetLastError());
+}
+
+void lz77_zopfli_batch_parse(const ZopfliBatchJob& J) { zopfli_batch_launch(J, false); }
+
+void lz77_zopfli_batch_parse_dicts(const ZopfliBatchJob& J) {
+  if (J.n_items != 0 && J.item_dict_bytes == nullptr) throw std::runtime_error("brotli_mi355x: a dictionary batch group without its dictionary sizes");
+  zopfli_batch_launch(J, true);
 }
 
 }  // namespace brotli_mi355x

@@ -1164,7 +1164,13 @@ void EncodeBatchMetaBlocks(const EncoderParams& p, const uint8_t* text, const Co
         d.prev_byte = items[m].prev_byte;
         d.prev_byte2 = items[m].prev_byte2;
       }
-      if (!items[m].follows) d.census_floor = d.start;  // (quality >= 10: the UTF-8 census must not see the neighbour in front either)
+      if (!items[m].follows) {
+        d.census_floor = d.start;  // (quality >= 10: the UTF-8 census must not see the neighbour in front either)
+        // ... but it does see the end of a custom dictionary, which lies in the reference's ring buffer in front of the stream: on
+        // an item's first entry prev_byte / prev_byte2 are the dictionary's last two bytes (0: none, or zeros -- the same census).
+        // The literal contexts above stay 0: the reference sets prev_byte only behind a written meta-block.
+        d.census_lead = (uint32_t)items[m].prev_byte2 | ((uint32_t)items[m].prev_byte << 8);
+      }
       d.num_distance_symbols = p.dist.alphabet_size;
       d.dist_postfix_bits = p.dist.distance_postfix_bits;
       d.num_direct_distance_codes = p.dist.num_direct_distance_codes;

@@ -1079,7 +1079,9 @@ BR_DEV void hq_item_distance_params(const MbBuffers& B, uint32_t m, HqWaveScratc
 // front of the stream read the zeroed slack).  Result: MbResult::hq_mostly_utf8.
 BR_DEV uint32_t hq_census_byte(const MbBuffers& B, const MbDesc& d, uint32_t i) {
   const uint32_t p = d.start + i;  // the reference reads data_mo[p] = ring[p - 2] (a custom dictionary lies in the ring too)
-  return p >= d.census_floor + 2 ? B.text[p - 2] : 0u;  // (census_floor: where the meta-block's own stream starts in the text)
+  if (p >= d.census_floor + 2) return B.text[p - 2];  // (census_floor: where the meta-block's own stream starts in the text)
+  // a batch item behind a custom dictionary of its own: the text holds the items back to back, the dictionary's end travels in the descriptor
+  return p >= d.census_floor ? (d.census_lead >> (8u * (p - d.census_floor))) & 0xffu : 0u;
 }
 // BrotliParseAsUTF8 (utf8_util.rs:3-43) at offset i of a census of `length` bytes: bytes consumed, and whether they count
 // as UTF-8 (symbol < 0x110000).  Returns bytes | valid << 3.

@@ -65,6 +65,8 @@ struct MbDesc {
   uint32_t simple;              // 0: greedy splitter (quality >= 4); 1 / 2: the one-block-type writers of quality 3 / 2 (metablock_fast.h)
   uint32_t census_floor;        // quality >= 10: the stream the meta-block belongs to starts at this text position (0: the text is one
                                 // stream; a batch group: the item's start) -- the UTF-8 census reads zeros in front of it
+  uint32_t census_lead;         // ... unless a custom dictionary lies in front of a batch item's stream: its last two bytes, the one
+                                // before last in bits 0 .. 7 and the last in bits 8 .. 15, which the census reads there (0: zeros)
 };
 
 // Results of the greedy splitters and the header pass, one per meta-block.

@@ -12,6 +12,27 @@
 
 #include "device_api.h"
 #include "zopfli_entry_api.h"
+#if defined(BROTLI_HOST_EMU)
+#include "batch_zopfli_device.h"
+
+namespace brotli_mi355x {
+// the scalar twin of k_zdebug_prepend (zopfli_entry_kernels.hip): the same two functions on plain memory; mode 1 walks the 64
+// key classes of the wave-wide partition one after the other
+void zopfli_debug_prepend(const uint8_t* text, uint32_t dict_bytes, uint32_t lgwin, uint32_t mode, uint32_t* buckets, uint32_t* forest) {
+  ZopfliParams Z{};
+  Z.quality = 11;
+  Z.lgwin = lgwin;
+  Z.max_backward_limit = (1u << lgwin) - 16u;
+  Z.ring_mask = 0xffffffffu;
+  Z.dict_break = dict_bytes;
+  ZopfliBuffers B{};
+  B.buckets = buckets;
+  B.forest = forest;
+  br_zopfli_batch_reset(B, lgwin, dict_bytes);
+  br_zopfli_batch_prepend(z_hasher_of(Z, B), Z, text, dict_bytes, mode == 0);
+}
+}  // namespace brotli_mi355x
+#endif
 
 using namespace brotli_mi355x;
 
@@ -137,6 +158,33 @@ int brotli_mi355x_debug_cost_from_histogram(uint32_t n_jobs, const uint32_t* siz
     dev_h2d(histograms_dev, histograms, total * 4);
     zopfli_debug_cost_from_histogram(n_jobs, sizes_dev, literal_dev, offsets_dev, histograms_dev, cost_dev);
     dev_d2h(out_cost_bits, cost_dev, total * 4);
+    return 0;
+  } catch (const std::exception&) {
+    return -2;
+  }
+}
+
+// HasherPrependCustomDictionary for H10 as the batch item of qualities 10 / 11 runs it (batch_zopfli_device.h), on a hasher that
+// br_zopfli_batch_reset has emptied: the first dict_bytes bytes of `text` are the dictionary (n_text >= dict_bytes: a Store
+// compares bytes of the dictionary only, what follows is carried along as the item would be).  mode 0: the loop of k_zopfli_prepend
+// on lane 0; mode 1: the batch item's wave-wide partition on one wavefront.  Out: the buckets (1 << 17 words) and the forest, 2
+// words for each of min(dict_bytes rounded up to 64, 1 << lgwin) positions.  Refused: mode > 1, lgwin outside 10 .. 24,
+// dict_bytes > n_text or > (1 << lgwin) - 16, more than 16 MiB of text.
+int brotli_mi355x_debug_zopfli_prepend(const uint8_t* text, uint32_t n_text, uint32_t dict_bytes, uint32_t lgwin, uint32_t mode, uint32_t* out_buckets,
+                                       uint32_t* out_forest) {
+  if (mode > 1 || lgwin < 10 || lgwin > 24 || !text || !out_buckets || !out_forest) return -1;
+  if (n_text == 0 || n_text > (16u << 20) || dict_bytes > n_text || dict_bytes > (1u << lgwin) - 16u) return -1;
+  const size_t rounded = ((size_t)dict_bytes + 63) & ~(size_t)63;
+  const size_t slots = rounded < ((size_t)1 << lgwin) ? rounded : ((size_t)1 << lgwin);
+  try {
+    DevMem mm;
+    uint8_t* text_dev = mm.alloc<uint8_t>((size_t)n_text + kZEntryTextPadding);  // (zero-filled)
+    uint32_t* buckets_dev = mm.alloc<uint32_t>((size_t)1 << 17);
+    uint32_t* forest_dev = mm.alloc<uint32_t>(2 * slots + 64);
+    dev_h2d(text_dev, text, n_text);
+    zopfli_debug_prepend(text_dev, dict_bytes, lgwin, mode, buckets_dev, forest_dev);
+    dev_d2h(out_buckets, buckets_dev, ((size_t)1 << 17) * 4);
+    if (slots) dev_d2h(out_forest, forest_dev, 2 * slots * 4);
     return 0;
   } catch (const std::exception&) {
     return -2;

@@ -26,5 +26,11 @@ void zopfli_debug_literal_costs(uint32_t n_jobs, const uint32_t* lengths, const 
 void zopfli_debug_cost_from_histogram(uint32_t n_jobs, const uint32_t* sizes, const uint32_t* literal, const unsigned long long* offsets,
                                       const uint32_t* histograms, float* cost);
 
+// ---- the custom-dictionary prepend of the batch item at qualities 10 / 11 (batch_zopfli_device.h; tests/test_batch_dictionaries_zopfli.py)
+// one 64-lane workgroup: br_zopfli_batch_reset over dict_bytes positions, then br_zopfli_batch_prepend of text[0, dict_bytes) --
+// mode 0 the loop of k_zopfli_prepend on lane 0, mode 1 the wave-wide partition of the batch item -- on buckets [1 << 17] and
+// forest [2 * forest slots], forest slots = min(dict_bytes rounded up to 64, 1 << lgwin)
+void zopfli_debug_prepend(const uint8_t* text, uint32_t dict_bytes, uint32_t lgwin, uint32_t mode, uint32_t* buckets, uint32_t* forest);
+
 }  // namespace brotli_mi355x
 #endif

@@ -3,6 +3,7 @@
 // product's own path goes through here.
 #include <hip/hip_runtime.h>
 
+#include "batch_zopfli_device.h"
 #include "device_api.h"
 #include "device_scan.h"
 #include "zopfli_device.h"
@@ -104,6 +105,31 @@ void zopfli_debug_cost_from_histogram(uint32_t n_jobs, const uint32_t* sizes, co
   if (n_jobs == 0) return;
   hipLaunchKernelGGL(k_zdebug_cost_from_histogram, dim3((n_jobs + 63) / 64), dim3(64), 0, BR_STREAM, zopfli_entry_tables(), n_jobs, sizes, literal,
                      offsets, histograms, cost);
+  HIP_CHECK(hipGetLastError());
+}
+
+// the hasher and the parameters the prepend looks at (a Store compares 128 bytes inside the dictionary: nothing else matters)
+static ZopfliParams zopfli_entry_prepend_params(uint32_t dict_bytes, uint32_t lgwin) {
+  ZopfliParams Z{};
+  Z.quality = 11;
+  Z.lgwin = lgwin;
+  Z.max_backward_limit = (1u << lgwin) - 16u;
+  Z.ring_mask = 0xffffffffu;
+  Z.dict_break = dict_bytes;
+  return Z;
+}
+__global__ __launch_bounds__(64) void k_zdebug_prepend(ZopfliParams Z, const uint8_t* __restrict__ text, uint32_t dict_bytes, uint32_t mode,
+                                                       uint32_t* buckets, uint32_t* forest) {
+  if (blockIdx.x != 0) return;
+  ZopfliBuffers B{};
+  B.buckets = buckets;
+  B.forest = forest;
+  br_zopfli_batch_reset(B, Z.lgwin, dict_bytes);
+  br_zopfli_batch_prepend(z_hasher_of(Z, B), Z, text, dict_bytes, mode == 0);
+}
+void zopfli_debug_prepend(const uint8_t* text, uint32_t dict_bytes, uint32_t lgwin, uint32_t mode, uint32_t* buckets, uint32_t* forest) {
+  hipLaunchKernelGGL(k_zdebug_prepend, dim3(1), dim3(64), 0, BR_STREAM, zopfli_entry_prepend_params(dict_bytes, lgwin), text, dict_bytes, mode, buckets,
+                     forest);
   HIP_CHECK(hipGetLastError());
 }
 
