@@ -357,9 +357,11 @@ int32_t BrotliMi355xCompressBatchEx(int quality, int lgwin, BrotliEncoderMode mo
 int32_t BrotliMi355xCompressBatchDevice(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t count,
                                         const uint8_t* const* inputs_device, const size_t* input_sizes, uint8_t* const* outputs_device,
                                         size_t* output_sizes /* in: capacity, out: size */, int32_t* item_results /* may be NULL */);
-/* BrotliMi355xCompressBatchWithDictionary with routes the caller opts into.  routes == 0 is that call in every respect.  The only
-   route this call knows is BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS; any other bit -- the other routes of
-   BrotliMi355xCompressBatchEx and the reserved values 2, 8 and 64 included -- fails the whole call as an unknown route fails that one
+/* BrotliMi355xCompressBatchWithDictionary with routes the caller opts into.  routes == 0 is that call in every respect.  The
+   routes this call knows are BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS (4) and BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS (4096,
+   defined and described with BrotliMi355xCompressBatchWithDictionaries below); they may be combined, and since a call has one
+   quality at most one of them takes items.  Any other bit -- the other routes of BrotliMi355xCompressBatchEx and the reserved
+   values 2, 8 and 64 included -- fails the whole call as an unknown route fails that one
    (returns 0, every size 0, BrotliMi355xLastError says so, only info[0] of BrotliMi355xLastBatchInfo is set).
    BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS: item i is still exactly the stream of BrotliEncoderSetCustomDictionary + one
    BrotliEncoderCompressStream(BROTLI_OPERATION_FINISH), by the rules above -- in bytes, size, success or failure.  In addition
@@ -400,11 +402,11 @@ int32_t BrotliMi355xCompressBatchWithDictionaryEx(int quality, int lgwin, Brotli
    item_dicts == NULL: item i takes dicts[i], and num_dicts must be count.  Several items may name one index.  Dictionaries are
    told apart by index, not by content.  dicts[k] may be NULL when dict_sizes[k] is 0.  count == 0 returns 1.
    An index >= num_dicts, item_dicts == NULL with num_dicts != count, or any bit in routes other than
-   BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS and BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS fails the whole call
-   before any work is done, as an unknown route fails BrotliMi355xCompressBatchEx (returns 0, every size 0, BrotliMi355xLastError
+   BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS, BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS and
+   BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS fails the whole call before any work is done, as an unknown route fails BrotliMi355xCompressBatchEx (returns 0, every size 0, BrotliMi355xLastError
    says why, only info[0] of BrotliMi355xLastBatchInfo is set).  routes == 0 is the call as described below in every respect.
-   The two routes this call knows, so a caller can probe; they may be combined, and since a call has one quality at most one of
-   them takes items.
+   The three routes this call knows, so a caller can probe; they may be combined, and since a call has one quality at most one
+   of them takes items.
    BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS (512; the bits of the other batch calls, 4 and 256 among them, stay unknown
    here, and 512 stays unknown there): item i is still exactly the stream described above.  In addition to the items the call
    takes side by side without it, an item of at most one input block at quality 2, 3 or 4 and lgwin 10 .. 24 -- 1 <=
@@ -459,6 +461,36 @@ int32_t BrotliMi355xCompressBatchWithDictionaryEx(int quality, int lgwin, Brotli
    85 / 155 .. 156 ms, 11 .. 12 x faster than without the bit and still LOSE to one CPU core (29 / 61 ms, 0.34 / 0.39 x).  No
    measured shape loses to the call without the bit or to the four-thread loop.  (The wave-wide filing against lane 0 filing the
    dictionary alone inside the same kernel: 1.04 .. 1.08 x faster with 16 KiB dictionaries, 1.32 .. 1.47 x with 64 KiB.)
+   BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS (4096; known to this call, its device form and
+   BrotliMi355xCompressBatchWithDictionaryEx; an unknown route of BrotliMi355xCompressBatchEx and BrotliMi355xCompressBatchDevice; 2048
+   is no route of any call): item i is still exactly the stream described above, at quality 9 -- the strongest greedy level, for
+   (old version, new file) pairs where the Zopfli qualities are too slow.  An item of 1 <= input_sizes[i] <= 65 536 bytes at quality
+   9 and lgwin 17 .. 24 behind a dictionary of dict_sizes[k] >= 2 of which at most 65 536 bytes are in use (min(dict_sizes[k],
+   (1 << lgwin) - 16)) runs on the device as ONE wavefront: a live chain on a private H9 table (64 KiB of ring counters, 32 MiB of
+   rings 256 deep; at most 255 tables, 8 GiB, per group) that empties the counters, files its item's dictionary wave-wide in the
+   reference's order, stitches, and parses dictionary | item from position D.  Dictionary + item stay inside the first half of the
+   smallest ring buffer of these windows, so the chain meets neither a masked position nor H9's ring-end case.  When every item
+   names one index -- and in BrotliMi355xCompressBatchWithDictionaryEx, where there is one dictionary -- the chains replay one image
+   of the dictionary, made once per call, instead of filing it (same bytes; equal info between the two calls).  Every other item --
+   the empty one, longer items, dict_sizes[k] <= 1, more than 65 536 bytes in use, lgwin <= 16 -- runs by itself through the stream
+   path.  Without the bit quality 9 runs one by one as before; the bit changes nothing at qualities 0 .. 8, 10 and 11.  Such items
+   count in info[1], their groups in info[4]; info[2], info[5] as below; info[6] and info[7] stay 0.  An item on which the
+   reference fails (a match cut to one byte at the dictionary's end: "the reference encoder fails on this input") fails alone,
+   11 of 4000 drawn pairs; so does one whose stream does not fit; a device error fails the call.
+   When to set it: dozens to thousands of small items at quality 9.  Measured (text, lgwin 22, every item behind a dictionary
+   of its own, min .. max of five alternating rounds; profiles/r28_batch_dictionaries_q9.json; the one-by-one baselines timed on 32
+   items and scaled): 4096 items of 4 KiB behind 16 KiB each in 108 .. 109 ms against 5.8 .. 6.2 s for the same call without the
+   bit (the parent build), 5.2 .. 6.4 s for the loop of stream calls from four threads and 10.7 s on one CPU core; 1024 items of
+   16 KiB behind 64 KiB each in 108 .. 109 ms against 1.41 .. 1.48 s (loop 1.13 .. 1.39 s, one core 4.4 s); 256 items of 64 KiB
+   behind 64 KiB each in 115 .. 116 ms against 388 .. 406 ms (loop 304 .. 375 ms, one core 1.6 s); 64 items of 4 KiB behind 16 KiB
+   each in 6.4 .. 6.5 ms against 83 .. 89 ms; 16 of them in 6.3 .. 6.4 ms against 21 .. 22 ms (one core 42 ms).  Behind ONE shared
+   16 KiB dictionary 4096 items of 4 KiB take 86 .. 88 ms with the image and 105 .. 107 ms with every chain filing it
+   (BROTLI_MI355X_BATCH_DICT_SELF_FILE=1): the image is 1.22 x faster.
+   When not: a call of a few items -- a chain is one wavefront and lasts its item's time however many run beside it, about 6 ms
+   for 4 KiB behind 16 KiB.  4 such items take 6.2 .. 6.3 ms and LOSE to the call without the bit (5.2 .. 5.5 ms, 0.84 x); 1 item
+   takes 6.1 .. 6.2 ms against 1.3 .. 1.4 ms (0.21 x) and loses to one CPU core as well (2.7 ms, 0.44 x).  Few long items lose too:
+   16 items of 64 KiB behind 64 KiB each take 65 .. 66 ms against 23 .. 25 ms without the bit (0.36 x) and 28 .. 34 ms for the
+   four-thread loop (0.47 x).  The break-even lies between 4 and 16 items of 4 KiB, and between 16 and 256 items of 64 KiB.
    Side by side on the device: quality 5 .. 8, lgwin 17 .. 24, 2 <= D_i <= 65536 (the bytes of the item's dictionary in use) and
    1 <= input_sizes[i] <= 65536.  A group uploads its items and, once each, the dictionaries they name; the text
    dictionary | item is laid out on the device per item, and one chain per item files the dictionary into a private hash table and
@@ -484,6 +516,9 @@ int32_t BrotliMi355xCompressBatchWithDictionaryEx(int quality, int lgwin, Brotli
 /* known to BrotliMi355xCompressBatchWithDictionaries and its device form only, like 512u; may be combined with it (a call has one
    quality, so at most one of the two takes items) */
 #define BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS 1024u
+/* known to BrotliMi355xCompressBatchWithDictionaryEx, BrotliMi355xCompressBatchWithDictionaries and its device form; an unknown
+   route of BrotliMi355xCompressBatchEx and BrotliMi355xCompressBatchDevice.  (2048u is taken by no route and stays unknown.) */
+#define BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS 4096u
 int32_t BrotliMi355xCompressBatchWithDictionaries(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t num_dicts,
                                                   const uint8_t* const* dicts, const size_t* dict_sizes, size_t count,
                                                   const size_t* item_dicts /* may be NULL */, const uint8_t* const* inputs,
@@ -500,16 +535,16 @@ int32_t BrotliMi355xCompressBatchWithDictionaries(int quality, int lgwin, Brotli
    no size hint, NO fallback to a stored stream and no BrotliEncoderMaxCompressedSize cap (an item goes out if and only if its
    stream fits its capacity, otherwise it fails alone with size 0), a dictionary cut to its last (1 << lgwin) - 16 bytes, no
    dictionary taken with dict_sizes[k] <= 1 or at qualities 0 and 1.  The rules of the call are the host call's: `routes` knows
-   BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS and BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS only; item_dicts == NULL means item i takes dicts_device[i] and num_dicts must be
+   BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS, BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS and BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS only; item_dicts == NULL means item i takes dicts_device[i] and num_dicts must be
    count; any other route bit, an index >= num_dicts, or item_dicts == NULL with num_dicts != count fails the whole call before any
    work is done (returns 0, every size 0, only info[0] set, nothing written to device memory); when every item names one index the
-   call takes the shared-image path (the shared route of qualities 5 .. 8, with the bit the quick shared route; the Zopfli route
-   of qualities 10 / 11 has no image and files a copy per chain), the dictionary reaching its image by one copy on the device; BrotliMi355xLastBatchInfo means what it means for the host call and has the same
+   call takes the shared-image path (the shared route of qualities 5 .. 8, with their bits the quick shared route and the shared
+   route of quality 9; the Zopfli route of qualities 10 / 11 has no image and files a copy per chain), the dictionary reaching its image by one copy on the device; BrotliMi355xLastBatchInfo means what it means for the host call and has the same
    values on the same data; BrotliMi355xLastError carries "the reference encoder fails on this input" for the items that fail that way.
    On the side-by-side routes (info[1]) nothing crosses the bus: one launch per group reads every item and every dictionary
    where it lies -- no page-locked staging, no dictionary pool, no upload -- and lays out dictionary | item per item on the device;
    one launch scatters the group's streams to their addresses.  Every other item -- the empty one, items longer than one input
-   block, other qualities or windows, dict_sizes[k] <= 1, more than 65 536 dictionary bytes in use, qualities 2 .. 4 and 10 / 11
+   block, other qualities or windows, dict_sizes[k] <= 1, more than 65 536 dictionary bytes in use, qualities 2 .. 4, 9 and 10 / 11
    without their bits -- is downloaded, the bytes in use of the dictionary it names are downloaded once per call however many items name it, the item
    runs through the stream path in the caller's order and its stream is uploaded if it fits: the same bytes and the same info as the
    host call, and no gain over it.  If every item of a call goes this way no dictionary is touched on the device but by these downloads.

@@ -200,6 +200,7 @@ class Library(object):
     BATCH_ROUTE_Q9_ITEMS = 128  # BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS (64 is reserved)
     BATCH_ROUTE_QUICK_DICTIONARY_ITEMS = 512  # BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS (compress_batch_with_dictionaries only)
     BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS = 1024  # BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS (compress_batch_with_dictionaries only)
+    BATCH_ROUTE_Q9_DICTIONARY_ITEMS = 4096  # BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS (the dictionary calls, shared and per item; 2048 is no route)
 
     def compress_batch(self, items, quality=0, lgwin=22, mode=0, dictionary=None, long_items=False, quick_items=False, quick_long_items=False,
                        zopfli_items=False, q9_items=False):
@@ -307,7 +308,7 @@ class Library(object):
             raise e
         return streams
 
-    def compress_batch_with_dictionary(self, items, dictionary, quality=5, lgwin=22, mode=0, quick_items=False):
+    def compress_batch_with_dictionary(self, items, dictionary, quality=5, lgwin=22, mode=0, quick_items=False, q9_items=False):
         """BrotliMi355xCompressBatchWithDictionaryEx: every item is the stream of an Encoder(params, dictionary) that gets the item
         in one finish(), as compress_batch(..., dictionary=dictionary) gives it; a decoder needs the same dictionary.  Returns a
         list of bytes.
@@ -320,6 +321,12 @@ class Library(object):
         bytes).  Without it these qualities run item by item; longer items and the empty item still do.  It pays with hundreds of
         small items of one kind in a call, not with a few: a chain is one wavefront.
 
+        q9_items=True: BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS -- at quality 9 and lgwin 17 to 24 the items of 1 to 65 536
+        bytes behind a dictionary of at least 2 bytes, of which at most 65 536 are in use, run side by side, one chain each on a
+        private H9 hash table of 32 MiB over which it replays the dictionary's image (the same bytes).  Without it quality 9 runs
+        item by item; longer items and the empty item still do.  It changes nothing at the other qualities and may be combined
+        with quick_items.  A chain lasts its item's time however many run beside it: see include/brotli_mi355x.h for when it pays.
+
         Items the reference itself fails on: behind a dictionary a match cut to one byte at the dictionary's end is a copy the
         reference cannot encode, and its stream call fails.  Such an item fails alone in the C call, which then returns 0 -- and
         this method raises BrotliCompressorException although every other stream was produced.  It is not rare at quality 2 on
@@ -328,6 +335,7 @@ class Library(object):
         streams of the others, None for a failed item): catch it, and send the failed items through another quality or without
         the dictionary."""
         routes = self.BATCH_ROUTE_QUICK_ITEMS if quick_items else 0
+        routes |= self.BATCH_ROUTE_Q9_DICTIONARY_ITEMS if q9_items else 0
         dictionary = bytes(dictionary)
 
         def call(count, inputs, in_sizes, outputs, out_sizes, results):
@@ -337,7 +345,7 @@ class Library(object):
         return self._batch(items, 1024, call)
 
     def compress_batch_with_dictionaries(self, items, dictionaries, item_dictionaries=None, quality=5, lgwin=22, mode=0, quick_items=False,
-                                         zopfli_items=False):
+                                         zopfli_items=False, q9_items=False):
         """BrotliMi355xCompressBatchWithDictionaries: item i is the stream of an Encoder(params, dictionaries[k]) with
         k = item_dictionaries[i] that gets the item in one finish(); a decoder needs that dictionary.  item_dictionaries=None:
         item i takes dictionaries[i], and there must be as many dictionaries as items.  Several items may name one index.
@@ -368,6 +376,13 @@ class Library(object):
         route all the same.  It changes nothing at qualities 0 to 9 and may be combined with quick_items.  A walk is one
         wavefront and lasts tens of microseconds per byte: it pays with hundreds of items in a call, see include/brotli_mi355x.h.
 
+        q9_items=True: BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS -- at quality 9 and lgwin 17 to 24 the items of 1 to 65 536
+        bytes behind a dictionary of at least 2 bytes, of which at most 65 536 are in use, run side by side: one chain each on a
+        private H9 hash table of 32 MiB that the chain empties and into which it files its item's dictionary itself (the same
+        bytes).  Without it quality 9 runs item by item.  It changes nothing at the other qualities and may be combined with the
+        other two flags.  When every item names the same index the call is compress_batch_with_dictionary(items, that
+        dictionary, q9_items=True).  The strongest greedy level for (old version, new file) pairs where Zopfli is too slow.
+
         Items the reference itself fails on: behind a dictionary a match cut to one byte at the dictionary's end is a copy the
         reference cannot encode, and its stream call fails.  Such an item fails alone in the C call, which then returns 0 -- and
         this method raises BrotliCompressorException although every other stream was produced.  It is not rare at quality 2 on
@@ -380,6 +395,7 @@ class Library(object):
         and for a dictionary count that does not match -- both fail the whole call."""
         routes = self.BATCH_ROUTE_QUICK_DICTIONARY_ITEMS if quick_items else 0
         routes |= self.BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS if zopfli_items else 0
+        routes |= self.BATCH_ROUTE_Q9_DICTIONARY_ITEMS if q9_items else 0
         items = list(items)
         dictionaries = [bytes(d) for d in dictionaries]
         num = len(dictionaries)
@@ -441,12 +457,12 @@ class Library(object):
         return sizes
 
     def compress_batch_with_dictionaries_device(self, inputs, outputs, dictionaries, item_dictionaries=None, quality=5, lgwin=22, mode=0,
-                                                quick_items=False, zopfli_items=False):
+                                                quick_items=False, zopfli_items=False, q9_items=False):
         """BrotliMi355xCompressBatchWithDictionariesDevice: compress_batch_with_dictionaries for items and dictionaries that lie
         in device memory (the new and the previous version of many resources, say), their streams left in device memory.
         inputs and dictionaries: sequences of (address, size), outputs: a sequence of (address, capacity), all plain integers as
         for compress_batch_device; any alignment.  Inputs and dictionaries may overlap each other (item i - 1 may be item i's
-        dictionary); outputs must not overlap each other, any input or any dictionary.  item_dictionaries, quick_items and zopfli_items are
+        dictionary); outputs must not overlap each other, any input or any dictionary.  item_dictionaries, quick_items, zopfli_items and q9_items are
         those of compress_batch_with_dictionaries; item i becomes the bytes that method gives, at outputs[i], under the stream
         API's rules: there is no fallback to a stored stream, an item whose stream does not fit its capacity fails alone.  On the
         side-by-side routes nothing crosses the bus; every other item (see compress_batch_with_dictionaries) is staged through
@@ -459,6 +475,7 @@ class Library(object):
         to hold a few the reference itself fails on."""
         routes = self.BATCH_ROUTE_QUICK_DICTIONARY_ITEMS if quick_items else 0
         routes |= self.BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS if zopfli_items else 0
+        routes |= self.BATCH_ROUTE_Q9_DICTIONARY_ITEMS if q9_items else 0
         inputs, outputs, dictionaries = list(inputs), list(outputs), list(dictionaries)
         count, num = len(inputs), len(dictionaries)
         if len(outputs) != count:
@@ -491,13 +508,14 @@ class Library(object):
             raise e
         return sizes
 
-    def compress_batch_with_dictionary_device(self, inputs, outputs, dictionary, quality=5, lgwin=22, mode=0, quick_items=False, zopfli_items=False):
+    def compress_batch_with_dictionary_device(self, inputs, outputs, dictionary, quality=5, lgwin=22, mode=0, quick_items=False, zopfli_items=False,
+                                              q9_items=False):
         """compress_batch_with_dictionaries_device with ONE dictionary, (address, size) in device memory, named by every item: the
         call takes the shared-image path -- the streams of compress_batch_with_dictionary(items, dictionary, ..., quick_items),
         the dictionary reaching its image by one copy on the device (zopfli_items=True at qualities 10 and 11: no image, every chain
-        files its own copy).  Returns the list of stream sizes."""
+        files its own copy; q9_items=True at quality 9: the image replayed over H9 tables).  Returns the list of stream sizes."""
         inputs = list(inputs)
-        return self.compress_batch_with_dictionaries_device(inputs, outputs, [dictionary], [0] * len(inputs), quality, lgwin, mode, quick_items, zopfli_items)
+        return self.compress_batch_with_dictionaries_device(inputs, outputs, [dictionary], [0] * len(inputs), quality, lgwin, mode, quick_items, zopfli_items, q9_items)
 
     def last_batch_info(self):
         """BrotliMi355xLastBatchInfo: the last compress_batch / compress_batch_with_dictionary / compress_batch_with_dictionaries call of this thread as a list of 8 integers -- [0] items, [1] items
@@ -505,7 +523,7 @@ class Library(object):
         [6] items that began side by side and were redone one by one (counted in [2]), [7] of the items in [1], those longer than one
         input block ([6] and [7]: long_items=True and quick_long_items=True only; the items quick_items=True, zopfli_items=True and
         q9_items=True take side by side count in [1] and [4], and so do those of compress_batch_with_dictionaries(...,
-        quick_items=True) and (..., zopfli_items=True))."""
+        quick_items=True), (..., zopfli_items=True) and (..., q9_items=True))."""
         info = (c_uint64 * 8)()
         self.lib.BrotliMi355xLastBatchInfo.restype = None
         self.lib.BrotliMi355xLastBatchInfo.argtypes = [POINTER(c_uint64)]

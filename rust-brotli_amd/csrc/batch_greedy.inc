@@ -12,6 +12,7 @@
 #include <utility>
 
 #include "batch_device.h"
+#include "batch_q9.h"
 #include "batch_quick.h"
 #include "batch_zopfli.h"
 #include "device_api.h"
@@ -527,7 +528,9 @@ void FinishLongItems(const EncoderParams& p, const BatchParseJob& J, const Batch
   }
 }
 
-// Qualities 5 .. 8, items of one block, and qualities 9 / 10 on the H9 hasher (BatchQ9Compress: p.hasher.type == 9, no dictionary).
+// Qualities 5 .. 8, items of one block, and qualities 9 / 10 on the H9 hasher (BatchQ9Compress: p.hasher.type == 9, no dictionary;
+// BatchQ9CompressWithDictionary: quality 9 behind the shared dictionary, whose image is 64 KiB of counters and at most D entries --
+// the scratch table lz77_batch_dict_image files it on is a whole H9 table, 32 MiB allocated and D slots of it touched).
 // p: the parameters the items share, finalized.  dict == nullptr: the plain call.
 void CompressGroups(const EncoderParams& p, const uint8_t* dict, uint32_t D, size_t count, const uint8_t* const* inputs, const size_t* sizes,
                     std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* reference_fails, uint32_t* groups,
@@ -647,6 +650,7 @@ DictsText StageDictsText(Group& g, const uint8_t* const* dicts, const size_t* di
 
 // Qualities 5 .. 8 behind a dictionary per item: the steps of CompressGroups' dictionary path without an image -- there is none
 // to share, so every chain files its own dictionary (br_batch_item<kRows, true, true>) in the text StageDictsText lays out.
+// Quality 9 (BatchQ9CompressWithDictionaries: p.hasher.type == 9) takes the same steps onto H9 tables and br_batch_item_h9_dict<true>.
 // dicts[i] / dict_sizes[i]: the dictionary of item i as in use.
 void CompressGroupsWithDictionaries(const EncoderParams& p, size_t count, const uint8_t* const* dicts, const size_t* dict_sizes,
                                     const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
@@ -670,7 +674,7 @@ void CompressGroupsWithDictionaries(const EncoderParams& p, size_t count, const 
     BatchParseJob J = GreedyJob(p, P, g, staged.text);
     J.records = g.mem.uninit<BatchRecord>((size_t)g.n * sizeof(BatchRecord));
     J.item_dict_bytes = staged.dict_bytes_dev;
-    lz77_batch_parse_dicts(J);
+    if (P.hasher_kind == 9) lz77_batch_parse_h9(J); else lz77_batch_parse_dicts(J);
     FinishOneBlockItems(p, J, g, streams, reference_fails, sink);
     first = g.last;
   }
@@ -722,6 +726,39 @@ void BatchQ9Compress(const EncoderParams& user, size_t count, const uint8_t* con
                      std::vector<std::vector<uint8_t>>* streams, uint32_t* groups, const BatchDeviceSink* sink) {
   // (nothing in the parameters differs between items of at most one block)
   CompressGroups(Q9ItemParams(user, count ? sizes[0] : 0), nullptr, 0, count, inputs, sizes, streams, nullptr, groups, sink);
+}
+
+// Quality 9 behind a custom dictionary (batch_q9.h).  D: the dictionary bytes in use, set_custom_dictionary's truncation applied.
+// What bounds it: D <= 65536 and input_size <= 65536 give D + input_size <= 131072, the first half of the smallest ring buffer in
+// range (1 << (1 + max(lgwin, lgblock)) >= 1 << 18 at lgwin 17).  So no filed position -- the dictionary's, the stitch's, the
+// chain's -- differs from its ring-buffer index, nothing is filed masked, and H9's ring-end case (SearchResult::stored,
+// lz77_chain.h: br_fold_probe, br_search) stays unreachable: it needs (cur & ring_mask) + best_len > ring_mask, and
+// cur + best_len <= D + input_size <= 131072 < ring_mask.  batch_q9_device.h carries the argument on the chain's side.
+// (lgwin <= 16 is hasher 42 in the reference, and quality 10 is Zopfli through the stream API: one by one, or the Zopfli route.)
+bool BatchQ9DictionaryEligible(const EncoderParams& user, size_t dict_size, size_t input_size) {
+  if (input_size == 0 || input_size > 65536 || dict_size < 2) return false;
+  if (user.quality != 9 || user.lgwin < 17 || user.lgwin > 24 || !PlainStreamParams(user)) return false;
+  const size_t D = std::min(dict_size, ((size_t)1 << user.lgwin) - 16);
+  if (D > 65536) return false;
+  const EncoderParams p = DictionaryItemParams(user, input_size);
+  return p.hasher.type == 9 && p.hasher.bucket_bits == 15 && p.hasher.block_bits == 8 && input_size <= ((size_t)1 << p.lgblock) &&
+         ComputeRbBits(p) >= 18;
+}
+
+// One dictionary that every item names: the steps of BatchGreedyCompressWithDictionary on H9 tables, parsed by k_parse_batch_h9_dict.
+void BatchQ9CompressWithDictionary(const EncoderParams& user, const uint8_t* dict, size_t dict_size, size_t count, const uint8_t* const* inputs,
+                                   const size_t* sizes, std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* reference_fails,
+                                   uint32_t* groups, const BatchDeviceSink* sink) {
+  // (nothing in the parameters differs between items of at most 65536 bytes)
+  CompressGroups(DictionaryItemParams(user, count ? sizes[0] : 0), dict, (uint32_t)dict_size, count, inputs, sizes, streams, reference_fails, groups, sink);
+}
+
+// A dictionary per item: the steps of BatchGreedyCompressWithDictionaries on H9 tables, parsed by k_parse_batch_h9_dicts.
+void BatchQ9CompressWithDictionaries(const EncoderParams& user, size_t count, const uint8_t* const* dicts, const size_t* dict_sizes,
+                                     const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
+                                     std::vector<uint8_t>* reference_fails, uint32_t* groups, const BatchDeviceSink* sink) {
+  CompressGroupsWithDictionaries(DictionaryItemParams(user, count ? sizes[0] : 0), count, dicts, dict_sizes, inputs, sizes, streams, reference_fails,
+                                 groups, sink);
 }
 
 // Qualities 5 .. 8, items of two to kBatchLongBlocks blocks: one chain and up to kBatchLongBlocks meta-blocks per item.

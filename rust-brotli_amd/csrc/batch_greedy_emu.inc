@@ -7,6 +7,7 @@
 #include <stdexcept>
 
 #include "batch_greedy_device.h"
+#include "batch_q9_device.h"
 #include "device_api.h"
 
 namespace brotli_mi355x {
@@ -68,11 +69,18 @@ void lz77_batch_parse_dicts(const BatchParseJob& J) {
 void lz77_batch_parse_h9(const BatchParseJob& J) {
   if (J.n_items == 0) return;
   if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
-  if (J.P.hasher_kind != 9 || J.P.block_bits != 8 || J.P.ndist > 16 || J.dict.bytes != 0) throw std::runtime_error("brotli_mi355x: not the job of an H9 batch chain");
+  if (J.P.hasher_kind != 9 || J.P.block_bits != 8 || J.P.ndist > 16) throw std::runtime_error("brotli_mi355x: not the job of an H9 batch chain");
+  if (J.dict.bytes > 65536 || (J.dict.bytes != 0 && J.item_dict_bytes != nullptr) || J.P.ring_mask < (1u << 18) - 1u)
+    throw std::runtime_error("brotli_mi355x: not the job of an H9 batch chain");
   const ChainTables T = EmuBatchChainTables(J);
   static thread_local ChainScratchT<true, false> scratch;
   uint32_t histo[256];
-  for (uint32_t place = 0; place < J.n_items; ++place) br_batch_item_h9(J, T, scratch, histo, J.order[place], place % J.tables);
+  // behind a dictionary (batch_q9_device.h): one per item, or the call's shared one
+  for (uint32_t place = 0; place < J.n_items; ++place) {
+    if (J.item_dict_bytes != nullptr) br_batch_item_h9_dict<true>(J, T, scratch, histo, J.order[place], place % J.tables);
+    else if (J.dict.bytes != 0) br_batch_item_h9_dict<false>(J, T, scratch, histo, J.order[place], place % J.tables);
+    else br_batch_item_h9(J, T, scratch, histo, J.order[place], place % J.tables);
+  }
   *J.counter = J.n_items;
 }
 

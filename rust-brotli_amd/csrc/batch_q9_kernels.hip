@@ -1,12 +1,14 @@
-// batch_q9_kernels.hip -- the gfx950 kernel of BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS (batch_greedy.h): the items of a batch at
-// qualities 9 and 10, one live chain each on a private H9 table (br_batch_item_h9, batch_greedy_device.h).  A translation unit of
-// its own, so that the parse kernels of lz77_kernels.hip compile as they did.
+// batch_q9_kernels.hip -- the gfx950 kernels of BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS and BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS
+// (batch_greedy.h): the items of a batch at qualities 9 and 10, one live chain each on a private H9 table (br_batch_item_h9,
+// batch_greedy_device.h), and the items of quality 9 behind a custom dictionary (br_batch_item_h9_dict, batch_q9_device.h).  A
+// translation unit of its own, so that the parse kernels of lz77_kernels.hip compile as they did.
 #include <hip/hip_runtime.h>
 
 #include <stdexcept>
 
 #undef BR_CHAIN_PROFILE  // (the profiling build: the chain's cycle counters are a device variable of lz77_kernels.hip, not linked across units)
 #include "batch_greedy_device.h"
+#include "batch_q9_device.h"
 #include "device_api.h"
 #include "device_scan.h"  // HIP_CHECK
 
@@ -26,14 +28,37 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 4))) void
   for (uint32_t index; br_batch_next_index(J.counter, J.order, J.n_items, index);) br_batch_item_h9(J, T, scratch, histo, index, table);
 }
 
+// The same launch shape, workgroup memory and occupancy bounds behind a custom dictionary: siblings of k_parse_batch_h9, so that
+// the instance without a dictionary compiles as it did.  k_parse_batch_h9_dict: the call's shared dictionary (J.dict: its image is
+// replayed over the table, or filed by the chain where there is no image); k_parse_batch_h9_dicts: a dictionary per item
+// (J.item_dict_bytes), filed by the chain.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_parse_batch_h9_dict(BatchParseJob J, ChainTables T) {
+  __shared__ ChainScratchT<true, false> scratch;
+  __shared__ uint32_t histo[256];
+  const uint32_t table = blockIdx.x;
+  if (table >= J.tables) return;
+  for (uint32_t index; br_batch_next_index(J.counter, J.order, J.n_items, index);) br_batch_item_h9_dict<false>(J, T, scratch, histo, index, table);
+}
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_parse_batch_h9_dicts(BatchParseJob J, ChainTables T) {
+  __shared__ ChainScratchT<true, false> scratch;
+  __shared__ uint32_t histo[256];
+  const uint32_t table = blockIdx.x;
+  if (table >= J.tables) return;
+  for (uint32_t index; br_batch_next_index(J.counter, J.order, J.n_items, index);) br_batch_item_h9_dict<true>(J, T, scratch, histo, index, table);
+}
+
 void lz77_batch_parse_h9(const BatchParseJob& J) {
   if (J.n_items == 0) return;
   if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
   // (what the scratch and the table layout are sized for)
-  if (J.P.hasher_kind != 9 || J.P.block_bits != 8 || J.P.ndist > 16 || J.dict.bytes != 0) throw std::runtime_error("brotli_mi355x: not the job of an H9 batch chain");
+  if (J.P.hasher_kind != 9 || J.P.block_bits != 8 || J.P.ndist > 16) throw std::runtime_error("brotli_mi355x: not the job of an H9 batch chain");
+  // (what batch_q9_device.h argues from: dictionary + item end inside the first half of the smallest ring buffer, 1 << 18)
+  if (J.dict.bytes > 65536 || (J.dict.bytes != 0 && J.item_dict_bytes != nullptr) || J.P.ring_mask < (1u << 18) - 1u)
+    throw std::runtime_error("brotli_mi355x: not the job of an H9 batch chain");
   const ChainTables T = batch_chain_tables(J);
   const uint32_t grid = J.tables < J.n_items ? J.tables : J.n_items;
-  hipLaunchKernelGGL(k_parse_batch_h9, dim3(grid), dim3(64), 0, BR_STREAM, J, T);
+  const auto kernel = J.item_dict_bytes != nullptr ? k_parse_batch_h9_dicts : (J.dict.bytes != 0 ? k_parse_batch_h9_dict : k_parse_batch_h9);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), 0, BR_STREAM, J, T);
   HIP_CHECK(hipGetLastError());
 }
 

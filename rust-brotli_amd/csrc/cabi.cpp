@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "batch_greedy.h"
+#include "batch_q9.h"
 #include "batch_quick.h"
 #include "batch_zopfli.h"
 #include "concat.h"
@@ -1370,13 +1371,14 @@ static std::vector<uint8_t> DownloadBytes(const uint8_t* device, size_t bytes) {
 }
 
 // The one body of the dictionary batch calls, entered with what its entry refuses (`refused`, made before any device address is
-// looked at), with quick_route, the entry's own bit for the side-by-side route of qualities 2 .. 4, and with zopfli_route, the bit
-// of the per-item entries for the one of qualities 10 and 11 (BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS).  Item i lies behind
+// looked at), with quick_route, the entry's own bit for the side-by-side route of qualities 2 .. 4, with zopfli_route, the bit
+// of the per-item entries for the one of qualities 10 and 11 (BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS), and with q9_route,
+// the bit of all three entries for the one of quality 9 (BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS).  Item i lies behind
 // dicts[all_first ? 0 : item_dicts ? item_dicts[i] : i].  on_device: dicts[k], inputs[i] and outputs[i] are device addresses (the
 // arrays themselves are host memory) -- the side-by-side routes read every dictionary and item where it lies and leave the streams
 // in device memory (BatchDeviceSink with StreamDeliveryRule); an item that runs one by one comes down, its dictionary's bytes in
 // use come down once per call, it runs through the stream path and its stream goes up; the frame's dev_sync() ends the call.
-static int32_t CompressBatchWithDictionaries(const char* entry, int quality, int lgwin, BrotliEncoderMode mode, bool quick_route, bool zopfli_route,
+static int32_t CompressBatchWithDictionaries(const char* entry, int quality, int lgwin, BrotliEncoderMode mode, bool quick_route, bool zopfli_route, bool q9_route,
                                              const std::string& refused, size_t num_dicts, const uint8_t* const* dicts, const size_t* dict_sizes, size_t count,
                                              const size_t* item_dicts, bool all_first, const uint8_t* const* inputs, const size_t* input_sizes,
                                              uint8_t* const* outputs, size_t* output_sizes, int32_t* item_results, bool on_device) {
@@ -1408,10 +1410,11 @@ static int32_t CompressBatchWithDictionaries(const char* entry, int quality, int
     // Side by side: the items of 1 .. 65536 bytes at qualities 5 .. 8, lgwin 17 .. 24, behind a dictionary of 2 .. 65536 bytes in
     // use (batch_greedy.h) and, where the caller asked for that route, the items of at most one input block at qualities 2 .. 4,
     // lgwin 10 .. 24, behind at most 65536 dictionary bytes in use (batch_quick.h), or of 1 .. 65536 bytes at qualities 10 and 11
-    // behind at most 65536 dictionary bytes in use (batch_zopfli.h) -- a call has one quality, so its items take one of the
-    // three.  Every other item goes through the stream path by itself with its own dictionary, on this thread, in the caller's
-    // order.  The Zopfli route has no shared tree image: its chains file their own copy also where every item names one index.
-    bool quick = false, zopfli = false;
+    // behind at most 65536 dictionary bytes in use (batch_zopfli.h), or of 1 .. 65536 bytes at quality 9, lgwin 17 .. 24, behind at
+    // most 65536 dictionary bytes in use (batch_q9.h) -- a call has one quality, so its items take one of the four.  Every other
+    // item goes through the stream path by itself with its own dictionary, on this thread, in the caller's order.  The Zopfli
+    // route has no shared tree image: its chains file their own copy also where every item names one index.
+    bool quick = false, zopfli = false, q9 = false;
     BatchItems r;
     // on_device: the bytes in use of the dictionaries that items running one by one name, each down once per call
     std::vector<std::vector<uint8_t>> host_dicts(on_device ? num_dicts : 0);
@@ -1421,12 +1424,14 @@ static int32_t CompressBatchWithDictionaries(const char* entry, int quality, int
       const bool greedy_item = BatchDictionaryEligible(params, dict_sizes[k], input_sizes[i]);
       const bool quick_item = !greedy_item && quick_route && BatchQuickDictionaryEligible(params, dict_sizes[k], input_sizes[i]);
       const bool zopfli_item = !greedy_item && !quick_item && zopfli_route && BatchZopfliDictionaryEligible(params, dict_sizes[k], input_sizes[i]);
+      const bool q9_item = !greedy_item && !quick_item && !zopfli_item && q9_route && BatchQ9DictionaryEligible(params, dict_sizes[k], input_sizes[i]);
       if (quick_item) quick = true;
       if (zopfli_item) zopfli = true;
-      if (greedy_item || quick_item || zopfli_item) {
+      if (q9_item) q9 = true;
+      if (greedy_item || quick_item || zopfli_item || q9_item) {
         r.Add(i, inputs[i], input_sizes[i], outputs[i], output_sizes[i], on_device);
         if (!one || zopfli_item) {
-          // (at qualities 5 .. 8 dict_sizes[k] itself: an eligible dictionary is below every window's limit; at lgwin 10 .. 16 its
+          // (at qualities 5 .. 9 dict_sizes[k] itself: an eligible dictionary is below every window's limit; at lgwin 10 .. 16 its
           // last (1 << lgwin) - 16 bytes)
           r.dict.push_back(dicts[k] + (dict_sizes[k] - in_use(k)));
           r.dict_size.push_back(in_use(k));
@@ -1454,11 +1459,11 @@ static int32_t CompressBatchWithDictionaries(const char* entry, int quality, int
       BatchZopfliCompressWithDictionaries(params, r.item.size(), r.dict.data(), r.dict_size.data(), r.in.data(), r.size.data(), &streams, &reference_fails,
                                           &groups, sink);
     else if (one)
-      (quick ? BatchQuickCompressWithDictionary : BatchGreedyCompressWithDictionary)(params, dicts[k0] + (dict_sizes[k0] - in_use(k0)), in_use(k0), r.item.size(),
-                                                                                     r.in.data(), r.size.data(), &streams, &reference_fails, &groups, sink);
+      (quick ? BatchQuickCompressWithDictionary : q9 ? BatchQ9CompressWithDictionary : BatchGreedyCompressWithDictionary)(
+          params, dicts[k0] + (dict_sizes[k0] - in_use(k0)), in_use(k0), r.item.size(), r.in.data(), r.size.data(), &streams, &reference_fails, &groups, sink);
     else
-      (quick ? BatchQuickCompressWithDictionaries : BatchGreedyCompressWithDictionaries)(params, r.item.size(), r.dict.data(), r.dict_size.data(), r.in.data(),
-                                                                                         r.size.data(), &streams, &reference_fails, &groups, sink);
+      (quick ? BatchQuickCompressWithDictionaries : q9 ? BatchQ9CompressWithDictionaries : BatchGreedyCompressWithDictionaries)(
+          params, r.item.size(), r.dict.data(), r.dict_size.data(), r.in.data(), r.size.data(), &streams, &reference_fails, &groups, sink);
     info[4] = groups;
     info[1] = r.item.size();
     for (size_t n = 0; n < r.item.size(); ++n) {
@@ -1495,11 +1500,12 @@ static int32_t CompressBatchWithSharedDictionary(const char* entry, int quality,
                                                  const uint8_t* dict, size_t count, const uint8_t* const* inputs, const size_t* input_sizes,
                                                  uint8_t* const* outputs, size_t* output_sizes, int32_t* item_results) {
   std::string refused;
-  if ((routes & ~(uint32_t)BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS) != 0) {
+  if ((routes & ~(uint32_t)(BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS | BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS)) != 0) {
     refused = "routes " + std::to_string(routes) + " names a route this call does not know (known behind a dictionary: "
-              "BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS = 4)";
+              "BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS = 4, BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS = 4096)";
   }
-  return CompressBatchWithDictionaries(entry, quality, lgwin, mode, (routes & BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS) != 0, false, refused, 1, &dict, &dict_size, count,
+  return CompressBatchWithDictionaries(entry, quality, lgwin, mode, (routes & BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS) != 0, false,
+                                       (routes & BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS) != 0, refused, 1, &dict, &dict_size, count,
                                        nullptr, true, inputs, input_sizes, outputs, output_sizes, item_results, false);
 }
 
@@ -1524,9 +1530,11 @@ static int32_t CompressBatchWithItemDictionaries(const char* entry, int quality,
                                                  const uint8_t* const* inputs, const size_t* input_sizes, uint8_t* const* outputs, size_t* output_sizes,
                                                  int32_t* item_results, bool on_device) {
   std::string refused;
-  if ((routes & ~(uint32_t)(BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS | BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS)) != 0) {
+  if ((routes & ~(uint32_t)(BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS | BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS |
+                            BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS)) != 0) {
     refused = "routes " + std::to_string(routes) + " names a route this call does not know (known behind a dictionary per item: "
-              "BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS = 512, BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS = 1024)";
+              "BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS = 512, BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS = 1024, "
+              "BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS = 4096)";
   } else if (item_dicts == nullptr && num_dicts != count) {
     refused = "item_dicts is NULL (item i takes dicts[i]) but num_dicts, " + std::to_string(num_dicts) + ", is not count, " + std::to_string(count);
   } else if (item_dicts != nullptr) {
@@ -1535,7 +1543,9 @@ static int32_t CompressBatchWithItemDictionaries(const char* entry, int quality,
         refused = "item " + std::to_string(i) + " names dictionary " + std::to_string(item_dicts[i]) + " of " + std::to_string(num_dicts);
   }
   return CompressBatchWithDictionaries(entry, quality, lgwin, mode, (routes & BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS) != 0,
-                                       (routes & BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS) != 0, refused, num_dicts, dicts, dict_sizes, count, item_dicts, false, inputs, input_sizes, outputs, output_sizes, item_results, on_device);
+                                       (routes & BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS) != 0, (routes & BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS) != 0,
+                                       refused, num_dicts, dicts, dict_sizes, count, item_dicts, false, inputs, input_sizes, outputs, output_sizes, item_results,
+                                       on_device);
 }
 
 int32_t BrotliMi355xCompressBatchWithDictionaries(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t num_dicts,

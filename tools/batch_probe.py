@@ -79,6 +79,12 @@ DICTS_ZOPFLI_HEADLINE (1024 items of 4 KiB behind 16 KiB, 256 of 16 KiB and of 4
 alternating rounds of one run each: the route; the route with BROTLI_MI355X_ZOPFLI_PREPEND_LANE0=1 on the classes of DICTS_ZOPFLI_AB (the
 dictionary filed by lane 0 alone inside the same kernel); the --parent-lib build through the same call without the bit, where every item runs
 one by one (first --loop-items items, scaled by item count); the loop of stream calls from four threads (the same); then the oracle on one core.
+With --dicts --qualities 9 this build is called with BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS (4096) on the classes of DICTS_Q9_HEADLINE
+(4096 items of 4 KiB behind 16 KiB, 1024 of 16 KiB and 256 of 64 KiB behind 64 KiB, 64 and 16 of 4 KiB behind 16 KiB, and the calls of few items
+of DICTS_Q9_FEW: 4 and 1 of 4 KiB behind 16 KiB, 16 of 64 KiB behind 64 KiB), in --rounds alternating
+rounds of one run each: the route; on the classes of DICTS_Q9_SHARED the shared form (BrotliMi355xCompressBatchWithDictionaryEx with 4096, every
+item behind the first dictionary) with the image and with BROTLI_MI355X_BATCH_DICT_SELF_FILE=1; the --parent-lib build through the per-item call
+without the bit (first --loop-items items, scaled); the loop of stream calls from four threads (the same); then the oracle on one core.
 
 With --device (and --parent-lib) the call measured is BrotliMi355xCompressBatchDevice on torch tensors -- one uint8 tensor of items in,
 one of streams out -- beside the parent's BrotliMi355xCompressBatchEx on the same items from host memory and beside the "honest
@@ -164,6 +170,12 @@ DICTS_CLASSES.update({"1024x4KiB+16KiB": (1024, 4 << 10, 16 << 10), "256x16KiB+6
                       "16x4KiB+16KiB": (16, 4 << 10, 16 << 10)})
 DICTS_ZOPFLI_HEADLINE = ["1024x4KiB+16KiB", "256x16KiB+64KiB", "256x4KiB+64KiB", "64x4KiB+16KiB", "16x4KiB+16KiB"]
 DICTS_ZOPFLI_AB = ["1024x4KiB+16KiB", "256x4KiB+64KiB"]
+# (--dicts --qualities 9) BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS: the classes, and the one of the shared form (image against self-filing)
+DICTS_Q9_FEW = {"4x4KiB+16KiB": (4, 4 << 10, 16 << 10), "1x4KiB+16KiB": (1, 4 << 10, 16 << 10), "16x64KiB+64KiB": (16, 64 << 10, 64 << 10)}  # (where a call is expected to lose)
+DICTS_CLASSES.update({"256x64KiB+64KiB": (256, 64 << 10, 64 << 10)})
+DICTS_CLASSES.update(DICTS_Q9_FEW)
+DICTS_Q9_HEADLINE = ["4096x4KiB+16KiB", "1024x16KiB+64KiB", "256x64KiB+64KiB", "64x4KiB+16KiB", "16x4KiB+16KiB"] + list(DICTS_Q9_FEW)
+DICTS_Q9_SHARED = ["4096x4KiB+16KiB"]
 Q9_HEADLINE = ["4096x4KiB", "1024x16KiB", "256x64KiB", "64x256KiB", "16x4KiB", "64x4KiB", "4096xlog200B-256KiB"]  # (--q9-items)
 
 
@@ -273,7 +285,8 @@ def measure_batch(lib_path, items, quality, runs, warmup, dictionary=None, route
 def measure_dicts(lib_path, items, dictionaries, quality, runs, warmup, shared=False, routes=None):
     """BrotliMi355xCompressBatchWithDictionaries with dictionaries[i] for item i; shared: BrotliMi355xCompressBatchWithDictionary with
     dictionaries[0].  At qualities 2 to 4 both with the route that takes such items side by side (512, and 4 through the Ex entry).
-    routes: the bits of the per-item call (default: 512 at qualities 2 to 4, else 0; 1024 is the caller's to give)."""
+    routes: the bits of the per-item call (default: 512 at qualities 2 to 4, else 0; 1024 and 4096 are the caller's to give); with
+    shared they go to BrotliMi355xCompressBatchWithDictionaryEx as they are (4096: quality 9)."""
     L = bind(lib_path)
     quick = 2 <= quality <= 4
     L.BrotliMi355xCompressBatchWithDictionaryEx.restype = ctypes.c_int32
@@ -296,8 +309,8 @@ def measure_dicts(lib_path, items, dictionaries, quality, runs, warmup, shared=F
         for i in range(n):
             out_sizes[i] = caps[i]
         t = time.perf_counter()
-        if shared and quick:
-            ok = L.BrotliMi355xCompressBatchWithDictionaryEx(quality, LGWIN, 0, ctypes.c_uint32(4), ctypes.c_size_t(len(dictionaries[0])), ctypes.c_char_p(dictionaries[0]),
+        if shared and (quick or routes):
+            ok = L.BrotliMi355xCompressBatchWithDictionaryEx(quality, LGWIN, 0, ctypes.c_uint32(routes if routes else 4), ctypes.c_size_t(len(dictionaries[0])), ctypes.c_char_p(dictionaries[0]),
                                                              ctypes.c_size_t(n), inputs, in_sizes, outputs, out_sizes, results)
         elif shared:
             ok = L.BrotliMi355xCompressBatchWithDictionary(quality, LGWIN, 0, ctypes.c_size_t(len(dictionaries[0])), ctypes.c_char_p(dictionaries[0]), ctypes.c_size_t(n),
@@ -409,7 +422,7 @@ def child_dicts(args):
             if args.child in ("batch", "same", "shared"):
                 ds = dictionaries if args.child == "batch" else [dictionaries[0]] * len(items)
                 times, csize, info, failed = measure_dicts(args.lib, items, ds, quality, args.runs, args.warmup, shared=args.child == "shared",
-                                                           routes=args.routes if args.child == "batch" and args.routes else None)
+                                                           routes=args.routes if args.child in ("batch", "shared") and args.routes else None)
                 row.update(stats(times), compressed_bytes=csize, batch_info=info, reference_fails_on_items=failed)
             elif args.child == "batch_first":  # the same call on the first --loop-items items (a library whose items run one by one)
                 times, csize, info, failed = measure_dicts(args.lib, items[:n], dictionaries[:n], quality, args.runs, args.warmup, routes=args.routes)
@@ -727,6 +740,7 @@ def run_child(args, what, classes, lib=None, lds=None, threads=1, limit=600, fir
               quick_long_items=False, zopfli_items=False, q9_items=False, routes=0, extra_env=None):
     env = dict(os.environ)
     env.pop("BROTLI_MI355X_ZOPFLI_PREPEND_LANE0", None)
+    env.pop("BROTLI_MI355X_BATCH_DICT_SELF_FILE", None)
     env.update(extra_env or {})
     env.pop("BROTLI_MI355X_BATCH_LDS_BITS", None)
     if lds is not None:
@@ -998,6 +1012,63 @@ def main_dicts_zopfli(args, doc, save, classes):
     print(json.dumps(doc, indent=1))
 
 
+def main_dicts_q9(args, doc, save, classes):
+    """--dicts --qualities 9: the dictionary batch calls with BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS (4096), --rounds alternating rounds of
+    one run each: this build with the route, every item behind a dictionary of its own; on the DICTS_Q9_SHARED classes the shared form (every item
+    behind the first dictionary, BrotliMi355xCompressBatchWithDictionaryEx with 4096) with the image and with BROTLI_MI355X_BATCH_DICT_SELF_FILE=1;
+    the parent's library through the per-item call without the bit (its items run one by one: the first --loop-items items, scaled by item
+    count), and the loop of stream calls from four threads (first --loop-items items, scaled); then the oracle on one core."""
+    doc["what"] = ("BrotliMi355xCompressBatchWithDictionaries with BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS (4096), a custom dictionary per item, text, lgwin 22, "
+                   "quality 9; min .. max over --rounds alternating rounds of one run each (one warm-up call per process).  shared_image / shared_self_file: "
+                   "BrotliMi355xCompressBatchWithDictionaryEx with 4096, every item behind the class's first dictionary, the image replayed (the default) or "
+                   "BROTLI_MI355X_BATCH_DICT_SELF_FILE=1; parent: a build of the parent commit through the per-item call with routes 0 -- every item one by one "
+                   "through the stream path -- TIMED ON THE FIRST --loop-items ITEMS AND SCALED BY ITEM COUNT; loop_4t: the loop of stream calls with "
+                   "BrotliEncoderSetCustomDictionary from four threads, first --loop-items items, scaled; cpu_one_core: the oracle's dictionary stream on "
+                   "one core, first --loop-items items, scaled")
+    rows = {}
+    shared = [c for c in DICTS_Q9_SHARED if c in classes]
+    one = argparse.Namespace(**vars(args))
+    one.runs, one.warmup = 1, 1
+    parent = os.path.abspath(args.parent_lib) if args.parent_lib else None
+
+    def note(v, name, ms, scale=1.0):
+        v.setdefault(name + "_ms", []).append(round(ms * scale, 3))
+
+    for rnd in range(args.rounds):
+        for row in run_child(one, "batch", classes, limit=900, routes=4096):
+            v = rows.setdefault(key(row), {"items": row["items"], "bytes": row["bytes"], "dictionary_bytes": row["dictionary_bytes"]})
+            note(v, "route", row["median_ms"])
+            v["route_info"], v["route_compressed_bytes"], v["route_reference_fails_on_items"] = row["batch_info"], row["compressed_bytes"], row["reference_fails_on_items"]
+        for name, env in (("shared_image", None), ("shared_self_file", {"BROTLI_MI355X_BATCH_DICT_SELF_FILE": "1"})):
+            for row in (run_child(one, "shared", shared, limit=900, routes=4096, extra_env=env) if shared else []):
+                note(rows[key(row)], name, row["median_ms"])
+                rows[key(row)][name + "_info"], rows[key(row)][name + "_compressed_bytes"] = row["batch_info"], row["compressed_bytes"]
+        for row in (run_child(one, "batch_first", classes, lib=parent, limit=1500) if parent else []):
+            note(rows[key(row)], "parent_scaled", row["median_ms"], row["items"] / row["measured_items"])
+            rows[key(row)]["parent_measured_items"], rows[key(row)]["parent_info"] = row["measured_items"], row["batch_info"]
+        for row in ([] if "loop" in args.skip.split(",") else run_child(one, "loop", classes, lib=parent, threads=4, limit=1500)):
+            note(rows[key(row)], "loop_4t_scaled", row["median_ms"], row["items"] / row["measured_items"])
+        doc["classes"] = rows
+        save()
+    for row in ([] if "cpu" in args.skip.split(",") else run_child(one, "cpu", classes, limit=1500)):
+        rows[key(row)]["cpu_one_core_scaled_ms"] = round(row["median_ms"] * row["items"] / row["measured_items"], 3)
+        rows[key(row)]["cpu_measured_items"] = row["measured_items"]
+    for v in rows.values():
+        for name in ("route", "shared_image", "shared_self_file", "parent_scaled", "loop_4t_scaled"):
+            if name + "_ms" in v:
+                v[name + "_min_max_ms"] = [min(v[name + "_ms"]), max(v[name + "_ms"])]
+        med = statistics.median(v["route_ms"])
+        for name, out in (("parent_scaled", "parent_over_route"), ("loop_4t_scaled", "loop_4t_over_route"), ("shared_image", "shared_image_over_route")):
+            if name + "_ms" in v:
+                v[out] = round(statistics.median(v[name + "_ms"]) / med, 2)
+        if "shared_image_ms" in v and "shared_self_file_ms" in v:
+            v["self_file_over_image"] = round(statistics.median(v["shared_self_file_ms"]) / statistics.median(v["shared_image_ms"]), 3)
+        if "cpu_one_core_scaled_ms" in v:
+            v["cpu_over_route"] = round(v["cpu_one_core_scaled_ms"] / med, 3)
+    save()
+    print(json.dumps(doc, indent=1))
+
+
 def main_same_call(args, doc, save, classes):
     """--same-call: this build and the parent's library through the very same call (route bits, dictionary), alternating, one child
     each -- for a change that keeps the routes and must not cost them anything.  Per class: the median of either build's round
@@ -1048,7 +1119,7 @@ def main():
     ap.add_argument("--quick-long-items", action="store_true", help="this build through routes QUICK_ITEMS | QUICK_LONG_ITEMS, the parent through QUICK_ITEMS (qualities 2,3,4 per class)")
     ap.add_argument("--zopfli-items", action="store_true", help="this build through BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS (--qualities 11)")
     ap.add_argument("--q9-items", action="store_true", help="this build through BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS (--qualities 9,10)")
-    ap.add_argument("--dicts", action="store_true", help="BrotliMi355xCompressBatchWithDictionaries: a dictionary per item (--qualities 5,8; 2,3,4 through BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS; 10,11 through BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS, "
+    ap.add_argument("--dicts", action="store_true", help="BrotliMi355xCompressBatchWithDictionaries: a dictionary per item (--qualities 5,8; 2,3,4 through BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS; 10,11 through BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS; 9 through BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS, shared form included, "
                     "with the prepend A/B and, with --parent-lib, the parent's one-by-one path on --loop-items items)")
     ap.add_argument("--device", action="store_true", help="BrotliMi355xCompressBatchDevice on torch tensors beside the parent's host call on the same items (DEVICE_SHAPES)")
     ap.add_argument("--device-dicts", action="store_true", help="BrotliMi355xCompressBatchWithDictionariesDevice on torch tensors beside download + the parent's host dictionary call + upload (DEVICE_DICTS_SHAPES)")
@@ -1097,8 +1168,10 @@ def main():
                        "--loop-items items, scaled by item count), and its 4-thread loop vs the oracle on one CPU core; lgwin 22")
     if args.dicts and not args.same_call and set(args.qualities.split(",")) <= {"10", "11"}:
         return main_dicts_zopfli(args, doc, save, [c for c in DICTS_ZOPFLI_HEADLINE if not args.only or c in args.only.split(",")])
+    if args.dicts and not args.same_call and set(args.qualities.split(",")) == {"9"}:
+        return main_dicts_q9(args, doc, save, [c for c in DICTS_Q9_HEADLINE if not args.only or c in args.only.split(",")])
     if args.dicts and not args.same_call:
-        return main_dicts(args, doc, save, [c for c in DICTS_CLASSES if (c in args.only.split(",") if args.only else c not in DICTS_ZOPFLI_HEADLINE or c == "64x4KiB+16KiB")])
+        return main_dicts(args, doc, save, [c for c in DICTS_CLASSES if (c in args.only.split(",") if args.only else (c not in DICTS_ZOPFLI_HEADLINE and c != "256x64KiB+64KiB" and c not in DICTS_Q9_FEW) or c == "64x4KiB+16KiB")])
     if args.same_call:
         if args.dicts:  # (the per-item call, every item behind its own dictionary)
             return main_same_call(args, doc, save, [c for c in DICTS_CLASSES if not args.only or c in args.only.split(",")])
