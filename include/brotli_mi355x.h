@@ -358,10 +358,11 @@ int32_t BrotliMi355xCompressBatchDevice(int quality, int lgwin, BrotliEncoderMod
                                         const uint8_t* const* inputs_device, const size_t* input_sizes, uint8_t* const* outputs_device,
                                         size_t* output_sizes /* in: capacity, out: size */, int32_t* item_results /* may be NULL */);
 /* BrotliMi355xCompressBatchWithDictionary with routes the caller opts into.  routes == 0 is that call in every respect.  The
-   routes this call knows are BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS (4) and BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS (4096,
-   defined and described with BrotliMi355xCompressBatchWithDictionaries below); they may be combined, and since a call has one
-   quality at most one of them takes items.  Any other bit -- the other routes of BrotliMi355xCompressBatchEx and the reserved
-   values 2, 8 and 64 included -- fails the whole call as an unknown route fails that one
+   routes this call knows are BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS (4), BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS (4096,
+   defined and described with BrotliMi355xCompressBatchWithDictionaries below) and
+   BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_SHARED_DICTIONARY_ITEMS (8192, defined there, described here); they may be combined, and
+   since a call has one quality at most one of them takes items.  Any other bit -- the other routes of
+   BrotliMi355xCompressBatchEx, 512 and 1024 of the per-item calls, and the reserved values 2, 8 and 64 included -- fails the whole call as an unknown route fails that one
    (returns 0, every size 0, BrotliMi355xLastError says so, only info[0] of BrotliMi355xLastBatchInfo is set).
    BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS: item i is still exactly the stream of BrotliEncoderSetCustomDictionary + one
    BrotliEncoderCompressStream(BROTLI_OPERATION_FINISH), by the rules above -- in bytes, size, success or failure.  In addition
@@ -382,7 +383,39 @@ int32_t BrotliMi355xCompressBatchDevice(int quality, int lgwin, BrotliEncoderMod
    applies (4096 tables by default; a group's byte limit counts one copy of the dictionary per item).
    When to set it: with hundreds of small items of one kind in a call that share a dictionary (dynamic responses, messages,
    records at the levels servers use for them).  When not: with a few items -- a chain is one wavefront bound by its own
-   dependent loads, so a call of a few items is no faster than the one-by-one path (see INTEGRATION.md for measured figures). */
+   dependent loads, so a call of a few items is no faster than the one-by-one path (see INTEGRATION.md for measured figures).
+   BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_SHARED_DICTIONARY_ITEMS (8192; known to this call only -- it is to
+   BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS, 1024, what 4 here is to 512 there, and 1024 stays an unknown route of this
+   call): item i is still exactly the stream of BrotliEncoderSetCustomDictionary + one FINISH, at quality 10 AND at quality 11 --
+   through the stream API both are Zopfli.  An item of 1 <= input_sizes[i] <= 65 536 bytes at quality 10 or 11 and lgwin 10 .. 24
+   behind a dictionary of dict_size >= 2 of which at most 65 536 bytes are in use (min(dict_size, (1 << lgwin) - 16)) runs on the
+   device as ONE wavefront on H10 trees of its own, side by side with the other such items of the call.  The dictionary's part of
+   those trees hangs on the dictionary alone (a stored position compares at most 128 bytes, all inside it), so the call builds ONE
+   image of it -- 512 KiB of buckets and 8 bytes of forest per dictionary byte, at most 1 MiB, by 1024 lanes of 16 workgroups
+   that each own a class of hash keys -- and in front of every item a chain copies the image over its table and zeroes the item's
+   part of the forest, where the per-item route files the dictionary anew; then it stitches and walks the item from position D as
+   that route does.  Every other item -- the empty one, longer items, dict_size <= 1, more than 65 536 bytes in use -- runs by
+   itself through the stream path, as every item of these qualities does without the bit (65 .. 440 ms apiece).  The bit changes
+   nothing at qualities 0 .. 9.  Such items count in info[1], their groups (at most 1024 items) in info[4]; info[5] is the
+   dictionary bytes in use; info[6] and info[7] stay 0.  BrotliMi355xCompressBatchWithDictionaries and its device form with 1024
+   take the same path when every item names one index: same bytes, equal info.  Memory is that route's: a table per item in
+   flight, at most 256, plus the image.
+   When to set it: tens to thousands of small items behind one dictionary at the level static files are pre-compressed at.
+   Measured (text, lgwin 22, quality 10 / 11, min .. max of five alternating runs; profiles/r29_batch_dictionary_zopfli.json; the
+   one-by-one baseline timed on 8 items and scaled): 1024 items of 4 KiB behind 16 KiB in 244 .. 245 / 546 .. 547 ms against
+   302 .. 304 / 603 .. 604 ms for the parent build's BrotliMi355xCompressBatchWithDictionaries with 1024 and one index, where
+   every chain filed its own copy (1.24 / 1.11 x), and 66 .. 67 / 110 .. 112 s for this call without the bit; 256 items of 16 KiB
+   behind 64 KiB in 283 .. 284 / 575 .. 577 against 338 .. 339 / 629 .. 631 ms (1.19 / 1.09 x; without the bit 65 .. 66 / 112 ..
+   113 s); 256 items of 4 KiB behind 64 KiB in 100 .. 101 / 172 .. 173 against 154 .. 155 / 227 .. 228 ms (1.54 / 1.31 x; 43 /
+   54 .. 55 s); 16 items of 4 KiB behind 16 KiB in 73 .. 74 / 144 .. 146 against 85 / 155 .. 156 ms (1.15 / 1.07 x; 1.04 .. 1.05 /
+   1.72 .. 1.75 s).  BROTLI_MI355X_BATCH_DICT_SELF_FILE=1 (every chain files the dictionary itself, for A/B runs) reproduces the
+   parent's figures within 1 %.  No measured shape is slower than self-filing or than the call without the bit.  The image's
+   build takes 3.7 .. 4.0 ms for 16 KiB and 17.7 .. 19.2 ms for 64 KiB, once per call; a lone chain files them in 15.0 .. 15.2 and
+   65.5 .. 68.7 ms wave-wide (17.6 .. 18.0 and 120 .. 122 ms on lane 0), in front of every item.
+   When not: a call of a few items -- a walk is one wavefront and lasts its item's time however many run beside it (about 70 /
+   140 ms for 4 KiB behind 16 KiB): one such item through the route takes 70 .. 71 / 138 .. 141 ms, no faster than the stream
+   path by itself (65 / 107 ms), and 16 of them still lose to one CPU core (29 / 61 ms in
+   profiles/r27_batch_dictionaries_zopfli.json).  The image does not change that: it removes the filing, not the walk. */
 int32_t BrotliMi355xCompressBatchWithDictionaryEx(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t dict_size,
                                                   const uint8_t* dict, size_t count, const uint8_t* const* inputs,
                                                   const size_t* input_sizes, uint8_t* const* outputs,
@@ -441,7 +474,9 @@ int32_t BrotliMi355xCompressBatchWithDictionaryEx(int quality, int lgwin, Brotli
    16)) runs on the device as ONE wavefront: it empties H10 trees of its own, files its item's dictionary into them -- every
    position with 127 bytes behind it, the 64 lanes each owning the hash keys of one class, which leaves exactly the trees of the
    reference's one loop --, stitches, and walks the item the reference's way from position D.  There is no tree image per
-   dictionary: a call in which every item names one index takes this route all the same, every chain with its own copy.  Every
+   dictionary.  A call in which every item names ONE index has one: it is BrotliMi355xCompressBatchWithDictionaryEx with
+   BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_SHARED_DICTIONARY_ITEMS and that dictionary -- the image of its trees is built once per call
+   and every chain copies it over its own table instead of filing the dictionary (same bytes; equal info between the calls).  Every
    other item -- the empty one, longer items, dict_sizes[k] <= 1, more than 65 536 bytes in use -- runs by itself through the
    stream path.  The bit changes nothing at qualities 0 .. 9.  Such items count in info[1], their groups (at most 1024 items) in
    info[4]; info[2], info[5] as below; info[6] and info[7] stay 0.  An item on which the reference's quality 10 / 11 parse itself
@@ -519,6 +554,9 @@ int32_t BrotliMi355xCompressBatchWithDictionaryEx(int quality, int lgwin, Brotli
 /* known to BrotliMi355xCompressBatchWithDictionaryEx, BrotliMi355xCompressBatchWithDictionaries and its device form; an unknown
    route of BrotliMi355xCompressBatchEx and BrotliMi355xCompressBatchDevice.  (2048u is taken by no route and stays unknown.) */
 #define BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS 4096u
+/* known to BrotliMi355xCompressBatchWithDictionaryEx only: there it is what 1024u is here, as 4u there is what 512u is here.  An
+   unknown route of this call, of its device form and of every other batch entry point. */
+#define BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_SHARED_DICTIONARY_ITEMS 8192u
 int32_t BrotliMi355xCompressBatchWithDictionaries(int quality, int lgwin, BrotliEncoderMode mode, uint32_t routes, size_t num_dicts,
                                                   const uint8_t* const* dicts, const size_t* dict_sizes, size_t count,
                                                   const size_t* item_dicts /* may be NULL */, const uint8_t* const* inputs,
@@ -539,7 +577,7 @@ int32_t BrotliMi355xCompressBatchWithDictionaries(int quality, int lgwin, Brotli
    count; any other route bit, an index >= num_dicts, or item_dicts == NULL with num_dicts != count fails the whole call before any
    work is done (returns 0, every size 0, only info[0] set, nothing written to device memory); when every item names one index the
    call takes the shared-image path (the shared route of qualities 5 .. 8, with their bits the quick shared route and the shared
-   route of quality 9; the Zopfli route of qualities 10 / 11 has no image and files a copy per chain), the dictionary reaching its image by one copy on the device; BrotliMi355xLastBatchInfo means what it means for the host call and has the same
+   route of quality 9, and with its bit the Zopfli route of qualities 10 / 11, whose image is the dictionary's H10 trees), the dictionary reaching its image by one copy on the device; BrotliMi355xLastBatchInfo means what it means for the host call and has the same
    values on the same data; BrotliMi355xLastError carries "the reference encoder fails on this input" for the items that fail that way.
    On the side-by-side routes (info[1]) nothing crosses the bus: one launch per group reads every item and every dictionary
    where it lies -- no page-locked staging, no dictionary pool, no upload -- and lays out dictionary | item per item on the device;

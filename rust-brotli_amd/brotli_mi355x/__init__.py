@@ -201,6 +201,7 @@ class Library(object):
     BATCH_ROUTE_QUICK_DICTIONARY_ITEMS = 512  # BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS (compress_batch_with_dictionaries only)
     BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS = 1024  # BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS (compress_batch_with_dictionaries only)
     BATCH_ROUTE_Q9_DICTIONARY_ITEMS = 4096  # BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS (the dictionary calls, shared and per item; 2048 is no route)
+    BATCH_ROUTE_ZOPFLI_SHARED_DICTIONARY_ITEMS = 8192  # BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_SHARED_DICTIONARY_ITEMS (compress_batch_with_dictionary only)
 
     def compress_batch(self, items, quality=0, lgwin=22, mode=0, dictionary=None, long_items=False, quick_items=False, quick_long_items=False,
                        zopfli_items=False, q9_items=False):
@@ -308,7 +309,7 @@ class Library(object):
             raise e
         return streams
 
-    def compress_batch_with_dictionary(self, items, dictionary, quality=5, lgwin=22, mode=0, quick_items=False, q9_items=False):
+    def compress_batch_with_dictionary(self, items, dictionary, quality=5, lgwin=22, mode=0, quick_items=False, q9_items=False, zopfli_items=False):
         """BrotliMi355xCompressBatchWithDictionaryEx: every item is the stream of an Encoder(params, dictionary) that gets the item
         in one finish(), as compress_batch(..., dictionary=dictionary) gives it; a decoder needs the same dictionary.  Returns a
         list of bytes.
@@ -327,6 +328,14 @@ class Library(object):
         item by item; longer items and the empty item still do.  It changes nothing at the other qualities and may be combined
         with quick_items.  A chain lasts its item's time however many run beside it: see include/brotli_mi355x.h for when it pays.
 
+        zopfli_items=True: BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_SHARED_DICTIONARY_ITEMS -- at qualities 10 AND 11 (through the stream
+        API, which defines these items, both are Zopfli) and lgwin 10 to 24 the items of 1 to 65 536 bytes behind a dictionary of
+        at least 2 bytes, of which at most 65 536 are in use, run side by side: one wavefront each on H10 trees of its own, over
+        which it copies the ONE image of the dictionary's trees that the call builds, and then walks the item the reference's way
+        (the same bytes).  Without it these qualities run item by item; longer items and the empty item still do.  It changes
+        nothing at qualities 0 to 9 and may be combined with the other two.  A walk is one wavefront and lasts tens of
+        microseconds per byte: it pays with hundreds of items in a call, see include/brotli_mi355x.h.
+
         Items the reference itself fails on: behind a dictionary a match cut to one byte at the dictionary's end is a copy the
         reference cannot encode, and its stream call fails.  Such an item fails alone in the C call, which then returns 0 -- and
         this method raises BrotliCompressorException although every other stream was produced.  It is not rare at quality 2 on
@@ -336,6 +345,7 @@ class Library(object):
         the dictionary."""
         routes = self.BATCH_ROUTE_QUICK_ITEMS if quick_items else 0
         routes |= self.BATCH_ROUTE_Q9_DICTIONARY_ITEMS if q9_items else 0
+        routes |= self.BATCH_ROUTE_ZOPFLI_SHARED_DICTIONARY_ITEMS if zopfli_items else 0
         dictionary = bytes(dictionary)
 
         def call(count, inputs, in_sizes, outputs, out_sizes, results):
@@ -372,8 +382,9 @@ class Library(object):
         which defines these items, both are Zopfli) and lgwin 10 to 24 the items of 1 to 65 536 bytes behind a dictionary of at
         least 2 bytes, of which at most 65 536 are in use, run side by side: one wavefront each that empties H10 trees of its
         own, files its item's dictionary into them wave-wide and walks the item the reference's way (the same bytes).  Without it
-        these qualities run item by item.  There is no shared tree image: a call in which every item names one index takes the
-        route all the same.  It changes nothing at qualities 0 to 9 and may be combined with quick_items.  A walk is one
+        these qualities run item by item.  There is no tree image per dictionary; when every item names the same index the call
+        is compress_batch_with_dictionary(items, that dictionary, zopfli_items=True), whose chains replay one image of it.  It
+        changes nothing at qualities 0 to 9 and may be combined with quick_items.  A walk is one
         wavefront and lasts tens of microseconds per byte: it pays with hundreds of items in a call, see include/brotli_mi355x.h.
 
         q9_items=True: BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS -- at quality 9 and lgwin 17 to 24 the items of 1 to 65 536
@@ -382,6 +393,14 @@ class Library(object):
         bytes).  Without it quality 9 runs item by item.  It changes nothing at the other qualities and may be combined with the
         other two flags.  When every item names the same index the call is compress_batch_with_dictionary(items, that
         dictionary, q9_items=True).  The strongest greedy level for (old version, new file) pairs where Zopfli is too slow.
+
+        zopfli_items=True: BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_SHARED_DICTIONARY_ITEMS -- at qualities 10 AND 11 (through the stream
+        API, which defines these items, both are Zopfli) and lgwin 10 to 24 the items of 1 to 65 536 bytes behind a dictionary of
+        at least 2 bytes, of which at most 65 536 are in use, run side by side: one wavefront each on H10 trees of its own, over
+        which it copies the ONE image of the dictionary's trees that the call builds, and then walks the item the reference's way
+        (the same bytes).  Without it these qualities run item by item; longer items and the empty item still do.  It changes
+        nothing at qualities 0 to 9 and may be combined with the other two.  A walk is one wavefront and lasts tens of
+        microseconds per byte: it pays with hundreds of items in a call, see include/brotli_mi355x.h.
 
         Items the reference itself fails on: behind a dictionary a match cut to one byte at the dictionary's end is a copy the
         reference cannot encode, and its stream call fails.  Such an item fails alone in the C call, which then returns 0 -- and
@@ -512,8 +531,9 @@ class Library(object):
                                               q9_items=False):
         """compress_batch_with_dictionaries_device with ONE dictionary, (address, size) in device memory, named by every item: the
         call takes the shared-image path -- the streams of compress_batch_with_dictionary(items, dictionary, ..., quick_items),
-        the dictionary reaching its image by one copy on the device (zopfli_items=True at qualities 10 and 11: no image, every chain
-        files its own copy; q9_items=True at quality 9: the image replayed over H9 tables).  Returns the list of stream sizes."""
+        the dictionary reaching its image by one copy on the device (zopfli_items=True at qualities 10 and 11: one image of the
+        dictionary's H10 trees, built once per call and copied by every chain over its own table; q9_items=True at quality 9: the
+        image replayed over H9 tables).  Returns the list of stream sizes."""
         inputs = list(inputs)
         return self.compress_batch_with_dictionaries_device(inputs, outputs, [dictionary], [0] * len(inputs), quality, lgwin, mode, quick_items, zopfli_items, q9_items)
 

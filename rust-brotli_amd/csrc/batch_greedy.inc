@@ -1022,8 +1022,9 @@ bool BatchZopfliDictionaryEligible(const EncoderParams& user, size_t dict_size, 
 }
 
 // Qualities 10 and 11 behind a dictionary per item (batch_zopfli.h), items of one block: the steps of BatchZopfliCompress with the
-// pool step of CompressGroupsWithDictionaries (StageDictsText).  There is no tree image to share: every chain empties its hasher
-// and files its item's dictionary itself (br_zopfli_batch_prepend), also where every item names the same one.
+// pool step of CompressGroupsWithDictionaries (StageDictsText).  No tree image per dictionary: every chain empties its hasher and
+// files its item's dictionary itself (br_zopfli_batch_prepend).  (A call in which every item names ONE dictionary has an image:
+// BatchZopfliCompressWithDictionary below.)
 void BatchZopfliCompressWithDictionaries(const EncoderParams& user, size_t count, const uint8_t* const* dicts, const size_t* dict_sizes,
                                          const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
                                          std::vector<uint8_t>* reference_fails, uint32_t* groups, const BatchDeviceSink* sink) {
@@ -1069,6 +1070,97 @@ void BatchZopfliCompressWithDictionaries(const EncoderParams& user, size_t count
     J.counter = g.mem.zeroed<uint32_t>(64);
     J.records = g.mem.uninit<BatchRecord>((size_t)g.n * sizeof(BatchRecord));
     lz77_zopfli_batch_parse_dicts(J);
+    BatchParseJob G{};  // what the gather wants (GatherJobOf); the raw commands carry distances, so it needs no D
+    G.P = J.P;
+    G.slabs = J.slabs;
+    G.items = J.items;
+    G.n_items = J.n_items;
+    G.records = J.records;
+    FinishOneBlockItems(p, G, g, streams, reference_fails, sink);
+    first = g.last;
+  }
+}
+
+// Qualities 10 and 11 behind ONE dictionary that every item names (batch_zopfli.h), items of one block: the steps above with the
+// dictionary steps of CompressGroups.  Once per call the dictionary goes up (the device mode: one device copy) and its tree image
+// is built in call-scoped memory (lz77_zopfli_dict_image: the buckets and at most 8 << 16 bytes of forest, 1 MiB in all); a group
+// stages dictionary | item per item as the shared routes of the other qualities do, and every chain replays the image
+// (k_zopfli_batch_dict).  Groups, tables and the forest's size are those of BatchZopfliCompressWithDictionaries.
+void BatchZopfliCompressWithDictionary(const EncoderParams& user, const uint8_t* dict, size_t dict_use, size_t count, const uint8_t* const* inputs,
+                                       const size_t* sizes, std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* reference_fails,
+                                       uint32_t* groups, const BatchDeviceSink* sink) {
+  streams->assign(count, std::vector<uint8_t>());
+  reference_fails->assign(count, 0);
+  *groups = 0;
+  if (count == 0) return;
+  const EncoderParams p = DictionaryItemParams(user, sizes[0]);  // (nothing in the parameters differs between items of at most one block)
+  if (dict_use < 2 || dict_use > ((size_t)1 << 16) || dict_use > ((size_t)1 << p.lgwin) - 16)
+    throw std::runtime_error("brotli_mi355x: a dictionary the Zopfli batch chains do not take");
+  const uint32_t D = (uint32_t)dict_use;
+  // measurement only (DESIGN.md section 10): no image, every chain files the dictionary itself (k_zopfli_batch_dicts)
+  static const bool self_file = EnvSize("BROTLI_MI355X_BATCH_DICT_SELF_FILE", 0) != 0;
+  static const bool prepend_lane0 = EnvSize("BROTLI_MI355X_ZOPFLI_PREPEND_LANE0", 0) != 0;
+  ZopfliBatchJob chains{};
+  chains.P = ChainParams(p);
+  chains.P.hasher_kind = 6;  // (as BatchZopfliCompress)
+  chains.quality = (uint32_t)p.quality;
+  chains.lgwin = (uint32_t)p.lgwin;
+  chains.use_dictionary = 0;  // (no static dictionary behind a custom one)
+  chains.dist_alphabet_size = p.dist.alphabet_size;
+  chains.prepend_lane0 = prepend_lane0 ? 1 : 0;
+  chains.dict_bytes = D;
+
+  DevBlocks call_mem;
+  // (shifted so that it ends on a 16-byte boundary, like its copies in the padded text: k_batch_dict_text moves whole words)
+  uint8_t* dict_shifted = call_mem.zeroed<uint8_t>((size_t)D + 16 + 64);
+  uint8_t* dict_dev = dict_shifted + ((0u - D) & 15u);
+  if (sink) batch_copy_device(dict_dev, dict, D); else dev_h2d_bulk(dict_dev, dict, D);  // (the device mode: `dict` is a device address)
+  if (!self_file) {
+    uint16_t* classes = call_mem.uninit<uint16_t>((size_t)zopfli_dict_image_class_entries(D) * 2 + 64);
+    uint32_t* image_buckets = call_mem.uninit<uint32_t>(((size_t)4 << 17) + 64);
+    uint32_t* image_forest = call_mem.uninit<uint32_t>((size_t)8 * zopfli_dict_image_slots(D, chains.lgwin) + 64);
+    lz77_zopfli_dict_image(dict_dev, D, chains.lgwin, classes, image_buckets, image_forest);
+    chains.image_buckets = image_buckets;
+    chains.image_forest = image_forest;
+  }
+
+  CallArrays A;
+  size_t first = 0;
+  while (first < count) {
+    Group g;
+    StageGroup(first, count, inputs, sizes, DictSizes(D, dict_dev), kZopfliBatchResident, &A, &g, kBatchHqGroupItems, sink != nullptr);
+    ++*groups;
+    uint8_t* text = g.dict_text;  // (the device mode: laid out with the staging, from the call's own copy of the dictionary)
+    if (!text) {
+      text = g.mem.zeroed<uint8_t>(g.padded + 64);
+      uint32_t* starts_dev = g.mem.uninit<uint32_t>((size_t)g.n * 4);
+      dev_h2d(starts_dev, A.starts.data(), (size_t)g.n * 4);
+      lz77_batch_dict_text(dict_shifted, D, g.uploaded, starts_dev, g.items_dev, g.n, text);
+    }
+    ZopfliBatchJob J = chains;
+    const uint32_t largest_item = A.items[A.order[0]].bytes;  // (behind one dictionary the order by dictionary + item is the order by item)
+    zopfli_batch_layout(&J, largest_item, D + largest_item);
+    g.tables = (uint32_t)std::min<size_t>(std::min<size_t>(kZopfliBatchResident, TablesMax(J.table_bytes)), g.n);
+    J.table_mem = g.mem.uninit<uint8_t>((size_t)g.tables * J.table_bytes + 256);
+    J.text = text;
+    J.slabs = g.mem.uninit<Command>(g.cmd_slots * sizeof(Command) + 64);
+    J.items = g.items_dev;
+    J.order = g.order_dev;
+    J.n_items = g.n;
+    J.tables = g.tables;
+    J.counter = g.mem.zeroed<uint32_t>(64);
+    J.records = g.mem.uninit<BatchRecord>((size_t)g.n * sizeof(BatchRecord));
+    if (self_file) {
+      uint32_t* dict_bytes_dev = g.dict_bytes_dev;  // (the device mode: StageGroup has sent A.dict_bytes up)
+      if (!dict_bytes_dev) {
+        dict_bytes_dev = g.mem.uninit<uint32_t>((size_t)g.n * 4);
+        dev_h2d(dict_bytes_dev, A.dict_bytes.data(), (size_t)g.n * 4);
+      }
+      J.item_dict_bytes = dict_bytes_dev;
+      lz77_zopfli_batch_parse_dicts(J);
+    } else {
+      lz77_zopfli_batch_parse_dict(J);
+    }
     BatchParseJob G{};  // what the gather wants (GatherJobOf); the raw commands carry distances, so it needs no D
     G.P = J.P;
     G.slabs = J.slabs;

@@ -62,6 +62,11 @@ struct ZopfliBatchJob {
   // is the item_dict_bytes[i] bytes that end where the item starts.  nullptr: no dictionaries (k_zopfli_batch)
   const uint32_t* item_dict_bytes;  // [n_items], device
   uint32_t prepend_lane0;           // the dictionary goes into the trees on lane 0 alone (the measured alternative), not wave-wide
+  // one dictionary that every item names (k_zopfli_batch_dict): `text` is staged the same way, every item behind the dict_bytes
+  // bytes of the call's dictionary, and a chain replays the call's tree image (lz77_zopfli_dict_image) instead of filing them
+  const uint32_t* image_buckets;  // [1 << 17]
+  const uint32_t* image_forest;   // [2 * zopfli_dict_image_slots(dict_bytes, lgwin)], 16-byte aligned
+  uint32_t dict_bytes;
   // the layout of a table (zopfli_batch_layout): byte offsets, multiples of 256
   uint32_t cap;   // the group's largest item rounded up to 64
   uint32_t span;  // the positions the forest has slots for: the group's largest dictionary + item rounded up to 64, at most 1 << lgwin
@@ -105,6 +110,27 @@ void lz77_zopfli_batch_parse(const ZopfliBatchJob& J);
 // ... behind a dictionary per item (J.item_dict_bytes): every chain empties its hasher, files its item's dictionary wave-wide
 // (br_zopfli_batch_prepend), stitches and walks the item from position D
 void lz77_zopfli_batch_parse_dicts(const ZopfliBatchJob& J);
+// ... behind the one dictionary of the call (J.dict_bytes, J.image_buckets, J.image_forest): every chain copies the image over
+// its buckets and the dictionary's part of its forest (br_zopfli_batch_replay), stitches and walks the item from position D
+void lz77_zopfli_batch_parse_dict(const ZopfliBatchJob& J);
+
+// The tree image of a dictionary of D bytes in use at `lgwin`: what br_zopfli_batch_reset(B, lgwin, D) and the prepend of the D
+// bytes leave in the buckets and in the forest slots of the positions below D rounded up to 64 (at most 1 << lgwin).  It hangs on
+// the dictionary alone -- a Store of position i, i + 127 < D, compares at most 128 bytes, all of them the dictionary's -- so one
+// image serves every item of a call.
+constexpr uint32_t zopfli_dict_image_slots(uint32_t D, uint32_t lgwin) {
+  const uint32_t rounded = (D + 63u) & ~63u;
+  return rounded < (1u << lgwin) ? rounded : (1u << lgwin);
+}
+// the positions the prepend stores: [0, D - 127)
+constexpr uint32_t zopfli_dict_image_stored(uint32_t D) { return D >= 128u ? D - 127u : 0u; }
+// entries of the class array the build writes in front of its stores (zopfli_dict_image_stored rounded up to 16)
+constexpr uint32_t zopfli_dict_image_class_entries(uint32_t D) { return (zopfli_dict_image_stored(D) + 15u) & ~15u; }
+// dict: the D bytes, the 4-byte loads of the stored positions end inside them; classes: [zopfli_dict_image_class_entries(D)],
+// scratch; buckets: [1 << 17]; forest: [2 * zopfli_dict_image_slots(D, lgwin)], 16-byte aligned.  All device memory, all written
+// here: a fill launch (every bucket the invalid position, the forest 0), the class of every stored position, and the store launch
+// in which lanes that own disjoint classes of hash keys file their positions in ascending order.  D <= (1 << lgwin) - 16.
+void lz77_zopfli_dict_image(const uint8_t* dict, uint32_t D, uint32_t lgwin, uint16_t* classes, uint32_t* buckets, uint32_t* forest);
 
 // ---- host
 // Does this item go side by side under the Zopfli route?  `params`: the caller's parameters as set, not finalized.
@@ -124,6 +150,12 @@ bool BatchZopfliDictionaryEligible(const EncoderParams& params, size_t dict_size
 void BatchZopfliCompressWithDictionaries(const EncoderParams& params, size_t count, const uint8_t* const* dicts, const size_t* dict_sizes,
                                          const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
                                          std::vector<uint8_t>* reference_fails, uint32_t* groups, const BatchDeviceSink* sink = nullptr);
+// ... behind ONE dictionary that every item names (dict / dict_size: as in use): the dictionary goes up once and its tree image is
+// built once per call; every chain replays it.  BROTLI_MI355X_BATCH_DICT_SELF_FILE=1 (measurement): no image, every chain files
+// the dictionary itself, as behind a dictionary per item.
+void BatchZopfliCompressWithDictionary(const EncoderParams& params, const uint8_t* dict, size_t dict_size, size_t count, const uint8_t* const* inputs,
+                                       const size_t* sizes, std::vector<std::vector<uint8_t>>* streams, std::vector<uint8_t>* reference_fails,
+                                       uint32_t* groups, const BatchDeviceSink* sink = nullptr);
 
 }  // namespace brotli_mi355x
 #endif

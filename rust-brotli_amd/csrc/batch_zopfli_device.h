@@ -109,16 +109,119 @@ BR_DEV void br_zopfli_batch_prepend(const ZH10& h, const ZopfliParams& Z, const 
   BR_SYNC();
 }
 
+// ---- one dictionary that every item names: its tree image, built once per call (lz77_zopfli_dict_image) ---------------------------
+// The argument above holds for any number of lanes, so the build spreads the keys over the lanes of SEVERAL wavefronts: a lane owns
+// the keys whose low ten bits are its number in the launch (kZImageClasses lanes).  No two lanes touch one word -- buckets[key] and
+// the children of the positions of that key -- and a lane reads only words that it or the fill launch in front has written, so the
+// workgroups exchange nothing: no atomics, no fences, no order between them.
+// How a lane finds its positions: with 16 times the classes, br_zopfli_prepend_next's dependent 4-byte load and multiply per
+// position would be the build's cost (every lane looks at every position).  A pass in front writes the class of every stored
+// position once, coalesced, as 16-bit entries; a lane then tests 16 positions per step -- two 16-byte loads that every lane near
+// the same cursor shares in the L1 -- and only the bit scan depends on them.
+static constexpr uint32_t kZImageClasses = 1024;
+static constexpr uint32_t kZImageNoClass = 0xffffu;  // the entries behind the last stored position
+BR_DEV ZopfliParams br_zopfli_image_params(uint32_t lgwin, uint32_t D) {
+  ZopfliParams Z{};  // what a Store looks at: it compares 128 bytes inside the dictionary, so no length is cut at dict_break
+  Z.quality = 11;
+  Z.lgwin = lgwin;
+  Z.max_backward_limit = (1u << lgwin) - 16u;
+  Z.ring_mask = 0xffffffffu;
+  Z.dict_break = D;
+  return Z;
+}
+// the fill: element `at` of `stride` -- every bucket the invalid position, the forest 0, 16 bytes per element
+BR_DEV void br_zopfli_image_fill(uint32_t* buckets, uint32_t* forest, uint32_t lgwin, uint32_t slots, uint32_t at, uint32_t stride) {
+  const uint32_t invalid = 0u - ((1u << lgwin) - 1u);
+  const uint32_t bucket_quads = (1u << kZBucketBits) / 4u, quads = bucket_quads + slots / 2u;
+  for (uint32_t q = at; q < quads; q += stride) {
+    uint32_t* w = q < bucket_quads ? buckets + 4u * (size_t)q : forest + 4u * (size_t)(q - bucket_quads);
+    const uint32_t v = q < bucket_quads ? invalid : 0u;
+    w[0] = v;
+    w[1] = v;
+    w[2] = v;
+    w[3] = v;
+  }
+}
+// the class pass: entry i of [0, entries), entries = zopfli_dict_image_class_entries(D)
+BR_DEV void br_zopfli_image_class_entry(const uint8_t* text, uint32_t end, uint16_t* classes, uint32_t i) {
+  classes[i] = (uint16_t)(i < end ? ((br_load32(text + i) * 0x1e35a7bdu) >> (32 - kZBucketBits)) & (kZImageClasses - 1u) : kZImageNoClass);
+}
+// the first position of [i, end) of class `cls`; end: none.  Reads whole groups of 16 entries: [i & ~15, ...) up to `end` rounded up.
+BR_DEV uint32_t br_zopfli_image_next(const uint16_t* classes, uint32_t i, uint32_t end, uint32_t cls) {
+  while (i < end) {
+    const uint32_t base = i & ~15u;
+    uint32_t w[8];
+#if BR_SCALAR
+    memcpy(w, classes + base, 32);
+#else
+    const uint4 a = ((const uint4*)(classes + base))[0], b = ((const uint4*)(classes + base))[1];
+    w[0] = a.x, w[1] = a.y, w[2] = a.z, w[3] = a.w, w[4] = b.x, w[5] = b.y, w[6] = b.z, w[7] = b.w;
+#endif
+    uint32_t hits = 0;
+    for (uint32_t k = 0; k < 8; ++k) hits |= ((w[k] & 0xffffu) == cls ? 1u << (2 * k) : 0u) | ((w[k] >> 16) == cls ? 2u << (2 * k) : 0u);
+    hits &= 0xffffffffu << (i & 15u);
+    if (hits != 0) return base + (uint32_t)__builtin_ctz(hits);  // (below end: the entries behind it are of no class)
+    i = base + 16u;
+  }
+  return end;
+}
+// the positions of one class, in ascending order: one lane of the store launch (the scalar build runs the classes one after the other)
+BR_DEV void br_zopfli_image_store_class(const ZH10& h, const ZopfliParams& Z, const uint8_t* text, const uint16_t* classes, uint32_t end, uint32_t cls) {
+  for (uint32_t i = br_zopfli_image_next(classes, 0, end, cls); i < end; i = br_zopfli_image_next(classes, i + 1, end, cls)) z_h10_store(h, Z, text, i);
+}
+
+// p[0 .. 4 * quads) = src[0 .. 4 * quads) by the whole wavefront, 16 bytes per lane and step, four steps in flight: the loads of a
+// round are issued together, then its stores (the loop of br_quick_batch_prime, batch_quick_device.h).  Both 16-byte aligned; `src` is read-only for the launch
+// (plain loads).  Barriers and fence are the caller's, as around a fill.
+BR_DEV void br_batch_copy16(uint32_t* p, const uint32_t* src, uint32_t quads) {
+#if BR_SCALAR
+  for (uint32_t i = 0; i < 4u * quads; ++i) p[i] = src[i];
+#else
+  uint4* w = (uint4*)p;
+  const uint4* s = (const uint4*)src;
+  for (uint32_t i = (uint32_t)BR_LANE; i < quads; i += 4u * BR_NLANES) {
+    const uint32_t i1 = i + BR_NLANES, i2 = i + 2u * BR_NLANES, i3 = i + 3u * BR_NLANES;
+    const uint4 v0 = s[i];
+    const uint4 v1 = s[i1 < quads ? i1 : i];
+    const uint4 v2 = s[i2 < quads ? i2 : i];
+    const uint4 v3 = s[i3 < quads ? i3 : i];
+    w[i] = v0;
+    if (i1 < quads) w[i1] = v1;
+    if (i2 < quads) w[i2] = v2;
+    if (i3 < quads) w[i3] = v3;
+  }
+#endif
+}
+
+// The hasher as br_zopfli_batch_reset(B, lgwin, D + bytes) and the prepend of the D dictionary bytes leave it, on a table that
+// the item in front has used: the image's buckets go over ALL buckets, its forest over the slots of the positions below D rounded
+// up to 64, and the slots from there to the item's end are zeroed.  Wave-wide, 16 bytes per lane and step; the image is read-only
+// for the launch (plain loads).  Made visible, and waited for, as the reset is.
+BR_DEV void br_zopfli_batch_replay(const ZopfliBuffers& B, const uint32_t* image_buckets, const uint32_t* image_forest, uint32_t lgwin, uint32_t D,
+                                   uint32_t bytes) {
+  const uint32_t s_dict = zopfli_dict_image_slots(D, lgwin), s_all = zopfli_dict_image_slots(D + bytes, lgwin);
+  BR_SYNC();
+  br_batch_copy16(B.buckets, image_buckets, (1u << kZBucketBits) / 4u);
+  br_batch_copy16(B.forest, image_forest, s_dict / 2u);
+  br_batch_fill16(B.forest + 2u * (size_t)s_dict, (s_all - s_dict) / 2u, 0u);
+#if !BR_SCALAR
+  __threadfence();
+#endif
+  BR_SYNC();
+}
+
 // histo: 256 words and fast: the node window, the cost tables and the queue, all the wavefront's own (LDS on the device; the
 // emulation passes an array and an empty ZFast).
-// kDicts: the item's text starts with J.item_dict_bytes[index] bytes of custom dictionary of its own
-// (BrotliMi355xCompressBatchWithDictionaries under BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS): position 0 is the
-// dictionary's first byte, the item starts at D, and the chain files the dictionary itself.
-template <bool kDicts = false>
+// kDict: the item's text starts with D bytes of custom dictionary: position 0 is the dictionary's first byte, the item starts at D.
+//   kZBatchItemDicts  a dictionary of the item's own, D = J.item_dict_bytes[index] (BrotliMi355xCompressBatchWithDictionaries under
+//                     BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS): the chain files it itself
+//   kZBatchSharedDict the call's one dictionary, D = J.dict_bytes: the chain replays the call's image of it
+enum : int { kZBatchNoDict = 0, kZBatchItemDicts = 1, kZBatchSharedDict = 2 };
+template <int kDict = kZBatchNoDict>
 BR_DEV void br_zopfli_batch_item(const ZopfliBatchJob& J, const ZopfliTables& T, uint32_t* histo, const ZFast& fast, uint32_t index, uint32_t table) {
   const BatchItem it = br_batch_load_item(J.items, index);
-  if constexpr (kDicts) {
-    const uint32_t D = BR_UNIFORM(J.item_dict_bytes[index]);
+  if constexpr (kDict != kZBatchNoDict) {
+    const uint32_t D = kDict == kZBatchSharedDict ? J.dict_bytes : BR_UNIFORM(J.item_dict_bytes[index]);
     // (never: the plan sizes the forest by the group's largest dictionary + item, and a dictionary in use ends 16 bytes below the window)
     const bool fits = it.bytes <= J.cap && (D + it.bytes <= J.span || J.span == (1u << J.lgwin)) && D + 16u <= (1u << J.lgwin);
     if (!fits) {
@@ -137,9 +240,13 @@ BR_DEV void br_zopfli_batch_item(const ZopfliBatchJob& J, const ZopfliTables& T,
     ZBlockCtl* ctl = (ZBlockCtl*)(base + J.off_ctl);
     SegExit* exit_slot = (SegExit*)(base + J.off_exit);
     const uint8_t* text = J.text + it.text_off - D;
-    br_zopfli_batch_reset(B, J.lgwin, D + it.bytes);
     const ZH10 h = z_hasher_of(Z, B);
-    br_zopfli_batch_prepend(h, Z, text, D, J.prepend_lane0 != 0);
+    if constexpr (kDict == kZBatchSharedDict) {
+      br_zopfli_batch_replay(B, J.image_buckets, J.image_forest, J.lgwin, D, it.bytes);
+    } else {
+      br_zopfli_batch_reset(B, J.lgwin, D + it.bytes);
+      br_zopfli_batch_prepend(h, Z, text, D, J.prepend_lane0 != 0);
+    }
     // StitchToPreviousBlockH10 as br_zopfli_begin runs it for a block behind a prefix (all lanes, identical state); a fresh
     // stream has no last command to extend
     z_h10_stitch(h, Z, text, it.bytes, D);

@@ -1371,8 +1371,9 @@ static std::vector<uint8_t> DownloadBytes(const uint8_t* device, size_t bytes) {
 }
 
 // The one body of the dictionary batch calls, entered with what its entry refuses (`refused`, made before any device address is
-// looked at), with quick_route, the entry's own bit for the side-by-side route of qualities 2 .. 4, with zopfli_route, the bit
-// of the per-item entries for the one of qualities 10 and 11 (BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS), and with q9_route,
+// looked at), with quick_route, the entry's own bit for the side-by-side route of qualities 2 .. 4, with zopfli_route, the entry's
+// own bit for the one of qualities 10 and 11 (BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS on the per-item entries,
+// BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_SHARED_DICTIONARY_ITEMS on the shared one: the pairing of 512 and 4), and with q9_route,
 // the bit of all three entries for the one of quality 9 (BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS).  Item i lies behind
 // dicts[all_first ? 0 : item_dicts ? item_dicts[i] : i].  on_device: dicts[k], inputs[i] and outputs[i] are device addresses (the
 // arrays themselves are host memory) -- the side-by-side routes read every dictionary and item where it lies and leave the streams
@@ -1412,8 +1413,9 @@ static int32_t CompressBatchWithDictionaries(const char* entry, int quality, int
     // lgwin 10 .. 24, behind at most 65536 dictionary bytes in use (batch_quick.h), or of 1 .. 65536 bytes at qualities 10 and 11
     // behind at most 65536 dictionary bytes in use (batch_zopfli.h), or of 1 .. 65536 bytes at quality 9, lgwin 17 .. 24, behind at
     // most 65536 dictionary bytes in use (batch_q9.h) -- a call has one quality, so its items take one of the four.  Every other
-    // item goes through the stream path by itself with its own dictionary, on this thread, in the caller's order.  The Zopfli
-    // route has no shared tree image: its chains file their own copy also where every item names one index.
+    // item goes through the stream path by itself with its own dictionary, on this thread, in the caller's order.  Where every
+    // item names one index the Zopfli route, like the others, builds one image of that dictionary per call and its chains replay
+    // it (BatchZopfliCompressWithDictionary); behind several dictionaries its chains file their own.
     bool quick = false, zopfli = false, q9 = false;
     BatchItems r;
     // on_device: the bytes in use of the dictionaries that items running one by one name, each down once per call
@@ -1430,7 +1432,7 @@ static int32_t CompressBatchWithDictionaries(const char* entry, int quality, int
       if (q9_item) q9 = true;
       if (greedy_item || quick_item || zopfli_item || q9_item) {
         r.Add(i, inputs[i], input_sizes[i], outputs[i], output_sizes[i], on_device);
-        if (!one || zopfli_item) {
+        if (!one) {
           // (at qualities 5 .. 9 dict_sizes[k] itself: an eligible dictionary is below every window's limit; at lgwin 10 .. 16 its
           // last (1 << lgwin) - 16 bytes)
           r.dict.push_back(dicts[k] + (dict_sizes[k] - in_use(k)));
@@ -1455,11 +1457,11 @@ static int32_t CompressBatchWithDictionaries(const char* entry, int quality, int
     BatchFlags reference_fails;
     uint32_t groups = 0;
     const BatchDeviceSink* sink = r.Sink(on_device, StreamDeliveryRule);
-    if (zopfli)
+    if (zopfli && !one)
       BatchZopfliCompressWithDictionaries(params, r.item.size(), r.dict.data(), r.dict_size.data(), r.in.data(), r.size.data(), &streams, &reference_fails,
                                           &groups, sink);
     else if (one)
-      (quick ? BatchQuickCompressWithDictionary : q9 ? BatchQ9CompressWithDictionary : BatchGreedyCompressWithDictionary)(
+      (zopfli ? BatchZopfliCompressWithDictionary : quick ? BatchQuickCompressWithDictionary : q9 ? BatchQ9CompressWithDictionary : BatchGreedyCompressWithDictionary)(
           params, dicts[k0] + (dict_sizes[k0] - in_use(k0)), in_use(k0), r.item.size(), r.in.data(), r.size.data(), &streams, &reference_fails, &groups, sink);
     else
       (quick ? BatchQuickCompressWithDictionaries : q9 ? BatchQ9CompressWithDictionaries : BatchGreedyCompressWithDictionaries)(
@@ -1500,11 +1502,14 @@ static int32_t CompressBatchWithSharedDictionary(const char* entry, int quality,
                                                  const uint8_t* dict, size_t count, const uint8_t* const* inputs, const size_t* input_sizes,
                                                  uint8_t* const* outputs, size_t* output_sizes, int32_t* item_results) {
   std::string refused;
-  if ((routes & ~(uint32_t)(BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS | BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS)) != 0) {
+  if ((routes & ~(uint32_t)(BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS | BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS |
+                            BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_SHARED_DICTIONARY_ITEMS)) != 0) {
     refused = "routes " + std::to_string(routes) + " names a route this call does not know (known behind a dictionary: "
-              "BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS = 4, BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS = 4096)";
+              "BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS = 4, BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS = 4096, "
+              "BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_SHARED_DICTIONARY_ITEMS = 8192)";
   }
-  return CompressBatchWithDictionaries(entry, quality, lgwin, mode, (routes & BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS) != 0, false,
+  return CompressBatchWithDictionaries(entry, quality, lgwin, mode, (routes & BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS) != 0,
+                                       (routes & BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_SHARED_DICTIONARY_ITEMS) != 0,
                                        (routes & BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS) != 0, refused, 1, &dict, &dict_size, count,
                                        nullptr, true, inputs, input_sizes, outputs, output_sizes, item_results, false);
 }

@@ -10,6 +10,7 @@
 #include <exception>
 #include <vector>
 
+#include "batch_zopfli.h"
 #include "device_api.h"
 #include "zopfli_entry_api.h"
 #if defined(BROTLI_HOST_EMU)
@@ -30,6 +31,13 @@ void zopfli_debug_prepend(const uint8_t* text, uint32_t dict_bytes, uint32_t lgw
   B.forest = forest;
   br_zopfli_batch_reset(B, lgwin, dict_bytes);
   br_zopfli_batch_prepend(z_hasher_of(Z, B), Z, text, dict_bytes, mode == 0);
+}
+void zopfli_debug_replay(const uint32_t* image_buckets, const uint32_t* image_forest, uint32_t lgwin, uint32_t dict_bytes, uint32_t item_bytes,
+                         uint32_t* buckets, uint32_t* forest) {
+  ZopfliBuffers B{};
+  B.buckets = buckets;
+  B.forest = forest;
+  br_zopfli_batch_replay(B, image_buckets, image_forest, lgwin, dict_bytes, item_bytes);
 }
 }  // namespace brotli_mi355x
 #endif
@@ -167,24 +175,42 @@ int brotli_mi355x_debug_cost_from_histogram(uint32_t n_jobs, const uint32_t* siz
 // HasherPrependCustomDictionary for H10 as the batch item of qualities 10 / 11 runs it (batch_zopfli_device.h), on a hasher that
 // br_zopfli_batch_reset has emptied: the first dict_bytes bytes of `text` are the dictionary (n_text >= dict_bytes: a Store
 // compares bytes of the dictionary only, what follows is carried along as the item would be).  mode 0: the loop of k_zopfli_prepend
-// on lane 0; mode 1: the batch item's wave-wide partition on one wavefront.  Out: the buckets (1 << 17 words) and the forest, 2
-// words for each of min(dict_bytes rounded up to 64, 1 << lgwin) positions.  Refused: mode > 1, lgwin outside 10 .. 24,
-// dict_bytes > n_text or > (1 << lgwin) - 16, more than 16 MiB of text.
+// on lane 0; mode 1: the batch item's wave-wide partition on one wavefront; mode 2: the tree image of the shared dictionary as the
+// call builds it (lz77_zopfli_dict_image: fill, class pass, store launch of several workgroups).  Out: the buckets (1 << 17 words)
+// and the forest, 2 words for each of min(dict_bytes rounded up to 64, 1 << lgwin) positions.
+// mode 3: that image, built and then replayed (br_zopfli_batch_replay) in front of an item of n_text - dict_bytes bytes over buckets
+// and a forest that hold 0xA5 bytes.  Out: the buckets and 2 forest words for each of min(n_text rounded up to 64, 1 << lgwin)
+// positions -- the caller sizes out_forest by n_text here.
+// Refused: mode > 3, lgwin outside 10 .. 24, dict_bytes > n_text or > (1 << lgwin) - 16, more than 16 MiB of text.
 int brotli_mi355x_debug_zopfli_prepend(const uint8_t* text, uint32_t n_text, uint32_t dict_bytes, uint32_t lgwin, uint32_t mode, uint32_t* out_buckets,
                                        uint32_t* out_forest) {
-  if (mode > 1 || lgwin < 10 || lgwin > 24 || !text || !out_buckets || !out_forest) return -1;
+  if (mode > 3 || lgwin < 10 || lgwin > 24 || !text || !out_buckets || !out_forest) return -1;
   if (n_text == 0 || n_text > (16u << 20) || dict_bytes > n_text || dict_bytes > (1u << lgwin) - 16u) return -1;
-  const size_t rounded = ((size_t)dict_bytes + 63) & ~(size_t)63;
-  const size_t slots = rounded < ((size_t)1 << lgwin) ? rounded : ((size_t)1 << lgwin);
+  const size_t slots = zopfli_dict_image_slots(dict_bytes, lgwin);
+  const size_t out_slots = mode == 3 ? zopfli_dict_image_slots(n_text, lgwin) : slots;
   try {
     DevMem mm;
     uint8_t* text_dev = mm.alloc<uint8_t>((size_t)n_text + kZEntryTextPadding);  // (zero-filled)
     uint32_t* buckets_dev = mm.alloc<uint32_t>((size_t)1 << 17);
     uint32_t* forest_dev = mm.alloc<uint32_t>(2 * slots + 64);
     dev_h2d(text_dev, text, n_text);
-    zopfli_debug_prepend(text_dev, dict_bytes, lgwin, mode, buckets_dev, forest_dev);
+    if (mode >= 2) {
+      uint16_t* classes_dev = mm.alloc<uint16_t>((size_t)zopfli_dict_image_class_entries(dict_bytes) + 64);
+      lz77_zopfli_dict_image(text_dev, dict_bytes, lgwin, classes_dev, buckets_dev, forest_dev);
+    } else {
+      zopfli_debug_prepend(text_dev, dict_bytes, lgwin, mode, buckets_dev, forest_dev);
+    }
+    if (mode == 3) {
+      uint32_t* table_buckets = mm.alloc<uint32_t>((size_t)1 << 17);
+      uint32_t* table_forest = mm.alloc<uint32_t>(2 * out_slots + 64);
+      dev_memset(table_buckets, 0xA5, ((size_t)1 << 17) * 4);
+      dev_memset(table_forest, 0xA5, (2 * out_slots + 64) * 4);
+      zopfli_debug_replay(buckets_dev, forest_dev, lgwin, dict_bytes, n_text - dict_bytes, table_buckets, table_forest);
+      buckets_dev = table_buckets;
+      forest_dev = table_forest;
+    }
     dev_d2h(out_buckets, buckets_dev, ((size_t)1 << 17) * 4);
-    if (slots) dev_d2h(out_forest, forest_dev, 2 * slots * 4);
+    if (out_slots) dev_d2h(out_forest, forest_dev, 2 * out_slots * 4);
     return 0;
   } catch (const std::exception&) {
     return -2;

@@ -31,6 +31,10 @@ void zopfli_debug_cost_from_histogram(uint32_t n_jobs, const uint32_t* sizes, co
 // mode 0 the loop of k_zopfli_prepend on lane 0, mode 1 the wave-wide partition of the batch item -- on buckets [1 << 17] and
 // forest [2 * forest slots], forest slots = min(dict_bytes rounded up to 64, 1 << lgwin)
 void zopfli_debug_prepend(const uint8_t* text, uint32_t dict_bytes, uint32_t lgwin, uint32_t mode, uint32_t* buckets, uint32_t* forest);
+// the shared dictionary's tree image (batch_zopfli.h: lz77_zopfli_dict_image; tests/test_batch_dictionary_zopfli.py) replayed by one
+// 64-lane workgroup over a table that holds something else: br_zopfli_batch_replay in front of an item of item_bytes bytes
+void zopfli_debug_replay(const uint32_t* image_buckets, const uint32_t* image_forest, uint32_t lgwin, uint32_t dict_bytes, uint32_t item_bytes,
+                         uint32_t* buckets, uint32_t* forest);
 
 }  // namespace brotli_mi355x
 #endif

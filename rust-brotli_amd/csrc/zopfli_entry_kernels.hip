@@ -127,6 +127,20 @@ __global__ __launch_bounds__(64) void k_zdebug_prepend(ZopfliParams Z, const uin
   br_zopfli_batch_reset(B, Z.lgwin, dict_bytes);
   br_zopfli_batch_prepend(z_hasher_of(Z, B), Z, text, dict_bytes, mode == 0);
 }
+// mode 3: one wavefront replays the image over a table of 0xA5 bytes, as a chain does in front of an item of item_bytes bytes
+__global__ __launch_bounds__(64) void k_zdebug_replay(const uint32_t* __restrict__ image_buckets, const uint32_t* __restrict__ image_forest, uint32_t lgwin,
+                                                      uint32_t dict_bytes, uint32_t item_bytes, uint32_t* buckets, uint32_t* forest) {
+  if (blockIdx.x != 0) return;
+  ZopfliBuffers B{};
+  B.buckets = buckets;
+  B.forest = forest;
+  br_zopfli_batch_replay(B, image_buckets, image_forest, lgwin, dict_bytes, item_bytes);
+}
+void zopfli_debug_replay(const uint32_t* image_buckets, const uint32_t* image_forest, uint32_t lgwin, uint32_t dict_bytes, uint32_t item_bytes,
+                         uint32_t* buckets, uint32_t* forest) {
+  hipLaunchKernelGGL(k_zdebug_replay, dim3(1), dim3(64), 0, BR_STREAM, image_buckets, image_forest, lgwin, dict_bytes, item_bytes, buckets, forest);
+  HIP_CHECK(hipGetLastError());
+}
 void zopfli_debug_prepend(const uint8_t* text, uint32_t dict_bytes, uint32_t lgwin, uint32_t mode, uint32_t* buckets, uint32_t* forest) {
   hipLaunchKernelGGL(k_zdebug_prepend, dim3(1), dim3(64), 0, BR_STREAM, zopfli_entry_prepend_params(dict_bytes, lgwin), text, dict_bytes, mode, buckets,
                      forest);

@@ -86,6 +86,16 @@ rounds of one run each: the route; on the classes of DICTS_Q9_SHARED the shared 
 item behind the first dictionary) with the image and with BROTLI_MI355X_BATCH_DICT_SELF_FILE=1; the --parent-lib build through the per-item call
 without the bit (first --loop-items items, scaled); the loop of stream calls from four threads (the same); then the oracle on one core.
 
+With --shared-zopfli (qualities 10 and 11) the call measured is BrotliMi355xCompressBatchWithDictionaryEx with
+BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_SHARED_DICTIONARY_ITEMS (8192) on the classes of SHARED_ZOPFLI_HEADLINE, every item behind the class's first
+dictionary, in --rounds alternating rounds of one run each: the tree image (the default); BROTLI_MI355X_BATCH_DICT_SELF_FILE=1 (every chain files
+the dictionary itself); the --parent-lib build through BrotliMi355xCompressBatchWithDictionaries with 1024 and one index named by every item (the
+self-filing baseline); this build's shared entry without the bit, one by one, on the first --loop-items items, scaled.  On SHARED_ZOPFLI_LONE (one
+item of 4 KiB behind 16 and 64 KiB) the first two and BROTLI_MI355X_BATCH_DICT_SELF_FILE=1 with BROTLI_MI355X_ZOPFLI_PREPEND_LANE0=1: a lone
+chain's filing, wave-wide and on lane 0, as a difference of whole calls.  Beside them the build and the filing by themselves, through the debug
+entry brotli_mi355x_debug_zopfli_prepend: modes 0 (lane 0), 1 (wave-wide, one wavefront) and 2 (the image build) at 16 and 64 KiB, less the same
+entry at 2 bytes (allocation, the fill and the copies, which every mode pays).
+
 With --device (and --parent-lib) the call measured is BrotliMi355xCompressBatchDevice on torch tensors -- one uint8 tensor of items in,
 one of streams out -- beside the parent's BrotliMi355xCompressBatchEx on the same items from host memory and beside the "honest
 alternative" a caller with device-resident payloads has without the call: the items down (one D2H), the parent's host call, the
@@ -176,6 +186,10 @@ DICTS_CLASSES.update({"256x64KiB+64KiB": (256, 64 << 10, 64 << 10)})
 DICTS_CLASSES.update(DICTS_Q9_FEW)
 DICTS_Q9_HEADLINE = ["4096x4KiB+16KiB", "1024x16KiB+64KiB", "256x64KiB+64KiB", "64x4KiB+16KiB", "16x4KiB+16KiB"] + list(DICTS_Q9_FEW)
 DICTS_Q9_SHARED = ["4096x4KiB+16KiB"]
+# (--shared-zopfli) BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_SHARED_DICTIONARY_ITEMS: every item behind the class's first dictionary
+DICTS_CLASSES.update({"1x4KiB+64KiB": (1, 4 << 10, 64 << 10)})
+SHARED_ZOPFLI_HEADLINE = ["1024x4KiB+16KiB", "256x16KiB+64KiB", "256x4KiB+64KiB", "16x4KiB+16KiB"]
+SHARED_ZOPFLI_LONE = ["1x4KiB+16KiB", "1x4KiB+64KiB"]
 Q9_HEADLINE = ["4096x4KiB", "1024x16KiB", "256x64KiB", "64x256KiB", "16x4KiB", "64x4KiB", "4096xlog200B-256KiB"]  # (--q9-items)
 
 
@@ -282,11 +296,12 @@ def measure_batch(lib_path, items, quality, runs, warmup, dictionary=None, route
     return times, sum(out_sizes), list(info), failed
 
 
-def measure_dicts(lib_path, items, dictionaries, quality, runs, warmup, shared=False, routes=None):
+def measure_dicts(lib_path, items, dictionaries, quality, runs, warmup, shared=False, routes=None, one_index=False):
     """BrotliMi355xCompressBatchWithDictionaries with dictionaries[i] for item i; shared: BrotliMi355xCompressBatchWithDictionary with
     dictionaries[0].  At qualities 2 to 4 both with the route that takes such items side by side (512, and 4 through the Ex entry).
     routes: the bits of the per-item call (default: 512 at qualities 2 to 4, else 0; 1024 and 4096 are the caller's to give); with
-    shared they go to BrotliMi355xCompressBatchWithDictionaryEx as they are (4096: quality 9)."""
+    shared they go to BrotliMi355xCompressBatchWithDictionaryEx as they are (4096: quality 9).  one_index: the per-item call with dictionaries[0]
+    alone and item_dicts = {0, 0, ...}."""
     L = bind(lib_path)
     quick = 2 <= quality <= 4
     L.BrotliMi355xCompressBatchWithDictionaryEx.restype = ctypes.c_int32
@@ -304,6 +319,7 @@ def measure_dicts(lib_path, items, dictionaries, quality, runs, warmup, shared=F
     dicts = (ctypes.c_char_p * n)(*dictionaries)
     dict_sizes = (ctypes.c_size_t * n)(*[len(d) for d in dictionaries])
     info = (ctypes.c_uint64 * 8)()
+    named = (ctypes.c_size_t * n)() if one_index else None
     times, failed = [], []
     for it in range(warmup + runs):
         for i in range(n):
@@ -316,8 +332,8 @@ def measure_dicts(lib_path, items, dictionaries, quality, runs, warmup, shared=F
             ok = L.BrotliMi355xCompressBatchWithDictionary(quality, LGWIN, 0, ctypes.c_size_t(len(dictionaries[0])), ctypes.c_char_p(dictionaries[0]), ctypes.c_size_t(n),
                                                            inputs, in_sizes, outputs, out_sizes, results)
         else:
-            ok = L.BrotliMi355xCompressBatchWithDictionaries(quality, LGWIN, 0, ctypes.c_uint32((512 if quick else 0) if routes is None else routes), ctypes.c_size_t(n), dicts, dict_sizes, ctypes.c_size_t(n), None,
-                                                             inputs, in_sizes, outputs, out_sizes, results)
+            ok = L.BrotliMi355xCompressBatchWithDictionaries(quality, LGWIN, 0, ctypes.c_uint32((512 if quick else 0) if routes is None else routes), ctypes.c_size_t(1 if one_index else n), dicts, dict_sizes,
+                                                             ctypes.c_size_t(n), named, inputs, in_sizes, outputs, out_sizes, results)
         dt = time.perf_counter() - t
         if ok != 1:
             # items on which the reference itself fails (a copy of one byte at the dictionary end) fail alone: counted, not fatal
@@ -409,6 +425,35 @@ def measure_cpu(items, quality, runs, dictionary=None, dictionaries=None):
     return times, total
 
 
+def child_prepend(args):
+    """--shared-zopfli: the debug entry by itself -- per dictionary size, --runs rounds of modes 0, 1 and 2 one after the other (host clock around the
+    synchronous entry: allocation, upload, launches, download of 512 KiB of buckets and the forest)"""
+    import synth
+    L = ctypes.CDLL(args.lib)
+    pool = synth.markov_text(1 << 20, 5)
+    out = []
+    for D in (2, 16 << 10, 64 << 10):
+        text = pool[:D + 64]
+        buckets = (ctypes.c_uint32 * (1 << 17))()
+        forest = (ctypes.c_uint32 * (2 * ((D + 63) & ~63)))()
+        times = {0: [], 1: [], 2: []}
+        for it in range(args.warmup + args.runs):
+            for mode in (0, 1, 2):
+                t = time.perf_counter()
+                ret = L.brotli_mi355x_debug_zopfli_prepend(text, ctypes.c_uint32(len(text)), ctypes.c_uint32(D), ctypes.c_uint32(LGWIN), ctypes.c_uint32(mode), buckets, forest)
+                dt = time.perf_counter() - t
+                assert ret == 0, (D, mode, ret)
+                if it >= args.warmup:
+                    times[mode].append(dt)
+        row = {"dictionary_bytes": D}
+        for mode, name in ((0, "lane0"), (1, "wave_wide"), (2, "image_build")):
+            row[name + "_min_max_ms"] = [round(1e3 * min(times[mode]), 3), round(1e3 * max(times[mode]), 3)]
+        out.append(row)
+        print(json.dumps(row), flush=True)
+    with open(args.child_out, "w") as f:
+        json.dump(out, f)
+
+
 def child_dicts(args):
     """--dicts: the children of main_dicts -- batch (own dictionaries), same (one dictionary as count indices), shared, loop, cpu"""
     out = []
@@ -419,11 +464,14 @@ def child_dicts(args):
             if quality not in DICTS_QUALITIES.get(name, (quality,)):
                 continue
             row = {"class": name, "data": "text", "quality": quality, "items": len(items), "bytes": sum(map(len, items)), "dictionary_bytes": len(dictionaries[0])}
-            if args.child in ("batch", "same", "shared"):
+            if args.child in ("batch", "same", "shared", "one_index"):
                 ds = dictionaries if args.child == "batch" else [dictionaries[0]] * len(items)
                 times, csize, info, failed = measure_dicts(args.lib, items, ds, quality, args.runs, args.warmup, shared=args.child == "shared",
-                                                           routes=args.routes if args.child in ("batch", "shared") and args.routes else None)
+                                                           routes=args.routes if args.child != "same" and args.routes else None, one_index=args.child == "one_index")
                 row.update(stats(times), compressed_bytes=csize, batch_info=info, reference_fails_on_items=failed)
+            elif args.child == "shared_first":  # the shared entry without a bit on the first --loop-items items: one by one
+                times, csize, info, failed = measure_dicts(args.lib, items[:n], [dictionaries[0]] * min(n, len(items)), quality, args.runs, args.warmup, shared=True)
+                row.update(stats(times), measured_items=min(n, len(items)), compressed_bytes=csize, batch_info=info, reference_fails_on_items=failed)
             elif args.child == "batch_first":  # the same call on the first --loop-items items (a library whose items run one by one)
                 times, csize, info, failed = measure_dicts(args.lib, items[:n], dictionaries[:n], quality, args.runs, args.warmup, routes=args.routes)
                 row.update(stats(times), measured_items=min(n, len(items)), compressed_bytes=csize, batch_info=info, reference_fails_on_items=failed)
@@ -705,6 +753,8 @@ def child(args):
         return child_device(args)
     if args.child == "device-dicts":
         return child_device_dicts(args)
+    if args.child == "prepend":
+        return child_prepend(args)
     if args.dicts:
         return child_dicts(args)
     out = []
@@ -1012,6 +1062,65 @@ def main_dicts_zopfli(args, doc, save, classes):
     print(json.dumps(doc, indent=1))
 
 
+def main_shared_zopfli(args, doc, save, classes):
+    """--shared-zopfli: see the module's text"""
+    doc["what"] = ("BrotliMi355xCompressBatchWithDictionaryEx with BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_SHARED_DICTIONARY_ITEMS (8192), every item behind ONE shared "
+                   "dictionary (the class's first), text, lgwin 22, qualities 10 and 11; min .. max over --rounds alternating rounds of one run each (one warm-up "
+                   "call per process).  image: the default, one tree image per call, replayed by every chain; self_file: BROTLI_MI355X_BATCH_DICT_SELF_FILE=1, "
+                   "every chain files the dictionary itself; parent_one_index: a build of the parent commit through BrotliMi355xCompressBatchWithDictionaries "
+                   "with 1024 and one index named by every item -- the self-filing baseline; one_by_one: this build's shared entry without the bit, TIMED ON THE "
+                   "FIRST --loop-items ITEMS AND SCALED BY ITEM COUNT; on the one-item classes self_file_lane0 adds BROTLI_MI355X_ZOPFLI_PREPEND_LANE0=1, so that "
+                   "self_file - image and self_file_lane0 - image are a lone chain's filing less the replay, as differences of whole calls.  prepend_entry: "
+                   "brotli_mi355x_debug_zopfli_prepend by itself (host clock around the synchronous entry), modes 0 / 1 / 2 = lane 0 / wave-wide on one wavefront / "
+                   "the image build; the row of 2 bytes is what every mode pays for allocation, fill and copies")
+    doc["method"] = ("host clock around the synchronous call; every figure is min .. max over --rounds alternating rounds of ONE run each, each arm of a round in a child process of its own behind one warm-up call (the environment is read once per process); one_by_one on the first --loop-items items of a class, scaled by item count; prepend_entry: one child, one warm-up round, then --rounds rounds of modes 0, 1, 2 one after the other")
+    rows = {}
+    lone = [c for c in SHARED_ZOPFLI_LONE if not args.only or c in args.only.split(",")]
+    one = argparse.Namespace(**vars(args))
+    one.runs, one.warmup, one.dicts = 1, 1, True
+    parent = os.path.abspath(args.parent_lib) if args.parent_lib else None
+    self_file = {"BROTLI_MI355X_BATCH_DICT_SELF_FILE": "1"}
+
+    def note(row, name, scale=1.0):
+        v = rows.setdefault(key(row), {"items": row["items"], "bytes": row["bytes"], "dictionary_bytes": row["dictionary_bytes"]})
+        v.setdefault(name + "_ms", []).append(round(row["median_ms"] * scale, 3))
+        v[name + "_info"], v[name + "_compressed_bytes"] = row["batch_info"], row["compressed_bytes"]
+
+    for rnd in range(args.rounds):
+        for row in run_child(one, "shared", classes + lone, limit=900, routes=8192):
+            note(row, "image")
+        for row in run_child(one, "shared", classes + lone, limit=900, routes=8192, extra_env=self_file):
+            note(row, "self_file")
+        for row in (run_child(one, "shared", lone, limit=900, routes=8192, extra_env=dict(self_file, BROTLI_MI355X_ZOPFLI_PREPEND_LANE0="1")) if lone else []):
+            note(row, "self_file_lane0")
+        for row in (run_child(one, "one_index", classes, lib=parent, limit=900, routes=1024) if parent else []):
+            note(row, "parent_one_index")
+        for row in ([] if "loop" in args.skip.split(",") else run_child(one, "shared_first", classes, limit=1500)):
+            note(row, "one_by_one_scaled", row["items"] / row["measured_items"])
+            rows[key(row)]["one_by_one_measured_items"] = row["measured_items"]
+        doc["classes"] = rows
+        save()
+    entry = argparse.Namespace(**vars(args))
+    entry.runs, entry.warmup = max(args.rounds, 1), 1
+    doc["prepend_entry"] = run_child(entry, "prepend", ["none"], limit=600)
+    for v in rows.values():
+        names = ("image", "self_file", "self_file_lane0", "parent_one_index", "one_by_one_scaled")
+        for name in names:
+            if name + "_ms" in v:
+                v[name + "_min_max_ms"] = [min(v[name + "_ms"]), max(v[name + "_ms"])]
+        med = statistics.median(v["image_ms"])
+        for name in names[1:]:
+            if name + "_ms" in v:
+                v[name + "_over_image"] = round(statistics.median(v[name + "_ms"]) / med, 3)
+        sizes = set(v[name + "_compressed_bytes"] for name in names[:4] if name + "_compressed_bytes" in v)
+        v["same_compressed_bytes"] = bool(len(sizes) == 1)
+        if "parent_one_index_ms" in v:
+            # the rule of the default: no slower than the parent's self-filing by more than the spread of the runs
+            v["image_within_parent_spread"] = bool(min(v["image_ms"]) <= max(v["parent_one_index_ms"]))
+    save()
+    print(json.dumps(doc, indent=1))
+
+
 def main_dicts_q9(args, doc, save, classes):
     """--dicts --qualities 9: the dictionary batch calls with BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS (4096), --rounds alternating rounds of
     one run each: this build with the route, every item behind a dictionary of its own; on the DICTS_Q9_SHARED classes the shared form (every item
@@ -1121,6 +1230,7 @@ def main():
     ap.add_argument("--q9-items", action="store_true", help="this build through BrotliMi355xCompressBatchEx with BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS (--qualities 9,10)")
     ap.add_argument("--dicts", action="store_true", help="BrotliMi355xCompressBatchWithDictionaries: a dictionary per item (--qualities 5,8; 2,3,4 through BROTLI_MI355X_BATCH_ROUTE_QUICK_DICTIONARY_ITEMS; 10,11 through BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_DICTIONARY_ITEMS; 9 through BROTLI_MI355X_BATCH_ROUTE_Q9_DICTIONARY_ITEMS, shared form included, "
                     "with the prepend A/B and, with --parent-lib, the parent's one-by-one path on --loop-items items)")
+    ap.add_argument("--shared-zopfli", action="store_true", help="BrotliMi355xCompressBatchWithDictionaryEx with BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_SHARED_DICTIONARY_ITEMS: the tree image against self-filing, the parent's one-index call and one by one (qualities 10,11)")
     ap.add_argument("--device", action="store_true", help="BrotliMi355xCompressBatchDevice on torch tensors beside the parent's host call on the same items (DEVICE_SHAPES)")
     ap.add_argument("--device-dicts", action="store_true", help="BrotliMi355xCompressBatchWithDictionariesDevice on torch tensors beside download + the parent's host dictionary call + upload (DEVICE_DICTS_SHAPES)")
     ap.add_argument("--routes", type=int, default=0, help="(child) route bits of the device shape")
@@ -1166,6 +1276,10 @@ def main():
     if args.q9_items:
         doc["what"] = ("BrotliMi355xCompressBatchEx(BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS) vs the parent commit's batch call, there one by one (on the first "
                        "--loop-items items, scaled by item count), and its 4-thread loop vs the oracle on one CPU core; lgwin 22")
+    if args.shared_zopfli:
+        if not set(args.qualities.split(",")) <= {"10", "11"}:
+            args.qualities = "10,11"
+        return main_shared_zopfli(args, doc, save, [c for c in SHARED_ZOPFLI_HEADLINE if not args.only or c in args.only.split(",")])
     if args.dicts and not args.same_call and set(args.qualities.split(",")) <= {"10", "11"}:
         return main_dicts_zopfli(args, doc, save, [c for c in DICTS_ZOPFLI_HEADLINE if not args.only or c in args.only.split(",")])
     if args.dicts and not args.same_call and set(args.qualities.split(",")) == {"9"}:
