@@ -445,10 +445,11 @@ int32_t BrotliMi355xCompressBatchWithDictionaryEx(int quality, int lgwin, Brotli
    takes side by side without it, an item of at most one input block at quality 2, 3 or 4 and lgwin 10 .. 24 -- 1 <=
    input_sizes[i] <= 16 384 at quality 2 / 3 and <= 65 536 at quality 4 -- behind a dictionary of dict_sizes[k] >= 2 of which at
    most 65 536 bytes are in use (the rule of BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS of BrotliMi355xCompressBatchWithDictionaryEx,
-   applied per item) runs on the device as ONE chain on a private BasicHasher table.  There is no table image per dictionary and
-   no device memory per dictionary beyond its bytes: in front of every item the chain zeroes its table and files the item's
-   dictionary itself, 64 positions per step with an atomic maximum (what the reference's prepend leaves in a slot is the largest
-   position filed under it), then parses the item.  Every other item -- the empty one, longer items, dict_sizes[k] <= 1, more than
+   applied per item) runs on the device as ONE chain on a private BasicHasher table.  A dictionary that enough items of a device group
+   name gets a table image, built once for that group (BrotliMi355xLastBatchImageInfo below has the rule, the threshold variable and
+   the cap of 64 images, 256 / 512 KiB each); the chain of an item that names it copies the image over its table.  Every other chain
+   zeroes its table and files the item's dictionary itself, 64 positions per step with an atomic maximum (what the reference's
+   prepend leaves in a slot is the largest position filed under it).  Either way it then parses the item.  Every other item -- the empty one, longer items, dict_sizes[k] <= 1, more than
    65 536 bytes in use -- runs by itself through the stream path with its own dictionary.  The bit changes nothing at qualities 0,
    1 and 5 .. 11.  Such items count in info[1], their groups in info[4]; info[2], info[5] as below; info[6] and info[7] stay 0.
    When every item names one index the call is BrotliMi355xCompressBatchWithDictionaryEx with
@@ -503,7 +504,9 @@ int32_t BrotliMi355xCompressBatchWithDictionaryEx(int quality, int lgwin, Brotli
    9 and lgwin 17 .. 24 behind a dictionary of dict_sizes[k] >= 2 of which at most 65 536 bytes are in use (min(dict_sizes[k],
    (1 << lgwin) - 16)) runs on the device as ONE wavefront: a live chain on a private H9 table (64 KiB of ring counters, 32 MiB of
    rings 256 deep; at most 255 tables, 8 GiB, per group) that empties the counters, files its item's dictionary wave-wide in the
-   reference's order, stitches, and parses dictionary | item from position D.  Dictionary + item stay inside the first half of the
+   reference's order -- or, where enough items of the group name that dictionary, replays the image the group has built of it
+   (BrotliMi355xLastBatchImageInfo below: at most 64 per group, 64 KiB of counters and 8 bytes per dictionary byte each) --,
+   stitches, and parses dictionary | item from position D.  Dictionary + item stay inside the first half of the
    smallest ring buffer of these windows, so the chain meets neither a masked position nor H9's ring-end case.  When every item
    names one index -- and in BrotliMi355xCompressBatchWithDictionaryEx, where there is one dictionary -- the chains replay one image
    of the dictionary, made once per call, instead of filing it (same bytes; equal info between the two calls).  Every other item --
@@ -528,9 +531,13 @@ int32_t BrotliMi355xCompressBatchWithDictionaryEx(int quality, int lgwin, Brotli
    four-thread loop (0.47 x).  The break-even lies between 4 and 16 items of 4 KiB, and between 16 and 256 items of 64 KiB.
    Side by side on the device: quality 5 .. 8, lgwin 17 .. 24, 2 <= D_i <= 65536 (the bytes of the item's dictionary in use) and
    1 <= input_sizes[i] <= 65536.  A group uploads its items and, once each, the dictionaries they name; the text
-   dictionary | item is laid out on the device per item, and one chain per item files the dictionary into a private hash table and
-   then parses the item -- there is no table image to share between items, as there is behind one shared dictionary, so a chain's
-   time grows with D_i + input_sizes[i].  Every other item -- other qualities and windows, the empty item, longer items, longer or
+   dictionary | item is laid out on the device per item, and one chain per item parses the item on a private hash table that holds
+   the item's dictionary.  A dictionary that at least BROTLI_MI355X_BATCH_DICT_IMAGE_MIN_ITEMS (default 16) items of a device group
+   name gets an image of what the reference's prepend leaves in a hash table, built once for that group from the dictionary's copy
+   in front of the first item that names it; the chains of those items replay the image, as the chains behind one shared
+   dictionary do.  At most 64 images per group, the most named dictionaries first; an image is 32 KiB of ring counters (64 KiB at
+   quality 9) and 8 bytes per dictionary byte.  Every other chain files its dictionary itself, so its time grows with
+   D_i + input_sizes[i].  BrotliMi355xLastBatchImageInfo tells what a call did.  Every other item -- other qualities and windows, the empty item, longer items, longer or
    shorter dictionaries -- is accepted and runs by itself through the stream path with its own dictionary, on the calling thread,
    in the same call and in the caller's order: the same bytes, no gain in speed.  info[0] .. info[4] mean what they mean for
    BrotliMi355xCompressBatchWithDictionary; info[5] is the sum of the dictionary bytes in use over the distinct indices that at
@@ -622,6 +629,29 @@ int32_t BrotliMi355xCompressBatchWithDictionariesDevice(int quality, int lgwin, 
    BROTLI_MI355X_BATCH_ROUTE_QUICK_ITEMS, BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_ITEMS and BROTLI_MI355X_BATCH_ROUTE_Q9_ITEMS count in
    [1] and [4] only).  After a call that failed as a whole only info[0] is set. */
 void BrotliMi355xLastBatchInfo(uint64_t info[8]);
+/* The dictionary images of the same call.  Behind a dictionary per item (BrotliMi355xCompressBatchWithDictionaries and its device
+   form; qualities 5 .. 8, and 2 .. 4 / 9 with their bits) a dictionary that at least BROTLI_MI355X_BATCH_DICT_IMAGE_MIN_ITEMS
+   side-by-side items of a device group name gets an image of what the reference's prepend leaves in a hash table, built once for
+   that group; the chains of those items replay it instead of filing the dictionary, every other chain files its own.  The variable
+   is read once per process; its default is 16, 0 means no images, and a dictionary that one item of a group names never gets one
+   whatever the value (BROTLI_MI355X_BATCH_DICT_SELF_FILE=1 means no images either, also for the shared calls).  A group builds at
+   most 64 images, the most named dictionaries first, ties to the one that appears first in the group; dictionaries are told apart by
+   pointer and size in use.  The streams, sizes, failures and BrotliMi355xLastBatchInfo do not depend on any of this.
+   Measured (text, lgwin 22, 4096 items of 4 KiB dealt round robin to K dictionaries of 16 KiB, min .. max of two alternating
+   rounds against the parent build through the same call; profiles/r30_batch_dictionaries_images.json): K = 4 .. 64 at quality 8
+   in 50 .. 54 against 59 .. 63 ms, at quality 2 / 4 in 17 .. 18 / 24 .. 26 against 20 .. 21 / 27 .. 28 ms, at quality 9 in 86 .. 89
+   against 103 .. 105 ms, within 1 .. 4 % of the shared call behind ONE dictionary; 512-byte items behind 16 dictionaries at
+   quality 2 in 4.6 .. 5.6 against 7.6 .. 8.1 ms.  K = 4096 builds nothing and stays inside the parent's spread.  When not:
+   quality 5, where a replay costs a chain about what filing 16 KiB does -- level with the parent at K <= 64, and SLOWER with many
+   dictionaries of a few dozen items each: K = 128 in 22.1 .. 23.9 against 20.7 .. 22.7 ms (0.95 x), and K = 256 under a
+   threshold of 2 in 23.8 .. 25.3 against 21.3 .. 22.7 ms (0.89 x; the default of 16 builds nothing there).  Such a call sets the
+   variable to 0.  The default is the top of the allowed range because the sweep found no smaller value that never loses; the
+   image build's own time was not measured.
+   out[0] images built, summed over the call's groups (a shared-dictionary call: 1 when it built its one image), [1] side-by-side
+   items whose chain replayed an image, [2] side-by-side items whose chain filed its own dictionary (all of them on the Zopfli
+   per-item route, which builds no image per dictionary), [3] 0, reserved.  All zeros after a call without a dictionary and after a
+   call that failed as a whole; items that run one by one count in neither [1] nor [2]. */
+void BrotliMi355xLastBatchImageInfo(uint64_t out[4]);
 /* Human-readable description of the device backing the library ("hip:gfx950 (...)"). */
 const char* BrotliMi355xDeviceName(void);
 /* Message of the last failure on the calling thread ("" if none). */

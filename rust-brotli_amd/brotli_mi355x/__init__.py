@@ -550,6 +550,17 @@ class Library(object):
         self.lib.BrotliMi355xLastBatchInfo(info)
         return list(info)
 
+    def last_batch_image_info(self):
+        """BrotliMi355xLastBatchImageInfo: the dictionary images of the last batch call of this thread as a list of 4 integers --
+        [0] images built, summed over the call's groups (a shared-dictionary call: 1 when it built its image), [1] side-by-side items
+        whose chain replayed an image, [2] side-by-side items whose chain filed its own dictionary, [3] 0.  All zeros after a call
+        without a dictionary and after one that failed as a whole."""
+        info = (c_uint64 * 4)()
+        self.lib.BrotliMi355xLastBatchImageInfo.restype = None
+        self.lib.BrotliMi355xLastBatchImageInfo.argtypes = [POINTER(c_uint64)]
+        self.lib.BrotliMi355xLastBatchImageInfo(info)
+        return list(info)
+
     def compress_device(self, device_ptr, nbytes, quality=5, lgwin=22, mode=0, out_buffer=None):
         """One-shot compression of `nbytes` at device address `device_ptr` (e.g. tensor.data_ptr()).
         Returns (bytes, stats list of 32 doubles)."""

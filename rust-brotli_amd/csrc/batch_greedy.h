@@ -68,9 +68,16 @@ struct BatchParseJob {
   BatchRecord* records;
   BatchDictImage dict;  // bytes == 0: the plain call
   // a dictionary per item (BrotliMi355xCompressBatchWithDictionaries, lz77_batch_parse_dicts): [n_items], the dictionary bytes in
-  // front of item i, 2 .. 65536; nullptr: every other caller.  No image: every chain files its dictionary itself.
+  // front of item i, 2 .. 65536; nullptr: every other caller.
   const uint32_t* item_dict_bytes;
+  // ... and the images of the group's frequently named dictionaries (lz77_batch_dict_images): item i's chain replays
+  // images[item_image[i]], or files its dictionary itself where item_image[i] is kBatchNoImage.  item_image == nullptr: no images,
+  // every chain files.  Read by the instances of a dictionary per item alone.
+  const BatchDictImage* images;  // [n_images], device
+  const uint32_t* item_image;    // [n_items], device
 };
+static constexpr uint32_t kBatchNoImage = 0xffffffffu;
+static constexpr uint32_t kBatchGroupImages = 64;  // images per group at most
 // one wavefront per table; a wavefront takes items from `counter` until none is left
 void lz77_batch_parse(const BatchParseJob& J);
 // The same launch shape for the H9 hasher of qualities 9 and 10 (batch_q9_kernels.hip: k_parse_batch_h9).  J.P is that of an H9
@@ -116,6 +123,23 @@ void lz77_batch_parse_dicts(const BatchParseJob& J);
 // -- `num` ends up as the image's counters -- and lists the covered entries: entries[2 * i], entries[2 * i + 1], *n_entries.
 void lz77_batch_dict_image(const Lz77Params& P, const uint16_t* keys, uint32_t dict_bytes, uint16_t* num, uint32_t* buckets,
                            uint32_t* entries, uint32_t* n_entries);
+// The images of a group behind a dictionary per item, built in the group's own arrays.  Image j is that of the dictionary whose
+// plan[j].bytes bytes start at text position plan[j].text_at (its copy in front of the first item that names it; J.keys holds the
+// keys of that copy, and the filed positions [0, bytes - 3) hash dictionary bytes only).  One wavefront per image files them on
+// table j % J.tables of the job -- the parse launch behind it empties or overwrites every counter of a table in front of every item,
+// so the tables serve as the scratch -- and one listing launch with an image dimension copies the counters to num[j] and lists the
+// covered entries from entries[2 * plan[j].entries_at] on, n_entries[j] of them.  More images than tables: rounds of J.tables images.
+// plan: [n_images], device; num: [n_images][1 << bucket_bits]; entries: room for two words per dictionary byte of all images;
+// n_entries: [n_images], zeroed by the caller.  A dictionary shorter than the hashed length gives an image with zero entries and
+// zero counters.  What a chain replays is BatchDictImage{bytes, num + j << bucket_bits, entries + 2 * entries_at, n_entries + j}.
+struct BatchImagePlan {
+  uint32_t text_at;     // where the dictionary's copy starts in the group's padded text
+  uint32_t bytes;       // D
+  uint32_t entries_at;  // its list starts at entry entries_at of `entries`; it has room for `bytes` entries
+  uint32_t pad;
+};
+void lz77_batch_dict_images(const BatchParseJob& J, uint32_t n_images, const BatchImagePlan* plan_dev, uint16_t* num, uint32_t* entries,
+                            uint32_t* n_entries);
 // out[offsets[i] ..) = the finished commands of item i (Command::init) and its trailing insert-only command
 void lz77_batch_gather(const BatchParseJob& J, const uint32_t* offsets_dev, Command* out);
 
@@ -167,13 +191,25 @@ void BatchGreedyCompressWithDictionary(const EncoderParams& params, const uint8_
                                        std::vector<uint8_t>* reference_fails, uint32_t* groups, const BatchDeviceSink* sink = nullptr);
 // The same with a dictionary per item: item i lies behind dicts[i] (dict_sizes[i] bytes, after the reference's truncation; several
 // items may share a pointer -- dictionaries are told apart by pointer and size, and each goes up once per group).  Every
-// (dict_sizes[i], sizes[i]) is BatchDictionaryEligible.
+// (dict_sizes[i], sizes[i]) is BatchDictionaryEligible.  A dictionary that at least BatchDictImageMinItems() items of a group name
+// gets an image, built once for the group (at most kBatchGroupImages, the most named first); those items' chains replay it.
 // sink != nullptr, for both: the device mode (BatchDeviceSink, with StreamDeliveryRule) -- `dict`, dicts[i] and inputs[i] are device
 // addresses of any alignment; every item reads its dictionary where it lies (batch_device.h: batch_stage_dicts_device), and the
 // shared dictionary reaches its image by a copy on the device.
 void BatchGreedyCompressWithDictionaries(const EncoderParams& params, size_t count, const uint8_t* const* dicts, const size_t* dict_sizes,
                                          const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
                                          std::vector<uint8_t>* reference_fails, uint32_t* groups, const BatchDeviceSink* sink = nullptr);
+// BROTLI_MI355X_BATCH_DICT_IMAGE_MIN_ITEMS, read once per process: the items of a group that must name a dictionary for it to get
+// an image.  0, or BROTLI_MI355X_BATCH_DICT_SELF_FILE=1: no images.  A dictionary named once never gets one, whatever the value.
+size_t BatchDictImageMinItems();
+// What BrotliMi355xLastBatchImageInfo reports, counted by the routes into a record of the calling thread: the caller empties it in
+// front of a call and reads it behind one.
+struct BatchImageCounts {
+  uint64_t images;    // dictionary images built, summed over the groups
+  uint64_t replayed;  // side-by-side items whose chain replayed an image
+  uint64_t filed;     // side-by-side items whose chain filed its own dictionary
+};
+BatchImageCounts& BatchImageTally();
 // Items of several blocks, each one chain: 1 << lgblock < size <= kBatchLongBytes, otherwise as BatchGreedyEligible.
 bool BatchLongEligible(const EncoderParams& params, size_t input_size);
 // (*demoted)[i] != 0: a meta-block of item i that is not its last took the size fallback (encode.rs:2141-2163), which the chain

@@ -63,6 +63,19 @@ bool PlainStreamParams(const EncoderParams& user) {
 
 }  // namespace
 
+// The default of BROTLI_MI355X_BATCH_DICT_IMAGE_MIN_ITEMS (DESIGN.md section 10 has the sweep behind it).
+static constexpr size_t kBatchDictImageMinItems = 16;
+size_t BatchDictImageMinItems() {
+  static const size_t min_items =
+      EnvSize("BROTLI_MI355X_BATCH_DICT_SELF_FILE", 0) != 0 ? 0 : EnvSize("BROTLI_MI355X_BATCH_DICT_IMAGE_MIN_ITEMS", kBatchDictImageMinItems);
+  return min_items;
+}
+
+BatchImageCounts& BatchImageTally() {
+  static thread_local BatchImageCounts counts{0, 0, 0};
+  return counts;
+}
+
 bool BatchGreedyEligible(const EncoderParams& user, size_t input_size) {
   if (input_size == 0) return false;  // (answered without an encoder)
   if (user.quality < 5 || user.quality > 8 || user.lgwin < 17 || user.lgwin > 24 || !PlainStreamParams(user)) return false;
@@ -575,6 +588,7 @@ void CompressGroups(const EncoderParams& p, const uint8_t* dict, uint32_t D, siz
     image.num = num;
     image.entries = entries;
     image.n_entries = n_entries;
+    ++BatchImageTally().images;
   }
 
   CallArrays A;
@@ -584,6 +598,7 @@ void CompressGroups(const EncoderParams& p, const uint8_t* dict, uint32_t D, siz
     StageGroup(first, count, inputs, sizes, DictSizes(D, dict_dev), tables_max, &A, &g, 0, sink != nullptr);
     ++*groups;
     uint8_t* text = g.uploaded;
+    if (D != 0) (image.entries != nullptr ? BatchImageTally().replayed : BatchImageTally().filed) += g.n;
     if (g.dict_text) {
       text = g.dict_text;  // (the device mode: laid out with the staging, from the call's own copy of the dictionary)
     } else if (D != 0) {
@@ -648,8 +663,95 @@ DictsText StageDictsText(Group& g, const uint8_t* const* dicts, const size_t* di
   return out;
 }
 
-// Qualities 5 .. 8 behind a dictionary per item: the steps of CompressGroups' dictionary path without an image -- there is none
-// to share, so every chain files its own dictionary (br_batch_item<kRows, true, true>) in the text StageDictsText lays out.
+// The dictionaries of a group that get an image: those that at least BatchDictImageMinItems() of its items name, and never one
+// that a single item names -- build plus replay cannot beat one filing.  At most kBatchGroupImages, the most named first, ties to
+// the dictionary that appears first in the group.  Dictionaries are told apart as StageDictsText does it: by pointer and size in use.
+struct GroupImages {
+  std::vector<uint32_t> item_image;  // [g.n]: the image of item i's dictionary, or kBatchNoImage
+  std::vector<uint32_t> first_item;  // [images]: the first item of the group that names the image's dictionary
+  uint32_t replayed = 0;             // items with an image
+};
+GroupImages PickGroupImages(const Group& g, const uint8_t* const* dicts, const size_t* dict_sizes) {
+  GroupImages out;
+  out.item_image.assign(g.n, kBatchNoImage);
+  const size_t min_items = BatchDictImageMinItems();
+  if (min_items == 0) return out;
+  struct Named {
+    uint32_t first, items;
+  };
+  std::map<std::pair<const uint8_t*, size_t>, uint32_t> place;  // -> index into `named`
+  std::vector<Named> named;
+  std::vector<uint32_t> of_item(g.n);
+  for (uint32_t i = 0; i < g.n; ++i) {
+    const auto slot = place.emplace(std::make_pair(dicts[g.first + i], dict_sizes[g.first + i]), (uint32_t)named.size());
+    if (slot.second) named.push_back(Named{i, 0});
+    of_item[i] = slot.first->second;
+    ++named[of_item[i]].items;
+  }
+  std::vector<uint32_t> chosen;
+  for (uint32_t k = 0; k < named.size(); ++k)
+    if (named[k].items >= std::max<size_t>(min_items, 2)) chosen.push_back(k);
+  // (`named` is in the order of first appearance, and the sort keeps it among equals)
+  std::stable_sort(chosen.begin(), chosen.end(), [&](uint32_t a, uint32_t b) { return named[a].items > named[b].items; });
+  if (chosen.size() > kBatchGroupImages) chosen.resize(kBatchGroupImages);
+  std::vector<uint32_t> image_of(named.size(), kBatchNoImage);
+  for (uint32_t j = 0; j < chosen.size(); ++j) {
+    image_of[chosen[j]] = j;
+    out.first_item.push_back(named[chosen[j]].first);
+  }
+  for (uint32_t i = 0; i < g.n; ++i) {
+    out.item_image[i] = image_of[of_item[i]];
+    if (out.item_image[i] != kBatchNoImage) ++out.replayed;
+  }
+  return out;
+}
+// ... counted for BrotliMi355xLastBatchImageInfo, and the image numbers of the items on the device (nullptr: the group has no image)
+const uint32_t* CountGroupImages(Group& g, const GroupImages& gi) {
+  BatchImageCounts& tally = BatchImageTally();
+  tally.images += gi.first_item.size();
+  tally.replayed += gi.replayed;
+  tally.filed += g.n - gi.replayed;
+  if (gi.first_item.empty()) return nullptr;
+  uint32_t* item_image_dev = g.mem.uninit<uint32_t>((size_t)g.n * 4);
+  dev_h2d(item_image_dev, gi.item_image.data(), (size_t)g.n * 4);
+  return item_image_dev;
+}
+
+// The images of an H5 / H9 group, built into group-scoped memory from the copy of each dictionary that the text layout has put in
+// front of the first item that names it, with the keys of the group's key pass (so the device form needs no copy of its own) and the
+// group's own tables as the scratch: the parse launch empties or overwrites every counter in front of every item anyway, which
+// saves 16 / 32 MiB of scratch per image at quality 8 / 9.  An image is its counters (32 / 64 KiB) and at most D entries of 8 bytes.
+void BuildGroupImages(Group& g, const GroupImages& gi, BatchParseJob* J) {
+  J->item_image = CountGroupImages(g, gi);
+  if (J->item_image == nullptr) return;
+  CallArrays& A = *g.A;
+  const uint32_t n_images = (uint32_t)gi.first_item.size();
+  const size_t keys_per_table = (size_t)1 << J->P.bucket_bits;
+  std::vector<BatchImagePlan> plan(n_images);
+  uint32_t entries_at = 0;
+  for (uint32_t j = 0; j < n_images; ++j) {
+    const uint32_t i = gi.first_item[j], D = A.dict_bytes[i];
+    plan[j] = BatchImagePlan{A.items[i].text_off - D, D, entries_at, 0};
+    entries_at += D;
+  }
+  BatchImagePlan* plan_dev = g.mem.uninit<BatchImagePlan>((size_t)n_images * sizeof(BatchImagePlan));
+  dev_h2d(plan_dev, plan.data(), (size_t)n_images * sizeof(BatchImagePlan));
+  uint16_t* num = g.mem.uninit<uint16_t>((size_t)n_images * keys_per_table * 2 + 64);
+  uint32_t* entries = g.mem.uninit<uint32_t>((size_t)entries_at * 8 + 64);
+  uint32_t* n_entries = g.mem.zeroed<uint32_t>((size_t)n_images * 4 + 64);
+  lz77_batch_dict_images(*J, n_images, plan_dev, num, entries, n_entries);
+  std::vector<BatchDictImage> images(n_images);
+  for (uint32_t j = 0; j < n_images; ++j)
+    images[j] = BatchDictImage{plan[j].bytes, num + (size_t)j * keys_per_table, entries + 2 * (size_t)plan[j].entries_at, n_entries + j};
+  BatchDictImage* images_dev = g.mem.uninit<BatchDictImage>((size_t)n_images * sizeof(BatchDictImage));
+  dev_h2d(images_dev, images.data(), (size_t)n_images * sizeof(BatchDictImage));
+  J->images = images_dev;
+}
+
+// Qualities 5 .. 8 behind a dictionary per item: the steps of CompressGroups' dictionary path in the text StageDictsText lays out,
+// with an image per frequently named dictionary of the group (PickGroupImages, BuildGroupImages) where CompressGroups has the one of
+// its call: the chain of an item that names such a dictionary replays the image, every other chain files its own dictionary
+// (br_batch_item<kRows, true, true>).
 // Quality 9 (BatchQ9CompressWithDictionaries: p.hasher.type == 9) takes the same steps onto H9 tables and br_batch_item_h9_dict<true>.
 // dicts[i] / dict_sizes[i]: the dictionary of item i as in use.
 void CompressGroupsWithDictionaries(const EncoderParams& p, size_t count, const uint8_t* const* dicts, const size_t* dict_sizes,
@@ -674,6 +776,7 @@ void CompressGroupsWithDictionaries(const EncoderParams& p, size_t count, const 
     BatchParseJob J = GreedyJob(p, P, g, staged.text);
     J.records = g.mem.uninit<BatchRecord>((size_t)g.n * sizeof(BatchRecord));
     J.item_dict_bytes = staged.dict_bytes_dev;
+    BuildGroupImages(g, PickGroupImages(g, dicts, dict_sizes), &J);
     if (P.hasher_kind == 9) lz77_batch_parse_h9(J); else lz77_batch_parse_dicts(J);
     FinishOneBlockItems(p, J, g, streams, reference_fails, sink);
     first = g.last;
@@ -859,6 +962,7 @@ void BatchQuickCompressWithDictionary(const EncoderParams& user, const uint8_t* 
     B.text = dict_dev;  // (every filed position hashes dictionary bytes only)
     lz77_quick_prepend(chains.P, B, image, D);
     chains.image = image.table;
+    ++BatchImageTally().images;
   }
 
   CallArrays A;
@@ -867,6 +971,7 @@ void BatchQuickCompressWithDictionary(const EncoderParams& user, const uint8_t* 
     Group g;
     StageGroup(first, count, inputs, sizes, DictSizes(D, dict_dev), tables_max, &A, &g, 0, sink != nullptr);
     ++*groups;
+    BatchImageTally().replayed += g.n;
     uint8_t* text = g.dict_text;  // (the device mode: laid out with the staging, from the call's own copy of the dictionary)
     if (!text) {
       text = g.mem.zeroed<uint8_t>(g.padded + 64);
@@ -885,8 +990,10 @@ void BatchQuickCompressWithDictionary(const EncoderParams& user, const uint8_t* 
 }
 
 // Qualities 2 .. 4 behind a dictionary per item (batch_quick.h), items of one block: the steps of BatchQuickCompressWithDictionary
-// with the pool step of CompressGroupsWithDictionaries (StageDictsText) in place of the one dictionary and its image -- a chain
-// zeroes its table and files its item's dictionary itself (br_quick_batch_file), so nothing is built per dictionary.
+// with the pool step of CompressGroupsWithDictionaries (StageDictsText) in place of the one dictionary, and a table image per
+// frequently named dictionary of the group in place of the call's one image -- the chain of an item that names such a dictionary
+// copies the image over its table (br_quick_batch_prime), every other chain zeroes its table and files its item's dictionary itself
+// (br_quick_batch_file).
 void BatchQuickCompressWithDictionaries(const EncoderParams& user, size_t count, const uint8_t* const* dicts, const size_t* dict_sizes,
                                         const uint8_t* const* inputs, const size_t* sizes, std::vector<std::vector<uint8_t>>* streams,
                                         std::vector<uint8_t>* reference_fails, uint32_t* groups, const BatchDeviceSink* sink) {
@@ -911,6 +1018,24 @@ void BatchQuickCompressWithDictionaries(const EncoderParams& user, size_t count,
     J.text = staged.text;
     J.records = g.mem.uninit<BatchRecord>((size_t)g.n * sizeof(BatchRecord));
     J.item_dict_bytes = staged.dict_bytes_dev;
+    // an image per frequently named dictionary of the group (PickGroupImages): the table lz77_quick_init + lz77_quick_prepend leave
+    // for the dictionary's copy in front of the first item that names it, 256 / 512 KiB each, all built by one launch
+    const GroupImages gi = PickGroupImages(g, dicts, dict_sizes);
+    J.item_image = CountGroupImages(g, gi);
+    if (J.item_image != nullptr) {
+      const uint32_t n_images = (uint32_t)gi.first_item.size();
+      std::vector<uint32_t> at(2 * (size_t)n_images);  // where each dictionary's copy starts in the text, then its bytes
+      for (uint32_t j = 0; j < n_images; ++j) {
+        const uint32_t i = gi.first_item[j];
+        at[j] = A.items[i].text_off - A.dict_bytes[i];
+        at[n_images + j] = A.dict_bytes[i];
+      }
+      uint32_t* at_dev = g.mem.uninit<uint32_t>(at.size() * 4);
+      dev_h2d(at_dev, at.data(), at.size() * 4);
+      uint32_t* images = g.mem.zeroed<uint32_t>((size_t)n_images * QuickTableBytes(J) + 64);
+      lz77_quick_dict_images(J.Q, staged.text, n_images, at_dev, at_dev + n_images, images);
+      J.images = images;
+    }
     lz77_quick_batch_parse_dicts(J);
     // (the gather reads raw commands, whose distance codes the chain took from positions that count the dictionary: it needs no D)
     FinishOneBlockItems(p, GatherJobOf(J), g, streams, reference_fails, sink);
@@ -1053,6 +1178,7 @@ void BatchZopfliCompressWithDictionaries(const EncoderParams& user, size_t count
     StageGroup(first, count, inputs, sizes, DictSizes(dict_sizes, sink ? dicts : nullptr), kZopfliBatchResident, &A, &g, kBatchHqGroupItems, sink != nullptr);
     ++*groups;
     const DictsText staged = StageDictsText(g, dicts, dict_sizes);
+    BatchImageTally().filed += g.n;  // (no image per dictionary on this route: its image is a tree forest with its own builder)
     // (the order is by dictionary + item, which sizes the forest; everything else hangs on the largest item)
     uint32_t largest_item = 0;
     for (uint32_t i = 0; i < g.n; ++i) largest_item = std::max(largest_item, A.items[i].bytes);
@@ -1122,6 +1248,7 @@ void BatchZopfliCompressWithDictionary(const EncoderParams& user, const uint8_t*
     lz77_zopfli_dict_image(dict_dev, D, chains.lgwin, classes, image_buckets, image_forest);
     chains.image_buckets = image_buckets;
     chains.image_forest = image_forest;
+    ++BatchImageTally().images;
   }
 
   CallArrays A;
@@ -1130,6 +1257,7 @@ void BatchZopfliCompressWithDictionary(const EncoderParams& user, const uint8_t*
     Group g;
     StageGroup(first, count, inputs, sizes, DictSizes(D, dict_dev), kZopfliBatchResident, &A, &g, kBatchHqGroupItems, sink != nullptr);
     ++*groups;
+    (self_file ? BatchImageTally().filed : BatchImageTally().replayed) += g.n;
     uint8_t* text = g.dict_text;  // (the device mode: laid out with the staging, from the call's own copy of the dictionary)
     if (!text) {
       text = g.mem.zeroed<uint8_t>(g.padded + 64);

@@ -37,6 +37,30 @@ BR_DEV void br_batch_replay_dictionary(const LiveRing& lr, const BatchDictImage&
   BR_SYNC();
 }
 
+// A dictionary per item: the image item `index` replays, or kBatchNoImage -- its chain files its dictionary itself.  The same for
+// every lane, so the item code branches wave-uniformly.
+BR_DEV uint32_t br_batch_item_image(const BatchParseJob& J, uint32_t index) {
+  return J.item_image != nullptr ? BR_UNIFORM(J.item_image[index]) : kBatchNoImage;
+}
+template <typename T>
+BR_DEV const T* br_batch_uniform_ptr(const T* p) {
+#if BR_SCALAR
+  return p;
+#else
+  const uint64_t v = (uint64_t)(uintptr_t)p;
+  return (const T*)(uintptr_t)(((uint64_t)BR_UNIFORM((uint32_t)(v >> 32)) << 32) | (uint64_t)BR_UNIFORM((uint32_t)v));
+#endif
+}
+// image `image` of the group's array, its fields the same in every lane
+BR_DEV BatchDictImage br_batch_load_image(const BatchDictImage* images, uint32_t image) {
+  BatchDictImage d = images[image];
+  d.bytes = BR_UNIFORM(d.bytes);
+  d.num = br_batch_uniform_ptr(d.num);
+  d.entries = br_batch_uniform_ptr(d.entries);
+  d.n_entries = br_batch_uniform_ptr(d.n_entries);
+  return d;
+}
+
 // Item-local coordinates on table `table`: position 0 of t.text / t.keys / t.flags_next lies D bytes in front of the item, and lr
 // is the table's bucket rings.  D == 0: position 0 is the item's first byte, so no distance reaches a neighbour and max_backward
 // is what the reference computes for a stream that starts at 0.  With a dictionary position 0 is the dictionary's first byte and
@@ -56,8 +80,17 @@ BR_DEV void br_batch_item_tables(const BatchParseJob& J, const Lz77Params& P, co
 // T: the job's tables with text / keys / flags / cmds still pointing at the group's arrays.
 // kDict: the item's text starts with J.dict.bytes bytes of custom dictionary (BrotliMi355xCompressBatchWithDictionary).
 // kDicts (with kDict): a dictionary per item (BrotliMi355xCompressBatchWithDictionaries) -- the item's text starts with
-// J.item_dict_bytes[index] bytes of its own dictionary, J.dict is not looked at and the chain files the dictionary itself.  A
-// parameter of the template, not a test of J.item_dict_bytes, so that the instances of the other calls stay what they were.
+// J.item_dict_bytes[index] bytes of its own dictionary, J.dict is not looked at, and the chain replays the image of that
+// dictionary (J.images[J.item_image[index]], built for the group: lz77_batch_dict_images) or, where the dictionary has none, files
+// it itself.  A parameter of the template, not a test of J.item_dict_bytes, so that the instances of the other calls stay what
+// they were.
+//
+// One table serves replayed and self-filed items in turn, behind dictionaries of any two lengths, and it served as the scratch of
+// an image build before the first of them.  Whatever was there cannot be reached, because both starts leave EVERY counter of the
+// table defined and every slot a counter covers written by this item's own start: the replay writes all 1 << bucket_bits counters
+// from the image and then exactly the min(counter, depth) slots in front of each (the image's list, also where it is empty: a
+// dictionary shorter than the hashed length has all counters 0); the reset zeroes all counters, and the filing behind it writes
+// its slot before it moves its counter.  From there on the chain does the same, whichever start it had.
 //
 // The table under kDicts is reused by the next item of its wavefront with only its counters emptied (br_live_reset), and that item's
 // dictionary may be shorter or longer than the one in front -- 2 bytes behind 65 536, say.  Nothing the item in front left can be
@@ -82,11 +115,14 @@ BR_DEV void br_batch_item(const BatchParseJob& J, const ChainTables& T, ChainScr
   if constexpr (kDict) {
     // the hasher as HasherPrependCustomDictionary left it, then StitchToPreviousBlock of the first block (mod.rs:210-222): the
     // last three dictionary positions, whose four bytes reach into the item
+    const uint32_t image = kDicts ? br_batch_item_image(J, index) : kBatchNoImage;  // (wave-uniform)
     if (!kDicts && J.dict.entries != nullptr) {
       br_batch_replay_dictionary(lr, J.dict, P.bucket_bits);
+    } else if (kDicts && image != kBatchNoImage) {
+      br_batch_replay_dictionary(lr, br_batch_load_image(J.images, image), P.bucket_bits);
     } else {
-      // (the A/B of DESIGN.md section 10, BROTLI_MI355X_BATCH_DICT_SELF_FILE, and every item of kDicts: the chain files the
-      // dictionary itself, wave-wide, in the reference's order)
+      // (the A/B of DESIGN.md section 10, BROTLI_MI355X_BATCH_DICT_SELF_FILE, and the items of kDicts whose dictionary has no
+      // image: the chain files the dictionary itself, wave-wide, in the reference's order)
       br_live_reset(lr, P.bucket_bits);
       if (D > P.htl - 1) br_live_store(lr, 0, 1, D - (P.htl - 1), 1, 0);
     }

@@ -149,6 +149,37 @@ void lz77_batch_dict_image(const Lz77Params& P, const uint16_t* keys, uint32_t d
   *n_entries = n_out;
 }
 
+// the images of a group: image j filed on table j % J.tables of the job, which the parse behind it takes over, as on the device
+void lz77_batch_dict_images(const BatchParseJob& J, uint32_t n_images, const BatchImagePlan* plan, uint16_t* num, uint32_t* entries,
+                            uint32_t* n_entries) {
+  if (n_images == 0) return;
+  if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
+  const size_t keys_per_table = (size_t)1 << J.P.bucket_bits;
+  const uint32_t depth = 1u << J.P.block_bits;
+  for (uint32_t j = 0; j < n_images; ++j) {
+    const uint32_t b = j % J.tables, D = plan[j].bytes;
+    LiveRing lr;
+    lr.num = J.num + (size_t)b * keys_per_table;
+    lr.buckets = J.buckets + (((size_t)b * keys_per_table) << J.P.block_bits);
+    lr.keys = J.keys + plan[j].text_at;
+    lr.bits = J.P.block_bits;
+    br_live_reset(lr, J.P.bucket_bits);
+    if (D > J.P.htl - 1) br_live_store(lr, 0, 1, D - (J.P.htl - 1), 1, 0);  // StoreLookaheadThenStore, mod.rs:224-229
+    uint32_t* out = entries + 2 * (size_t)plan[j].entries_at;
+    uint32_t n_out = 0;
+    for (uint32_t key = 0; key < keys_per_table; ++key) {
+      const uint32_t n = lr.num[key], visible = n < depth ? n : depth;
+      num[(size_t)j * keys_per_table + key] = (uint16_t)n;
+      for (uint32_t i = 0; i < visible && n_out < D; ++i, ++n_out) {
+        const uint32_t slot = (key << J.P.block_bits) | ((n - 1u - i) & (depth - 1u));
+        out[2 * (size_t)n_out] = slot;
+        out[2 * (size_t)n_out + 1] = lr.buckets[slot];
+      }
+    }
+    n_entries[j] = n_out;
+  }
+}
+
 void lz77_batch_gather(const BatchParseJob& J, const uint32_t* offsets, Command* out) {
   for (uint32_t i = 0; i < J.n_items; ++i) {
     const BatchRecord& r = J.records[i];

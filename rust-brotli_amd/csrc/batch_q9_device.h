@@ -16,8 +16,10 @@ namespace brotli_mi355x {
 //
 // kDicts == false: the shared dictionary of the call (J.dict).  With an image (J.dict.entries != nullptr) the chain replays it over
 // its table, br_batch_replay_dictionary; without one (BROTLI_MI355X_BATCH_DICT_SELF_FILE) it files the dictionary itself.
-// kDicts == true: J.item_dict_bytes[index] bytes of the item's own dictionary, filed by the chain wave-wide with br_live_store
-// in the reference's order (ascending positions; lanes of one key take consecutive slots in position order).
+// kDicts == true: J.item_dict_bytes[index] bytes of the item's own dictionary.  Where the group has built an image of it
+// (J.item_image[index], lz77_batch_dict_images) the chain replays that one; otherwise it files the dictionary wave-wide with
+// br_live_store in the reference's order (ascending positions; lanes of one key take consecutive slots in position order).  A
+// table takes both starts in turn: the paragraph on reuse below covers each, and neither relies on what the other left.
 //
 // Why a chain that starts at D on an H9 table is the reference's stream.  The host admits an item only with D <= 65536 and
 // bytes <= 65536 (BatchQ9DictionaryEligible), and the ring buffer of a quality 9 stream has 1 << (1 + max(lgwin, lgblock)) >= 1 << 18
@@ -54,8 +56,11 @@ BR_DEV void br_batch_item_h9_dict(const BatchParseJob& J, const ChainTables& T, 
   ChainTables t = T;
   LiveRing lr;
   br_batch_item_tables(J, P, it, D, table, t, lr);
+  const uint32_t image = kDicts ? br_batch_item_image(J, index) : kBatchNoImage;  // (wave-uniform)
   if (!kDicts && J.dict.entries != nullptr) {
     br_batch_replay_dictionary(lr, J.dict, P.bucket_bits);
+  } else if (kDicts && image != kBatchNoImage) {
+    br_batch_replay_dictionary(lr, br_batch_load_image(J.images, image), P.bucket_bits);
   } else {
     br_live_reset(lr, P.bucket_bits);
     if (D > P.htl - 1) br_live_store(lr, 0, 1, D - (P.htl - 1), 1, 0);  // StoreLookaheadThenStore, mod.rs:224-229

@@ -31,7 +31,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 4))) void
 // The same launch shape, workgroup memory and occupancy bounds behind a custom dictionary: siblings of k_parse_batch_h9, so that
 // the instance without a dictionary compiles as it did.  k_parse_batch_h9_dict: the call's shared dictionary (J.dict: its image is
 // replayed over the table, or filed by the chain where there is no image); k_parse_batch_h9_dicts: a dictionary per item
-// (J.item_dict_bytes), filed by the chain.
+// (J.item_dict_bytes), filed by the chain or, where the group has built an image of it (J.images, J.item_image), replayed.
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_parse_batch_h9_dict(BatchParseJob J, ChainTables T) {
   __shared__ ChainScratchT<true, false> scratch;
   __shared__ uint32_t histo[256];

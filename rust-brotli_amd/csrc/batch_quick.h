@@ -37,15 +37,25 @@ struct QuickBatchJob {
                           // dictionary (slots and books), which every chain copies over its own table in front of every item
   // behind a custom dictionary per item (lz77_quick_batch_parse_dicts); nullptr for every other launch
   const uint32_t* item_dict_bytes;  // [n_items]: item i's text is its own dictionary | item, as above; dict_bytes and image are not
-                                    // looked at -- a chain files its item's dictionary into its zeroed table itself
+                                    // looked at -- a chain files its item's dictionary into its zeroed table itself, or
+  // ... copies the image the group has built of that dictionary (lz77_quick_dict_images): table image item_image[i] of `images`,
+  // kBatchNoImage: none, the chain files.  item_image == nullptr: no images
+  const uint32_t* images;      // [n_images][quick_table_words(Q)], 16-byte aligned
+  const uint32_t* item_image;  // [n_items]
 };
+// The table images of a group behind a dictionary per item, in one launch: image j is what lz77_quick_init + lz77_quick_prepend
+// leave for the dict_bytes[j] bytes at text + text_at[j] (the dictionary's copy in front of the first item that names it; every
+// filed position hashes dictionary bytes only).  images: [n_images][quick_table_words(Q)], ZEROED by the caller -- the slots
+// nothing is filed under and the books stay 0; text_at / dict_bytes: [n_images], device.
+void lz77_quick_dict_images(const QuickJob& Q, const uint8_t* text, uint32_t n_images, const uint32_t* text_at_dev, const uint32_t* dict_bytes_dev,
+                            uint32_t* images);
 // one wavefront per table; a wavefront takes items from `counter` until none is left
 void lz77_quick_batch_parse(const QuickBatchJob& J);
 // the same launch for items behind a shared custom dictionary (J.dict_bytes >= 2, J.image): a chain starts on the image instead of
 // a zeroed table and cuts its matches at the dictionary's end; BatchRecord::bad_commands flags the items the reference fails on
 void lz77_quick_batch_parse_dict(const QuickBatchJob& J);
 // the same launch for items behind a dictionary of their own (J.item_dict_bytes: 2 .. 65536 bytes each): a chain zeroes its table
-// and files its item's dictionary itself (br_quick_batch_file), since there is no image to share, then runs as the one above
+// and files its item's dictionary itself (br_quick_batch_file) or copies the group's image of it (J.images), then runs as the one above
 void lz77_quick_batch_parse_dicts(const QuickBatchJob& J);
 
 // ---- items of several blocks (BROTLI_MI355X_BATCH_ROUTE_QUICK_LONG_ITEMS): an item of two to kBatchLongBlocks input blocks is still

@@ -96,7 +96,8 @@ BR_DEV void br_quick_batch_job(const QuickBatchJob& J, uint32_t table, uint32_t 
 // kDict: the item's text starts with J.dict_bytes bytes of custom dictionary (BrotliMi355xCompressBatchWithDictionaryEx) and its
 // chain starts on J.image.
 // kDicts (with kDict): the dictionary is the item's own, J.item_dict_bytes[index] bytes (BrotliMi355xCompressBatchWithDictionaries);
-// the chain zeroes its table and files that dictionary itself, J.dict_bytes and J.image are not looked at.
+// J.dict_bytes and J.image are not looked at.  The chain copies the image the group built of that dictionary
+// (J.images, J.item_image[index]) over its table, or, where the dictionary has none, zeroes its table and files the dictionary itself.
 template <bool kDict = false, bool kDicts = false>
 BR_DEV void br_quick_batch_item(const QuickBatchJob& J, const QuickTables& T, const EntropyTables& logs, uint32_t* histo, SegExit* exit_slot,
                                 uint32_t index, uint32_t table) {
@@ -108,8 +109,15 @@ BR_DEV void br_quick_batch_item(const QuickBatchJob& J, const QuickTables& T, co
   br_quick_batch_job(J, table, D, it.bytes, Q, P);
   if constexpr (kDicts) {
     static_assert(kDict || !kDicts, "kDicts goes with kDict");
-    br_quick_batch_zero(Q.table, quick_table_words(Q));
-    br_quick_batch_file(Q, J.text + it.text_off - D, D);
+    // One table takes both starts in turn, behind dictionaries of any two lengths: the prime writes ALL words of the table, the
+    // zero fill all of them too, so neither start sees a word of the item in front (or of another image).
+    const uint32_t image = J.item_image != nullptr ? BR_UNIFORM(J.item_image[index]) : kBatchNoImage;  // (wave-uniform)
+    if (image != kBatchNoImage) {
+      br_quick_batch_prime(Q.table, J.images + (size_t)image * quick_table_words(Q), quick_table_words(Q));
+    } else {
+      br_quick_batch_zero(Q.table, quick_table_words(Q));
+      br_quick_batch_file(Q, J.text + it.text_off - D, D);
+    }
   } else if constexpr (kDict) {
     br_quick_batch_prime(Q.table, J.image, quick_table_words(Q));
   } else {

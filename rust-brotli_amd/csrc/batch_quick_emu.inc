@@ -4,7 +4,8 @@
 // a table serves several items, as on the device.  The gather is lz77_batch_gather (batch_greedy_emu.inc).
 // lz77_quick_batch_parse_dict: the same loop over the item code behind a shared custom dictionary (the image is the emulation's
 // lz77_quick_init + lz77_quick_prepend, i.e. br_quick_prepend).
-// lz77_quick_batch_parse_dicts: the same loop behind a dictionary per item; a chain files its dictionary with br_quick_prepend.
+// lz77_quick_batch_parse_dicts: the same loop behind a dictionary per item; a chain files its dictionary with br_quick_prepend, or
+// copies the image lz77_quick_dict_images (br_quick_prepend per image) has made of it.
 // lz77_quick_batch_parse_long: the same loop over the item code of the items of several blocks; its gather is lz77_batch_gather_long.
 #include <stdexcept>
 
@@ -57,6 +58,16 @@ void lz77_quick_batch_parse_dicts(const QuickBatchJob& J) {
   SegExit exit_slot;
   for (uint32_t place = 0; place < J.n_items; ++place) br_quick_batch_item<true, true>(J, T, logs, histo, &exit_slot, J.order[place], place % J.tables);
   *J.counter = J.n_items;
+}
+
+// the table images of a group: br_quick_prepend per image, on the zeroed table the caller hands over
+void lz77_quick_dict_images(const QuickJob& Q, const uint8_t* text, uint32_t n_images, const uint32_t* text_at, const uint32_t* dict_bytes,
+                            uint32_t* images) {
+  for (uint32_t j = 0; j < n_images; ++j) {
+    QuickJob image = Q;
+    image.table = images + (size_t)j * quick_table_words(Q);
+    br_quick_prepend(image, text + text_at[j], dict_bytes[j]);
+  }
 }
 
 void lz77_quick_batch_parse_long(const QuickBatchJob& J, BatchLongRecord* records) {

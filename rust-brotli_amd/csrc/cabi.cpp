@@ -1014,6 +1014,8 @@ BROTLI_BOOL BrotliMi355xCompressDevice(int quality, int lgwin, BrotliEncoderMode
 
 // what BrotliMi355xLastBatchInfo reports: the last batch call of this thread
 static thread_local uint64_t g_batch_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+// ... and BrotliMi355xLastBatchImageInfo: what the routes of that call counted into BatchImageTally()
+static thread_local uint64_t g_batch_image_info[4] = {0, 0, 0, 0};
 
 using BatchStreams = std::vector<std::vector<uint8_t>>;
 using BatchFlags = std::vector<uint8_t>;
@@ -1061,6 +1063,8 @@ static int32_t RunBatchCall(const char* entry, int quality, int lgwin, BrotliEnc
                             size_t* output_sizes, int32_t* item_results, bool on_device, const std::string& refused, const BatchBody& body) {
   uint64_t info[8] = {count, 0, 0, 0, 0, 0, 0, 0};
   memcpy(g_batch_info, info, sizeof(info));
+  memset(g_batch_image_info, 0, sizeof(g_batch_image_info));
+  BatchImageTally() = BatchImageCounts{0, 0, 0};
   const auto fails = [&](const char* what) {
     SetError(entry, what);
     for (size_t i = 0; i < count; ++i) output_sizes[i] = 0;
@@ -1094,6 +1098,9 @@ static int32_t RunBatchCall(const char* entry, int quality, int lgwin, BrotliEnc
     return 0;
   }
   memcpy(g_batch_info, info, sizeof(info));
+  g_batch_image_info[0] = BatchImageTally().images;
+  g_batch_image_info[1] = BatchImageTally().replayed;
+  g_batch_image_info[2] = BatchImageTally().filed;
   int32_t all = 1;
   for (size_t i = 0; i < count; ++i) {
     if (item_results) item_results[i] = results[i];
@@ -1570,6 +1577,8 @@ int32_t BrotliMi355xCompressBatchWithDictionariesDevice(int quality, int lgwin, 
 }
 
 void BrotliMi355xLastBatchInfo(uint64_t info[8]) { memcpy(info, g_batch_info, sizeof(g_batch_info)); }
+
+void BrotliMi355xLastBatchImageInfo(uint64_t info[4]) { memcpy(info, g_batch_image_info, sizeof(g_batch_image_info)); }
 
 int32_t BrotliEncoderCompressMulti(size_t num_params, const BrotliEncoderParameter* param_keys, const uint32_t* param_values,
                                    size_t input_size, const uint8_t* input_buffer, size_t* encoded_size, uint8_t* encoded,

@@ -2928,6 +2928,60 @@ void lz77_batch_dict_image(const Lz77Params& P, const uint16_t* keys, uint32_t d
   HIP_CHECK(hipGetLastError());
 }
 
+// The images of a group behind a dictionary per item (batch_greedy.h: lz77_batch_dict_images).  k_batch_dict_file with an image
+// dimension: wavefront b files image first + b on table b of the group, whose counters it empties first ...
+__global__ __launch_bounds__(64) void k_batch_dict_images_file(BatchParseJob J, uint32_t first, uint32_t n_images, const BatchImagePlan* __restrict__ plan) {
+  const uint32_t b = blockIdx.x;
+  if (b >= J.tables || first + b >= n_images) return;
+  const uint32_t text_at = BR_UNIFORM(plan[first + b].text_at), D = BR_UNIFORM(plan[first + b].bytes);
+  const size_t keys_per_table = (size_t)1 << J.P.bucket_bits;
+  LiveRing lr;
+  lr.num = J.num + (size_t)b * keys_per_table;
+  lr.buckets = J.buckets + (((size_t)b * keys_per_table) << J.P.block_bits);
+  lr.keys = J.keys + text_at;
+  lr.bits = J.P.block_bits;
+  br_live_reset(lr, J.P.bucket_bits);
+  if (D > J.P.htl - 1) br_live_store(lr, 0, 1, D - (J.P.htl - 1), 1, 0);  // StoreLookaheadThenStore, mod.rs:224-229
+}
+// ... and k_batch_dict_list with one: blockIdx.y is the table, one thread per key copies the counter to the image and lists the
+// entries it covers, behind those of the image's other keys (n_entries[image], one count per image)
+__global__ __launch_bounds__(256) void k_batch_dict_images_list(BatchParseJob J, uint32_t first, uint32_t n_images, const BatchImagePlan* __restrict__ plan,
+                                                                 uint16_t* __restrict__ image_num, uint32_t* __restrict__ entries,
+                                                                 uint32_t* __restrict__ n_entries) {
+  const uint32_t b = blockIdx.y, image = first + b;
+  const uint32_t key = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= J.tables || image >= n_images || key >= (1u << J.P.bucket_bits)) return;
+  const size_t keys_per_table = (size_t)1 << J.P.bucket_bits;
+  const uint32_t bits = J.P.block_bits, depth = 1u << bits;
+  const uint32_t* __restrict__ buckets = J.buckets + (((size_t)b * keys_per_table) << bits);
+  const uint32_t n = J.num[(size_t)b * keys_per_table + key];
+  image_num[(size_t)image * keys_per_table + key] = (uint16_t)n;
+  const uint32_t visible = n < depth ? n : depth;
+  if (visible == 0) return;
+  const uint32_t cap = plan[image].bytes;
+  uint32_t* __restrict__ out = entries + 2 * (size_t)plan[image].entries_at;
+  const uint32_t base = atomicAdd(n_entries + image, visible);
+  for (uint32_t i = 0; i < visible; ++i) {
+    if (base + i >= cap) return;  // (never: at most one entry per filed position)
+    const uint32_t slot = (key << bits) | ((n - 1u - i) & (depth - 1u));
+    out[2 * (size_t)(base + i)] = slot;
+    out[2 * (size_t)(base + i) + 1] = buckets[slot];
+  }
+}
+
+void lz77_batch_dict_images(const BatchParseJob& J, uint32_t n_images, const BatchImagePlan* plan_dev, uint16_t* num, uint32_t* entries,
+                            uint32_t* n_entries) {
+  if (n_images == 0) return;
+  if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
+  for (uint32_t first = 0; first < n_images; first += J.tables) {
+    const uint32_t round = n_images - first < J.tables ? n_images - first : J.tables;
+    hipLaunchKernelGGL(k_batch_dict_images_file, dim3(round), dim3(64), 0, BR_STREAM, J, first, n_images, plan_dev);
+    hipLaunchKernelGGL(k_batch_dict_images_list, dim3(((1u << J.P.bucket_bits) + 255u) / 256u, round), dim3(256), 0, BR_STREAM, J, first, n_images,
+                       plan_dev, num, entries, n_entries);
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
 void lz77_batch_parse(const BatchParseJob& J) {
   if (J.n_items == 0) return;
   if (J.tables == 0) throw std::runtime_error("brotli_mi355x: a batch group without a table");
@@ -2941,7 +2995,8 @@ void lz77_batch_parse(const BatchParseJob& J) {
 }
 
 // k_parse_batch's launch shape for items behind a dictionary of their own (J.item_dict_bytes): a sibling of k_parse_batch, so that
-// its instances stay what they were.  Every chain files its dictionary itself: there is no image to share.
+// its instances stay what they were.  A chain replays the image the group has built of its item's dictionary (J.images,
+// J.item_image: lz77_batch_dict_images above) or, where that dictionary has none, files it itself.
 template <bool kRows>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_parse_batch_dicts(BatchParseJob J, ChainTables T) {
   __shared__ ChainScratchT<false, kRows> scratch;

@@ -95,13 +95,41 @@ __global__ __launch_bounds__(64) void k_quick_batch_dict(QuickBatchJob J, QuickT
 }
 
 // The same launch for items behind a custom dictionary each (J.item_dict_bytes): a chain zeroes its table and files its item's
-// dictionary itself, 64 positions per step (br_quick_batch_file).  (A kernel of its own for the reason above.)
+// dictionary itself, 64 positions per step (br_quick_batch_file), or copies the image the group has built of that dictionary
+// (J.images, J.item_image: k_quick_dict_images below).  (A kernel of its own for the reason above.)
 __global__ __launch_bounds__(64) void k_quick_batch_dicts(QuickBatchJob J, QuickTables T, EntropyTables logs) {
   __shared__ uint32_t histo[256];
   __shared__ SegExit exit_slot;
   const uint32_t table = blockIdx.x;
   if (table >= J.tables) return;
   for (uint32_t index; br_batch_next_index(J.counter, J.order, J.n_items, index);) br_quick_batch_item<true, true>(J, T, logs, histo, &exit_slot, index, table);
+}
+
+// The table images of a group behind a dictionary per item (batch_quick.h: lz77_quick_dict_images), all in one launch: blockIdx.y
+// is the image, the threads of its row file the dictionary's positions with the atomic maximum of k_quick_prepend into a table
+// the caller has zeroed.  Every 8-byte load ends inside the dictionary's copy: count = D - 7 positions.
+__global__ __launch_bounds__(256) void k_quick_dict_images(QuickJob J, const uint8_t* __restrict__ text, uint32_t n_images,
+                                                            const uint32_t* __restrict__ text_at, const uint32_t* __restrict__ dict_bytes,
+                                                            uint32_t* __restrict__ images) {
+  const uint32_t image = blockIdx.y;
+  if (image >= n_images) return;
+  const uint32_t D = dict_bytes[image];
+  if (D <= kQuickHtl - 1u) return;
+  const uint32_t count = D - (kQuickHtl - 1u);
+  const uint8_t* __restrict__ dict = text + text_at[image];
+  uint32_t* __restrict__ table = images + (size_t)image * quick_table_words(J);
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
+    const uint64_t v = (br_load64(dict + i) << (64u - 8u * J.hash_len)) * kQuickHashMul64;
+    const uint32_t key = (uint32_t)(v >> (64u - J.bucket_bits));
+    atomicMax(table + key + ((i >> 3) & (J.sweep - 1u)), i);
+  }
+}
+void lz77_quick_dict_images(const QuickJob& Q, const uint8_t* text, uint32_t n_images, const uint32_t* text_at_dev, const uint32_t* dict_bytes_dev,
+                            uint32_t* images) {
+  if (n_images == 0) return;
+  // (a dictionary has at most 65536 bytes: 64 blocks of 256 threads file four positions each at the most)
+  hipLaunchKernelGGL(k_quick_dict_images, dim3(64, n_images), dim3(256), 0, BR_STREAM, Q, text, n_images, text_at_dev, dict_bytes_dev, images);
+  HIP_CHECK(hipGetLastError());
 }
 
 // Items of two to kBatchLongBlocks input blocks (batch_quick.h): the launch shape of k_quick_batch, the item code walks from

@@ -96,6 +96,13 @@ chain's filing, wave-wide and on lane 0, as a difference of whole calls.  Beside
 entry brotli_mi355x_debug_zopfli_prepend: modes 0 (lane 0), 1 (wave-wide, one wavefront) and 2 (the image build) at 16 and 64 KiB, less the same
 entry at 2 bytes (allocation, the fill and the copies, which every mode pays).
 
+With --dicts --kinds the call measured is BrotliMi355xCompressBatchWithDictionaries with K distinct dictionaries, the items dealt to them round
+robin -- a few dictionaries that each serve many items, where this build makes an image per dictionary that enough items of a group name: this
+build against --parent-lib through the same call (there every chain files its dictionary), against the shared call on the same items behind ONE
+dictionary, and against this build with BROTLI_MI355X_BATCH_DICT_IMAGE_MIN_ITEMS=0, --rounds alternating rounds, one process per measurement.
+--kinds all runs KINDS_SHAPES and the sweep of that variable (KINDS_SWEEP), --kinds sweep the sweep alone, --kinds 4,16 with --only and
+--qualities those shapes.
+
 With --device (and --parent-lib) the call measured is BrotliMi355xCompressBatchDevice on torch tensors -- one uint8 tensor of items in,
 one of streams out -- beside the parent's BrotliMi355xCompressBatchEx on the same items from host memory and beside the "honest
 alternative" a caller with device-resident payloads has without the call: the items down (one D2H), the parent's host call, the
@@ -296,12 +303,14 @@ def measure_batch(lib_path, items, quality, runs, warmup, dictionary=None, route
     return times, sum(out_sizes), list(info), failed
 
 
-def measure_dicts(lib_path, items, dictionaries, quality, runs, warmup, shared=False, routes=None, one_index=False):
+def measure_dicts(lib_path, items, dictionaries, quality, runs, warmup, shared=False, routes=None, one_index=False, kinds=0):
     """BrotliMi355xCompressBatchWithDictionaries with dictionaries[i] for item i; shared: BrotliMi355xCompressBatchWithDictionary with
     dictionaries[0].  At qualities 2 to 4 both with the route that takes such items side by side (512, and 4 through the Ex entry).
     routes: the bits of the per-item call (default: 512 at qualities 2 to 4, else 0; 1024 and 4096 are the caller's to give); with
     shared they go to BrotliMi355xCompressBatchWithDictionaryEx as they are (4096: quality 9).  one_index: the per-item call with dictionaries[0]
-    alone and item_dicts = {0, 0, ...}."""
+    alone and item_dicts = {0, 0, ...}.  kinds = K: the per-item call with dictionaries[:K] and item_dicts = {0, 1, .. K - 1, 0, 1, ..}, the items
+    dealt to K distinct dictionaries round robin; the returned info then carries BrotliMi355xLastBatchImageInfo behind its 8 values
+    (zeros on a library without it)."""
     L = bind(lib_path)
     quick = 2 <= quality <= 4
     L.BrotliMi355xCompressBatchWithDictionaryEx.restype = ctypes.c_int32
@@ -320,6 +329,8 @@ def measure_dicts(lib_path, items, dictionaries, quality, runs, warmup, shared=F
     dict_sizes = (ctypes.c_size_t * n)(*[len(d) for d in dictionaries])
     info = (ctypes.c_uint64 * 8)()
     named = (ctypes.c_size_t * n)() if one_index else None
+    if kinds:
+        named = (ctypes.c_size_t * n)(*[i % kinds for i in range(n)])
     times, failed = [], []
     for it in range(warmup + runs):
         for i in range(n):
@@ -332,7 +343,7 @@ def measure_dicts(lib_path, items, dictionaries, quality, runs, warmup, shared=F
             ok = L.BrotliMi355xCompressBatchWithDictionary(quality, LGWIN, 0, ctypes.c_size_t(len(dictionaries[0])), ctypes.c_char_p(dictionaries[0]), ctypes.c_size_t(n),
                                                            inputs, in_sizes, outputs, out_sizes, results)
         else:
-            ok = L.BrotliMi355xCompressBatchWithDictionaries(quality, LGWIN, 0, ctypes.c_uint32((512 if quick else 0) if routes is None else routes), ctypes.c_size_t(1 if one_index else n), dicts, dict_sizes,
+            ok = L.BrotliMi355xCompressBatchWithDictionaries(quality, LGWIN, 0, ctypes.c_uint32((512 if quick else 0) if routes is None else routes), ctypes.c_size_t(1 if one_index else kinds if kinds else n), dicts, dict_sizes,
                                                              ctypes.c_size_t(n), named, inputs, in_sizes, outputs, out_sizes, results)
         dt = time.perf_counter() - t
         if ok != 1:
@@ -342,6 +353,11 @@ def measure_dicts(lib_path, items, dictionaries, quality, runs, warmup, shared=F
         if it >= warmup:
             times.append(dt)
     L.BrotliMi355xLastBatchInfo(info)
+    if kinds:
+        images = (ctypes.c_uint64 * 4)()
+        if hasattr(L, "BrotliMi355xLastBatchImageInfo"):  # (the parent's library has none)
+            L.BrotliMi355xLastBatchImageInfo(images)
+        return times, sum(out_sizes), list(info) + list(images), failed
     return times, sum(out_sizes), list(info), failed
 
 
@@ -485,6 +501,100 @@ def child_dicts(args):
             print(json.dumps(row), flush=True)
     with open(args.child_out, "w") as f:
         json.dump(out, f)
+
+
+# (--dicts --kinds) the per-item call with K distinct dictionaries, the items dealt to them round robin: (class, qualities, the K)
+KINDS_ALL = (4, 16, 64, 256, 4096)
+KINDS_SHAPES = [("4096x4KiB+16KiB", (5, 8, 2, 4, 9), KINDS_ALL), ("4096x512B+16KiB", (2,), (16,)), ("1024x16KiB+64KiB", (5,), (16,)), ("64x4KiB+16KiB", (5,), (4,))]
+KINDS_SWEEP = (2, 4, 8, 16)  # BROTLI_MI355X_BATCH_DICT_IMAGE_MIN_ITEMS, on 4096x4KiB+16KiB with K = 4096 / that value
+
+
+def kinds_routes(quality):
+    return 512 if 2 <= quality <= 4 else 4096 if quality == 9 else 0
+
+
+def child_kinds(args):
+    """one measurement: `--classes` one class, `--qualities` one quality, --kinds K (0: the shared call behind the first dictionary)"""
+    name, quality = args.classes, int(args.qualities)
+    items, dictionaries = dicts_of(name)
+    if int(args.kinds):
+        times, csize, info, failed = measure_dicts(args.lib, items, dictionaries, quality, args.runs, args.warmup, routes=kinds_routes(quality), kinds=int(args.kinds))
+    else:
+        shared_routes = 4 if 2 <= quality <= 4 else 4096 if quality == 9 else None
+        times, csize, info, failed = measure_dicts(args.lib, items, [dictionaries[0]] * len(items), quality, args.runs, args.warmup, shared=True, routes=shared_routes)
+    row = {"class": name, "quality": quality, "kinds": int(args.kinds), "compressed_bytes": csize, "batch_info": info[:8], "image_info": info[8:], "reference_fails_on_items": len(failed)}
+    row.update(stats(times))
+    with open(args.child_out, "w") as f:
+        json.dump(row, f)
+
+
+def main_kinds(args, doc, save):
+    """--dicts --kinds: a mixed group.  Every shape this build against the parent's library through the same call, --rounds alternating rounds, one
+    process per measurement; the shared call on the same items behind ONE dictionary (the floor); this build with images off
+    (BROTLI_MI355X_BATCH_DICT_IMAGE_MIN_ITEMS=0); and the sweep of that variable behind the default.  --kinds all: KINDS_SHAPES; --kinds sweep: the
+    sweep alone; --kinds K[,K..] with --only and --qualities: those."""
+    doc["what"] = ("BrotliMi355xCompressBatchWithDictionaries with K distinct dictionaries, the items dealt to them round robin: this build (an image per dictionary that "
+                   "BROTLI_MI355X_BATCH_DICT_IMAGE_MIN_ITEMS items of a group name) vs the parent commit's library through the same call (every chain files its dictionary), vs "
+                   "the shared call on the same items behind one dictionary; lgwin 22")
+    doc["method"] = "host clock around the synchronous call, %d warm-up runs and %d runs per process, one process per measurement, %d alternating rounds; min .. max over all runs of a setting" % (
+        args.warmup, args.runs, args.rounds)
+    doc["rows"], doc["sweep"] = [], []
+    tmp = args.out + ".child.json"
+    parent = os.path.abspath(args.parent_lib) if args.parent_lib else None
+
+    def one(lib, name, quality, kinds, env=None):
+        cmd = ["timeout", "-k", "10", "240", sys.executable, os.path.abspath(__file__), "--child", "kinds", "--classes", name, "--qualities", str(quality), "--kinds", str(kinds),
+               "--lib", lib, "--runs", str(args.runs), "--warmup", str(args.warmup), "--child-out", tmp]
+        e = dict(os.environ)
+        e.pop("BROTLI_MI355X_BATCH_DICT_IMAGE_MIN_ITEMS", None)
+        e.update(env or {})
+        r = subprocess.run(cmd, env=e)
+        if r.returncode != 0:  # (a fault or a time limit: nothing more is started)
+            raise SystemExit("the measurement %r ended with %d" % (cmd, r.returncode))
+        with open(tmp) as f:
+            return json.load(f)
+
+    def settle(rows):
+        return {"min_ms": min(r["min_ms"] for r in rows), "max_ms": max(r["max_ms"] for r in rows), "median_ms": round(statistics.median(r["median_ms"] for r in rows), 3),
+                "image_info": rows[-1]["image_info"], "batch_info": rows[-1]["batch_info"], "compressed_bytes": rows[-1]["compressed_bytes"]}
+
+    if args.kinds == "sweep":
+        shapes = []
+    elif args.kinds == "all":
+        shapes = KINDS_SHAPES
+    else:
+        shapes = [(c, tuple(int(q) for q in args.qualities.split(",")), tuple(int(k) for k in args.kinds.split(","))) for c in args.only.split(",")]
+    for name, qualities, all_kinds in shapes:
+        for quality in qualities:
+            floor = settle([one(args.lib, name, quality, 0) for _ in range(args.rounds)])
+            for kinds in all_kinds:
+                this, base, off = [], [], []
+                for _ in range(args.rounds):
+                    this.append(one(args.lib, name, quality, kinds))
+                    if parent:
+                        base.append(one(parent, name, quality, kinds))
+                    off.append(one(args.lib, name, quality, kinds, {"BROTLI_MI355X_BATCH_DICT_IMAGE_MIN_ITEMS": "0"}))
+                row = {"class": name, "quality": quality, "kinds": kinds, "this": settle(this), "images_off": settle(off), "shared_one_dictionary": floor}
+                if base:
+                    row["parent"] = settle(base)
+                    assert row["parent"]["compressed_bytes"] == row["this"]["compressed_bytes"], row
+                doc["rows"].append(row)
+                print(json.dumps(row), flush=True)
+                save()
+    if args.kinds in ("sweep", "all"):
+        name = "4096x4KiB+16KiB"
+        for quality in (5, 2, 9):
+            for m in KINDS_SWEEP:
+                on, off = [], []
+                for _ in range(args.rounds):
+                    on.append(one(args.lib, name, quality, 4096 // m, {"BROTLI_MI355X_BATCH_DICT_IMAGE_MIN_ITEMS": str(m)}))
+                    off.append(one(args.lib, name, quality, 4096 // m, {"BROTLI_MI355X_BATCH_DICT_IMAGE_MIN_ITEMS": "0"}))
+                row = {"class": name, "quality": quality, "min_items": m, "kinds": 4096 // m, "images_on": settle(on), "images_off": settle(off)}
+                doc["sweep"].append(row)
+                print(json.dumps(row), flush=True)
+                save()
+    if os.path.exists(tmp):
+        os.remove(tmp)
 
 
 # (--device) class, quality, route bits
@@ -753,6 +863,8 @@ def child(args):
         return child_device(args)
     if args.child == "device-dicts":
         return child_device_dicts(args)
+    if args.child == "kinds":
+        return child_kinds(args)
     if args.child == "prepend":
         return child_prepend(args)
     if args.dicts:
@@ -1233,6 +1345,8 @@ def main():
     ap.add_argument("--shared-zopfli", action="store_true", help="BrotliMi355xCompressBatchWithDictionaryEx with BROTLI_MI355X_BATCH_ROUTE_ZOPFLI_SHARED_DICTIONARY_ITEMS: the tree image against self-filing, the parent's one-index call and one by one (qualities 10,11)")
     ap.add_argument("--device", action="store_true", help="BrotliMi355xCompressBatchDevice on torch tensors beside the parent's host call on the same items (DEVICE_SHAPES)")
     ap.add_argument("--device-dicts", action="store_true", help="BrotliMi355xCompressBatchWithDictionariesDevice on torch tensors beside download + the parent's host dictionary call + upload (DEVICE_DICTS_SHAPES)")
+    ap.add_argument("--kinds", default="", help="with --dicts: K distinct dictionaries, the items dealt to them round robin -- a comma list (with --only and --qualities), "
+                    "'all' (KINDS_SHAPES and the sweep of BROTLI_MI355X_BATCH_DICT_IMAGE_MIN_ITEMS) or 'sweep'; --rounds alternating rounds against --parent-lib")
     ap.add_argument("--routes", type=int, default=0, help="(child) route bits of the device shape")
     ap.add_argument("--shared", action="store_true", help="(child, device-dicts) one dictionary named by every item")
     ap.add_argument("--same-call", action="store_true", help="the parent's library through the same call as this build, alternating --rounds times (needs --parent-lib)")
@@ -1255,6 +1369,8 @@ def main():
         with open(args.out, "w") as f:
             json.dump(doc, f, indent=1)
 
+    if args.dicts and args.kinds:
+        return main_kinds(args, doc, save)
     if args.device:
         return main_device(args, doc, save)
     if args.device_dicts:
